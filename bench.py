@@ -19,6 +19,12 @@ paired view (both directions from one logits block, entropy regulariser riding a
 and the backward through both.  N = 1 emulates the all-gather with resident unit-norm keys (this rank's 8192 rows of the
 paired view sit at their offset among them); N > 1 gathers them (dp.all_gather_rows) every step.
 
+`--dump-outputs DIR`: after the K timed steps rank 0 writes what the last of them handed its caller (the step's output, info
+dict, loss and gradients; c4: the loss, info and the updated model) as DIR/<name>.npy, float32 or float64, at most 64 MB --
+a fixed, seeded sample of the rows of batch-major outputs where the whole batch does not fit.  The inputs are seeded and the
+settle steps are counted, not clocked, under this flag, so two builds run with the same arguments can be compared output
+for output.
+
 `python bench.py --gpus N` without a launcher starts the N ranks itself (child processes, started before this process
 touches the GPU) and relays rank 0's JSON line; under torch.distributed.run (WORLD_SIZE set) it is one of the ranks.
 """
@@ -71,6 +77,40 @@ def settle(one_step, extra, by_clock):
     return n
 NCE_KEYS = 65536                 # --contrastive: gathered keys of configs[2] (8 ranks x 8192 rows)
 NCE_TEMPERATURE = 0.07
+DUMP_BYTES = 60 << 20            # --dump-outputs: array bytes written at most (the .npy headers stay well under 64 MB with them)
+DUMP_SEED = 0                    # --dump-outputs: seed of the row sample of batch-major outputs
+
+
+def dump_outputs(path, batch, per_row, whole):
+    """--dump-outputs: what the timed path handed its caller in its last step, one <path>/<name>.npy per array (float64 stays
+    float64, every other dtype is written as float32).  `whole` arrays are written in full; the batch-major `per_row` arrays
+    keep the same rows, all of them when they fit in DUMP_BYTES, else a fixed sample (a seeded CPU draw, sorted, written as
+    rows.npy) of as many rows as fit.  Returns the summary the result line carries."""
+    import numpy as np
+    width = lambda t_: 8 if t_.dtype == torch.float64 else 4
+    host = lambda t_: t_.detach().to(torch.float64 if t_.dtype == torch.float64 else torch.float32).cpu().numpy()
+    fixed = sum(t_.numel() * width(t_) for t_ in whole.values())
+    row_bytes = sum(t_[0].numel() * width(t_) for t_ in per_row.values()) + 8          # (+ its entry in rows.npy)
+    assert fixed + min(batch, 1) * row_bytes <= DUMP_BYTES, "the outputs of one row do not fit in DUMP_BYTES"
+    n = min(batch, (DUMP_BYTES - fixed) // row_bytes)
+    arrays = {k: host(v) for k, v in whole.items()}
+    if n < batch:
+        rows = torch.randperm(batch, generator=torch.Generator().manual_seed(DUMP_SEED))[:n].sort().values
+        arrays["rows"] = rows.to(torch.float64).numpy()
+        arrays.update({k: host(v.detach()[rows.to(v.device)]) for k, v in per_row.items()})
+    else:
+        arrays.update({k: host(v) for k, v in per_row.items()})
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {"dir": path, "arrays": len(arrays), "bytes": sum(a.nbytes for a in arrays.values()), "rows": int(n), "batch": batch}
+
+
+def split_info(info, batch):
+    """An info dict's tensors as (batch-major, the rest) for dump_outputs, named info.<key>."""
+    ts = {"info." + k: v for k, v in info.items() if torch.is_tensor(v)}
+    major = {k: v for k, v in ts.items() if v.dim() > 0 and v.shape[0] == batch}
+    return major, {k: v for k, v in ts.items() if k not in major}
 
 
 def make_inputs(cfg, device, seed_offset=0, f32_params=False):
@@ -115,7 +155,7 @@ def step(pool, query, x, dy, params, dp_on, shard=None, overlap=None):
             # ONE RCCL all-reduce (sum of pre-scaled values) of the 4E^2+5E gradients, over the run the backward wrote them into
             from aecf_amd.dp import all_reduce_grads
             all_reduce_grads(params, rehearse=True)
-    return out, ent_loss
+    return out, ent_loss, info
 
 
 class StageTimer:
@@ -367,13 +407,18 @@ def bench_c4(args):
             dist.barrier()
         torch.cuda.synchronize()
 
-    settled = settle(one_step, args.warmup, world == 1)
+    # (--dump-outputs: the settle steps are counted, not clocked -- the parameters the dumped step starts from are then a
+    #  function of the arguments)
+    settled = settle(one_step, args.warmup, world == 1 and not args.dump_outputs)
     barrier()
     t0 = time.perf_counter()
     enqueue = 0.0
-    for _ in range(args.steps):
+    for i in range(args.steps):
         h0 = time.perf_counter()
-        one_step()
+        if i + 1 < args.steps:
+            one_step()
+        else:
+            last = one_step()            # (only the last step's results outlive it: what --dump-outputs writes)
         enqueue += time.perf_counter() - h0
     barrier()
     elapsed = time.perf_counter() - t0
@@ -381,6 +426,17 @@ def bench_c4(args):
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt[0].item())
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # the caller of the step receives the loss (+ the info dict, eager) and the model it updated
+        loss, info = (last, {}) if graphed is not None else last
+        per_row, whole = split_info(info, B)
+        whole["loss"] = loss
+        for name, prm in model.named_parameters():
+            whole["param." + name] = prm
+            if prm.grad is not None:
+                whole["grad." + name] = prm.grad
+        dumped = dump_outputs(args.dump_outputs, B, per_row, whole)
     if rank == 0:
         sec = elapsed / args.steps
         line = {
@@ -403,6 +459,7 @@ def bench_c4(args):
                      "host-bound: the step is ~50 small launches (4 nn.Linear layers each way, routing, pool, AdamW) and one "
                      "device->host read of the routing counts; host_enqueue_ms ~ ms_per_step means the GPU waits for the host"),
             "cpu_baseline": None,
+            "dump_outputs": dumped,
         }
         emit(line)
     if world > 1:
@@ -462,7 +519,13 @@ def main():
     ap.add_argument("--rows", type=int, default=0,
                     help="pool configurations: rows per GPU instead of the config's batch (strong-scaling shards on one GPU)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=30.0, help="budget of the CPU-oracle leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller (output, info, loss, gradients) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed sample of the rows of batch-major outputs); "
+                         "the settle steps are then counted only, so that the same arguments give the same inputs every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     globals()["SETTLE_SECONDS"] = args.settle_seconds
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -566,7 +629,7 @@ def main():
         if dp_on:
             from aecf_amd.dp import all_reduce_grads
             all_reduce_grads(params, rehearse=True)
-        return out, loss
+        return out, loss, info
 
     def one_step():
         if nce is not None:
@@ -597,26 +660,42 @@ def main():
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local" if dp_on else "global"):
-            eager_step()
+            captured = eager_step()          # (the step's outputs: tensors every replay writes again)
 
         def one_step():
             graph.replay()
+            return captured
 
     # A fresh process needs ~25 steps (~15 ms) before its step time settles (tools/step_trend.py: 0.66, 0.65 ... 0.59 ms; 300 ms
     # of unrelated device work beforehand does not shorten it): SETTLE_STEPS untimed steps come first and are reported in the line
     # ("settle_steps", "effective_warmup"), then the W warm-up steps, then exactly K timed steps.
     # the clock-based part of the settle only for host-bound call sizes: the device-bound configurations gain nothing from it
     # and their first timed step after the barrier gets slower behind a long settle (1.0-1.5 ms against 0.66-0.8 ms)
-    settled = settle(one_step, args.warmup, world == 1 and B * M * E <= (1 << 25))
+    # (--dump-outputs: counted only -- every step draws its curriculum mask, so the dumped step's mask is then a function of
+    #  the arguments)
+    settled = settle(one_step, args.warmup, world == 1 and B * M * E <= (1 << 25) and not args.dump_outputs)
     barrier()
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # per-step times (same stream)
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        one_step()
+        if i + 1 < args.steps:
+            one_step()
+        else:
+            last = one_step()            # (only the last step's results outlive it: what --dump-outputs writes)
         marks[i + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # the step's caller receives the fused rows, the info dict, the loss and the gradients the backward left
+        out, loss, info = last
+        per_row, whole = split_info(info, B)
+        per_row.update({"out": out, "grad.x": x.grad})
+        whole.update({"loss": loss, "grad.query": query.grad})
+        whole.update({"grad." + name: prm.grad for name, prm in pool.named_parameters() if prm.grad is not None})
+        dumped = dump_outputs(args.dump_outputs, B, per_row, whole)
+    last = None
     per_step_raw = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     if os.environ.get("AECF_BENCH_DUMP_STEPS"):
         print("step_ms", [round(v, 4) for v in per_step_raw], file=sys.stderr)
@@ -850,6 +929,7 @@ def main():
             "strong_scaling": strong,
             "collective_library": None if world == 1 else (
                 f"RCCL {'.'.join(str(v) for v in torch.cuda.nccl.version())}" if backend == "nccl" else backend),
+            "dump_outputs": dumped,
         }
         emit(line)
     if world > 1 or args.force_dp:
