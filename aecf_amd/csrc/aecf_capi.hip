@@ -4,9 +4,7 @@
 // as one HIP graph) gets them as nodes of ITS graph.  No device allocation, no synchronisation, no exceptions, no state.
 #include <math.h>
 #include <stdio.h>
-#include <string>
 #include <stdint.h>
-#include <stdlib.h>
 
 
 #include "../../include/aecf_hip.h"
@@ -17,10 +15,9 @@ using namespace aecf;
 namespace {
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-int env_dx_reserve();          // tokens of the one debug knob AECF_DEBUG, read once per process (defined below;
-bool env_no_gate_fusion();     //  env_no_ws / env_no_wide_tn / env_no_slab are declared in aecf_kernels.h: other files ask too)
-bool env_fused_fwd();
 inline int esize(int dtype) { return dtype == AECF_BF16 ? 2 : 4; }
+// the weight-stationary kernels read W_v and W_o (and their transposes) from fragment-major copies: bf16, these E only
+inline bool ws_frag_shape(int dtype, int E) { return dtype == AECF_BF16 && (E == 256 || E == 512 || E == 768 || E == 1024); }
 
 struct FwdWs {
     size_t qs, a_f32, a_hi, a_lo, obuf, wv_frag, wo_frag, total;
@@ -227,7 +224,7 @@ size_t aecf_pool_precise_workspace_bytes(const aecf_pool_desc* d, int backward) 
 
 int aecf_pool_wants_saved_v(const aecf_pool_desc* d) {
     if (aecf_pool_check(d) != AECF_OK) return 0;
-    if (d->dtype == AECF_BF16 && !env_no_ws()) {
+    if (d->dtype == AECF_BF16) {
         BwdGArgs g;
         g.B = d->batch; g.M = d->modalities; g.E = d->embed_dim; g.H = d->num_heads; g.hd = d->embed_dim / d->num_heads;
         if (dsu_ws_chunks(g) > 0) return 0;        // the score gradient comes from x (dsu_ws_kernel): nothing to save
@@ -238,7 +235,7 @@ int aecf_pool_wants_saved_v(const aecf_pool_desc* d) {
 // AECF_HILO_GRADS is built for the bf16 shapes whose value projection runs on the weight-stationary kernel in its
 // per-sample form (the kernels that can write the low part of o and of do)
 static bool hilo_supported(const aecf_pool_desc* d) {
-    if (aecf_pool_check(d) != AECF_OK || d->dtype != AECF_BF16 || env_no_ws()) return false;
+    if (aecf_pool_check(d) != AECF_OK || d->dtype != AECF_BF16) return false;
     GemmNtArgs v;
     v.a = nullptr; v.w = nullptr; v.bias = nullptr; v.c = nullptr; v.probs = nullptr; v.R = d->batch; v.N = d->embed_dim;
     v.K = d->embed_dim; v.lda = (int64_t)d->modalities * d->embed_dim; v.M = d->modalities; v.H = d->num_heads;
@@ -309,8 +306,8 @@ int pool_forward_on(const aecf_pool_desc* d, const aecf_pool_fwd_args* a, hipStr
 
     void** ev = a->stage_events;
     mark(ev, 0, s);
-    // fragment-major copies of W_v and W_o for the weight-stationary kernels (bf16, E in {256, 512, 768, 1024})
-    const bool frag = d->dtype == AECF_BF16 && (E == 256 || E == 512 || E == 768 || E == 1024) && !env_no_ws();
+    // fragment-major copies of W_v and W_o for the weight-stationary kernels
+    const bool frag = ws_frag_shape(d->dtype, E);
     FragJobs fj;
     if (frag) {
         fj.n = 2;
@@ -354,26 +351,9 @@ int pool_forward_on(const aecf_pool_desc* d, const aecf_pool_fwd_args* a, hipStr
         if (!a->saved_o || !a->saved_o_lo) return AECF_ERR_NULL_POINTER;
         v.c_lo = a->saved_o_lo;
     }
-    if (env_fused_fwd() && !precise && !hilo && row_fwd_supported(d->dtype, E, M, H)) {
-        // ONE kernel from x to y: scores, softmax, statistics, value projection, pooling, out-projection (aecf_row_fwd.hip)
-        GemmNtArgs yo;
-        yo.a = o; yo.w = a->w_out; yo.bias = a->b_out; yo.c = a->y; yo.probs = nullptr; yo.R = d->batch; yo.N = E; yo.K = E;
-        yo.lda = E; yo.M = 1; yo.H = H; yo.hd = hd; yo.pooled = 0; yo.out_f32 = 0; yo.v_out = nullptr;
-        v.c = a->saved_o;                                  // kept only when the caller wants it (backward)
-        mark(ev, 2, s);
-        launch_row_fwd(g, v, yo, s);
-        if (d->mask_mode == 1 && a->ent_loss_partial) {
-            if (a->info_entropy) launch_entropy_partials(d->dtype, d->batch, a->target_entropy_value, a->info_entropy, a->ent_loss_partial, s);
-            else if (a->entropy) launch_entropy_partials(AECF_F32, d->batch, a->target_entropy_value, a->entropy, a->ent_loss_partial, s);
-            if (a->ent_loss) launch_entropy_from_partials(d->dtype, d->batch, a->ent_loss_partial, a->ent_loss, s);
-        }
-        mark(ev, 3, s);
-        mark(ev, 4, s);
-        return launch_status();
-    }
     // bf16, shapes of the weight-stationary kernel, M <= 3: the scores are formed inside the value projection (one pass
     // over x for both) and the per-sample statistics follow from the saved weights; otherwise the gate kernel runs first
-    bool fuse_gate = d->dtype == AECF_BF16 && M <= 3 && !env_no_gate_fusion() && !env_no_ws();   // (A/B timing switches)
+    bool fuse_gate = d->dtype == AECF_BF16 && M <= 3;
     if (fuse_gate) {
         v.g_ahi = a_hi; v.g_alo = a_lo; v.g_kpm = a->key_padding_mask;
         if (!gemm_ws_supported(v)) { fuse_gate = false; v.g_ahi = v.g_alo = nullptr; v.g_kpm = nullptr; }
@@ -409,7 +389,7 @@ int pool_forward_on(const aecf_pool_desc* d, const aecf_pool_fwd_args* a, hipStr
     // the entropy regulariser's final sum rides in the out-projection launch where the weight-stationary kernel runs it
     // (its first block adds the statistics kernel's partial sums: no launch of its own), else it is one small launch
     const bool want_loss = ent_partial && a->ent_loss;
-    const bool loss_rides = want_loss && d->dtype == AECF_BF16 && !env_no_ws() && gemm_ws_supported(y);
+    const bool loss_rides = want_loss && d->dtype == AECF_BF16 && gemm_ws_supported(y);
     if (loss_rides) {
         y.ent_partial = ent_partial; y.ent_nblk = (int)((d->batch + 255) / 256); y.ent_inv_n = 1.0f / (float)d->batch;
         y.ent_loss = a->ent_loss;
@@ -443,7 +423,7 @@ int pool_backward_precise(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, 
     char* pb = ws + L.prep16;
     const float scale = sqrtf(1.0f / (float)hd);
     const char* w_v = (const char*)a->w_in + (size_t)2 * E * E * 2;
-    const bool frag = (E == 256 || E == 512 || E == 768 || E == 1024) && !env_no_ws();
+    const bool frag = ws_frag_shape(AECF_BF16, E);
     FragJobs fj;
     if (frag) {
         fj.n = 2;
@@ -497,7 +477,7 @@ int pool_backward_on(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, hipSt
 
     void** ev = a->stage_events;
     mark(ev, 0, s);
-    const bool frag = d->dtype == AECF_BF16 && (E == 256 || E == 512 || E == 768 || E == 1024) && !env_no_ws();
+    const bool frag = ws_frag_shape(d->dtype, E);
     FragJobs fj;
     if (!a->saved_prep) {                             // (with saved_prep the forward already produced all of this)
         if (frag) {                                   // fragment-major W_v^T (dx) and W_o^T (dout)
@@ -545,7 +525,7 @@ int pool_backward_on(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, hipSt
     // nothing saved by the forward; otherwise from the saved V (memory-bound dot), else by recomputing W_v^T do per head
     int dsu_chunks = 0;
     if (hilo) g2.do_lo = ws + L.do_lo;                // (read by dsu_ws_kernel only: other shapes keep the default key-side accuracy)
-    if (d->dtype == AECF_BF16 && !env_no_ws() && dsu_ws_chunks(g2) > 0 && dsu_ws_chunks(g2) <= L.u_splits_cap)
+    if (d->dtype == AECF_BF16 && dsu_ws_chunks(g2) > 0 && dsu_ws_chunks(g2) <= L.u_splits_cap)
         dsu_chunks = launch_dsu_ws(g2, (float*)(ws + L.u_slab), s);
     else if (!(a->saved_v && launch_dscore_v(d->dtype, g2, a->saved_v, s)))
         launch_bwd_g(d->dtype, g2, false, s);
@@ -567,9 +547,10 @@ int pool_backward_on(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, hipSt
     // input gradient: here, or -- when the caller wants to be told the moment the parameter gradients are final -- last
     const bool dx_last = a->param_grads_event != nullptr;
     // ... and then with a few CUs left free: the dx kernel otherwise takes every CU's whole register file for its one
-    // block, and the collective's workgroups could only start as those retire (AECF_DX_RESERVE_CUS, default 16 of 256;
-    // UNMEASURED here -- no multi-GPU box -- it costs the dx kernel ~6 % and is meant to buy the all-reduce its overlap)
-    if (dx_last) g2.cu_budget = 256 - env_dx_reserve();
+    // block, and the collective's workgroups could only start as those retire (16 of 256; UNMEASURED -- no multi-GPU
+    // box -- it costs the dx kernel ~6 % and is meant to buy the all-reduce its overlap)
+    constexpr int DX_RESERVE_CUS = 16;
+    if (dx_last) g2.cu_budget = 256 - DX_RESERVE_CUS;
     // where the weight-stationary dx kernel runs between the score gradient and the finalize launch, it also adds up the
     // u slabs (a side job of its weight prologue): the finalize launch then depends on no reduction launch
     bool u_reduced = false;
@@ -636,55 +617,7 @@ int pool_backward_on(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, hipSt
     return launch_status();
 }
 
-// ONE debug knob, read once per process (tests and A/B timing; never on the call path): AECF_DEBUG = comma-separated tokens
-//   no_ws               tiled round-1 kernels instead of the weight-stationary ones
-//   no_gate_fusion      scores / softmax as their own kernel instead of inside the value projection
-//   no_wide_tn          128-row tiles instead of the 1024-thread 256-row form of the pooled batch reduction
-//   no_slab             the two-barrier gated value projection instead of its column-slab form (d = 512)
-//   fused_fwd           the one-kernel forward north_star names (aecf_row_fwd.hip; measured slower: profiles/r03_c2_fusedfwd_*)
-//   dx_reserve=N        CUs the dx kernel leaves free when it runs beside a collective (default 16, 0..128)
-struct EnvSwitches {
-    bool no_ws = false, no_gate_fusion = false, no_wide_tn = false, no_slab = false, fused_fwd = false;
-    int dx_reserve = 16;
-};
-const EnvSwitches& env_switches() {
-    static const EnvSwitches e = [] {
-        EnvSwitches v;
-        const char* env = getenv("AECF_DEBUG");
-        if (!env) return v;
-        std::string all(env);
-        size_t pos = 0;
-        while (pos <= all.size()) {
-            size_t end = all.find(',', pos);
-            if (end == std::string::npos) end = all.size();
-            const std::string tok = all.substr(pos, end - pos);
-            pos = end + 1;
-            if (tok == "no_ws") v.no_ws = true;
-            else if (tok == "no_gate_fusion") v.no_gate_fusion = true;
-            else if (tok == "no_wide_tn") v.no_wide_tn = true;
-            else if (tok == "no_slab") v.no_slab = true;
-            else if (tok == "fused_fwd") v.fused_fwd = true;
-            else if (tok.rfind("dx_reserve=", 0) == 0) {
-                const int n = atoi(tok.c_str() + 11);
-                if (n >= 0 && n <= 128) v.dx_reserve = n;
-            } else if (!tok.empty()) {
-                fprintf(stderr, "libaecf_hip: unknown AECF_DEBUG token '%s' (ignored)\n", tok.c_str());
-            }
-        }
-        return v;
-    }();
-    return e;
-}
-
-bool env_no_gate_fusion() { return env_switches().no_gate_fusion; }
-bool env_fused_fwd() { return env_switches().fused_fwd; }
-int env_dx_reserve() { return env_switches().dx_reserve; }
 }  // namespace
-namespace aecf {
-bool env_no_ws() { return env_switches().no_ws; }
-bool env_no_wide_tn() { return env_switches().no_wide_tn; }
-bool env_no_slab() { return env_switches().no_slab; }
-}  // namespace aecf
 
 extern "C" {
 

@@ -169,7 +169,7 @@ static void launch_one(const GemmNtArgs& a, hipStream_t s) {
 
 void launch_gemm_nt(int dtype, const GemmNtArgs& a_in, hipStream_t s) {
     GemmNtArgs a = a_in;
-    if (dtype == 0 && !env_no_ws() && gemm_ws_supported(a)) { launch_gemm_ws(a, s); return; }   // aecf_gemm_ws.hip
+    if (dtype == 0 && gemm_ws_supported(a)) { launch_gemm_ws(a, s); return; }   // aecf_gemm_ws.hip
     if (a.pooled & 1) { launch_vproj(dtype, a, s); return; }     // per-modality accumulators (aecf_vproj.hip)
     // fewer than 64 block tiles of 128 x 128: 32 x 32 tiles instead (16 x the blocks, each 1/16 of the K loop's MFMAs)
     const bool small = ((a.R + 127) / 128) * (int64_t)((a.N + 127) / 128) < 64;

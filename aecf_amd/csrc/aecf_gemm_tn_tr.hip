@@ -759,7 +759,7 @@ static int max_slots_256(int E, int hd) {
 void launch_gemm_tn_tr(const GemmTnArgs& a, hipStream_t s) {
     if (!a.pooled) { launch_one<1, false, 1>(a, s); return; }
     // 256-row tiles (1024 threads) when they tile E exactly with at most 4 head slots and M <= 3 (128-VGPR budget)
-    if (!env_no_wide_tn() && a.Ej <= 0 && a.E % 256 == 0 && max_slots_256(a.E, a.hd) <= 4 &&
+    if (a.Ej <= 0 && a.E % 256 == 0 && max_slots_256(a.E, a.hd) <= 4 &&
         (a.M <= 3 || (a.M == 4 && max_slots_256(a.E, a.hd) <= 2))) {
         const bool two = max_slots_256(a.E, a.hd) <= 2;
         switch (a.M) {

@@ -35,7 +35,7 @@ constexpr int WS_PF = 3, VPROJ_PF = 3, DX_PF = 3;
 // LDS tiles of gemm_ws_kernel: two.  (A third tile for the plain form -- copy two steps ahead -- measured neutral at C2, 38 us
 // either way, profiles/r04_c2_plain_ablation.txt: copy, stores and MFMA + operand reads each take ~19 us on their own and
 // already overlap.  The phase-ablation and in-kernel timeline builds these numbers came from are kept out of the product
-// source: tools/micro/variants/.)
+// source: tools/micro/variants/ in git history at 14eca16292f5.)
 constexpr int ws_plain_bufs(int, int) { return 2; }
 
 // copy NROWS rows (K bf16 each) to an LDS tile; row r's physical chunk p holds logical chunk p ^ key(r),
@@ -1008,7 +1008,7 @@ __global__ __launch_bounds__(512, 2) void dsu_ws_kernel(BwdGArgs p, float* __res
 
 // (A second form of this kernel around WAVE-PRIVATE x slabs -- dsu_slab_kernel, round 4: one barrier per step instead of three,
 // every wave runs the softmax backward for all heads -- measured level with it, 118 against 113-120 us,
-// profiles/r04_c2_dsu_slab_ablation.txt; it left the product library in round 5: tools/micro/variants/aecf_gemm_ws_ablations.hip.)
+// profiles/r04_c2_dsu_slab_ablation.txt; it left the product library in round 5: tools/micro/variants/aecf_gemm_ws_ablations.hip in git history at 14eca16292f5.)
 
 template <int KT, int KJ, int HK, int M_>
 int launch_dsu_t(const BwdGArgs& a, float* u_slab, hipStream_t s) {
@@ -1331,9 +1331,6 @@ void launch_ws(const GemmNtArgs& a, hipStream_t s) {
     const int64_t nchunk = (a.R + rpb - 1) / rpb;
     dim3 grid(xcd_grid((unsigned)nchunk, (unsigned)groups)), block(512);
     if (GATE) smem += (size_t)8 * M_ * 256 * sizeof(float);
-    if (MODE == WS_VPROJ && GATE && KT == 16 && M_ <= 3) {         // hot shape (K = 512): the column-slab form
-        if (!env_no_slab()) { launch_vproj_slab<(M_ <= 3 ? M_ : 3)>(a, s); return; }
-    }
     auto kern = gemm_ws_kernel<KT, MODE, M_, GATE, CT>;
     if (smem > 64 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
@@ -1346,7 +1343,9 @@ void launch_kt(const GemmNtArgs& a, hipStream_t s) {
         case 4: launch_ws<4, MODE, M_, GATE>(a, s); break;
         case 8: launch_ws<8, MODE, M_, GATE>(a, s); break;
         case 12: launch_ws<12, MODE, M_, GATE>(a, s); break;
-        case 16: launch_ws<16, MODE, M_, GATE>(a, s); break;
+        case 16:                                                   // hot shape (K = 512): the gated form is the column slab
+            if constexpr (GATE) launch_vproj_slab<M_>(a, s); else launch_ws<16, MODE, M_, GATE>(a, s);
+            break;
         case 24: launch_ws<24, MODE, M_, GATE>(a, s); break;
         default: launch_ws<32, MODE, M_, GATE>(a, s); break;
     }
@@ -1390,7 +1389,7 @@ void launch_gemm_ws(const GemmNtArgs& a, hipStream_t s) {
             case 1: if (a.g_ahi) launch_kt<WS_VPROJ, 1, true>(a, s); else launch_kt<WS_VPROJ, 1, false>(a, s); break;
             case 2: if (a.g_ahi) launch_kt<WS_VPROJ, 2, true>(a, s); else launch_kt<WS_VPROJ, 2, false>(a, s); break;
             case 3: if (a.g_ahi) launch_kt<WS_VPROJ, 3, true>(a, s); else launch_kt<WS_VPROJ, 3, false>(a, s); break;
-            default: if (a.g_ahi) launch_kt<WS_VPROJ, 4, true>(a, s); else launch_kt<WS_VPROJ, 4, false>(a, s); break;
+            default: launch_kt<WS_VPROJ, 4, false>(a, s); break;      // (the scores ride along for M <= 3 only: pool_forward_on)
         }
     } else {
         launch_kt<WS_PLAIN, 1, false>(a, s);
@@ -1445,7 +1444,6 @@ int launch_dsu_ws(const BwdGArgs& a, float* u_slab, hipStream_t s) {
 
 // dx through the weight-stationary engine (bf16); false = shape not taken (caller uses launch_bwd_g(dx = true))
 bool launch_dx_ws(const BwdGArgs& a, hipStream_t s) {
-    if (env_no_ws()) return false;
     if (a.M < 1 || a.M > 4) return false;
     if (a.hd % 32 != 0 || a.E != a.H * a.hd || 16 * a.H * a.M > 1024) return false;
     switch (a.E) {

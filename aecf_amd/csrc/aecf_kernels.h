@@ -98,11 +98,6 @@ void launch_vproj(int dtype, const GemmNtArgs& a, hipStream_t s);   // pooled ==
 bool gemm_ws_supported(const GemmNtArgs& a);                          // weight-stationary streaming form (bf16)
 void launch_gemm_ws(const GemmNtArgs& a, hipStream_t s);
 
-// fused forward (aecf_row_fwd.hip): prep products in g (a_hi / a_lo), value projection operands in v (w, bias, c = saved o,
-// v_out = saved V or null), out-projection operands in y (w, bias, c = y)
-bool row_fwd_supported(int dtype, int E, int M, int H);
-void launch_row_fwd(const GateArgs& g, const GemmNtArgs& v, const GemmNtArgs& y, hipStream_t s);
-
 // ---------------- backward ----------------
 // g_h[b] = W_v,h^T do_h[b] kernels (aecf_bwd_g.hip):
 //   dx == false: da[b,h,m] = g_h[b] . x[b,m] -> ds = softmax-backward(da + dwbar/H) -> dsbuf [B,H,M]
@@ -187,11 +182,6 @@ struct ReduceSegs {
     int dst_bf16[N];      // 1: dst is bf16 (one rounding of the float32 sum)
     float scale[N] = {1.f, 1.f, 1.f, 1.f, 1.f};   // the sum is multiplied by this before it is stored (aecf_pool_bwd_args.grad_scale)
 };
-// tokens of the debug knob AECF_DEBUG (aecf_capi.hip)
-bool env_no_ws();
-bool env_no_wide_tn();
-bool env_no_slab();
-
 void launch_reduce_segments(const ReduceSegs& r, hipStream_t s);
 
 // dW_k[j][k] = qs[j] u[h(j)][k];  dqp[j] = scale * sum_k W_k[j][k] u[h(j)][k]

@@ -20,11 +20,7 @@
  *    gradients are float32, or bf16 when aecf_pool_bwd_args.grad_dtype asks for it (bf16 parameters: the float32 batch
  *    sums are rounded once, in the reduction kernel).
  *  - thread-safe and stateless: any thread may call with any stream of the current device; the library keeps nothing between
- *    calls.  The only process-wide input is ONE debug knob, read once: the environment variable AECF_DEBUG = comma-separated
- *    tokens -- no_ws, no_gate_fusion, no_wide_tn, no_slab (route a shape through the kernels that serve the shapes the fast
- *    ones do not take: what the parity tests of those kernels use), fused_fwd (the one-kernel forward instead of the
- *    weight-stationary kernel pair), dx_reserve=N.  Unknown tokens are reported on stderr and ignored; unset = production
- *    behaviour.
+ *    calls and reads no environment: the kernels a call launches follow from its description and arguments alone.
  */
 #ifndef AECF_HIP_H
 #define AECF_HIP_H

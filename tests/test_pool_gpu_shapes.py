@@ -1,10 +1,12 @@
 """GPU parity sweep over the shapes the kernels template on: modality count 1..8, head count 1..16, embed sizes that
 exercise ragged tiles (64, 192, 768, 1024), head sizes 16..256, batch sizes that are not multiples of any tile,
-with and without key_padding_mask / gradient on the attention weights.  Checked against the CPU oracle."""
+with and without key_padding_mask / gradient on the attention weights.  Checked against the CPU oracle.  The kernels
+that serve shapes outside the weight-stationary engine are reached by shape here (E = 64 / 128 / 192, M >= 5), not by
+a switch: the library has none."""
 import pytest
 import torch
 
-from tests.helpers import BF16_F32GRAD_BOUNDS, assert_bf16_bounds, f32grad_bounds, record_errors, rel_err
+from tests.helpers import assert_bf16_bounds, f32grad_bounds, record_errors, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -119,36 +121,6 @@ def test_bf16_head_dim_16_runs_on_the_general_kernels():
     # carries a few more roundings than the collapsed shared-query kernels: 1e-2 of the largest magnitude
     for k, e in errs.items():
         assert e < 1e-2, (k, e)
-
-
-_FALLBACK_SCRIPT = r"""
-import json, sys, torch
-sys.path.insert(0, {root!r})
-from tests.test_pool_gpu_shapes import _case
-errs, agree = _case(300, 3, 512, 8, torch.bfloat16, True, seed=11)
-print("RESULT " + json.dumps(dict(errs=errs, agree=agree)))
-"""
-
-
-@pytest.mark.parametrize("knobs", [{"AECF_DEBUG": "no_ws"}, {"AECF_DEBUG": "no_gate_fusion"}, {"AECF_DEBUG": "no_wide_tn"},
-                                   {"AECF_DEBUG": "fused_fwd"}, {"AECF_DEBUG": "no_slab"}],
-                         ids=["tiled", "separate_gate", "narrow_batch_reduction", "one_kernel_forward", "two_barrier_gate"])
-def test_bf16_fallback_kernels_at_the_hot_path_shape(knobs):
-    """The kernels that serve shapes the weight-stationary engine does not take (tiled NT GEMM, per-modality value
-    projection, stand-alone gate, tiled dx) stay correct at d=512 / 8 heads / M=3: the library's A/B switches route the
-    hot-path shape through them in a child process (the switches are read once per process)."""
-    import json
-    import os
-    import subprocess
-    import sys
-    from tests.helpers import ROOT
-    env = dict(os.environ, **knobs)
-    out = subprocess.run([sys.executable, "-c", _FALLBACK_SCRIPT.format(root=ROOT)], env=env, capture_output=True,
-                         text=True, timeout=280)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res = json.loads([l for l in out.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
-    assert_bf16_bounds(res["errs"], BF16_F32GRAD_BOUNDS, sorted(knobs))
-    assert res["agree"] > 0.99
 
 
 _BACK_TO_BACK_SCRIPT = r"""

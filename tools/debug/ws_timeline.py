@@ -1,5 +1,5 @@
 """Phase timeline of vproj_slab_kernel at C2 from in-kernel shader-clock stamps (experiment build -DAECF_WS_TIMELINE:
-a scratch checkout with tools/micro/variants/aecf_gemm_ws_ablations.hip (the round-4 source that carries the stamps) in place of aecf_gemm_ws.hip, built with -DAECF_WS_TIMELINE; AECF_LIB_PATH=build/var/wtl/libaecf_hip.so).
+a scratch checkout with tools/micro/variants/aecf_gemm_ws_ablations.hip from git history at 14eca16292f5 (the round-4 source that carries the stamps) in place of aecf_gemm_ws.hip, built with -DAECF_WS_TIMELINE; AECF_LIB_PATH=build/var/wtl/libaecf_hip.so).
 Stamps per 16-sample step: 0 top, 1 after (lgkmcnt + barrier), 2 after the softmax, 3 after the MFMA loop, 4 after vmcnt(0),
 5 after the next step's partial scores, 6 after the stores."""
 import ctypes

@@ -30,10 +30,9 @@ python3 bench.py --steps 50 --warmup 10 > $out/${tag}_c2_bench.json 2> /dev/null
 python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --force-dp > $out/${tag}_c2_forcedp_bench.json 2> /dev/null
 python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --force-dp --graph > $out/${tag}_c2_forcedp_graph_bench.json 2> /dev/null
 python3 bench.py --config c3 --steps 50 --warmup 10 --no-cpu-baseline --graph > $out/${tag}_c3shard_graph_bench.json 2> /dev/null
-AECF_DEBUG=no_ws python3 bench.py --config c5 --steps 30 --warmup 10 --no-cpu-baseline > $out/${tag}_c5shard_no_ws_bench.json 2> /dev/null
 python3 bench.py --config c3 --steps 50 --warmup 10 --no-cpu-baseline > $out/${tag}_c3shard_bench.json 2> /dev/null
 python3 bench.py --config c5 --steps 50 --warmup 10 --no-cpu-baseline > $out/${tag}_c5shard_bench.json 2> /dev/null
-for f in c2 c2_forcedp c2_forcedp_graph c3shard c3shard_graph c5shard c5shard_no_ws; do python3 -c "
+for f in c2 c2_forcedp c2_forcedp_graph c3shard c3shard_graph c5shard; do python3 -c "
 import json; l=json.load(open('$out/${tag}_${f}_bench.json')); r=l['roofline']
 print('$f', round(l['ms_per_step'],4), round(l['value']/1e6,1), 'M/s', r['kernel'], round(r['frac'],3), r['traffic'], round(l['path_hbm_frac'],3), round(l['path_mfma_frac'],3))"; done
 # configs[3] (the example model): captured step and eager step at the reference's batch and at a device-bound batch
