@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import weakref
 from typing import Any, Dict, Optional, Tuple, Union
 
 import torch
@@ -37,6 +38,11 @@ def _stream() -> int:
     if _raw_stream is not None:
         return _raw_stream(torch.cuda.current_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+def _capturing() -> bool:
+    """The current stream is being captured into a graph (never before the device runtime is up)."""
+    return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
 
 
 def _draw_uniforms(shape, device, uniforms: Optional[torch.Tensor] = None,
@@ -209,6 +215,47 @@ class PoolOptions:
 
 
 _DEFAULT_OPTIONS = PoolOptions()           # direct users of _PoolFunction.apply (never modified)
+
+
+def _stamp(tensors) -> Tuple:
+    """What a cache entry remembers of the tensors it was derived from: per tensor, the object that owns its storage (a weak
+    reference: the tensor itself, or the base of a view), its address and its version counter.  Identity is what makes the
+    address safe to compare: a tensor freed and replaced by another at the same address (a query recomputed per call, which the
+    caching allocator hands the previous one's block) cannot match, since the weak reference of the old one is dead by then."""
+    return tuple(None if t is None else (weakref.ref(t if t._base is None else t._base), t.data_ptr(), t._version)
+                 for t in tensors)
+
+
+def _stamp_matches(stamp, tensors) -> bool:
+    """True if ``stamp`` (``_stamp`` of earlier tensors) describes these very tensors, unchanged since."""
+    if stamp is None or len(stamp) != len(tensors):
+        return False
+    for s, t in zip(stamp, tensors):
+        if t is None or s is None:
+            if s is not t:
+                return False
+        elif s[0]() is not (t if t._base is None else t._base) or s[1] != t.data_ptr() or s[2] != t._version:
+            return False
+    return True
+
+
+# pools that hold inference caches, and the optimizer hook that drops them: torch's fused optimizers (torch.optim.AdamW(fused=True)
+# and its kin) write the parameters without moving their version counters, so after ANY optimizer step nothing cached is trusted
+_caching_pools: "weakref.WeakSet" = weakref.WeakSet()
+_step_hook = None
+
+
+def _drop_inference_caches(optimizer, args, kwargs) -> None:
+    for pool in list(_caching_pools):
+        pool.invalidate_cast_cache()
+
+
+def _watch_optimizer_steps(pool) -> None:
+    global _step_hook
+    if _step_hook is None:
+        from torch.optim.optimizer import register_optimizer_step_post_hook
+        _step_hook = register_optimizer_step_post_hook(_drop_inference_caches)
+    _caching_pools.add(pool)
 
 
 def _require_device(t: torch.Tensor, what: str) -> None:
@@ -837,6 +884,19 @@ class MultimodalAttentionPool(nn.Module):
         self._prep_cache: Optional[Tuple[Tuple, torch.Tensor]] = None       # (key, preparation buffer) while the parameters stand still
         self.options = PoolOptions()
 
+    def __getstate__(self):
+        # copies and pickles start without the caches (their keys hold weak references to THIS module's tensors)
+        state = super().__getstate__()
+        state["_cast_cache"] = {}
+        state["_prep_cache"] = None
+        return state
+
+    def train(self, mode: bool = True):
+        # a switch between training and inference is where loops that step their parameters behind the version counters
+        # (optimizers writing through raw pointers or .data) hand over to evaluation: nothing cached survives it
+        self.invalidate_cast_cache()
+        return super().train(mode)
+
     def _options(self) -> PoolOptions:
         o = self.__dict__.get("options")
         if o is None:                              # (a module unpickled from a build that had no per-module options)
@@ -844,20 +904,27 @@ class MultimodalAttentionPool(nn.Module):
         return o
 
     def invalidate_cast_cache(self) -> None:
-        """Forget the activation-dtype copies of the parameters (see _activation_dtype_params).  Call it after changing a
-        parameter through ``p.data`` (``p.data.copy_(...)``, EMA / weight swapping, optimizers that step on ``.data``) while
-        the module is in eval mode under ``torch.no_grad()``: such writes do not move the parameter's version counter."""
+        """Forget what inference derived from the parameters and the query: the activation-dtype copies of master weights
+        (see _activation_dtype_params) and the kernels' preparation (AECF_PREP_READY).  Both are reused while each keyed tensor
+        is the same object with the same storage and version counter.  In-place ops, ``nn.Parameter`` replacement,
+        ``load_state_dict``, ``p.data = t``, ``train()`` / ``eval()``, the ``step()`` of any ``torch.optim.Optimizer`` (torch's
+        fused ones and ``aecf_amd.optim.FusedAdamW`` included: an optimizer step drops the caches of every pool) and
+        ``xray.GraphedTrainStep`` replays are seen without help.  Call it after any other write the version counter does not
+        see, while the module runs inference: ``p.data.copy_(...)`` (EMA / weight swapping), optimizers that are not
+        ``torch.optim.Optimizer`` subclasses, replays of your own captured graphs that update the parameters."""
         self._cast_cache.clear()
         self._prep_cache = None
+        _caching_pools.discard(self)
 
     def _activation_dtype_params(self, dt: torch.dtype, query: Optional[torch.Tensor] = None):
         """Master weights kept in another dtype than the activations (float32 parameters, bf16 data): the kernels want
-        them in the activation dtype.  Inference (eval mode, or no gradient recording) reuses the copies while the
-        parameters' version counters and storage stand still; whenever the module trains they are remade on every forward:
-        an optimizer that steps through ``p.data`` (apex / DeepSpeed style, EMA, clipping on ``.data``) leaves the version
-        counter alone, and stale weights would go unnoticed.  ``invalidate_cast_cache()`` covers ``.data`` writes in eval."""
+        them in the activation dtype.  Inference (eval mode, or no gradient recording) reuses the copies while each parameter
+        is the same object with the same storage and version counter (``_stamp``); whenever the module trains they are remade
+        on every forward: an optimizer that steps through ``p.data`` (apex / DeepSpeed style, EMA, clipping on ``.data``) leaves
+        the version counter alone, and stale weights would go unnoticed.  ``invalidate_cast_cache()`` covers such writes in
+        inference.  Never reused while the stream is captured: a replay must cast the parameters as they are then."""
         a = self.attention
-        reuse = not (self.training and torch.is_grad_enabled())
+        reuse = not (self.training and torch.is_grad_enabled()) and not _capturing()
         named = (("w_in", a.in_proj_weight), ("b_in", a.in_proj_bias), ("w_out", a.out_proj.weight), ("b_out", a.out_proj.bias))
         if not reuse:
             # training: ONE cast launch for the four of them + the query (aecf_cast_f32_to_bf16; one torch launch each was ~22 us
@@ -883,11 +950,11 @@ class MultimodalAttentionPool(nn.Module):
             if p is None:
                 out.append(None)
                 continue
-            key = (p._version, p.data_ptr(), p.device, dt)
             hit = self._cast_cache.get(name)
-            if hit is None or hit[0] != key:
-                hit = (key, p.detach().to(dt).contiguous())
+            if hit is None or hit[1].dtype != dt or not _stamp_matches(hit[0], (p,)):
+                hit = (_stamp((p,)), p.detach().to(dt).contiguous())
                 self._cast_cache[name] = hit
+                _watch_optimizer_steps(self)
             out.append(hit[1])
         return tuple(out) + (None,)
 
@@ -1023,14 +1090,22 @@ class MultimodalAttentionPool(nn.Module):
         tgt_value = math.log(float(src_len)) * cm.entropy_target if mask_mode == 1 else None        # ref :273
         side: Dict[str, Any] = {}
         prep_key = None
-        if not (self.training and torch.is_grad_enabled()):
+        if not (self.training and torch.is_grad_enabled()) and not _capturing():
             # inference / no gradient recording: what the kernels derive from the parameters alone (scaled query projection, folded
             # key matrix, transposes, MFMA-fragment copies: one launch, ~10 us) is kept until a parameter or the query moves --
-            # same policy as the cast cache (version counters + storage; invalidate_cast_cache() after writes through .data)
-            prep_key = tuple((t._version, t.data_ptr()) for t in (a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, q_base)
-                             if t is not None) + (x.dtype, x.device, embed_dim, self.num_heads)
+            # same policy as the cast cache (same objects, storage and version counters: _stamp; invalidate_cast_cache() after
+            # writes the version counter does not see).  Not while the stream is captured: a captured forward prepares for itself
+            # (its replays must see the parameters as they are then), and its buffer is not written until a replay runs
+            keyed = (a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, q_base)
+            fixed = (x.dtype, x.device, embed_dim, self.num_heads)
             hit = self.__dict__.get("_prep_cache")
-            side["prep_cache"] = (hit[1], True) if (hit is not None and hit[0] == prep_key) else (None, False)
+            if hit is not None and hit[0][1] == fixed and _stamp_matches(hit[0][0], keyed):
+                prep_key = hit[0]
+                side["prep_cache"] = (hit[1], True)
+            else:
+                prep_key = (_stamp(keyed), fixed)
+                side["prep_cache"] = (None, False)
+                _watch_optimizer_steps(self)
         y, attn_w, masked_w, entropy, mask_rate, tgt_entropy = _PoolFunction.apply(
             x, q_base, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, kpm, mask_u,
             self.num_heads, mask_mode, 1 if cm is None else int(cm.min_active),

@@ -3,7 +3,9 @@
 ``step`` -- a float32 scalar on the device --, ``exp_avg``, ``exp_avg_sq``), so state dicts move between the two; the step
 counters advance on the device, which makes ``step()`` capturable into a HIP graph without further flags.  One limit under
 capture: the hyper-parameters (``lr`` included) are kernel ARGUMENTS, so a captured step replays with the values it was captured
-with -- a learning-rate schedule needs a re-capture (or the eager step) when the rate changes."""
+with -- a learning-rate schedule needs a re-capture (or the eager step) when the rate changes.  A replay moves no version counter: ``xray.GraphedTrainStep`` tells the
+pools of its model after each one; after replays of a graph of your own, call ``invalidate_cast_cache()`` on the pools before
+inference."""
 from __future__ import annotations
 
 import ctypes
@@ -80,4 +82,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 (ctypes.c_int64 * len(ps))(*[p.numel() for p in ps]), self._ticket(dev, gi, len(ps)).data_ptr(),
                 float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), _stream()),
                 "aecf_adamw_step")
+            # the launch wrote the parameters through raw pointers: move their version counters the way an in-place torch op
+            # would, so that whatever keys on them (the pool's inference caches, autograd's saved-tensor checks) sees the update
+            torch.autograd.graph.increment_version(ps)
         return loss

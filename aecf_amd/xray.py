@@ -399,6 +399,8 @@ class GraphedTrainStep:
                 os.close(fd)
                 tunable.set_filename(name)
         self.model, self.optimizer, self.criterion = model, optimizer, criterion
+        # a replay updates the parameters without moving a version counter: the pools forget what inference derived from them
+        self._pools = tuple(m for m in model.modules() if isinstance(m, MultimodalAttentionPool))
         self.image = torch.zeros(batch, image_dim, device=device, dtype=dtype)
         self.text = torch.zeros(batch, text_dim, device=device, dtype=dtype)
         self.labels = torch.zeros(batch, num_classes, device=device, dtype=dtype)
@@ -455,6 +457,8 @@ class GraphedTrainStep:
         self.text.copy_(texts, non_blocking=True)
         self.labels.copy_(labels, non_blocking=True)
         self.graph.replay()
+        for pool in self._pools:
+            pool.invalidate_cast_cache()
         return self.loss
 
 

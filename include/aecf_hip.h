@@ -161,8 +161,9 @@ typedef struct aecf_pool_fwd_args {
 /* AECF_PREP_READY (forward only, with saved_prep; ABI v9): saved_prep already holds the preparation an earlier forward made from
  * these very parameters and this query (same embed_dim / num_heads / dtype; the batch may differ): the preparation launch is
  * skipped.  For loops in which the parameters provably stand still -- inference, gradient accumulation over micro-batches.  The
- * caller is responsible for "unchanged" (the Python layer keys its cache on the parameters' version counters and storage, in
- * eval mode / without gradient recording only). */
+ * caller is responsible for "unchanged" (the Python layer keys its cache on the identity, storage and version counter of the
+ * parameters and the query, in eval mode / without gradient recording only, and never sets the flag while the stream is being
+ * captured: a captured forward always prepares for itself). */
 #define AECF_PREP_READY 8
 
 /* Backward (autograd transpose of the above). */

@@ -204,6 +204,63 @@ def test_cast_cache_follows_data_writes():
         assert torch.equal(pool._activation_dtype_params(torch.bfloat16)[0].float(), c0.float())
 
 
+def test_inference_caches_key_on_tensor_identity():
+    """The inference caches (cast copies, the kernels' preparation) are dropped by train() / eval(), are not carried into copies
+    or pickles, and are keyed on the tensor object as well as its address and version counter: another tensor at the same
+    address with the same version (a freed query whose block the allocator hands the next one) does not match."""
+    import copy
+    import pickle
+    import torch
+    import torch.nn as nn
+    import aecf_amd
+    from aecf_amd.layer import _stamp, _stamp_matches
+    _, pool = aecf_amd.create_fusion_pool(64, 2, num_heads=2)
+    bf = torch.bfloat16
+    for mode in (True, False):
+        pool.eval()
+        with torch.no_grad():
+            c0 = pool._activation_dtype_params(bf)[0]
+            assert pool._activation_dtype_params(bf)[0] is c0
+        pool._prep_cache = ("key", torch.empty(4))
+        pool.train(mode)                                                       # train() and eval() alike
+        assert pool._cast_cache == {} and pool._prep_cache is None
+    pool.eval()
+    with torch.no_grad():
+        c0 = pool._activation_dtype_params(bf)[0]
+        pool._prep_cache = ("key", torch.empty(4))
+        assert copy.deepcopy(pool)._cast_cache == {} and copy.deepcopy(pool)._prep_cache is None
+        assert pickle.loads(pickle.dumps(pool))._cast_cache == {}
+        assert pool._activation_dtype_params(bf)[0] is c0                      # (the original keeps its own)
+        w = pool.attention.in_proj_weight
+        pool.attention.in_proj_weight = nn.Parameter(w.detach())               # same storage, another object
+        assert pool.attention.in_proj_weight.data_ptr() == w.data_ptr()
+        c1 = pool._activation_dtype_params(bf)[0]
+        assert c1 is not c0 and torch.equal(c1, c0)
+    # torch's fused AdamW writes the parameters without moving their version counters: any optimizer step drops the caches
+    opt = torch.optim.AdamW(pool.parameters(), lr=1e-3, fused=True)
+    for p in pool.parameters():
+        p.grad = torch.ones_like(p)
+    version = pool.attention.in_proj_weight._version
+    opt.step()
+    assert pool.attention.in_proj_weight._version == version and pool._cast_cache == {}
+    t_ = torch.randn(8)
+    s = _stamp((t_, None))
+    assert _stamp_matches(s, (t_, None))
+    assert _stamp_matches(s, (t_.view(2, 4), None))                            # a view of the same tensor: same object behind it
+    other = t_.detach()                                                        # same address, same version, another tensor
+    assert other.data_ptr() == t_.data_ptr() and other._version == t_._version
+    assert not _stamp_matches(s, (other, None))
+    assert not _stamp_matches(s, (t_, t_)) and not _stamp_matches(s, (t_,))
+    t_.add_(1.0)                                                               # version counter
+    assert not _stamp_matches(s, (t_, None))
+    s = _stamp((t_, None))
+    t_.data = torch.randn(8)                                                   # storage (.data = keeps the version)
+    assert not _stamp_matches(s, (t_, None))
+    s = _stamp((t_, None))
+    del t_
+    assert s[0][0]() is None                                                   # a freed tensor can match nothing
+
+
 def _philox_py(ctr, key):
     """Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11), restated."""
     c, k = list(ctr), list(key)
