@@ -13,9 +13,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # AECF_LIB_PATH: another build of the same library (A/B timing of kernel variants on one box); default = the in-tree build
 LIB_PATH = os.environ.get("AECF_LIB_PATH") or os.path.join(_HERE, "lib", "libaecf_hip.so")
 
-AECF_ABI_VERSION = 9
+AECF_ABI_VERSION = 10
 AECF_BF16 = 0
 AECF_F32 = 1
+AECF_F16 = 2
 AECF_PRECISE = 1
 AECF_DRAW_UNIFORMS = 2
 AECF_HILO_GRADS = 4
@@ -137,6 +138,7 @@ _SYMBOLS = [
     ("aecf_front_pair", c_int, [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("aecf_cast_f32_to_bf16", c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("aecf_cast_f32_to_f16", c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("aecf_adamw_step", c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                 c_float, c_float, c_float, c_void_p]),
     ("aecf_rows_split", c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),

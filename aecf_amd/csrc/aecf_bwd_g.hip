@@ -244,11 +244,7 @@ static void launch_one(const BwdGArgs& a, hipStream_t s) {
 
 void launch_bwd_g(int dtype, const BwdGArgs& a, bool dx, hipStream_t s) {
     AECF_DISPATCH_M(a.M, {
-        if (dtype == 0) {
-            if (dx) launch_one<BF16, M_, true>(a, s); else launch_one<BF16, M_, false>(a, s);
-        } else {
-            if (dx) launch_one<F32, M_, true>(a, s); else launch_one<F32, M_, false>(a, s);
-        }
+        AECF_DISPATCH_T(dtype, { if (dx) launch_one<T_, M_, true>(a, s); else launch_one<T_, M_, false>(a, s); });
     });
 }
 

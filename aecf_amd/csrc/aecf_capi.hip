@@ -15,7 +15,7 @@ using namespace aecf;
 namespace {
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-inline int esize(int dtype) { return dtype == AECF_BF16 ? 2 : 4; }
+inline int esize(int dtype) { return dtype == AECF_F32 ? 4 : 2; }
 // the weight-stationary kernels read W_v and W_o (and their transposes) from fragment-major copies: bf16, these E only
 inline bool ws_frag_shape(int dtype, int E) { return dtype == AECF_BF16 && (E == 256 || E == 512 || E == 768 || E == 1024); }
 
@@ -177,7 +177,7 @@ const char* aecf_status_string(int status) {
         case AECF_ERR_BAD_DIMS: return "bad dimensions";
         case AECF_ERR_UNSUPPORTED:
             return "configuration not supported by the HIP path (need 1<=M<=8, 1<=H<=16, E%64==0, head_dim%32==0 for "
-                   "bf16 / %16==0 for f32)";
+                   "bf16 / f16, %16==0 for f32)";
         case AECF_ERR_NULL_POINTER: return "required pointer is null";
         case AECF_ERR_WORKSPACE: return "workspace too small";
         case AECF_ERR_LAUNCH: return "kernel launch failed";
@@ -197,11 +197,11 @@ int aecf_pool_check(const aecf_pool_desc* d) {
     if (!d) return AECF_ERR_NULL_POINTER;
     if (d->batch <= 0 || d->modalities <= 0 || d->embed_dim <= 0 || d->num_heads <= 0) return AECF_ERR_BAD_DIMS;
     if (d->embed_dim % d->num_heads != 0) return AECF_ERR_BAD_DIMS;
-    if (d->dtype != AECF_BF16 && d->dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (d->dtype != AECF_BF16 && d->dtype != AECF_F32 && d->dtype != AECF_F16) return AECF_ERR_UNSUPPORTED;
     if (d->modalities > 8 || d->num_heads > HPAD) return AECF_ERR_UNSUPPORTED;
     if (d->embed_dim % 64 != 0) return AECF_ERR_UNSUPPORTED;
     const int hd = d->embed_dim / d->num_heads;
-    if (hd % (d->dtype == AECF_BF16 ? 32 : 16) != 0) return AECF_ERR_UNSUPPORTED;
+    if (hd % (d->dtype == AECF_F32 ? 16 : 32) != 0) return AECF_ERR_UNSUPPORTED;
     if (d->embed_dim > 1024) return AECF_ERR_UNSUPPORTED;
     if (d->mask_mode < 0 || d->mask_mode > 2) return AECF_ERR_BAD_DIMS;
     return AECF_OK;
@@ -454,7 +454,9 @@ int pool_backward_on(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, hipSt
         !a->dquery || !a->dw_in || !a->db_in || !a->dw_out || !a->db_out || !a->workspace)
         return AECF_ERR_NULL_POINTER;
     if (a->d_entropy && !a->attn_w) return AECF_ERR_NULL_POINTER;
-    if (a->grad_dtype != AECF_F32 && !(a->grad_dtype == AECF_BF16 && d->dtype == AECF_BF16)) return AECF_ERR_UNSUPPORTED;
+    // parameter gradients: float32, or the 16-bit activation dtype itself (bf16 / f16 parameters)
+    if (a->grad_dtype != AECF_F32 && !(a->grad_dtype == d->dtype && (d->dtype == AECF_BF16 || d->dtype == AECF_F16)))
+        return AECF_ERR_UNSUPPORTED;
     const bool hilo = (a->flags & AECF_HILO_GRADS) != 0;
     if (hilo && (!hilo_supported(d) || do_ready)) return AECF_ERR_UNSUPPORTED;
     if (hilo && !a->saved_o_lo) return AECF_ERR_NULL_POINTER;
@@ -513,7 +515,7 @@ int pool_backward_on(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, hipSt
     } else {
         launch_gemm_tn(d->dtype, t1, s);
     }
-    const int gb = a->grad_dtype == AECF_BF16 ? 1 : 0;
+    const int gt = a->grad_dtype == AECF_BF16 ? GRAD_BF16 : (a->grad_dtype == AECF_F16 ? GRAD_F16 : GRAD_F32);
     mark(ev, 3, s);
 
     BwdGArgs g2;
@@ -581,9 +583,9 @@ int pool_backward_on(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, hipSt
     ReduceSegs rs;
     for (int i = 0; i < ReduceSegs::N; ++i) rs.splits[i] = L.splits;
     rs.splits[4] = dsu_chunks ? dsu_chunks : L.u_splits;
-    const size_t gsz = gb ? 2 : 4;                                    // bytes per parameter-gradient element
-    for (int i = 0; i < ReduceSegs::N; ++i) rs.dst_bf16[i] = gb;
-    rs.dst_bf16[4] = 0;                                               // u stays float32 (internal)
+    const size_t gsz = gt != GRAD_F32 ? 2 : 4;                        // bytes per parameter-gradient element
+    for (int i = 0; i < ReduceSegs::N; ++i) rs.dst_gt[i] = gt;
+    rs.dst_gt[4] = GRAD_F32;                                          // u stays float32 (internal)
     const float gscale = a->grad_scale != 0.f ? a->grad_scale : 1.f;  // (ABI v9: 1 / world of a data-parallel caller)
     for (int i = 0; i < 4; ++i) rs.scale[i] = gscale;
     rs.src[0] = (const float*)(ws + L.slab_o); rs.dst[0] = a->dw_out;                              rs.n[0] = (int64_t)E * E;
@@ -606,7 +608,7 @@ int pool_backward_on(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, hipSt
     FinalizeArgs f;
     f.w_in = a->w_in; f.query = a->query; f.qs = qs; f.u = u; f.dqp = (float*)(ws + L.dqp);
     f.dq_part = (float*)(ws + L.dq_part); f.dw_in = a->dw_in;
-    f.db_in = a->db_in; f.dquery = a->dquery; f.E = E; f.H = H; f.hd = hd; f.scale = scale; f.grad_bf16 = gb;
+    f.db_in = a->db_in; f.dquery = a->dquery; f.E = E; f.H = H; f.hd = hd; f.scale = scale; f.grad_gt = gt;
     f.gscale = gscale;
     launch_finalize_all(d->dtype, f, rs, s);
     if (dx_last) {
@@ -658,7 +660,7 @@ size_t aecf_entropy_loss_workspace_bytes(int64_t n) { (void)n; return 1024 * siz
 int aecf_entropy_loss_fwd_bwd(int64_t n, int32_t dtype, int32_t last_seq_len, float entropy_target, const void* entropy,
                               float upstream, void* loss, float* d_entropy, void* workspace, void* stream) {
     if (n <= 0) return AECF_ERR_BAD_DIMS;
-    if (dtype != AECF_BF16 && dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (dtype != AECF_BF16 && dtype != AECF_F32 && dtype != AECF_F16) return AECF_ERR_UNSUPPORTED;
     if (!entropy || !loss || !workspace) return AECF_ERR_NULL_POINTER;
     const double max_ent = last_seq_len > 1 ? log((double)last_seq_len) : 0.0;   // ref :307
     const float target = (float)(max_ent * (double)entropy_target);
@@ -669,7 +671,7 @@ int aecf_entropy_loss_fwd_bwd(int64_t n, int32_t dtype, int32_t last_seq_len, fl
 int aecf_sdpa_forward(int64_t B, int32_t S, int32_t T, int32_t E, int32_t dtype, float scale, const void* q,
                       const void* k, const void* v, void* out, float* probs, void* stream) {
     if (B <= 0 || S <= 0 || T <= 0 || E <= 0) return AECF_ERR_BAD_DIMS;
-    if (S > 64 || T > 64 || (dtype != AECF_BF16 && dtype != AECF_F32)) return AECF_ERR_UNSUPPORTED;
+    if (S > 64 || T > 64 || (dtype != AECF_BF16 && dtype != AECF_F32 && dtype != AECF_F16)) return AECF_ERR_UNSUPPORTED;
     if (!q || !k || !v || !out) return AECF_ERR_NULL_POINTER;
     launch_sdpa_fwd(dtype, B, S, T, E, scale, q, k, v, out, probs, (hipStream_t)stream);
     return launch_status();
@@ -679,7 +681,7 @@ int aecf_sdpa_backward(int64_t B, int32_t S, int32_t T, int32_t E, int32_t dtype
                        const void* k, const void* v, const float* probs, const void* dout, void* dq, void* dk,
                        void* dv, void* stream) {
     if (B <= 0 || S <= 0 || T <= 0 || E <= 0) return AECF_ERR_BAD_DIMS;
-    if (S > 64 || T > 64 || (dtype != AECF_BF16 && dtype != AECF_F32)) return AECF_ERR_UNSUPPORTED;
+    if (S > 64 || T > 64 || (dtype != AECF_BF16 && dtype != AECF_F32 && dtype != AECF_F16)) return AECF_ERR_UNSUPPORTED;
     if (!q || !k || !v || !probs || !dout || !dq || !dk || !dv) return AECF_ERR_NULL_POINTER;
     launch_sdpa_bwd(dtype, B, S, T, E, scale, q, k, v, probs, dout, dq, dk, dv, (hipStream_t)stream);
     return launch_status();
@@ -710,7 +712,7 @@ float aecf_philox_host(uint64_t seed, uint64_t offset, uint32_t threads, int64_t
 
 int aecf_entropy_loss_from_partials(int64_t n, int32_t dtype, const float* partial, void* loss, void* stream) {
     if (n <= 0) return AECF_ERR_BAD_DIMS;
-    if (dtype != AECF_BF16 && dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (dtype != AECF_BF16 && dtype != AECF_F32 && dtype != AECF_F16) return AECF_ERR_UNSUPPORTED;
     if (!partial || !loss) return AECF_ERR_NULL_POINTER;
     launch_entropy_from_partials(dtype, n, partial, loss, (hipStream_t)stream);
     return launch_status();
@@ -839,6 +841,18 @@ int aecf_cast_f32_to_bf16(int32_t n, const float* const* src, void* const* dst, 
     return launch_status();
 }
 
+int aecf_cast_f32_to_f16(int32_t n, const float* const* src, void* const* dst, const int64_t* numel, void* stream) {
+    if (n < 0 || n > 8) return AECF_ERR_BAD_DIMS;
+    if (n == 0) return AECF_OK;
+    if (!src || !dst || !numel) return AECF_ERR_NULL_POINTER;
+    for (int i = 0; i < n; ++i) {
+        if (numel[i] < 0) return AECF_ERR_BAD_DIMS;
+        if (numel[i] > 0 && (!src[i] || !dst[i])) return AECF_ERR_NULL_POINTER;
+    }
+    launch_cast_f32_f16_multi(n, src, dst, numel, (hipStream_t)stream);
+    return launch_status();
+}
+
 int aecf_adamw_step(int32_t n, void* const* param, const void* const* grad, void* const* exp_avg, void* const* exp_avg_sq,
                     void* const* step, const int64_t* numel, void* ticket, float lr, float beta1, float beta2, float eps,
                     float weight_decay, void* stream) {
@@ -902,6 +916,7 @@ static size_t nce_generic_workspace_bytes(int64_t rows, int64_t cols, int32_t d,
 // that can be selected for (d, dtype) needs, so the call never runs a form on a buffer sized for another one.
 size_t aecf_nce_workspace_bytes(int64_t rows, int64_t cols, int32_t d, int32_t dtype) {
     if (rows <= 0 || cols <= 0 || d <= 0) return 0;
+    if (dtype != AECF_BF16 && dtype != AECF_F32) return 0;               // (no float16 InfoNCE)
     size_t need = 0;
     if (nce_gemm_supported(dtype, d, 1.0f)) need = nce_gemm_workspace_bytes(rows, cols, d);
     if (nce_flash_supported(dtype, d)) {

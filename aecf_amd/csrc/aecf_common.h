@@ -2,17 +2,20 @@
 //
 // Conventions used throughout:
 //   * one wavefront = 64 lanes; r16 = lane & 15, lg = lane >> 4.
-//   * MFMA tiles are 16x16 (v_mfma_f32_16x16x32_bf16 for bf16, v_mfma_f32_16x16x4_f32 for f32).
+//   * MFMA tiles are 16x16 (v_mfma_f32_16x16x32_bf16 / _f16 for bf16 / f16, v_mfma_f32_16x16x4_f32 for f32).
 //     A "fragment" is the 16 bytes one lane contributes to one K-step:
-//        bf16: 8 consecutive k (KSTEP = 32 per MFMA),  A[row r16][k0 + 8*lg + j]
+//        bf16, f16: 8 consecutive k (KSTEP = 32 per MFMA),  A[row r16][k0 + 8*lg + j]
 //        f32 : 4 consecutive k (KSTEP = 16 = 4 MFMAs), A[row r16][k0 + 4*lg + t] feeds MFMA t
 //     (the K order inside a step is a free choice as long as A and B agree).
 //   * accumulator (C/D) layout of a 16x16 tile: col = r16, row = 4*lg + reg   (reg = 0..3).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
@@ -20,6 +23,7 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 struct BF16 {};
 struct F32 {};
+struct F16 {};
 
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned int b) { return __uint_as_float(b << 16); }
 __device__ __forceinline__ unsigned int f32_to_bf16_bits(float f) {
@@ -30,6 +34,28 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 __device__ __forceinline__ unsigned int pack_bf16x2(float lo, float hi) {
     bf16x2 v = __builtin_convertvector(f32x2{lo, hi}, bf16x2);      // ONE v_cvt_pk_bf16_f32 (both halves, RNE)
     return __builtin_bit_cast(unsigned int, v);
+}
+
+// float32 -> IEEE half.  v_cvt_f16_f32 / v_cvt_pk_f16_f32 in the default rounding mode: round to nearest even, overflow to
+// +-inf, NaN stays NaN -- what torch's Tensor.half() does.  (NOT __builtin_amdgcn_cvt_pkrtz: that rounds toward zero.)  Every
+// float16 store of the library goes through these two, aecf_cast_f32_to_f16 included, so its known-answer test guards them.
+__device__ __forceinline__ unsigned int f32_to_f16_bits(float f) {
+    _Float16 h = (_Float16)f;
+    return (unsigned int)__builtin_bit_cast(unsigned short, h);
+}
+__device__ __forceinline__ unsigned int pack_f16x2(float lo, float hi) {
+    f16x2 v = __builtin_convertvector(f32x2{lo, hi}, f16x2);
+    return __builtin_bit_cast(unsigned int, v);
+}
+__device__ __forceinline__ float f16_bits_to_f32(unsigned int b) {
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)b);
+}
+
+// two floats as one 32-bit word of the 16-bit element type T (bf16 or f16), low element first
+template <typename T>
+__device__ __forceinline__ unsigned int pack2(float lo, float hi) {
+    if constexpr (std::is_same<T, F16>::value) return pack_f16x2(lo, hi);
+    else return pack_bf16x2(lo, hi);
 }
 
 template <typename T> struct Tr;
@@ -77,6 +103,46 @@ template <> struct Tr<BF16> {
     static __device__ __forceinline__ elem from_f32(float f) { return (elem)f32_to_bf16_bits(f); }
 };
 
+// IEEE half: the bf16 layout (8 elements per lane and K-step, the same accumulator layout), v_mfma_f32_16x16x32_f16
+template <> struct Tr<F16> {
+    typedef unsigned short elem;
+    typedef u32x4 frag;                 // 8 f16
+    static constexpr int EPL = 8;
+    static constexpr int KSTEP = 32;
+    static constexpr int BYTES = 2;
+    static __device__ __forceinline__ frag zero() { return frag{0u, 0u, 0u, 0u}; }
+    static __device__ __forceinline__ frag load(const elem* p) { return *reinterpret_cast<const frag*>(p); }
+    static __device__ __forceinline__ void unpack(frag f, float* o) {
+        const f16x8 h = __builtin_bit_cast(f16x8, f);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = (float)h[i];
+    }
+    static __device__ __forceinline__ frag pack(const float* v) {
+        frag f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f[i] = pack_f16x2(v[2 * i], v[2 * i + 1]);
+        return f;
+    }
+    static __device__ __forceinline__ f32x4 mma(frag a, frag b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ void load4(const elem* p, float* o) {
+        const u32x2 v = *reinterpret_cast<const u32x2*>(p);
+        o[0] = f16_bits_to_f32(v[0] & 0xffffu);
+        o[1] = f16_bits_to_f32(v[0] >> 16);
+        o[2] = f16_bits_to_f32(v[1] & 0xffffu);
+        o[3] = f16_bits_to_f32(v[1] >> 16);
+    }
+    static __device__ __forceinline__ void store4(elem* p, const float* v) {
+        u32x2 o;
+        o[0] = pack_f16x2(v[0], v[1]);
+        o[1] = pack_f16x2(v[2], v[3]);
+        *reinterpret_cast<u32x2*>(p) = o;
+    }
+    static __device__ __forceinline__ float to_f32(elem e) { return f16_bits_to_f32(e); }
+    static __device__ __forceinline__ elem from_f32(float f) { return (elem)f32_to_f16_bits(f); }
+};
+
 template <> struct Tr<F32> {
     typedef float elem;
     typedef f32x4 frag;                 // 4 f32
@@ -106,9 +172,13 @@ template <> struct Tr<F32> {
     static __device__ __forceinline__ elem from_f32(float f) { return f; }
 };
 
-// parameter-gradient element store: float32, or bf16 (one rounding of the float32 value)
-__device__ __forceinline__ void store_grad(void* base, int64_t i, float v, int bf16) {
-    if (bf16) reinterpret_cast<unsigned short*>(base)[i] = (unsigned short)f32_to_bf16_bits(v);
+// element type of a parameter-gradient store (internal; the values of the float32 and bf16 stores are those of the former
+// 0 / 1 bf16 flag)
+enum GradType { GRAD_F32 = 0, GRAD_BF16 = 1, GRAD_F16 = 2 };
+// parameter-gradient element store: float32, or bf16 / f16 (one rounding of the float32 value)
+__device__ __forceinline__ void store_grad(void* base, int64_t i, float v, int gt) {
+    if (gt == GRAD_BF16) reinterpret_cast<unsigned short*>(base)[i] = (unsigned short)f32_to_bf16_bits(v);
+    else if (gt == GRAD_F16) reinterpret_cast<unsigned short*>(base)[i] = (unsigned short)f32_to_f16_bits(v);
     else reinterpret_cast<float*>(base)[i] = v;
 }
 
@@ -347,4 +417,14 @@ __device__ __forceinline__ void curriculum_row(const MaskCfg& c, int L, float* w
         case 7: { constexpr int M_ = 7; __VA_ARGS__; break; } \
         case 8: { constexpr int M_ = 8; __VA_ARGS__; break; } \
         default: break;                                       \
+    }
+
+// launcher dispatch on the aecf_dtype of an entry point (AECF_BF16 = 0, AECF_F32 = 1, AECF_F16 = 2): T_ is the element tag.  Any
+// other value launches nothing -- the entry points reject it before a launcher is reached.
+#define AECF_DISPATCH_T(dtype, ...)                              \
+    switch (dtype) {                                             \
+        case 0: { typedef BF16 T_; __VA_ARGS__; break; }         \
+        case 1: { typedef F32 T_; __VA_ARGS__; break; }          \
+        case 2: { typedef F16 T_; __VA_ARGS__; break; }          \
+        default: break;                                          \
     }

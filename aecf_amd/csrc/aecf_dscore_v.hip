@@ -92,13 +92,12 @@ __global__ __launch_bounds__(256) void dscore_v_kernel(BwdGArgs p, const typenam
 }
 
 bool launch_dscore_v(int dtype, const BwdGArgs& a, const void* saved_v, hipStream_t s) {
-    const int bytes = dtype == 0 ? 2 : 4;
+    const int bytes = dtype == 1 ? 4 : 2;
     const int lph = a.hd * bytes / 16;               // lanes per head
     if (lph < 1 || lph > 64 || (a.hd * bytes) % 16 != 0) return false;
     dim3 grid((unsigned)((a.B + 3) / 4)), block(256);
     AECF_DISPATCH_M(a.M, {
-        if (dtype == 0) dscore_v_kernel<BF16, M_><<<grid, block, 0, s>>>(a, (const unsigned short*)saved_v, lph);
-        else dscore_v_kernel<F32, M_><<<grid, block, 0, s>>>(a, (const float*)saved_v, lph);
+        AECF_DISPATCH_T(dtype, dscore_v_kernel<T_, M_><<<grid, block, 0, s>>>(a, (const Tr<T_>::elem*)saved_v, lph));
     });
     return true;
 }

@@ -55,10 +55,15 @@ __device__ __forceinline__ void reduce_segments_block(const ReduceSegs& r, int64
             }
             if (on && g == 0) {
                 a *= r.scale[s];
-                if (r.dst_bf16[s]) {
+                if (r.dst_gt[s] == GRAD_BF16) {
                     u32x2 o;
                     o[0] = pack_bf16x2(a[0], a[1]);
                     o[1] = pack_bf16x2(a[2], a[3]);
+                    *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(r.dst[s]) + 4 * q) = o;
+                } else if (r.dst_gt[s] == GRAD_F16) {
+                    u32x2 o;
+                    o[0] = pack_f16x2(a[0], a[1]);
+                    o[1] = pack_f16x2(a[2], a[3]);
                     *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(r.dst[s]) + 4 * q) = o;
                 } else {
                     *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(r.dst[s]) + 4 * q) = a;
@@ -85,11 +90,11 @@ __device__ __forceinline__ void fin_outer_block(const FinalizeArgs& p, int kc, i
         for (int jj = jg; jj < 16; jj += 4) {
             const int j = jb * 16 + jj;
             const float dq = p.dqp[j] * p.gscale;
-            store_grad(p.dw_in, (int64_t)j * E + k, dq * qk, p.grad_bf16);                                         // dW_q
-            store_grad(p.dw_in, (int64_t)(E + j) * E + k, p.qs[j] * p.gscale * p.u[(int64_t)(j / p.hd) * E + k], p.grad_bf16);   // dW_k
+            store_grad(p.dw_in, (int64_t)j * E + k, dq * qk, p.grad_gt);                                         // dW_q
+            store_grad(p.dw_in, (int64_t)(E + j) * E + k, p.qs[j] * p.gscale * p.u[(int64_t)(j / p.hd) * E + k], p.grad_gt);   // dW_k
             if (bx == 0 && c == 0 && lane == 0) {
-                store_grad(p.db_in, j, dq, p.grad_bf16);         // db_q
-                store_grad(p.db_in, E + j, 0.f, p.grad_bf16);    // db_k
+                store_grad(p.db_in, j, dq, p.grad_gt);         // db_q
+                store_grad(p.db_in, E + j, 0.f, p.grad_gt);    // db_k
             }
         }
     }
@@ -130,7 +135,7 @@ __device__ __forceinline__ void fin_dquery_block(const FinalizeArgs& p, int kb, 
         float t = 0.f;
 #pragma unroll 8
         for (int r = 0; r < 32; ++r) t += scratch[r * 64 + threadIdx.x];
-        store_grad(p.dquery, kb * 64 + threadIdx.x, t * p.gscale, p.grad_bf16);
+        store_grad(p.dquery, kb * 64 + threadIdx.x, t * p.gscale, p.grad_gt);
     }
 }
 
@@ -150,8 +155,7 @@ __global__ __launch_bounds__(256) void dqp_kernel(DqpJob q) { dqp_rows<T>(q, blo
 
 void launch_dqp(int dtype, const DqpJob& q, hipStream_t s) {
     const unsigned grid = (unsigned)((q.E + 3) / 4);               // a wave per row
-    if (dtype == 0) dqp_kernel<BF16><<<dim3(grid), dim3(256), 0, s>>>(q);
-    else dqp_kernel<F32><<<dim3(grid), dim3(256), 0, s>>>(q);
+    AECF_DISPATCH_T(dtype, dqp_kernel<T_><<<dim3(grid), dim3(256), 0, s>>>(q));
 }
 
 void launch_reduce_segments(const ReduceSegs& r, hipStream_t s) {
@@ -171,8 +175,7 @@ void launch_finalize_all(int dtype, const FinalizeArgs& a, const ReduceSegs& r, 
     for (int i = 0; i < ReduceSegs::N; ++i) waves += (r.n[i] + 63) / 64;
     const int nd = E / 64, nqx = E / 64 / kc, nqy = E / 16;
     const unsigned grid = (unsigned)(nd + nqx * nqy + (waves + 3) / 4);
-    if (dtype == 0) finalize_all_kernel<BF16><<<dim3(grid), dim3(256), 0, s>>>(a, r, kc, nd, nqx, nqy);
-    else finalize_all_kernel<F32><<<dim3(grid), dim3(256), 0, s>>>(a, r, kc, nd, nqx, nqy);
+    AECF_DISPATCH_T(dtype, finalize_all_kernel<T_><<<dim3(grid), dim3(256), 0, s>>>(a, r, kc, nd, nqx, nqy));
 }
 
 }  // namespace aecf

@@ -12,7 +12,7 @@
 // formed in registers from the M staged x tiles while the fragments are read (fp32 FMA, one rounding to the
 // MFMA input type), so V is projected once per sample instead of once per (sample, modality).
 //
-// bf16 output leaves through LDS as full 256-byte rows; f32 output is stored from the accumulator layout.
+// bf16 / f16 output leaves through LDS as full 256-byte rows; f32 output is stored from the accumulator layout.
 #include <stdlib.h>
 
 #include "aecf_kernels.h"
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNtArgs p) {
         bv[ct] = (bias && ct < nct) ? X::to_f32(bias[n]) : 0.f;
     }
     if (X::BYTES == 2 && !p.out_f32 && WT == 4) {
-        // accumulators -> LDS as a [128][128] bf16 image (256-byte rows), then full-row 16-byte stores
+        // accumulators -> LDS as a [128][128] 16-bit image (256-byte rows), then full-row 16-byte stores
         __syncthreads();
         char* cl = smem;
 #pragma unroll
@@ -119,8 +119,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNtArgs p) {
                 const float got0 = __shfl_xor(send0, 1, 64), got1 = __shfl_xor(send1, 1, 64);
                 const int col = 64 * wc + 16 * ct + (r16 & ~1);
                 const int rowb = 64 * wr + 16 * rt + 4 * lg + (odd ? 2 : 0);
-                const unsigned int d0 = odd ? pack_bf16x2(got0, v2) : pack_bf16x2(v0, got0);
-                const unsigned int d1 = odd ? pack_bf16x2(got1, v3) : pack_bf16x2(v1, got1);
+                const unsigned int d0 = odd ? pack2<T>(got0, v2) : pack2<T>(v0, got0);
+                const unsigned int d1 = odd ? pack2<T>(got1, v3) : pack2<T>(v1, got1);
                 *reinterpret_cast<unsigned int*>(cl + (rowb + 0) * 256 + col * 2) = d0;
                 *reinterpret_cast<unsigned int*>(cl + (rowb + 1) * 256 + col * 2) = d1;
             }
@@ -173,8 +173,7 @@ void launch_gemm_nt(int dtype, const GemmNtArgs& a_in, hipStream_t s) {
     if (a.pooled & 1) { launch_vproj(dtype, a, s); return; }     // per-modality accumulators (aecf_vproj.hip)
     // fewer than 64 block tiles of 128 x 128: 32 x 32 tiles instead (16 x the blocks, each 1/16 of the K loop's MFMAs)
     const bool small = ((a.R + 127) / 128) * (int64_t)((a.N + 127) / 128) < 64;
-    if (dtype == 0) { if (small) launch_one<BF16, 1, false, 1>(a, s); else launch_one<BF16, 1, false>(a, s); }
-    else { if (small) launch_one<F32, 1, false, 1>(a, s); else launch_one<F32, 1, false>(a, s); }
+    AECF_DISPATCH_T(dtype, { if (small) launch_one<T_, 1, false, 1>(a, s); else launch_one<T_, 1, false>(a, s); });
 }
 
 }  // namespace aecf

@@ -22,14 +22,14 @@ namespace aecf {
 
 // ---- NR x NF register block (NR batch rows x NF features, one 16-byte load per row): load, (optionally
 //      combine), transpose, write feature-major to LDS.  bf16: 4 x 8, f32: 4 x 4 -> 256 blocks per tile.
-template <typename T> struct TBlk;
-template <> struct TBlk<BF16> {
+// (16-bit element types, bf16 and f16: the same block, only the conversions differ)
+template <typename T> struct TBlk {
     static constexpr int NR = 4, NF = 8;
     u32x4 r[4];                                   // r[t] = 8 features of batch row t
     __device__ __forceinline__ void load_row(int t, const char* p) { r[t] = *reinterpret_cast<const u32x4*>(p); }
     __device__ __forceinline__ void zero_row(int t) { r[t] = u32x4{0u, 0u, 0u, 0u}; }
-    __device__ __forceinline__ void get_row(int t, float* v) const { Tr<BF16>::unpack(r[t], v); }
-    __device__ __forceinline__ void set_row(int t, const float* v) { r[t] = Tr<BF16>::pack(v); }
+    __device__ __forceinline__ void get_row(int t, float* v) const { Tr<T>::unpack(r[t], v); }
+    __device__ __forceinline__ void set_row(int t, const float* v) { r[t] = Tr<T>::pack(v); }
     // write feature rows frow0..frow0+7; this block's 4 batch entries are the 8-byte half `bgr & 1` of chunk bgr >> 1
     __device__ __forceinline__ void store_t(char* lds, int frow0, int bgr) const {
 #pragma unroll
@@ -403,9 +403,11 @@ static void launch_wj(const GemmTnArgs& a, hipStream_t s) {
 }
 
 void launch_gemm_tn(int dtype, const GemmTnArgs& a, hipStream_t s) {
-    // bf16: transposed-LDS-read kernel (aecf_gemm_tn_tr.hip); f32: register-transposed staging (this file)
+    // bf16: transposed-LDS-read kernel (aecf_gemm_tn_tr.hip); f32 and f16: register-transposed staging (this file)
     if (!a.pooled) {
-        if (dtype == 0) launch_gemm_tn_tr(a, s); else launch_wj<F32, 1, false>(a, s);
+        if (dtype == 0) launch_gemm_tn_tr(a, s);
+        else if (dtype == 1) launch_wj<F32, 1, false>(a, s);
+        else if (dtype == 2) launch_wj<F16, 1, false>(a, s);
         return;
     }
     const bool do_main = a.parts != 2, do_u = a.parts != 1;
@@ -413,7 +415,8 @@ void launch_gemm_tn(int dtype, const GemmTnArgs& a, hipStream_t s) {
     if (dtype == 0 && do_u && u_mfma_supported(a)) { launch_u_mfma(a, s); return; }
     AECF_DISPATCH_M(a.M, {
         if (dtype == 0) { if (do_u) launch_u<BF16, M_>(a, s); }
-        else { if (do_main) launch_wj<F32, M_, true>(a, s); if (do_u) launch_u<F32, M_>(a, s); }
+        else if (dtype == 1) { if (do_main) launch_wj<F32, M_, true>(a, s); if (do_u) launch_u<F32, M_>(a, s); }
+        else if (dtype == 2) { if (do_main) launch_wj<F16, M_, true>(a, s); if (do_u) launch_u<F16, M_>(a, s); }
     });
 }
 

@@ -36,7 +36,7 @@ void launch_prep_all(int dtype, const void* w_in, const void* b_in, const void* 
 struct GateArgs {
     const void* x;            // [B,M,E]
     const void* a_hi;         // [HPAD,E] dtype
-    const void* a_lo;         // [HPAD,E] dtype (bf16 only)
+    const void* a_lo;         // [HPAD,E] dtype (16-bit types only)
     const uint8_t* kpm;       // [B,M] or null
     const float* uniforms;    // [B,M] or null
     float* probs;             // [B,H,M]
@@ -179,7 +179,7 @@ struct ReduceSegs {
     void* dst[N];
     int64_t n[N];
     int splits[N];
-    int dst_bf16[N];      // 1: dst is bf16 (one rounding of the float32 sum)
+    int dst_gt[N];        // GradType of dst: GRAD_F32, or GRAD_BF16 / GRAD_F16 (one rounding of the float32 sum)
     float scale[N] = {1.f, 1.f, 1.f, 1.f, 1.f};   // the sum is multiplied by this before it is stored (aecf_pool_bwd_args.grad_scale)
 };
 void launch_reduce_segments(const ReduceSegs& r, hipStream_t s);
@@ -193,12 +193,12 @@ struct FinalizeArgs {
     const float* u;       // [HPAD,E] reduced
     const float* dqp;     // [E] dq' (DqpJob: side job of the dW_v launch, or launch_dqp)
     float* dq_part;       // (unused since round 4)
-    void* dw_in;          // [3E,E]  float32, or bf16 when grad_bf16
+    void* dw_in;          // [3E,E]  float32, or bf16 / f16 (grad_gt)
     void* db_in;          // [3E]
     void* dquery;         // [E]
     int E, H, hd;
     float scale;
-    int grad_bf16;
+    int grad_gt;          // GradType of the five gradients
     float gscale = 1.f;   // every gradient this launch writes is multiplied by it (aecf_pool_bwd_args.grad_scale)
 };
 void launch_dqp(int dtype, const DqpJob& q, hipStream_t s);        // dq' as its own small launch (shapes without the side job)
@@ -233,6 +233,7 @@ void launch_modality_frontend(int dtype, int64_t rows, int dim, const void* feat
 void launch_transpose_rect(int dtype, const void* src, void* dst, int64_t R, int64_t C, hipStream_t s);
 void launch_cast_bf16_f32(const void* src, float* dst, int64_t n, hipStream_t s);     // 16-byte aligned src / dst
 int launch_cast_f32_bf16_multi(int n, const float* const* src, void* const* dst, const int64_t* numel, hipStream_t s);   // n <= 8
+int launch_cast_f32_f16_multi(int n, const float* const* src, void* const* dst, const int64_t* numel, hipStream_t s);    // n <= 8
 
 // flash-style InfoNCE direction (aecf_nce_flash.hip): no [rows, cols] logits; optional entropy regulariser in the same call
 bool nce_flash_supported(int dtype, int d);

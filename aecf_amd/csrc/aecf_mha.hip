@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void mha_core_bwd_kernel(CoreArgs p) {
 }
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-inline int esize(int dtype) { return dtype == AECF_BF16 ? 2 : 4; }
+inline int esize(int dtype) { return dtype == AECF_F32 ? 4 : 2; }
 inline int launch_status() { return hipGetLastError() == hipSuccess ? AECF_OK : AECF_ERR_LAUNCH; }
 
 void nt(int dtype, const void* a, int64_t rows, const void* w, const void* bias, void* c, int E, int H, hipStream_t s) {
@@ -269,11 +269,11 @@ int aecf_mha_check(const aecf_mha_desc* d) {
     if (d->batch <= 0 || d->tgt_len <= 0 || d->src_len <= 0 || d->embed_dim <= 0 || d->num_heads <= 0)
         return AECF_ERR_BAD_DIMS;
     if (d->embed_dim % d->num_heads != 0) return AECF_ERR_BAD_DIMS;
-    if (d->dtype != AECF_BF16 && d->dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (d->dtype != AECF_BF16 && d->dtype != AECF_F32 && d->dtype != AECF_F16) return AECF_ERR_UNSUPPORTED;
     if (d->tgt_len > LMAX || d->src_len > LMAX) return AECF_ERR_UNSUPPORTED;
     // any head count dividing E; E itself a whole number of 128-byte K slices of the GEMM tiles: a multiple of 32 (f32) /
-    // 64 (bf16) -- E = 32, 96, ... in float32
-    if (d->embed_dim % (d->dtype == AECF_BF16 ? 64 : 32) != 0 || d->embed_dim > 1024) return AECF_ERR_UNSUPPORTED;
+    // 64 (bf16 / f16) -- E = 32, 96, ... in float32
+    if (d->embed_dim % (d->dtype == AECF_F32 ? 32 : 64) != 0 || d->embed_dim > 1024) return AECF_ERR_UNSUPPORTED;
     if (!(d->dropout_p >= 0.f && d->dropout_p < 1.f)) return AECF_ERR_BAD_DIMS;
     return AECF_OK;
 }
@@ -307,13 +307,10 @@ int aecf_mha_forward(const aecf_mha_desc* d, const aecf_mha_fwd_args* a, void* s
     {
         const size_t smem = (size_t)2 * c.tc * (d->src_len + 1) * sizeof(float);
         const dim3 grid((unsigned)d->batch, (unsigned)((d->tgt_len + c.tc - 1) / c.tc));
-        if (d->dtype == AECF_BF16) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mha_core_fwd_kernel<BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, CORE_LDS + 4096);
-            mha_core_fwd_kernel<BF16><<<grid, dim3(256), smem, s>>>(c);
-        } else {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mha_core_fwd_kernel<F32>), hipFuncAttributeMaxDynamicSharedMemorySize, CORE_LDS + 4096);
-            mha_core_fwd_kernel<F32><<<grid, dim3(256), smem, s>>>(c);
-        }
+        AECF_DISPATCH_T(d->dtype, {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mha_core_fwd_kernel<T_>), hipFuncAttributeMaxDynamicSharedMemorySize, CORE_LDS + 4096);
+            mha_core_fwd_kernel<T_><<<grid, dim3(256), smem, s>>>(c);
+        });
     }
     nt(d->dtype, a->saved_o, RT, a->w_out, a->b_out, a->y, E, H, s);
     return launch_status();
@@ -352,13 +349,10 @@ int aecf_mha_backward(const aecf_mha_desc* d, const aecf_mha_bwd_args* a, void* 
     if (c.tc < d->tgt_len) { c.dk32 = (float*)(ws + L.dk32); c.dv32 = (float*)(ws + L.dv32); }
     {
         const size_t smem = (size_t)2 * c.tc * (d->src_len + 1) * sizeof(float);
-        if (d->dtype == AECF_BF16) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mha_core_bwd_kernel<BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, CORE_LDS + 4096);
-            mha_core_bwd_kernel<BF16><<<dim3((unsigned)d->batch), dim3(256), smem, s>>>(c);
-        } else {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mha_core_bwd_kernel<F32>), hipFuncAttributeMaxDynamicSharedMemorySize, CORE_LDS + 4096);
-            mha_core_bwd_kernel<F32><<<dim3((unsigned)d->batch), dim3(256), smem, s>>>(c);
-        }
+        AECF_DISPATCH_T(d->dtype, {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mha_core_bwd_kernel<T_>), hipFuncAttributeMaxDynamicSharedMemorySize, CORE_LDS + 4096);
+            mha_core_bwd_kernel<T_><<<dim3((unsigned)d->batch), dim3(256), smem, s>>>(c);
+        });
     }
     nt(d->dtype, dqb, RT, wt[0], nullptr, a->dquery, E, H, s);
     nt(d->dtype, dkb, RS, wt[1], nullptr, a->dkey, E, H, s);

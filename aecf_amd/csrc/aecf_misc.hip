@@ -477,13 +477,47 @@ __global__ __launch_bounds__(256) void cast_f32_bf16_multi_kernel(CastJobs j) {
     }
 }
 
-int launch_cast_f32_bf16_multi(int n, const float* const* src, void* const* dst, const int64_t* numel, hipStream_t s) {
+// the same for float32 -> IEEE half (round to nearest even through pack_f16x2 / f32_to_f16_bits, the conversions of Tr<F16>)
+__global__ __launch_bounds__(256) void cast_f32_f16_multi_kernel(CastJobs j) {
+    int t = 0;
+#pragma unroll
+    for (int i = 1; i < 8; ++i)
+        if (i < j.n && (int64_t)blockIdx.x >= j.first_block[i]) t = i;
+    const int64_t i0 = (((int64_t)blockIdx.x - j.first_block[t]) * 256 + threadIdx.x) * 8;
+    const float* src = j.src[t];
+    unsigned short* dst = j.dst[t];
+    const int64_t n = j.numel[t];
+    const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+    if (vec && i0 + 8 <= n) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(src + i0), b = *reinterpret_cast<const f32x4*>(src + i0 + 4);
+        *reinterpret_cast<u32x4*>(dst + i0) = u32x4{pack_f16x2(a[0], a[1]), pack_f16x2(a[2], a[3]), pack_f16x2(b[0], b[1]),
+                                                    pack_f16x2(b[2], b[3])};
+    } else {
+        for (int64_t k = i0; k < n && k < i0 + 8; ++k) dst[k] = (unsigned short)f32_to_f16_bits(src[k]);
+    }
+}
+
+static CastJobs cast_jobs(int n, const float* const* src, void* const* dst, const int64_t* numel, int64_t& blocks) {
     CastJobs j;
-    int64_t blocks = 0;
+    blocks = 0;
     for (int i = 0; i < n; ++i) {
         j.src[j.n] = src[i]; j.dst[j.n] = (unsigned short*)dst[i]; j.numel[j.n] = numel[i]; j.first_block[j.n] = blocks;
         if (numel[i] > 0) { blocks += (numel[i] + 2047) / 2048; ++j.n; }
     }
+    return j;
+}
+
+int launch_cast_f32_f16_multi(int n, const float* const* src, void* const* dst, const int64_t* numel, hipStream_t s) {
+    int64_t blocks;
+    const CastJobs j = cast_jobs(n, src, dst, numel, blocks);
+    if (blocks == 0) return 0;
+    cast_f32_f16_multi_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(j);
+    return 1;
+}
+
+int launch_cast_f32_bf16_multi(int n, const float* const* src, void* const* dst, const int64_t* numel, hipStream_t s) {
+    int64_t blocks;
+    const CastJobs j = cast_jobs(n, src, dst, numel, blocks);
     if (blocks == 0) return 0;
     cast_f32_bf16_multi_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(j);
     return 1;
@@ -497,7 +531,7 @@ void launch_cast_bf16_f32(const void* src, float* dst, int64_t n, hipStream_t s)
 void launch_modality_frontend(int dtype, int64_t rows, int dim, const void* feat, const uint8_t* drop, void* out,
                               uint8_t* present, hipStream_t s) {
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-    if (dtype == 0)
+    if (dtype == 0)         // (bf16 / f32 only: aecf_modality_frontend refuses every other dtype)
         modality_frontend_kernel<BF16><<<grid, block, 0, s>>>(rows, dim, (const unsigned short*)feat, drop,
                                                               (unsigned short*)out, present);
     else
@@ -543,66 +577,53 @@ __global__ __launch_bounds__(1024) void entropy_loss_single_kernel(int64_t n, fl
 
 void launch_entropy_partials(int dtype, int64_t n, float target, const void* entropy, float* partial, hipStream_t s) {
     const int nblk = (int)((n + 255) / 256);                // (one block per 256 rows: the partition gate_stats uses)
-    if (dtype == 0)
-        entropy_loss_partial_kernel<BF16><<<dim3(nblk), dim3(256), 0, s>>>(n, target, (const unsigned short*)entropy, 0.f, nullptr, partial);
-    else
-        entropy_loss_partial_kernel<F32><<<dim3(nblk), dim3(256), 0, s>>>(n, target, (const float*)entropy, 0.f, nullptr, partial);
+    AECF_DISPATCH_T(dtype, entropy_loss_partial_kernel<T_><<<dim3(nblk), dim3(256), 0, s>>>(
+                               n, target, (const Tr<T_>::elem*)entropy, 0.f, nullptr, partial));
 }
 
 void launch_entropy_from_partials(int dtype, int64_t n, const float* partial, void* loss, hipStream_t s) {
     const int nblk = (int)((n + 255) / 256);
-    if (dtype == 0) entropy_loss_final_kernel<BF16><<<dim3(1), dim3(256), 0, s>>>(nblk, 1.0f / (float)n, partial, (unsigned short*)loss);
-    else entropy_loss_final_kernel<F32><<<dim3(1), dim3(256), 0, s>>>(nblk, 1.0f / (float)n, partial, (float*)loss);
+    AECF_DISPATCH_T(dtype, entropy_loss_final_kernel<T_><<<dim3(1), dim3(256), 0, s>>>(nblk, 1.0f / (float)n, partial,
+                                                                                        (Tr<T_>::elem*)loss));
 }
 
 void launch_entropy_loss(int dtype, int64_t n, float target, const void* entropy, float upstream, void* loss,
                          float* d_entropy, float* partial, hipStream_t s) {
     if (n <= 8192) {       // (one block: measured 31 us at 65536 rows against 4.6 + 4.3 us for the two-kernel form below)
         const float inv = 1.0f / (float)n;
-        if (dtype == 0)
-            entropy_loss_single_kernel<BF16><<<dim3(1), dim3(1024), 0, s>>>(n, target, (const unsigned short*)entropy,
-                                                                          2.0f * inv * upstream, inv, d_entropy, (unsigned short*)loss);
-        else
-            entropy_loss_single_kernel<F32><<<dim3(1), dim3(1024), 0, s>>>(n, target, (const float*)entropy,
-                                                                         2.0f * inv * upstream, inv, d_entropy, (float*)loss);
+        AECF_DISPATCH_T(dtype, entropy_loss_single_kernel<T_><<<dim3(1), dim3(1024), 0, s>>>(
+                                   n, target, (const Tr<T_>::elem*)entropy, 2.0f * inv * upstream, inv, d_entropy, (Tr<T_>::elem*)loss));
         return;
     }
     int nblk = (int)((n + 255) / 256);
     if (nblk > 1024) nblk = 1024;
     if (nblk < 1) nblk = 1;
     const float inv_n = 1.0f / (float)n;
-    if (dtype == 0) {
-        entropy_loss_partial_kernel<BF16><<<dim3(nblk), dim3(256), 0, s>>>(n, target, (const unsigned short*)entropy,
-                                                                          2.0f * inv_n * upstream, d_entropy, partial);
-        entropy_loss_final_kernel<BF16><<<dim3(1), dim3(256), 0, s>>>(nblk, inv_n, partial, (unsigned short*)loss);
-    } else {
-        entropy_loss_partial_kernel<F32><<<dim3(nblk), dim3(256), 0, s>>>(n, target, (const float*)entropy,
-                                                                         2.0f * inv_n * upstream, d_entropy, partial);
-        entropy_loss_final_kernel<F32><<<dim3(1), dim3(256), 0, s>>>(nblk, inv_n, partial, (float*)loss);
-    }
+    AECF_DISPATCH_T(dtype, {
+        typedef Tr<T_>::elem el;
+        entropy_loss_partial_kernel<T_><<<dim3(nblk), dim3(256), 0, s>>>(n, target, (const el*)entropy, 2.0f * inv_n * upstream,
+                                                                         d_entropy, partial);
+        entropy_loss_final_kernel<T_><<<dim3(1), dim3(256), 0, s>>>(nblk, inv_n, partial, (el*)loss);
+    });
 }
 
 void launch_sdpa_fwd(int dtype, int64_t B, int S, int T, int E, float scale, const void* q, const void* k, const void* v,
                      void* out, float* probs, hipStream_t s) {
     dim3 grid((unsigned)B), block(256);
-    if (dtype == 0)
-        sdpa_fwd_kernel<BF16><<<grid, block, 0, s>>>(S, T, E, scale, (const unsigned short*)q, (const unsigned short*)k,
-                                                     (const unsigned short*)v, (unsigned short*)out, probs);
-    else
-        sdpa_fwd_kernel<F32><<<grid, block, 0, s>>>(S, T, E, scale, (const float*)q, (const float*)k, (const float*)v,
-                                                    (float*)out, probs);
+    AECF_DISPATCH_T(dtype, {
+        typedef Tr<T_>::elem el;
+        sdpa_fwd_kernel<T_><<<grid, block, 0, s>>>(S, T, E, scale, (const el*)q, (const el*)k, (const el*)v, (el*)out, probs);
+    });
 }
 
 void launch_sdpa_bwd(int dtype, int64_t B, int S, int T, int E, float scale, const void* q, const void* k, const void* v,
                      const float* probs, const void* dout, void* dq, void* dk, void* dv, hipStream_t s) {
     dim3 grid((unsigned)B), block(256);
-    if (dtype == 0)
-        sdpa_bwd_kernel<BF16><<<grid, block, 0, s>>>(S, T, E, scale, (const unsigned short*)q, (const unsigned short*)k,
-                                                     (const unsigned short*)v, probs, (const unsigned short*)dout,
-                                                     (unsigned short*)dq, (unsigned short*)dk, (unsigned short*)dv);
-    else
-        sdpa_bwd_kernel<F32><<<grid, block, 0, s>>>(S, T, E, scale, (const float*)q, (const float*)k, (const float*)v, probs,
-                                                    (const float*)dout, (float*)dq, (float*)dk, (float*)dv);
+    AECF_DISPATCH_T(dtype, {
+        typedef Tr<T_>::elem el;
+        sdpa_bwd_kernel<T_><<<grid, block, 0, s>>>(S, T, E, scale, (const el*)q, (const el*)k, (const el*)v, probs, (const el*)dout,
+                                                   (el*)dq, (el*)dk, (el*)dv);
+    });
 }
 
 }  // namespace aecf

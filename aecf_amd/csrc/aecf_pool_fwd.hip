@@ -396,12 +396,10 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(GateArgs p) {
 void launch_prep_qs(int dtype, const void* w_in, const void* b_in, const void* query, float* qs, int E, float scale,
                     hipStream_t s) {
     dim3 grid((E + 3) / 4), block(256);
-    if (dtype == 0)
-        prep_qs_kernel<BF16><<<grid, block, 0, s>>>((const unsigned short*)w_in, (const unsigned short*)b_in,
-                                                    (const unsigned short*)query, qs, E, scale);
-    else
-        prep_qs_kernel<F32><<<grid, block, 0, s>>>((const float*)w_in, (const float*)b_in, (const float*)query, qs, E,
-                                                   scale);
+    AECF_DISPATCH_T(dtype, {
+        typedef Tr<T_>::elem el;
+        prep_qs_kernel<T_><<<grid, block, 0, s>>>((const el*)w_in, (const el*)b_in, (const el*)query, qs, E, scale);
+    });
 }
 
 void launch_prep_amat(int dtype, const void* w_in, const float* qs, float* a_f32, void* a_hi, void* a_lo, int E, int H,
@@ -410,7 +408,10 @@ void launch_prep_amat(int dtype, const void* w_in, const float* qs, float* a_f32
     if (dtype == 0)
         prep_amat_kernel<BF16><<<grid, block, 0, s>>>((const unsigned short*)w_in, qs, a_f32, (unsigned short*)a_hi,
                                                       (unsigned short*)a_lo, E, H);
-    else
+    else if (dtype == 2)
+        prep_amat_kernel<F16><<<grid, block, 0, s>>>((const unsigned short*)w_in, qs, a_f32, (unsigned short*)a_hi,
+                                                     (unsigned short*)a_lo, E, H);
+    else if (dtype == 1)
         prep_amat_kernel<F32><<<grid, block, 0, s>>>((const float*)w_in, qs, a_f32, (float*)a_hi, (float*)nullptr, E, H);
 }
 
@@ -426,7 +427,13 @@ void launch_prep_all(int dtype, const void* w_in, const void* b_in, const void* 
                                                      (unsigned short*)a_lo, (const unsigned short*)t_src0,
                                                      (unsigned short*)t_dst0, (const unsigned short*)t_src1,
                                                      (unsigned short*)t_dst1, E, H, fj);
-    else
+    else if (dtype == 2)        // (hi + lo copies of A as for bf16; no fragment-major copies: those feed the bf16 engines only)
+        prep_all_kernel<F16><<<grid, block, 0, s>>>((const unsigned short*)w_in, (const unsigned short*)b_in,
+                                                    (const unsigned short*)query, scale, qs, a_f32, (unsigned short*)a_hi,
+                                                    (unsigned short*)a_lo, (const unsigned short*)t_src0,
+                                                    (unsigned short*)t_dst0, (const unsigned short*)t_src1,
+                                                    (unsigned short*)t_dst1, E, H, FragJobs{});
+    else if (dtype == 1)
         prep_all_kernel<F32><<<grid, block, 0, s>>>((const float*)w_in, (const float*)b_in, (const float*)query, scale, qs,
                                                     a_f32, (float*)a_hi, (float*)nullptr, (const float*)t_src0,
                                                     (float*)t_dst0, (const float*)t_src1, (float*)t_dst1, E, H, FragJobs{});
@@ -434,10 +441,10 @@ void launch_prep_all(int dtype, const void* w_in, const void* b_in, const void* 
 
 void launch_transpose(int dtype, const void* src, void* dst, int E, hipStream_t s) {
     dim3 grid((E + 31) / 32, (E + 31) / 32), block(256);
-    if (dtype == 0)
-        transpose_kernel<BF16><<<grid, block, 0, s>>>((const unsigned short*)src, (unsigned short*)dst, E);
-    else
-        transpose_kernel<F32><<<grid, block, 0, s>>>((const float*)src, (float*)dst, E);
+    AECF_DISPATCH_T(dtype, {
+        typedef Tr<T_>::elem el;
+        transpose_kernel<T_><<<grid, block, 0, s>>>((const el*)src, (el*)dst, E);
+    });
 }
 
 // Per-sample statistics from the per-head softmax weights (used when the scores are produced inside the value-projection
@@ -502,24 +509,20 @@ __global__ __launch_bounds__(256) void gate_stats_kernel(GateArgs p) {
 void launch_gate_stats(int dtype, const GateArgs& a, hipStream_t s) {
     dim3 grid((unsigned)((a.B + 255) / 256)), block(256);
     AECF_DISPATCH_M(a.M, {
-        if (dtype == 0) gate_stats_kernel<BF16, M_><<<grid, block, 0, s>>>(a);
-        else gate_stats_kernel<F32, M_><<<grid, block, 0, s>>>(a);
+        AECF_DISPATCH_T(dtype, gate_stats_kernel<T_, M_><<<grid, block, 0, s>>>(a));
     });
 }
 
 void launch_gate_fwd(int dtype, const GateArgs& a, hipStream_t s) {
     // fewer than ~2048 waves of 16 samples (8 per CU): split K over the block's waves instead of the samples
-    const int kstep = dtype == 0 ? 32 : 16;
+    const int kstep = dtype == 1 ? 16 : 32;
     const bool ksplit = (a.B + 15) / 16 < 2048 && a.E % (4 * kstep) == 0;
     dim3 grid((unsigned)(ksplit ? (a.B + 15) / 16 : (a.B + 63) / 64)), block(256);
     AECF_DISPATCH_M(a.M, {
-        if (dtype == 0) {
-            if (ksplit) gate_fwd_kernel<BF16, M_, true><<<grid, block, 0, s>>>(a);
-            else gate_fwd_kernel<BF16, M_, false><<<grid, block, 0, s>>>(a);
-        } else {
-            if (ksplit) gate_fwd_kernel<F32, M_, true><<<grid, block, 0, s>>>(a);
-            else gate_fwd_kernel<F32, M_, false><<<grid, block, 0, s>>>(a);
-        }
+        AECF_DISPATCH_T(dtype, {
+            if (ksplit) gate_fwd_kernel<T_, M_, true><<<grid, block, 0, s>>>(a);
+            else gate_fwd_kernel<T_, M_, false><<<grid, block, 0, s>>>(a);
+        });
     });
 }
 

@@ -42,6 +42,7 @@ __device__ __forceinline__ bool xcd_tile(unsigned int id, unsigned int npanel, u
 template <typename T> struct TileK;   // elements of K per 128-byte LDS row
 template <> struct TileK<BF16> { static constexpr int value = 64; };
 template <> struct TileK<F32> { static constexpr int value = 32; };
+template <> struct TileK<F16> { static constexpr int value = 64; };
 
 // Cooperative register staging of a ROWS x 128 B tile from a row-major source, NT threads.
 // chunk c = tid + NT*i  ->  row = c >> 3, 16-byte chunk = c & 7: 8 consecutive lanes read one full 128-B line.

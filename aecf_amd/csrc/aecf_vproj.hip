@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void vproj_modal_kernel(GemmNtArgs p) {
                 o[rt][ct][r] = v;
             }
     }
-    // ---- stores.  bf16: ONE LDS pass -- image [64 rows][1 + M slots][128 cols] (slot 0 = o, slot 1+m = V_m, the
+    // ---- stores.  bf16 / f16: ONE LDS pass -- image [64 rows][1 + M slots][128 cols] (slot 0 = o, slot 1+m = V_m, the
     //      per-modality products W x_m + bias kept for the backward score gradient), then full-row 16-byte stores.
     if (X::BYTES == 2 && !p.out_f32 && CW == 4) {
         const int nslot = p.v_out ? M_ + 1 : 1;
@@ -125,8 +125,8 @@ __global__ __launch_bounds__(256, 2) void vproj_modal_kernel(GemmNtArgs p) {
             const int col = 64 * wc + 16 * ct + (r16 & ~1);
             const int rowb = 32 * wr + 16 * rt + 4 * lg + (odd ? 2 : 0);
             char* base = cl + slot * 256 + col * 2;
-            *reinterpret_cast<unsigned int*>(base + (rowb + 0) * pitch) = odd ? pack_bf16x2(got0, v2) : pack_bf16x2(v0, got0);
-            *reinterpret_cast<unsigned int*>(base + (rowb + 1) * pitch) = odd ? pack_bf16x2(got1, v3) : pack_bf16x2(v1, got1);
+            *reinterpret_cast<unsigned int*>(base + (rowb + 0) * pitch) = odd ? pack2<T>(got0, v2) : pack2<T>(v0, got0);
+            *reinterpret_cast<unsigned int*>(base + (rowb + 1) * pitch) = odd ? pack2<T>(got1, v3) : pack2<T>(v1, got1);
         };
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
@@ -196,8 +196,7 @@ static void launch_one(const GemmNtArgs& a, hipStream_t s) {
 void launch_vproj(int dtype, const GemmNtArgs& a, hipStream_t s) {
     const bool small = ((a.R + 63) / 64) * (int64_t)((a.N + 127) / 128) < 64;
     AECF_DISPATCH_M(a.M, {
-        if (dtype == 0) { if (small) launch_one<BF16, M_, 1>(a, s); else launch_one<BF16, M_, 4>(a, s); }
-        else { if (small) launch_one<F32, M_, 1>(a, s); else launch_one<F32, M_, 4>(a, s); }
+        AECF_DISPATCH_T(dtype, { if (small) launch_one<T_, M_, 1>(a, s); else launch_one<T_, M_, 4>(a, s); });
     });
 }
 

@@ -23,6 +23,10 @@ from . import _lib
 __all__ = ['CurriculumMasking', 'MultimodalAttentionPool', 'multimodal_attention_pool', 'create_fusion_pool']
 
 _DTYPES = {torch.bfloat16: _lib.AECF_BF16, torch.float32: _lib.AECF_F32}
+# what this module's operators take: the above and float16 (ABI v10).  _DTYPES itself stays bf16 / float32: losses.py and xray.py
+# share it, and their kernels (InfoNCE, the x-ray front-ends) are not built for float16
+_POOL_DTYPES = {**_DTYPES, torch.float16: _lib.AECF_F16}
+_CAST_F32_TO = {torch.bfloat16: "aecf_cast_f32_to_bf16", torch.float16: "aecf_cast_f32_to_f16"}
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -301,7 +305,7 @@ class _PoolFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)       # unused outputs arrive as None, not as zero tensors (fill + cast launches)
         B, M, E = x.shape
         dt = x.dtype
-        desc = _lib.PoolDesc(B, M, E, num_heads, _DTYPES[dt], mask_mode, min_active, base_mask_prob,
+        desc = _lib.PoolDesc(B, M, E, num_heads, _POOL_DTYPES[dt], mask_mode, min_active, base_mask_prob,
                              entropy_target, eps)
         facts = _pool_facts(lib, desc, (B, M, E, num_heads, dt, mask_mode))
         _lib.check(facts[0], "aecf_pool_check")
@@ -455,7 +459,7 @@ class _PoolFunction(torch.autograd.Function):
             _ptr(attn_w), _ptr(probs), _ptr(saved_o), _ptr(saved_v), _ptr(dx), _ptr(dquery), _ptr(dw_in), _ptr(db_in),
             _ptr(dw_out), _ptr(db_out), _ptr(ws), ws_bytes,
             None if opts.stage_events is None else ctypes.addressof(opts.stage_events[1]),
-            _DTYPES[out_dt], 0 if saved_o_lo is None else _lib.AECF_HILO_GRADS, _ptr(saved_prep),
+            _POOL_DTYPES[out_dt], 0 if saved_o_lo is None else _lib.AECF_HILO_GRADS, _ptr(saved_prep),
             None if early is None else early.cuda_event, _ptr(saved_o_lo), float(gscale))
         _lib.check(lib.aecf_pool_backward(ctypes.byref(desc), ctypes.byref(args), _stream()), "aecf_pool_backward")
         flat32 = None
@@ -582,7 +586,7 @@ class _EntropyLossFunction(torch.autograd.Function):
     def forward(ctx, entropy, last_seq_len, entropy_target):
         lib = _lib.load()
         ec = entropy.detach()
-        if ec.dtype not in _DTYPES:
+        if ec.dtype not in _POOL_DTYPES:
             ec = ec.to(torch.float32)
         ec = ec.contiguous()
         n = ec.numel()
@@ -590,7 +594,7 @@ class _EntropyLossFunction(torch.autograd.Function):
         loss = torch.empty(1, dtype=ec.dtype, device=dev)
         dent = torch.empty(ec.shape, dtype=torch.float32, device=dev)
         ws = torch.empty(lib.aecf_entropy_loss_workspace_bytes(n), dtype=torch.uint8, device=dev)
-        _lib.check(lib.aecf_entropy_loss_fwd_bwd(n, _DTYPES[ec.dtype], last_seq_len, entropy_target, _ptr(ec), 1.0,
+        _lib.check(lib.aecf_entropy_loss_fwd_bwd(n, _POOL_DTYPES[ec.dtype], last_seq_len, entropy_target, _ptr(ec), 1.0,
                                                  _ptr(loss), _ptr(dent), _ptr(ws), _stream()),
                    "aecf_entropy_loss_fwd_bwd")
         ctx.save_for_backward(dent)
@@ -617,7 +621,7 @@ class _MhaFunction(torch.autograd.Function):
         S = key.shape[1]
         dt = query.dtype
         dev = query.device
-        desc = _lib.MhaDesc(B, T, S, E, num_heads, _DTYPES[dt], float(drop_p))
+        desc = _lib.MhaDesc(B, T, S, E, num_heads, _POOL_DTYPES[dt], float(drop_p))
         _lib.check(lib.aecf_mha_check(ctypes.byref(desc)), "aecf_mha_check")
         qc, kc, vc = query.detach().contiguous(), key.detach().to(dt).contiguous(), value.detach().to(dt).contiguous()
         w_in_c, w_out_c = w_in.detach().to(dt).contiguous(), w_out.detach().to(dt).contiguous()
@@ -680,7 +684,7 @@ class _SdpaFunction(torch.autograd.Function):
         qc, kc, vc = q.contiguous(), k.to(dt).contiguous(), v.to(dt).contiguous()
         out = torch.empty(B, S, E, dtype=dt, device=q.device)
         probs = torch.empty(B, S, T, dtype=torch.float32, device=q.device)
-        _lib.check(lib.aecf_sdpa_forward(B, S, T, E, _DTYPES[dt], scale, _ptr(qc), _ptr(kc), _ptr(vc), _ptr(out),
+        _lib.check(lib.aecf_sdpa_forward(B, S, T, E, _POOL_DTYPES[dt], scale, _ptr(qc), _ptr(kc), _ptr(vc), _ptr(out),
                                          _ptr(probs), _stream()), "aecf_sdpa_forward")
         ctx.save_for_backward(qc, kc, vc, probs)
         ctx.scale = scale
@@ -695,7 +699,7 @@ class _SdpaFunction(torch.autograd.Function):
         dt = qc.dtype
         do = dout.to(dt).contiguous()
         dq, dk, dv = torch.empty_like(qc), torch.empty_like(kc), torch.empty_like(vc)
-        _lib.check(lib.aecf_sdpa_backward(B, S, T, E, _DTYPES[dt], ctx.scale, _ptr(qc), _ptr(kc), _ptr(vc), _ptr(probs),
+        _lib.check(lib.aecf_sdpa_backward(B, S, T, E, _POOL_DTYPES[dt], ctx.scale, _ptr(qc), _ptr(kc), _ptr(vc), _ptr(probs),
                                           _ptr(do), _ptr(dq), _ptr(dk), _ptr(dv), _stream()), "aecf_sdpa_backward")
         return dq, dk, dv, None
 
@@ -770,7 +774,7 @@ class CurriculumMasking(nn.Module):
         _require_device(entropy, "entropy")
         seq_len = self._last_seq_len if hasattr(self, '_last_seq_len') else 2
         tag = getattr(entropy, "_aecf_entropy_partials", None)
-        if tag is not None and not entropy.requires_grad and entropy.dtype in _DTYPES:
+        if tag is not None and not entropy.requires_grad and entropy.dtype in _POOL_DTYPES:
             # info['entropy'] of a fused pool forward, untouched: the kernel that wrote it left the per-block sums of
             # (nan_to_num(H) - target)^2 behind (aecf_pool_fwd_args.ent_loss_partial) -- one small launch adds them up
             (partial, n, target, ready), version = tag
@@ -782,7 +786,7 @@ class CurriculumMasking(nn.Module):
                 if ready is not None and ready.dtype == entropy.dtype:
                     return ready.reshape(())       # the forward's out-projection launch already added the partials up
                 loss = torch.empty(1, dtype=entropy.dtype, device=entropy.device)
-                _lib.check(_lib.load().aecf_entropy_loss_from_partials(n, _DTYPES[entropy.dtype], _ptr(partial), _ptr(loss),
+                _lib.check(_lib.load().aecf_entropy_loss_from_partials(n, _POOL_DTYPES[entropy.dtype], _ptr(partial), _ptr(loss),
                                                                        _stream()), "aecf_entropy_loss_from_partials")
                 return loss.reshape(())
         return _EntropyLossFunction.apply(entropy, int(seq_len), float(self.entropy_target))
@@ -811,9 +815,9 @@ def _shared_query_base(query: torch.Tensor) -> Optional[torch.Tensor]:
 
 
 def _padded_embed(E: int, H: int, dtype: torch.dtype) -> Optional[Tuple[int, int]]:
-    """(E', head_dim') of the smallest per-head padding the general kernels tile: E' = H * head_dim' a multiple of 64 (bf16) /
-    32 (float32).  None when E already is one."""
-    unit = 64 if dtype == torch.bfloat16 else 32
+    """(E', head_dim') of the smallest per-head padding the general kernels tile: E' = H * head_dim' a multiple of 64 (bf16,
+    float16) / 32 (float32).  None when E already is one."""
+    unit = 32 if dtype == torch.float32 else 64
     if E % H != 0 or E % unit == 0:
         return None
     hd = E // H
@@ -853,10 +857,12 @@ class MultimodalAttentionPool(nn.Module):
     in ``libaecf_hip.so``.
 
     Hot path (the fused kernels): one query shared by the batch (``fusion_query.expand(B, -1, -1)``, tgt_len 1),
-    ``value is key``, optional boolean ``key_padding_mask``, dropout 0, bf16 or fp32.  Every other argument combination
+    ``value is key``, optional boolean ``key_padding_mask``, dropout 0, bf16, fp16 or fp32 (float16 on the LDS-tile kernels of
+    the float32 route; the weight-stationary engines are bf16 only).  Every other argument combination
     ``nn.MultiheadAttention`` takes here (per-sample queries, tgt_len > 1, key != value, attn_mask, float masks, attention
     dropout, embedding sizes the fused kernels do not tile) runs on the general kernels (``_forward_general``); only dtypes
-    other than bfloat16 / float32 raise NotImplementedError.  Nothing is routed to PyTorch.
+    other than bfloat16 / float16 / float32 raise NotImplementedError (and float16 on a data-parallel pool).  Nothing is
+    routed to PyTorch.
 
     ``self.options`` (``PoolOptions``): per-module switches of the fused path; ``aecf_amd.dp.attach(pool)`` makes the module
     data-parallel (gradients pre-scaled by 1 / world, float32 sums kept for the collective).
@@ -927,7 +933,7 @@ class MultimodalAttentionPool(nn.Module):
         reuse = not (self.training and torch.is_grad_enabled()) and not _capturing()
         named = (("w_in", a.in_proj_weight), ("b_in", a.in_proj_bias), ("w_out", a.out_proj.weight), ("b_out", a.out_proj.bias))
         if not reuse:
-            # training: ONE cast launch for the four of them + the query (aecf_cast_f32_to_bf16; one torch launch each was ~22 us
+            # training: ONE cast launch for the four of them + the query (aecf_cast_f32_to_bf16 / _f16; one torch launch each was ~22 us
             # of a 0.7 ms step, and torch's multi-tensor copy takes as long: it hands a block 65536 elements) into fresh
             # allocations (the backward keeps them: a later forward must not write over what an earlier one saved)
             srcs = [p.detach() for _, p in named if p is not None]
@@ -935,12 +941,13 @@ class MultimodalAttentionPool(nn.Module):
             if ride:
                 srcs.append(query.detach())
             dsts = [torch.empty(p.shape, dtype=dt, device=p.device) for p in srcs]
-            if (dt == torch.bfloat16 and all(p.dtype == torch.float32 and p.is_cuda and p.is_contiguous() for p in srcs)):
+            if (dt in _CAST_F32_TO and all(p.dtype == torch.float32 and p.is_cuda and p.is_contiguous() for p in srcs)):
                 n = len(srcs)
                 vp = ctypes.c_void_p
-                _lib.check(_lib.load().aecf_cast_f32_to_bf16(
+                name = _CAST_F32_TO[dt]
+                _lib.check(getattr(_lib.load(), name)(
                     n, (vp * n)(*[p.data_ptr() for p in srcs]), (vp * n)(*[d.data_ptr() for d in dsts]),
-                    (ctypes.c_int64 * n)(*[p.numel() for p in srcs]), _stream()), "aecf_cast_f32_to_bf16")
+                    (ctypes.c_int64 * n)(*[p.numel() for p in srcs]), _stream()), name)
             else:
                 torch._foreach_copy_(dsts, srcs)
             it = iter(dsts)
@@ -1024,8 +1031,11 @@ class MultimodalAttentionPool(nn.Module):
             return self._forward_empty(query, key, tgt_len, src_len, return_info)
         same_kv = (value is key) or (value.data_ptr() == key.data_ptr() and value.shape == key.shape
                                      and value.stride() == key.stride())
-        if key.dtype not in _DTYPES:
-            raise NotImplementedError(f"aecf_amd: dtype {key.dtype} is not supported (bfloat16 / float32 only)")
+        if key.dtype not in _POOL_DTYPES:
+            raise NotImplementedError(f"aecf_amd: dtype {key.dtype} is not supported (bfloat16 / float16 / float32 only)")
+        if self._options().dp is not None and torch.float16 in (key.dtype, self.attention.in_proj_weight.dtype):
+            raise NotImplementedError("aecf_amd: float16 is not supported on a data-parallel pool (dp.attach): "
+                                      "bfloat16 / float32 only")
 
         # to batch-first [B, M, E] / [B, 1, E] (ref: torch activation.py:1453-1463 does the inverse)
         if self.batch_first:
@@ -1039,11 +1049,11 @@ class MultimodalAttentionPool(nn.Module):
         fkey = (batch_size, src_len, embed_dim, self.num_heads, key.dtype, 0)
         facts = _shape_facts.get(fkey)
         if facts is None:
-            facts = _pool_facts(_lib.load(), _lib.PoolDesc(batch_size, src_len, embed_dim, self.num_heads, _DTYPES[key.dtype],
+            facts = _pool_facts(_lib.load(), _lib.PoolDesc(batch_size, src_len, embed_dim, self.num_heads, _POOL_DTYPES[key.dtype],
                                                            0, 1, 0.15, 0.7, 1e-8), fkey)
         fast_ok = facts[0] == 0
         general_ok = fast_ok or _lib.load().aecf_mha_check(ctypes.byref(_lib.MhaDesc(
-            batch_size, tgt_len, src_len, embed_dim, self.num_heads, _DTYPES[key.dtype], 0.0))) == 0
+            batch_size, tgt_len, src_len, embed_dim, self.num_heads, _POOL_DTYPES[key.dtype], 0.0))) == 0
         float_kpm = key_padding_mask is not None and key_padding_mask.is_floating_point()   # additive in torch
         pad_to = None
         if not general_ok:
@@ -1051,7 +1061,7 @@ class MultimodalAttentionPool(nn.Module):
             # zero rows / columns to the next size the general kernels take -- the same function of the inputs
             pad_to = _padded_embed(embed_dim, self.num_heads, key.dtype)
             if pad_to is not None and _lib.load().aecf_mha_check(ctypes.byref(_lib.MhaDesc(
-                    batch_size, tgt_len, src_len, pad_to[0], self.num_heads, _DTYPES[key.dtype], 0.0))) != 0:
+                    batch_size, tgt_len, src_len, pad_to[0], self.num_heads, _POOL_DTYPES[key.dtype], 0.0))) != 0:
                 pad_to = None
         if (q_base is None or not same_kv or attn_mask is not None or dropping or float_kpm
                 or (not fast_ok and general_ok) or pad_to is not None):
@@ -1257,8 +1267,8 @@ def _scaled_dot_product_attention(query: torch.Tensor, key: torch.Tensor, value:
                                   scale: Optional[float] = None) -> torch.Tensor:
     """softmax(Q K^T * scale) V without projections (ref :556-581), HIP kernel."""
     _require_device(query, "query")
-    if query.dtype not in _DTYPES:
-        raise NotImplementedError(f"aecf_amd: dtype {query.dtype} is not supported (bfloat16 / float32 only)")
+    if query.dtype not in _POOL_DTYPES:
+        raise NotImplementedError(f"aecf_amd: dtype {query.dtype} is not supported (bfloat16 / float16 / float32 only)")
     if scale is None:
         scale = query.size(-1) ** -0.5
     return _SdpaFunction.apply(query, key, value, float(scale))

@@ -15,10 +15,12 @@
  *  - every call only enqueues kernels on `stream` (a hipStream_t passed as void*) -- plain launches: a caller that is
  *    capturing `stream` (a whole training step as one HIP graph) gets them as nodes of its own graph.
  *  - return value: AECF_OK (0) or a negative aecf_status.
- *  - dtype: AECF_BF16 or AECF_F32 for x / query / weights / y.  All statistics (attention weights, entropy, mask rate,
- *    saved probabilities) are float32 (optional copies in the activation dtype: aecf_pool_fwd_args.info_*).  Parameter
- *    gradients are float32, or bf16 when aecf_pool_bwd_args.grad_dtype asks for it (bf16 parameters: the float32 batch
- *    sums are rounded once, in the reduction kernel).
+ *  - dtype: AECF_BF16, AECF_F32 or AECF_F16 for x / query / weights / y.  All statistics (attention weights, entropy, mask
+ *    rate, saved probabilities) are float32 (optional copies in the activation dtype: aecf_pool_fwd_args.info_*).  Parameter
+ *    gradients are float32, or bf16 / f16 when aecf_pool_bwd_args.grad_dtype asks for it (16-bit parameters: the float32
+ *    batch sums are rounded once, in the reduction kernel).  AECF_F16 (ABI v10) runs the LDS-tile kernels the float32 path
+ *    runs, on the f16 MFMA; the bf16-only engines (weight-stationary, transposed-read reductions, AECF_HILO_GRADS,
+ *    AECF_PRECISE, InfoNCE, the x-ray front-ends) are not built for it and those entry points answer AECF_ERR_UNSUPPORTED.
  *  - thread-safe and stateless: any thread may call with any stream of the current device; the library keeps nothing between
  *    calls and reads no environment: the kernels a call launches follow from its description and arguments alone.
  */
@@ -32,7 +34,7 @@
 extern "C" {
 #endif
 
-#define AECF_ABI_VERSION 9
+#define AECF_ABI_VERSION 10
 
 typedef enum aecf_status {
     AECF_OK = 0,
@@ -43,7 +45,7 @@ typedef enum aecf_status {
     AECF_ERR_LAUNCH = -5           /* hipGetLastError() != hipSuccess after a launch         */
 } aecf_status;
 
-typedef enum aecf_dtype { AECF_BF16 = 0, AECF_F32 = 1 } aecf_dtype;
+typedef enum aecf_dtype { AECF_BF16 = 0, AECF_F32 = 1, AECF_F16 = 2 /* ABI v10 */ } aecf_dtype;
 
 /* Problem description shared by forward and backward.
  * Replaces: MultimodalAttentionPool.__init__/forward shape contract
@@ -54,7 +56,7 @@ typedef struct aecf_pool_desc {
     int64_t batch;        /* B                                   */
     int32_t modalities;   /* M = src_len, 1..8                    */
     int32_t embed_dim;    /* E, multiple of 64                    */
-    int32_t num_heads;    /* H, 1..16, E % H == 0, (E/H) % 32 == 0 (bf16) or % 16 == 0 (f32) */
+    int32_t num_heads;    /* H, 1..16, E % H == 0, (E/H) % 32 == 0 (bf16, f16) or % 16 == 0 (f32) */
     int32_t dtype;        /* aecf_dtype of x/query/weights/y      */
     /* curriculum masking (ref aecf/AECFLayer.py:76-99); mask_mode 0 = no CurriculumMasking
      * module attached, 1 = training-mode masking (:158-283), 2 = eval-mode (:150-156)      */
@@ -189,8 +191,8 @@ typedef struct aecf_pool_bwd_args {
     void* workspace;
     size_t workspace_bytes;
     void** stage_events;         /* AECF_BWD_STAGES+1 hipEvent_t handles or NULL (profiling hook) */
-    /* element type of the five parameter gradients: AECF_F32, or AECF_BF16 when desc.dtype is AECF_BF16 (the
-     * float32 batch sums are rounded once, in the reduction kernel -- what autograd's cast to a bf16 parameter does) */
+    /* element type of the five parameter gradients: AECF_F32, or AECF_BF16 / AECF_F16 when desc.dtype is that type (the
+     * float32 batch sums are rounded once, in the reduction kernel -- what autograd's cast to a 16-bit parameter does) */
     int32_t grad_dtype;
     int32_t flags;               /* AECF_PRECISE: dy bf16; saved_o, dx and the gradients float32 (see aecf_pool_fwd_args.flags) */
     const void* saved_prep;      /* buffer filled by aecf_pool_forward (see aecf_pool_fwd_args.saved_prep) or NULL */
@@ -222,7 +224,7 @@ size_t aecf_pool_fwd_workspace_bytes(const aecf_pool_desc* d);
 size_t aecf_pool_bwd_workspace_bytes(const aecf_pool_desc* d);
 /* 1 when the backward of this description is faster with the forward's per-modality value projections
  * (aecf_pool_fwd_args.saved_v), 0 when it derives the score gradient from x itself and saved_v should stay NULL
- * (bf16, E in {256, 512}, M <= 4: the forward then writes B*M*E fewer elements) */
+ * (bf16, E in {256, 512}, M <= 4: the forward then writes B*M*E fewer elements; always 1 for f32 and f16) */
 int aecf_pool_wants_saved_v(const aecf_pool_desc* d);
 /* workspace bytes of a call with AECF_PRECISE set (backward == 0: forward) */
 size_t aecf_pool_precise_workspace_bytes(const aecf_pool_desc* d, int backward);
@@ -262,14 +264,14 @@ int aecf_curriculum_mask_backward(int64_t rows, int32_t L, int32_t mode, float e
 size_t aecf_entropy_loss_workspace_bytes(int64_t n);
 /* loss[0] (dtype) = max(sum of the (n + 255) / 256 partial sums aecf_pool_forward left in ent_loss_partial, 0) / n */
 int aecf_entropy_loss_from_partials(int64_t n, int32_t dtype, const float* partial, void* loss, void* stream);
-/* entropy [n] and loss [1] have element type dtype (the reference computes the loss in the dtype of
- * info['entropy']); the arithmetic and d_entropy [n] are float32. */
+/* entropy [n] and loss [1] have element type dtype -- AECF_BF16, AECF_F32 or AECF_F16 (the reference computes the loss in
+ * the dtype of info['entropy']); the arithmetic and d_entropy [n] are float32. */
 int aecf_entropy_loss_fwd_bwd(int64_t n, int32_t dtype, int32_t last_seq_len, float entropy_target,
                               const void* entropy, float upstream, void* loss,
                               float* d_entropy, void* workspace, void* stream);
 
 /* Projection-free single-head attention softmax(Q K^T * scale) V (ref aecf/AECFLayer.py:556-581).
- * q [B,S,E], k,v [B,T,E] dtype; out [B,S,E] dtype; probs [B,S,T] float32 saved for backward. */
+ * q [B,S,E], k,v [B,T,E] dtype (AECF_BF16, AECF_F32 or AECF_F16); out [B,S,E] dtype; probs [B,S,T] float32 saved for backward. */
 int aecf_sdpa_forward(int64_t B, int32_t S, int32_t T, int32_t E, int32_t dtype, float scale,
                       const void* q, const void* k, const void* v, void* out, float* probs,
                       void* stream);
@@ -291,7 +293,7 @@ typedef struct aecf_mha_desc {
     int64_t batch;
     int32_t tgt_len;      /* T */
     int32_t src_len;      /* S */
-    int32_t embed_dim;    /* E <= 1024, multiple of 32 (f32) / 64 (bf16) */
+    int32_t embed_dim;    /* E <= 1024, multiple of 32 (f32) / 64 (bf16, f16) */
     int32_t num_heads;    /* H, any divisor of E */
     int32_t dtype;        /* aecf_dtype of activations and weights */
     float dropout_p;      /* 0 = no dropout (then dropout_uniforms may be NULL) */
@@ -352,7 +354,8 @@ int aecf_mha_backward(const aecf_mha_desc* d, const aecf_mha_bwd_args* a, void* 
  * One pass over one modality's feature rows feat [rows,dim]: rows with drop[r] != 0 are zeroed (the reference's
  * clone + masked write, :173-176) and present[r] = (||row||_2 > 1e-6) of the row AS WRITTEN (the reference's
  * torch.norm(...) > 1e-6 presence test, :202-203).  drop may be NULL (evaluation: presence only); out may equal
- * feat (in place) and may be NULL when drop is NULL (nothing to write).  Norm accumulated in float32. */
+ * feat (in place) and may be NULL when drop is NULL (nothing to write).  Norm accumulated in float32.  dtype: AECF_BF16 or
+ * AECF_F32 (AECF_F16: AECF_ERR_UNSUPPORTED, checked before the pointers; the same for aecf_front_pair). */
 int aecf_modality_frontend(int64_t rows, int32_t dim, int32_t dtype, const void* feat, const uint8_t* drop,
                            void* out, uint8_t* present, void* stream);
 
@@ -394,6 +397,9 @@ int aecf_rows_split(int64_t rows, int64_t row_bytes, const int32_t* route, const
  * `p.to(torch.bfloat16)` does per tensor (ref: the reference trains in one dtype; torch's autocast makes these copies), as one
  * launch of 2048-element blocks.  src[i] / dst[i]: device pointers, numel[i] elements each; host arrays of length n <= 8. */
 int aecf_cast_f32_to_bf16(int32_t n, const float* const* src, void* const* dst, const int64_t* numel, void* stream);
+/* The same for float32 -> IEEE half (ABI v10): round to nearest even, overflow to +-inf, NaN stays NaN -- `p.to(torch.float16)`
+ * bit for bit.  The kernels' own float16 stores use the same conversion. */
+int aecf_cast_f32_to_f16(int32_t n, const float* const* src, void* const* dst, const int64_t* numel, void* stream);
 
 /* ---- the example trainer's optimiser step (ref xrays/train_xrays_example.py:322-323, 376: torch.optim.AdamW) ----
  * AdamW (decoupled weight decay, no amsgrad) over n float32 tensors in one launch per 24 tensors: arrays of n device
