@@ -154,13 +154,18 @@ _attached = {}
 
 
 def attach(pool, group=None, average: bool = True, keep_f32: bool = True, defer_rounding: bool = False, world: Optional[int] = None):
-    """Make ONE ``MultimodalAttentionPool`` data-parallel (explicit, per module).  Its fused backward then
-    (a) multiplies the five parameter gradients by 1 / world as it stores them (``average``; aecf_pool_bwd_args.grad_scale),
-    so ``all_reduce_grads`` / ``GradOverlap`` issue ONE sum collective with no divide launch around it, and
-    (b) with bf16 parameters (``keep_f32``) writes its float32 batch sums: the collective moves and adds THOSE and the bf16
-    gradient is rounded ONCE from the mean -- an N-rank gradient then differs from the one-rank gradient by float32 summation
-    order only.  ``defer_rounding``: the bf16 ``p.grad`` tensors stay UNINITIALISED between the backward and the collective
-    (no cast launch; the caller promises to call ``all_reduce_grads`` / ``GradOverlap.finish`` before reading them).
+    """Make ONE ``MultimodalAttentionPool`` data-parallel (explicit, per module).  Its backward then
+    (a) multiplies the parameter gradients -- and the gradient of a leaf fusion query the call expands -- by 1 / world as it
+    stores them (``average``; aecf_pool_bwd_args.grad_scale on the fused route, the float32 sums before their rounding on the
+    general route), so ``all_reduce_grads`` / ``GradOverlap`` issue ONE sum collective with no divide launch around it; dx and
+    any other query (per-sample, or computed by the caller) are inputs and stay unscaled;
+    (b) on the fused route with bf16 parameters (``keep_f32``) writes its float32 batch sums: the collective moves and adds
+    THOSE and the bf16 gradient is rounded ONCE from the mean -- an N-rank gradient then differs from the one-rank gradient by
+    float32 summation order only.  ``all_reduce_grads`` finds the sums behind any part of that run (the parameters without the
+    query, several pools in one call) and keeps them until every part has been reduced.  ``defer_rounding``: the bf16 ``p.grad``
+    tensors stay UNINITIALISED between the backward and the collective (no cast launch; the caller promises to call
+    ``all_reduce_grads`` / ``GradOverlap.finish`` before reading them; a gradient whose sums are no longer on record is refused,
+    never read).  A backward whose query is computed, or whose parameters already hold gradients, rounds at once instead.
     Until the collective has run, ``p.grad`` holds this rank's gradient divided by world.  ``world`` overrides the group's
     size (rehearsals).  ``detach(pool)`` undoes it.  Returns the module's ``layer.DpState``."""
     from . import layer
@@ -240,6 +245,28 @@ def flat_grad_alias(params: Iterable[torch.nn.Parameter]) -> Optional[torch.Tens
     return torch.empty(0, dtype=g0.dtype, device=g0.device).set_(st, spans[0][0], (off - spans[0][0],))
 
 
+def _kept_sums(g: torch.Tensor, states):
+    """``(run, offset)`` of the float32 sums an attached pool's backward kept behind the gradient ``g``, or None."""
+    for st in states:
+        src = st.sums_of(g)
+        if src is not None:
+            return src
+    return None
+
+
+def _mark_reduced(pieces, sources, states) -> None:
+    """The records of the runs just written follow the write; fully reduced runs are dropped, the rest stay for a later call."""
+    done = {}
+    for g, src in zip(pieces, sources):
+        if src is not None:
+            run, n = done.get(id(src[0]), (src[0], 0))
+            done[id(run)] = (run, n + g.numel())
+    for run, n in done.values():
+        for st in states:
+            if any(r is run for r in st.runs):
+                st.reduced(run, n)
+
+
 def all_reduce_grads(params: Iterable[torch.nn.Parameter], group=None, average: bool = True, fp32: Optional[bool] = None,
                      rehearse: bool = False):
     """One collective for the gradients of ``params``: in place over their shared allocation when they alias one
@@ -258,7 +285,8 @@ def all_reduce_grads(params: Iterable[torch.nn.Parameter], group=None, average: 
         return
     # parameters whose gradients an attached pool's backward already multiplied by 1 / world (the module's own and the leaf
     # fusion queries it has seen: layer.DpState.scaled) go through their own collective, without the divide
-    states = [st for st in _all_states() if st.grad_scale != 1.0]
+    attached = _all_states()
+    states = [st for st in attached if st.grad_scale != 1.0]
     pre = [p for p in params if any(st.is_scaled(p) for st in states)]
     if pre and len(pre) < len(params):
         taken = {id(p) for p in pre}
@@ -266,34 +294,44 @@ def all_reduce_grads(params: Iterable[torch.nn.Parameter], group=None, average: 
         all_reduce_grads([p for p in params if id(p) not in taken], group, average, fp32, rehearse)
         return
     prescaled = bool(pre)
+    for st in states:
+        if any(st.is_scaled(p) for p in pre):
+            st.mixed = False                          # (this is the collective the general route's gradients wait for)
     flat = flat_grad_alias(params)
     reduced = any(p.grad.dtype in (torch.bfloat16, torch.float16) for p in params)
     if fp32 is None:
         fp32 = reduced
-    # the float32 sums the backward kept behind this very run (bf16 parameters, dp.attach(keep_f32=True))
-    wide = None
-    for st in _all_states():
-        w_ = st.take(flat)
-        if w_ is not None:
-            wide = w_
     if prescaled and not average:
         raise RuntimeError("all_reduce_grads(average=False) on gradients an attached pool already divided by world")
     divide = average and not prescaled
+    # where each gradient's float32 sums are: inside a run an attached pool's backward kept (bf16 parameters,
+    # dp.attach(keep_f32=True)) that contains it -- one source for the whole aliased run when there is one, else one per gradient
+    pieces = [flat] if flat is not None else [p.grad for p in params]
+    sources = [_kept_sums(g, attached) for g in pieces]
+    if flat is not None and sources[0] is None:
+        pieces = [p.grad for p in params]
+        sources = [_kept_sums(g, attached) for g in pieces]
+    for g, src in zip(pieces, sources):
+        if src is None and any(st.unwritten(g) for st in attached):
+            raise RuntimeError("all_reduce_grads: a gradient the backward left unwritten (dp.attach(defer_rounding=True)) has no "
+                               "float32 sums on record")
     if fp32 and reduced:
-        if wide is None:
-            wide = flat.float() if flat is not None else torch.cat([p.grad.reshape(-1).float() for p in params])
+        wide = [src[0].flat32[src[1]:src[1] + g.numel()] if src else g.reshape(-1).float() for g, src in zip(pieces, sources)]
+        wide = wide[0] if len(wide) == 1 else torch.cat(wide)
         if divide:
             wide.div_(world)                          # (before the sum, as GradOverlap does: the two paths stay bit-equal)
         dist.all_reduce(wide, op=dist.ReduceOp.SUM, group=group)
-        if flat is not None:
-            flat.copy_(wide)                          # one rounding, in place over the allocation autograd holds
-            return
         off = 0
-        for p in params:
-            n = p.grad.numel()
-            p.grad.copy_(wide[off:off + n].view_as(p.grad))
-            off += n
+        for g in pieces:                              # one rounding, in place over the allocations autograd holds
+            g.copy_(wide[off:off + g.numel()].view_as(g))
+            off += g.numel()
+        _mark_reduced(pieces, sources, attached)
         return
+    if any(src is not None for src in sources):       # gradients on the wire in their own dtype: the kept sums rounded first
+        for g, src in zip(pieces, sources):
+            if src is not None:
+                g.copy_(src[0].flat32[src[1]:src[1] + g.numel()].view_as(g))
+        _mark_reduced(pieces, sources, attached)
     copied = flat is None
     if copied:
         flat = torch.cat([p.grad.reshape(-1).to(params[0].grad.dtype) for p in params])
@@ -377,7 +415,7 @@ class GradOverlap:
         prescaled = state is not None and state.grad_scale != 1.0
         if state is not None:
             if state.runs:
-                state.runs.pop()                             # this call's record: consumed here, not by all_reduce_grads
+                state.runs[-1].hooked = True                 # this call's record: reduced here, not by all_reduce_grads
             if not any(st is state for st in self._fired):
                 self._fired.append(state)
         low = None

@@ -143,31 +143,61 @@ def _device_props(index: int) -> Tuple[int, int]:
     return p
 
 
+class _Run:
+    """One fused backward's gradient run as DpState keeps it: ``flat`` (the allocation autograd holds), ``flat32`` (its float32
+    sums, or None), ``version`` (``flat._version`` when last written by the backward or a collective), ``left`` (elements not yet
+    reduced), ``deferred`` (``flat`` was left uninitialised) and ``hooked`` (a ``dp.GradOverlap`` reduces it)."""
+    __slots__ = ("flat", "flat32", "version", "left", "deferred", "hooked")
+
+    def __init__(self, flat, flat32, deferred):
+        self.flat, self.flat32, self.version, self.left = flat, flat32, flat._version, flat.numel()
+        self.deferred, self.hooked = bool(deferred), False
+
+    def live(self) -> bool:
+        """Nothing but this module's backward and collectives has written ``flat`` since (an accumulation moves its version)."""
+        return self.flat._version == self.version
+
+    def offset_of(self, g: torch.Tensor) -> Optional[int]:
+        """Element offset of ``g`` inside ``flat`` when ``g`` is a contiguous run of it, else None."""
+        f = self.flat
+        if (g.dtype != f.dtype or not g.is_contiguous() or g.device != f.device
+                or g.untyped_storage().data_ptr() != f.untyped_storage().data_ptr()):
+            return None
+        lo = g.storage_offset() - f.storage_offset()
+        return lo if 0 <= lo and lo + g.numel() <= f.numel() else None
+
+
 class DpState:
     """Data-parallel state of ONE pool module (``aecf_amd.dp.attach`` makes it; nothing here is process-global).
 
-    ``grad_scale``: factor the backward folds into the five parameter gradients as it stores them (1 / world: the gradient
-    average is then ONE sum all-reduce, no divide launch).  ``scaled``: the leaf tensors whose gradients carry that factor -- the
-    module's parameters and every leaf fusion query its forward has seen (weak references) -- which is how
-    ``dp.all_reduce_grads`` knows not to divide them again, whatever autograd did with the tensors in between (two pool
-    applications in one backward are summed into fresh allocations).
-    ``keep_f32``: bf16 parameters -- the backward writes its float32 batch sums, the collective averages THOSE and the bf16
+    ``grad_scale``: factor the backward folds into the parameter gradients as it stores them (1 / world: the gradient average is
+    then ONE sum all-reduce, no divide launch), on the fused route and on the general one alike.  ``scaled``: the leaf tensors
+    whose gradients carry that factor -- the module's parameters and every leaf fusion query (a ``[1, 1, E]`` tensor the call
+    expands) its forward has seen (weak references) -- which is how ``dp.all_reduce_grads`` knows not to divide them again,
+    whatever autograd did with the tensors in between.  Any other query (per-sample, or computed by the caller) is an input like
+    ``x``: its gradient is not scaled.
+    ``keep_f32``: bf16 parameters -- the fused backward writes its float32 batch sums, the collective averages THOSE and the bf16
     gradient is rounded once from the mean.  ``defer_rounding``: with ``keep_f32`` the bf16 tensors autograd receives stay
     UNINITIALISED until ``dp.all_reduce_grads`` / ``GradOverlap.finish`` writes the rounded mean into them (no cast launch;
-    reading ``p.grad`` before the collective is an error).  ``hook``: a ``dp.GradOverlap`` while one is active.
-    ``runs``: (flat, flat32, version) of the fused backward calls since the last collective -- where the float32 sums behind a
-    gradient run are found.  The tensors are held (a few MB each, at most 8), so a pointer compared against them cannot have
-    been freed and reused."""
-    __slots__ = ("world", "grad_scale", "keep_f32", "defer_rounding", "hook", "runs", "scaled")
+    reading ``p.grad`` before the collective is an error).  Not when the query is computed (its gradient flows on into whoever
+    made it) or a parameter already holds a gradient (autograd adds into it): those backwards round at once.
+    ``hook``: a ``dp.GradOverlap`` while one is active.
+    ``runs``: ``_Run`` records of the fused backward calls whose gradients are not all reduced yet -- where the float32 sums
+    behind a gradient are found (``sums_of``).  A collective that reduces part of a run uses that part and leaves the record
+    for the rest.  The tensors are held (a few MB each, at most 8), so a pointer compared against them cannot have been freed
+    and reused.
+    ``mixed``: the general route has run for this module since its last collective -- autograd may sum its gradients with a
+    fused backward's inside the engine, before any ``p.grad`` exists, so fused backwards then neither defer nor hook."""
+    __slots__ = ("world", "grad_scale", "keep_f32", "defer_rounding", "hook", "runs", "scaled", "mixed")
 
     def __init__(self, world: int = 1, grad_scale: float = 1.0, keep_f32: bool = True, defer_rounding: bool = False):
         self.world, self.grad_scale, self.keep_f32, self.defer_rounding = int(world), float(grad_scale), bool(keep_f32), bool(defer_rounding)
         self.hook = None
         self.runs = []
         self.scaled = {}                           # id(tensor) -> weak reference (identity, never tensor equality)
+        self.mixed = False
 
     def add_scaled(self, t: torch.Tensor) -> None:
-        import weakref
         if len(self.scaled) > 64:
             self.scaled = {k: r for k, r in self.scaled.items() if r() is not None}
         self.scaled[id(t)] = weakref.ref(t)
@@ -176,23 +206,44 @@ class DpState:
         r = self.scaled.get(id(t))
         return r is not None and r() is t
 
-    def record(self, flat, flat32) -> None:
+    def record(self, flat, flat32, deferred: bool = False) -> _Run:
+        # records something else has written since are dropped; a live deferred run is never the one dropped (a deferring
+        # backward first gives every earlier live run its values, so the last record is the only unwritten one)
+        self.runs = [r for r in self.runs if r.live()]
         if len(self.runs) >= 8:
             del self.runs[1:-1]
-        self.runs.append((flat, flat32, flat._version))
+        run = _Run(flat, flat32, deferred)
+        self.runs.append(run)
+        return run
 
-    def take(self, flat: Optional[torch.Tensor]):
-        """The float32 sums behind the gradient run ``flat`` (as dp.flat_grad_alias returns it), if ``flat`` IS a run one of this
-        module's backward calls wrote since the last collective and nothing has written to it since (an accumulation moves its
-        version counter); else None.  Consumes the records."""
-        runs, self.runs = self.runs, []
-        if flat is None:
-            return None
-        for f, w, version in runs:
-            if (w is not None and f._version == version and f.data_ptr() == flat.data_ptr() and f.numel() == flat.numel()
-                    and f.dtype == flat.dtype):
-                return w
+    def sums_of(self, g: torch.Tensor):
+        """``(run, offset)`` of the float32 sums behind gradient ``g``: a record whose ``flat`` contains ``g`` and that nothing has
+        written to since (an accumulation moves its version counter); else None."""
+        for r in self.runs:
+            if r.flat32 is not None and not r.hooked and r.live():
+                lo = r.offset_of(g)
+                if lo is not None:
+                    return r, lo
         return None
+
+    def unwritten(self, g: torch.Tensor) -> bool:
+        """``g`` lies in a run the backward left uninitialised and no collective has written yet."""
+        return any(r.deferred and r.live() and r.offset_of(g) is not None for r in self.runs)
+
+    def materialize(self) -> None:
+        """Round every unwritten run's float32 sums into it (autograd is about to add to those gradients)."""
+        for r in self.runs:
+            if r.deferred and not r.hooked and r.live():
+                r.flat.copy_(r.flat32)
+                r.version, r.deferred = r.flat._version, False
+
+    def reduced(self, run: _Run, n: int) -> None:
+        """A collective has written ``n`` more elements of ``run``: the record follows the version it gave ``run.flat`` and is
+        dropped once every element is reduced."""
+        run.version = run.flat._version
+        run.left -= n
+        if run.left <= 0:
+            self.runs = [r for r in self.runs if r is not run]
 
 
 class PoolOptions:
@@ -401,8 +452,11 @@ class _PoolFunction(torch.autograd.Function):
         ctx.desc = desc
         ctx.opts = opts
         ctx.q_leaf = bool(q.is_leaf)
-        if opts.dp is not None and q.is_leaf and q.requires_grad:
-            opts.dp.add_scaled(q)                  # its gradient will carry grad_scale (dp.all_reduce_grads asks)
+        if opts.dp is not None:
+            if q.is_leaf and q.requires_grad:
+                opts.dp.add_scaled(q)              # its gradient will carry grad_scale (dp.all_reduce_grads asks)
+            # the tensors whose .grad autograd will add this call's gradients to (a backward may only defer when none holds one)
+            ctx.grad_targets = [weakref.ref(t) for t in (q, w_in, b_in, w_out, b_out) if t is not None and t.is_leaf]
         ctx.bwd_ws_bytes = hilo_ws if saved_o_lo is not None else bwd_ws_bytes
         ctx.q_shape = q.shape
         ctx.param_dtypes = (q.dtype, w_in.dtype, None if b_in is None else b_in.dtype, w_out.dtype,
@@ -448,7 +502,11 @@ class _PoolFunction(torch.autograd.Function):
         dw_in, dw_out = dw_in.view(3 * E, E), dw_out.view(E, E)
         ws_bytes = ctx.bwd_ws_bytes
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        hook, early = (None if dp_ is None else dp_.hook), None
+        needs = ctx.needs_input_grad
+        # a COMPUTED query: dquery flows on into whoever made it, so it must hold finished values when this call returns -- the
+        # run is neither left unwritten nor handed to a side-stream collective that mutates it in place
+        computed_q = needs[1] and not ctx.q_leaf
+        hook, early = (None if (dp_ is None or computed_q or dp_.mixed) else dp_.hook), None
         if hook is not None and any(p is not None and p != gdt for p in ctx.param_dtypes):
             hook = None        # the gradients handed to autograd would be cast COPIES of `flat`: nothing to reduce in place
         if hook is not None:
@@ -468,24 +526,21 @@ class _PoolFunction(torch.autograd.Function):
             # What autograd gets meanwhile: this rank's sums rounded to the parameters' dtype -- unless the collective is certain
             # to overwrite them before anyone may look (GradOverlap's hook is about to mutate flat32 on its side stream, so a cast
             # on this stream would race it; DpState.defer_rounding: the caller promised to call all_reduce_grads): then the
-            # tensors stay uninitialised and the backward has no cast launch at all
+        # tensors stay uninitialised and the backward has no cast launch at all
             flat32 = flat
-            defer = hook is not None or dp_.defer_rounding
-            if defer and hook is None and dp_.runs:
-                # an earlier run of this step is still unreduced and autograd is about to ADD this call's gradients to it (two
-                # pool applications, micro-batches): both get their real values now
-                for f_, w_, v_ in dp_.runs:
-                    if w_ is not None and f_._version == v_:
-                        f_.copy_(w_)
+            defer = hook is not None or (dp_.defer_rounding and not computed_q and not dp_.mixed)
+            if defer and hook is None and (dp_.runs or any(r() is not None and r().grad is not None for r in ctx.grad_targets)):
+                # autograd is about to ADD this call's gradients to gradients already there (two pool applications, micro-batches,
+                # an earlier call on the general route): every earlier run gets its real values now, and so does this one
+                dp_.materialize()
                 defer = False
             flat = torch.empty_like(flat32, dtype=gdt) if defer else flat32.to(gdt)
             dquery, dw_in, db_in, dw_out, db_out = flat.split([E, 3 * E * E, 3 * E, E * E, E])
             dw_in, dw_out = dw_in.view(3 * E, E), dw_out.view(E, E)
         if dp_ is not None:
-            dp_.record(flat, flat32)
+            dp_.record(flat, flat32, flat32 is not None and defer)
         if hook is not None:
             hook(flat, early, flat32, dp_)         # [dquery | dw_in | db_in | dw_out | db_out]: final once `early` has fired
-        needs = ctx.needs_input_grad
         if gscale != 1.0 and not ctx.q_leaf and needs[1]:
             dquery = dquery * (1.0 / gscale)       # a COMPUTED query: its gradient flows on into whoever made it, unscaled like dx
         return (dx if needs[0] else None,
@@ -610,11 +665,13 @@ class _EntropyLossFunction(torch.autograd.Function):
 class _MhaFunction(torch.autograd.Function):
     """aecf_mha_forward / aecf_mha_backward: the general nn.MultiheadAttention case (per-sample queries, tgt_len > 1,
     key != value, attn_mask, key_padding_mask, dropout).  Batch-major [B,T,E] / [B,S,E].  Outputs y [B,T,E] and the
-    head-averaged (post-dropout) weights [B,T,S] float32."""
+    head-averaged (post-dropout) weights [B,T,S] float32.  ``dp``: DpState of a data-parallel module -- the parameter gradients
+    (and the query's, ``scale_query``: an expanded leaf fusion query) come out multiplied by its grad_scale, as on the fused
+    route."""
 
     @staticmethod
     def forward(ctx, query, key, value, w_in, b_in, w_out, b_out, attn_mask, mask_stride, kpm, drop_u, drop_p,
-                num_heads):
+                num_heads, dp=None, scale_query=False):
         lib = _lib.load()
         ctx.set_materialize_grads(False)
         B, T, E = query.shape
@@ -642,6 +699,7 @@ class _MhaFunction(torch.autograd.Function):
         ctx.desc = desc
         ctx.in_dtypes = (key.dtype, value.dtype, w_in.dtype, None if b_in is None else b_in.dtype, w_out.dtype,
                          None if b_out is None else b_out.dtype)
+        ctx.dp, ctx.scale_query = dp, bool(scale_query)
         return y, attn_w
 
     @staticmethod
@@ -664,12 +722,20 @@ class _MhaFunction(torch.autograd.Function):
                                _ptr(daw), _ptr(sq), _ptr(sk), _ptr(sv), _ptr(so), _ptr(probs), _ptr(dq), _ptr(dk),
                                _ptr(dv), _ptr(dw_in), _ptr(db_in), _ptr(dw_out), _ptr(db_out), _ptr(ws), ws_bytes)
         _lib.check(lib.aecf_mha_backward(ctypes.byref(desc), ctypes.byref(args), _stream()), "aecf_mha_backward")
+        dp_ = ctx.dp
+        if dp_ is not None:
+            dp_.materialize()                      # a deferred fused run of this step is about to be added to
+            if dp_.grad_scale != 1.0:
+                # the float32 sums times 1 / world before their one rounding, as the fused backward stores them
+                torch._foreach_mul_([dw_in, db_in, dw_out, db_out], dp_.grad_scale)
+                if ctx.scale_query:
+                    dq.mul_(dp_.grad_scale)
         kd, vd, wid, bid, wod, bod = ctx.in_dtypes
         needs = ctx.needs_input_grad
         return (dq if needs[0] else None, dk.to(kd) if needs[1] else None, dv.to(vd) if needs[2] else None,
                 dw_in.to(wid) if needs[3] else None, db_in.to(bid) if (bid is not None and needs[4]) else None,
                 dw_out.to(wod) if needs[5] else None, db_out.to(bod) if (bod is not None and needs[6]) else None,
-                None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None)
 
 
 class _SdpaFunction(torch.autograd.Function):
@@ -1071,7 +1137,7 @@ class MultimodalAttentionPool(nn.Module):
                 uniforms = _draw_uniforms((global_batch, tgt_len, src_len), key.device, None, generator)[row0:row0 + batch_size]
             return self._forward_general(q_bf, x, value if self.batch_first else value.transpose(0, 1),
                                          key_padding_mask, attn_mask, return_info, batch_size, tgt_len, src_len,
-                                         uniforms, generator, pad_to)
+                                         uniforms, generator, pad_to, q_base)
         kpm = None
         if key_padding_mask is not None:
             if key_padding_mask.shape != (batch_size, src_len):
@@ -1186,10 +1252,12 @@ class MultimodalAttentionPool(nn.Module):
         return (attn_output, info) if return_info else attn_output
 
     def _forward_general(self, q_bf, k_bf, v_bf, key_padding_mask, attn_mask, return_info, batch_size, tgt_len,
-                         src_len, uniforms=None, generator=None, pad_to=None):
+                         src_len, uniforms=None, generator=None, pad_to=None, q_base=None):
         """nn.MultiheadAttention semantics for per-sample queries / tgt_len > 1 / key != value / attn_mask / dropout
         (ref :503-521 -> torch functional.py:5836-5852, 6504-6612), then the curriculum hook exactly as the
-        reference applies it to the pooled weights (ref :526-541)."""
+        reference applies it to the pooled weights (ref :526-541).  On a data-parallel module (dp.attach) the parameter
+        gradients carry grad_scale as on the fused route, and so does the query's when it expands a leaf ``q_base``
+        (``_shared_query_base``); any other query is an input whose gradient is not scaled."""
         dev, dt, H = k_bf.device, k_bf.dtype, self.num_heads
         add_mask, stride = None, 0
         if attn_mask is not None:                                              # torch functional.py:6237-6264
@@ -1226,16 +1294,22 @@ class MultimodalAttentionPool(nn.Module):
         drop_p = float(self.attention.dropout) if (self.attention.dropout > 0.0 and self.training) else 0.0
         drop_u = torch.rand(batch_size * H, tgt_len, src_len, device=dev) if drop_p > 0.0 else None
         a = self.attention
+        st = self._options().dp
+        scale_q = st is not None and q_base is not None and q_base.is_leaf and q_base.requires_grad
+        if scale_q:
+            st.add_scaled(q_base)
+        if st is not None and torch.is_grad_enabled():
+            st.mixed = True
         if pad_to is None:
             y, attn_w = _MhaFunction.apply(q_bf.to(dt), k_bf, v_bf, a.in_proj_weight, a.in_proj_bias, a.out_proj.weight,
-                                           a.out_proj.bias, add_mask, stride, kpm, drop_u, drop_p, H)
+                                           a.out_proj.bias, add_mask, stride, kpm, drop_u, drop_p, H, st, scale_q)
         else:
             E = self.embed_dim
             w_in2, b_in2, w_out2, b_out2 = _pad_heads(a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
                                                       E, H, pad_to)
             wide = lambda t_: torch.nn.functional.pad(t_.to(dt), (0, pad_to[0] - E))
             y, attn_w = _MhaFunction.apply(wide(q_bf), wide(k_bf), wide(v_bf), w_in2, b_in2, w_out2, b_out2, add_mask, stride,
-                                           kpm, drop_u, drop_p, H)
+                                           kpm, drop_u, drop_p, H, st, scale_q)
             y = y[..., :E]
         attn_output = y if self.batch_first else y.transpose(0, 1)
         attn_weights = attn_w.to(dt)                                           # [B,T,S], always batch-major

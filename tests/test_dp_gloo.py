@@ -330,3 +330,91 @@ def test_attached_module_gradients_are_prescaled_and_rounded_once():
         assert scale == 0.5 and fresh and consumed
         assert torch.equal(torch.from_numpy(first), want), rank
         assert torch.equal(torch.from_numpy(second), want2), rank
+
+
+def _deferred_run(pool, st, seed, query=None):
+    """What the fused backward leaves behind under dp.attach(defer_rounding=True): [dquery | dw | db] in ONE bf16 allocation that
+    is NOT written (NaN here, so that a read of it cannot pass), and the float32 sums / world it keeps on record."""
+    n_q = 0 if query is None else query.numel()
+    sums = torch.randn(n_q + 4096, generator=torch.Generator().manual_seed(seed)) * 3.0
+    flat = torch.full((n_q + 4096,), float("nan"), dtype=torch.bfloat16)
+    if query is not None:
+        st.add_scaled(query)
+        query.grad = flat[:n_q].view_as(query)
+    pool.w.grad, pool.b.grad = flat[n_q:n_q + 3840].view(60, 64), flat[n_q + 3840:]
+    st.record(flat, sums * st.grad_scale, deferred=True)
+    return sums
+
+
+def _call_shapes_worker(rank, world, port, q):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        out = {}
+        cat = lambda ps: torch.cat([p.grad.reshape(-1).float() for p in ps])
+        # (a) the pool's parameters without the query (the run starts at dw_in), then the query on its own
+        pool, query = _StandInPool(), torch.nn.Parameter(torch.zeros(1, 1, 128, dtype=torch.bfloat16))
+        st = dp.attach(pool, defer_rounding=True)
+        sums = _deferred_run(pool, st, 300 + rank, query)
+        dp.all_reduce_grads([pool.w, pool.b])
+        dp.all_reduce_grads([query])
+        out["split"] = (sums, cat([query, pool.w, pool.b]), len(st.runs))
+        dp.detach(pool)
+        # (b) two attached pools in one call
+        p1, p2 = _StandInPool(), _StandInPool()
+        s1, s2 = dp.attach(p1, defer_rounding=True), dp.attach(p2, defer_rounding=True)
+        sums = torch.cat([_deferred_run(p1, s1, 400 + rank), _deferred_run(p2, s2, 500 + rank)])
+        dp.all_reduce_grads([p1.w, p1.b, p2.w, p2.b])
+        out["two_pools"] = (sums, cat([p1.w, p1.b, p2.w, p2.b]), len(s1.runs) + len(s2.runs))
+        dp.detach(p1)
+        dp.detach(p2)
+        # (c) an unrelated all_reduce_grads first: it must leave the pool's record alone
+        pool = _StandInPool()
+        st = dp.attach(pool, defer_rounding=True)
+        sums = _deferred_run(pool, st, 600 + rank)
+        lin = torch.nn.Linear(4, 3)
+        lin(torch.ones(2, 4)).sum().backward()
+        dp.all_reduce_grads(list(lin.parameters()))
+        dp.all_reduce_grads([pool.w, pool.b])
+        out["unrelated_first"] = (sums, cat([pool.w, pool.b]), len(st.runs))
+        # (d) a run whose record is gone while it is still unwritten is refused, never read
+        _deferred_run(pool, st, 700 + rank)
+        st.runs[-1].hooked = True                            # (what a GradOverlap collective in flight does to the record)
+        try:
+            dp.all_reduce_grads([pool.w, pool.b])
+            out["refused"] = False
+        except RuntimeError as e:
+            out["refused"] = "unwritten" in str(e)
+        dp.detach(pool)
+        q.put((rank, st.grad_scale, {k: v if isinstance(v, bool) else (v[0].numpy(), v[1].numpy(), v[2])
+                                     for k, v in out.items()}))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(180)
+def test_deferred_gradients_are_reduced_from_their_float32_sums_in_every_call_shape():
+    """dp.attach(defer_rounding=True) leaves the bf16 gradients unwritten until the collective; all_reduce_grads must find the
+    float32 sums behind every gradient it is handed -- a part of a run, runs of two pools in one call, after an unrelated
+    call -- and round the mean once into them; a gradient whose sums are gone is refused, never read."""
+    world = 2
+    port = _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_call_shapes_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted([q.get(timeout=150) for _ in range(world)], key=lambda r: r[0])
+    for p in procs:
+        p.join(30)
+        assert p.exitcode == 0
+    for name in ("split", "two_pools", "unrelated_first"):
+        mean = sum(torch.from_numpy(r[2][name][0]) * r[1] for r in res)
+        want = mean.to(torch.bfloat16).float()
+        for rank, _, out in res:
+            got = torch.from_numpy(out[name][1])
+            assert torch.isfinite(got).all(), (name, rank, "an unwritten gradient was read")
+            assert torch.equal(got, want), (name, rank)
+            assert out[name][2] == 0, (name, rank, "records left behind")
+    assert all(r[2]["refused"] for r in res)

@@ -325,9 +325,10 @@ def test_philox_launch_geometry_matches_torchs_formula(monkeypatch):
         assert (seed, offset, threads, inc) == (2 ** 64 - 3, 40, want_threads, want_inc), n
 
 
-def test_dp_state_records_are_matched_by_identity():
-    """layer.DpState: the float32 sums behind a gradient run are handed out only for THAT run, untouched; which tensors carry the
-    1 / world factor is a matter of object identity (never of tensor equality, never of a storage pointer that may be reused)."""
+def test_dp_state_records_match_any_part_of_their_run():
+    """layer.DpState: the float32 sums behind a gradient are handed out only for a run that contains it, untouched, and a record
+    stays until every part of its run has been reduced (another run's lookup leaves it alone); which tensors carry the 1 / world
+    factor is a matter of object identity (never of tensor equality, never of a storage pointer that may be reused)."""
     from aecf_amd import layer
     st = layer.DpState(world=4, grad_scale=0.25)
     a, b = torch.nn.Parameter(torch.zeros(3)), torch.nn.Parameter(torch.zeros(3))
@@ -335,14 +336,25 @@ def test_dp_state_records_are_matched_by_identity():
     assert st.is_scaled(a) and not st.is_scaled(b)
     flat = torch.zeros(8, dtype=torch.bfloat16)
     wide = torch.ones(8)
-    st.record(flat, wide)
+    run = st.record(flat, wide, deferred=True)
     other = torch.zeros(8, dtype=torch.bfloat16)
-    assert st.take(other) is None and st.runs == []          # somebody else's run: nothing handed out, records consumed
-    st.record(flat, wide)
-    assert st.take(flat) is wide
-    st.record(flat, wide)
+    assert st.sums_of(other) is None and len(st.runs) == 1   # somebody else's run: nothing handed out, the record stays
+    assert not st.unwritten(other) and st.unwritten(flat[2:5])
+    assert st.sums_of(flat) == (run, 0) and st.sums_of(flat[2:5]) == (run, 2)     # the run, or any contiguous part of it
+    assert run.flat32 is wide                                # the kept sums themselves, not a copy
+    assert st.sums_of(flat[::2]) is None and st.sums_of(flat.float()) is None
+    flat[:3].copy_(wide[:3])
+    st.reduced(run, 3)                                       # part of the run reduced: the record stays for the rest
+    assert st.sums_of(flat[3:]) == (run, 3)
+    flat[3:].copy_(wide[3:])
+    st.reduced(run, 5)
+    assert st.runs == [] and not st.unwritten(flat)          # all of it: the record is gone
+    run = st.record(flat, wide, deferred=True)
     flat.add_(1)                                             # autograd accumulated into it: the sums no longer describe it
-    assert st.take(flat) is None
+    assert st.sums_of(flat) is None and not st.unwritten(flat)
+    run = st.record(flat, wide, deferred=True)
+    st.materialize()                                         # autograd is about to add to it: rounded now, sums still valid
+    assert torch.equal(flat, wide.to(torch.bfloat16)) and not st.unwritten(flat) and st.sums_of(flat) == (run, 0)
     for _ in range(20):                                      # bounded: the first run (autograd's accumulation target) + the latest
         st.record(torch.zeros(2), None)
     assert len(st.runs) <= 8
