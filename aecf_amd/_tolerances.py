@@ -15,8 +15,9 @@ BF16_BOUNDS = dict(y=4.0e-3, wbar=4.0e-3, dx=4.5e-3, dquery=5.0e-3, dw_in=5.2e-3
 #                                                      db_in 3.63e-3  dw_out 2.46e-3  db_out 8e-8 (a float32 column sum of dy)
 BF16_F32GRAD_BOUNDS = dict(y=4.2e-3, wbar=4.2e-3, dx=4.5e-3, dq=5.0e-3, dquery=5.0e-3, dw_in=4.4e-3, db_in=4.0e-3, dw_out=3.0e-3,
                            db_out=1e-5)
-#   ... where the hi + lo weight-gradient products are built (bf16, d = 256 / 512, M <= 3: on by themselves for float32-stored
-#   gradients, layer.PoolOptions.hilo_grads; round 5) the three gradients that are sums of products of DERIVED operands meet
-#   north_star's 1e-3 with an order of magnitude to spare: measured 3-5e-6 at the headline shape.  dq / dquery here is the
+#   ... where the hi + lo weight-gradient products are built (bf16, d = 256 / 512 / 768 / 1024, M <= 4, as the weight-stationary
+#   value projection takes them: on by themselves for float32-stored gradients, layer.PoolOptions.hilo_grads) the three gradients
+#   that are sums of products of DERIVED operands meet north_star's 1e-3 with an order of magnitude to spare: measured 3-5e-6 at
+#   the headline shape.  dq / dquery here is the
 #   gradient handed back through a bf16 query tensor (one output rounding) and keeps its bound.
 BF16_F32GRAD_HILO_BOUNDS = dict(BF16_F32GRAD_BOUNDS, dw_in=1e-4, db_in=1e-4, dw_out=1e-4)

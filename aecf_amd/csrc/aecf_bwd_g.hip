@@ -19,6 +19,10 @@
 // The da reduction over E is deterministic (no atomics): the two waves that share a sample tile write their
 // partials to their own LDS slots, and after the next barrier a fixed thread adds them in order into its own
 // (sample, head, m) cell.
+//
+// LO (bf16 DA pass, AECF_HILO_GRADS where dsu_ws_kernel does not take the low part): g_h = W_v,h^T (do_hi + do_lo), the
+// do_lo slice staged beside the do_hi slice and multiplied into the same accumulators -- the score gradient then rests on the
+// exact bf16 W_v and x and a float32-accurate do, so that u (dW_q, dW_k, db_q, dquery) is float32-accurate as well.
 #include "aecf_kernels.h"
 #include "aecf_tile.h"
 
@@ -28,7 +32,7 @@ constexpr int G_SAMPLES = 128;               // samples per block
 constexpr int G_WAVES = 2 * (G_SAMPLES / 16);  // (sample tiles) x (2 row halves)
 constexpr int G_THREADS = 64 * G_WAVES;
 
-template <typename T, int M_, bool DX>
+template <typename T, int M_, bool DX, bool LO = false>
 __global__ __launch_bounds__(G_THREADS) void bwd_g_kernel(BwdGArgs p) {
     using X = Tr<T>;
     typedef typename X::elem elem;
@@ -36,7 +40,8 @@ __global__ __launch_bounds__(G_THREADS) void bwd_g_kernel(BwdGArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ldsA = smem;                               // [128][128 B]  W_v^T rows
     char* ldsB = smem + 128 * TILE_ROW_BYTES;        // [64][128 B]   do rows (samples)
-    float* fl = reinterpret_cast<float*>(smem + (128 + G_SAMPLES) * TILE_ROW_BYTES);
+    char* ldsBl = ldsB + G_SAMPLES * TILE_ROW_BYTES; // LO: [G_SAMPLES][128 B] do_lo rows
+    float* fl = reinterpret_cast<float*>(smem + (128 + (LO ? 2 : 1) * G_SAMPLES) * TILE_ROW_BYTES);
     const int E = p.E, H = p.H, hd = p.hd;
     const int HM = H * M_;
     // DA: fl = da[64][H][M] | slot[2][2][64][M]        DX: fl = probs[64][H][M] | ds[64][H][M] | av[H][128]
@@ -61,6 +66,7 @@ __global__ __launch_bounds__(G_THREADS) void bwd_g_kernel(BwdGArgs p) {
     const int nit = H * nkt;
     const char* wvt = reinterpret_cast<const char*>(p.wvt);
     const char* dob = reinterpret_cast<const char*>(p.dobuf) + b0 * E * X::BYTES;
+    const char* dobl = LO ? reinterpret_cast<const char*>(p.do_lo) + b0 * E * X::BYTES : dob;
     const int64_t ld_bytes = (int64_t)E * X::BYTES;
 
     const int ct = w & (G_SAMPLES / 16 - 1), rh = w / (G_SAMPLES / 16);                           // this wave: samples 16ct.., E-row half rh
@@ -70,6 +76,7 @@ __global__ __launch_bounds__(G_THREADS) void bwd_g_kernel(BwdGArgs p) {
 
     DirectStage<128, G_THREADS> sa;
     DirectStage<G_SAMPLES, G_THREADS> sb;
+    DirectStage<LO ? G_SAMPLES : 8, G_THREADS> sbl;
     int pending_h = -1;                                          // DA: head whose slots wait to be folded into da
 
     // DX with a 2-D grid (few samples: launch_one below): one 128-row block of E per blockIdx.y -- the passes over kb share
@@ -103,6 +110,7 @@ __global__ __launch_bounds__(G_THREADS) void bwd_g_kernel(BwdGArgs p) {
             const int cv = (hd * X::BYTES >= 128) ? 8 : (hd * X::BYTES) / 16;
             sa.load(wvt + (int64_t)(kb * 128) * ld_bytes, ld_bytes, rows_k, cv);
             sb.load(dob, ld_bytes, rows_b, cv);
+            if (LO) sbl.load(dobl, ld_bytes, rows_b, cv);
         }
         f32x4 acc[4][1];
         for (int it = 0; it < nit; ++it) {
@@ -114,6 +122,7 @@ __global__ __launch_bounds__(G_THREADS) void bwd_g_kernel(BwdGArgs p) {
             __syncthreads();
             sa.store(ldsA);
             sb.store(ldsB);
+            if (LO) sbl.store(ldsBl);
             if (DX && it == 0) {                                 // A[h][kb rows] for every head, used by the epilogues
                 for (int i = threadIdx.x; i < H * 128; i += G_THREADS) {
                     const int hh = i >> 7, kk = i & 127;
@@ -136,8 +145,12 @@ __global__ __launch_bounds__(G_THREADS) void bwd_g_kernel(BwdGArgs p) {
                 const int cv = rem >= 128 ? 8 : rem / 16;
                 sa.load(wvt + (int64_t)(kb * 128) * ld_bytes + coff, ld_bytes, rows_k, cv);
                 sb.load(dob + coff, ld_bytes, rows_b, cv);
+                if (LO) sbl.load(dobl + coff, ld_bytes, rows_b, cv);
             }
-            if (wave_on) tile_mma<T, 4, 1>(acc, ldsA, 64 * rh, ldsB, 16 * ct);
+            if (wave_on) {
+                tile_mma<T, 4, 1>(acc, ldsA, 64 * rh, ldsB, 16 * ct);
+                if (LO) tile_mma<T, 4, 1>(acc, ldsA, 64 * rh, ldsBl, 16 * ct);
+            }
             if (kt != nkt - 1) continue;
 
             // ---- g_h tile complete: acc[rt][0][r] = g_h[sample srow][E index krow + 16 rt + r] ----
@@ -229,20 +242,24 @@ __global__ __launch_bounds__(G_THREADS) void bwd_g_kernel(BwdGArgs p) {
     }
 }
 
-template <typename T, int M_, bool DX>
+template <typename T, int M_, bool DX, bool LO = false>
 static void launch_one(const BwdGArgs& a, hipStream_t s) {
     const size_t HM = (size_t)a.H * a.M;
     const size_t floats = DX ? (2 * G_SAMPLES * HM + (size_t)a.H * 128) : (G_SAMPLES * HM + 2 * 2 * G_SAMPLES * (size_t)a.M);
-    const size_t smem = (size_t)(128 + G_SAMPLES) * TILE_ROW_BYTES + floats * sizeof(float);
+    const size_t smem = (size_t)(128 + (LO ? 2 : 1) * G_SAMPLES) * TILE_ROW_BYTES + floats * sizeof(float);
     dim3 grid((unsigned)((a.B + G_SAMPLES - 1) / G_SAMPLES)), block(G_THREADS);
     if (DX && grid.x < 64) grid.y = (unsigned)((a.E + 127) / 128);       // a few hundred samples: spread the E blocks too
-    auto kern = bwd_g_kernel<T, M_, DX>;
+    auto kern = bwd_g_kernel<T, M_, DX, LO>;
     if (smem > 64 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     kern<<<grid, block, smem, s>>>(a);
 }
 
 void launch_bwd_g(int dtype, const BwdGArgs& a, bool dx, hipStream_t s) {
+    if (!dx && a.do_lo && dtype == 0) {                      // bf16, AECF_HILO_GRADS: g from do_hi + do_lo
+        AECF_DISPATCH_M(a.M, { launch_one<BF16, M_, false, true>(a, s); });
+        return;
+    }
     AECF_DISPATCH_M(a.M, {
         AECF_DISPATCH_T(dtype, { if (dx) launch_one<T_, M_, true>(a, s); else launch_one<T_, M_, false>(a, s); });
     });

@@ -232,22 +232,20 @@ int aecf_pool_wants_saved_v(const aecf_pool_desc* d) {
     return 1;
 }
 
-// AECF_HILO_GRADS is built for the bf16 shapes whose value projection runs on the weight-stationary kernel in its
-// per-sample form (the kernels that can write the low part of o and of do)
+// AECF_HILO_GRADS is built for the bf16 shapes whose value projection runs on the weight-stationary kernel (E = 256, 512, 768,
+// 1024; M <= 4, hd % 32 == 0): per-sample and flat-row forms both write the low part of o, the plain form that of do
 static bool hilo_supported(const aecf_pool_desc* d) {
-    if (aecf_pool_check(d) != AECF_OK || d->dtype != AECF_BF16) return false;
+    if (aecf_pool_check(d) != AECF_OK || d->dtype != AECF_BF16 || !ws_frag_shape(d->dtype, d->embed_dim)) return false;
     GemmNtArgs v;
     v.a = nullptr; v.w = nullptr; v.bias = nullptr; v.c = nullptr; v.probs = nullptr; v.R = d->batch; v.N = d->embed_dim;
     v.K = d->embed_dim; v.lda = (int64_t)d->modalities * d->embed_dim; v.M = d->modalities; v.H = d->num_heads;
     v.hd = d->embed_dim / d->num_heads; v.pooled = 1; v.out_f32 = 0; v.v_out = nullptr;
     if (!gemm_ws_supported(v)) return false;
-    if (d->modalities == 4 && d->embed_dim > 512) return false;         // (the flat-row form has no per-sample o in a lane)
     GemmNtArgs y = v;
     y.pooled = 0; y.M = 1; y.lda = d->embed_dim;
     if (!gemm_ws_supported(y)) return false;
-    BwdGArgs g;                                                         // ... and the score gradient on dsu_ws_kernel (do_hi + do_lo)
-    g.B = d->batch; g.M = d->modalities; g.E = d->embed_dim; g.H = d->num_heads; g.hd = d->embed_dim / d->num_heads;
-    if (dsu_ws_chunks(g) <= 0) return false;
+    // (the score gradient from do_hi + do_lo: dsu_ws_kernel where it has room for the low tiles, else bwd_g_kernel's recompute
+    //  pass -- any shape: pool_backward_on)
     GemmTnArgs t;                                                       // ... and the two batch reductions on hi + lo tiles in one launch each
     t.lhs = t.rhs = nullptr; t.probs = nullptr; t.dsbuf = nullptr; t.out = nullptr; t.colsum = nullptr; t.u = nullptr;
     t.B = d->batch; t.M = d->modalities; t.E = d->embed_dim; t.H = d->num_heads; t.hd = d->embed_dim / d->num_heads; t.Ej = 0;
@@ -525,11 +523,15 @@ int pool_backward_on(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, hipSt
     if (frag) g2.wvt_frag = pb + P.wvt_frag;
     // score gradient.  bf16 shapes of the head-split weight-stationary kernel: ds AND u = ds^T x in one pass over (do, x),
     // nothing saved by the forward; otherwise from the saved V (memory-bound dot), else by recomputing W_v^T do per head
+    // AECF_HILO_GRADS: from do_hi + do_lo -- on the head-split kernel where it holds the low tiles too, else on the recompute
+    // pass (exact bf16 W_v and x, float32 accumulation); never from the saved V, which is rounded to bf16
     int dsu_chunks = 0;
-    if (hilo) g2.do_lo = ws + L.do_lo;                // (read by dsu_ws_kernel only: other shapes keep the default key-side accuracy)
-    if (d->dtype == AECF_BF16 && dsu_ws_chunks(g2) > 0 && dsu_ws_chunks(g2) <= L.u_splits_cap)
+    if (hilo) g2.do_lo = ws + L.do_lo;
+    const bool dsu = d->dtype == AECF_BF16 && dsu_ws_chunks(g2) > 0 && dsu_ws_chunks(g2) <= L.u_splits_cap &&
+                     (!hilo || dsu_ws_takes_lo(g2));
+    if (dsu)
         dsu_chunks = launch_dsu_ws(g2, (float*)(ws + L.u_slab), s);
-    else if (!(a->saved_v && launch_dscore_v(d->dtype, g2, a->saved_v, s)))
+    else if (!(!hilo && a->saved_v && launch_dscore_v(d->dtype, g2, a->saved_v, s)))
         launch_bwd_g(d->dtype, g2, false, s);
     mark(ev, 4, s);
 

@@ -179,30 +179,47 @@ __global__ __launch_bounds__(512, 4) void gemm_tn_hilo_pooled_kernel(GemmTnArgs 
             load_probs(base + HRB);
         }
         const f32x2* plc = pl + prow * (MAXS * M_);
-        f32x2 xv[M_][4];
+        // this step's x chunks, before load_x refills Rb: unpacked to float32 pairs -- or, M = 4 (LAZY), kept packed and unpacked
+        // in the slot loop, which holds the kernel to its 128 VGPRs (the unpacked copy spilled there)
+        constexpr bool LAZY = M_ >= 4;
+        f32x2 xv[LAZY ? 1 : M_][4];
+        u32x4 Rc[LAZY ? M_ : 1];
+        if constexpr (LAZY) {
 #pragma unroll
-        for (int m = 0; m < M_; ++m)
+            for (int m = 0; m < M_; ++m) {
+                Rc[m] = Rb[m];
+                asm volatile("" : "+v"(Rc[m]));
+            }
+        } else {
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                xv[m][i] = f32x2{__uint_as_float(Rb[m][i] << 16), __uint_as_float(Rb[m][i] & 0xffff0000u)};
+            for (int m = 0; m < M_; ++m)
 #pragma unroll
-        for (int m = 0; m < M_; ++m)
+                for (int i = 0; i < 4; ++i)
+                    xv[m][i] = f32x2{__uint_as_float(Rb[m][i] << 16), __uint_as_float(Rb[m][i] & 0xffff0000u)};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(xv[m][i]));
+            for (int m = 0; m < M_; ++m)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(xv[m][i]));
+        }
+        auto xat = [&](int m, int i) -> f32x2 {
+            if constexpr (LAZY) return f32x2{__uint_as_float(Rc[m][i] << 16), __uint_as_float(Rc[m][i] & 0xffff0000u)};
+            else return xv[m][i];
+        };
         if (more) load_x(base + HRB);
         const int woff = tr_off(prow, pc);
-#pragma unroll
+        constexpr int SL_UNROLL = LAZY ? 1 : MAXS;                 // (M = 4: the slots one after the other, for the same reason)
+#pragma unroll SL_UNROLL
         for (int sl = 0; sl < MAXS; ++sl) {
             if (MAXS > 2 && sl >= nslots) continue;       // (two slots: straight-line code, a missing slot has zero probabilities)
             f32x2 pv[4];
             const f32x2 p0 = plc[sl * M_];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) pv[i] = xv[0][i] * p0;
+            for (int i = 0; i < 4; ++i) pv[i] = xat(0, i) * p0;
 #pragma unroll
             for (int m = 1; m < M_; ++m) {
                 const f32x2 pm_ = plc[sl * M_ + m];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) pv[i] = __builtin_elementwise_fma(xv[m][i], pm_, pv[i]);
+                for (int i = 0; i < 4; ++i) pv[i] = __builtin_elementwise_fma(xat(m, i), pm_, pv[i]);
             }
             u32x4 oh, ol;
 #pragma unroll
@@ -421,9 +438,9 @@ int hilo_slots_128(int E, int hd) {               // head slots of the widest al
 }  // namespace
 
 // shapes of the one-launch hi + lo products: E a multiple of 128 (128 x 128 block tiles), at most 4 head slots per 128 rows,
-// M <= 3 (the 128-VGPR budget of the pooled kernel), rows_per_split a multiple of 32
+// M <= 4 (a pooled step's probabilities: 32 rows x 4 slots x M <= 512 threads), rows_per_split a multiple of 32
 bool gemm_tn_hilo_supported(const GemmTnArgs& a) {               // (the plain product needs rhs_lo at launch, the pooled one lhs_lo)
-    if (a.E % 128 != 0 || a.M < 1 || a.M > 3 || (a.Ej > 0 && a.Ej != a.E) || a.rows_per_split % HRB != 0) return false;
+    if (a.E % 128 != 0 || a.M < 1 || a.M > 4 || (a.Ej > 0 && a.Ej != a.E) || a.rows_per_split % HRB != 0) return false;
     return !a.pooled || hilo_slots_128(a.E, a.hd) != 0;
 }
 
@@ -443,7 +460,8 @@ void launch_gemm_tn_hilo(const GemmTnArgs& a, hipStream_t s) {
     switch (a.M) {
         case 1: if (two128) launch_hilo_pooled<1, 2>(a, s); else launch_hilo_pooled<1, 4>(a, s); return;
         case 2: if (two128) launch_hilo_pooled<2, 2>(a, s); else launch_hilo_pooled<2, 4>(a, s); return;
-        default: if (two128) launch_hilo_pooled<3, 2>(a, s); else launch_hilo_pooled<3, 4>(a, s); return;
+        case 3: if (two128) launch_hilo_pooled<3, 2>(a, s); else launch_hilo_pooled<3, 4>(a, s); return;
+        default: if (two128) launch_hilo_pooled<4, 2>(a, s); else launch_hilo_pooled<4, 4>(a, s); return;
     }
 }
 

@@ -15,7 +15,8 @@
 //                o[b,n] = sum_m probs[b, head(n), m] V[b,m,n]
 //         VFLAT  the same result for M = 4 when 16 samples x M rows x K do not fit LDS twice (K = 768 / 1024): the
 //                (b,m) rows are walked as PLAIN rows (32 per step = 8 samples), a lane holds ONE (b,m) row, so its
-//                softmax weight is a per-lane scalar and o is a sum over the 4 lanes of a quad (two xor shuffles)
+//                softmax weight is a per-lane scalar and o is a sum over the 4 lanes of a quad (two xor shuffles);
+//                the low part of o (c_lo, AECF_HILO_GRADS) is taken from that float32 sum like everywhere else
 // One barrier per step; LDS tile rows are K*2 bytes with the 16-byte chunk index XOR-ed with the MFMA column index
 // (bank-conflict-free ds_read_b128; the DMA destination is lane-linear, so the XOR is applied to the source address).
 #include <stdlib.h>
@@ -423,8 +424,10 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(GemmNtArgs p, int rows_
                         a += __shfl_xor(a, 2, 64);
                         ow[j] = a;
                     }
-                    if ((r16 & 3) == 0 && row < o_end)
+                    if ((r16 & 3) == 0 && row < o_end) {
                         store_cols<CT>(reinterpret_cast<unsigned short*>(p.c) + (row / M_) * N + ncol0 + NV * lg, ow);
+                        if (p.c_lo) store_cols_lo<CT>(reinterpret_cast<unsigned short*>(p.c_lo) + (row / M_) * N + ncol0 + NV * lg, ow);
+                    }
                 }
             }
         } else {
@@ -1010,14 +1013,20 @@ __global__ __launch_bounds__(512, 2) void dsu_ws_kernel(BwdGArgs p, float* __res
 // every wave runs the softmax backward for all heads -- measured level with it, 118 against 113-120 us,
 // profiles/r04_c2_dsu_slab_ablation.txt; it left the product library in round 5: tools/micro/variants/aecf_gemm_ws_ablations.hip in git history at 14eca16292f5.)
 
+// LDS bytes of dsu_ws_kernel at a shape it takes (JB = 256 columns j per block), with or without the do_lo tiles
+static size_t dsu_ws_smem(int E, int M, int hd, bool lo) {
+    constexpr int JB = 256;
+    const int xrows = 16 * M, zrows = (32 * ((xrows + 31) / 32) - xrows) > 0 ? 1 : 0, hbl = JB / hd;
+    return (size_t)(2 * xrows + zrows) * 2 * E + (size_t)(lo ? 4 : 2) * 16 * 2 * JB + (size_t)8 * (16 * hbl * M) * 4 +
+           (size_t)2 * 16 * 72 * 2;
+}
+
 template <int KT, int KJ, int HK, int M_>
 int launch_dsu_t(const BwdGArgs& a, float* u_slab, hipStream_t s) {
-    constexpr int E = 32 * KT, JB = 32 * KJ, HBL = KJ / HK;
-    constexpr int XROWS = 16 * M_, ZROWS = (32 * ((XROWS + 31) / 32) - XROWS) > 0 ? 1 : 0;
-    const size_t smem_base = (size_t)(2 * XROWS + ZROWS) * 2 * E + (size_t)2 * 16 * 2 * JB + (size_t)8 * (16 * HBL * M_) * 4 +
-                             (size_t)2 * 16 * 72 * 2;
-    const bool hilo = a.do_lo && smem_base + (size_t)2 * 16 * 2 * JB <= 160 * 1024;      // (else: the default key-side accuracy)
-    const size_t smem = smem_base + (hilo ? (size_t)2 * 16 * 2 * JB : 0);
+    constexpr int E = 32 * KT, JB = 32 * KJ;
+    static_assert(JB == 256, "dsu_ws_smem");
+    const bool hilo = a.do_lo && dsu_ws_takes_lo(a);             // (else: the default key-side accuracy)
+    const size_t smem = dsu_ws_smem(E, M_, a.hd, hilo);
     const int groups = E / JB;
     int64_t chunks = 256 / groups;
     if (chunks < 1) chunks = 1;
@@ -1405,16 +1414,19 @@ int dsu_ws_chunks(const BwdGArgs& a) {
     if (jb % a.hd != 0) return 0;
     const int hk = a.hd / 32;
     if (hk != 1 && hk != 2 && hk != 4 && hk != 8) return 0;
-    {   // LDS: two x tiles + K-padding page + two do tiles + partial dots + ds operand arrays
-        const int xrows = 16 * a.M, zrows = (32 * ((xrows + 31) / 32) - xrows) > 0 ? 1 : 0, hbl = jb / a.hd;
-        const size_t smem = (size_t)(2 * xrows + zrows) * 2 * a.E + (size_t)2 * 16 * 2 * jb + (size_t)8 * (16 * hbl * a.M) * 4 + 4608;
-        if (smem > 160 * 1024) return 0;
-    }
+    // LDS: two x tiles + K-padding page + two do tiles + partial dots + ds operand arrays
+    if (dsu_ws_smem(a.E, a.M, a.hd, false) > 160 * 1024) return 0;
     const int groups = a.E / jb;
     int64_t chunks = 256 / groups;
     int64_t rpb = (a.B + chunks - 1) / chunks;
     rpb = (rpb + 15) / 16 * 16;
     return (int)((a.B + rpb - 1) / rpb);
+}
+
+// AECF_HILO_GRADS: the kernel also has room for two do_lo tiles (P from do_hi + do_lo).  Where it has not (E = 512, M = 4) the
+// caller forms the score gradient on bwd_g_kernel's recompute pass from do_hi + do_lo instead (aecf_capi.hip)
+bool dsu_ws_takes_lo(const BwdGArgs& a) {
+    return dsu_ws_chunks(a) > 0 && dsu_ws_smem(a.E, a.M, a.hd, true) <= 160 * 1024;
 }
 
 template <int KT, int HK>

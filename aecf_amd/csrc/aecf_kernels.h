@@ -136,6 +136,7 @@ bool launch_dx_ws(const BwdGArgs& a, hipStream_t s);
 // (aecf_gemm_ws.hip: dsu_ws_kernel).  dsu_ws_chunks: number of [H, E] u slabs it will write (0 = shape not taken)
 int dsu_ws_chunks(const BwdGArgs& a);
 int launch_dsu_ws(const BwdGArgs& a, float* u_slab, hipStream_t s);        // bf16 dx on the weight-stationary engine (aecf_gemm_ws.hip)
+bool dsu_ws_takes_lo(const BwdGArgs& a);     // AECF_HILO_GRADS: dsu_ws_kernel forms P from do_hi + do_lo at this shape
 
 // out[split][j][k] = sum_{b in split} lhs[b][j] * rhs(b,k)        (f32 partial slabs, deterministic)
 //   pooled == 0: rhs(b,k) = rhs[b*E + k]

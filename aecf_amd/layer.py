@@ -253,8 +253,10 @@ class PoolOptions:
     ``hilo_grads``: the weight-gradient products of the backward on bf16 hi + lo operand pairs (AECF_HILO_GRADS,
     include/aecf_hip.h) -- None (default) = whenever the parameter gradients are float32-STORED under bf16 activations (float32
     master weights: there the operand roundings of the default products are visible, 1.3e-3 .. 2.3e-3 of fp32 math at the
-    headline shape; a bf16-stored gradient hides them behind its own rounding), True / False = forced.  Shapes the flag is not
-    built for run the default products.
+    headline shape; a bf16-stored gradient hides them behind its own rounding), True / False = forced.  Built for every bf16
+    shape whose value projection runs on the weight-stationary engine: d = 256, 512, 768, 1024 with M <= 4 and head_dim % 32
+    == 0 (``aecf_pool_hilo_bwd_workspace_bytes > 0``); there the forward keeps no per-modality V.  Other shapes (M = 5..8,
+    d = 1024 at M = 3, other d) run the default products.
     ``draw_in_kernel``: the curriculum mask's uniforms are drawn by the statistics kernel (no torch.rand launch, no [B, M]
     tensor).  ``share_prep``: the forward's preparation launch also produces what the backward derives from the parameters
     alone.  ``stage_events``: (forward, backward) arrays of hipEvent_t the library records at its stage boundaries (bench.py).
@@ -378,9 +380,14 @@ class _PoolFunction(torch.autograd.Function):
         attn_w = torch.empty(B, M, dtype=torch.float32, device=dev)
         probs = torch.empty(B, num_heads, M, dtype=torch.float32, device=dev)
         saved_o = torch.empty(B, E, dtype=dt, device=dev)
-        # per-modality value projections, kept only when a backward will follow (B*M*E elements)
         need_bwd = any(t is not None and t.requires_grad for t in (x, q, w_in, b_in, w_out, b_out))
-        saved_v = torch.empty(B, M, E, dtype=dt, device=dev) if (need_bwd and wants_v) else None
+        hilo = opts.hilo_grads
+        if hilo is None:                           # automatic: the parameter gradients will be STORED in float32 (layer.PoolOptions)
+            hilo = any(t is not None and t.dtype != dt for t in (q, w_in, b_in, w_out, b_out))
+        hilo = bool(hilo and need_bwd and dt == torch.bfloat16 and hilo_bytes > 0)
+        # per-modality value projections, kept only when a backward will follow (B*M*E elements) that reads them: a hi/lo
+        # backward forms its score gradient from x and the exact W_v instead (include/aecf_hip.h, AECF_HILO_GRADS)
+        saved_v = torch.empty(B, M, E, dtype=dt, device=dev) if (need_bwd and wants_v and not hilo) else None
         # what the backward derives from the parameters alone is produced by the forward's preparation launch
         saved_prep = torch.empty(prep_bytes, dtype=torch.uint8, device=dev) if (need_bwd and opts.share_prep) else None
         prep_ready = False
@@ -424,10 +431,7 @@ class _PoolFunction(torch.autograd.Function):
         flags = 0
         saved_o_lo = None
         hilo_ws = 0
-        hilo = opts.hilo_grads
-        if hilo is None:                           # automatic: the parameter gradients will be STORED in float32 (layer.PoolOptions)
-            hilo = any(t is not None and t.dtype != dt for t in (q, w_in, b_in, w_out, b_out))
-        if hilo and need_bwd and dt == torch.bfloat16 and hilo_bytes > 0:
+        if hilo:
             hilo_ws = hilo_bytes
             saved_o_lo = torch.empty(B, E, dtype=dt, device=dev)
             flags |= _lib.AECF_HILO_GRADS

@@ -158,7 +158,12 @@ typedef struct aecf_pool_fwd_args {
  * aecf_gemm_tn_hilo.hip: hi and lo tiles of a step side by side in LDS, one accumulator set, one slab set); the backward
  * workspace is the larger aecf_pool_hilo_bwd_workspace_bytes (do_lo).  The Python layer sets it by itself whenever the parameter
  * gradients are float32-stored (float32 master weights under bf16 activations); with bf16 parameters the gradient's own
- * rounding (2^-9) hides what the flag buys. */
+ * rounding (2^-9) hides what the flag buys.  Built for every bf16 shape whose value projection runs on the weight-stationary
+ * kernel: E in {256, 512, 768, 1024}, M <= 4, head_dim % 32 == 0 (not E = 1024 with M = 3); M = 5..8, other E, float16 and
+ * float32 return AECF_ERR_UNSUPPORTED.  The key-side term comes from do_hi + do_lo on the head-split score-gradient kernel where
+ * it has room for the low tiles (E = 256 / 512, M <= 3; E = 256, M = 4), else on the recompute pass (W_v^T do per head from the
+ * exact bf16 W_v, float32 accumulation) -- never from saved_v, whose elements are rounded to bf16: with the flag the backward
+ * does not read saved_v, and the forward may be given NULL there. */
 #define AECF_HILO_GRADS 4
 /* AECF_PREP_READY (forward only, with saved_prep; ABI v9): saved_prep already holds the preparation an earlier forward made from
  * these very parameters and this query (same embed_dim / num_heads / dtype; the batch may differ): the preparation launch is
@@ -181,7 +186,8 @@ typedef struct aecf_pool_bwd_args {
     const float* attn_w;         /* [B,M] forward output (needed with d_entropy)         */
     const float* saved_probs;    /* [B,H,M]                                              */
     const void* saved_o;         /* [B,E]                                                */
-    const void* saved_v;         /* [B,M,E] or NULL (NULL: the score gradient recomputes W_v^T do per head)  */
+    const void* saved_v;         /* [B,M,E] or NULL (NULL: the score gradient recomputes W_v^T do per head;
+                                  * not read with AECF_HILO_GRADS) */
     void* dx;                    /* [B,M,E] dtype                                        */
     void* dquery;                /* [E]     grad_dtype                                   */
     void* dw_in;                 /* [3E,E]  grad_dtype                                   */
