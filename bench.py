@@ -25,6 +25,11 @@ a fixed, seeded sample of the rows of batch-major outputs where the whole batch 
 settle steps are counted, not clocked, under this flag, so two builds run with the same arguments can be compared output
 for output.
 
+A plain run does what the headline figure needs and nothing more: it sets up, settles and warms up, times the K steps, writes
+the outputs (--dump-outputs) and prints the line.  `--full` adds, after the timed steps and each in passes of its own, the
+per-stage HIP-event times and the roofline, the collective alone, the strong-scaling point of N > 1, the InfoNCE kernels'
+pass (--contrastive) and the CPU baseline on the host; without it those fields of the line are null.
+
 `python bench.py --gpus N` without a launcher starts the N ranks itself (child processes, started before this process
 touches the GPU) and relays rank 0's JSON line; under torch.distributed.run (WORLD_SIZE set) it is one of the ranks.
 """
@@ -460,6 +465,7 @@ def bench_c4(args):
                      "device->host read of the routing counts; host_enqueue_ms ~ ms_per_step means the GPU waits for the host"),
             "cpu_baseline": None,
             "dump_outputs": dumped,
+            "full": args.full,
         }
         emit(line)
     if world > 1:
@@ -499,7 +505,12 @@ def main():
                     help="N>1: weak = B per GPU fixed (default), strong = the config's B is the GLOBAL batch, sharded")
     ap.add_argument("--contrastive", action="store_true",
                     help="configs[2]: add the symmetric InfoNCE against 65536 gathered keys (+ entropy loss) to the step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need, each in passes of its own: "
+                         "per-stage HIP-event times and the roofline, the collective alone (N > 1 / --force-dp), the "
+                         "strong-scaling point (N > 1, weak scaling), the InfoNCE kernels (--contrastive) and the CPU baseline; "
+                         "default: set up, warm up, time the K steps, dump (--dump-outputs) and print the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU-baseline leg out")
     ap.add_argument("--hilo", action="store_true",
                     help="AECF_HILO_GRADS: weight-gradient products on bf16 hi + lo operand pairs (float32-accurate parameter "
                          "gradients; a verification / high-accuracy mode, timed for the record)")
@@ -518,7 +529,7 @@ def main():
                     help="N>1 weak scaling: do not attempt the graph-captured form of the strong-scaling point")
     ap.add_argument("--rows", type=int, default=0,
                     help="pool configurations: rows per GPU instead of the config's batch (strong-scaling shards on one GPU)")
-    ap.add_argument("--cpu-baseline-seconds", type=float, default=30.0, help="budget of the CPU-oracle leg")
+    ap.add_argument("--cpu-baseline-seconds", type=float, default=30.0, help="--full: budget of the CPU-oracle leg")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one handed its caller (output, info, loss, gradients) as "
                          "DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed sample of the rows of batch-major outputs); "
@@ -707,24 +718,27 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, median_ms = float(tt[0].item()), float(tt[1].item())
 
+    # Everything from here to the line is --full only: passes of their own after the timed region, none of which the headline
+    # figure needs.  A plain run reports null for them (stage_ms, stage_pass, roofline, collective_ms, strong_scaling, cpu_baseline).
     # per-stage durations (HIP events the library records on its launch stream), measured live over STAGE_PASS_STEPS extra steps
     # AFTER the timed region (device warm: the stage times are those of steps like the timed ones), per-stage median
     roofline = None
     stages = None
-    st = StageTimer()                    # (every rank runs the pass -- the same tail for all -- rank 0 reports it)
-    for _ in range(STAGE_PASS_STEPS):
-        st.arm(pool)
-        step(pool, query, x, dy, params, False, None)
-        st.disarm(pool)
-        torch.cuda.synchronize()
-        st.collect()
+    if args.full:
+        st = StageTimer()                # (every rank runs the pass -- the same tail for all -- rank 0 reports it)
+        for _ in range(STAGE_PASS_STEPS):
+            st.arm(pool)
+            step(pool, query, x, dy, params, False, None)
+            st.disarm(pool)
+            torch.cuda.synchronize()
+            st.collect()
     # N > 1, weak scaling (what the driver's one run per N measures): the STRONG-scaling point of the same N rides along in the
     # same line (field "strong_scaling"), after the timed region and the stage pass -- the config's global batch sharded over the
     # ranks, same step, same collective -- so that one lease of a multi-GPU node yields both curves
     # the collective on its own: HIP events on the launch stream around all_reduce_grads (which includes the one rounding of the
     # float32 mean into bf16 parameters' gradients), over extra steps after the timed region; median over the steps, max over ranks
     collective_ms = None
-    if dp_on and nce is None:
+    if args.full and dp_on and nce is None:
         from aecf_amd.dp import all_reduce_grads
         cev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(STAGE_PASS_STEPS)]
         for e0, e1 in cev:
@@ -745,7 +759,7 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             collective_ms = float(tt[0].item())
     strong = None
-    if world > 1 and args.scaling == "weak" and nce is None and graph is None:
+    if args.full and world > 1 and args.scaling == "weak" and nce is None and graph is None:
         import torch.distributed as dist
         lo_s, hi_s = dp.shard_bounds(Bc, rank, world)
         bs = hi_s - lo_s
@@ -798,7 +812,7 @@ def main():
             else:
                 strong["graph"] = {"value": None, "graph_replay": False, "note": why or "another rank failed to capture"}
     nce_ms = None
-    if nce is not None:                  # the two C-ABI calls of the loss side, HIP events on the launch stream
+    if args.full and nce is not None:    # the two C-ABI calls of the loss side, HIP events on the launch stream
         from aecf_amd import _lib
         from aecf_amd.layer import _ptr, _stream
         lib = _lib.load()
@@ -828,7 +842,7 @@ def main():
             t2.append(ev[1].elapsed_time(ev[2]))
         nce_ms = {"nce.pass1 (logits GEMM + exp + sums)": sorted(t1)[5], "nce.loss + nce.grads (normalisers, weights, da, db)": sorted(t2)[5]}
         del ws, da, db
-    if rank == 0:
+    if rank == 0 and args.full:
         stages = st.median_ms()
         model = stage_model(cfg)
         dom = max((k for k in stages if k in model), key=lambda k: stages[k])
@@ -874,7 +888,7 @@ def main():
             path_flops += 6.0 * nce["cols"] * E                   # per local sample: logits + the two gradient products
             path_bytes += s_bytes * (2 * E + 2 * nce["cols"]) + 4 * E        # z, dz, the E row written + re-read twice ... per sample
         cb = None
-        if not (args.no_cpu_baseline or world > 1):
+        if args.full and not (args.no_cpu_baseline or world > 1):
             cb = cpu_baseline(cfg, args.cpu_baseline_seconds)
             cb["cpu_model"] = cpu_model()
         workload = f"{args.config}: [B={B} per GPU, M={M}, d={E}, {H} heads] mask_prob={p} train-mode curriculum masking, fwd+bwd"
@@ -889,12 +903,14 @@ def main():
         # every hipEventRecord of the stage pass is a marker the stream has to process (~5 us): a stage with no launch in it
         # reads that much.  Reported as measured; `sum_ms` adds everything up, `launch_stages_sum_ms` leaves the empty stages
         # out -- the figure to hold against ms_per_step (it still carries one marker per non-empty stage)
-        empty = [k for k, v in stages.items() if k.startswith(("fwd.", "bwd.")) and v < 0.008]
-        pool_stage_sum = sum(v for k, v in stages.items() if k.startswith(("fwd.", "bwd.")))
-        stage_pass = {"steps": STAGE_PASS_STEPS, "when": "after the timed region", "stat": "median",
-                      "sum_ms": pool_stage_sum, "empty_stages": empty,
-                      "event_overhead_ms_per_mark": (sum(stages[k] for k in empty) / len(empty)) if empty else None,
-                      "launch_stages_sum_ms": pool_stage_sum - sum(stages[k] for k in empty)}
+        stage_pass = None
+        if stages is not None:
+            empty = [k for k, v in stages.items() if k.startswith(("fwd.", "bwd.")) and v < 0.008]
+            pool_stage_sum = sum(v for k, v in stages.items() if k.startswith(("fwd.", "bwd.")))
+            stage_pass = {"steps": STAGE_PASS_STEPS, "when": "after the timed region", "stat": "median",
+                          "sum_ms": pool_stage_sum, "empty_stages": empty,
+                          "event_overhead_ms_per_mark": (sum(stages[k] for k in empty) / len(empty)) if empty else None,
+                          "launch_stages_sum_ms": pool_stage_sum - sum(stages[k] for k in empty)}
         pdt = next(iter(pool.parameters())).dtype
         hilo_on = pool.options.hilo_grads if pool.options.hilo_grads is not None else (pdt != dtype)
         grad_mode = ("float32-stored parameter gradients, weight-gradient products on bf16 hi + lo operand pairs (AECF_HILO_GRADS)"
@@ -930,6 +946,7 @@ def main():
             "collective_library": None if world == 1 else (
                 f"RCCL {'.'.join(str(v) for v in torch.cuda.nccl.version())}" if backend == "nccl" else backend),
             "dump_outputs": dumped,
+            "full": args.full,
         }
         emit(line)
     if world > 1 or args.force_dp:

@@ -255,15 +255,15 @@ def test_bench_gpus2_launches_two_ranks():
 
 @pytest.mark.timeout(600)
 def test_bench_weak_scaling_line_carries_the_strong_point():
-    """The driver runs ONE `bench.py --gpus N` per N (weak scaling): the same line also carries the strong-scaling point of
-    that N and names the collective library, so one lease of a multi-GPU node yields both curves."""
+    """One `bench.py --gpus N --full` per N (weak scaling): the same line also carries the strong-scaling point of that N and
+    names the collective library, so one lease of a multi-GPU node yields both curves."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     if torch.cuda.device_count() < 2:
         env["AECF_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "tiny", "--steps", "5",
-                        "--warmup", "2"], env=env, capture_output=True, text=True, timeout=560)
+                        "--warmup", "2", "--full"], env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["config"]["global_batch"] == 2 * 4096
@@ -275,14 +275,14 @@ def test_bench_weak_scaling_line_carries_the_strong_point():
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("graph", [False, True])
 def test_bench_force_dp_runs_the_rccl_step_on_one_gpu(graph):
-    """`bench.py --force-dp`: the N > 1 step (dp.attach: pre-scaled gradients, float32 sums, the sharded in-kernel mask draw,
+    """`bench.py --force-dp --full`: the N > 1 step (dp.attach: pre-scaled gradients, float32 sums, the sharded in-kernel mask draw,
     ONE collective) on a one-rank RCCL group -- the RCCL call itself and, with --graph, its capture with the step into one HIP
     graph, which is what the strong-scaling point replays on a multi-GPU node."""
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "AECF_DIST_BACKEND"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "tiny", "--steps", "5", "--warmup", "2", "--force-dp",
-           "--no-cpu-baseline", "--settle-seconds", "0"] + (["--graph"] if graph else [])
+           "--full", "--no-cpu-baseline", "--settle-seconds", "0"] + (["--graph"] if graph else [])
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -6,6 +6,6 @@ summ='import sys,json; l=json.loads(sys.stdin.read()); s=l["stage_ms"]; print(sy
 for i in $(seq $rounds); do
   for n in "$@"; do
     if [ "$n" = main ]; then lib=""; else lib=$PWD/aecf_amd/lib/var/$n/libaecf_hip.so; fi
-    AECF_LIB_PATH=$lib timeout -k 10 300 python bench.py --config $cfg --steps 50 --warmup 10 --no-cpu-baseline $EXTRA 2>/dev/null | python -c "$summ" $n
+    AECF_LIB_PATH=$lib timeout -k 10 300 python bench.py --config $cfg --steps 50 --warmup 10 --full --no-cpu-baseline $EXTRA 2>/dev/null | python -c "$summ" $n
   done
 done

@@ -9,7 +9,7 @@ mkdir -p $out
 rocprofv3 --kernel-trace --stats -d $out/ks_nce -o r -- python3 bench.py --settle-seconds 0 --config c3 --contrastive --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
 python3 tools/kernel_stats_from_db.py $out/ks_nce/r_results.db $out/${tag}_c3nce_kernel_stats.csv | head -12
 rm -rf $out/ks_nce
-python3 bench.py --config c3 --contrastive --steps 50 --warmup 10 > $out/${tag}_c3nce_bench.json 2> /dev/null
+python3 bench.py --config c3 --contrastive --steps 50 --warmup 10 --full > $out/${tag}_c3nce_bench.json 2> /dev/null
 i=0
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VMEM" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE TCC_HIT_sum TCC_MISS_sum SQ_INSTS_VALU SQ_INSTS_LDS GRBM_GUI_ACTIVE" \

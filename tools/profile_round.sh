@@ -26,12 +26,12 @@ rm -rf $out/ksd
 rocprofv3 --kernel-trace --stats -d $out/ksh -o r -- python3 bench.py --settle-seconds 0 --steps 20 --warmup 5 --no-cpu-baseline --f32-params > /dev/null 2>&1
 python3 tools/kernel_stats_from_db.py $out/ksh/r_results.db $out/${tag}_c2_f32params_kernel_stats.csv | head -14
 rm -rf $out/ksh
-python3 bench.py --steps 50 --warmup 10 > $out/${tag}_c2_bench.json 2> /dev/null
-python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --force-dp > $out/${tag}_c2_forcedp_bench.json 2> /dev/null
-python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --force-dp --graph > $out/${tag}_c2_forcedp_graph_bench.json 2> /dev/null
-python3 bench.py --config c3 --steps 50 --warmup 10 --no-cpu-baseline --graph > $out/${tag}_c3shard_graph_bench.json 2> /dev/null
-python3 bench.py --config c3 --steps 50 --warmup 10 --no-cpu-baseline > $out/${tag}_c3shard_bench.json 2> /dev/null
-python3 bench.py --config c5 --steps 50 --warmup 10 --no-cpu-baseline > $out/${tag}_c5shard_bench.json 2> /dev/null
+python3 bench.py --steps 50 --warmup 10 --full > $out/${tag}_c2_bench.json 2> /dev/null
+python3 bench.py --steps 50 --warmup 10 --full --no-cpu-baseline --force-dp > $out/${tag}_c2_forcedp_bench.json 2> /dev/null
+python3 bench.py --steps 50 --warmup 10 --full --no-cpu-baseline --force-dp --graph > $out/${tag}_c2_forcedp_graph_bench.json 2> /dev/null
+python3 bench.py --config c3 --steps 50 --warmup 10 --full --no-cpu-baseline --graph > $out/${tag}_c3shard_graph_bench.json 2> /dev/null
+python3 bench.py --config c3 --steps 50 --warmup 10 --full --no-cpu-baseline > $out/${tag}_c3shard_bench.json 2> /dev/null
+python3 bench.py --config c5 --steps 50 --warmup 10 --full --no-cpu-baseline > $out/${tag}_c5shard_bench.json 2> /dev/null
 for f in c2 c2_forcedp c2_forcedp_graph c3shard c3shard_graph c5shard; do python3 -c "
 import json; l=json.load(open('$out/${tag}_${f}_bench.json')); r=l['roofline']
 print('$f', round(l['ms_per_step'],4), round(l['value']/1e6,1), 'M/s', r['kernel'], round(r['frac'],3), r['traffic'], round(l['path_hbm_frac'],3), round(l['path_mfma_frac'],3))"; done
