@@ -62,7 +62,7 @@ PrepWs prep_layout(const aecf_pool_desc* d) {
 
 struct BwdWs {
     PrepWs prep;
-    size_t dobuf, dsbuf, slab_o, slab_v, cs_o, cs_v, u_slab, u, dqp, dq_part, do_lo, total;
+    size_t dobuf, dsbuf, slab_o, slab_v, cs_o, cs_v, u_slab, u, dqp, do_lo, total;
     int splits, u_splits, u_splits_cap;
     int64_t rows_per_split, u_rows_per_split;
 };
@@ -105,7 +105,6 @@ BwdWs bwd_layout(const aecf_pool_desc* d, bool hilo = false) {
     w.u_slab = off; off = align_up(off + (size_t)w.u_splits_cap * HPAD * E * 4);
     w.u = off;      off = align_up(off + HPAD * E * 4);
     w.dqp = off;    off = align_up(off + E * 4);
-    w.dq_part = off; off = align_up(off + (E / 16) * E * 4);
     w.do_lo = off;  if (hilo) off = align_up(off + B * E * es);
     w.total = off;
     return w;
@@ -608,8 +607,7 @@ int pool_backward_on(const aecf_pool_desc* d, const aecf_pool_bwd_args* a, hipSt
     if (!dqp_rides) launch_dqp(d->dtype, dq, s);
 
     FinalizeArgs f;
-    f.w_in = a->w_in; f.query = a->query; f.qs = qs; f.u = u; f.dqp = (float*)(ws + L.dqp);
-    f.dq_part = (float*)(ws + L.dq_part); f.dw_in = a->dw_in;
+    f.w_in = a->w_in; f.query = a->query; f.qs = qs; f.u = u; f.dqp = (float*)(ws + L.dqp); f.dw_in = a->dw_in;
     f.db_in = a->db_in; f.dquery = a->dquery; f.E = E; f.H = H; f.hd = hd; f.scale = scale; f.grad_gt = gt;
     f.gscale = gscale;
     launch_finalize_all(d->dtype, f, rs, s);

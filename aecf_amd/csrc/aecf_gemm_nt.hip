@@ -5,12 +5,7 @@
 // through LDS from registers: the global loads of tile t+1 are issued before the MFMAs of tile t and written
 // to LDS after the next barrier, so their latency hides under the matrix work (one LDS buffer, two barriers
 // per tile).  Rows of the weight matrix come from L2 (<= 2 MB, shared by every block); the activation tile
-// is read once per column block.
-//
-// POOLED (the V projection of the fusion pool): the A operand of output head h is
-//     pooled_h[b,:] = sum_m probs[b,h,m] * x[b,m,:]
-// formed in registers from the M staged x tiles while the fragments are read (fp32 FMA, one rounding to the
-// MFMA input type), so V is projected once per sample instead of once per (sample, modality).
+// is read once per column block.  (Pooled products -- the V projection -- run on gemm_ws or vproj_modal.)
 //
 // bf16 / f16 output leaves through LDS as full 256-byte rows; f32 output is stored from the accumulator layout.
 #include <stdlib.h>
@@ -22,17 +17,16 @@ namespace aecf {
 
 // WT = 16 x 16 MFMA tiles per wave and dimension: 4 (block tile 128 x 128) or 1 (32 x 32: problems of a few hundred rows --
 // the example model's batch of 64 -- would otherwise run on one or two CUs, 26 us for a [64 x 256] . [256 x 256]^T in float32)
-template <typename T, int M_, bool POOLED, int WT>
+template <typename T, int WT>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNtArgs p) {
     using X = Tr<T>;
     typedef typename X::elem elem;
-    constexpr int NA = POOLED ? M_ : 1;          // A-side LDS tiles (one per modality when pooling)
     constexpr int BT = 32 * WT, WTR = 16 * WT;   // block tile and wave tile edge
     constexpr int TILE = BT * TILE_ROW_BYTES;    // 16 KB (WT = 4)
     constexpr int BK = TileK<T>::value;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ldsA = smem;
-    char* ldsB = smem + NA * TILE;
+    char* ldsB = smem + TILE;
 
     const int lane = lane_id(), r16 = lane & 15, lg = lane >> 4, w = wave_id();
     const int wr = w >> 1, wc = w & 1;
@@ -53,24 +47,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNtArgs p) {
     // wave-level column bookkeeping
     const int nw0 = n0 + WTR * wc;
     int nct = (p.N - nw0) >= WTR ? WT : ((p.N - nw0) > 0 ? (p.N - nw0) / 16 : 0);
-    int head[4];
-    float pr[4][4][M_];
-    if (POOLED && WT == 4) {
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) {
-            int h = (nw0 + 16 * ct) / p.hd;
-            head[ct] = h < p.H ? h : p.H - 1;
-        }
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) {
-            int64_t row = r0 + 64 * wr + 16 * rt + r16;
-            if (row >= p.R) row = p.R - 1;
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-                for (int m = 0; m < M_; ++m) pr[rt][ct][m] = p.probs[(row * p.H + head[ct]) * M_ + m];
-        }
-    }
 
     f32x4 acc[WT][WT];
 #pragma unroll
@@ -78,21 +54,19 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNtArgs p) {
 #pragma unroll
         for (int ct = 0; ct < WT; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    if (!POOLED) {
-        // LDS-DMA, two buffers, one barrier per K tile: barrier (tile kt landed, tile kt-1 consumed) -> issue kt+1 -> MFMAs of kt
-        dma_tile<BT, 256>(a_src, lda_bytes, rows_valid, ldsA);
-        dma_tile<BT, 256>(w_src, ldw_bytes, cols_valid, ldsB);
-        for (int kt = 0; kt < nkt; ++kt) {
-            char* curA = ldsA + (kt & 1) * 2 * TILE;
-            char* curB = ldsB + (kt & 1) * 2 * TILE;
-            __syncthreads();
-            if (kt + 1 < nkt) {
-                const int64_t koff = (int64_t)(kt + 1) * TILE_ROW_BYTES;
-                dma_tile<BT, 256>(a_src + koff, lda_bytes, rows_valid, ldsA + ((kt + 1) & 1) * 2 * TILE);
-                dma_tile<BT, 256>(w_src + koff, ldw_bytes, cols_valid, ldsB + ((kt + 1) & 1) * 2 * TILE);
-            }
-            tile_mma<T, WT, WT>(acc, curA, WTR * wr, curB, WTR * wc);
+    // LDS-DMA, two buffers, one barrier per K tile: barrier (tile kt landed, tile kt-1 consumed) -> issue kt+1 -> MFMAs of kt
+    dma_tile<BT, 256>(a_src, lda_bytes, rows_valid, ldsA);
+    dma_tile<BT, 256>(w_src, ldw_bytes, cols_valid, ldsB);
+    for (int kt = 0; kt < nkt; ++kt) {
+        char* curA = ldsA + (kt & 1) * 2 * TILE;
+        char* curB = ldsB + (kt & 1) * 2 * TILE;
+        __syncthreads();
+        if (kt + 1 < nkt) {
+            const int64_t koff = (int64_t)(kt + 1) * TILE_ROW_BYTES;
+            dma_tile<BT, 256>(a_src + koff, lda_bytes, rows_valid, ldsA + ((kt + 1) & 1) * 2 * TILE);
+            dma_tile<BT, 256>(w_src + koff, ldw_bytes, cols_valid, ldsB + ((kt + 1) & 1) * 2 * TILE);
         }
+        tile_mma<T, WT, WT>(acc, curA, WTR * wr, curB, WTR * wc);
     }
     // ---------------- epilogue ----------------
     const elem* bias = reinterpret_cast<const elem*>(p.bias);
@@ -155,13 +129,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmNtArgs p) {
     }
 }
 
-template <typename T, int M_, bool POOLED, int WT = 4>
+template <typename T, int WT>
 static void launch_one(const GemmNtArgs& a, hipStream_t s) {
-    constexpr int NA = POOLED ? M_ : 1;
     constexpr int BT = 32 * WT;
-    const size_t smem = (size_t)(POOLED ? (NA + 1) : 4) * BT * TILE_ROW_BYTES;
+    const size_t smem = (size_t)4 * BT * TILE_ROW_BYTES;          // two buffers of the A and the W tile
     dim3 grid(xcd_grid((unsigned)((a.R + BT - 1) / BT), (unsigned)((a.N + BT - 1) / BT))), block(256);
-    auto kern = gemm_nt_kernel<T, M_, POOLED, WT>;
+    auto kern = gemm_nt_kernel<T, WT>;
     if (smem > 64 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     kern<<<grid, block, smem, s>>>(a);
@@ -173,7 +146,7 @@ void launch_gemm_nt(int dtype, const GemmNtArgs& a_in, hipStream_t s) {
     if (a.pooled & 1) { launch_vproj(dtype, a, s); return; }     // per-modality accumulators (aecf_vproj.hip)
     // fewer than 64 block tiles of 128 x 128: 32 x 32 tiles instead (16 x the blocks, each 1/16 of the K loop's MFMAs)
     const bool small = ((a.R + 127) / 128) * (int64_t)((a.N + 127) / 128) < 64;
-    AECF_DISPATCH_T(dtype, { if (small) launch_one<T_, 1, false, 1>(a, s); else launch_one<T_, 1, false>(a, s); });
+    AECF_DISPATCH_T(dtype, { if (small) launch_one<T_, 1>(a, s); else launch_one<T_, 4>(a, s); });
 }
 
 }  // namespace aecf

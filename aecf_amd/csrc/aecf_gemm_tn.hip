@@ -375,39 +375,30 @@ static void launch_one(const GemmTnArgs& a, hipStream_t s) {
     kern<<<grid, block, smem, s>>>(a);
 }
 
-// head slots a block needs = the most heads any aligned BJ-row window of the E output rows touches
-static int max_slots(int E, int hd, int BJ) {
-    int mx = 1;
-    for (int j0 = 0; j0 < E; j0 += BJ) {
-        const int j1 = (j0 + BJ < E ? j0 + BJ : E) - 1;
-        const int n = j1 / hd - j0 / hd + 1;
-        if (n > mx) mx = n;
+// pooled: the widest wave tile whose j rows lie inside one head (WJ) and the head slots (MAXS) the widest BJ-row window needs.
+// WJ = 64 (hd % 64 == 0): a 128-row window touches at most 2 heads.  WJ = 32 or 16: hd is an odd multiple of the wave tile,
+// so every window that holds a head boundary touches 2 or more.  WJ = 16 is float32 only (16-bit types: hd % 32 == 0).
+template <typename T, int M_>
+static void launch_pooled(const GemmTnArgs& a, hipStream_t s) {
+    const int ns = head_slots(a.E, a.hd, a.hd % 32 == 0 ? 128 : 64);
+    if (a.hd % 64 == 0) {
+        if (ns <= 1) launch_one<T, M_, true, 64, 1>(a, s);
+        else launch_one<T, M_, true, 64, 2>(a, s);
+    } else if (Tr<T>::BYTES == 2 || a.hd % 32 == 0) {
+        if (ns <= 2) launch_one<T, M_, true, 32, 2>(a, s);
+        else launch_one<T, M_, true, 32, 4>(a, s);
+    } else if constexpr (Tr<T>::BYTES == 4) {
+        if (ns <= 2) launch_one<T, M_, true, 16, 2>(a, s);
+        else launch_one<T, M_, true, 16, 4>(a, s);
     }
-    return mx;
-}
-
-template <typename T, int M_, bool POOLED, int WJ>
-static void launch_slots(const GemmTnArgs& a, hipStream_t s) {
-    if (!POOLED) { launch_one<T, M_, POOLED, WJ, 1>(a, s); return; }
-    const int ns = max_slots(a.E, a.hd, (WJ == 16) ? 64 : 128);
-    if (ns <= 1) launch_one<T, M_, POOLED, WJ, 1>(a, s);
-    else if (ns <= 2) launch_one<T, M_, POOLED, WJ, 2>(a, s);
-    else launch_one<T, M_, POOLED, WJ, 4>(a, s);
-}
-
-template <typename T, int M_, bool POOLED>
-static void launch_wj(const GemmTnArgs& a, hipStream_t s) {
-    if (!POOLED || a.hd % 64 == 0) launch_slots<T, M_, POOLED, 64>(a, s);
-    else if (a.hd % 32 == 0) launch_slots<T, M_, POOLED, 32>(a, s);
-    else launch_slots<T, M_, POOLED, 16>(a, s);
 }
 
 void launch_gemm_tn(int dtype, const GemmTnArgs& a, hipStream_t s) {
     // bf16: transposed-LDS-read kernel (aecf_gemm_tn_tr.hip); f32 and f16: register-transposed staging (this file)
     if (!a.pooled) {
         if (dtype == 0) launch_gemm_tn_tr(a, s);
-        else if (dtype == 1) launch_wj<F32, 1, false>(a, s);
-        else if (dtype == 2) launch_wj<F16, 1, false>(a, s);
+        else if (dtype == 1) launch_one<F32, 1, false, 64, 1>(a, s);
+        else if (dtype == 2) launch_one<F16, 1, false, 64, 1>(a, s);
         return;
     }
     const bool do_main = a.parts != 2, do_u = a.parts != 1;
@@ -415,8 +406,8 @@ void launch_gemm_tn(int dtype, const GemmTnArgs& a, hipStream_t s) {
     if (dtype == 0 && do_u && u_mfma_supported(a)) { launch_u_mfma(a, s); return; }
     AECF_DISPATCH_M(a.M, {
         if (dtype == 0) { if (do_u) launch_u<BF16, M_>(a, s); }
-        else if (dtype == 1) { if (do_main) launch_wj<F32, M_, true>(a, s); if (do_u) launch_u<F32, M_>(a, s); }
-        else if (dtype == 2) { if (do_main) launch_wj<F16, M_, true>(a, s); if (do_u) launch_u<F16, M_>(a, s); }
+        else if (dtype == 1) { if (do_main) launch_pooled<F32, M_>(a, s); if (do_u) launch_u<F32, M_>(a, s); }
+        else if (dtype == 2) { if (do_main) launch_pooled<F16, M_>(a, s); if (do_u) launch_u<F16, M_>(a, s); }
     });
 }
 

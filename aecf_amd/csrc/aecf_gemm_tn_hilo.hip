@@ -295,12 +295,12 @@ __global__ __launch_bounds__(512, 4) void gemm_tn_hilo_pooled_kernel(GemmTnArgs 
 // Plain product (dW_o = dy^T o): 512 threads = 8 waves as 2 (j) x 4 (k), block tile 128 x 128, wave tile 64 x 32; every tile by
 // LDS-DMA into a RING of D stages, the copy of step k + D - 1 issued at step k: a 32-row step is ~0.2 us of MFMAs, far less
 // than a trip to HBM, so one step of lead (the two-buffer form) left every step waiting for its tiles (measured: 64 steps of
-// ~1.3 us).  HILO: rhs = o_hi and o_lo (two tiles per stage, two MFMAs per fragment pair); its lhs dy is an exact input.
-template <bool HILO, int D>
+// ~1.3 us).  rhs = o_hi and o_lo (two tiles per stage, two MFMAs per fragment pair); its lhs dy is an exact input.
 __global__ __launch_bounds__(512, 4) void gemm_tn_ring_kernel(GemmTnArgs p) {
     using X = Tr<BF16>;
     constexpr int RT = 4, CT = 2, WK = 4;
-    constexpr int NI = HILO ? 3 : 2;                                  // DMA instructions per thread and step
+    constexpr int D = 3;                                              // ring stages
+    constexpr int NI = 3;                                             // DMA instructions per thread and step
     constexpr int STAGE = NI * HR_TILE;
     extern __shared__ __attribute__((aligned(16))) char smem[];       // [D stages][lhs | rhs hi | rhs lo]
 
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(512, 4) void gemm_tn_ring_kernel(GemmTnArgs p) {
         char* st = smem + stage * STAGE;
         dma_hr_images(lhs + base * (int64_t)ld + (int64_t)j0 * 2, ld, nvalid, st);
         dma_hr_images(rhs_hi + base * (int64_t)ld + (int64_t)k0 * 2, ld, nvalid, st + HR_TILE);
-        if (HILO) dma_hr_images(rhs_lo + base * (int64_t)ld + (int64_t)k0 * 2, ld, nvalid, st + 2 * HR_TILE);
+        dma_hr_images(rhs_lo + base * (int64_t)ld + (int64_t)k0 * 2, ld, nvalid, st + 2 * HR_TILE);
     };
 
 #pragma unroll
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(512, 4) void gemm_tn_ring_kernel(GemmTnArgs p) {
             for (int c = threadIdx.x; c < (HRB - nvalid_cur) * 16; c += 512) {
                 const int off = tr_off(nvalid_cur + (c >> 4), c & 15);
                 *reinterpret_cast<u32x4*>(st + HR_TILE + off) = u32x4{0u, 0u, 0u, 0u};
-                if (HILO) *reinterpret_cast<u32x4*>(st + 2 * HR_TILE + off) = u32x4{0u, 0u, 0u, 0u};
+                *reinterpret_cast<u32x4*>(st + 2 * HR_TILE + off) = u32x4{0u, 0u, 0u, 0u};
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
@@ -390,11 +390,9 @@ __global__ __launch_bounds__(512, 4) void gemm_tn_ring_kernel(GemmTnArgs p) {
         for (int ct = 0; ct < CT; ++ct) {
             const char* bt = st + HR_TILE + b_org + 512 * (ct >> 1);
             const u32x4 bh = tr_frag(bt, tx[ct & 1][0], tx[ct & 1][1]);
-            if (HILO) {
-                const u32x4 bl = tr_frag(bt + HR_TILE, tx[ct & 1][0], tx[ct & 1][1]);
+            const u32x4 bl = tr_frag(bt + HR_TILE, tx[ct & 1][0], tx[ct & 1][1]);
 #pragma unroll
-                for (int rt = 0; rt < RT; ++rt) acc[rt][ct] = X::mma(a[rt], bl, acc[rt][ct]);
-            }
+            for (int rt = 0; rt < RT; ++rt) acc[rt][ct] = X::mma(a[rt], bl, acc[rt][ct]);
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) acc[rt][ct] = X::mma(a[rt], bh, acc[rt][ct]);
         }
@@ -427,11 +425,7 @@ void launch_hilo_pooled(const GemmTnArgs& a, hipStream_t s) {
 }
 
 int hilo_slots_128(int E, int hd) {               // head slots of the widest aligned 128-row window: 1 or 2 -> 2, 3 or 4 -> 4
-    int mx = 1;
-    for (int j0 = 0; j0 < E; j0 += 128) {
-        const int n = (j0 + 127) / hd - j0 / hd + 1;
-        if (n > mx) mx = n;
-    }
+    const int mx = head_slots(E, hd, 128);
     return mx <= 2 ? 2 : (mx <= 4 ? 4 : 0);
 }
 
@@ -448,10 +442,10 @@ void launch_gemm_tn_hilo(const GemmTnArgs& a, hipStream_t s) {
     if (!a.pooled) {
         // the plain product with both rhs tiles of a step (o_hi, o_lo): a ring of three 24 KB stages, two blocks per CU (75 us at
         // the headline shape; two stages: 85).  (The same kernel without the low tile -- the default product on 32-row steps with
-        // four stages -- measured 53 us against the 46 us of the default path's 64-row two-buffer kernel: not instantiated.)
+        // four stages -- measured 53 us against the 46 us of the default path's 64-row two-buffer kernel: not built.)
         dim3 grid(xcd_grid((unsigned)a.splits, (unsigned)((a.E / 128) * (a.E / 128)))), block(512);
         const size_t smem = (size_t)3 * 3 * HR_TILE;
-        auto kern = gemm_tn_ring_kernel<true, 3>;
+        auto kern = gemm_tn_ring_kernel;
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         kern<<<grid, block, smem, s>>>(a);
         return;

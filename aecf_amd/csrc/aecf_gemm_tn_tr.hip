@@ -733,35 +733,13 @@ void launch_u_mfma(const GemmTnArgs& a, hipStream_t s) {
     }
 }
 
-// head slots a block needs = the most heads any aligned 128-row window of the E output rows touches
-static int max_slots_128(int E, int hd) {
-    int mx = 1;
-    for (int j0 = 0; j0 < E; j0 += 128) {
-        const int j1 = (j0 + 128 < E ? j0 + 128 : E) - 1;
-        const int n = j1 / hd - j0 / hd + 1;
-        if (n > mx) mx = n;
-    }
-    return mx;
-}
-
 // bf16 only; head_dim % 32 == 0 (a wave's 32 output rows lie inside one head)
-// head slots of the widest aligned 256-row window
-static int max_slots_256(int E, int hd) {
-    int mx = 1;
-    for (int j0 = 0; j0 < E; j0 += 256) {
-        const int j1 = (j0 + 256 < E ? j0 + 256 : E) - 1;
-        const int n = j1 / hd - j0 / hd + 1;
-        if (n > mx) mx = n;
-    }
-    return mx;
-}
-
 void launch_gemm_tn_tr(const GemmTnArgs& a, hipStream_t s) {
     if (!a.pooled) { launch_one<1, false, 1>(a, s); return; }
     // 256-row tiles (1024 threads) when they tile E exactly with at most 4 head slots and M <= 3 (128-VGPR budget)
-    if (a.Ej <= 0 && a.E % 256 == 0 && max_slots_256(a.E, a.hd) <= 4 &&
-        (a.M <= 3 || (a.M == 4 && max_slots_256(a.E, a.hd) <= 2))) {
-        const bool two = max_slots_256(a.E, a.hd) <= 2;
+    const int ns256 = head_slots(a.E, a.hd, 256);
+    if (a.Ej <= 0 && a.E % 256 == 0 && ns256 <= 4 && (a.M <= 3 || (a.M == 4 && ns256 <= 2))) {
+        const bool two = ns256 <= 2;
         switch (a.M) {
             case 1: if (two) launch_wide<1, 2>(a, s); else launch_wide<1, 4>(a, s); return;
             case 2: if (two) launch_wide<2, 2>(a, s); else launch_wide<2, 4>(a, s); return;
@@ -769,7 +747,7 @@ void launch_gemm_tn_tr(const GemmTnArgs& a, hipStream_t s) {
             default: launch_wide<4, 2>(a, s); return;
         }
     }
-    const int ns = max_slots_128(a.E, a.hd);
+    const int ns = head_slots(a.E, a.hd, 128);
     AECF_DISPATCH_M(a.M, {
         if (ns <= 2) launch_one<M_, true, 2>(a, s);
         else launch_one<M_, true, 4>(a, s);

@@ -695,20 +695,14 @@ __global__ __launch_bounds__(512, 2) void dx_ws2_kernel(BwdGArgs p, int rows_per
 // used three times without leaving the CU: as the vector operand of the dot, and -- read column-wise with
 // ds_read_b64_tr_b16 -- as the MFMA A operand of u^T = x^T ds (ds split hi/lo bf16).  HBM: do once, x once (the second
 // head group of a row chunk finds the rows in its XCD's L2), ds written (tiny); the forward no longer stores V.
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-__device__ __forceinline__ float dot2_bf16(unsigned int a, unsigned int b, float c) {     // v_dot2c_f32_bf16
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
-}
-
-// WIDE (round 4): the resident weights' rows are permuted so that a lane's accumulators of a tile PAIR hold 8 CONSECUTIVE
-// columns k (k = ncol0 + 32 (ct >> 1) + 8 lg + 4 (ct & 1) + reg, the trick of the plain kernel's 16-byte stores), so the dot
-// reads x in 16-byte pieces: half the LDS reads of the 8-byte form -- each of them is waited for right in front of its use
-// (the kernel has no registers left to run them ahead: profiles/r01_pmc_notes.md, end of round 3).
-template <int KT, int KJ, int HK, int M_, bool PKDOT, int VAR, bool HILO = false>
+// The resident weights' rows are permuted so that a lane's accumulators of a tile PAIR hold 8 CONSECUTIVE columns k
+// (k = ncol0 + 32 (ct >> 1) + 8 lg + 4 (ct & 1) + reg, the trick of the plain kernel's 16-byte stores), so the dot reads x in
+// 16-byte pieces -- each of them is waited for right in front of its use (the kernel has no registers left to run them
+// ahead: profiles/r01_pmc_notes.md, end of round 3).
+template <int KT, int HK, int M_, bool HILO>
 __global__ __launch_bounds__(512, 2) void dsu_ws_kernel(BwdGArgs p, float* __restrict__ u_slab, int rows_per_block, int nchunk) {
     using X = Tr<BF16>;
-    constexpr bool WIDE = VAR >= 1;                               // 16-byte dot reads (VAR 0: the 8-byte form of rounds 2-3)
-    constexpr bool NOBR = VAR >= 2;                               // partial dots leave the wave without a branch (below)
+    constexpr int KJ = 8;                                         // K-steps of the block's JB = 256 columns j
     constexpr int E = 32 * KT, JB = 32 * KJ, NCT = KT / 4;        // a wave owns E / 8 = 16 NCT columns k
     constexpr int HBL = KJ / HK;                                  // heads per block
     constexpr int ROWX = 2 * E, ROWD = 2 * JB;
@@ -757,10 +751,10 @@ __global__ __launch_bounds__(512, 2) void dsu_ws_kernel(BwdGArgs p, float* __res
     // ---- resident weights: A operand row r16 of column tile ct <-> k = ncol0 + 16 ct + r16, K = j
     const unsigned short* wsrc = reinterpret_cast<const unsigned short*>(p.wvt);
     u32x4 wreg[KJ][NCT];
-    static_assert(!WIDE || NCT % 2 == 0, "tile pairs");
+    static_assert(NCT % 2 == 0, "tile pairs");
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
-        const int krow = WIDE ? ncol0 + 32 * (ct >> 1) + 8 * (r16 >> 2) + 4 * (ct & 1) + (r16 & 3) : ncol0 + 16 * ct + r16;
+        const int krow = ncol0 + 32 * (ct >> 1) + 8 * (r16 >> 2) + 4 * (ct & 1) + (r16 & 3);
         const unsigned short* wr = wsrc + (int64_t)krow * E + jbase + 8 * lg;
 #pragma unroll
         for (int ks = 0; ks < KJ; ++ks) wreg[ks][ct] = *reinterpret_cast<const u32x4*>(wr + 32 * ks);
@@ -768,14 +762,11 @@ __global__ __launch_bounds__(512, 2) void dsu_ws_kernel(BwdGArgs p, float* __res
     int daddr[4];
 #pragma unroll
     for (int v = 0; v < 4; ++v) daddr[v] = r16 * ROWD + ((((4 * v) + lg) ^ r16) << 4);
-    // the 8-byte piece of x row (r16, m = 0) that holds columns ncol0 + 4 lg .. + 3 of column tile 0; tile ct adds
-    // 2 ct to the chunk index BEFORE the xor with the sample, which (2 ct < 8, ncol0 / 8 a multiple of 8) is an xor of the
-    // byte offset with 32 ct
-    // WIDE: the 16-byte piece that holds columns ncol0 + 8 lg .. + 7 of tile pair 0; pair c2 adds 4 to the chunk index (bit 2 of
-    // (ncol0 >> 3) + lg is clear), an xor of the byte offset with 64.  ds_read_b128's 16-lane groups then touch 16 different
-    // 16-byte slots of the 256-byte bank window (lane-group rows {0-3,12-15 | 4-11} xor two chunk numbers one apart): conflict-free.
-    const int xaddr0 = WIDE ? r16 * M_ * ROWX + ((((ncol0 >> 3) + lg) ^ r16) << 4)
-                            : r16 * M_ * ROWX + (((((ncol0 >> 3) + (lg >> 1))) ^ r16) << 4) + 8 * (lg & 1);
+    // the 16-byte piece of x row (r16, m = 0) that holds columns ncol0 + 8 lg .. + 7 of tile pair 0; pair c2 adds 4 to the
+    // chunk index (bit 2 of (ncol0 >> 3) + lg is clear), an xor of the byte offset with 64.  ds_read_b128's 16-lane groups then
+    // touch 16 different 16-byte slots of the 256-byte bank window (lane-group rows {0-3,12-15 | 4-11} xor two chunk numbers one
+    // apart): conflict-free.
+    const int xaddr0 = r16 * M_ * ROWX + ((((ncol0 >> 3) + lg) ^ r16) << 4);
     // transposed-read addresses of the u product (constant over the steps).  The K index of that product is any
     // numbering of the tile's (sample, modality) rows, as long as the ds operand arrays use the same one -- and the
     // row stride is a multiple of the 256-byte bank window, so rows read together must differ in their swizzle key
@@ -846,13 +837,13 @@ __global__ __launch_bounds__(512, 2) void dsu_ws_kernel(BwdGArgs p, float* __res
             load_stats(o0 + 16, pmv_n, dwb_n);
         }
         const char* tb = db + cur * DT;
-        // heads in groups of HG: P_h by MFMA, then the dot with this lane's x values (8-byte LDS reads at a per-tile base +
-        // an immediate; one read and one unpack serve the HG heads of the group).  Every lane writes its partial (16 NCT
-        // columns of one sample) to part[wave, lane group][head, m][sample]; the ds threads add the 32 of them.
-        constexpr int HG = (HBL % 2 == 0 && !PKDOT) ? 2 : 1;
+        // heads in groups of HG: P_h by MFMA, then the dot with this lane's x values (16-byte LDS reads at a per-pair base +
+        // an immediate; one read and one unpack serve the HG heads of the group).  Every lane's partial (16 NCT columns of
+        // one sample) is summed over the wave's lane groups into part[wave][head, m][sample]; the ds threads add the 8 of them.
+        constexpr int HG = HBL % 2 == 0 ? 2 : 1;
         int xa[NCT];
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) xa[ct] = cur * XT + (WIDE ? (xaddr0 ^ (64 * (ct >> 1))) : (xaddr0 ^ (32 * ct)));
+        for (int ct = 0; ct < NCT; ++ct) xa[ct] = cur * XT + (xaddr0 ^ (64 * (ct >> 1)));
         float* pw = part + w * PSTR + r16;
 #pragma unroll
         for (int h0 = 0; h0 < HBL; h0 += HG) {
@@ -874,81 +865,35 @@ __global__ __launch_bounds__(512, 2) void dsu_ws_kernel(BwdGArgs p, float* __res
                     }
                 }
             }
-            unsigned int pk[HG][NCT][2];
-            if (PKDOT) {
-#pragma unroll
-                for (int g = 0; g < HG; ++g)
-#pragma unroll
-                    for (int ct = 0; ct < NCT; ++ct) {
-                        pk[g][ct][0] = pack_bf16x2(P[g][ct][0], P[g][ct][1]);
-                        pk[g][ct][1] = pack_bf16x2(P[g][ct][2], P[g][ct][3]);
-                    }
-            }
 #pragma unroll
             for (int m = 0; m < M_; ++m) {
                 float a[HG];
 #pragma unroll
                 for (int g = 0; g < HG; ++g) a[g] = 0.f;
-                if (WIDE) {
 #pragma unroll
-                    for (int c2 = 0; c2 < NCT / 2; ++c2) {
-                        const u32x4 xv = *reinterpret_cast<const u32x4*>(xb + xa[2 * c2] + m * ROWX);
-                        float xf[8];
+                for (int c2 = 0; c2 < NCT / 2; ++c2) {
+                    const u32x4 xv = *reinterpret_cast<const u32x4*>(xb + xa[2 * c2] + m * ROWX);
+                    float xf[8];
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            xf[2 * i] = __uint_as_float(xv[i] << 16);
-                            xf[2 * i + 1] = __uint_as_float(xv[i] & 0xffff0000u);
-                        }
-#pragma unroll
-                        for (int g = 0; g < HG; ++g)
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) a[g] = fmaf(P[g][2 * c2 + (i >> 2)][i & 3], xf[i], a[g]);
+                    for (int i = 0; i < 4; ++i) {
+                        xf[2 * i] = __uint_as_float(xv[i] << 16);
+                        xf[2 * i + 1] = __uint_as_float(xv[i] & 0xffff0000u);
                     }
-                } else
 #pragma unroll
-                for (int ct = 0; ct < NCT; ++ct) {
-                    const u32x2 xv = *reinterpret_cast<const u32x2*>(xb + xa[ct] + m * ROWX);
-                    if (PKDOT) {
+                    for (int g = 0; g < HG; ++g)
 #pragma unroll
-                        for (int g = 0; g < HG; ++g) {
-                            a[g] = dot2_bf16(pk[g][ct][0], xv[0], a[g]);
-                            a[g] = dot2_bf16(pk[g][ct][1], xv[1], a[g]);
-                        }
-                    } else {
-                        const float x0 = __uint_as_float(xv[0] << 16), x1 = __uint_as_float(xv[0] & 0xffff0000u);
-                        const float x2 = __uint_as_float(xv[1] << 16), x3 = __uint_as_float(xv[1] & 0xffff0000u);
-#pragma unroll
-                        for (int g = 0; g < HG; ++g) {
-                            a[g] = fmaf(P[g][ct][0], x0, a[g]);
-                            a[g] = fmaf(P[g][ct][1], x1, a[g]);
-                            a[g] = fmaf(P[g][ct][2], x2, a[g]);
-                            a[g] = fmaf(P[g][ct][3], x3, a[g]);
-                        }
-                    }
+                        for (int i = 0; i < 8; ++i) a[g] = fmaf(P[g][2 * c2 + (i >> 2)][i & 3], xf[i], a[g]);
                 }
-                if (NOBR) {
-                    // the same sums as a reduce-scatter: one row swap pairs the group's two heads (even rows end with head g = 0,
-                    // odd rows with g = 1, each summed over a row pair), one half swap adds the halves; every lane then holds
-                    // the total of head h0 + (lg & 1) and stores it -- lanes 32 apart store the same value to the same word.
-                    // No exec-mask branch per value (12 per step before): the step's dot phase is ONE basic block, so the
-                    // next modality's x reads can be scheduled above this one's arithmetic.
-                    const unsigned int u0 = __float_as_uint(a[0]), u1 = __float_as_uint(a[HG - 1]);
-                    const auto r1 = __builtin_amdgcn_permlane16_swap(u0, u1, false, false);
-                    const unsigned int us = __float_as_uint(__uint_as_float(r1[0]) + __uint_as_float(r1[1]));
-                    const auto r2 = __builtin_amdgcn_permlane32_swap(us, us, false, false);
-                    pw[((h0 + (HG == 2 ? (lg & 1) : 0)) * M_ + m) * 16] = __uint_as_float(r2[0]) + __uint_as_float(r2[1]);
-                } else
-#pragma unroll
-                for (int g = 0; g < HG; ++g) {
-                    // sum over the wave's four lane groups (lanes r16, r16 + 16, + 32, + 48): rows swapped pairwise, then halves
-                    const unsigned int ua = __float_as_uint(a[g]);
-                    const auto r1 = __builtin_amdgcn_permlane16_swap(ua, ua, false, false);
-                    const float s1 = __uint_as_float(r1[0]) + __uint_as_float(r1[1]);
-                    const unsigned int us = __float_as_uint(s1);
-                    const auto r2 = __builtin_amdgcn_permlane32_swap(us, us, false, false);
-                    const float s2 = __uint_as_float(r2[0]) + __uint_as_float(r2[1]);
-                    if (lg == 0) pw[((h0 + g) * M_ + m) * 16] = s2;
-                }
+                // sum over the wave's four lane groups as a reduce-scatter: one row swap pairs the group's two heads (even
+                // rows end with head g = 0, odd rows with g = 1, each summed over a row pair), one half swap adds the halves;
+                // every lane then holds the total of head h0 + (lg & 1) and stores it -- lanes 32 apart store the same value to
+                // the same word.  No exec-mask branch per value: the step's dot phase is ONE basic block, so the next
+                // modality's x reads can be scheduled above this one's arithmetic.
+                const unsigned int u0 = __float_as_uint(a[0]), u1 = __float_as_uint(a[HG - 1]);
+                const auto r1 = __builtin_amdgcn_permlane16_swap(u0, u1, false, false);
+                const unsigned int us = __float_as_uint(__uint_as_float(r1[0]) + __uint_as_float(r1[1]));
+                const auto r2 = __builtin_amdgcn_permlane32_swap(us, us, false, false);
+                pw[((h0 + (HG == 2 ? (lg & 1) : 0)) * M_ + m) * 16] = __uint_as_float(r2[0]) + __uint_as_float(r2[1]);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1021,10 +966,9 @@ static size_t dsu_ws_smem(int E, int M, int hd, bool lo) {
            (size_t)2 * 16 * 72 * 2;
 }
 
-template <int KT, int KJ, int HK, int M_>
+template <int KT, int HK, int M_>
 int launch_dsu_t(const BwdGArgs& a, float* u_slab, hipStream_t s) {
-    constexpr int E = 32 * KT, JB = 32 * KJ;
-    static_assert(JB == 256, "dsu_ws_smem");
+    constexpr int E = 32 * KT, JB = 256;                           // (dsu_ws_kernel's block columns, as in dsu_ws_smem)
     const bool hilo = a.do_lo && dsu_ws_takes_lo(a);             // (else: the default key-side accuracy)
     const size_t smem = dsu_ws_smem(E, M_, a.hd, hilo);
     const int groups = E / JB;
@@ -1034,15 +978,16 @@ int launch_dsu_t(const BwdGArgs& a, float* u_slab, hipStream_t s) {
     rpb = (rpb + 15) / 16 * 16;
     const int64_t nchunk = (a.B + rpb - 1) / rpb;
     dim3 grid(xcd_grid((unsigned)nchunk, (unsigned)groups)), block(512);
-    // dot phase: 16-byte x reads and branch-free partial dots (VAR 2) where the K-step count allows, else the 8-byte form (VAR 0)
-    constexpr int VAR = (KT / 4) % 2 == 0 ? 2 : 0;
-    if (hilo) {                                                   // AECF_HILO_GRADS: P from do_hi + do_lo
-        auto kern = dsu_ws_kernel<KT, KJ, HK, M_, false, VAR, true>;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        kern<<<grid, block, smem, s>>>(a, u_slab, (int)rpb, (int)nchunk);
-        return (int)nchunk;
+    // AECF_HILO_GRADS: P from do_hi + do_lo.  dsu_ws_takes_lo refuses E = 512 with M = 4 (LDS): that kernel is not built
+    if constexpr (!(E == 512 && M_ == 4)) {
+        if (hilo) {
+            auto kern = dsu_ws_kernel<KT, HK, M_, true>;
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+            kern<<<grid, block, smem, s>>>(a, u_slab, (int)rpb, (int)nchunk);
+            return (int)nchunk;
+        }
     }
-    auto kern = dsu_ws_kernel<KT, KJ, HK, M_, false, VAR>;
+    auto kern = dsu_ws_kernel<KT, HK, M_, false>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     kern<<<grid, block, smem, s>>>(a, u_slab, (int)rpb, (int)nchunk);
     return (int)nchunk;
@@ -1077,16 +1022,22 @@ void launch_dx2_m(const BwdGArgs& a, hipStream_t s) {
     }
 }
 
-// heads of HK K-steps (head_dim = 32 HK); only the (K, head_dim) pairs with a power-of-two or small head count are built
+// heads of HK K-steps (head_dim = 32 HK); only head_dim = 32, 64, 96, 128, 256 and the single head are built, and only
+// with at most 16 heads (aecf_pool_check)
 template <int KT>
 bool launch_dx2_hk(const BwdGArgs& a, hipStream_t s) {
+    static_assert(KT % 8 == 0 && KT <= 32, "K = 256, 512, 768, 1024");
     const int hk = a.hd / 32;
     if (hk * a.H != KT) return false;
-    if (hk == 1 && KT <= 16) { launch_dx2_m<KT, 1>(a, s); return true; }          // up to 16 heads of 32
-    if (hk == 2 && KT % 2 == 0 && KT <= 32) { launch_dx2_m<KT, (KT % 2 == 0 ? 2 : 1)>(a, s); return true; }
-    if (hk == 3 && KT % 3 == 0) { launch_dx2_m<KT, (KT % 3 == 0 ? 3 : 1)>(a, s); return true; }
-    if (hk == 4 && KT % 4 == 0) { launch_dx2_m<KT, (KT % 4 == 0 ? 4 : 1)>(a, s); return true; }
-    if (hk == 8 && KT % 8 == 0) { launch_dx2_m<KT, (KT % 8 == 0 ? 8 : 1)>(a, s); return true; }
+    if constexpr (KT <= 16) {
+        if (hk == 1) { launch_dx2_m<KT, 1>(a, s); return true; }
+    }
+    if (hk == 2) { launch_dx2_m<KT, 2>(a, s); return true; }
+    if constexpr (KT % 3 == 0) {
+        if (hk == 3) { launch_dx2_m<KT, 3>(a, s); return true; }
+    }
+    if (hk == 4) { launch_dx2_m<KT, 4>(a, s); return true; }
+    if (hk == 8) { launch_dx2_m<KT, 8>(a, s); return true; }
     if (hk == KT) { launch_dx2_m<KT, KT>(a, s); return true; }                     // a single head
     return false;
 }
@@ -1346,17 +1297,29 @@ void launch_ws(const GemmNtArgs& a, hipStream_t s) {
     kern<<<grid, block, smem, s>>>(a, (int)rpb, (int)nchunk);
 }
 
+// the forms gemm_ws_supported admits at K = 32 KT (only these are built): the pooled ones need N = E = K to be a multiple of
+// 256 (not K = 128 / 384); the flat form is M = 4 where two per-sample tiles exceed 150 KB (K = 768 / 1024), and takes
+// those shapes from the per-sample form; the per-sample form (+ the score partials when gated) within 150 KB of LDS
+constexpr bool ws_built(int KT, int MODE, int M, bool gate) {
+    if (MODE == WS_PLAIN) return true;
+    if (KT == 4 || KT == 12) return false;
+    if (MODE == WS_VFLAT) return KT >= 24;
+    if (M == 4) return KT <= 16;
+    return 2 * 16 * M * 2 * 32 * KT + (gate ? 8 * M * 1024 : 0) <= 150 * 1024;
+}
+
 template <int MODE, int M_, bool GATE>
 void launch_kt(const GemmNtArgs& a, hipStream_t s) {
     switch (a.K / 32) {
-        case 4: launch_ws<4, MODE, M_, GATE>(a, s); break;
-        case 8: launch_ws<8, MODE, M_, GATE>(a, s); break;
-        case 12: launch_ws<12, MODE, M_, GATE>(a, s); break;
+        case 4: if constexpr (ws_built(4, MODE, M_, GATE)) launch_ws<4, MODE, M_, GATE>(a, s); break;
+        case 8: if constexpr (ws_built(8, MODE, M_, GATE)) launch_ws<8, MODE, M_, GATE>(a, s); break;
+        case 12: if constexpr (ws_built(12, MODE, M_, GATE)) launch_ws<12, MODE, M_, GATE>(a, s); break;
         case 16:                                                   // hot shape (K = 512): the gated form is the column slab
-            if constexpr (GATE) launch_vproj_slab<M_>(a, s); else launch_ws<16, MODE, M_, GATE>(a, s);
+            if constexpr (GATE) launch_vproj_slab<M_>(a, s);
+            else if constexpr (ws_built(16, MODE, M_, GATE)) launch_ws<16, MODE, M_, GATE>(a, s);
             break;
-        case 24: launch_ws<24, MODE, M_, GATE>(a, s); break;
-        default: launch_ws<32, MODE, M_, GATE>(a, s); break;
+        case 24: if constexpr (ws_built(24, MODE, M_, GATE)) launch_ws<24, MODE, M_, GATE>(a, s); break;
+        default: if constexpr (ws_built(32, MODE, M_, GATE)) launch_ws<32, MODE, M_, GATE>(a, s); break;
     }
 }
 
@@ -1432,10 +1395,10 @@ bool dsu_ws_takes_lo(const BwdGArgs& a) {
 template <int KT, int HK>
 static int launch_dsu_m(const BwdGArgs& a, float* u_slab, hipStream_t s) {
     switch (a.M) {
-        case 1: return launch_dsu_t<KT, 8, HK, 1>(a, u_slab, s);
-        case 2: return launch_dsu_t<KT, 8, HK, 2>(a, u_slab, s);
-        case 3: return launch_dsu_t<KT, 8, HK, 3>(a, u_slab, s);
-        default: return launch_dsu_t<KT, 8, HK, 4>(a, u_slab, s);
+        case 1: return launch_dsu_t<KT, HK, 1>(a, u_slab, s);
+        case 2: return launch_dsu_t<KT, HK, 2>(a, u_slab, s);
+        case 3: return launch_dsu_t<KT, HK, 3>(a, u_slab, s);
+        default: return launch_dsu_t<KT, HK, 4>(a, u_slab, s);
     }
 }
 

@@ -193,7 +193,6 @@ struct FinalizeArgs {
     const float* qs;
     const float* u;       // [HPAD,E] reduced
     const float* dqp;     // [E] dq' (DqpJob: side job of the dW_v launch, or launch_dqp)
-    float* dq_part;       // (unused since round 4)
     void* dw_in;          // [3E,E]  float32, or bf16 / f16 (grad_gt)
     void* db_in;          // [3E]
     void* dquery;         // [E]

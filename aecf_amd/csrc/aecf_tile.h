@@ -39,6 +39,17 @@ __device__ __forceinline__ bool xcd_tile(unsigned int id, unsigned int npanel, u
     return (id >> 3) < per && q < total;
 }
 
+// head slots of a batch-reduction block = the most heads (of hd rows) any aligned window of `window` output rows of E touches
+inline int head_slots(int E, int hd, int window) {
+    int mx = 1;
+    for (int j0 = 0; j0 < E; j0 += window) {
+        const int j1 = (j0 + window < E ? j0 + window : E) - 1;
+        const int n = j1 / hd - j0 / hd + 1;
+        if (n > mx) mx = n;
+    }
+    return mx;
+}
+
 template <typename T> struct TileK;   // elements of K per 128-byte LDS row
 template <> struct TileK<BF16> { static constexpr int value = 64; };
 template <> struct TileK<F32> { static constexpr int value = 32; };
