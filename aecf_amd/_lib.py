@@ -158,6 +158,21 @@ _SYMBOLS = [
     ("aecf_nce_fwd_bwd", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_void_p, c_size_t, c_void_p]),
+    # device temperature: (const float* temperature, float min_temperature) in place of the float, + float* d_temperature
+    ("aecf_nce_fwd_bwd_dt", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("aecf_loss_fwd_bwd_dt", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_int64, c_int32, c_float, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("aecf_nce_sym_pass1_dt", c_int,
+     [c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("aecf_nce_sym_loss_dt", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+      c_int64, c_int32, c_float, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    ("aecf_nce_sym_grads_dt", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+      c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 

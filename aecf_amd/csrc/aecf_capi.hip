@@ -799,6 +799,79 @@ int aecf_nce_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d
     return launch_status();
 }
 
+// ---- the same five calls with the temperature on the device (include/aecf_hip.h, "device temperature")
+
+int aecf_loss_fwd_bwd_dt(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                         float coef, const void* q, const void* k, float* loss_rows, float* dq, float* dk, float* d_temperature,
+                         int64_t n_entropy, int32_t last_seq_len, float entropy_target, const float* entropy,
+                         float entropy_upstream, float* entropy_loss, float* d_entropy, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || n_entropy < 0) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!temperature || !q || !k || !loss_rows || !dq || !dk || !workspace) return AECF_ERR_NULL_POINTER;
+    if (n_entropy > 0 && (!entropy || !entropy_loss)) return AECF_ERR_NULL_POINTER;
+    const double max_ent = last_seq_len > 1 ? log((double)last_seq_len) : 0.0;       // ref :301-308
+    const float ent_t = (float)(max_ent * (double)entropy_target);
+    const float* ent = n_entropy > 0 ? entropy : nullptr;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    if (nce_gemm_supported(AECF_BF16, d, min_temperature) && workspace_bytes >= nce_gemm_workspace_bytes(rows, cols, d)) {
+        launch_nce_gemm_pass1(rows, cols, d, 0.f, q, k, workspace, nullptr, (hipStream_t)stream, &dt);
+        launch_nce_gemm_loss(rows, cols, row_offset, d, 0.f, 0, q, k, nullptr, workspace, loss_rows, ent, n_entropy, ent_t,
+                             entropy_upstream, d_entropy, entropy_loss, (hipStream_t)stream, &dt);
+        launch_nce_gemm_grads(rows, cols, row_offset, d, 0.f, coef, 0, q, k, workspace, nullptr, 0, dq, dk, (hipStream_t)stream, &dt);
+        return launch_status();
+    }
+    if (!nce_flash_supported(AECF_BF16, d)) return AECF_ERR_UNSUPPORTED;
+    if (workspace_bytes < nce_flash_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    launch_nce_flash(rows, cols, row_offset, d, 0.f, coef, q, k, loss_rows, dq, dk, workspace, ent, n_entropy, ent_t,
+                     entropy_upstream, d_entropy, entropy_loss, (hipStream_t)stream, &dt);
+    return launch_status();
+}
+
+int aecf_nce_sym_pass1_dt(int64_t rows, int64_t cols, int32_t d, const float* temperature, float min_temperature, const void* a,
+                          const void* b, void* workspace, size_t workspace_bytes, float* col_sums, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!nce_gemm_supported(AECF_BF16, d, min_temperature)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a || !b || !workspace || !col_sums) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_nce_gemm_pass1(rows, cols, d, 0.f, a, b, workspace, col_sums, (hipStream_t)stream, &dt);
+    return launch_status();
+}
+
+int aecf_nce_sym_loss_dt(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                         const void* a, const void* b, const float* col_sums, void* workspace, size_t workspace_bytes,
+                         float* loss_rows, int64_t n_entropy, int32_t last_seq_len, float entropy_target, const float* entropy,
+                         float entropy_upstream, float* entropy_loss, float* d_entropy, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || n_entropy < 0) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!nce_gemm_supported(AECF_BF16, d, min_temperature)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a || !b || !col_sums || !workspace || !loss_rows) return AECF_ERR_NULL_POINTER;
+    if (n_entropy > 0 && (!entropy || !entropy_loss)) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const double max_ent = last_seq_len > 1 ? log((double)last_seq_len) : 0.0;       // ref :301-308
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_nce_gemm_loss(rows, cols, row_offset, d, 0.f, 1, a, b, col_sums, workspace, loss_rows, n_entropy > 0 ? entropy : nullptr,
+                         n_entropy, (float)(max_ent * (double)entropy_target), entropy_upstream, d_entropy, entropy_loss,
+                         (hipStream_t)stream, &dt);
+    return launch_status();
+}
+
+int aecf_nce_sym_grads_dt(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                          float coef, const void* a, const void* b, void* workspace, size_t workspace_bytes, const float* upstream,
+                          int32_t grad_dtype, void* da, void* db, float* d_temperature, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f)) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (grad_dtype != AECF_BF16 && grad_dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!nce_gemm_supported(AECF_BF16, d, min_temperature)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a || !b || !workspace || !da || !db) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    launch_nce_gemm_grads(rows, cols, row_offset, d, 0.f, coef, 1, a, b, workspace, upstream, grad_dtype == AECF_BF16 ? 1 : 0, da, db,
+                          (hipStream_t)stream, &dt);
+    return launch_status();
+}
+
 int aecf_route_build(int64_t rows, const uint8_t* present_a, const uint8_t* present_b, int32_t* route, int32_t* slot,
                      int32_t* index, int32_t* counts, void* stream) {
     if (rows <= 0 || rows > 0x7fffffff) return AECF_ERR_BAD_DIMS;
@@ -911,6 +984,33 @@ static size_t nce_generic_workspace_bytes(int64_t rows, int64_t cols, int32_t d,
     return align_up((size_t)rows * cols * 4) + align_up((size_t)rows * cols * es) + align_up((size_t)d * cols * es);
 }
 
+// the materialising form of aecf_nce_fwd_bwd (float32, or d outside the streaming kernels' set): float32 logits in the workspace
+static void nce_generic_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t dtype, float inv_temp, float coef,
+                                const void* q, const void* k, float* loss_rows, float* dq, float* dk, void* workspace, hipStream_t s,
+                                const NceDevTemp* dt) {
+    const size_t es = esize(dtype);
+    char* ws = (char*)workspace;
+    float* S = (float*)ws;
+    void* G = ws + align_up((size_t)rows * cols * 4);
+    void* kT = (char*)G + align_up((size_t)rows * cols * es);
+
+    GemmNtArgs g1;       // S = q k^T  (float32 logits before the temperature)
+    g1.a = q; g1.w = k; g1.bias = nullptr; g1.c = S; g1.probs = nullptr; g1.R = rows; g1.N = (int)cols; g1.K = d;
+    g1.lda = d; g1.M = 1; g1.H = 1; g1.hd = d; g1.pooled = 0; g1.out_f32 = 1; g1.v_out = nullptr;
+    launch_gemm_nt(dtype, g1, s);
+    launch_nce_rows(dtype, rows, cols, row_offset, inv_temp, coef, S, G, loss_rows, s, dt, (float*)kT);   // (kT: written next)
+    launch_transpose_rect(dtype, k, kT, cols, d, s);
+    GemmNtArgs g2;       // dq = G k
+    g2.a = G; g2.w = kT; g2.bias = nullptr; g2.c = dq; g2.probs = nullptr; g2.R = rows; g2.N = d; g2.K = (int)cols;
+    g2.lda = cols; g2.M = 1; g2.H = 1; g2.hd = d; g2.pooled = 0; g2.out_f32 = 1; g2.v_out = nullptr;
+    launch_gemm_nt(dtype, g2, s);
+    GemmTnArgs t;        // dk = G^T q   (reduction over the local rows)
+    t.lhs = G; t.rhs = q; t.probs = nullptr; t.dsbuf = nullptr; t.out = dk; t.colsum = nullptr; t.u = nullptr;
+    t.B = rows; t.M = 1; t.E = d; t.H = 1; t.hd = d; t.Ej = (int)cols; t.splits = 1; t.u_splits = 0; t.u_rows_per_split = 0;
+    t.rows_per_split = (rows + 63) / 64 * 64; t.pooled = 0;
+    launch_gemm_tn(dtype, t, s);
+}
+
 // The form aecf_nce_fwd_bwd takes depends on the TEMPERATURE as well (the tile GEMMs' constant-shift softmax needs
 // 1/T within the float32 exponent range), which this query does not see: it answers the LARGEST workspace any form
 // that can be selected for (d, dtype) needs, so the call never runs a form on a buffer sized for another one.
@@ -958,28 +1058,36 @@ int aecf_nce_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, 
     }
     if (d % 64 != 0 || cols % 64 != 0) return AECF_ERR_UNSUPPORTED;
     if (workspace_bytes < nce_generic_workspace_bytes(rows, cols, d, dtype)) return AECF_ERR_WORKSPACE;   // its OWN size
-    hipStream_t s = (hipStream_t)stream;
-    const size_t es = esize(dtype);
-    char* ws = (char*)workspace;
-    float* S = (float*)ws;
-    void* G = ws + align_up((size_t)rows * cols * 4);
-    void* kT = (char*)G + align_up((size_t)rows * cols * es);
+    nce_generic_fwd_bwd(rows, cols, row_offset, d, dtype, 1.0f / temperature, coef, q, k, loss_rows, dq, dk, workspace,
+                        (hipStream_t)stream, nullptr);
+    return launch_status();
+}
 
-    GemmNtArgs g1;       // S = q k^T  (float32 logits before the temperature)
-    g1.a = q; g1.w = k; g1.bias = nullptr; g1.c = S; g1.probs = nullptr; g1.R = rows; g1.N = (int)cols; g1.K = d;
-    g1.lda = d; g1.M = 1; g1.H = 1; g1.hd = d; g1.pooled = 0; g1.out_f32 = 1; g1.v_out = nullptr;
-    launch_gemm_nt(dtype, g1, s);
-    launch_nce_rows(dtype, rows, cols, row_offset, 1.0f / temperature, coef, S, G, loss_rows, s);
-    launch_transpose_rect(dtype, k, kT, cols, d, s);
-    GemmNtArgs g2;       // dq = G k
-    g2.a = G; g2.w = kT; g2.bias = nullptr; g2.c = dq; g2.probs = nullptr; g2.R = rows; g2.N = d; g2.K = (int)cols;
-    g2.lda = cols; g2.M = 1; g2.H = 1; g2.hd = d; g2.pooled = 0; g2.out_f32 = 1; g2.v_out = nullptr;
-    launch_gemm_nt(dtype, g2, s);
-    GemmTnArgs t;        // dk = G^T q   (reduction over the local rows)
-    t.lhs = G; t.rhs = q; t.probs = nullptr; t.dsbuf = nullptr; t.out = dk; t.colsum = nullptr; t.u = nullptr;
-    t.B = rows; t.M = 1; t.E = d; t.H = 1; t.hd = d; t.Ej = (int)cols; t.splits = 1; t.u_splits = 0; t.u_rows_per_split = 0;
-    t.rows_per_split = (rows + 63) / 64 * 64; t.pooled = 0;
-    launch_gemm_tn(dtype, t, s);
+int aecf_nce_fwd_bwd_dt(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t dtype, const float* temperature,
+                        float min_temperature, float coef, const void* q, const void* k, float* loss_rows, float* dq, float* dk,
+                        float* d_temperature, void* workspace, size_t workspace_bytes, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f)) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (dtype != AECF_BF16 && dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !q || !k || !loss_rows || !dq || !dk || !workspace) return AECF_ERR_NULL_POINTER;
+    hipStream_t s = (hipStream_t)stream;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    if (nce_gemm_supported(dtype, d, min_temperature) && workspace_bytes >= nce_gemm_workspace_bytes(rows, cols, d)) {
+        launch_nce_gemm_pass1(rows, cols, d, 0.f, q, k, workspace, nullptr, s, &dt);
+        launch_nce_gemm_loss(rows, cols, row_offset, d, 0.f, 0, q, k, nullptr, workspace, loss_rows, nullptr, 0, 0.f, 0.f, nullptr,
+                             nullptr, s, &dt);
+        launch_nce_gemm_grads(rows, cols, row_offset, d, 0.f, coef, 0, q, k, workspace, nullptr, 0, dq, dk, s, &dt);
+        return launch_status();
+    }
+    if (nce_flash_supported(dtype, d)) {
+        if (workspace_bytes < nce_flash_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+        launch_nce_flash(rows, cols, row_offset, d, 0.f, coef, q, k, loss_rows, dq, dk, workspace, nullptr, 0, 0.f, 0.f, nullptr,
+                         nullptr, s, &dt);
+        return launch_status();
+    }
+    if (d % 64 != 0 || cols % 64 != 0) return AECF_ERR_UNSUPPORTED;
+    if (workspace_bytes < nce_generic_workspace_bytes(rows, cols, d, dtype)) return AECF_ERR_WORKSPACE;
+    nce_generic_fwd_bwd(rows, cols, row_offset, d, dtype, 0.f, coef, q, k, loss_rows, dq, dk, workspace, s, &dt);
     return launch_status();
 }
 

@@ -60,13 +60,16 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// one block per local row
-template <typename T>
+// one block per local row.  DT: the temperature comes from the device, and tdot[row] = sum_j G_ij S_ij from the float32 G (the
+// row's share of -T dL/dT; tdot = NULL: not wanted)
+template <typename T, bool DT>
 __global__ __launch_bounds__(256) void nce_rows_kernel(int64_t cols, int64_t row_offset, float inv_temp, float coef,
                                                        const float* __restrict__ S, typename Tr<T>::elem* __restrict__ G,
-                                                       float* __restrict__ loss_rows) {
+                                                       float* __restrict__ loss_rows, const float* temp, float min_temp,
+                                                       float* __restrict__ tdot) {
     using X = Tr<T>;
     __shared__ float red[4];
+    if (DT) inv_temp = nce_dev_inv_temp(temp, min_temp);
     const int64_t row = blockIdx.x;
     const float* s = S + row * cols;
     typename X::elem* g = G + row * cols;
@@ -79,11 +82,36 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(int64_t cols, int64_t row
     const float lse = mx + logf(sum);
     const int64_t pos = row_offset + row;
     const float scale = coef * inv_temp;
+    float gs = 0.f;
     for (int64_t j = threadIdx.x; j < cols; j += 256) {
         const float pj = expf(s[j] * inv_temp - lse);
-        g[j] = X::from_f32((pj - (j == pos ? 1.0f : 0.0f)) * scale);
+        const float gj = (pj - (j == pos ? 1.0f : 0.0f)) * scale;
+        g[j] = X::from_f32(gj);
+        if (DT) gs = fmaf(gj, s[j], gs);
     }
     if (threadIdx.x == 0) loss_rows[row] = lse - s[pos] * inv_temp;
+    if (DT && tdot) {
+        gs = block_reduce_sum(gs, red);
+        if (threadIdx.x == 0) tdot[row] = gs;
+    }
+}
+
+// d_t[0] = -(1/Tc) sum_k part[k * stride] (0 where T < min_t): 256 strided partial sums in order, then a fixed tree
+__global__ __launch_bounds__(256) void nce_dtemp_kernel(const float* part, int64_t n, int64_t stride, const float* t, float min_t,
+                                                        float* d_t) {
+    __shared__ float red[256];
+    float s = 0.f;
+    for (int64_t k = threadIdx.x; k < n; k += 256) s += part[k * stride];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float tv = *t, tc = fmaxf(tv, min_t);
+        d_t[0] = tv >= min_t ? -red[0] / tc : 0.f;
+    }
 }
 
 template <typename T>
@@ -111,10 +139,25 @@ void launch_l2norm_bwd(int dtype, int64_t n, int d, const void* zn, const float*
 }
 
 void launch_nce_rows(int dtype, int64_t rows, int64_t cols, int64_t row_offset, float inv_temp, float coef, const float* S,
-                     void* G, float* loss_rows, hipStream_t s) {
+                     void* G, float* loss_rows, hipStream_t s, const NceDevTemp* dt, float* tdot_scratch) {
     dim3 grid((unsigned)rows), block(256);
-    if (dtype == 0) nce_rows_kernel<BF16><<<grid, block, 0, s>>>(cols, row_offset, inv_temp, coef, S, (unsigned short*)G, loss_rows);
-    else nce_rows_kernel<F32><<<grid, block, 0, s>>>(cols, row_offset, inv_temp, coef, S, (float*)G, loss_rows);
+    if (dt) {
+        float* tdot = dt->d_t ? tdot_scratch : nullptr;
+        if (dtype == 0)
+            nce_rows_kernel<BF16, true><<<grid, block, 0, s>>>(cols, row_offset, 0.f, coef, S, (unsigned short*)G, loss_rows, dt->t,
+                                                               dt->min_t, tdot);
+        else nce_rows_kernel<F32, true><<<grid, block, 0, s>>>(cols, row_offset, 0.f, coef, S, (float*)G, loss_rows, dt->t, dt->min_t, tdot);
+        if (tdot) launch_nce_dtemp(tdot, rows, 1, *dt, s);
+        return;
+    }
+    if (dtype == 0)
+        nce_rows_kernel<BF16, false><<<grid, block, 0, s>>>(cols, row_offset, inv_temp, coef, S, (unsigned short*)G, loss_rows, nullptr,
+                                                            0.f, nullptr);
+    else nce_rows_kernel<F32, false><<<grid, block, 0, s>>>(cols, row_offset, inv_temp, coef, S, (float*)G, loss_rows, nullptr, 0.f, nullptr);
+}
+
+void launch_nce_dtemp(const float* part, int64_t n, int64_t stride, const NceDevTemp& dt, hipStream_t s) {
+    nce_dtemp_kernel<<<dim3(1), dim3(256), 0, s>>>(part, n, stride, dt.t, dt.min_t, dt.d_t);
 }
 
 void launch_transpose_rect(int dtype, const void* src, void* dst, int64_t R, int64_t C, hipStream_t s) {

@@ -220,13 +220,27 @@ void launch_sdpa_bwd(int dtype, int64_t B, int S, int T, int E, float scale, con
                      const float* probs, const void* dout, void* dq, void* dk, void* dv, hipStream_t s);
 
 // ---------------- contrastive (aecf_contrastive.hip) ----------------
+// A temperature that lives on the device (the aecf_*_dt entry points): the kernels use Tc = max(*t, min_t), deriving 1/Tc with
+// the same float operations the host does for a float T (equal T, equal bits).  d_t (optional, NULL = not wanted) is WRITTEN
+// with dL/dT = -(1/Tc) sum_i q_i.dq_i (0 where *t < min_t), reduced in a fixed order from float32 partials.
+struct NceDevTemp {
+    const float* t;
+    float min_t;
+    float* d_t;
+};
+__device__ __forceinline__ float nce_dev_inv_temp(const float* t, float min_t) { return 1.0f / fmaxf(*t, min_t); }
+// d_t[0] from n partials part[k * stride] (one block; fixed order)
+void launch_nce_dtemp(const float* part, int64_t n, int64_t stride, const NceDevTemp& dt, hipStream_t s);
+
 void launch_l2norm_fwd(int dtype, int64_t n, int d, float eps, const void* z, void* zn, float* inv_norm, hipStream_t s);
 void launch_l2norm_bwd(int dtype, int64_t n, int d, const void* zn, const float* inv_norm, const float* dzn, void* dz,
                        hipStream_t s);
 // per local row i: logits = S[i,:] * inv_temp; loss_rows[i] = logsumexp - logits[row_offset + i];
 // G[i,:] = (softmax - onehot) * coef * inv_temp   (dtype)
+// dt != NULL: inv_temp comes from the device; with dt->d_t, the rows' sums_j G_ij S_ij go to tdot_scratch [rows] and d_t is
+// formed from those (one more single-block launch)
 void launch_nce_rows(int dtype, int64_t rows, int64_t cols, int64_t row_offset, float inv_temp, float coef, const float* S,
-                     void* G, float* loss_rows, hipStream_t s);
+                     void* G, float* loss_rows, hipStream_t s, const NceDevTemp* dt = nullptr, float* tdot_scratch = nullptr);
 // dst[c][r] = src[r][c]   (R x C, dtype; R, C multiples of 32)
 void launch_modality_frontend(int dtype, int64_t rows, int dim, const void* feat, const uint8_t* drop, void* out,
                               uint8_t* present, hipStream_t s);
@@ -240,18 +254,22 @@ bool nce_flash_supported(int dtype, int d);
 size_t nce_flash_workspace_bytes(int64_t rows, int64_t cols, int d);
 void launch_nce_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, float inv_temp, float coef, const void* q,
                       const void* k, float* loss_rows, float* dq, float* dk, void* workspace, const float* ent, int64_t n_ent,
-                      float ent_target, float ent_upstream, float* d_ent, float* ent_loss, hipStream_t s);
+                      float ent_target, float ent_upstream, float* d_ent, float* ent_loss, hipStream_t s,
+                      const NceDevTemp* dt = nullptr);
 
-// InfoNCE on tile GEMMs (aecf_nce_gemm.hip): bf16 exponentials E [rows, cols] in the workspace, one or both directions
+// InfoNCE on tile GEMMs (aecf_nce_gemm.hip): bf16 exponentials E [rows, cols] in the workspace, one or both directions.
+// dt != NULL: the temperature comes from the device (inv_temp is not read); launch_nce_gemm_grads then also writes dt->d_t.
 bool nce_gemm_supported(int dtype, int d, float temperature);
 size_t nce_gemm_workspace_bytes(int64_t rows, int64_t cols, int d);
 void launch_nce_gemm_pass1(int64_t rows, int64_t cols, int d, float inv_temp, const void* a, const void* b, void* workspace,
-                           float* col_sums, hipStream_t s);
+                           float* col_sums, hipStream_t s, const NceDevTemp* dt = nullptr);
 void launch_nce_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, float inv_temp, int sym, const void* a,
                           const void* b, const float* col_sums, void* workspace, float* loss_rows, const float* ent, int64_t n_ent,
-                          float ent_target, float ent_upstream, float* d_ent, float* ent_loss, hipStream_t s);
+                          float ent_target, float ent_upstream, float* d_ent, float* ent_loss, hipStream_t s,
+                          const NceDevTemp* dt = nullptr);
 void launch_nce_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, float inv_temp, float coef, int sym, const void* a,
-                           const void* b, void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s);
+                           const void* b, void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s,
+                           const NceDevTemp* dt = nullptr);
 
 // ---------------- presence routing (aecf_route.hip) ----------------
 void launch_route_build(int64_t rows, const uint8_t* pa, const uint8_t* pb, int32_t* route, int32_t* slot, int32_t* index,

@@ -29,7 +29,7 @@ namespace {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-enum { NCE_DQ = 0, NCE_DK = 1 };
+enum { NCE_DQ = 0, NCE_DK = 1, NCE_DQ_DT = 2, NCE_DK_DT = 3 };     // _DT: the temperature is read from the device
 
 struct NceFlashArgs {
     const unsigned short* stat;     // stationary rows [ns, d]   (DQ: q, DK: k)
@@ -44,14 +44,18 @@ struct NceFlashArgs {
     float* out;                     // DK: dk [ns, d]
     int ksplit;                     // DQ: key splits
     int64_t strm_per_split;         // DQ: streamed rows per split (multiple of 32)
+    const float* temp;              // _DT modes: inv_temp = 1 / max(*temp, min_temp)
+    float min_temp;
 };
 
 // CSPLIT > 1: the output columns are produced in CSPLIT launches of D / CSPLIT columns each (cpart = which), every one
 // recomputing S -- the 16 x D float32 accumulator of a wave plus the stationary fragments exceed the register file of a
 // wave beyond D = 512 (DQ, whose rescaling touches the accumulator with vector instructions) / D = 768 (DK).
-template <int KT, int MODE, int CSPLIT>
+template <int KT, int MODE_, int CSPLIT>
 __global__ __launch_bounds__(256, 1) void nce_flash_kernel(NceFlashArgs p, int cpart) {
     using X = Tr<BF16>;
+    constexpr int MODE = MODE_ & 1;
+    if (MODE_ >= NCE_DQ_DT) p.inv_temp = nce_dev_inv_temp(p.temp, p.min_temp);
     constexpr int D = 32 * KT, NC = D / 16 / CSPLIT, ROWB = 2 * D;
     const int c_first = cpart * NC;
     constexpr int TILE = 32 * ROWB;
@@ -218,9 +222,16 @@ struct NceCombineArgs {
     float* ent_loss;
     int64_t n_ent;
     float ent_target, ent_scale;
+    // device temperature (DT): inv_temp = 1 / max(*temp, min_temp); with tdot, the wave of row i writes
+    // q_i.dq_i to part_l[i] once it has read that row's partials (nothing reads part_l after this launch)
+    const float* temp;
+    float min_temp;
+    int tdot;
 };
 
+template <bool DT>
 __global__ __launch_bounds__(256) void nce_combine_kernel(NceCombineArgs p) {
+    if (DT) p.inv_temp = nce_dev_inv_temp(p.temp, p.min_temp);
     const int lane = lane_id();
     const int64_t i = (int64_t)blockIdx.x * 4 + wave_id();
     if (i < p.rows) {
@@ -234,7 +245,7 @@ __global__ __launch_bounds__(256) void nce_combine_kernel(NceCombineArgs p) {
         const unsigned short* kp = p.k + (p.row_offset + i) * p.d;
         const unsigned short* qp = p.q + i * p.d;
         const float ct = p.coef * p.inv_temp, inv_l = 1.0f / lstar;
-        float dot = 0.f;
+        float dot = 0.f, tq = 0.f;
         for (int c = lane; c < p.d; c += 64) {
             float o = 0.f;
             for (int s = 0; s < p.ksplit; ++s) {
@@ -242,14 +253,20 @@ __global__ __launch_bounds__(256) void nce_combine_kernel(NceCombineArgs p) {
                 if (ms != -INFINITY) o += p.part_o[((int64_t)s * p.rows + i) * p.d + c] * expf(ms - mstar);
             }
             const float kv = Tr<BF16>::to_f32(kp[c]);
-            p.dq[i * p.d + c] = ct * (o * inv_l - kv);
+            const float g = ct * (o * inv_l - kv);
+            p.dq[i * p.d + c] = g;
             dot = fmaf(Tr<BF16>::to_f32(qp[c]), kv, dot);
+            if (DT) tq = fmaf(Tr<BF16>::to_f32(qp[c]), g, tq);
         }
         dot = reduce_wave(dot);
         if (lane == 0) {
             const float lse = mstar + logf(lstar);
             p.lse[i] = lse;
             p.loss_rows[i] = lse - dot * p.inv_temp;
+        }
+        if (DT && p.tdot) {
+            tq = reduce_wave(tq);
+            if (lane == 0) const_cast<float*>(p.part_l)[i] = tq;
         }
     }
     if (blockIdx.x == 0 && p.n_ent > 0) {                         // entropy regulariser: one block, fixed order
@@ -272,7 +289,7 @@ __global__ __launch_bounds__(256) void nce_combine_kernel(NceCombineArgs p) {
 template <int KT, int MODE>
 void launch_flash_mode(const NceFlashArgs& a, int blocks, hipStream_t s) {
     constexpr int D = 32 * KT;
-    constexpr int CSPLIT = (MODE == NCE_DQ ? (KT >= 32 ? 4 : (KT >= 24 ? 2 : 1)) : (KT >= 32 ? 2 : 1));
+    constexpr int CSPLIT = ((MODE & 1) == NCE_DQ ? (KT >= 32 ? 4 : (KT >= 24 ? 2 : 1)) : (KT >= 32 ? 2 : 1));
     const size_t smem = (size_t)2 * 32 * 2 * D;
     auto kern = nce_flash_kernel<KT, MODE, CSPLIT>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
@@ -303,7 +320,8 @@ size_t nce_flash_workspace_bytes(int64_t rows, int64_t cols, int d) {
 
 void launch_nce_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, float inv_temp, float coef, const void* q,
                       const void* k, float* loss_rows, float* dq, float* dk, void* workspace, const float* ent, int64_t n_ent,
-                      float ent_target, float ent_upstream, float* d_ent, float* ent_loss, hipStream_t s) {
+                      float ent_target, float ent_upstream, float* d_ent, float* ent_loss, hipStream_t s,
+                      const NceDevTemp* dt) {
     const int ks = nce_flash_ksplit(rows, cols);
     float* ws = reinterpret_cast<float*>(workspace);
     float* part_m = ws;
@@ -323,9 +341,29 @@ void launch_nce_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, flo
     c.dq = dq; c.loss_rows = loss_rows; c.lse = lse; c.rows = rows; c.row_offset = row_offset; c.d = d; c.ksplit = ks;
     c.inv_temp = inv_temp; c.coef = coef; c.ent = ent; c.d_ent = d_ent; c.ent_loss = ent_loss; c.n_ent = ent ? n_ent : 0;
     c.ent_target = ent_target; c.ent_scale = n_ent > 0 ? 2.0f * ent_upstream / (float)n_ent : 0.f;
+    a.temp = b.temp = c.temp = nullptr; a.min_temp = b.min_temp = c.min_temp = 0.f; c.tdot = 0;
+    if (dt) {
+        // device temperature: the _DT instances; the temperature gradient from the float32 dq of the combine launch
+        a.temp = b.temp = c.temp = dt->t; a.min_temp = b.min_temp = c.min_temp = dt->min_t; c.tdot = dt->d_t != nullptr;
+#define NCE_KT(KT_)                                                                                  \
+        launch_flash_mode<KT_, NCE_DQ_DT>(a, (int)(((rows + 63) / 64) * ks), s);                     \
+        nce_combine_kernel<true><<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s>>>(c);            \
+        launch_flash_mode<KT_, NCE_DK_DT>(b, (int)((cols + 63) / 64), s);
+        switch (d / 32) {
+            case 4: NCE_KT(4) break;
+            case 8: NCE_KT(8) break;
+            case 12: NCE_KT(12) break;
+            case 16: NCE_KT(16) break;
+            case 24: NCE_KT(24) break;
+            default: NCE_KT(32) break;
+        }
+#undef NCE_KT
+        if (dt->d_t) launch_nce_dtemp(part_l, rows, 1, *dt, s);
+        return;
+    }
 #define NCE_KT(KT_)                                                                                  \
     launch_flash_mode<KT_, NCE_DQ>(a, (int)(((rows + 63) / 64) * ks), s);                            \
-    nce_combine_kernel<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s>>>(c);                   \
+    nce_combine_kernel<false><<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s>>>(c);            \
     launch_flash_mode<KT_, NCE_DK>(b, (int)((cols + 63) / 64), s);
     switch (d / 32) {
         case 4: NCE_KT(4) break;

@@ -33,7 +33,10 @@ namespace aecf {
 namespace {
 
 enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the tiled E (m operand of db)
-enum { EPI_EXP = 0, EPI_OUT = 1 };
+// _DT / _TD forms (device temperature): EPI_EXP_DT derives scale2 / shift2 from max(*temp, min_temp); EPI_OUT_TD also writes the
+// block's sum of acc * (the bf16 m-operand rows of tdot_src at the output's position) -- q_i.dq_i summed over the tile, from the
+// float32 accumulator -- to tdot_part[(split m_tiles + mi) n_tiles + ni]
+enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3 };
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -60,6 +63,12 @@ struct NceGemmArgs {
     void* out;                          // [splits][m_valid][ldo] float32, or (out_bf16, no splits) bf16
     int64_t ldo, slab_stride;
     int out_bf16;
+    // EPI_EXP_DT
+    const float* temp;
+    float min_temp;
+    // EPI_OUT_TD
+    const unsigned short* tdot_src;     // [m_valid][ldo] bf16
+    float* tdot_part;                   // [splits][m_tiles][n_tiles]
 };
 
 #pragma clang diagnostic push
@@ -300,7 +309,7 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
         // ---- epilogue: lane (r16, lg) holds C[m = 128 wm + 16 rt + r16][n = 64 wn + 16 ct + 4 lg + r], r = 0..3
         const int64_t gi0 = (int64_t)BT * mi + 128 * wm + r16;
         const int gj0 = BT * ni + 64 * wn + 4 * lg;
-        if (EPI == EPI_OUT) {
+        if (EPI == EPI_OUT || EPI == EPI_OUT_TD) {
             float* o = reinterpret_cast<float*>(p.out) + (int64_t)split * p.slab_stride;
             unsigned short* ob = reinterpret_cast<unsigned short*>(p.out);
 #pragma unroll
@@ -319,7 +328,41 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                     }
                 }
             }
+            if (EPI == EPI_OUT_TD) {
+                float td = 0.f;
+#pragma unroll
+                for (int rt = 0; rt < 8; ++rt) {
+                    const int64_t i = gi0 + 16 * rt;
+                    if (i < p.m_valid) {
+#pragma unroll
+                        for (int ct = 0; ct < 4; ++ct) {
+                            const int j = gj0 + 16 * ct;
+                            if (j < p.n_valid) {
+                                const u32x2 x = *reinterpret_cast<const u32x2*>(p.tdot_src + i * p.ldo + j);
+                                td = fmaf(acc[rt][ct][0], __uint_as_float(x[0] << 16), td);
+                                td = fmaf(acc[rt][ct][1], __uint_as_float(x[0] & 0xffff0000u), td);
+                                td = fmaf(acc[rt][ct][2], __uint_as_float(x[1] << 16), td);
+                                td = fmaf(acc[rt][ct][3], __uint_as_float(x[1] & 0xffff0000u), td);
+                            }
+                        }
+                    }
+                }
+                td = reduce_wave(td);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();                   // every wave is past its last read of the stages
+                float* red = reinterpret_cast<float*>(smem);
+                if (lane == 0) red[w] = td;
+                __syncthreads();
+                if (threadIdx.x == 0)
+                    p.tdot_part[((int64_t)split * p.m_tiles + mi) * p.n_tiles + ni] =
+                        ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
+            }
         } else {
+            float scale2 = p.scale2, shift2 = p.shift2;
+            if (EPI == EPI_EXP_DT) {
+                scale2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f;
+                shift2 = scale2;
+            }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
             // E = exp2(acc scale - shift): 4 consecutive columns per lane, 8-byte stores (16 rows x 32 B per wave-instruction).
@@ -340,10 +383,10 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                 for (int ct = 0; ct < 4; ++ct) {
                     const int j = gj0 + 16 * ct;
                     f32x2 e01, e23;
-                    e01[0] = __builtin_amdgcn_exp2f(acc[rt][ct][0] * p.scale2 - p.shift2);
-                    e01[1] = __builtin_amdgcn_exp2f(acc[rt][ct][1] * p.scale2 - p.shift2);
-                    e23[0] = __builtin_amdgcn_exp2f(acc[rt][ct][2] * p.scale2 - p.shift2);
-                    e23[1] = __builtin_amdgcn_exp2f(acc[rt][ct][3] * p.scale2 - p.shift2);
+                    e01[0] = __builtin_amdgcn_exp2f(acc[rt][ct][0] * scale2 - shift2);
+                    e01[1] = __builtin_amdgcn_exp2f(acc[rt][ct][1] * scale2 - shift2);
+                    e23[0] = __builtin_amdgcn_exp2f(acc[rt][ct][2] * scale2 - shift2);
+                    e23[1] = __builtin_amdgcn_exp2f(acc[rt][ct][3] * scale2 - shift2);
                     if (edge) {
                         const bool iok = i < p.m_valid;
                         e01[0] = (iok && j + 0 < p.n_valid) ? e01[0] : 0.f;
@@ -429,11 +472,15 @@ struct NceFinArgs {
     float* ent_loss;
     int64_t n_ent;
     float ent_target, ent_scale;
+    const float* temp;                  // DT: inv_temp = 1 / max(*temp, min_temp)
+    float min_temp;
 };
 
 // one wave per local row: u_i, the positive logit a_i.b_pos, loss_i = log l_i + 1/T - s_ii/T (+ log c_pos + 1/T - s_ii/T);
 // the waves past the rows fill v; block 0 also carries CurriculumMasking.entropy_loss (ref aecf/AECFLayer.py:285-314)
+template <bool DT>
 __global__ __launch_bounds__(256) void nce_finalize_kernel(NceFinArgs p) {
+    if (DT) p.inv_temp = nce_dev_inv_temp(p.temp, p.min_temp);
     const int lane = lane_id();
     const int64_t i = (int64_t)blockIdx.x * 4 + wave_id();
     if (i < p.rows) {
@@ -474,9 +521,9 @@ __global__ __launch_bounds__(256) void nce_finalize_kernel(NceFinArgs p) {
 
 // W = ct (E (u_i + v_j) - npos [j = off + i]) in place over the tiled E, 8 elements per thread.  The positive's weight is a
 // small difference of O(1) terms (softmax weight minus one): it is formed from the float32 exponential, not from the bf16 one.
-__global__ __launch_bounds__(256) void nce_weights_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
-                                                          const float* v, const float* ediag, int64_t rows, int64_t row_offset,
-                                                          float ct, float npos, const float* upstream) {
+__device__ __forceinline__ void nce_weights_body(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u, const float* v,
+                                                 const float* ediag, int64_t rows, int64_t row_offset, float ct, float npos,
+                                                 const float* upstream) {
     const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;         // 16-byte chunk: 2048 per tile, 8 per tile row
     if (id >= m_tiles * e_tiles * 2048) return;
     const int64_t tile = id >> 11;
@@ -498,6 +545,20 @@ __global__ __launch_bounds__(256) void nce_weights_kernel(unsigned short* e, int
         x[k] = ct * wv;
     }
     *ptr = Tr<BF16>::pack(x);
+}
+
+__global__ __launch_bounds__(256) void nce_weights_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
+                                                          const float* v, const float* ediag, int64_t rows, int64_t row_offset,
+                                                          float ct, float npos, const float* upstream) {
+    nce_weights_body(e, e_tiles, m_tiles, u, v, ediag, rows, row_offset, ct, npos, upstream);
+}
+
+// ct = coef / max(*temp, min_temp), formed as the host forms coef * (1 / T)
+__global__ __launch_bounds__(256) void nce_weights_dt_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
+                                                             const float* v, const float* ediag, int64_t rows, int64_t row_offset,
+                                                             float coef, float npos, const float* upstream, const float* temp,
+                                                             float min_temp) {
+    nce_weights_body(e, e_tiles, m_tiles, u, v, ediag, rows, row_offset, coef * nce_dev_inv_temp(temp, min_temp), npos, upstream);
 }
 
 // out[i] = sum_s slab[s][i], float4 (rounded once to bf16 when the caller wants the gradient in that dtype)
@@ -578,7 +639,7 @@ size_t nce_gemm_workspace_bytes(int64_t rows, int64_t cols, int d) { return carv
 
 // pass 1: E, row sums (workspace) and this rank's column sums (col_sums, may be NULL when sym == 0)
 void launch_nce_gemm_pass1(int64_t rows, int64_t cols, int d, float inv_temp, const void* a, const void* b, void* workspace,
-                           float* col_sums, hipStream_t s) {
+                           float* col_sums, hipStream_t s, const NceDevTemp* dt) {
     const NceWs w = carve(workspace, rows, cols, d);
     const int64_t Rp = up256(rows), Cp = up256(cols);
     NceGemmArgs g = {};
@@ -593,7 +654,12 @@ void launch_nce_gemm_pass1(int64_t rows, int64_t cols, int d, float inv_temp, co
     g.rowsum_part = w.rowsum_part; g.colsum_part = w.colsum_part;
     const unsigned int nsm = (g.m_tiles + 3) / 4, nsn = (g.n_tiles + 7) / 8;
     const unsigned int blocks = ((nsm * nsn + 7) / 8) * 8 * 32;
-    launch_gemm<OP_ROW, OP_ROW, EPI_EXP, MAP_2D>(g, blocks, s);
+    if (dt) {
+        g.temp = dt->t; g.min_temp = dt->min_t;
+        launch_gemm<OP_ROW, OP_ROW, EPI_EXP_DT, MAP_2D>(g, blocks, s);
+    } else {
+        launch_gemm<OP_ROW, OP_ROW, EPI_EXP, MAP_2D>(g, blocks, s);
+    }
     nce_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64)), dim3(256), 0, s>>>(w.rowsum_part, w.colsum_part, g.m_tiles, g.n_tiles,
                                                                                    rows, cols, w.l, col_sums ? col_sums : w.c_local);
 }
@@ -601,7 +667,7 @@ void launch_nce_gemm_pass1(int64_t rows, int64_t cols, int d, float inv_temp, co
 // normalisers + loss rows (col_sums: all ranks' sums when sym; NULL = pass 1's own) [+ the entropy regulariser riding along]
 void launch_nce_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, float inv_temp, int sym, const void* a,
                           const void* b, const float* col_sums, void* workspace, float* loss_rows, const float* ent, int64_t n_ent,
-                          float ent_target, float ent_upstream, float* d_ent, float* ent_loss, hipStream_t s) {
+                          float ent_target, float ent_upstream, float* d_ent, float* ent_loss, hipStream_t s, const NceDevTemp* dt) {
     const NceWs w = carve(workspace, rows, cols, d);
     const int64_t Rp = up256(rows), Cp = up256(cols);
     NceFinArgs f = {};
@@ -610,18 +676,28 @@ void launch_nce_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d,
     f.d = d; f.sym = sym; f.inv_temp = inv_temp;
     f.ent = ent; f.d_ent = d_ent; f.ent_loss = ent_loss; f.n_ent = ent ? n_ent : 0; f.ent_target = ent_target;
     f.ent_scale = n_ent > 0 ? 2.0f * ent_upstream / (float)n_ent : 0.f;
-    nce_finalize_kernel<<<dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, s>>>(f);
+    if (dt) {
+        f.temp = dt->t; f.min_temp = dt->min_t;
+        nce_finalize_kernel<true><<<dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, s>>>(f);
+    } else {
+        nce_finalize_kernel<false><<<dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, s>>>(f);
+    }
 }
 
 // gradients: weights in place over E (scaled by the device scalar `upstream` when given), da = W b, db = W^T a; outputs float32
 // or -- one rounding of the float32 sums -- bf16.  launch_nce_gemm_loss must have run on this workspace.
 void launch_nce_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, float inv_temp, float coef, int sym, const void* a,
-                           const void* b, void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s) {
+                           const void* b, void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s,
+                           const NceDevTemp* dt) {
     const NceWs w = carve(workspace, rows, cols, d);
     const int64_t Rp = up256(rows), Cp = up256(cols);
     const int64_t chunks = Rp * (Cp / 8);
-    nce_weights_kernel<<<dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset,
-                                                                                    coef * inv_temp, sym ? 2.0f : 1.0f, upstream);
+    if (dt)
+        nce_weights_dt_kernel<<<dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s>>>(
+            w.e, Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset, coef, sym ? 2.0f : 1.0f, upstream, dt->t, dt->min_t);
+    else
+        nce_weights_kernel<<<dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset,
+                                                                                        coef * inv_temp, sym ? 2.0f : 1.0f, upstream);
     const int n_tiles_d = (d + BT - 1) / BT;
     {   // da = W b: m = local rows, n = d, K = keys
         NceGemmArgs g = {};
@@ -635,12 +711,22 @@ void launch_nce_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d
         g.out = g.splits > 1 ? (void*)w.slabs : da; g.ldo = d; g.slab_stride = rows * (int64_t)d;
         g.out_bf16 = g.splits > 1 ? 0 : out_bf16;
         const unsigned int units = (unsigned)(g.m_tiles * g.splits);
-        if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_OUT, MAP_SPLITX>(g, 8u * g.m_tiles * g.n_tiles, s);
-        else launch_gemm<OP_ROW, OP_COL, EPI_OUT, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
+        if (dt && dt->d_t) {
+            // dL/dT = -(1/T) sum_i a_i.da_i: per-block partials of the float32 products (this rank's rows, both directions when
+            // sym), into the row-sum partials pass 1 left behind (dead since its sums launch; splits <= max(1, Cp / 512) and
+            // n_tiles <= 16, so the splits m_tiles n_tiles partials fit in its Cp m_tiles floats)
+            g.tdot_src = (const unsigned short*)a; g.tdot_part = w.rowsum_part;
+            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_OUT_TD, MAP_SPLITX>(g, 8u * g.m_tiles * g.n_tiles, s);
+            else launch_gemm<OP_ROW, OP_COL, EPI_OUT_TD, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
+        } else {
+            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_OUT, MAP_SPLITX>(g, 8u * g.m_tiles * g.n_tiles, s);
+            else launch_gemm<OP_ROW, OP_COL, EPI_OUT, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
+        }
         if (g.splits > 1) {
             const int64_t n4 = rows * (int64_t)d / 4;
             nce_slab_sum_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s>>>(w.slabs, g.splits, n4, g.slab_stride, da, out_bf16);
         }
+        if (dt && dt->d_t) launch_nce_dtemp(w.rowsum_part, (int64_t)g.splits * g.m_tiles * g.n_tiles, 1, *dt, s);
     }
     {   // db = W^T a: m = keys, n = d, K = local rows
         NceGemmArgs g = {};

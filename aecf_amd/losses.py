@@ -13,7 +13,7 @@ the exchange steps are ``dp.all_gather_rows`` (forward) and its reduce-scatter (
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 
@@ -30,6 +30,25 @@ def _plus(total: torch.Tensor, term: torch.Tensor) -> torch.Tensor:
         term = term.to(torch.promote_types(total.dtype, term.dtype))
         total = total.to(term.dtype)
     return total + term
+
+
+MIN_TEMPERATURE = 0.025     # the tile forms' bound: 1/T is the constant shift of every exponential (nce_gemm_supported)
+
+
+def _temperature_arg(temperature, z: torch.Tensor, min_temperature: float):
+    """A Python number -> float (the host path, as before).  A tensor -> itself, checked: one float32 element on z's device,
+    read by the kernels (``max(T, min_temperature)``) with no host read, its gradient formed by the library's kernels."""
+    if not isinstance(temperature, torch.Tensor):
+        return float(temperature)
+    if temperature.dtype != torch.float32:
+        raise TypeError(f"aecf_amd: a tensor temperature must be float32, got {temperature.dtype}")
+    if temperature.numel() != 1:
+        raise ValueError(f"aecf_amd: a tensor temperature must hold one element, got shape {tuple(temperature.shape)}")
+    if temperature.device != z.device:
+        raise ValueError(f"aecf_amd: the temperature lives on {temperature.device}, the embeddings on {z.device}")
+    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
+        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
+    return temperature
 
 
 class _L2Norm(torch.autograd.Function):
@@ -61,10 +80,11 @@ class _L2Norm(torch.autograd.Function):
 
 class _NceDirection(torch.autograd.Function):
     """aecf_nce_fwd_bwd: sum_i [logsumexp_j(q_i.k_j/T) - q_i.k_{off+i}/T] * coef for local unit-norm q against all k.
-    Forward and both gradients come out of the same call (the gradients are linear in the upstream scalar)."""
+    Forward and both gradients come out of the same call (the gradients are linear in the upstream scalar).  A tensor
+    temperature runs aecf_nce_fwd_bwd_dt, which also forms dL/dT."""
 
     @staticmethod
-    def forward(ctx, q, k_all, row_offset, temperature, coef, low_memory=False):
+    def forward(ctx, q, k_all, row_offset, temperature, coef, low_memory=False, min_temperature=MIN_TEMPERATURE):
         lib = _lib.load()
         rows, d = q.shape
         cols = k_all.shape[0]
@@ -82,18 +102,27 @@ class _NceDirection(torch.autograd.Function):
                 raise NotImplementedError(f"aecf_amd: no streaming InfoNCE for dtype {dt}, d = {d}")
             ws_bytes = lib.aecf_nce_workspace_bytes(rows, cols, d, _DTYPES[dt])
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.aecf_nce_fwd_bwd(rows, cols, row_offset, d, _DTYPES[dt], temperature, coef, _ptr(qc), _ptr(kc),
-                                        _ptr(loss_rows), _ptr(dq), _ptr(dk), _ptr(ws), ws_bytes, _stream()),
-                   "aecf_nce_fwd_bwd")
-        ctx.save_for_backward(dq, dk)
+        d_t = None
+        if isinstance(temperature, torch.Tensor):
+            d_t = torch.empty(1, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
+            _lib.check(lib.aecf_nce_fwd_bwd_dt(rows, cols, row_offset, d, _DTYPES[dt], _ptr(temperature), float(min_temperature),
+                                               coef, _ptr(qc), _ptr(kc), _ptr(loss_rows), _ptr(dq), _ptr(dk), _ptr(d_t), _ptr(ws),
+                                               ws_bytes, _stream()), "aecf_nce_fwd_bwd_dt")
+            ctx.t_shape = temperature.shape
+        else:
+            _lib.check(lib.aecf_nce_fwd_bwd(rows, cols, row_offset, d, _DTYPES[dt], temperature, coef, _ptr(qc), _ptr(kc),
+                                            _ptr(loss_rows), _ptr(dq), _ptr(dk), _ptr(ws), ws_bytes, _stream()),
+                       "aecf_nce_fwd_bwd")
+        ctx.save_for_backward(dq, dk, d_t)
         ctx.dtypes = (q.dtype, k_all.dtype)
         return loss_rows.sum() * coef
 
     @staticmethod
     def backward(ctx, dloss):
-        dq, dk = ctx.saved_tensors
+        dq, dk, d_t = ctx.saved_tensors
         g = dloss.to(torch.float32)
-        return (dq * g).to(ctx.dtypes[0]), (dk * g).to(ctx.dtypes[1]), None, None, None, None
+        g_t = (d_t * g).reshape(ctx.t_shape) if d_t is not None else None
+        return (dq * g).to(ctx.dtypes[0]), (dk * g).to(ctx.dtypes[1]), None, g_t, None, None, None
 
 
 class _NceSymmetric(torch.autograd.Function):
@@ -103,10 +132,13 @@ class _NceSymmetric(torch.autograd.Function):
     caller's all-gather backward reduce-scatters it).  The forward runs the logits pass and the loss; the two gradient products
     run in the backward, scaled on the device by the gradient that arrives there and written in the inputs' dtype (no float32
     [cols, d] intermediate, no multiply / cast passes).  Optionally carries CurriculumMasking.entropy_loss (ref
-    aecf/AECFLayer.py:285-314) in the loss launch.  Returns (this rank's rows' share of the loss, entropy loss)."""
+    aecf/AECFLayer.py:285-314) in the loss launch.  Returns (this rank's rows' share of the loss, entropy loss).
+    A tensor temperature runs the _dt calls: T is read on the device, and the backward returns dL/dT -- this rank's share
+    (-(1/T) sum_i a_i.da_i over its rows, which sum to the global value over ranks) times ``t_grad_scale``."""
 
     @staticmethod
-    def forward(ctx, a, b_all, entropy, row_offset, temperature, coef, group, last_seq_len, entropy_target):
+    def forward(ctx, a, b_all, entropy, row_offset, temperature, coef, group, last_seq_len, entropy_target,
+                min_temperature=MIN_TEMPERATURE, t_grad_scale=1.0):
         lib = _lib.load()
         rows, d = a.shape
         cols = b_all.shape[0]
@@ -118,8 +150,14 @@ class _NceSymmetric(torch.autograd.Function):
             raise NotImplementedError(f"aecf_amd: symmetric InfoNCE needs d % 64 == 0, got d = {d}")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         col_sums = torch.empty(cols, **f32)
-        _lib.check(lib.aecf_nce_sym_pass1(rows, cols, d, temperature, _ptr(ac), _ptr(bc), _ptr(ws), ws_bytes, _ptr(col_sums),
-                                          _stream()), "aecf_nce_sym_pass1")
+        dev_t = isinstance(temperature, torch.Tensor)
+        if dev_t:
+            tp, t_min = _ptr(temperature), float(min_temperature)
+            _lib.check(lib.aecf_nce_sym_pass1_dt(rows, cols, d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(ws), ws_bytes, _ptr(col_sums),
+                                                 _stream()), "aecf_nce_sym_pass1_dt")
+        else:
+            _lib.check(lib.aecf_nce_sym_pass1(rows, cols, d, temperature, _ptr(ac), _ptr(bc), _ptr(ws), ws_bytes, _ptr(col_sums),
+                                              _stream()), "aecf_nce_sym_pass1")
         if dp.world_info(group)[1] > 1:
             torch.distributed.all_reduce(col_sums, group=group)
         loss_rows = torch.empty(rows, **f32)
@@ -129,18 +167,25 @@ class _NceSymmetric(torch.autograd.Function):
             n_ent, p_ent, p_el, p_de = ent.numel(), _ptr(ent), _ptr(ent_loss), _ptr(dent)
         else:
             ent_loss, dent, n_ent, p_ent, p_el, p_de = torch.zeros(1, **f32), None, 0, None, None, None
-        _lib.check(lib.aecf_nce_sym_loss(rows, cols, row_offset, d, temperature, _ptr(ac), _ptr(bc), _ptr(col_sums), _ptr(ws),
-                                         ws_bytes, _ptr(loss_rows), n_ent, last_seq_len, entropy_target, p_ent, 1.0, p_el, p_de,
-                                         _stream()), "aecf_nce_sym_loss")
-        ctx.save_for_backward(ac, bc, ws, *([dent] if dent is not None else []))
+        if dev_t:
+            _lib.check(lib.aecf_nce_sym_loss_dt(rows, cols, row_offset, d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(col_sums), _ptr(ws),
+                                                ws_bytes, _ptr(loss_rows), n_ent, last_seq_len, entropy_target, p_ent, 1.0, p_el, p_de,
+                                                _stream()), "aecf_nce_sym_loss_dt")
+        else:
+            _lib.check(lib.aecf_nce_sym_loss(rows, cols, row_offset, d, temperature, _ptr(ac), _ptr(bc), _ptr(col_sums), _ptr(ws),
+                                             ws_bytes, _ptr(loss_rows), n_ent, last_seq_len, entropy_target, p_ent, 1.0, p_el, p_de,
+                                             _stream()), "aecf_nce_sym_loss")
+        # (a device temperature is kept as a tensor: the backward reads it where it lives)
+        ctx.save_for_backward(ac, bc, ws, temperature.detach() if dev_t else None, *([dent] if dent is not None else []))
         ctx.meta = (a.dtype, b_all.dtype, None if entropy is None else (entropy.dtype, entropy.shape),
-                    (rows, cols, int(row_offset), d, float(temperature), float(coef), ws_bytes))
+                    (rows, cols, int(row_offset), d, None if dev_t else float(temperature), float(coef), ws_bytes))
+        ctx.dev_t = (temperature.shape, float(min_temperature), float(t_grad_scale)) if dev_t else None
         return loss_rows.sum() * coef, ent_loss.reshape(())
 
     @staticmethod
     def backward(ctx, d_nce, d_ent):
         lib = _lib.load()
-        ac, bc, ws = ctx.saved_tensors[:3]
+        ac, bc, ws, t_dev = ctx.saved_tensors[:4]
         ad, bd, em, (rows, cols, row_offset, d, temperature, coef, ws_bytes) = ctx.meta
         if getattr(ctx, "_spent", False):
             raise RuntimeError("aecf_amd: the symmetric InfoNCE backward runs once per forward (it consumes the stored logits)")
@@ -149,18 +194,30 @@ class _NceSymmetric(torch.autograd.Function):
         da = torch.empty(rows, d, dtype=gdt, device=ac.device)
         db = torch.empty(cols, d, dtype=gdt, device=ac.device)
         up = d_nce.detach().to(torch.float32).reshape(1).contiguous()
-        _lib.check(lib.aecf_nce_sym_grads(rows, cols, row_offset, d, temperature, coef, _ptr(ac), _ptr(bc), _ptr(ws), ws_bytes,
-                                          _ptr(up), _DTYPES[gdt], _ptr(da), _ptr(db), _stream()), "aecf_nce_sym_grads")
+        g_t = None
+        if ctx.dev_t is not None:
+            t_shape, t_min, t_scale = ctx.dev_t
+            d_t = torch.empty(1, dtype=torch.float32, device=ac.device) if ctx.needs_input_grad[4] else None
+            _lib.check(lib.aecf_nce_sym_grads_dt(rows, cols, row_offset, d, _ptr(t_dev), t_min, coef, _ptr(ac), _ptr(bc), _ptr(ws),
+                                                 ws_bytes, _ptr(up), _DTYPES[gdt], _ptr(da), _ptr(db), _ptr(d_t), _stream()),
+                       "aecf_nce_sym_grads_dt")
+            if d_t is not None:
+                g_t = (d_t * t_scale if t_scale != 1.0 else d_t).reshape(t_shape)
+        else:
+            _lib.check(lib.aecf_nce_sym_grads(rows, cols, row_offset, d, temperature, coef, _ptr(ac), _ptr(bc), _ptr(ws), ws_bytes,
+                                              _ptr(up), _DTYPES[gdt], _ptr(da), _ptr(db), _stream()), "aecf_nce_sym_grads")
         g_ent = None
         if em is not None:
-            g_ent = (ctx.saved_tensors[3] * d_ent.to(torch.float32)).reshape(em[1]).to(em[0])
-        return da.to(ad), db.to(bd), g_ent, None, None, None, None, None, None
+            g_ent = (ctx.saved_tensors[4] * d_ent.to(torch.float32)).reshape(em[1]).to(em[0])
+        return da.to(ad), db.to(bd), g_ent, None, g_t, None, None, None, None, None, None
 
 
-def _sym_supported(z: torch.Tensor, temperature: float, cols: Optional[int] = None) -> bool:
+def _sym_supported(z: torch.Tensor, temperature, cols: Optional[int] = None, min_temperature: float = MIN_TEMPERATURE) -> bool:
     """The tile-GEMM form applies (bf16, d % 64 == 0, 1/T a safe exponent shift) AND its workspace -- rows x cols bf16 -- fits
-    comfortably in what the device has free; otherwise the callers take the streaming kernels (O(rows d) workspace)."""
-    if not (z.dtype == torch.bfloat16 and z.shape[1] % 64 == 0 and temperature >= 0.025):
+    comfortably in what the device has free; otherwise the callers take the streaming kernels (O(rows d) workspace).  A tensor
+    temperature is never read here: its bound is min_temperature (the kernels use max(T, min_temperature))."""
+    bound = min_temperature if isinstance(temperature, torch.Tensor) else temperature
+    if not (z.dtype == torch.bfloat16 and z.shape[1] % 64 == 0 and bound >= MIN_TEMPERATURE):
         return False
     if cols is not None and z.is_cuda:
         need = _lib.load().aecf_nce_sym_workspace_bytes(z.shape[0], cols, z.shape[1])
@@ -180,10 +237,12 @@ def _stream_form(z: torch.Tensor, cols: int) -> bool:
 class _LossDirection(torch.autograd.Function):
     """aecf_loss_fwd_bwd: ONE call for one InfoNCE direction (streaming form: no [rows, cols] logits) AND the entropy
     regulariser of the reference (CurriculumMasking.entropy_loss, ref aecf/AECFLayer.py:285-314) with their gradients
-    -- BASELINE.json north_star's "second fused kernel".  Returns (contrastive share, entropy loss)."""
+    -- BASELINE.json north_star's "second fused kernel".  Returns (contrastive share, entropy loss).  A tensor temperature
+    runs aecf_loss_fwd_bwd_dt, which also forms dL/dT."""
 
     @staticmethod
-    def forward(ctx, q, k_all, entropy, row_offset, temperature, coef, last_seq_len, entropy_target):
+    def forward(ctx, q, k_all, entropy, row_offset, temperature, coef, last_seq_len, entropy_target,
+                min_temperature=MIN_TEMPERATURE):
         lib = _lib.load()
         rows, d = q.shape
         cols = k_all.shape[0]
@@ -200,60 +259,81 @@ class _LossDirection(torch.autograd.Function):
         if ws_bytes == 0:
             ws_bytes = lib.aecf_nce_workspace_bytes(rows, cols, d, _lib.AECF_BF16)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.aecf_loss_fwd_bwd(rows, cols, row_offset, d, temperature, coef, _ptr(qc), _ptr(kc), _ptr(loss_rows),
-                                         _ptr(dq), _ptr(dk), ent.numel(), last_seq_len, entropy_target, _ptr(ent), 1.0,
-                                         _ptr(ent_loss), _ptr(dent), _ptr(ws), ws_bytes, _stream()), "aecf_loss_fwd_bwd")
-        ctx.save_for_backward(dq, dk, dent)
+        d_t = None
+        if isinstance(temperature, torch.Tensor):
+            d_t = torch.empty(1, **f32) if ctx.needs_input_grad[4] else None
+            _lib.check(lib.aecf_loss_fwd_bwd_dt(rows, cols, row_offset, d, _ptr(temperature), float(min_temperature), coef,
+                                                _ptr(qc), _ptr(kc), _ptr(loss_rows), _ptr(dq), _ptr(dk), _ptr(d_t), ent.numel(),
+                                                last_seq_len, entropy_target, _ptr(ent), 1.0, _ptr(ent_loss), _ptr(dent), _ptr(ws),
+                                                ws_bytes, _stream()), "aecf_loss_fwd_bwd_dt")
+            ctx.t_shape = temperature.shape
+        else:
+            _lib.check(lib.aecf_loss_fwd_bwd(rows, cols, row_offset, d, temperature, coef, _ptr(qc), _ptr(kc), _ptr(loss_rows),
+                                             _ptr(dq), _ptr(dk), ent.numel(), last_seq_len, entropy_target, _ptr(ent), 1.0,
+                                             _ptr(ent_loss), _ptr(dent), _ptr(ws), ws_bytes, _stream()), "aecf_loss_fwd_bwd")
+        ctx.save_for_backward(dq, dk, dent, d_t)
         ctx.meta = (q.dtype, k_all.dtype, entropy.dtype, entropy.shape)
         return loss_rows.sum() * coef, ent_loss.reshape(())
 
     @staticmethod
     def backward(ctx, d_nce, d_ent):
-        dq, dk, dent = ctx.saved_tensors
+        dq, dk, dent, d_t = ctx.saved_tensors
         qd, kd, ed, eshape = ctx.meta
         g = d_nce.to(torch.float32)
+        g_t = (d_t * g).reshape(ctx.t_shape) if d_t is not None else None
         return ((dq * g).to(qd), (dk * g).to(kd), (dent * d_ent.to(torch.float32)).reshape(eshape).to(ed),
-                None, None, None, None, None)
+                None, g_t, None, None, None, None)
 
 
 def contrastive_entropy_loss(za: torch.Tensor, zb: torch.Tensor, masking: CurriculumMasking, entropy: torch.Tensor,
-                             temperature: float = 0.07, entropy_weight: float = 0.01,
-                             contrastive_weight: float = 1.0) -> torch.Tensor:
+                             temperature: Union[float, torch.Tensor] = 0.07, entropy_weight: float = 0.01,
+                             contrastive_weight: float = 1.0, min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
     """``contrastive_weight * info_nce(za, zb) + entropy_weight * masking.entropy_loss(entropy)`` (single rank, bf16
-    embeddings) with the entropy regulariser riding in the launch of the first InfoNCE direction (aecf_loss_fwd_bwd)."""
+    embeddings) with the entropy regulariser riding in the launch of the first InfoNCE direction (aecf_loss_fwd_bwd).
+    ``temperature`` / ``min_temperature``: as for ``info_nce``."""
     _require_device(za, "za")
     if za.shape != zb.shape or za.dim() != 2:
         raise ValueError(f"expected two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+    t = _temperature_arg(temperature, za, min_temperature)
     na, nb = l2_normalize(za), l2_normalize(zb)
     coef = 0.5 / float(za.shape[0])
     seq_len = masking._last_seq_len if hasattr(masking, "_last_seq_len") else 2
-    if _sym_supported(za, temperature, za.shape[0]):
-        l_nce, l_ent = _NceSymmetric.apply(na, nb, entropy, 0, float(temperature), coef, None, int(seq_len),
-                                           float(masking.entropy_target))
+    if _sym_supported(za, t, za.shape[0], min_temperature):
+        l_nce, l_ent = _NceSymmetric.apply(na, nb, entropy, 0, t, coef, None, int(seq_len), float(masking.entropy_target),
+                                           min_temperature, 1.0)
         return _plus(contrastive_weight * l_nce, entropy_weight * l_ent.to(za.dtype))
-    l_ab, l_ent = _LossDirection.apply(na, nb, entropy, 0, float(temperature), coef, int(seq_len),
-                                       float(masking.entropy_target))
-    l_ba = _NceDirection.apply(nb, na, 0, float(temperature), coef, _stream_form(nb, na.shape[0]))
+    l_ab, l_ent = _LossDirection.apply(na, nb, entropy, 0, t, coef, int(seq_len), float(masking.entropy_target), min_temperature)
+    l_ba = _NceDirection.apply(nb, na, 0, t, coef, _stream_form(nb, na.shape[0]), min_temperature)
     return _plus(contrastive_weight * (l_ab + l_ba), entropy_weight * l_ent.to(za.dtype))
 
 
 def gathered_contrastive_entropy_loss(za: torch.Tensor, nb_all: torch.Tensor, row_offset: int, masking: CurriculumMasking,
-                                      entropy: torch.Tensor, temperature: float = 0.07, entropy_weight: float = 0.01,
-                                      contrastive_weight: float = 1.0, group=None) -> torch.Tensor:
+                                      entropy: torch.Tensor, temperature: Union[float, torch.Tensor] = 0.07,
+                                      entropy_weight: float = 0.01, contrastive_weight: float = 1.0, group=None,
+                                      min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
     """The loss side of a data-parallel step in ONE operator: this rank's rows ``za`` [b_local, d] (bf16, not yet normalised)
     against the unit-norm rows of the other view from EVERY rank ``nb_all`` [b_all, d] (``dp.all_gather_rows(l2_normalize(zb))``:
     its backward reduce-scatters the share of the gradient this call returns), positives at ``row_offset + i``; both InfoNCE
     directions from the one block of logits (``aecf_nce_sym_pass1`` / ``_loss`` / ``_grads``; the column sums are all-reduced over ``group`` between
     the passes) plus ``entropy_weight * masking.entropy_loss(entropy)`` riding in the same call.  Returns this rank's share of
-    ``contrastive_weight * L_nce`` (coef = 0.5 / b_all) plus the entropy term."""
+    ``contrastive_weight * L_nce`` (coef = 0.5 / b_all) plus the entropy term.
+
+    A tensor ``temperature`` (as for ``info_nce``, ``min_temperature >= 0.025``) gets the gradient ``world * (this rank's share
+    of dL/dT)``: the gradient average of the training loop (``dp.all_reduce_grads``) then leaves the one-rank gradient of the
+    global objective on a replicated temperature -- the convention ``info_nce`` follows for every input."""
     _require_device(za, "za")
-    if not _sym_supported(za, temperature):
+    t = _temperature_arg(temperature, za, min_temperature)
+    if not _sym_supported(za, t, None, min_temperature):
+        if isinstance(t, torch.Tensor):
+            raise NotImplementedError("aecf_amd: the gathered contrastive loss needs bfloat16 rows with d % 64 == 0 and "
+                                      "min_temperature >= 0.025 for a tensor temperature")
         raise NotImplementedError("aecf_amd: the gathered contrastive loss needs bfloat16 rows with d % 64 == 0 and temperature >= 0.025")
     na = l2_normalize(za)
     coef = 0.5 / float(nb_all.shape[0])
     seq_len = masking._last_seq_len if hasattr(masking, "_last_seq_len") else 2
-    l_nce, l_ent = _NceSymmetric.apply(na, nb_all, entropy, int(row_offset), float(temperature), coef, group, int(seq_len),
-                                       float(masking.entropy_target))
+    world = dp.world_info(group)[1] if isinstance(t, torch.Tensor) else 1
+    l_nce, l_ent = _NceSymmetric.apply(na, nb_all, entropy, int(row_offset), t, coef, group, int(seq_len),
+                                       float(masking.entropy_target), min_temperature, float(world))
     return _plus(contrastive_weight * l_nce, entropy_weight * l_ent.to(za.dtype))
 
 
@@ -262,22 +342,29 @@ def l2_normalize(z: torch.Tensor, eps: float = 1e-12) -> torch.Tensor:
     return _L2Norm.apply(z, float(eps))
 
 
-def info_nce(za: torch.Tensor, zb: torch.Tensor, temperature: float = 0.07, group=None) -> torch.Tensor:
+def info_nce(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch.Tensor] = 0.07, group=None,
+             min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
     """Symmetric InfoNCE between the local rows of two views with negatives from every rank of ``group``.
     ``za``, ``zb``: [b_local, d] on a ROCm device.  bfloat16 with d % 64 == 0 (temperature >= 0.025) runs the symmetric tile-GEMM
     form: both directions from ONE block of logits, exponentials kept as bf16 [b_local, b_all] (any row counts); float32:
-    d % 64 == 0 and total rows over ranks % 64 == 0."""
+    d % 64 == 0 and total rows over ranks % 64 == 0.
+
+    ``temperature``: a Python float, or a learnable one -- a one-element float32 tensor on za's device, e.g.
+    ``1 / logit_scale.exp()``.  A tensor is read by the kernels on the device (no host read: a captured step replays its current
+    value) as ``max(T, min_temperature)``, and its gradient (zero where ``T < min_temperature``) comes from the same kernels.
+    The form is chosen from the dtype, d, memory and ``min_temperature`` (below 0.025: the streaming form), never from T."""
     _require_device(za, "za")
     _require_device(zb, "zb")
     if za.shape != zb.shape or za.dim() != 2:
         raise ValueError(f"info_nce expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
     if za.dtype not in _DTYPES:
         raise NotImplementedError(f"aecf_amd: dtype {za.dtype} is not supported (bfloat16 / float32 only)")
+    t = _temperature_arg(temperature, za, min_temperature)
     rank, world = dp.world_info(group)
     na, nb = l2_normalize(za), l2_normalize(zb)
     nb_all = dp.all_gather_rows(nb, group) if world > 1 else nb
     b_all = nb_all.shape[0]
-    sym = _sym_supported(za, temperature, b_all)
+    sym = _sym_supported(za, t, b_all, min_temperature)
     if world > 1:                                   # every rank must take the same form (they exchange different things)
         flag = torch.tensor([1 if sym else 0], device=za.device)
         torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
@@ -293,14 +380,14 @@ def info_nce(za: torch.Tensor, zb: torch.Tensor, temperature: float = 0.07, grou
     if sym:
         # both directions from the one block of logits this rank owns (its rows of view a against every row of view b):
         # view a is never gathered, one all-reduce of b_all floats replaces the second direction's pass
-        share, _ = _NceSymmetric.apply(na, nb_all, None, offset, float(temperature), coef, group, 2, 0.0)
+        share, _ = _NceSymmetric.apply(na, nb_all, None, offset, t, coef, group, 2, 0.0, min_temperature, 1.0)
     else:
         na_all = dp.all_gather_rows(na, group) if world > 1 else na
         # (the symmetric form was refused -- memory, temperature or dtype: the streaming kernels where they exist, never
         #  a second rows x cols allocation per direction)
         low = _stream_form(na, b_all)
-        l_ab = _NceDirection.apply(na, nb_all, offset, float(temperature), coef, low)
-        l_ba = _NceDirection.apply(nb, na_all, offset, float(temperature), coef, low)
+        l_ab = _NceDirection.apply(na, nb_all, offset, t, coef, low, min_temperature)
+        l_ba = _NceDirection.apply(nb, na_all, offset, t, coef, low, min_temperature)
         share = l_ab + l_ba              # this rank's rows' share of the global objective
     if world == 1:
         return share
@@ -314,11 +401,13 @@ def info_nce(za: torch.Tensor, zb: torch.Tensor, temperature: float = 0.07, grou
 
 def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMasking], entropy: Optional[torch.Tensor],
                      za: Optional[torch.Tensor] = None, zb: Optional[torch.Tensor] = None, entropy_weight: float = 0.01,
-                     contrastive_weight: float = 1.0, temperature: float = 0.07, group=None) -> torch.Tensor:
-    """task + entropy_weight * entropy_loss(entropy) [ref README.md:205-208] + contrastive_weight * info_nce(za, zb)."""
+                     contrastive_weight: float = 1.0, temperature: Union[float, torch.Tensor] = 0.07, group=None,
+                     min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
+    """task + entropy_weight * entropy_loss(entropy) [ref README.md:205-208] + contrastive_weight * info_nce(za, zb)
+    (``temperature`` / ``min_temperature``: as for ``info_nce``)."""
     total = task_loss
     if masking is not None and entropy is not None:
         total = _plus(total, entropy_weight * masking.entropy_loss(entropy))
     if za is not None and zb is not None:
-        total = _plus(total, contrastive_weight * info_nce(za, zb, temperature, group))
+        total = _plus(total, contrastive_weight * info_nce(za, zb, temperature, group, min_temperature))
     return total

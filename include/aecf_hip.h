@@ -488,6 +488,42 @@ int aecf_nce_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d
                        const void* a, const void* b, void* workspace, size_t workspace_bytes, const float* upstream,
                        int32_t grad_dtype, void* da, void* db, void* stream);
 
+/* ---- device temperature: the five calls above with T read from device memory (a learnable temperature) ----
+ * `temperature` is a DEVICE float32 scalar; the kernels use Tc = max(*temperature, min_temperature) (min_temperature > 0, a host
+ * float) and derive 1/Tc on the device with the float operations the host uses for a float T: a device T equal to a float T
+ * gives bit-identical outputs.  Nothing is read on the host, so the calls can be captured in a graph and replay the value the
+ * scalar holds at replay time.  The form is chosen from dtype, d, the workspace and min_temperature, never from T: the tile
+ * forms need min_temperature >= 0.025 (the constant shift 1/T of their exponentials; the sym calls answer
+ * AECF_ERR_UNSUPPORTED below it, aecf_nce_fwd_bwd_dt / aecf_loss_fwd_bwd_dt take the streaming or materialising form).
+ * d_temperature (DEVICE float32 scalar, may be NULL = not wanted) is WRITTEN, not accumulated, with
+ *   dL/dT = -(1/Tc) sum_i q_i . dq_i      (0 where *temperature < min_temperature: the gradient of clamp(T, min))
+ * for this call's term: one direction at upstream 1 (aecf_nce_fwd_bwd_dt, aecf_loss_fwd_bwd_dt: scale it as dq / dk), both
+ * directions of THIS rank's rows times upstream[0] (aecf_nce_sym_grads_dt: the shares of the ranks sum to the global value).
+ * It is reduced in a fixed order from the float32 gradient before any rounding (one extra single-block launch); no float
+ * atomics.  Checks before any launch: sizes, then dtype (float16: AECF_ERR_UNSUPPORTED) and the tile form's min_temperature,
+ * then NULL pointers (temperature included). */
+int aecf_nce_fwd_bwd_dt(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t dtype,
+                        const float* temperature, float min_temperature, float coef, const void* q, const void* k,
+                        float* loss_rows, float* dq, float* dk, float* d_temperature, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int aecf_loss_fwd_bwd_dt(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                         float min_temperature, float coef, const void* q, const void* k, float* loss_rows, float* dq,
+                         float* dk, float* d_temperature, int64_t n_entropy, int32_t last_seq_len, float entropy_target,
+                         const float* entropy, float entropy_upstream, float* entropy_loss, float* d_entropy,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int aecf_nce_sym_pass1_dt(int64_t rows, int64_t cols, int32_t d, const float* temperature, float min_temperature,
+                          const void* a, const void* b, void* workspace, size_t workspace_bytes, float* col_sums,
+                          void* stream);
+int aecf_nce_sym_loss_dt(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                         float min_temperature, const void* a, const void* b, const float* col_sums, void* workspace,
+                         size_t workspace_bytes, float* loss_rows, int64_t n_entropy, int32_t last_seq_len,
+                         float entropy_target, const float* entropy, float entropy_upstream, float* entropy_loss,
+                         float* d_entropy, void* stream);
+int aecf_nce_sym_grads_dt(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                          float min_temperature, float coef, const void* a, const void* b, void* workspace,
+                          size_t workspace_bytes, const float* upstream, int32_t grad_dtype, void* da, void* db,
+                          float* d_temperature, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
