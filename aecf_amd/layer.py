@@ -1341,12 +1341,20 @@ class MultimodalAttentionPool(nn.Module):
 # ----------------------------------------------------------------------------------------------
 # ref: aecf/AECFLayer.py:556-652
 # ----------------------------------------------------------------------------------------------
+_SDPA_MAX_LEN = 64        # rows and columns of the score array of aecf_sdpa_forward / _backward (aecf_misc.hip)
+
+
 def _scaled_dot_product_attention(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,
                                   scale: Optional[float] = None) -> torch.Tensor:
     """softmax(Q K^T * scale) V without projections (ref :556-581), HIP kernel."""
     _require_device(query, "query")
     if query.dtype not in _POOL_DTYPES:
         raise NotImplementedError(f"aecf_amd: dtype {query.dtype} is not supported (bfloat16 / float16 / float32 only)")
+    if query.dim() == 3 and key.dim() == 3 and (query.size(1) > _SDPA_MAX_LEN or key.size(1) > _SDPA_MAX_LEN):
+        # aecf_sdpa_forward would answer AECF_ERR_UNSUPPORTED; say which limit, not a bare status (the reference takes any length)
+        raise RuntimeError(f"aecf_amd: projection-free attention with {query.size(1)} queries and {key.size(1)} keys is not "
+                           f"supported: the aecf_sdpa kernels take at most {_SDPA_MAX_LEN} queries and {_SDPA_MAX_LEN} keys "
+                           "(use MultimodalAttentionPool, whose general route takes lengths up to 4096)")
     if scale is None:
         scale = query.size(-1) ** -0.5
     return _SdpaFunction.apply(query, key, value, float(scale))
