@@ -141,6 +141,12 @@ _SYMBOLS = [
     ("aecf_cast_f32_to_f16", c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("aecf_adamw_step", c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                 c_float, c_float, c_float, c_void_p]),
+    # mixed precision: + master[], param_dtype[], grad_dtype[] and the device scalars lr_dev, grad_scale, grad_coef, found_inf x 2
+    ("aecf_adamw_mp_step", c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]),
+    ("aecf_grad_norm_workspace_bytes", c_size_t, [c_int32, c_void_p]),
+    ("aecf_grad_norm", c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     ("aecf_rows_split", c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("aecf_l2norm_forward", c_int, [c_int64, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("aecf_l2norm_backward", c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -940,6 +940,62 @@ int aecf_adamw_step(int32_t n, void* const* param, const void* const* grad, void
     return launch_status();
 }
 
+static bool optim_dtype_ok(int32_t dt) { return dt == AECF_BF16 || dt == AECF_F32 || dt == AECF_F16; }
+
+int aecf_adamw_mp_step(int32_t n, void* const* param, const void* const* grad, void* const* master, void* const* exp_avg,
+                       void* const* exp_avg_sq, void* const* step, const int64_t* numel, const int32_t* param_dtype,
+                       const int32_t* grad_dtype, void* ticket, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       const float* lr_dev, const float* grad_scale, const float* grad_coef, const float* found_inf,
+                       const float* found_inf2, void* stream) {
+    if (n < 0) return AECF_ERR_BAD_DIMS;
+    if (n == 0) return AECF_OK;
+    if (!numel) return AECF_ERR_NULL_POINTER;
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (numel[i] < 0) return AECF_ERR_BAD_DIMS;
+        total += numel[i];
+    }
+    if (!param_dtype || !grad_dtype) return AECF_ERR_NULL_POINTER;
+    for (int i = 0; i < n; ++i)
+        if (!optim_dtype_ok(param_dtype[i]) || !optim_dtype_ok(grad_dtype[i])) return AECF_ERR_UNSUPPORTED;
+    if (total == 0) return AECF_OK;
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !step || !ticket) return AECF_ERR_NULL_POINTER;      // master may be NULL
+    for (int i = 0; i < n; ++i)
+        if (numel[i] > 0 && (!param[i] || !grad[i] || !exp_avg[i] || !exp_avg_sq[i] || !step[i])) return AECF_ERR_NULL_POINTER;
+    launch_adamw_mp(n, param, grad, (float* const*)master, (float* const*)exp_avg, (float* const*)exp_avg_sq, (float* const*)step,
+                    numel, param_dtype, grad_dtype, (unsigned int*)ticket, lr, beta1, beta2, eps, weight_decay, lr_dev, grad_scale,
+                    grad_coef, found_inf, found_inf2, (hipStream_t)stream);
+    return launch_status();
+}
+
+size_t aecf_grad_norm_workspace_bytes(int32_t n, const int64_t* numel) {
+    if (n <= 0 || !numel) return 0;
+    for (int i = 0; i < n; ++i)
+        if (numel[i] < 0) return 0;
+    return (size_t)grad_norm_blocks(n, numel) * sizeof(float);
+}
+
+int aecf_grad_norm(int32_t n, const void* const* grad, const int32_t* grad_dtype, const int64_t* numel, float max_norm,
+                   const float* grad_scale, void* workspace, size_t workspace_bytes, float* out, void* stream) {
+    if (n < 0) return AECF_ERR_BAD_DIMS;
+    if (n == 0) return AECF_OK;
+    if (!numel) return AECF_ERR_NULL_POINTER;
+    for (int i = 0; i < n; ++i)
+        if (numel[i] < 0) return AECF_ERR_BAD_DIMS;
+    if (!grad_dtype) return AECF_ERR_NULL_POINTER;
+    for (int i = 0; i < n; ++i)
+        if (!optim_dtype_ok(grad_dtype[i])) return AECF_ERR_UNSUPPORTED;
+    const int64_t blocks = grad_norm_blocks(n, numel);
+    if (blocks == 0) return AECF_OK;
+    if (!grad || !out) return AECF_ERR_NULL_POINTER;
+    for (int i = 0; i < n; ++i)
+        if (numel[i] > 0 && !grad[i]) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < (size_t)blocks * sizeof(float)) return AECF_ERR_WORKSPACE;
+    if (!workspace) return AECF_ERR_NULL_POINTER;
+    launch_grad_norm(n, grad, grad_dtype, numel, max_norm, grad_scale, (float*)workspace, out, (hipStream_t)stream);
+    return launch_status();
+}
+
 int aecf_rows_split(int64_t rows, int64_t row_bytes, const int32_t* route, const void* src, void* const* dst, void* stream) {
     if (rows <= 0 || row_bytes <= 0 || row_bytes % 2 != 0) return AECF_ERR_BAD_DIMS;
     if (!route || !src || !dst) return AECF_ERR_NULL_POINTER;

@@ -279,6 +279,14 @@ void launch_rows_gather(int njobs, const void* const* src, const int64_t* src_pi
 void launch_adamw_multi(int n, float* const* p, const float* const* g, float* const* m, float* const* v, float* const* step,
                         const int64_t* numel, unsigned int* ticket, float lr, float beta1, float beta2, float eps, float weight_decay,
                         hipStream_t s);
+// mixed-precision AdamW / gradient norm (aecf_optim.hip); empty tensors are skipped, dtypes are aecf_dtype values
+int launch_adamw_mp(int n, void* const* p, const void* const* g, float* const* master, float* const* m, float* const* v,
+                    float* const* step, const int64_t* numel, const int32_t* pdt, const int32_t* gdt, unsigned int* ticket, float lr,
+                    float beta1, float beta2, float eps, float weight_decay, const float* lr_dev, const float* grad_scale,
+                    const float* grad_coef, const float* found_inf, const float* found_inf2, hipStream_t s);
+int64_t grad_norm_blocks(int n, const int64_t* numel);
+void launch_grad_norm(int n, const void* const* g, const int32_t* gdt, const int64_t* numel, float max_norm, const float* grad_scale,
+                      float* partial, float* out, hipStream_t s);
 void launch_rows_split(int64_t rows, int64_t row_bytes, const int32_t* route, const void* src, void* const* dst, hipStream_t s);
 void launch_front_pair(int dtype, int64_t rows, int dim_a, int dim_b, const void* feat_a, const void* feat_b, const float* uniforms,
                        float missing_prob, const uint8_t* drop_a, const uint8_t* drop_b, void* out_a, void* out_b,

@@ -8,6 +8,7 @@
 //   p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps),   t = step + 1        (torch/optim/adamw.py, amsgrad off)
 #include <math.h>
 
+#include "../../include/aecf_hip.h"
 #include "aecf_kernels.h"
 
 namespace aecf {
@@ -118,6 +119,320 @@ void launch_adamw_multi(int n, float* const* p, const float* const* g, float* co
         a.log_beta2 = (float)log((double)beta2);
         if (blocks) adamw_multi_kernel<<<dim3(blocks), dim3(256), 0, s>>>(a);
     }
+}
+
+// ---- mixed precision: the same update over parameters and gradients of float32 / bf16 / f16, optional float32 masters ----
+// (replaces torch.optim.AdamW of ref xrays/train_xrays_example.py:322-323 for a bf16 / f16 model, torch.amp.GradScaler's
+// unscale + skip and the scaling pass of torch.nn.utils.clip_grad_norm_, all on the one elementwise pass)
+// A lane takes 4 elements where parameter and gradient are both float32 (the layout of adamw_multi_kernel) and 8 where either
+// is 16-bit: one 16-byte access per 16-bit tensor, two per float32 tensor.  With a master the float32 weight is read from and
+// written to it and the 16-bit parameter is only WRITTEN, as the round-to-nearest-even of the new master (pack2 /
+// Tr::from_f32, the conversions of aecf_cast_f32_to_bf16 / _f16: param == master.to(dtype) bit for bit); without one the
+// parameter is widened, updated in float32 and rounded once on the store.  Moments are float32 always.
+// Launch-wide device scalars, each optional: lr_dev (replaces the float lr; a captured step follows it), grad_scale (the AMP
+// loss scale: g * (1 / scale), the reciprocal formed once per block by a correctly rounded division), grad_coef (the clip
+// coefficient grad_sumsq_finalize_kernel wrote) and two found_inf flags (GradScaler's and the norm's; either non-zero: every
+// block returns before it reads or writes anything else, the tickets stay armed and no counter advances).
+namespace {
+
+struct AdamMpArgs {
+    void* p[OPT_MAX_TENSORS];
+    const void* g[OPT_MAX_TENSORS];
+    float* master[OPT_MAX_TENSORS];                   // NULL: none
+    float* m[OPT_MAX_TENSORS];
+    float* v[OPT_MAX_TENSORS];
+    float* step[OPT_MAX_TENSORS];
+    int64_t numel[OPT_MAX_TENSORS];
+    unsigned int first_block[OPT_MAX_TENSORS + 1];
+    unsigned char pdt[OPT_MAX_TENSORS], gdt[OPT_MAX_TENSORS];          // aecf_dtype
+    unsigned int* ticket;
+    const float *lr_dev, *grad_scale, *grad_coef, *found_inf, *found_inf2;
+    int n;
+    float lr, beta1, beta2, eps, weight_decay;
+    float log_beta1, log_beta2;
+};
+
+template <typename T> __device__ __forceinline__ float opt_load1(const void* q, int64_t i) {
+    if constexpr (std::is_same<T, F32>::value) return reinterpret_cast<const float*>(q)[i];
+    else if constexpr (std::is_same<T, F16>::value) return f16_bits_to_f32(reinterpret_cast<const unsigned short*>(q)[i]);
+    else return bf16_bits_to_f32(reinterpret_cast<const unsigned short*>(q)[i]);
+}
+template <typename T> __device__ __forceinline__ void opt_store1(void* q, int64_t i, float f) {
+    if constexpr (std::is_same<T, F32>::value) reinterpret_cast<float*>(q)[i] = f;
+    else reinterpret_cast<unsigned short*>(q)[i] = Tr<T>::from_f32(f);
+}
+// N consecutive elements from a 16-byte aligned address: N / 4 accesses of float32, one access of 8 16-bit elements
+template <typename T, int N> __device__ __forceinline__ void opt_loadv(const void* q, int64_t i, float (&o)[N]) {
+    if constexpr (std::is_same<T, F32>::value) {
+#pragma unroll
+        for (int k = 0; k < N; k += 4) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(q) + i + k);
+            o[k] = x[0]; o[k + 1] = x[1]; o[k + 2] = x[2]; o[k + 3] = x[3];
+        }
+    } else {
+        static_assert(N == 8, "a 16-bit tensor moves 8 elements per lane");
+        const u32x4 w = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned short*>(q) + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if constexpr (std::is_same<T, F16>::value) {
+                o[2 * k] = f16_bits_to_f32(w[k] & 0xffffu); o[2 * k + 1] = f16_bits_to_f32(w[k] >> 16);
+            } else {
+                o[2 * k] = bf16_bits_to_f32(w[k] & 0xffffu); o[2 * k + 1] = bf16_bits_to_f32(w[k] >> 16);
+            }
+        }
+    }
+}
+template <typename T, int N> __device__ __forceinline__ void opt_storev(void* q, int64_t i, const float (&o)[N]) {
+    if constexpr (std::is_same<T, F32>::value) {
+#pragma unroll
+        for (int k = 0; k < N; k += 4)
+            *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(q) + i + k) = f32x4{o[k], o[k + 1], o[k + 2], o[k + 3]};
+    } else {
+        static_assert(N == 8, "a 16-bit tensor moves 8 elements per lane");
+        *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(q) + i) =
+            u32x4{pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3]), pack2<T>(o[4], o[5]), pack2<T>(o[6], o[7])};
+    }
+}
+
+template <typename T> constexpr bool opt_is_f32 = std::is_same<T, F32>::value;
+// elements per lane and per block of a (parameter, gradient) dtype pair; the host sizes the grid with the same numbers
+template <typename PT, typename GT> constexpr int opt_lane_elems = (opt_is_f32<PT> && opt_is_f32<GT>) ? 4 : 8;
+static int opt_block_elems(int pdt, int gdt) { return (pdt == AECF_F32 && gdt == AECF_F32) ? OPT_BLOCK_ELEMS : 2 * OPT_BLOCK_ELEMS; }
+
+template <typename PT, typename GT>
+__device__ __forceinline__ void adamw_mp_body(const AdamMpArgs& a, int t, float lr, float gmul) {
+    constexpr int L = opt_lane_elems<PT, GT>;
+    // (the expressions of adamw_multi_kernel, in its order)
+    const float step = a.step[t][0] + 1.0f;
+    const float step_size = lr / -expm1f(step * a.log_beta1), bc2_sqrt = sqrtf(-expm1f(step * a.log_beta2));
+    const float decay = 1.0f - lr * a.weight_decay;
+    const int64_t base = ((int64_t)(blockIdx.x - a.first_block[t]) * 256 + threadIdx.x) * L;
+    const int64_t n = a.numel[t];
+    void* p = a.p[t];
+    const void* g = a.g[t];
+    float* m = a.m[t];
+    float* v = a.v[t];
+    float* w = opt_is_f32<PT> ? nullptr : a.master[t];           // float32 weight of a 16-bit parameter, if kept
+    auto update = [&](float& pp, float gg, float& mm, float& vv) {
+        gg *= gmul;
+        pp *= decay;
+        mm = a.beta1 * mm + (1.0f - a.beta1) * gg;
+        vv = a.beta2 * vv + (1.0f - a.beta2) * gg * gg;
+        const float denom = sqrtf(vv) / bc2_sqrt + a.eps;
+        pp -= step_size * (mm / denom);
+    };
+    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                       reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(w)) & 15) == 0;
+    if (vec && base + L <= n) {
+        float pa[L], ga[L], ma[L], va[L];
+        if (w) opt_loadv<F32, L>(w, base, pa);
+        else opt_loadv<PT, L>(p, base, pa);
+        opt_loadv<GT, L>(g, base, ga);
+        opt_loadv<F32, L>(m, base, ma);
+        opt_loadv<F32, L>(v, base, va);
+#pragma unroll
+        for (int i = 0; i < L; ++i) update(pa[i], ga[i], ma[i], va[i]);
+        if (w) opt_storev<F32, L>(w, base, pa);
+        opt_storev<PT, L>(p, base, pa);
+        opt_storev<F32, L>(m, base, ma);
+        opt_storev<F32, L>(v, base, va);
+    } else {
+        for (int64_t i = base; i < base + L && i < n; ++i) {
+            float pp = w ? w[i] : opt_load1<PT>(p, i), mm = m[i], vv = v[i];
+            update(pp, opt_load1<GT>(g, i), mm, vv);
+            if (w) w[i] = pp;
+            opt_store1<PT>(p, i, pp);
+            m[i] = mm;
+            v[i] = vv;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void adamw_mp_kernel(AdamMpArgs a) {
+    // block-uniform, read by every block and written by none of this launch
+    if ((a.found_inf && a.found_inf[0] != 0.0f) || (a.found_inf2 && a.found_inf2[0] != 0.0f)) return;
+    int t = 0;
+    while (t + 1 < a.n && blockIdx.x >= a.first_block[t + 1]) ++t;
+    const float lr = a.lr_dev ? a.lr_dev[0] : a.lr;
+    float gmul = a.grad_scale ? __fdiv_rn(1.0f, a.grad_scale[0]) : 1.0f;
+    if (a.grad_coef) gmul *= a.grad_coef[0];
+    switch (a.pdt[t] * 3 + a.gdt[t]) {                // aecf_dtype: AECF_BF16 = 0, AECF_F32 = 1, AECF_F16 = 2
+        case 0: adamw_mp_body<BF16, BF16>(a, t, lr, gmul); break;
+        case 1: adamw_mp_body<BF16, F32>(a, t, lr, gmul); break;
+        case 2: adamw_mp_body<BF16, F16>(a, t, lr, gmul); break;
+        case 3: adamw_mp_body<F32, BF16>(a, t, lr, gmul); break;
+        case 4: adamw_mp_body<F32, F32>(a, t, lr, gmul); break;
+        case 5: adamw_mp_body<F32, F16>(a, t, lr, gmul); break;
+        case 6: adamw_mp_body<F16, BF16>(a, t, lr, gmul); break;
+        case 7: adamw_mp_body<F16, F32>(a, t, lr, gmul); break;
+        default: adamw_mp_body<F16, F16>(a, t, lr, gmul); break;
+    }
+    // the two-level ticket of adamw_multi_kernel, and no fence for the reason given there
+    __shared__ int is_last;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int last = 0;
+        const unsigned int sub = blockIdx.x % OPT_SUBTICKETS;
+        const unsigned int expect = (gridDim.x - sub + OPT_SUBTICKETS - 1) / OPT_SUBTICKETS;
+        if (atomicAdd(a.ticket + 1 + sub, 1u) == expect - 1) {
+            a.ticket[1 + sub] = 0u;
+            const unsigned int nsub = gridDim.x < OPT_SUBTICKETS ? gridDim.x : OPT_SUBTICKETS;
+            if (atomicAdd(a.ticket, 1u) == nsub - 1) {
+                a.ticket[0] = 0u;
+                last = 1;
+            }
+        }
+        is_last = last;
+    }
+    __syncthreads();
+    if (is_last && (int)threadIdx.x < a.n) a.step[threadIdx.x][0] += 1.0f;
+}
+
+// ---- global L2 norm of gradients of mixed dtype (torch.nn.utils.clip_grad_norm_'s norm; torch.amp.GradScaler's inf check) ----
+// Launch 1: a block sums the squares of NORM_BLOCK_ELEMS consecutive elements of one tensor (16-byte accesses, a lane's
+// elements in order, then a fixed butterfly over the wave and the four waves in order) and stores ONE float32 partial at its
+// own index.  Launch 2: one block adds the partials (lane i takes i, i + 256, ... in order, the same fixed tree) and writes
+// the norm, the clip coefficient and the non-finite flag.  No float atomics, no fence: the kernel boundary is the hand-off.
+constexpr int NORM_BLOCK_ELEMS = 4096;
+
+struct NormArgs {
+    const void* g[OPT_MAX_TENSORS];
+    int64_t numel[OPT_MAX_TENSORS];
+    unsigned int first_block[OPT_MAX_TENSORS + 1];
+    unsigned char gdt[OPT_MAX_TENSORS];
+    float* partial;                                   // [first_block[n]]
+    int n;
+};
+
+// sum over the 256 lanes of a block in a fixed order; valid in lane 0
+__device__ __forceinline__ float block_sum_256(float x) {
+    __shared__ float wave_sum[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+}
+
+template <typename T>
+__device__ __forceinline__ float sumsq_body(const void* g, int64_t n, int64_t block0) {
+    constexpr int L = opt_is_f32<T> ? 4 : 8;
+    const bool aligned = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+    float acc = 0.0f;
+#pragma unroll
+    for (int it = 0; it < NORM_BLOCK_ELEMS / (256 * L); ++it) {
+        const int64_t i = block0 + ((int64_t)it * 256 + threadIdx.x) * L;
+        if (aligned && i + L <= n) {
+            float x[L];
+            opt_loadv<T, L>(g, i, x);
+#pragma unroll
+            for (int k = 0; k < L; ++k) acc += x[k] * x[k];
+        } else {
+            for (int64_t k = i; k < i + L && k < n; ++k) {
+                const float x = opt_load1<T>(g, k);
+                acc += x * x;
+            }
+        }
+    }
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(NormArgs a) {
+    int t = 0;
+    while (t + 1 < a.n && blockIdx.x >= a.first_block[t + 1]) ++t;
+    const int64_t block0 = (int64_t)(blockIdx.x - a.first_block[t]) * NORM_BLOCK_ELEMS;
+    float acc;
+    if (a.gdt[t] == AECF_F32) acc = sumsq_body<F32>(a.g[t], a.numel[t], block0);
+    else if (a.gdt[t] == AECF_F16) acc = sumsq_body<F16>(a.g[t], a.numel[t], block0);
+    else acc = sumsq_body<BF16>(a.g[t], a.numel[t], block0);
+    acc = block_sum_256(acc);
+    if (threadIdx.x == 0) a.partial[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_finalize_kernel(const float* __restrict__ partial, int64_t count, float max_norm,
+                                                                  const float* __restrict__ grad_scale, float* __restrict__ out) {
+    float acc = 0.0f;
+    for (int64_t i = threadIdx.x; i < count; i += 256) acc += partial[i];
+    acc = block_sum_256(acc);
+    if (threadIdx.x == 0) {
+        const float total = grad_scale ? sqrtf(acc) / grad_scale[0] : sqrtf(acc);
+        out[0] = total;
+        out[1] = max_norm > 0.0f ? fminf(1.0f, max_norm / (total + 1e-6f)) : 1.0f;
+        out[2] = isfinite(acc) ? 0.0f : 1.0f;
+    }
+}
+
+}  // namespace
+
+// tensors with numel > 0 in groups of OPT_MAX_TENSORS; ticket as for launch_adamw_multi.  Returns the number of launches
+int launch_adamw_mp(int n, void* const* p, const void* const* g, float* const* master, float* const* m, float* const* v,
+                    float* const* step, const int64_t* numel, const int32_t* pdt, const int32_t* gdt, unsigned int* ticket, float lr,
+                    float beta1, float beta2, float eps, float weight_decay, const float* lr_dev, const float* grad_scale,
+                    const float* grad_coef, const float* found_inf, const float* found_inf2, hipStream_t s) {
+    int launches = 0;
+    AdamMpArgs a;
+    a.n = 0;
+    unsigned int blocks = 0;
+    auto flush = [&]() {
+        if (a.n == 0) return;
+        a.first_block[a.n] = blocks;
+        a.ticket = ticket + (size_t)launches * (OPT_SUBTICKETS + 1);
+        a.lr_dev = lr_dev; a.grad_scale = grad_scale; a.grad_coef = grad_coef; a.found_inf = found_inf; a.found_inf2 = found_inf2;
+        a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
+        a.log_beta1 = (float)log((double)beta1);
+        a.log_beta2 = (float)log((double)beta2);
+        adamw_mp_kernel<<<dim3(blocks), dim3(256), 0, s>>>(a);
+        ++launches;
+        a.n = 0;
+        blocks = 0;
+    };
+    for (int i = 0; i < n; ++i) {
+        if (numel[i] == 0) continue;
+        const int k = a.n++;
+        a.p[k] = p[i]; a.g[k] = g[i]; a.master[k] = master ? master[i] : nullptr; a.m[k] = m[i]; a.v[k] = v[i]; a.step[k] = step[i];
+        a.numel[k] = numel[i];
+        a.pdt[k] = (unsigned char)pdt[i]; a.gdt[k] = (unsigned char)gdt[i];
+        a.first_block[k] = blocks;
+        const int be = opt_block_elems(pdt[i], gdt[i]);
+        blocks += (unsigned int)((numel[i] + be - 1) / be);
+        if (a.n == OPT_MAX_TENSORS) flush();
+    }
+    flush();
+    return launches;
+}
+
+int64_t grad_norm_blocks(int n, const int64_t* numel) {
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) blocks += (numel[i] + NORM_BLOCK_ELEMS - 1) / NORM_BLOCK_ELEMS;
+    return blocks;
+}
+
+// partial: grad_norm_blocks(n, numel) floats (> 0: the caller returns early otherwise); out: 3 floats
+void launch_grad_norm(int n, const void* const* g, const int32_t* gdt, const int64_t* numel, float max_norm, const float* grad_scale,
+                      float* partial, float* out, hipStream_t s) {
+    NormArgs a;
+    a.n = 0;
+    unsigned int blocks = 0;
+    int64_t done = 0;
+    auto flush = [&]() {
+        if (a.n == 0) return;
+        a.first_block[a.n] = blocks;
+        a.partial = partial + done;
+        grad_sumsq_kernel<<<dim3(blocks), dim3(256), 0, s>>>(a);
+        done += blocks;
+        a.n = 0;
+        blocks = 0;
+    };
+    for (int i = 0; i < n; ++i) {
+        if (numel[i] == 0) continue;
+        const int k = a.n++;
+        a.g[k] = g[i]; a.numel[k] = numel[i]; a.gdt[k] = (unsigned char)gdt[i];
+        a.first_block[k] = blocks;
+        blocks += (unsigned int)((numel[i] + NORM_BLOCK_ELEMS - 1) / NORM_BLOCK_ELEMS);
+        if (a.n == OPT_MAX_TENSORS) flush();
+    }
+    flush();
+    grad_sumsq_finalize_kernel<<<dim3(1), dim3(256), 0, s>>>(partial, done, max_norm, grad_scale, out);
 }
 
 }  // namespace aecf

@@ -1,14 +1,25 @@
-"""AdamW of the example trainer as one launch (``aecf_adamw_step``; ref xrays/train_xrays_example.py:322-323, 376 uses
+"""AdamW of the example trainer as one launch (ref xrays/train_xrays_example.py:322-323, 376 uses
 ``torch.optim.AdamW(lr=1e-4, weight_decay=0.01)``).  Same update rule and the same state layout as torch's (per parameter:
 ``step`` -- a float32 scalar on the device --, ``exp_avg``, ``exp_avg_sq``), so state dicts move between the two; the step
-counters advance on the device, which makes ``step()`` capturable into a HIP graph without further flags.  One limit under
-capture: the hyper-parameters (``lr`` included) are kernel ARGUMENTS, so a captured step replays with the values it was captured
-with -- a learning-rate schedule needs a re-capture (or the eager step) when the rate changes.  A replay moves no version counter: ``xray.GraphedTrainStep`` tells the
-pools of its model after each one; after replays of a graph of your own, call ``invalidate_cast_cache()`` on the pools before
-inference."""
+counters advance on the device, which makes ``step()`` capturable into a HIP graph without further flags.
+
+Two entry points of the library sit behind ``FusedAdamW.step``:
+
+* ``aecf_adamw_step``: float32 parameters with float32 gradients, a Python-number ``lr``, no clipping, no GradScaler -- the
+  step of the float32 trainer, unchanged.
+* ``aecf_adamw_mp_step``: everything else -- bf16 / f16 parameters (gradients in the parameter's dtype or float32) with
+  float32 moments and, with ``master_weights=True``, float32 master weights in ``state[p]["master"]``; global-norm clipping
+  (``max_grad_norm``); ``torch.amp.GradScaler`` on the device; a learning rate read from device memory.
+
+Under capture the Python-number hyper-parameters are kernel ARGUMENTS: a captured step replays with the values it was captured
+with.  A learning-rate schedule therefore passes ``lr`` as a one-element float32 tensor on the parameters' device (as torch's
+fused AdamW allows): the kernel reads it at replay time, so ``lr.fill_(...)`` between replays is followed.  A replay moves no
+version counter: ``xray.GraphedTrainStep`` tells the pools of its model after each one; after replays of a graph of your own,
+call ``invalidate_cast_cache()`` on the pools before inference."""
 from __future__ import annotations
 
 import ctypes
+from itertools import chain
 from typing import Iterable
 
 import torch
@@ -16,13 +27,91 @@ import torch
 from . import _lib
 from .layer import _stream
 
+_DTYPES = {torch.bfloat16: _lib.AECF_BF16, torch.float32: _lib.AECF_F32, torch.float16: _lib.AECF_F16}
+_F32_STATE = ("master", "exp_avg", "exp_avg_sq")
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _launch_grad_norm(grads, max_norm, grad_scale, workspace, out):
+    lib = _lib.load()
+    numel = (ctypes.c_int64 * len(grads))(*[g.numel() for g in grads])
+    _lib.check(lib.aecf_grad_norm(
+        len(grads), _ptr_array(grads), (ctypes.c_int32 * len(grads))(*[_DTYPES[g.dtype] for g in grads]), numel,
+        float(max_norm), None if grad_scale is None else grad_scale.data_ptr(), workspace.data_ptr(),
+        workspace.numel() * 4, out.data_ptr(), _stream()), "aecf_grad_norm")
+
+
+def _dense_grads(params):
+    grads = []
+    for p in params:
+        g = p.grad
+        if g is None or g.numel() == 0:
+            continue
+        if g.device.type != "cuda" or g.is_sparse or g.dtype not in _DTYPES:
+            raise RuntimeError("aecf_amd.optim: dense float32 / bfloat16 / float16 gradients on a ROCm device only")
+        grads.append(g if g.is_contiguous() else g.contiguous())
+    return grads
+
+
+def grad_norm(params, *, grad_scale=None) -> torch.Tensor:
+    """Global L2 norm of the gradients of ``params`` (``aecf_grad_norm``: two launches, fixed summation order) as a float32
+    scalar ON THE DEVICE -- no host synchronisation.  ``grad_scale`` (a one-element float32 device tensor, e.g. a GradScaler's
+    scale) divides the result.  What ``torch.nn.utils.clip_grad_norm_(params, inf)`` returns, without touching the gradients."""
+    grads = _dense_grads([params] if torch.is_tensor(params) else list(params))
+    if not grads:
+        raise RuntimeError("aecf_amd.optim.grad_norm: no gradients")
+    dev = grads[0].device
+    if any(g.device != dev for g in grads):
+        raise RuntimeError("aecf_amd.optim.grad_norm: gradients on one device only")
+    lib = _lib.load()
+    need = lib.aecf_grad_norm_workspace_bytes(len(grads), (ctypes.c_int64 * len(grads))(*[g.numel() for g in grads]))
+    workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    _launch_grad_norm(grads, 0.0, grad_scale, workspace, out)
+    return out[0]
+
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2):
-        if lr < 0 or eps < 0 or not 0 < betas[0] < 1 or not 0 < betas[1] < 1 or weight_decay < 0:
+    """``torch.optim.AdamW`` (amsgrad / maximize off) in one launch per 24 tensors.
+
+    ``lr``: a Python number, or a one-element float32 tensor on the parameters' device that the kernel reads.
+    ``master_weights``: keep a float32 ``state[p]["master"]`` for every bf16 / f16 parameter (created from the parameter at
+    its first step); the parameter is then the round-to-nearest-even of its master after every step.  At lr = 1e-4 the update
+    of a bf16 weight near 1 is below half an ulp: without masters such a weight never moves.
+    ``max_grad_norm``: clip by the global L2 norm of all gradients of this optimiser (they must live on one device), computed
+    by one ``aecf_grad_norm`` before the update launches.  ``last_grad_norm`` is the (unscaled) norm and ``last_clip_coef`` the
+    coefficient, as device tensors that are never read on the host.  Two differences from ``torch.nn.utils.clip_grad_norm_``: the gradients themselves are NOT rewritten
+    (the coefficient ``min(1, max / (norm + 1e-6))`` is applied inside the update), and a non-finite norm does not let NaN
+    through -- the step is skipped on the device (nothing is written, no step counter advances) and the device counter
+    ``skipped_steps`` (None until the first clipped step) goes up by one.
+    ``torch.amp.GradScaler``: ``scaler.step(opt)`` hands over its scale and its found-inf flag as device tensors; the kernel
+    unscales and skips by them, with no ``.item()``.  With clipping on, the scaler's flag and the norm's are two pointer
+    arguments of the same launch (OR-ed by the kernel)."""
+
+    _step_supports_amp_scaling = True
+
+    def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, *,
+                 master_weights: bool = False, max_grad_norm=None):
+        if torch.is_tensor(lr):
+            if lr.numel() != 1 or lr.dtype != torch.float32:
+                raise ValueError("FusedAdamW: a tensor lr is ONE float32 element (on the parameters' device)")
+        elif lr < 0:
             raise ValueError("FusedAdamW: invalid hyper-parameter")
+        if eps < 0 or not 0 < betas[0] < 1 or not 0 < betas[1] < 1 or weight_decay < 0:
+            raise ValueError("FusedAdamW: invalid hyper-parameter")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError("FusedAdamW: max_grad_norm must be positive (None: no clipping)")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.master_weights = bool(master_weights)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = self.last_clip_coef = None
+        self.skipped_steps = None
         self._tickets = {}
+        self._norm_out = None             # [norm, coef, non-finite flag] on the device
+        self._norm_workspaces = []
 
     def _ticket(self, device, group_index, n):
         """Ticket words of one parameter group's launch, kept for the optimizer's lifetime: a buffer that has been handed to a
@@ -37,6 +126,42 @@ class FusedAdamW(torch.optim.Optimizer):
         held.append(t)
         return t
 
+    def _clip(self, grads, grad_scale):
+        """One aecf_grad_norm over every gradient of the step; its buffers are kept like the tickets."""
+        dev = grads[0].device
+        if any(g.device != dev for g in grads):
+            raise RuntimeError("FusedAdamW: max_grad_norm needs all parameters on one device")
+        if self._norm_out is None:
+            self._norm_out = torch.zeros(3, dtype=torch.float32, device=dev)
+            self.skipped_steps = torch.zeros((), dtype=torch.float32, device=dev)
+            self.last_grad_norm, self.last_clip_coef = self._norm_out[0], self._norm_out[1]
+        elif self._norm_out.device != dev:
+            raise RuntimeError("FusedAdamW: the parameters moved to another device")
+        need = _lib.load().aecf_grad_norm_workspace_bytes(len(grads), (ctypes.c_int64 * len(grads))(*[g.numel() for g in grads])) // 4
+        workspace = next((w for w in self._norm_workspaces if w.numel() >= need), None)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.float32, device=dev)
+            self._norm_workspaces.append(workspace)
+        _launch_grad_norm(grads, self.max_grad_norm, grad_scale, workspace, self._norm_out)
+        self.skipped_steps.add_(self._norm_out[2])                 # (bookkeeping on the device; the skip itself is the kernel's)
+
+    def load_state_dict(self, state_dict):
+        """``Optimizer.load_state_dict`` casts floating-point state to the parameter's dtype, which would round the float32
+        masters and moments of a bf16 / f16 parameter: the float32 tensors of the incoming state are put back afterwards, on
+        the parameter's device.  (A state written by ``torch.optim.AdamW`` for bf16 parameters holds bf16 moments and no
+        master: the next step widens the moments and creates the masters from the parameters.)"""
+        super().load_state_dict(state_dict)
+        saved_ids = list(chain.from_iterable(g["params"] for g in state_dict["param_groups"]))
+        own = list(chain.from_iterable(g["params"] for g in self.param_groups))
+        for pid, p in zip(saved_ids, own):
+            src = state_dict["state"].get(pid)
+            if not src or p.dtype == torch.float32:
+                continue
+            for key in _F32_STATE:
+                value = src.get(key)
+                if torch.is_tensor(value) and value.dtype == torch.float32:
+                    self.state[p][key] = value.detach().to(device=p.device, copy=True)
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -45,6 +170,14 @@ class FusedAdamW(torch.optim.Optimizer):
                 loss = closure()
         lib = _lib.load()
         vp = ctypes.c_void_p
+        # what torch.amp.GradScaler.step sets for the duration of this call (grad_scale is None when the gradients have been
+        # unscaled already, found_inf is the scaler's flag either way)
+        grad_scale = getattr(self, "grad_scale", None)
+        found_inf = getattr(self, "found_inf", None)
+        for t in (grad_scale, found_inf):
+            if t is not None and (not torch.is_tensor(t) or t.numel() != 1 or t.dtype != torch.float32 or t.device.type != "cuda"):
+                raise RuntimeError("FusedAdamW: grad_scale / found_inf must be one-element float32 device tensors")
+        work = []
         for gi, group in enumerate(self.param_groups):
             if group.get("amsgrad") or group.get("maximize"):
                 # (a state dict loaded from torch.optim.AdamW can carry these; the kernel implements neither)
@@ -52,18 +185,19 @@ class FusedAdamW(torch.optim.Optimizer):
             ps = [p for p in group["params"] if p.grad is not None and p.numel() > 0]    # (torch skips empty tensors too)
             if not ps:
                 continue
-            dev = ps[0].device
             for p in ps:
-                if p.device.type != "cuda" or p.dtype != torch.float32 or p.grad.dtype != torch.float32 or p.grad.is_sparse:
-                    raise RuntimeError("FusedAdamW: float32 parameters with dense float32 gradients on a ROCm device only "
-                                       "(no CPU fallback is provided)")
+                if p.device.type != "cuda" or p.dtype not in _DTYPES or p.grad.dtype not in _DTYPES or p.grad.is_sparse:
+                    raise RuntimeError("FusedAdamW: float32 / bfloat16 / float16 parameters with dense gradients on a ROCm "
+                                       "device only (no CPU fallback is provided)")
+                if p.grad.dtype != torch.float32 and p.grad.dtype != p.dtype:
+                    raise RuntimeError("FusedAdamW: a gradient is float32 or of its parameter's dtype")
                 if not p.is_contiguous():
                     raise RuntimeError("FusedAdamW: parameters must be contiguous")
                 st = self.state[p]
                 if len(st) == 0:
                     st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
                 else:
                     # a state loaded from torch.optim.AdamW keeps `step` on the host (or as a Python number) unless that optimizer
                     # was capturable: the kernel reads and advances it on the device
@@ -73,15 +207,55 @@ class FusedAdamW(torch.optim.Optimizer):
                     for key in ("exp_avg", "exp_avg_sq"):
                         if st[key].device != p.device or st[key].dtype != torch.float32 or not st[key].is_contiguous():
                             st[key] = st[key].to(device=p.device, dtype=torch.float32).contiguous()
+                if p.dtype != torch.float32:
+                    master = st.get("master")                       # (a loaded state may carry one without the flag: it is kept)
+                    if master is None:
+                        if self.master_weights:
+                            st["master"] = p.detach().to(torch.float32, memory_format=torch.contiguous_format)
+                    elif master.device != p.device or master.dtype != torch.float32 or not master.is_contiguous():
+                        st["master"] = master.to(device=p.device, dtype=torch.float32).contiguous()
             grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
-            arr = lambda ts: (vp * len(ts))(*[t.data_ptr() for t in ts])
+            work.append((gi, group, ps, grads))
+        if not work:
+            return loss
+        clip = self.max_grad_norm is not None
+        if clip:
+            self._clip([g for _, _, _, grads in work for g in grads], grad_scale)
+        for gi, group, ps, grads in work:
+            dev = ps[0].device
+            lr = group["lr"]
             b1, b2 = group["betas"]
-            _lib.check(lib.aecf_adamw_step(
-                len(ps), arr(ps), arr(grads), arr([self.state[p]["exp_avg"] for p in ps]),
-                arr([self.state[p]["exp_avg_sq"] for p in ps]), arr([self.state[p]["step"] for p in ps]),
-                (ctypes.c_int64 * len(ps))(*[p.numel() for p in ps]), self._ticket(dev, gi, len(ps)).data_ptr(),
-                float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), _stream()),
-                "aecf_adamw_step")
+            states = [self.state[p] for p in ps]
+            numel = (ctypes.c_int64 * len(ps))(*[p.numel() for p in ps])
+            ticket = self._ticket(dev, gi, len(ps)).data_ptr()
+            plain = (not clip and grad_scale is None and found_inf is None and not torch.is_tensor(lr)
+                     and all(p.dtype == torch.float32 and g.dtype == torch.float32 for p, g in zip(ps, grads)))
+            if plain:
+                _lib.check(lib.aecf_adamw_step(
+                    len(ps), _ptr_array(ps), _ptr_array(grads), _ptr_array([st["exp_avg"] for st in states]),
+                    _ptr_array([st["exp_avg_sq"] for st in states]), _ptr_array([st["step"] for st in states]),
+                    numel, ticket, float(lr), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), _stream()),
+                    "aecf_adamw_step")
+            else:
+                lr_dev = None
+                if torch.is_tensor(lr):
+                    if lr.numel() != 1 or lr.dtype != torch.float32 or lr.device != dev:
+                        raise RuntimeError("FusedAdamW: a tensor lr is ONE float32 element on the parameters' device")
+                    lr_dev = lr.data_ptr()
+                for t in (grad_scale, found_inf):
+                    if t is not None and t.device != dev:
+                        raise RuntimeError("FusedAdamW: the GradScaler's tensors and the parameters must share a device")
+                i32 = ctypes.c_int32 * len(ps)
+                _lib.check(lib.aecf_adamw_mp_step(
+                    len(ps), _ptr_array(ps), _ptr_array(grads), _ptr_array([st.get("master") for st in states]),
+                    _ptr_array([st["exp_avg"] for st in states]), _ptr_array([st["exp_avg_sq"] for st in states]),
+                    _ptr_array([st["step"] for st in states]), numel, i32(*[_DTYPES[p.dtype] for p in ps]),
+                    i32(*[_DTYPES[g.dtype] for g in grads]), ticket, 0.0 if lr_dev else float(lr), float(b1), float(b2),
+                    float(group["eps"]), float(group["weight_decay"]), lr_dev,
+                    None if grad_scale is None else grad_scale.data_ptr(),
+                    self._norm_out[1:].data_ptr() if clip else None,
+                    None if found_inf is None else found_inf.data_ptr(),
+                    self._norm_out[2:].data_ptr() if clip else None, _stream()), "aecf_adamw_mp_step")
             # the launch wrote the parameters through raw pointers: move their version counters the way an in-place torch op
             # would, so that whatever keys on them (the pool's inference caches, autograd's saved-tensor checks) sees the update
             torch.autograd.graph.increment_version(ps)

@@ -5,6 +5,7 @@ of ``train_both_models`` / ``main`` in ``xrays/train_xrays_example.py:312-427, 7
 
     python -m aecf_amd.train_xray --epochs 60 --switch-epoch 40                     # one GPU
     python -m torch.distributed.run --nproc-per-node 4 --master-addr 127.0.0.1 -m aecf_amd.train_xray   # DP x 4
+    python -m aecf_amd.train_xray --param-dtype bfloat16 --max-grad-norm 1.0        # bf16 model, float32 masters, clipping
 
 The reference trains on precomputed CLIP features of a chest X-ray set that is not part of its repository
 (``.MISSING_LARGE_BLOBS``); ``--data train.pt,val.pt`` loads such files (dicts with image / text / labels), otherwise a
@@ -82,6 +83,9 @@ def main(argv=None):
     ap.add_argument("--data", default=None, help="train.pt,val.pt with image/text/labels tensors (default: synthetic)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--save", default=None, help="state_dict file written by rank 0 at the end (ref :766-772)")
+    ap.add_argument("--param-dtype", choices=("float32", "bfloat16"), default="float32",
+                    help="bfloat16: the model and its inputs in bf16, FusedAdamW keeps float32 master weights and moments")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm inside the optimiser step")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -106,12 +110,18 @@ def main(argv=None):
         image, text, labels = synthetic_split(args.samples, args.classes, 512, args.seed + 1, device)
         v_image, v_text, v_labels = synthetic_split(args.val_samples, args.classes, 512, args.seed + 2, device)
 
+    low = args.param_dtype == "bfloat16"
+    if low:
+        image, text, v_image, v_text = (t.bfloat16() for t in (image, text, v_image, v_text))
     torch.manual_seed(args.seed + 17 * rank)                       # replicas differ until the broadcast below
     model = AECFModel(image.shape[1], text.shape[1], args.classes, args.hidden).to(device)
+    if low:
+        model = model.bfloat16()
     params = list(model.parameters())
     dp.broadcast_parameters(params + list(model.buffers()))
     bucket = dp.FlatGradBucket(params) if world > 1 else None
-    opt = FusedAdamW(params, lr=args.lr, weight_decay=0.01)                 # ref :322-323 (torch.optim.AdamW's update, one launch)
+    opt = FusedAdamW(params, lr=args.lr, weight_decay=0.01,                 # ref :322-323 (torch.optim.AdamW's update, one launch)
+                     master_weights=low, max_grad_norm=args.max_grad_norm)
     crit = torch.nn.BCEWithLogitsLoss()
     n = image.shape[0]
     steps = (n + args.batch - 1) // args.batch                              # the short last batch is kept (DataLoader default)
@@ -144,7 +154,7 @@ def main(argv=None):
                 opt.step()
                 continue
             logits, info = model(image[sel], text[sel], return_info=True, mask_uniforms=u, missing=missing)
-            loss = crit(logits, labels[sel])
+            loss = crit(logits.float(), labels[sel])
             if bucket is None:
                 opt.zero_grad(set_to_none=True)
             else:

@@ -419,6 +419,43 @@ int aecf_adamw_step(int32_t n, void* const* param, const void* const* grad, void
                     void* const* exp_avg_sq, void* const* step, const int64_t* numel, void* ticket, float lr,
                     float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* ---- the optimiser step of a mixed-precision trainer (new entry points under ABI v10, no bump) ----
+ * aecf_adamw_mp_step: the update and the ticket contract of aecf_adamw_step (it replaces the same torch.optim.AdamW of ref
+ * xrays/train_xrays_example.py:322-323, for a model held in bf16 / f16) over tensors whose param[i] is param_dtype[i] and whose
+ * grad[i] is grad_dtype[i] (aecf_dtype values, independent of each other).  exp_avg / exp_avg_sq / step are float32 always.
+ * master (the array, or any entry) may be NULL; master[i] != NULL with a 16-bit param[i] is its float32 master weight [numel[i]]:
+ * it is read and updated in float32 and param[i] is only WRITTEN, with the round-to-nearest-even conversion of
+ * aecf_cast_f32_to_bf16 / _f16 (param == master.to(dtype) bit for bit).  Without a master the parameter is widened, updated in
+ * float32 and rounded once on the store.  (A master beside a float32 parameter is ignored.)  Tensors with numel[i] == 0 are
+ * skipped, their pointers are not read.
+ * Launch-wide DEVICE float32 scalars, each may be NULL:
+ *   lr_dev      replaces `lr` (what a tensor lr is to torch's fused AdamW): a captured step follows the value at replay time;
+ *   grad_scale  the loss scale of torch.amp.GradScaler: gradients are multiplied by 1 / *grad_scale (replaces unscale_);
+ *   grad_coef   the clip coefficient aecf_grad_norm wrote (out + 1): gradients are multiplied by it (replaces the in-place
+ *               scaling of torch.nn.utils.clip_grad_norm_; the gradients themselves are not rewritten);
+ *   found_inf, found_inf2   when either holds a non-zero value the launches write NOTHING: no parameter, master, moment or
+ *               step counter changes (the skipped step of torch.amp.GradScaler / torch's fused AdamW).  Two, so that the
+ *               scaler's flag and aecf_grad_norm's (out + 2) are OR-ed on the device without a launch in between.
+ * Checks, before anything touches the device: n < 0 or a negative numel -> AECF_ERR_BAD_DIMS; a dtype outside the three ->
+ * AECF_ERR_UNSUPPORTED; n == 0 or every tensor empty -> AECF_OK without a launch; a required pointer NULL ->
+ * AECF_ERR_NULL_POINTER. */
+int aecf_adamw_mp_step(int32_t n, void* const* param, const void* const* grad, void* const* master, void* const* exp_avg,
+                       void* const* exp_avg_sq, void* const* step, const int64_t* numel, const int32_t* param_dtype,
+                       const int32_t* grad_dtype, void* ticket, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, const float* lr_dev, const float* grad_scale, const float* grad_coef,
+                       const float* found_inf, const float* found_inf2, void* stream);
+/* Global L2 norm of n gradients of mixed dtype (replaces the norm of torch.nn.utils.clip_grad_norm_ and the inf check of
+ * torch.amp.GradScaler) in two launches, fixed summation order, no float atomics: blocks store partial sums of squares into
+ * `workspace` (aecf_grad_norm_workspace_bytes(n, numel); 0 for n <= 0, NULL or a negative numel), one block adds them in index
+ * order and writes three DEVICE floats:
+ *   out[0] = sqrt(sum g^2) / scale                  (scale = *grad_scale, 1 when grad_scale is NULL)
+ *   out[1] = min(1, max_norm / (out[0] + 1e-6))     (clip_grad_norm_'s coefficient; 1 when max_norm <= 0: norm only)
+ *   out[2] = 1 if the sum is not finite, else 0.
+ * Checks as above, then workspace_bytes too small -> AECF_ERR_WORKSPACE. */
+size_t aecf_grad_norm_workspace_bytes(int32_t n, const int64_t* numel);
+int aecf_grad_norm(int32_t n, const void* const* grad, const int32_t* grad_dtype, const int64_t* numel, float max_norm,
+                   const float* grad_scale, void* workspace, size_t workspace_bytes, float* out, void* stream);
+
 /* ---- contrastive term (BASELINE.json north_star; NOT in the reference: SURVEY.md 8a row A9, build-defined) ----
  * Row-wise L2 normalisation zn = z / max(||z||, eps) and its backward dz = (dzn - zn (dzn.zn)) * inv_norm. */
 int aecf_l2norm_forward(int64_t n, int32_t d, int32_t dtype, float eps, const void* z, void* zn,
