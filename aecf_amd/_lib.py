@@ -179,6 +179,14 @@ _SYMBOLS = [
     ("aecf_nce_sym_grads_dt", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
       c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # sigmoid contrastive loss: device temperature and bias
+    ("aecf_sig_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
+    ("aecf_sig_pass1", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+      c_void_p, c_void_p]),
+    ("aecf_sig_grads", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+      c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 

@@ -872,6 +872,41 @@ int aecf_nce_sym_grads_dt(int64_t rows, int64_t cols, int64_t row_offset, int32_
     return launch_status();
 }
 
+// ---- pairwise sigmoid (SigLIP) loss (include/aecf_hip.h, "sigmoid contrastive loss")
+
+size_t aecf_sig_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !sig_gemm_supported(AECF_BF16, d)) return 0;
+    return sig_gemm_workspace_bytes(rows, cols, d);
+}
+
+int aecf_sig_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                   const float* bias, const void* a, const void* b, void* workspace, size_t workspace_bytes, float* loss_rows,
+                   float* d_bias, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!sig_gemm_supported(AECF_BF16, d)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !bias || !a || !b || !workspace || !loss_rows || !d_bias) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < sig_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    launch_sig_gemm_pass1(rows, cols, row_offset, d, temperature, min_temperature, bias, a, b, workspace, loss_rows, d_bias,
+                          (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_sig_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                   float coef, const void* a, const void* b, void* workspace, size_t workspace_bytes, const float* upstream,
+                   int32_t grad_dtype, void* da, void* db, float* d_temperature, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (grad_dtype != AECF_BF16 && grad_dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!sig_gemm_supported(AECF_BF16, d)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a || !b || !workspace || !da || !db) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < sig_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    launch_sig_gemm_grads(rows, cols, d, dt, coef, a, b, workspace, upstream, grad_dtype == AECF_BF16 ? 1 : 0, da, db,
+                          (hipStream_t)stream);
+    return launch_status();
+}
+
 int aecf_route_build(int64_t rows, const uint8_t* present_a, const uint8_t* present_b, int32_t* route, int32_t* slot,
                      int32_t* index, int32_t* counts, void* stream) {
     if (rows <= 0 || rows > 0x7fffffff) return AECF_ERR_BAD_DIMS;

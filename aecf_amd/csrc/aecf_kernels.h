@@ -271,6 +271,17 @@ void launch_nce_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d
                            const void* b, void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s,
                            const NceDevTemp* dt = nullptr);
 
+// Pairwise sigmoid (SigLIP) loss on the same tile GEMMs (aecf_nce_gemm.hip): g = sigmoid(l) - [positive] as bf16 [rows, cols] in
+// the workspace (unscaled: coef / Tc and the upstream gradient are applied to the float32 sums of the gradient GEMMs).
+// T and the bias are device scalars; pass 1 writes loss_rows[i] = sum_j softplus(-y_ij l_ij) and d_bias[0] = sum_ij g_ij,
+// the gradient call writes dt.d_t when it is given.
+bool sig_gemm_supported(int dtype, int d);
+size_t sig_gemm_workspace_bytes(int64_t rows, int64_t cols, int d);
+void launch_sig_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const float* temp, float min_temp, const float* bias,
+                           const void* a, const void* b, void* workspace, float* loss_rows, float* d_bias, hipStream_t s);
+void launch_sig_gemm_grads(int64_t rows, int64_t cols, int d, const NceDevTemp& dt, float coef, const void* a, const void* b,
+                           void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s);
+
 // ---------------- presence routing (aecf_route.hip) ----------------
 void launch_route_build(int64_t rows, const uint8_t* pa, const uint8_t* pb, int32_t* route, int32_t* slot, int32_t* index,
                         int32_t* counts, hipStream_t s);

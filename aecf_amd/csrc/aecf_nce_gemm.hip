@@ -22,6 +22,19 @@
 // [64 k][512 B] tile read TRANSPOSED with ds_read_b64_tr_b16 -- no transposed copy of W or of the embeddings exists.
 // The product is formed transposed (the n operand is the MFMA A operand), so a lane ends with 4 consecutive output columns
 // of one row: 8-byte bf16 / 16-byte float32 stores.
+//
+// The pairwise sigmoid (SigLIP) loss rides on the same kernel (aecf_sig_pass1 / aecf_sig_grads): l = a.b / Tc + bias,
+// L = coef sum_ij softplus(-y_ij l_ij).  Its logits pass is the EPI_SIG epilogue: g = sigmoid(l) - [j = off + i] goes ONCE, as
+// bf16, into the tiled workspace layout above (padding stored as 0), with two per-row float32 partials per n tile (sum softplus,
+// sum g before the rounding) reduced in a fixed order by sig_rows_kernel / sig_dbias_kernel -- no column sums, no exchange
+// between the passes, no weights pass.  g is stored UNSCALED: coef / Tc and the upstream scalar multiply the float32
+// accumulators in the output stage of the two gradient products (EPI_OUT_S / EPI_OUT_TD_S), so nothing small is rounded to bf16
+// (sigmoid = e^-30 is 9e-14 there) and one logits pass serves any upstream.  The epilogue holds v_exp, v_rcp and v_log per
+// element (EPI_EXP: one v_exp); a block owns its CU (128 KB of stages), so there is no other block's MFMA work to hide them
+// behind and no next tile in this block: what was done instead is to keep everything around them short -- the logit is never
+// formed (n = l log2 e comes out of one packed fma on the accumulator), softplus needs no max, no select and no second
+// exponential (sig_terms), the sums are packed adds, and the positive / ragged-edge selects run only in the tiles that hold
+// such elements (a block-uniform branch).
 #include <math.h>
 #include <type_traits>
 
@@ -36,7 +49,9 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // _DT / _TD forms (device temperature): EPI_EXP_DT derives scale2 / shift2 from max(*temp, min_temp); EPI_OUT_TD also writes the
 // block's sum of acc * (the bf16 m-operand rows of tdot_src at the output's position) -- q_i.dq_i summed over the tile, from the
 // float32 accumulator -- to tdot_part[(split m_tiles + mi) n_tiles + ni]
-enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3 };
+// EPI_SIG (sigmoid loss, logits pass): g = sigmoid(l) - [positive] as bf16 into the tiled workspace + two per-row partials per
+// n tile; EPI_OUT_S / EPI_OUT_TD_S: EPI_OUT / EPI_OUT_TD with the float32 accumulator multiplied by coef / Tc * upstream first
+enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6 };
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -69,7 +84,34 @@ struct NceGemmArgs {
     // EPI_OUT_TD
     const unsigned short* tdot_src;     // [m_valid][ldo] bf16
     float* tdot_part;                   // [splits][m_tiles][n_tiles]
+    // EPI_SIG (also reads temp / min_temp and writes g through e / e_tiles)
+    const float* bias;                  // device scalar
+    int64_t row_offset;                 // the positive of output row i is column row_offset + i
+    float* sp_part;                     // [n_tiles][m_tiles 256]  sum_j softplus(-y l)
+    float* sg_part;                     // [n_tiles][m_tiles 256]  sum_j (sigmoid(l) - [positive]), float32 before the bf16 rounding
+    // EPI_OUT_S / EPI_OUT_TD_S (also read temp / min_temp)
+    float coef;
+    const float* upstream;              // device scalar, may be NULL (= 1)
 };
+
+// sigmoid(x) and the pieces of softplus(x) for x = n ln 2, two elements: u = 2^min(n, 126), t = 1 + u, r = 1 / t;
+//   sigmoid = u r,   softplus = ln 2 * lg2 + corr with lg2 = log2 t + (n - min(n, 126)) and corr = (u - (t - 1)) r:
+// corr hands back what the rounding of 1 + u dropped (t - 1 and u - (t - 1) are exact), so softplus keeps its relative
+// accuracy down to u ~ 1e-38 without a branch; the clamp keeps u finite for any 1 / T (past it sigmoid is 1 and softplus x).
+struct SigTerms {
+    f32x2 sig, lg2, corr;
+};
+__device__ __forceinline__ SigTerms sig_terms(f32x2 n) {
+    const f32x2 nc = f32x2{fminf(n[0], 126.f), fminf(n[1], 126.f)};
+    const f32x2 u = f32x2{__builtin_amdgcn_exp2f(nc[0]), __builtin_amdgcn_exp2f(nc[1])};
+    const f32x2 t = u + f32x2{1.f, 1.f};
+    const f32x2 r = f32x2{__builtin_amdgcn_rcpf(t[0]), __builtin_amdgcn_rcpf(t[1])};
+    SigTerms o;
+    o.sig = u * r;
+    o.lg2 = f32x2{__builtin_amdgcn_logf(t[0]), __builtin_amdgcn_logf(t[1])} + (n - nc);
+    o.corr = (u - (t - f32x2{1.f, 1.f})) * r;
+    return o;
+}
 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
@@ -309,7 +351,16 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
         // ---- epilogue: lane (r16, lg) holds C[m = 128 wm + 16 rt + r16][n = 64 wn + 16 ct + 4 lg + r], r = 0..3
         const int64_t gi0 = (int64_t)BT * mi + 128 * wm + r16;
         const int gj0 = BT * ni + 64 * wn + 4 * lg;
-        if (EPI == EPI_OUT || EPI == EPI_OUT_TD) {
+        if (EPI == EPI_OUT || EPI == EPI_OUT_TD || EPI == EPI_OUT_S || EPI == EPI_OUT_TD_S) {
+            if (EPI == EPI_OUT_S || EPI == EPI_OUT_TD_S) {
+                // g is stored unscaled: coef / Tc and the gradient arriving at the loss meet the float32 sums here
+                float osc = p.coef * nce_dev_inv_temp(p.temp, p.min_temp);
+                if (p.upstream) osc *= p.upstream[0];
+#pragma unroll
+                for (int rt = 0; rt < 8; ++rt)
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) acc[rt][ct] *= osc;
+            }
             float* o = reinterpret_cast<float*>(p.out) + (int64_t)split * p.slab_stride;
             unsigned short* ob = reinterpret_cast<unsigned short*>(p.out);
 #pragma unroll
@@ -328,7 +379,7 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                     }
                 }
             }
-            if (EPI == EPI_OUT_TD) {
+            if (EPI == EPI_OUT_TD || EPI == EPI_OUT_TD_S) {
                 float td = 0.f;
 #pragma unroll
                 for (int rt = 0; rt < 8; ++rt) {
@@ -357,6 +408,71 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                     p.tdot_part[((int64_t)split * p.m_tiles + mi) * p.n_tiles + ni] =
                         ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
             }
+        } else if (EPI == EPI_SIG) {
+            // n = l log2(e) straight from the accumulator: l = acc / Tc + bias is never formed
+            const float s2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f, b2 = p.bias[0] * 1.4426950408889634f;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
+            float* lsp = reinterpret_cast<float*>(smem);        // [4][256] softplus sums | [4][256] g sums
+            float* lsg = lsp + 4 * BT;
+            // block-uniform: only tiles on the band of positives or on the ragged edge pay for the selects
+            const int64_t p0 = p.row_offset + (int64_t)BT * mi;
+            const bool special = BT * (mi + 1) > p.m_valid || BT * (ni + 1) > p.n_valid ||
+                                 (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
+            unsigned short* gtile = p.e + ((int64_t)mi * p.e_tiles + 4 * ni + wn) * (BT * 64) + (128 * wm + r16) * 64 + 4 * lg;
+            float rsp[8], rsg[8];
+            auto rows8 = [&](auto special_c) {
+                constexpr bool SP = decltype(special_c)::value;
+#pragma unroll
+                for (int rt = 0; rt < 8; ++rt) {
+                    const int64_t i = gi0 + 16 * rt;
+                    const bool iok = i < p.m_valid;
+                    const int64_t jp = p.row_offset + i;
+                    f32x2 sl = f32x2{0.f, 0.f}, sc = f32x2{0.f, 0.f}, sg = f32x2{0.f, 0.f};
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+                        const int j = gj0 + 16 * ct;
+                        f32x2 g[2];
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            const f32x2 n = f32x2{acc[rt][ct][2 * h], acc[rt][ct][2 * h + 1]} * f32x2{s2, s2} + f32x2{b2, b2};
+                            SigTerms x = sig_terms(n);
+                            if (SP) {
+                                // the positive: softplus(-l) and -sigmoid(-l), formed from -n (not as differences)
+                                const SigTerms y = sig_terms(-n);
+#pragma unroll
+                                for (int k = 0; k < 2; ++k) {
+                                    const int col = j + 2 * h + k;
+                                    const bool pos = col == jp, ok = iok && col < p.n_valid;
+                                    x.sig[k] = ok ? (pos ? -y.sig[k] : x.sig[k]) : 0.f;
+                                    x.lg2[k] = ok ? (pos ? y.lg2[k] : x.lg2[k]) : 0.f;
+                                    x.corr[k] = ok ? (pos ? y.corr[k] : x.corr[k]) : 0.f;
+                                }
+                            }
+                            sl += x.lg2; sc += x.corr; sg += x.sig;
+                            g[h] = x.sig;
+                        }
+                        // tile (mi, 4 ni + wn) of g: row 128 wm + 16 rt + r16, columns 16 ct + 4 lg .. + 3 of its 64
+                        *reinterpret_cast<u32x2*>(gtile + (16 * rt) * 64 + 16 * ct) = u32x2{pack_bf16x2(g[0][0], g[0][1]), pack_bf16x2(g[1][0], g[1][1])};
+                    }
+                    rsp[rt] = reduce_lg(fmaf(sl[0] + sl[1], 0.6931471805599453f, sc[0] + sc[1]));     // over the wave's 64 columns
+                    rsg[rt] = reduce_lg(sg[0] + sg[1]);
+                }
+            };
+            if (special) rows8(std::integral_constant<bool, true>{});
+            else rows8(std::integral_constant<bool, false>{});
+            if (lg == 0) {
+#pragma unroll
+                for (int rt = 0; rt < 8; ++rt) {
+                    lsp[wn * BT + 128 * wm + 16 * rt + r16] = rsp[rt];
+                    lsg[wn * BT + 128 * wm + 16 * rt + r16] = rsg[rt];
+                }
+            }
+            __syncthreads();
+            const int tdx = threadIdx.x & (BT - 1);
+            const float* src = threadIdx.x < BT ? lsp : lsg;
+            (threadIdx.x < BT ? p.sp_part : p.sg_part)[((int64_t)ni * p.m_tiles + mi) * BT + tdx] =
+                (src[tdx] + src[BT + tdx]) + (src[2 * BT + tdx] + src[3 * BT + tdx]);
         } else {
             float scale2 = p.scale2, shift2 = p.shift2;
             if (EPI == EPI_EXP_DT) {
@@ -575,6 +691,43 @@ __global__ __launch_bounds__(256) void nce_slab_sum_kernel(const float* slabs, i
     else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + 4 * id) = s;
 }
 
+// ---- sigmoid loss: the reductions behind EPI_SIG -----------------------------------------------------------------------
+
+// loss_rows[i] = sum over the n tiles of the softplus partials, gsum[i] = the same of the g partials (fixed order: four
+// strided partial sums per row, added in order).  Block = 64 rows x 4 parts; both arrays are [n_tiles][Rp].
+__global__ __launch_bounds__(256) void sig_rows_kernel(const float* sp_part, const float* sg_part, int n_tiles, int64_t Rp, int64_t rows,
+                                                       float* loss_rows, float* gsum) {
+    __shared__ float red[2][4][64];
+    const int e = threadIdx.x & 63, part = threadIdx.x >> 6;
+    const int64_t id = (int64_t)blockIdx.x * 64 + e;            // < Rp (a multiple of 64)
+    float s = 0.f, g = 0.f;
+    for (int t = part; t < n_tiles; t += 4) {
+        s += sp_part[(int64_t)t * Rp + id];
+        g += sg_part[(int64_t)t * Rp + id];
+    }
+    red[0][part][e] = s;
+    red[1][part][e] = g;
+    __syncthreads();
+    if (part == 0) {
+        if (id < rows) loss_rows[id] = (red[0][0][e] + red[0][1][e]) + (red[0][2][e] + red[0][3][e]);
+        gsum[id] = (red[1][0][e] + red[1][1][e]) + (red[1][2][e] + red[1][3][e]);         // 0 in the padding
+    }
+}
+
+// d_bias[0] = sum_i gsum[i]: 256 strided partial sums in order, then a fixed tree (one block)
+__global__ __launch_bounds__(256) void sig_dbias_kernel(const float* gsum, int64_t n, float* d_bias) {
+    __shared__ float red[256];
+    float s = 0.f;
+    for (int64_t k = threadIdx.x; k < n; k += 256) s += gsum[k];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) d_bias[0] = red[0];
+}
+
 template <int AM, int BM, int EPI, int MAP>
 void launch_gemm(const NceGemmArgs& a, unsigned int blocks, hipStream_t s) {
     auto kern = nce_gemm_kernel<AM, BM, EPI, MAP>;
@@ -623,6 +776,34 @@ NceWs carve(void* ws, int64_t rows, int64_t cols, int d) {
     w.v = (float*)take((size_t)Cp * 4);
     w.ediag = (float*)take((size_t)Rp * 4);
     w.c_local = (float*)take((size_t)Cp * 4);
+    w.slabs = (float*)take((size_t)da_splits(Rp, Cp, d) * rows * d * 4);
+    w.bytes = off;
+    return w;
+}
+
+// workspace carve of the sigmoid loss
+struct SigWs {
+    unsigned short* g;                  // [Rp][Cp] bf16, tiled as E
+    float* sp_part;                     // [n_tiles][Rp]
+    float* sg_part;                     // [n_tiles][Rp]
+    float* gsum;                        // [Rp]
+    float* tdot_part;                   // [splits <= 32][m_tiles][n_tiles_d <= 16]
+    float* slabs;                       // [splits][rows][d]
+    size_t bytes;
+};
+
+SigWs sig_carve(void* ws, int64_t rows, int64_t cols, int d) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t mt = Rp / BT, nt = Cp / BT;
+    SigWs w;
+    char* p = (char*)ws;
+    size_t off = 0;
+    auto take = [&](size_t n) { char* r = p + off; off += al256(n); return r; };
+    w.g = (unsigned short*)take((size_t)Rp * Cp * 2);
+    w.sp_part = (float*)take((size_t)nt * Rp * 4);
+    w.sg_part = (float*)take((size_t)nt * Rp * 4);
+    w.gsum = (float*)take((size_t)Rp * 4);
+    w.tdot_part = (float*)take((size_t)32 * 16 * mt * 4);
     w.slabs = (float*)take((size_t)da_splits(Rp, Cp, d) * rows * d * 4);
     w.bytes = off;
     return w;
@@ -738,6 +919,81 @@ void launch_nce_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d
         g.out = db; g.ldo = d; g.slab_stride = 0; g.out_bf16 = out_bf16;
         const unsigned int units = (unsigned)g.m_tiles;
         launch_gemm<OP_COLB, OP_COL, EPI_OUT, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
+    }
+}
+
+// ---- sigmoid (SigLIP) loss on the same GEMMs ---------------------------------------------------------------------------
+
+bool sig_gemm_supported(int dtype, int d) { return dtype == 0 && d % 64 == 0 && d >= 64 && d <= 4096; }
+
+size_t sig_gemm_workspace_bytes(int64_t rows, int64_t cols, int d) { return sig_carve(nullptr, rows, cols, d).bytes + 256; }
+
+// logits pass: g (workspace), loss_rows[i] = sum_j softplus(-y_ij l_ij), d_bias[0] = sum_ij g_ij
+void launch_sig_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const float* temp, float min_temp, const float* bias,
+                           const void* a, const void* b, void* workspace, float* loss_rows, float* d_bias, hipStream_t s) {
+    const SigWs w = sig_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    NceGemmArgs g = {};
+    g.a = (const char*)a; g.b = (const char*)b; g.lda = g.ldb = 2u * (unsigned)d;
+    g.a_sm = (int64_t)BT * g.lda; g.a_st = 128;
+    g.a_rows = (int)rows; g.b_rows = (int)cols;
+    g.m_tiles = (int)(Rp / BT); g.n_tiles = (int)(Cp / BT); g.k_steps = d / 64;
+    g.splits = 1; g.steps_per_split = g.k_steps;
+    g.m_valid = (int)rows; g.n_valid = (int)cols;
+    g.e = w.g; g.e_tiles = Cp / 64;
+    g.temp = temp; g.min_temp = min_temp; g.bias = bias; g.row_offset = row_offset;
+    g.sp_part = w.sp_part; g.sg_part = w.sg_part;
+    const unsigned int nsm = (g.m_tiles + 3) / 4, nsn = (g.n_tiles + 7) / 8;
+    launch_gemm<OP_ROW, OP_ROW, EPI_SIG, MAP_2D>(g, ((nsm * nsn + 7) / 8) * 8 * 32, s);
+    sig_rows_kernel<<<dim3((unsigned)(Rp / 64)), dim3(256), 0, s>>>(w.sp_part, w.sg_part, g.n_tiles, Rp, rows, loss_rows, w.gsum);
+    sig_dbias_kernel<<<dim3(1), dim3(256), 0, s>>>(w.gsum, rows, d_bias);
+}
+
+// da = (coef / Tc upstream) g b, db = (coef / Tc upstream) g^T a over the g launch_sig_gemm_pass1 left (read, not modified);
+// dt.d_t (when wanted) from the float32 da as in launch_nce_gemm_grads
+void launch_sig_gemm_grads(int64_t rows, int64_t cols, int d, const NceDevTemp& dt, float coef, const void* a, const void* b,
+                           void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s) {
+    const SigWs w = sig_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int n_tiles_d = (d + BT - 1) / BT;
+    {   // da: m = local rows, n = d, K = keys
+        NceGemmArgs g = {};
+        g.a = (const char*)w.g; g.lda = 128; g.a_rows = (int)Rp;
+        g.a_sm = (Cp / 64) * (int64_t)32768; g.a_st = 32768;
+        g.b = (const char*)b; g.ldb = 2u * (unsigned)d; g.b_rows = (int)cols; g.b_cbytes = 2 * d;
+        g.m_tiles = (int)(Rp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Cp / 64);
+        g.splits = da_splits(Rp, Cp, d);
+        g.steps_per_split = (g.k_steps + g.splits - 1) / g.splits;
+        g.m_valid = (int)rows; g.n_valid = d;
+        g.out = g.splits > 1 ? (void*)w.slabs : da; g.ldo = d; g.slab_stride = rows * (int64_t)d;
+        g.out_bf16 = g.splits > 1 ? 0 : out_bf16;
+        g.temp = dt.t; g.min_temp = dt.min_t; g.coef = coef; g.upstream = upstream;
+        const unsigned int units = (unsigned)(g.m_tiles * g.splits);
+        if (dt.d_t) {
+            g.tdot_src = (const unsigned short*)a; g.tdot_part = w.tdot_part;
+            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_OUT_TD_S, MAP_SPLITX>(g, 8u * g.m_tiles * g.n_tiles, s);
+            else launch_gemm<OP_ROW, OP_COL, EPI_OUT_TD_S, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
+        } else {
+            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_OUT_S, MAP_SPLITX>(g, 8u * g.m_tiles * g.n_tiles, s);
+            else launch_gemm<OP_ROW, OP_COL, EPI_OUT_S, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
+        }
+        if (g.splits > 1) {
+            const int64_t n4 = rows * (int64_t)d / 4;
+            nce_slab_sum_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s>>>(w.slabs, g.splits, n4, g.slab_stride, da, out_bf16);
+        }
+        if (dt.d_t) launch_nce_dtemp(w.tdot_part, (int64_t)g.splits * g.m_tiles * g.n_tiles, 1, dt, s);
+    }
+    {   // db: m = keys, n = d, K = local rows
+        NceGemmArgs g = {};
+        g.a = (const char*)w.g; g.lda = 128; g.a_rows = (int)Rp; g.a_cbytes = 0; g.a_sm = Cp / 64;
+        g.b = (const char*)a; g.ldb = 2u * (unsigned)d; g.b_rows = (int)rows; g.b_cbytes = 2 * d;
+        g.m_tiles = (int)(Cp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Rp / 64);
+        g.splits = 1; g.steps_per_split = g.k_steps;
+        g.m_valid = (int)cols; g.n_valid = d;
+        g.out = db; g.ldo = d; g.slab_stride = 0; g.out_bf16 = out_bf16;
+        g.temp = dt.t; g.min_temp = dt.min_t; g.coef = coef; g.upstream = upstream;
+        const unsigned int units = (unsigned)g.m_tiles;
+        launch_gemm<OP_COLB, OP_COL, EPI_OUT_S, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
     }
 }
 

@@ -18,7 +18,7 @@ from typing import Optional, Union
 import torch
 
 from . import _lib, dp
-from .layer import _DTYPES, _ptr, _require_device, _stream, CurriculumMasking
+from .layer import _DTYPES, _capturing, _ptr, _require_device, _stream, CurriculumMasking
 
 
 def _plus(total: torch.Tensor, term: torch.Tensor) -> torch.Tensor:
@@ -399,15 +399,132 @@ def info_nce(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch
     return scaled + (total - scaled.detach())
 
 
+def _sig_scalar_arg(value, z: torch.Tensor, what: str):
+    """``temperature`` / ``bias`` of ``sigmoid_contrastive``: a Python number -> float; a tensor -> itself, checked like
+    ``_temperature_arg`` (one float32 element on z's device: the kernels read it there)."""
+    if not isinstance(value, torch.Tensor):
+        return float(value)
+    if value.dtype != torch.float32:
+        raise TypeError(f"aecf_amd: a tensor {what} must be float32, got {value.dtype}")
+    if value.numel() != 1:
+        raise ValueError(f"aecf_amd: a tensor {what} must hold one element, got shape {tuple(value.shape)}")
+    if value.device != z.device:
+        raise ValueError(f"aecf_amd: the {what} lives on {value.device}, the embeddings on {z.device}")
+    return value
+
+
+def _sig_args(temperature, bias, z: torch.Tensor, min_temperature):
+    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
+        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
+    return _sig_scalar_arg(temperature, z, "temperature"), _sig_scalar_arg(bias, z, "bias")
+
+
+class _SigmoidContrastive(torch.autograd.Function):
+    """aecf_sig_pass1 / aecf_sig_grads: the pairwise sigmoid loss of local unit-norm rows ``a`` against the gathered rows
+    ``b_all`` (positives at ``row_offset + i``), temperature and bias one-element float32 device tensors.  The forward runs the
+    logits GEMM, whose epilogue leaves g = sigmoid(l) - [positive] in the workspace together with the loss rows and dbias; the
+    backward runs the two gradient products over it, scaled on the device by the gradient that arrives.  Every logit is its own
+    term: NO collective runs between the two passes (the only exchanges are the caller's all-gather and its reduce-scatter).
+    Returns this rank's rows' share of the loss; gradients: da, this rank's share of db_all, dT, dbias."""
+
+    @staticmethod
+    def forward(ctx, a, b_all, temperature, bias, row_offset, coef, min_temperature):
+        lib = _lib.load()
+        rows, d = a.shape
+        cols = b_all.shape[0]
+        dev = a.device
+        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws_bytes = lib.aecf_sig_workspace_bytes(rows, cols, d)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        loss_rows, d_bias = torch.empty(rows, **f32), torch.empty(1, **f32)
+        t = temperature.detach()
+        _lib.check(lib.aecf_sig_pass1(rows, cols, row_offset, d, _ptr(t), float(min_temperature), _ptr(bias.detach()), _ptr(ac),
+                                      _ptr(bc), _ptr(ws), ws_bytes, _ptr(loss_rows), _ptr(d_bias), _stream()), "aecf_sig_pass1")
+        ctx.save_for_backward(ac, bc, ws, t, d_bias)
+        ctx.meta = (a.dtype, b_all.dtype, temperature.shape, bias.shape,
+                    (rows, cols, int(row_offset), d, float(coef), float(min_temperature), ws_bytes))
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = _lib.load()
+        ac, bc, ws, t, d_bias = ctx.saved_tensors
+        ad, bd, t_shape, b_shape, (rows, cols, row_offset, d, coef, t_min, ws_bytes) = ctx.meta
+        gdt = torch.bfloat16 if (ad == torch.bfloat16 and bd == torch.bfloat16) else torch.float32
+        da = torch.empty(rows, d, dtype=gdt, device=ac.device)
+        db = torch.empty(cols, d, dtype=gdt, device=ac.device)
+        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
+        d_t = torch.empty(1, dtype=torch.float32, device=ac.device) if ctx.needs_input_grad[2] else None
+        _lib.check(lib.aecf_sig_grads(rows, cols, row_offset, d, _ptr(t), t_min, coef, _ptr(ac), _ptr(bc), _ptr(ws), ws_bytes,
+                                      _ptr(up), _DTYPES[gdt], _ptr(da), _ptr(db), _ptr(d_t), _stream()), "aecf_sig_grads")
+        g_t = d_t.reshape(t_shape) if d_t is not None else None
+        g_b = (d_bias * coef * up).reshape(b_shape) if ctx.needs_input_grad[3] else None
+        return da.to(ad), db.to(bd), g_t, g_b, None, None, None
+
+
+def sigmoid_contrastive(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch.Tensor] = 0.1,
+                        bias: Union[float, torch.Tensor] = -10.0, group=None, min_temperature: float = 1e-3) -> torch.Tensor:
+    """Pairwise sigmoid (SigLIP) loss between the local rows of two views, negatives from every rank of ``group``:
+
+        L = 1 / B_all * sum_ij softplus(-y_ij (na_i . nb_j / max(T, min_temperature) + bias)),  y_ij = +1 on the positives, else -1
+
+    ``za``, ``zb``: [b_local, d] bfloat16 on a ROCm device, d % 64 == 0, any row count (the same on every rank).  Every logit is
+    its own binary term, so nothing is normalised over rows, columns or ranks: the forward issues ONE all-gather (the rows of
+    view b) and one scalar all-reduce (the returned value), and no collective runs between the logits pass and the gradient
+    products.  ``temperature`` and ``bias``: a Python float, or a learnable one -- a one-element float32 tensor on za's device
+    (e.g. ``1 / logit_scale.exp()``).  Both are read by the kernels on the device (a float is filled into a one-element tensor;
+    no host read anywhere, so a captured step replays the values the tensors hold then) and both get their gradient from the
+    same kernels (dT is zero where ``T < min_temperature``; any positive ``min_temperature`` is legal).
+
+    Data-parallel convention: ``info_nce``'s -- the returned value is the global loss on every rank, the local term carries
+    ``world`` so that an averaging gradient reduce leaves the one-rank gradient on the replicated parameters, T and bias
+    included."""
+    _require_device(za, "za")
+    _require_device(zb, "zb")
+    if za.shape != zb.shape or za.dim() != 2:
+        raise ValueError(f"sigmoid_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+    t, b = _sig_args(temperature, bias, za, min_temperature)
+    rank, world = dp.world_info(group)
+    rows, d = za.shape
+    cols = rows * world
+    need = _lib.load().aecf_sig_workspace_bytes(rows, cols, d) if za.dtype == torch.bfloat16 and zb.dtype == torch.bfloat16 else 0
+    if need == 0 or (not _capturing() and need > 0.6 * torch.cuda.mem_get_info(za.device)[0]):
+        raise NotImplementedError("aecf_amd: the sigmoid contrastive loss needs bfloat16 rows with d % 64 == 0 and a workspace "
+                                  f"(b_local x b_all bfloat16, {need} bytes here) within 0.6 of the free device memory; got "
+                                  f"{za.dtype}, d = {d}")
+    if not isinstance(t, torch.Tensor):
+        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    if not isinstance(b, torch.Tensor):
+        b = torch.full((1,), b, dtype=torch.float32, device=za.device)
+    na, nb = l2_normalize(za), l2_normalize(zb)
+    nb_all = dp.all_gather_rows(nb, group, sizes=[rows] * world) if world > 1 else nb
+    share = _SigmoidContrastive.apply(na, nb_all, t, b, rank * rows, 1.0 / float(cols), float(min_temperature))
+    if world == 1:
+        return share
+    total = share.detach().clone()
+    torch.distributed.all_reduce(total, group=group)
+    scaled = share * world
+    return scaled + (total - scaled.detach())
+
+
 def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMasking], entropy: Optional[torch.Tensor],
                      za: Optional[torch.Tensor] = None, zb: Optional[torch.Tensor] = None, entropy_weight: float = 0.01,
                      contrastive_weight: float = 1.0, temperature: Union[float, torch.Tensor] = 0.07, group=None,
-                     min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
+                     min_temperature: float = MIN_TEMPERATURE, contrastive: str = "info_nce",
+                     bias: Union[None, float, torch.Tensor] = None) -> torch.Tensor:
     """task + entropy_weight * entropy_loss(entropy) [ref README.md:205-208] + contrastive_weight * info_nce(za, zb)
-    (``temperature`` / ``min_temperature``: as for ``info_nce``)."""
+    (``temperature`` / ``min_temperature``: as for ``info_nce``).  ``contrastive="sigmoid"`` takes ``sigmoid_contrastive(za, zb,
+    temperature, bias)`` as the contrastive term instead (``bias``: None = its default of -10)."""
+    if contrastive not in ("info_nce", "sigmoid"):
+        raise ValueError(f"aecf_amd: contrastive must be 'info_nce' or 'sigmoid', got {contrastive!r}")
     total = task_loss
     if masking is not None and entropy is not None:
         total = _plus(total, entropy_weight * masking.entropy_loss(entropy))
     if za is not None and zb is not None:
-        total = _plus(total, contrastive_weight * info_nce(za, zb, temperature, group, min_temperature))
+        if contrastive == "sigmoid":
+            term = sigmoid_contrastive(za, zb, temperature, -10.0 if bias is None else bias, group, min_temperature)
+        else:
+            term = info_nce(za, zb, temperature, group, min_temperature)
+        total = _plus(total, contrastive_weight * term)
     return total

@@ -561,6 +561,41 @@ int aecf_nce_sym_grads_dt(int64_t rows, int64_t cols, int64_t row_offset, int32_
                           size_t workspace_bytes, const float* upstream, int32_t grad_dtype, void* da, void* db,
                           float* d_temperature, void* stream);
 
+/* ---- sigmoid contrastive loss (SigLIP; build-defined like the InfoNCE term: the reference has no contrastive term) ----
+ * Local rows a [rows,d] (global indices row_offset .. row_offset + rows) against all gathered rows b [cols,d] of the other view,
+ * unit-norm bf16 rows, d % 64 == 0, any row and column counts (rows <= cols).  The temperature and the bias are DEVICE float32
+ * scalars (learnable; nothing is read on the host, so the calls capture into a graph):
+ *   Tc    = max(*temperature, min_temperature)            (any min_temperature > 0: no exponent shift, no 0.025 floor)
+ *   l_ij  = (a_i . b_j) / Tc + *bias
+ *   L     = coef * sum_ij softplus(-y_ij l_ij)            y_ij = +1 if j == row_offset + i else -1,  coef = 1 / cols
+ *   g_ij  = sigmoid(l_ij) - [j == row_offset + i]         (the positive's entry is formed as -sigmoid(-l))
+ *   da    = coef/Tc * upstream * g b        db = coef/Tc * upstream * g^T a        dbias = coef * sum_ij g_ij
+ *   dT    = -(1/Tc) sum_i a_i . da_i   (0 where *temperature < min_temperature)
+ * Every logit is its own binary term: no row or column normaliser, nothing to exchange between the two calls.
+ *   pass1: the logits GEMM with g written ONCE as bf16 into the workspace by its epilogue (softplus as max(x, 0) +
+ *          log1p(exp(-|x|)) in exact-residual form; padded rows and columns are stored as 0 and enter no sum);
+ *          loss_rows[i] = sum_j softplus(-y_ij l_ij)  (float32 [rows]) and d_bias[0] = sum_ij g_ij  -- both WITHOUT coef:
+ *          pass1 does not take it; the caller multiplies (d_bias is this rank's share at upstream 1, from the float32 g before
+ *          its rounding).
+ *   grads: da [rows,d] and this rank's share of db [cols,d] (the sum over ranks is the caller's reduce-scatter), float32 or --
+ *          one rounding of the float32 sums -- bf16 (grad_dtype).  g is stored unscaled; coef / Tc and upstream[0] (`upstream`:
+ *          a DEVICE float32 scalar, NULL = 1) are applied to the float32 sums in the output stage of the two products.
+ *          d_temperature (may be NULL = not wanted) is this rank's share of dL/dT times upstream[0].  The workspace is only
+ *          read: grads may run any number of times after one pass1, with T unchanged in between.
+ * d_bias and d_temperature are WRITTEN, not accumulated; all sums are reduced in a fixed order from float32 partials (no float
+ * atomics: the same inputs give the same bits).  Caller-owned buffers, a stream argument, no allocation, no synchronisation.
+ * Checks before any launch: sizes, then dtype / shape support (d % 64 != 0, a grad_dtype other than bf16 / float32:
+ * AECF_ERR_UNSUPPORTED), then NULL pointers, then the workspace size.  6 rows cols d MFMA flops.
+ * Workspace: rows x cols bf16 + O((rows + cols) (cols / 256 + d)) floats; aecf_sig_workspace_bytes answers 0 where the
+ * shape is not served. */
+size_t aecf_sig_workspace_bytes(int64_t rows, int64_t cols, int32_t d);
+int aecf_sig_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                   const float* bias, const void* a, const void* b, void* workspace, size_t workspace_bytes,
+                   float* loss_rows, float* d_bias, void* stream);
+int aecf_sig_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                   float coef, const void* a, const void* b, void* workspace, size_t workspace_bytes, const float* upstream,
+                   int32_t grad_dtype, void* da, void* db, float* d_temperature, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
