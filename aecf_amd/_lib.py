@@ -187,6 +187,10 @@ _SYMBOLS = [
     ("aecf_sig_grads", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
       c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("aecf_sig_stream_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
+    ("aecf_sig_stream_fwd_bwd", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 

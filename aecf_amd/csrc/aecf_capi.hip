@@ -907,6 +907,27 @@ int aecf_sig_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, co
     return launch_status();
 }
 
+size_t aecf_sig_stream_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !sig_flash_supported(d)) return 0;
+    return sig_flash_workspace_bytes(rows, cols, d);
+}
+
+int aecf_sig_stream_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                            float min_temperature, const float* bias, float coef, const void* a, const void* b, float* loss_rows,
+                            float* d_bias, float* d_temperature, float* da, float* db, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!sig_flash_supported(d)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !bias || !a || !b || !loss_rows || !workspace || (da == nullptr) != (db == nullptr))
+        return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < sig_flash_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, da ? d_temperature : nullptr};
+    launch_sig_flash(rows, cols, row_offset, d, dt, bias, coef, a, b, loss_rows, da ? d_bias : nullptr, da, db, workspace,
+                     (hipStream_t)stream);
+    return launch_status();
+}
+
 int aecf_route_build(int64_t rows, const uint8_t* present_a, const uint8_t* present_b, int32_t* route, int32_t* slot,
                      int32_t* index, int32_t* counts, void* stream) {
     if (rows <= 0 || rows > 0x7fffffff) return AECF_ERR_BAD_DIMS;

@@ -282,6 +282,15 @@ void launch_sig_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d
 void launch_sig_gemm_grads(int64_t rows, int64_t cols, int d, const NceDevTemp& dt, float coef, const void* a, const void* b,
                            void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s);
 
+// The same loss without the [rows, cols] block (aecf_sig_flash.hip): both roles stream the other matrix through LDS, workspace
+// O(rows d).  Writes loss_rows; with da / db (both or neither) also the gradients at upstream 1, d_bias[0] = sum_ij g_ij and
+// dt.d_t (each NULL = not wanted).
+bool sig_flash_supported(int d);
+size_t sig_flash_workspace_bytes(int64_t rows, int64_t cols, int d);
+void launch_sig_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const float* bias, float coef,
+                      const void* a, const void* b, float* loss_rows, float* d_bias, float* da, float* db, void* workspace,
+                      hipStream_t s);
+
 // ---------------- presence routing (aecf_route.hip) ----------------
 void launch_route_build(int64_t rows, const uint8_t* pa, const uint8_t* pb, int32_t* route, int32_t* slot, int32_t* index,
                         int32_t* counts, hipStream_t s);

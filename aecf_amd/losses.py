@@ -463,8 +463,53 @@ class _SigmoidContrastive(torch.autograd.Function):
         return da.to(ad), db.to(bd), g_t, g_b, None, None, None
 
 
+SIG_STREAM_WIDTHS = (128, 256, 384, 512, 768, 1024)     # the widths aecf_sig_stream_workspace_bytes answers for
+
+
+class _SigmoidStream(torch.autograd.Function):
+    """aecf_sig_stream_fwd_bwd: the same share of the loss as ``_SigmoidContrastive`` without the b_local x b_all block, modelled
+    on ``_NceDirection``: the forward makes the one call with gradients at upstream 1 and saves them (float32), the backward
+    multiplies them by the gradient that arrives, on the device.  Where no input requires a gradient or grad mode is off the
+    forward takes the call's loss-only mode (``grads`` False, decided by the caller: grad mode is off inside a forward; the same
+    loss bits).  No collective anywhere."""
+
+    @staticmethod
+    def forward(ctx, a, b_all, temperature, bias, row_offset, coef, min_temperature, grads):
+        lib = _lib.load()
+        rows, d = a.shape
+        cols = b_all.shape[0]
+        dev = a.device
+        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws_bytes = lib.aecf_sig_stream_workspace_bytes(rows, cols, d)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        loss_rows = torch.empty(rows, **f32)
+        da = db = d_bias = d_t = None
+        if grads:
+            da, db = torch.empty(rows, d, **f32), torch.empty(cols, d, **f32)
+            d_bias = torch.empty(1, **f32) if ctx.needs_input_grad[3] else None
+            d_t = torch.empty(1, **f32) if ctx.needs_input_grad[2] else None
+        _lib.check(lib.aecf_sig_stream_fwd_bwd(rows, cols, row_offset, d, _ptr(temperature.detach()), float(min_temperature),
+                                               _ptr(bias.detach()), float(coef), _ptr(ac), _ptr(bc), _ptr(loss_rows), _ptr(d_bias),
+                                               _ptr(d_t), _ptr(da), _ptr(db), _ptr(ws), ws_bytes, _stream()),
+                   "aecf_sig_stream_fwd_bwd")
+        ctx.save_for_backward(da, db, d_t, d_bias)
+        ctx.meta = (a.dtype, b_all.dtype, temperature.shape, bias.shape, float(coef))
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        da, db, d_t, d_bias = ctx.saved_tensors
+        ad, bd, t_shape, b_shape, coef = ctx.meta
+        g = d_loss.detach().to(torch.float32)
+        g_t = (d_t * g).reshape(t_shape) if d_t is not None else None
+        g_b = (d_bias * coef * g).reshape(b_shape) if d_bias is not None else None
+        return (da * g).to(ad), (db * g).to(bd), g_t, g_b, None, None, None, None
+
+
 def sigmoid_contrastive(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch.Tensor] = 0.1,
-                        bias: Union[float, torch.Tensor] = -10.0, group=None, min_temperature: float = 1e-3) -> torch.Tensor:
+                        bias: Union[float, torch.Tensor] = -10.0, group=None, min_temperature: float = 1e-3,
+                        low_memory: Optional[bool] = None) -> torch.Tensor:
     """Pairwise sigmoid (SigLIP) loss between the local rows of two views, negatives from every rank of ``group``:
 
         L = 1 / B_all * sum_ij softplus(-y_ij (na_i . nb_j / max(T, min_temperature) + bias)),  y_ij = +1 on the positives, else -1
@@ -477,6 +522,12 @@ def sigmoid_contrastive(za: torch.Tensor, zb: torch.Tensor, temperature: Union[f
     no host read anywhere, so a captured step replays the values the tensors hold then) and both get their gradient from the
     same kernels (dT is zero where ``T < min_temperature``; any positive ``min_temperature`` is legal).
 
+    ``low_memory``: which of the two implementations runs.  ``False``: the tile-GEMM form, which keeps g = sigmoid(l) -
+    [positive] as a b_local x b_all bfloat16 block between forward and backward (d % 64 == 0, and the block within 0.6 of the
+    free device memory).  ``True``: the streaming form (d in 128, 256, 384, 512, 768, 1024), which never holds that block -- its
+    workspace is O(b_local d) -- at 8/6 or more of the matrix work.  ``None`` (the default): the tile form wherever it runs, else
+    the streaming form.  Ranks may take different forms: nothing is exchanged between the passes of either.
+
     Data-parallel convention: ``info_nce``'s -- the returned value is the global loss on every rank, the local term carries
     ``world`` so that an averaging gradient reduce leaves the one-rank gradient on the replicated parameters, T and bias
     included."""
@@ -488,18 +539,38 @@ def sigmoid_contrastive(za: torch.Tensor, zb: torch.Tensor, temperature: Union[f
     rank, world = dp.world_info(group)
     rows, d = za.shape
     cols = rows * world
-    need = _lib.load().aecf_sig_workspace_bytes(rows, cols, d) if za.dtype == torch.bfloat16 and zb.dtype == torch.bfloat16 else 0
-    if need == 0 or (not _capturing() and need > 0.6 * torch.cuda.mem_get_info(za.device)[0]):
-        raise NotImplementedError("aecf_amd: the sigmoid contrastive loss needs bfloat16 rows with d % 64 == 0 and a workspace "
-                                  f"(b_local x b_all bfloat16, {need} bytes here) within 0.6 of the free device memory; got "
-                                  f"{za.dtype}, d = {d}")
+    bf16 = za.dtype == torch.bfloat16 and zb.dtype == torch.bfloat16
+    stream_need = _lib.load().aecf_sig_stream_workspace_bytes(rows, cols, d) if bf16 and low_memory is not False else 0
+    if low_memory:
+        if stream_need == 0:
+            raise NotImplementedError("aecf_amd: the streaming sigmoid contrastive loss needs bfloat16 rows with d in "
+                                      f"{SIG_STREAM_WIDTHS}; got {za.dtype}, d = {d}")
+        form = _SigmoidStream
+    else:
+        need = _lib.load().aecf_sig_workspace_bytes(rows, cols, d) if bf16 else 0
+        form = _SigmoidContrastive
+        if need == 0 or (not _capturing() and need > 0.6 * torch.cuda.mem_get_info(za.device)[0]):
+            if low_memory is False:
+                raise NotImplementedError("aecf_amd: the sigmoid contrastive loss needs bfloat16 rows with d % 64 == 0 and a "
+                                          f"workspace (b_local x b_all bfloat16, {need} bytes here) within 0.6 of the free device "
+                                          f"memory; got {za.dtype}, d = {d}")
+            if stream_need == 0:
+                raise NotImplementedError("aecf_amd: the sigmoid contrastive loss needs bfloat16 rows and either d % 64 == 0 with a "
+                                          f"workspace (b_local x b_all bfloat16, {need} bytes here) within 0.6 of the free device "
+                                          f"memory (the tile form) or d in {SIG_STREAM_WIDTHS} (the streaming form); got "
+                                          f"{za.dtype}, d = {d}")
+            form = _SigmoidStream
     if not isinstance(t, torch.Tensor):
         t = torch.full((1,), t, dtype=torch.float32, device=za.device)
     if not isinstance(b, torch.Tensor):
         b = torch.full((1,), b, dtype=torch.float32, device=za.device)
     na, nb = l2_normalize(za), l2_normalize(zb)
     nb_all = dp.all_gather_rows(nb, group, sizes=[rows] * world) if world > 1 else nb
-    share = _SigmoidContrastive.apply(na, nb_all, t, b, rank * rows, 1.0 / float(cols), float(min_temperature))
+    if form is _SigmoidStream:
+        grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb_all, t, b))
+        share = form.apply(na, nb_all, t, b, rank * rows, 1.0 / float(cols), float(min_temperature), grads)
+    else:
+        share = form.apply(na, nb_all, t, b, rank * rows, 1.0 / float(cols), float(min_temperature))
     if world == 1:
         return share
     total = share.detach().clone()
@@ -512,10 +583,11 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
                      za: Optional[torch.Tensor] = None, zb: Optional[torch.Tensor] = None, entropy_weight: float = 0.01,
                      contrastive_weight: float = 1.0, temperature: Union[float, torch.Tensor] = 0.07, group=None,
                      min_temperature: float = MIN_TEMPERATURE, contrastive: str = "info_nce",
-                     bias: Union[None, float, torch.Tensor] = None) -> torch.Tensor:
+                     bias: Union[None, float, torch.Tensor] = None, low_memory: Optional[bool] = None) -> torch.Tensor:
     """task + entropy_weight * entropy_loss(entropy) [ref README.md:205-208] + contrastive_weight * info_nce(za, zb)
     (``temperature`` / ``min_temperature``: as for ``info_nce``).  ``contrastive="sigmoid"`` takes ``sigmoid_contrastive(za, zb,
-    temperature, bias)`` as the contrastive term instead (``bias``: None = its default of -10)."""
+    temperature, bias)`` as the contrastive term instead (``bias``: None = its default of -10; ``low_memory``: its choice of
+    implementation, ignored for ``info_nce``)."""
     if contrastive not in ("info_nce", "sigmoid"):
         raise ValueError(f"aecf_amd: contrastive must be 'info_nce' or 'sigmoid', got {contrastive!r}")
     total = task_loss
@@ -523,7 +595,7 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
         total = _plus(total, entropy_weight * masking.entropy_loss(entropy))
     if za is not None and zb is not None:
         if contrastive == "sigmoid":
-            term = sigmoid_contrastive(za, zb, temperature, -10.0 if bias is None else bias, group, min_temperature)
+            term = sigmoid_contrastive(za, zb, temperature, -10.0 if bias is None else bias, group, min_temperature, low_memory)
         else:
             term = info_nce(za, zb, temperature, group, min_temperature)
         total = _plus(total, contrastive_weight * term)

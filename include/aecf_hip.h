@@ -596,6 +596,36 @@ int aecf_sig_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, co
                    float coef, const void* a, const void* b, void* workspace, size_t workspace_bytes, const float* upstream,
                    int32_t grad_dtype, void* da, void* db, float* d_temperature, void* stream);
 
+/* The same loss in ONE call that never holds the rows x cols block: the streaming form, for batches whose g does not fit.  Same
+ * inputs and formulas (bf16 unit-norm rows, device T and bias, Tc = max(*temperature, min_temperature), y_ij = +1 only on
+ * j == row_offset + i), d in {128, 256, 384, 512, 768, 1024}:
+ *   l_ij = (a_i . b_j) / Tc + *bias        g_ij = sigmoid(l_ij) - [j == row_offset + i]
+ *   loss_rows[i] = sum_j softplus(-y_ij l_ij)          float32 [rows], WITHOUT coef
+ *   d_bias[0]    = sum_ij g_ij                         WITHOUT coef, from the float32 g
+ *   da = coef/Tc g b   float32 [rows,d]        db = coef/Tc g^T a   float32 [cols,d] (this rank's share)       at upstream 1
+ *   d_temperature[0] = -(1/Tc) sum_i a_i . da_i        (0 where *temperature < min_temperature)
+ * Two roles of one kernel, each a single independent pass (no maximum, no normaliser, nothing handed from one to the other): da
+ * with the rows of a held in registers and b streamed through LDS, its column range split over blocks and the splits' float32
+ * partials added in a fixed order by a combine launch that also leaves d_bias and d_temperature; db with the rows of b held and
+ * a streamed, no partials.  g is rounded to bf16 only as the operand of the gradient products; every scalar sum takes the
+ * float32 value.  No float atomics: the same inputs give the same bits.  d_bias and d_temperature are WRITTEN, not accumulated,
+ * and may be NULL (= not wanted).
+ * Loss-only mode: da == db == NULL runs the first role without its gradient product and writes loss_rows alone (d_bias and
+ * d_temperature are ignored and may be NULL); loss_rows has the same bits as with gradients.
+ * 8 rows cols d MFMA flops (each role forms the logits: 2 + 2, and 2 + 2 for the products) against the tile form's 6; at
+ * d = 768 and d = 1024 the output columns of each role come from two launches that both form the logits (12 rows cols d).
+ * Workspace, in order: [splits, rows, d] float32 da partials | [splits, rows] softplus sums | [splits, rows] g sums |
+ * [rows] sum_j g_ij | [rows] a_i . da_i; splits <= 64 does not grow with cols beyond that.  aecf_sig_stream_workspace_bytes
+ * answers 0 where the width is not served.  Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing
+ * read on the host.  Checks before any launch: sizes (AECF_ERR_BAD_DIMS), then the width (AECF_ERR_UNSUPPORTED), then NULL among
+ * temperature, bias, a, b, loss_rows, workspace or exactly one of da / db NULL (AECF_ERR_NULL_POINTER), then the workspace
+ * size (AECF_ERR_WORKSPACE). */
+size_t aecf_sig_stream_workspace_bytes(int64_t rows, int64_t cols, int32_t d);      /* 0: width not served */
+int aecf_sig_stream_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                            float min_temperature, const float* bias, float coef, const void* a, const void* b,
+                            float* loss_rows, float* d_bias, float* d_temperature, float* da, float* db,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
