@@ -928,6 +928,37 @@ int aecf_sig_stream_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int3
     return launch_status();
 }
 
+// ---- retrieval ranks of the contrastive views (include/aecf_hip.h, "retrieval ranks")
+
+size_t aecf_retrieval_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || cols > 0x7fffffff || !retrieval_supported(d)) return 0;
+    return retrieval_workspace_bytes(rows, cols, d);
+}
+
+int aecf_retrieval_positive(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const void* a, const void* b, float* pos_row,
+                            void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!retrieval_supported(d)) return AECF_ERR_UNSUPPORTED;
+    if (!a || !b || !pos_row) return AECF_ERR_NULL_POINTER;
+    launch_retrieval_positive(rows, row_offset, d, a, b, pos_row, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_retrieval_ranks(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const void* a, const void* b, const float* pos_row,
+                         const float* pos_col, int32_t* row_greater, int32_t* row_equal, int32_t* col_greater, int32_t* col_equal,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!retrieval_supported(d)) return AECF_ERR_UNSUPPORTED;
+    if (!a || !b || !pos_row || !row_greater || !row_equal || !workspace) return AECF_ERR_NULL_POINTER;
+    if (pos_col && (!col_greater || !col_equal)) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < retrieval_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    launch_retrieval_ranks(rows, cols, row_offset, d, a, b, pos_row, pos_col, row_greater, row_equal, col_greater, col_equal, workspace,
+                           (hipStream_t)stream);
+    return launch_status();
+}
+
 int aecf_route_build(int64_t rows, const uint8_t* present_a, const uint8_t* present_b, int32_t* route, int32_t* slot,
                      int32_t* index, int32_t* counts, void* stream) {
     if (rows <= 0 || rows > 0x7fffffff) return AECF_ERR_BAD_DIMS;

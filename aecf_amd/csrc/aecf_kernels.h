@@ -291,6 +291,18 @@ void launch_sig_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, con
                       const void* a, const void* b, float* loss_rows, float* d_bias, float* da, float* db, void* workspace,
                       hipStream_t s);
 
+// Retrieval ranks of the contrastive views (aecf_retrieval.hip; the counting pass is the EPI_RANK epilogue of the logits GEMM in
+// aecf_nce_gemm.hip): pos[i] = a_i . b_(row_offset + i), then per row / per column how many other logits are greater than / equal
+// to the positive's.  Nothing of size rows x cols exists; the workspace is (rows + cols) x tiles int32 partials.
+bool retrieval_supported(int d);
+size_t retrieval_workspace_bytes(int64_t rows, int64_t cols, int d);
+void launch_retrieval_positive(int64_t rows, int64_t row_offset, int d, const void* a, const void* b, float* pos_row, hipStream_t s);
+void launch_retrieval_ranks(int64_t rows, int64_t cols, int64_t row_offset, int d, const void* a, const void* b, const float* pos_row,
+                            const float* pos_col, int32_t* row_greater, int32_t* row_equal, int32_t* col_greater, int32_t* col_equal,
+                            void* workspace, hipStream_t s);
+void launch_rank_gemm(int64_t rows, int64_t cols, int64_t row_offset, int d, const void* a, const void* b, const float* pos_row,
+                      const float* pos_col, int* row_part, int* col_part, hipStream_t s);
+
 // ---------------- presence routing (aecf_route.hip) ----------------
 void launch_route_build(int64_t rows, const uint8_t* pa, const uint8_t* pb, int32_t* route, int32_t* slot, int32_t* index,
                         int32_t* counts, hipStream_t s);

@@ -35,6 +35,17 @@
 // formed (n = l log2 e comes out of one packed fma on the accumulator), softplus needs no max, no select and no second
 // exponential (sig_terms), the sums are packed adds, and the positive / ragged-edge selects run only in the tiles that hold
 // such elements (a block-uniform branch).
+//
+// Retrieval ranks (aecf_retrieval_ranks, host side in aecf_retrieval.hip) are a fourth epilogue of the logits arrangement,
+// EPI_RANK: nothing of the tile is stored.  Every float32 accumulator s_ij is compared with the threshold of its row
+// (pos_row[i]) and of its column (pos_col[j], NULL = that direction off) and counted: greater and equal, per row over the
+// tile's 256 columns and per column over its 256 rows, the positive (j = off + i) and the padding excluded -- selects that run
+// only in the tiles that hold such elements, as in EPI_SIG.  A comparison with a NaN is false on both sides: such an
+// element is counted nowhere.  How the counts leave the block: per-tile integer partials, greater in the low and equal in
+// the high 16 bits of one int32 (a tile holds at most 256 of either), [n_tiles][Rp] for the rows and [m_tiles][Cp] for the
+// columns, summed by rank_counts_kernel.  Taken over vector atomics onto zeroed outputs because it is the arrangement the
+// row / column sums of the two losses already have (no memset node in front of the launch, no contended atomics on the
+// 256 tiles of a row, plain coalesced stores); integer sums are exact in any order, so either would be deterministic.
 #include <math.h>
 #include <type_traits>
 
@@ -51,7 +62,8 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // float32 accumulator -- to tdot_part[(split m_tiles + mi) n_tiles + ni]
 // EPI_SIG (sigmoid loss, logits pass): g = sigmoid(l) - [positive] as bf16 into the tiled workspace + two per-row partials per
 // n tile; EPI_OUT_S / EPI_OUT_TD_S: EPI_OUT / EPI_OUT_TD with the float32 accumulator multiplied by coef / Tc * upstream first
-enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6 };
+// EPI_RANK (retrieval ranks, logits pass): nothing stored; per-tile counts of acc > / == the row's and the column's threshold
+enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7 };
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -92,6 +104,11 @@ struct NceGemmArgs {
     // EPI_OUT_S / EPI_OUT_TD_S (also read temp / min_temp)
     float coef;
     const float* upstream;              // device scalar, may be NULL (= 1)
+    // EPI_RANK (also reads row_offset)
+    const float* pos_row;               // [m_valid]  threshold of output row i
+    const float* pos_col;               // [n_valid]  threshold of output column j; NULL: no column counts
+    int* rank_row_part;                 // [n_tiles][m_tiles 256]  greater | equal << 16
+    int* rank_col_part;                 // [m_tiles][n_tiles 256]
 };
 
 // sigmoid(x) and the pieces of softplus(x) for x = n ln 2, two elements: u = 2^min(n, 126), t = 1 + u, r = 1 / t;
@@ -473,6 +490,106 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
             const float* src = threadIdx.x < BT ? lsp : lsg;
             (threadIdx.x < BT ? p.sp_part : p.sg_part)[((int64_t)ni * p.m_tiles + mi) * BT + tdx] =
                 (src[tdx] + src[BT + tdx]) + (src[2 * BT + tdx] + src[3 * BT + tdx]);
+        } else if (EPI == EPI_RANK) {
+            // row thresholds first (their latency passes while the other waves arrive); padding re-reads the last one
+            const bool cols_on = p.pos_col != nullptr;                  // block-uniform
+            float pr[8];
+#pragma unroll
+            for (int rt = 0; rt < 8; ++rt) {
+                const int64_t i = gi0 + 16 * rt;
+                pr[rt] = p.pos_row[i < p.m_valid ? i : p.m_valid - 1];
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
+            int* lrow = reinterpret_cast<int*>(smem);           // [4][256] row counts | [2][256] column counts
+            int* lcol = lrow + 4 * BT;
+            // block-uniform: only tiles on the band of positives or on the ragged edge pay for the selects
+            const int64_t p0 = p.row_offset + (int64_t)BT * mi;
+            const bool special = BT * (mi + 1) > p.m_valid || BT * (ni + 1) > p.n_valid ||
+                                 (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
+            // the accumulator of (rt, ct, r); SP: the positive and the padding become a NaN -- one select, and every comparison
+            // with it is false.  The empty asm keeps the value opaque: comparisons that the variants below have in common would
+            // otherwise be hoisted in front of the branch, hundreds of masks at once, and spill.
+            auto elem = [&](auto special_c, int rt, int ct, int r) -> float {
+                constexpr bool SP = decltype(special_c)::value;
+                float sv = acc[rt][ct][r];
+                asm volatile("" : "+v"(sv));
+                if (SP) {
+                    const int64_t i = gi0 + 16 * rt;
+                    const int col = gj0 + 16 * ct + r;
+                    sv = ((i < p.m_valid) & (col < p.n_valid) & (col != p.row_offset + i)) ? sv : __builtin_nanf("");
+                }
+                return sv;
+            };
+            // rows: greater | equal << 16 over the wave's 64 columns (<= 64 in either half), then over the 4 lane groups
+            auto count_rows = [&](auto special_c) {
+#pragma unroll
+                for (int rt = 0; rt < 8; ++rt) {
+                    int rg = 0, re = 0;
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float sv = elem(special_c, rt, ct, r);
+                            rg += (int)(sv > pr[rt]);
+                            re += (int)(sv == pr[rt]);
+                        }
+                    }
+                    int v = rg | (re << 16);
+                    v += __shfl_xor(v, 16, 64);
+                    v += __shfl_xor(v, 32, 64);
+                    if (lg == 0) lrow[wn * BT + 128 * wm + 16 * rt + r16] = v;
+                }
+            };
+            // columns: the same over the wave's 128 rows (<= 128 in either half), then over the 16 lanes of a group
+            auto count_cols = [&](auto special_c) {
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) {
+                    float pc[4];
+                    int cg[4], ce[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int j = gj0 + 16 * ct + r;
+                        pc[r] = p.pos_col[j < p.n_valid ? j : p.n_valid - 1];
+                        cg[r] = ce[r] = 0;
+                    }
+#pragma unroll
+                    for (int rt = 0; rt < 8; ++rt) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float sv = elem(special_c, rt, ct, r);
+                            cg[r] += (int)(sv > pc[r]);
+                            ce[r] += (int)(sv == pc[r]);
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        int v = cg[r] | (ce[r] << 16);
+                        v += __shfl_xor(v, 1, 64);
+                        v += __shfl_xor(v, 2, 64);
+                        v += __shfl_xor(v, 4, 64);
+                        v += __shfl_xor(v, 8, 64);
+                        if (r16 == 0) lcol[wm * BT + 64 * wn + 16 * ct + 4 * lg + r] = v;
+                    }
+                }
+            };
+            using T_ = std::integral_constant<bool, true>;
+            using F_ = std::integral_constant<bool, false>;
+            if (special) {
+                count_rows(T_{});
+                if (cols_on) count_cols(T_{});
+            } else {
+                count_rows(F_{});
+                if (cols_on) count_cols(F_{});
+            }
+            __syncthreads();
+            const int tdx = threadIdx.x;
+            if (tdx < BT) {
+                p.rank_row_part[((int64_t)ni * p.m_tiles + mi) * BT + tdx] = (lrow[tdx] + lrow[BT + tdx]) + (lrow[2 * BT + tdx] + lrow[3 * BT + tdx]);
+            } else if (cols_on) {
+                const int c = tdx - BT;
+                p.rank_col_part[((int64_t)mi * p.n_tiles + ni) * BT + c] = lcol[c] + lcol[BT + c];
+            }
         } else {
             float scale2 = p.scale2, shift2 = p.shift2;
             if (EPI == EPI_EXP_DT) {
@@ -995,6 +1112,26 @@ void launch_sig_gemm_grads(int64_t rows, int64_t cols, int d, const NceDevTemp& 
         const unsigned int units = (unsigned)g.m_tiles;
         launch_gemm<OP_COLB, OP_COL, EPI_OUT_S, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
     }
+}
+
+// ---- retrieval ranks: the counting pass (thresholds, reduction and checks in aecf_retrieval.hip) -------------------------
+
+// per-tile packed counts of a [rows, d] . b [cols, d]^T against pos_row / pos_col (NULL: rows only) into row_part [n_tiles][Rp] and
+// col_part [m_tiles][Cp] (Rp, Cp: rows, cols rounded up to 256)
+void launch_rank_gemm(int64_t rows, int64_t cols, int64_t row_offset, int d, const void* a, const void* b, const float* pos_row,
+                      const float* pos_col, int* row_part, int* col_part, hipStream_t s) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    NceGemmArgs g = {};
+    g.a = (const char*)a; g.b = (const char*)b; g.lda = g.ldb = 2u * (unsigned)d;
+    g.a_sm = (int64_t)BT * g.lda; g.a_st = 128;
+    g.a_rows = (int)rows; g.b_rows = (int)cols;
+    g.m_tiles = (int)(Rp / BT); g.n_tiles = (int)(Cp / BT); g.k_steps = d / 64;
+    g.splits = 1; g.steps_per_split = g.k_steps;
+    g.m_valid = (int)rows; g.n_valid = (int)cols;
+    g.row_offset = row_offset;
+    g.pos_row = pos_row; g.pos_col = pos_col; g.rank_row_part = row_part; g.rank_col_part = col_part;
+    const unsigned int nsm = (g.m_tiles + 3) / 4, nsn = (g.n_tiles + 7) / 8;
+    launch_gemm<OP_ROW, OP_ROW, EPI_RANK, MAP_2D>(g, ((nsm * nsn + 7) / 8) * 8 * 32, s);
 }
 
 }  // namespace aecf

@@ -13,7 +13,7 @@ the exchange steps are ``dp.all_gather_rows`` (forward) and its reduce-scatter (
 """
 from __future__ import annotations
 
-from typing import Optional, Union
+from typing import NamedTuple, Optional, Sequence, Union
 
 import torch
 
@@ -577,6 +577,102 @@ def sigmoid_contrastive(za: torch.Tensor, zb: torch.Tensor, temperature: Union[f
     torch.distributed.all_reduce(total, group=group)
     scaled = share * world
     return scaled + (total - scaled.detach())
+
+
+class RetrievalRanks(NamedTuple):
+    """What ``retrieval_ranks`` returns: for each of this rank's rows, how many OTHER rows of the other view score higher than
+    (``greater``) or exactly as high as (``equal``) its partner; int32 [b_local] each."""
+    a2b_greater: torch.Tensor
+    a2b_equal: torch.Tensor
+    b2a_greater: torch.Tensor
+    b2a_equal: torch.Tensor
+
+
+_TIES = {"optimistic": 0.0, "average": 0.5, "pessimistic": 1.0}
+
+
+def retrieval_ranks(za: torch.Tensor, zb: torch.Tensor, group=None, normalize: bool = True) -> RetrievalRanks:
+    """Retrieval ranks of the contrastive views, both directions from ONE logits pass that stores nothing of size
+    b_local x b_all (aecf_retrieval_positive / aecf_retrieval_ranks).  ``za``, ``zb``: [b_local, d] bfloat16 on a ROCm device,
+    d % 64 == 0, 64 <= d <= 4096, the same row count on every rank; row i of one view is the partner of row i of the other.
+
+    With s_ij = a_i . b_j (float32 accumulation) over the rows of view b from every rank of ``group``, the call returns, for
+    this rank's rows, ``a2b_greater[i] = #{j != i : s_ij > s_ii}`` and ``a2b_equal`` (the same with ==), and for its rows of
+    view b against the rows of view a from every rank ``b2a_greater`` / ``b2a_equal``.  A positive's rank under a tie rule f is
+    ``greater + f * equal``.  A comparison with a NaN is false on both sides.
+
+    ``normalize=True`` brings the rows to unit norm with the library's kernel first; ``False`` takes them as given.  Nothing
+    is rounded to bfloat16 on the way in -- a ranking is the one output where that would change answers -- so other dtypes are
+    refused.  Runs without a graph (inputs detached, outputs carry none) and without a host read: it captures on one rank.
+    Data parallel: one all-gather of the rows of view b, one of the b_local positive logits, one all-reduce of the b_all int32
+    column counts."""
+    _require_device(za, "za")
+    _require_device(zb, "zb")
+    if za.shape != zb.shape or za.dim() != 2:
+        raise ValueError(f"retrieval_ranks expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+    if za.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16:
+        raise NotImplementedError(f"aecf_amd: retrieval_ranks takes bfloat16 rows only (nothing is rounded on the way in); got "
+                                  f"{za.dtype} and {zb.dtype}")
+    rows, d = za.shape
+    if d % 64 != 0 or not 64 <= d <= 4096:
+        raise NotImplementedError(f"aecf_amd: retrieval_ranks needs d % 64 == 0 and 64 <= d <= 4096, got d = {d}")
+    lib = _lib.load()
+    rank, world = dp.world_info(group)
+    cols, offset = rows * world, rank * rows
+    ws_bytes = lib.aecf_retrieval_workspace_bytes(rows, cols, d)
+    if ws_bytes == 0:
+        raise NotImplementedError(f"aecf_amd: retrieval_ranks does not serve {rows} x {cols} x {d}")
+    with torch.no_grad():
+        a, b = za.detach(), zb.detach()
+        if normalize:
+            a, b = l2_normalize(a), l2_normalize(b)
+        a, b = a.contiguous(), b.contiguous()
+        b_all = dp.all_gather_rows(b, group, sizes=[rows] * world).contiguous() if world > 1 else b
+        dev = za.device
+        pos = torch.empty(rows, dtype=torch.float32, device=dev)
+        _lib.check(lib.aecf_retrieval_positive(rows, cols, offset, d, _ptr(a), _ptr(b_all), _ptr(pos), _stream()),
+                   "aecf_retrieval_positive")
+        pos_all = dp.all_gather_rows(pos, group, sizes=[rows] * world).contiguous() if world > 1 else pos
+        i32 = dict(dtype=torch.int32, device=dev)
+        row_g, row_e = torch.empty(rows, **i32), torch.empty(rows, **i32)
+        col = torch.empty(2, cols, **i32)                    # greater | equal: one all-reduce
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.aecf_retrieval_ranks(rows, cols, offset, d, _ptr(a), _ptr(b_all), _ptr(pos), _ptr(pos_all), _ptr(row_g),
+                                            _ptr(row_e), _ptr(col[0]), _ptr(col[1]), _ptr(ws), ws_bytes, _stream()),
+                   "aecf_retrieval_ranks")
+        if world > 1:
+            torch.distributed.all_reduce(col, group=group)
+        return RetrievalRanks(row_g, row_e, col[0, offset:offset + rows], col[1, offset:offset + rows])
+
+
+def retrieval_metrics(za: torch.Tensor, zb: torch.Tensor, ks: Sequence[int] = (1, 5, 10), group=None, ties: str = "average",
+                      normalize: bool = True) -> dict:
+    """Recall@k, mean reciprocal rank and mean rank of both retrieval directions, global over ``group``, from
+    ``retrieval_ranks``.  The 0-based rank of a positive is ``greater + f * equal`` with f = 0 (``ties="optimistic"``), 0.5
+    (``"average"``) or 1 (``"pessimistic"``).  Returns 0-dim float32 device tensors: ``a2b_R@k`` / ``b2a_R@k`` for every k in
+    ``ks`` (the share of rows with rank < k), ``a2b_mrr`` / ``b2a_mrr`` (mean of 1 / (rank + 1)) and ``a2b_mean_rank`` /
+    ``b2a_mean_rank``.  The means over this rank's rows are torch reductions; the ranks exchange one all-reduce of one small
+    vector.  No host read."""
+    if ties not in _TIES:
+        raise ValueError(f"aecf_amd: ties must be one of {sorted(_TIES)}, got {ties!r}")
+    ks = tuple(ks)
+    if not ks or any(isinstance(k, bool) or not isinstance(k, int) or k <= 0 for k in ks):
+        raise ValueError(f"aecf_amd: ks must be positive integers, got {ks!r}")
+    r = retrieval_ranks(za, zb, group, normalize)
+    f = _TIES[ties]
+    world = dp.world_info(group)[1]
+    with torch.no_grad():
+        sums = []
+        for g, e in ((r.a2b_greater, r.a2b_equal), (r.b2a_greater, r.b2a_equal)):
+            # float64 sums: every term is exact there, so the value does not depend on how the rows are dealt over ranks
+            rank = g.to(torch.float64) + f * e.to(torch.float64)
+            sums += [(rank < k).to(torch.float64).sum() for k in ks] + [(1.0 / (rank + 1.0)).sum(), rank.sum()]
+        vec = torch.stack(sums)
+        if world > 1:
+            torch.distributed.all_reduce(vec, group=group)
+        vec = (vec / float(za.shape[0] * world)).to(torch.float32)
+    names = [f"R@{k}" for k in ks] + ["mrr", "mean_rank"]
+    return {f"{side}_{n}": vec[i * len(names) + j] for i, side in enumerate(("a2b", "b2a")) for j, n in enumerate(names)}
 
 
 def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMasking], entropy: Optional[torch.Tensor],

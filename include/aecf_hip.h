@@ -626,6 +626,34 @@ int aecf_sig_stream_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int3
                             float* loss_rows, float* d_bias, float* d_temperature, float* da, float* db,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- retrieval ranks of the contrastive views (build-defined like the contrastive terms they evaluate: the reference has no
+ * contrastive term and no retrieval evaluation, so there are no reference lines to cite) ----
+ * Local rows a [rows,d] (global indices row_offset .. row_offset + rows) against all gathered rows b [cols,d] of the other view,
+ * bf16, d % 64 == 0, 64 <= d <= 4096, any row and column counts with row_offset + rows <= cols.  The rows are taken as given
+ * (unit norm or not).  With s_ij = a_i . b_j accumulated in float32, the positive of row i is column row_offset + i:
+ *   positive:  pos_row[i]     = s_(i, row_offset + i)                                                  float32 [rows]
+ *   ranks:     row_greater[i] = #{ j < cols, j != row_offset + i : s_ij >  pos_row[i] }                int32 [rows]
+ *              row_equal[i]   = #{ j < cols, j != row_offset + i : s_ij == pos_row[i] }
+ *              col_greater[j] = #{ i < rows, i != j - row_offset : s_ij >  pos_col[j] }                int32 [cols]
+ *              col_equal[j]   = #{ i < rows, i != j - row_offset : s_ij == pos_col[j] }
+ * pos_col [cols] holds every column's threshold (the positives of all ranks, gathered by the caller); col_* are THIS rank's
+ * share over its rows, for every column: the caller sums the ranks' shares.  pos_col == NULL switches the column direction
+ * off (col_greater / col_equal are then not touched and may be NULL).  The rank of a positive is greater + f * equal with the
+ * caller's tie rule f.  A comparison with a NaN is false on both sides: a NaN logit or threshold is counted nowhere.
+ * One logits pass (2 rows cols d MFMA flops) whose epilogue compares and counts; nothing of size rows x cols is stored.
+ * Workspace: (rows + cols) * tiles int32 partials, O((rows + cols) cols / 256) in all; aecf_retrieval_workspace_bytes answers 0
+ * where the shape is not served.  Outputs are WRITTEN, not accumulated; integer sums: the same inputs give the same counts.
+ * Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host.  Checks before any
+ * launch: sizes and row_offset + rows <= cols (AECF_ERR_BAD_DIMS), then the width (AECF_ERR_UNSUPPORTED), then NULL pointers
+ * (AECF_ERR_NULL_POINTER), then the workspace size (AECF_ERR_WORKSPACE). */
+size_t aecf_retrieval_workspace_bytes(int64_t rows, int64_t cols, int32_t d);      /* 0: shape not served */
+int aecf_retrieval_positive(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const void* a, const void* b,
+                            float* pos_row, void* stream);
+int aecf_retrieval_ranks(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const void* a, const void* b,
+                         const float* pos_row, const float* pos_col /* [cols] or NULL */, int32_t* row_greater,
+                         int32_t* row_equal, int32_t* col_greater, int32_t* col_equal, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
