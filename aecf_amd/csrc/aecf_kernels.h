@@ -214,6 +214,28 @@ void launch_entropy_partials(int dtype, int64_t n, float target, const void* ent
 void launch_entropy_from_partials(int dtype, int64_t n, const float* partial, void* loss, hipStream_t s);
 void launch_entropy_loss(int dtype, int64_t n, float target, const void* entropy, float upstream, void* loss,
                          float* d_entropy, float* partial, hipStream_t s);
+__device__ __forceinline__ float nan_to_num_ref(float e) {   // nan=0, +inf=1, -inf=0 (ref :296)
+    if (e != e) return 0.f;
+    if (isinf(e)) return e > 0.f ? 1.f : 0.f;
+    return e;
+}
+// the same regulariser riding in ONE 256-thread block of another launch (the InfoNCE combine / finalize kernels): loss[0] =
+// max(mean((nan_to_num(H) - target)^2), 0), d_ent[j] = scale (H_j - target) (0 where H_j is not finite; d_ent may be NULL);
+// fixed order: 256 strided sums, a wave reduction, the four waves added in order
+__device__ __forceinline__ void entropy_rider(const float* ent, int64_t n_ent, float target, float scale, float* d_ent, float* loss) {
+    __shared__ float red[4];
+    float acc = 0.f;
+    for (int64_t j = threadIdx.x; j < n_ent; j += 256) {
+        const float raw = ent[j];
+        const float dlt = nan_to_num_ref(raw) - target;
+        acc += dlt * dlt;
+        if (d_ent) d_ent[j] = isfinite(raw) ? scale * dlt : 0.f;
+    }
+    acc = reduce_wave(acc);
+    if (lane_id() == 0) red[wave_id()] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) loss[0] = fmaxf((red[0] + red[1] + red[2] + red[3]) / (float)n_ent, 0.f);
+}
 void launch_sdpa_fwd(int dtype, int64_t B, int S, int T, int E, float scale, const void* q, const void* k, const void* v,
                      void* out, float* probs, hipStream_t s);
 void launch_sdpa_bwd(int dtype, int64_t B, int S, int T, int E, float scale, const void* q, const void* k, const void* v,

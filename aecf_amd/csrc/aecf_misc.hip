@@ -241,12 +241,6 @@ __global__ __launch_bounds__(256) void mask_bwd_long_kernel(int64_t rows, int L,
 
 // ------------------------------------------------------------------------------------------
 // entropy_loss (ref aecf/AECFLayer.py:285-314): mean((nan_to_num(H) - target)^2), two-stage reduce
-__device__ __forceinline__ float nan_to_num_ref(float e) {   // nan=0, +inf=1, -inf=0 (ref :296)
-    if (e != e) return 0.f;
-    if (isinf(e)) return e > 0.f ? 1.f : 0.f;
-    return e;
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void entropy_loss_partial_kernel(int64_t n, float target,
                                                                    const typename Tr<T>::elem* __restrict__ e,

@@ -735,21 +735,7 @@ __global__ __launch_bounds__(256) void nce_finalize_kernel(NceFinArgs p) {
     }
     for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.Cp; j += (int64_t)gridDim.x * 256)
         p.v[j] = (p.sym && j < p.cols) ? 1.0f / p.c[j] : 0.f;
-    if (blockIdx.x == 0 && p.n_ent > 0) {
-        __shared__ float red[4];
-        float acc = 0.f;
-        for (int64_t j = threadIdx.x; j < p.n_ent; j += 256) {
-            const float raw = p.ent[j];
-            const float h = isnan(raw) ? 0.f : (isinf(raw) ? (raw > 0.f ? 1.f : 0.f) : raw);      // nan_to_num (ref :295-296)
-            const float dlt = h - p.ent_target;
-            acc += dlt * dlt;
-            if (p.d_ent) p.d_ent[j] = isfinite(raw) ? p.ent_scale * dlt : 0.f;
-        }
-        acc = reduce_wave(acc);
-        if (lane == 0) red[wave_id()] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) p.ent_loss[0] = fmaxf((red[0] + red[1] + red[2] + red[3]) / (float)p.n_ent, 0.f);
-    }
+    if (blockIdx.x == 0 && p.n_ent > 0) entropy_rider(p.ent, p.n_ent, p.ent_target, p.ent_scale, p.d_ent, p.ent_loss);
 }
 
 // W = ct (E (u_i + v_j) - npos [j = off + i]) in place over the tiled E, 8 elements per thread.  The positive's weight is a
@@ -926,6 +912,77 @@ SigWs sig_carve(void* ws, int64_t rows, int64_t cols, int d) {
     return w;
 }
 
+// the logits arrangement: a [rows, d] . b [cols, d]^T as OP_ROW x OP_ROW operands over MAP_2D, and its block count; the
+// caller adds its epilogue's fields
+struct LogitsLaunch {
+    NceGemmArgs g;
+    unsigned int blocks;
+};
+LogitsLaunch logits_args(int64_t rows, int64_t cols, int d, const void* a, const void* b) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    LogitsLaunch o = {};
+    NceGemmArgs& g = o.g;
+    g.a = (const char*)a; g.b = (const char*)b; g.lda = g.ldb = 2u * (unsigned)d;
+    g.a_sm = (int64_t)BT * g.lda; g.a_st = 128;
+    g.a_rows = (int)rows; g.b_rows = (int)cols;
+    g.m_tiles = (int)(Rp / BT); g.n_tiles = (int)(Cp / BT); g.k_steps = d / 64;
+    g.splits = 1; g.steps_per_split = g.k_steps;
+    g.m_valid = (int)rows; g.n_valid = (int)cols;
+    const unsigned int nsm = (g.m_tiles + 3) / 4, nsn = (g.n_tiles + 7) / 8;
+    o.blocks = ((nsm * nsn + 7) / 8) * 8 * 32;
+    return o;
+}
+
+// da = W b (m = local rows, n = d, K = keys, split over K into slabs that are then summed) and db = W^T a (m = keys, n = d,
+// K = local rows) over the tiled bf16 weights wt [Rp][Cp]; outputs float32 or -- one rounding of the float32 sums -- bf16.
+// g0: the epilogue's scalar fields (coef / upstream / temp), everything else zero.  dt with d_t: dL/dT = -(1/T) sum_i a_i.da_i
+// from per-block partials of the float32 da products (EPI_TD) in tdot_part [splits m_tiles n_tiles].
+template <int EPI_PLAIN, int EPI_TD>
+void launch_grad_products(int64_t rows, int64_t cols, int d, const NceGemmArgs& g0, const unsigned short* wt, float* slabs,
+                          float* tdot_part, const NceDevTemp* dt, const void* a, const void* b, int out_bf16, void* da, void* db,
+                          hipStream_t s) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int n_tiles_d = (d + BT - 1) / BT;
+    {
+        NceGemmArgs g = g0;
+        g.a = (const char*)wt; g.lda = 128; g.a_rows = (int)Rp;           // tile (mi, t) of W: [256][128 B], contiguous
+        g.a_sm = (Cp / 64) * (int64_t)32768; g.a_st = 32768;
+        g.b = (const char*)b; g.ldb = 2u * (unsigned)d; g.b_rows = (int)cols; g.b_cbytes = 2 * d;
+        g.m_tiles = (int)(Rp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Cp / 64);
+        g.splits = da_splits(Rp, Cp, d);
+        g.steps_per_split = (g.k_steps + g.splits - 1) / g.splits;
+        g.m_valid = (int)rows; g.n_valid = d;
+        g.out = g.splits > 1 ? (void*)slabs : da; g.ldo = d; g.slab_stride = rows * (int64_t)d;
+        g.out_bf16 = g.splits > 1 ? 0 : out_bf16;
+        const unsigned int units = (unsigned)(g.m_tiles * g.splits);
+        const unsigned int bx = 8u * g.m_tiles * g.n_tiles, bu = ((units + 7) / 8) * 8 * g.n_tiles;
+        if (dt && dt->d_t) {
+            g.tdot_src = (const unsigned short*)a; g.tdot_part = tdot_part;
+            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_TD, MAP_SPLITX>(g, bx, s);
+            else launch_gemm<OP_ROW, OP_COL, EPI_TD, MAP_UNITS>(g, bu, s);
+        } else {
+            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_PLAIN, MAP_SPLITX>(g, bx, s);
+            else launch_gemm<OP_ROW, OP_COL, EPI_PLAIN, MAP_UNITS>(g, bu, s);
+        }
+        if (g.splits > 1) {
+            const int64_t n4 = rows * (int64_t)d / 4;
+            nce_slab_sum_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s>>>(slabs, g.splits, n4, g.slab_stride, da, out_bf16);
+        }
+        if (dt && dt->d_t) launch_nce_dtemp(tdot_part, (int64_t)g.splits * g.m_tiles * g.n_tiles, 1, *dt, s);
+    }
+    {
+        NceGemmArgs g = g0;
+        g.a = (const char*)wt; g.lda = 128; g.a_rows = (int)Rp; g.a_cbytes = 0; g.a_sm = Cp / 64;
+        g.b = (const char*)a; g.ldb = 2u * (unsigned)d; g.b_rows = (int)rows; g.b_cbytes = 2 * d;
+        g.m_tiles = (int)(Cp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Rp / 64);
+        g.splits = 1; g.steps_per_split = g.k_steps;
+        g.m_valid = (int)cols; g.n_valid = d;
+        g.out = db; g.ldo = d; g.slab_stride = 0; g.out_bf16 = out_bf16;
+        const unsigned int units = (unsigned)g.m_tiles;
+        launch_gemm<OP_COLB, OP_COL, EPI_PLAIN, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
+    }
+}
+
 }  // namespace
 
 bool nce_gemm_supported(int dtype, int d, float temperature) {
@@ -940,23 +997,16 @@ void launch_nce_gemm_pass1(int64_t rows, int64_t cols, int d, float inv_temp, co
                            float* col_sums, hipStream_t s, const NceDevTemp* dt) {
     const NceWs w = carve(workspace, rows, cols, d);
     const int64_t Rp = up256(rows), Cp = up256(cols);
-    NceGemmArgs g = {};
-    g.a = (const char*)a; g.b = (const char*)b; g.lda = g.ldb = 2u * (unsigned)d;
-    g.a_sm = (int64_t)BT * g.lda; g.a_st = 128;
-    g.a_rows = (int)rows; g.b_rows = (int)cols;
-    g.m_tiles = (int)(Rp / BT); g.n_tiles = (int)(Cp / BT); g.k_steps = d / 64;
-    g.splits = 1; g.steps_per_split = g.k_steps;
-    g.m_valid = (int)rows; g.n_valid = (int)cols;
+    LogitsLaunch L = logits_args(rows, cols, d, a, b);
+    NceGemmArgs& g = L.g;
     g.e = w.e; g.e_tiles = Cp / 64;
     g.scale2 = inv_temp * 1.4426950408889634f; g.shift2 = g.scale2;
     g.rowsum_part = w.rowsum_part; g.colsum_part = w.colsum_part;
-    const unsigned int nsm = (g.m_tiles + 3) / 4, nsn = (g.n_tiles + 7) / 8;
-    const unsigned int blocks = ((nsm * nsn + 7) / 8) * 8 * 32;
     if (dt) {
         g.temp = dt->t; g.min_temp = dt->min_t;
-        launch_gemm<OP_ROW, OP_ROW, EPI_EXP_DT, MAP_2D>(g, blocks, s);
+        launch_gemm<OP_ROW, OP_ROW, EPI_EXP_DT, MAP_2D>(g, L.blocks, s);
     } else {
-        launch_gemm<OP_ROW, OP_ROW, EPI_EXP, MAP_2D>(g, blocks, s);
+        launch_gemm<OP_ROW, OP_ROW, EPI_EXP, MAP_2D>(g, L.blocks, s);
     }
     nce_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64)), dim3(256), 0, s>>>(w.rowsum_part, w.colsum_part, g.m_tiles, g.n_tiles,
                                                                                    rows, cols, w.l, col_sums ? col_sums : w.c_local);
@@ -996,47 +1046,10 @@ void launch_nce_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d
     else
         nce_weights_kernel<<<dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset,
                                                                                         coef * inv_temp, sym ? 2.0f : 1.0f, upstream);
-    const int n_tiles_d = (d + BT - 1) / BT;
-    {   // da = W b: m = local rows, n = d, K = keys
-        NceGemmArgs g = {};
-        g.a = (const char*)w.e; g.lda = 128; g.a_rows = (int)Rp;          // tile (mi, t) of E: [256][128 B], contiguous
-        g.a_sm = (Cp / 64) * (int64_t)32768; g.a_st = 32768;
-        g.b = (const char*)b; g.ldb = 2u * (unsigned)d; g.b_rows = (int)cols; g.b_cbytes = 2 * d;
-        g.m_tiles = (int)(Rp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Cp / 64);
-        g.splits = da_splits(Rp, Cp, d);
-        g.steps_per_split = (g.k_steps + g.splits - 1) / g.splits;
-        g.m_valid = (int)rows; g.n_valid = d;
-        g.out = g.splits > 1 ? (void*)w.slabs : da; g.ldo = d; g.slab_stride = rows * (int64_t)d;
-        g.out_bf16 = g.splits > 1 ? 0 : out_bf16;
-        const unsigned int units = (unsigned)(g.m_tiles * g.splits);
-        if (dt && dt->d_t) {
-            // dL/dT = -(1/T) sum_i a_i.da_i: per-block partials of the float32 products (this rank's rows, both directions when
-            // sym), into the row-sum partials pass 1 left behind (dead since its sums launch; splits <= max(1, Cp / 512) and
-            // n_tiles <= 16, so the splits m_tiles n_tiles partials fit in its Cp m_tiles floats)
-            g.tdot_src = (const unsigned short*)a; g.tdot_part = w.rowsum_part;
-            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_OUT_TD, MAP_SPLITX>(g, 8u * g.m_tiles * g.n_tiles, s);
-            else launch_gemm<OP_ROW, OP_COL, EPI_OUT_TD, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
-        } else {
-            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_OUT, MAP_SPLITX>(g, 8u * g.m_tiles * g.n_tiles, s);
-            else launch_gemm<OP_ROW, OP_COL, EPI_OUT, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
-        }
-        if (g.splits > 1) {
-            const int64_t n4 = rows * (int64_t)d / 4;
-            nce_slab_sum_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s>>>(w.slabs, g.splits, n4, g.slab_stride, da, out_bf16);
-        }
-        if (dt && dt->d_t) launch_nce_dtemp(w.rowsum_part, (int64_t)g.splits * g.m_tiles * g.n_tiles, 1, *dt, s);
-    }
-    {   // db = W^T a: m = keys, n = d, K = local rows
-        NceGemmArgs g = {};
-        g.a = (const char*)w.e; g.lda = 128; g.a_rows = (int)Rp; g.a_cbytes = 0; g.a_sm = Cp / 64;
-        g.b = (const char*)a; g.ldb = 2u * (unsigned)d; g.b_rows = (int)rows; g.b_cbytes = 2 * d;
-        g.m_tiles = (int)(Cp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Rp / 64);
-        g.splits = 1; g.steps_per_split = g.k_steps;
-        g.m_valid = (int)cols; g.n_valid = d;
-        g.out = db; g.ldo = d; g.slab_stride = 0; g.out_bf16 = out_bf16;
-        const unsigned int units = (unsigned)g.m_tiles;
-        launch_gemm<OP_COLB, OP_COL, EPI_OUT, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
-    }
+    // the tdot partials go into the row-sum partials pass 1 left behind (dead since its sums launch; splits <= max(1, Cp / 512)
+    // and n_tiles <= 16, so the splits m_tiles n_tiles partials fit in its Cp m_tiles floats); this rank's rows, both directions
+    // when sym.  The weights carry every scalar: the epilogues scale nothing.
+    launch_grad_products<EPI_OUT, EPI_OUT_TD>(rows, cols, d, NceGemmArgs{}, w.e, w.slabs, w.rowsum_part, dt, a, b, out_bf16, da, db, s);
 }
 
 // ---- sigmoid (SigLIP) loss on the same GEMMs ---------------------------------------------------------------------------
@@ -1050,18 +1063,12 @@ void launch_sig_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d
                            const void* a, const void* b, void* workspace, float* loss_rows, float* d_bias, hipStream_t s) {
     const SigWs w = sig_carve(workspace, rows, cols, d);
     const int64_t Rp = up256(rows), Cp = up256(cols);
-    NceGemmArgs g = {};
-    g.a = (const char*)a; g.b = (const char*)b; g.lda = g.ldb = 2u * (unsigned)d;
-    g.a_sm = (int64_t)BT * g.lda; g.a_st = 128;
-    g.a_rows = (int)rows; g.b_rows = (int)cols;
-    g.m_tiles = (int)(Rp / BT); g.n_tiles = (int)(Cp / BT); g.k_steps = d / 64;
-    g.splits = 1; g.steps_per_split = g.k_steps;
-    g.m_valid = (int)rows; g.n_valid = (int)cols;
+    LogitsLaunch L = logits_args(rows, cols, d, a, b);
+    NceGemmArgs& g = L.g;
     g.e = w.g; g.e_tiles = Cp / 64;
     g.temp = temp; g.min_temp = min_temp; g.bias = bias; g.row_offset = row_offset;
     g.sp_part = w.sp_part; g.sg_part = w.sg_part;
-    const unsigned int nsm = (g.m_tiles + 3) / 4, nsn = (g.n_tiles + 7) / 8;
-    launch_gemm<OP_ROW, OP_ROW, EPI_SIG, MAP_2D>(g, ((nsm * nsn + 7) / 8) * 8 * 32, s);
+    launch_gemm<OP_ROW, OP_ROW, EPI_SIG, MAP_2D>(g, L.blocks, s);
     sig_rows_kernel<<<dim3((unsigned)(Rp / 64)), dim3(256), 0, s>>>(w.sp_part, w.sg_part, g.n_tiles, Rp, rows, loss_rows, w.gsum);
     sig_dbias_kernel<<<dim3(1), dim3(256), 0, s>>>(w.gsum, rows, d_bias);
 }
@@ -1071,47 +1078,9 @@ void launch_sig_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d
 void launch_sig_gemm_grads(int64_t rows, int64_t cols, int d, const NceDevTemp& dt, float coef, const void* a, const void* b,
                            void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s) {
     const SigWs w = sig_carve(workspace, rows, cols, d);
-    const int64_t Rp = up256(rows), Cp = up256(cols);
-    const int n_tiles_d = (d + BT - 1) / BT;
-    {   // da: m = local rows, n = d, K = keys
-        NceGemmArgs g = {};
-        g.a = (const char*)w.g; g.lda = 128; g.a_rows = (int)Rp;
-        g.a_sm = (Cp / 64) * (int64_t)32768; g.a_st = 32768;
-        g.b = (const char*)b; g.ldb = 2u * (unsigned)d; g.b_rows = (int)cols; g.b_cbytes = 2 * d;
-        g.m_tiles = (int)(Rp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Cp / 64);
-        g.splits = da_splits(Rp, Cp, d);
-        g.steps_per_split = (g.k_steps + g.splits - 1) / g.splits;
-        g.m_valid = (int)rows; g.n_valid = d;
-        g.out = g.splits > 1 ? (void*)w.slabs : da; g.ldo = d; g.slab_stride = rows * (int64_t)d;
-        g.out_bf16 = g.splits > 1 ? 0 : out_bf16;
-        g.temp = dt.t; g.min_temp = dt.min_t; g.coef = coef; g.upstream = upstream;
-        const unsigned int units = (unsigned)(g.m_tiles * g.splits);
-        if (dt.d_t) {
-            g.tdot_src = (const unsigned short*)a; g.tdot_part = w.tdot_part;
-            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_OUT_TD_S, MAP_SPLITX>(g, 8u * g.m_tiles * g.n_tiles, s);
-            else launch_gemm<OP_ROW, OP_COL, EPI_OUT_TD_S, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
-        } else {
-            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_OUT_S, MAP_SPLITX>(g, 8u * g.m_tiles * g.n_tiles, s);
-            else launch_gemm<OP_ROW, OP_COL, EPI_OUT_S, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
-        }
-        if (g.splits > 1) {
-            const int64_t n4 = rows * (int64_t)d / 4;
-            nce_slab_sum_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s>>>(w.slabs, g.splits, n4, g.slab_stride, da, out_bf16);
-        }
-        if (dt.d_t) launch_nce_dtemp(w.tdot_part, (int64_t)g.splits * g.m_tiles * g.n_tiles, 1, dt, s);
-    }
-    {   // db: m = keys, n = d, K = local rows
-        NceGemmArgs g = {};
-        g.a = (const char*)w.g; g.lda = 128; g.a_rows = (int)Rp; g.a_cbytes = 0; g.a_sm = Cp / 64;
-        g.b = (const char*)a; g.ldb = 2u * (unsigned)d; g.b_rows = (int)rows; g.b_cbytes = 2 * d;
-        g.m_tiles = (int)(Cp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Rp / 64);
-        g.splits = 1; g.steps_per_split = g.k_steps;
-        g.m_valid = (int)cols; g.n_valid = d;
-        g.out = db; g.ldo = d; g.slab_stride = 0; g.out_bf16 = out_bf16;
-        g.temp = dt.t; g.min_temp = dt.min_t; g.coef = coef; g.upstream = upstream;
-        const unsigned int units = (unsigned)g.m_tiles;
-        launch_gemm<OP_COLB, OP_COL, EPI_OUT_S, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
-    }
+    NceGemmArgs g0 = {};
+    g0.temp = dt.t; g0.min_temp = dt.min_t; g0.coef = coef; g0.upstream = upstream;
+    launch_grad_products<EPI_OUT_S, EPI_OUT_TD_S>(rows, cols, d, g0, w.g, w.slabs, w.tdot_part, &dt, a, b, out_bf16, da, db, s);
 }
 
 // ---- retrieval ranks: the counting pass (thresholds, reduction and checks in aecf_retrieval.hip) -------------------------
@@ -1120,18 +1089,11 @@ void launch_sig_gemm_grads(int64_t rows, int64_t cols, int d, const NceDevTemp& 
 // col_part [m_tiles][Cp] (Rp, Cp: rows, cols rounded up to 256)
 void launch_rank_gemm(int64_t rows, int64_t cols, int64_t row_offset, int d, const void* a, const void* b, const float* pos_row,
                       const float* pos_col, int* row_part, int* col_part, hipStream_t s) {
-    const int64_t Rp = up256(rows), Cp = up256(cols);
-    NceGemmArgs g = {};
-    g.a = (const char*)a; g.b = (const char*)b; g.lda = g.ldb = 2u * (unsigned)d;
-    g.a_sm = (int64_t)BT * g.lda; g.a_st = 128;
-    g.a_rows = (int)rows; g.b_rows = (int)cols;
-    g.m_tiles = (int)(Rp / BT); g.n_tiles = (int)(Cp / BT); g.k_steps = d / 64;
-    g.splits = 1; g.steps_per_split = g.k_steps;
-    g.m_valid = (int)rows; g.n_valid = (int)cols;
+    LogitsLaunch L = logits_args(rows, cols, d, a, b);
+    NceGemmArgs& g = L.g;
     g.row_offset = row_offset;
     g.pos_row = pos_row; g.pos_col = pos_col; g.rank_row_part = row_part; g.rank_col_part = col_part;
-    const unsigned int nsm = (g.m_tiles + 3) / 4, nsn = (g.n_tiles + 7) / 8;
-    launch_gemm<OP_ROW, OP_ROW, EPI_RANK, MAP_2D>(g, ((nsm * nsn + 7) / 8) * 8 * 32, s);
+    launch_gemm<OP_ROW, OP_ROW, EPI_RANK, MAP_2D>(g, L.blocks, s);
 }
 
 }  // namespace aecf

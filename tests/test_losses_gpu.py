@@ -105,11 +105,14 @@ def _nce_reference(q, k, off, T, coef, rows_sel=None, cols_sel=None):
 
 @pytest.mark.parametrize("low_memory", [False, True], ids=["gemm", "stream"])
 @pytest.mark.parametrize("rows,cols,off,d", [(128, 128, 0, 128), (100, 333, 57, 256), (640, 2048, 1000, 512),
-                                             (97, 1500, 3, 768), (64, 700, 600, 1024), (200, 200, 0, 384)])
+                                             (97, 1500, 3, 768), (64, 700, 600, 1024), (200, 200, 0, 384),
+                                             (512, 16385, 0, 128)])
 def test_flash_nce_matches_float32_reference(rows, cols, off, d, low_memory):
     """One InfoNCE direction -- tile-GEMM form (aecf_nce_gemm.hip, the default) and streaming form (aecf_nce_flash.hip, chosen
     by handing over the O(rows d) workspace) -- against float32 torch math on the same bf16 inputs: ragged row / column
-    counts (no % 64 restriction), key splits, every supported width, positives at an offset (a data-parallel shard)."""
+    counts (no % 64 restriction), key splits, every supported width, positives at an offset (a data-parallel shard).
+    (512, 16385): the streaming form's split rule gives 32 key splits of 544 columns, of which the last holds none and the one
+    before it 65."""
     from aecf_amd.losses import _NceDirection, l2_normalize
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(rows + cols + d)

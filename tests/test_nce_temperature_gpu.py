@@ -34,6 +34,17 @@ def _ref(na, nb, T, coef=None):
     return loss.item(), t.grad.item()
 
 
+def _ref_direction(q, k, T, coef):
+    """float64 InfoNCE of unit-norm local rows q against the keys k (positives at column i) and dL/dT."""
+    a, b = q.detach().double(), k.detach().double()
+    t = torch.tensor(float(T), dtype=torch.float64, device=a.device, requires_grad=True)
+    s = a @ b.T / t
+    i = torch.arange(a.shape[0], device=a.device)
+    loss = coef * (torch.logsumexp(s, 1) - s[i, i]).sum()
+    loss.backward()
+    return loss.item(), t.grad.item()
+
+
 def _normed(za, zb):
     from aecf_amd import losses
     return losses.l2_normalize(za).detach(), losses.l2_normalize(zb).detach()
@@ -50,15 +61,23 @@ def _rel(got, want):
     (1000, 512, torch.bfloat16, 0.025, 5e-3),
     (333, 256, torch.bfloat16, 0.01, 5e-3),         # min_temperature < 0.025: streaming form
     (320, 256, torch.float32, 0.025, 1e-5),         # float32: materialising form
-])
+    ((512, 16385), 128, torch.bfloat16, 0.025, 5e-3),   # (rows, cols): one direction on the streaming workspace; of its 32 key
+])                                                      # splits of 544 columns the last is empty
 def test_temperature_grad_matches_float64(n, d, dtype, min_t, bound):
     from aecf_amd import losses
-    za, zb = _views(n, d, dtype)
     T = torch.tensor(0.07, device=DEV, requires_grad=True)
-    loss = losses.info_nce(za, zb, temperature=T, min_temperature=min_t)
+    if isinstance(n, tuple):
+        rows, cols = n
+        za, zb = _views(cols, d, dtype)
+        q, k = _normed(za[:rows], zb)
+        loss = losses._NceDirection.apply(q, k, 0, T, 1.0 / rows, True, min_t)
+        want_loss, want_g = _ref_direction(q, k, 0.07, 1.0 / rows)
+    else:
+        za, zb = _views(n, d, dtype)
+        loss = losses.info_nce(za, zb, temperature=T, min_temperature=min_t)
+        want_loss, want_g = _ref(*_normed(za, zb), 0.07)
     loss.backward()
     assert T.grad is not None and T.grad.shape == T.shape
-    want_loss, want_g = _ref(*_normed(za, zb), 0.07)
     assert _rel(float(loss), want_loss) < (1e-5 if dtype == torch.float32 else 2e-3)
     err = _rel(float(T.grad), want_g)
     print(f"T.grad rel err {err:.2e} ({n}, {d}, {dtype}, min_t {min_t})")
