@@ -197,6 +197,10 @@ _SYMBOLS = [
     ("aecf_retrieval_ranks", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_size_t, c_void_p]),
+    # top-k retrieval: values / indices of the k best columns of every row
+    ("aecf_retrieval_topk_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    ("aecf_retrieval_topk", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 

@@ -959,6 +959,25 @@ int aecf_retrieval_ranks(int64_t rows, int64_t cols, int64_t row_offset, int32_t
     return launch_status();
 }
 
+// ---- top-k retrieval (include/aecf_hip.h, "top-k retrieval")
+
+size_t aecf_retrieval_topk_workspace_bytes(int64_t rows, int64_t cols, int32_t d, int32_t k) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || k <= 0 || rows > 0x7fffffff || cols > 0x7fffffff || !retrieval_topk_supported(d, k)) return 0;
+    return retrieval_topk_workspace_bytes(rows, cols, d, k);
+}
+
+int aecf_retrieval_topk(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t k, int32_t exclude_partner, const void* a,
+                        const void* b, float* values, int32_t* indices, void* workspace, size_t workspace_bytes, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || k <= 0 || rows > 0x7fffffff || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (k > cols - (exclude_partner ? 1 : 0)) return AECF_ERR_BAD_DIMS;
+    if (exclude_partner && (row_offset < 0 || row_offset + rows > cols)) return AECF_ERR_BAD_DIMS;
+    if (!retrieval_topk_supported(d, k)) return AECF_ERR_UNSUPPORTED;
+    if (!a || !b || !values || !indices || !workspace) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < retrieval_topk_workspace_bytes(rows, cols, d, k)) return AECF_ERR_WORKSPACE;
+    launch_retrieval_topk(rows, cols, row_offset, d, k, exclude_partner ? 1 : 0, a, b, values, indices, workspace, (hipStream_t)stream);
+    return launch_status();
+}
+
 int aecf_route_build(int64_t rows, const uint8_t* present_a, const uint8_t* present_b, int32_t* route, int32_t* slot,
                      int32_t* index, int32_t* counts, void* stream) {
     if (rows <= 0 || rows > 0x7fffffff) return AECF_ERR_BAD_DIMS;

@@ -325,6 +325,17 @@ void launch_retrieval_ranks(int64_t rows, int64_t cols, int64_t row_offset, int 
 void launch_rank_gemm(int64_t rows, int64_t cols, int64_t row_offset, int d, const void* a, const void* b, const float* pos_row,
                       const float* pos_col, int* row_part, int* col_part, hipStream_t s);
 
+// Top-k retrieval (aecf_retrieval.hip; the selection pass is the EPI_TOPK epilogue of the same GEMM): values [rows, k] float32
+// and indices [rows, k] int32 of the k <= 16 best columns of every row -- higher score first, lower column first among equal
+// scores, NaN below -inf; exclude_partner drops column row_offset + i of row i.  Workspace: 8 KP bytes per row and column
+// tile (KP: k rounded up to a power of two), never rows x cols.
+bool retrieval_topk_supported(int d, int k);
+size_t retrieval_topk_workspace_bytes(int64_t rows, int64_t cols, int d, int k);
+void launch_retrieval_topk(int64_t rows, int64_t cols, int64_t row_offset, int d, int k, int exclude_partner, const void* a,
+                           const void* b, float* values, int32_t* indices, void* workspace, hipStream_t s);
+void launch_topk_gemm(int64_t rows, int64_t cols, int64_t row_offset, int d, int k, int kp, int exclude_partner, const void* a,
+                      const void* b, unsigned long long* part, hipStream_t s);
+
 // ---------------- presence routing (aecf_route.hip) ----------------
 void launch_route_build(int64_t rows, const uint8_t* pa, const uint8_t* pb, int32_t* route, int32_t* slot, int32_t* index,
                         int32_t* counts, hipStream_t s);

@@ -46,6 +46,17 @@
 // columns, summed by rank_counts_kernel.  Taken over vector atomics onto zeroed outputs because it is the arrangement the
 // row / column sums of the two losses already have (no memset node in front of the launch, no contended atomics on the
 // 256 tiles of a row, plain coalesced stores); integer sums are exact in any order, so either would be deterministic.
+//
+// Top-k retrieval (aecf_retrieval_topk, host side and merge in aecf_retrieval.hip) is a fifth epilogue of the same arrangement,
+// EPI_TOPK: nothing of the tile is stored either; every row of the tile leaves its best k candidates.  A candidate is ONE
+// 64-bit key -- high word the order-preserving integer image of the float32 score (NaN -> 1: below -inf's 0x007fffff, above
+// the sentinel 0; -0 counted as +0), low word the inverted global column -- so "higher score first, lower column first among
+// equal scores" is a single unsigned compare and the result cannot depend on tile, block or rank order.  A lane sorts the 16
+// keys it holds of a row (63 compare-exchanges, all in registers); the 4 lane groups holding the row's 64 columns of this
+// wave then pop the largest head k times (two xor shuffles per pop) into LDS, where the stages were; one thread per row
+// merges the 4 waves' lists into the tile's list [k] of the workspace [n_tiles][Rp][KP].  The accumulators are consumed rt by
+// rt: 32 key registers at a time next to them, no scratch.  The excluded partner and the padding become the sentinel -- a
+// select that only the tiles holding such elements run, as above.
 #include <math.h>
 #include <type_traits>
 
@@ -63,7 +74,8 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // EPI_SIG (sigmoid loss, logits pass): g = sigmoid(l) - [positive] as bf16 into the tiled workspace + two per-row partials per
 // n tile; EPI_OUT_S / EPI_OUT_TD_S: EPI_OUT / EPI_OUT_TD with the float32 accumulator multiplied by coef / Tc * upstream first
 // EPI_RANK (retrieval ranks, logits pass): nothing stored; per-tile counts of acc > / == the row's and the column's threshold
-enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7 };
+// EPI_TOPK (top-k retrieval, logits pass): nothing stored; per-tile sorted lists of the k best (score, column) keys of every row
+enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8 };
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -109,6 +121,9 @@ struct NceGemmArgs {
     const float* pos_col;               // [n_valid]  threshold of output column j; NULL: no column counts
     int* rank_row_part;                 // [n_tiles][m_tiles 256]  greater | equal << 16
     int* rank_col_part;                 // [m_tiles][n_tiles 256]
+    // EPI_TOPK (also reads row_offset: the excluded partner of output row i is column row_offset + i)
+    unsigned long long* topk_part;      // [n_tiles][m_tiles 256][topk_kp]  keys, best first; slots >= topk are not written
+    int topk, topk_kp;                  // k <= 16 and the list pitch (k rounded up to a power of two)
 };
 
 // sigmoid(x) and the pieces of softplus(x) for x = n ln 2, two elements: u = 2^min(n, 126), t = 1 + u, r = 1 / t;
@@ -589,6 +604,99 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
             } else if (cols_on) {
                 const int c = tdx - BT;
                 p.rank_col_part[((int64_t)mi * p.n_tiles + ni) * BT + c] = lcol[c] + lcol[BT + c];
+            }
+        } else if (EPI == EPI_TOPK) {
+            typedef unsigned long long u64;
+            const int kk = p.topk;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
+            u64* lst = reinterpret_cast<u64*>(smem);            // [4 wn][16 slots][256 rows] keys: the 128 KB of the stages
+            // block-uniform: only tiles holding an excluded partner or a ragged edge pay for the selects
+            const int64_t p0 = p.row_offset + (int64_t)BT * mi;
+            const bool special = BT * (mi + 1) > p.m_valid || BT * (ni + 1) > p.n_valid ||
+                                 (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
+            const unsigned int inv0 = ~(unsigned)gj0;           // inverted column of (ct, r): inv0 - (16 ct + r)
+            auto rows8 = [&](auto special_c) {
+                constexpr bool SP = decltype(special_c)::value;
+#pragma unroll
+                for (int rt = 0; rt < 8; ++rt) {
+                    const int64_t i = gi0 + 16 * rt;
+                    u64 K[16];
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            float sv = acc[rt][ct][r];
+                            asm volatile("" : "+v"(sv));        // (opaque: keeps the two variants' common work behind the branch)
+                            sv += 0.f;                          // -0 -> +0: equal scores have one image
+                            const unsigned int b = __float_as_uint(sv);
+                            unsigned int u = b ^ ((unsigned)((int)b >> 31) | 0x80000000u);
+                            u = sv != sv ? 1u : u;
+                            u64 key = ((u64)u << 32) | (u64)(inv0 - (unsigned)(16 * ct + r));
+                            if (SP) {
+                                const int col = gj0 + 16 * ct + r;
+                                key = ((i < p.m_valid) & (col < p.n_valid) & (col != p.row_offset + i)) ? key : 0ull;
+                            }
+                            K[4 * ct + r] = key;
+                        }
+                    }
+                    // the lane's 16 keys, best first: Batcher's merge exchange, 63 compare-exchanges
+#define TOPK_CE(x_, y_)                                                                                                 \
+    do {                                                                                                                \
+        const u64 hi_ = K[x_] > K[y_] ? K[x_] : K[y_], lo_ = K[x_] > K[y_] ? K[y_] : K[x_];                             \
+        K[x_] = hi_; K[y_] = lo_;                                                                                       \
+    } while (0)
+                    TOPK_CE(0, 1); TOPK_CE(2, 3); TOPK_CE(4, 5); TOPK_CE(6, 7); TOPK_CE(8, 9); TOPK_CE(10, 11); TOPK_CE(12, 13); TOPK_CE(14, 15);
+                    TOPK_CE(0, 2); TOPK_CE(1, 3); TOPK_CE(4, 6); TOPK_CE(5, 7); TOPK_CE(8, 10); TOPK_CE(9, 11); TOPK_CE(12, 14); TOPK_CE(13, 15);
+                    TOPK_CE(1, 2); TOPK_CE(5, 6); TOPK_CE(9, 10); TOPK_CE(13, 14);
+                    TOPK_CE(0, 4); TOPK_CE(1, 5); TOPK_CE(2, 6); TOPK_CE(3, 7); TOPK_CE(8, 12); TOPK_CE(9, 13); TOPK_CE(10, 14); TOPK_CE(11, 15);
+                    TOPK_CE(2, 4); TOPK_CE(3, 5); TOPK_CE(10, 12); TOPK_CE(11, 13);
+                    TOPK_CE(1, 2); TOPK_CE(3, 4); TOPK_CE(5, 6); TOPK_CE(9, 10); TOPK_CE(11, 12); TOPK_CE(13, 14);
+                    TOPK_CE(0, 8); TOPK_CE(1, 9); TOPK_CE(2, 10); TOPK_CE(3, 11); TOPK_CE(4, 12); TOPK_CE(5, 13); TOPK_CE(6, 14); TOPK_CE(7, 15);
+                    TOPK_CE(4, 8); TOPK_CE(5, 9); TOPK_CE(6, 10); TOPK_CE(7, 11);
+                    TOPK_CE(2, 4); TOPK_CE(3, 5); TOPK_CE(6, 8); TOPK_CE(7, 9); TOPK_CE(10, 12); TOPK_CE(11, 13);
+                    TOPK_CE(1, 2); TOPK_CE(3, 4); TOPK_CE(5, 6); TOPK_CE(7, 8); TOPK_CE(9, 10); TOPK_CE(11, 12); TOPK_CE(13, 14);
+#undef TOPK_CE
+                    // the wave's 64 columns of the row lie in 4 lane groups: pop the largest of the 4 heads k times
+                    u64* dst = lst + (wn * 16) * BT + 128 * wm + 16 * rt + r16;
+                    for (int t = 0; t < kk; ++t) {
+                        u64 win = K[0];
+                        u64 o = __shfl_xor(win, 16, 64);
+                        win = o > win ? o : win;
+                        o = __shfl_xor(win, 32, 64);
+                        win = o > win ? o : win;
+                        if (lg == 0) dst[t * BT] = win;
+                        const bool mine = K[0] == win;          // keys are distinct (only sentinels repeat)
+#pragma unroll
+                        for (int j = 0; j < 15; ++j) K[j] = mine ? K[j + 1] : K[j];
+                        K[15] = mine ? 0ull : K[15];
+                    }
+                }
+            };
+            if (special) rows8(std::integral_constant<bool, true>{});
+            else rows8(std::integral_constant<bool, false>{});
+            __syncthreads();
+            if (threadIdx.x < BT) {
+                // one thread per row: the 4 waves' sorted lists into the tile's list
+                const u64* l0 = lst + threadIdx.x;
+                u64* out = p.topk_part + (((int64_t)ni * p.m_tiles + mi) * BT + threadIdx.x) * p.topk_kp;
+                u64 h[4];
+                int c[4];
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) { h[q4] = l0[(q4 * 16) * BT]; c[q4] = 0; }
+                for (int t = 0; t < kk; ++t) {
+                    const u64 h01 = h[0] > h[1] ? h[0] : h[1], h23 = h[2] > h[3] ? h[2] : h[3];
+                    const u64 best = h01 > h23 ? h01 : h23;
+                    out[t] = best;
+#pragma unroll
+                    for (int q4 = 0; q4 < 4; ++q4) {
+                        const bool won = h[q4] == best;
+                        c[q4] += (int)won;
+                        const bool more = c[q4] < kk;
+                        const u64 nx = l0[(q4 * 16 + (more ? c[q4] : 0)) * BT];
+                        h[q4] = won ? (more ? nx : 0ull) : h[q4];
+                    }
+                }
             }
         } else {
             float scale2 = p.scale2, shift2 = p.shift2;
@@ -1094,6 +1202,19 @@ void launch_rank_gemm(int64_t rows, int64_t cols, int64_t row_offset, int d, con
     g.row_offset = row_offset;
     g.pos_row = pos_row; g.pos_col = pos_col; g.rank_row_part = row_part; g.rank_col_part = col_part;
     launch_gemm<OP_ROW, OP_ROW, EPI_RANK, MAP_2D>(g, L.blocks, s);
+}
+
+// ---- top-k retrieval: the selection pass (merge of the tiles' lists and checks in aecf_retrieval.hip) ---------------------
+
+// per-tile sorted lists of the k <= 16 best keys of every row of a [rows, d] . b [cols, d]^T into part [n_tiles][Rp][kp];
+// exclude_partner: element (i, row_offset + i) is not a candidate
+void launch_topk_gemm(int64_t rows, int64_t cols, int64_t row_offset, int d, int k, int kp, int exclude_partner, const void* a,
+                      const void* b, unsigned long long* part, hipStream_t s) {
+    LogitsLaunch L = logits_args(rows, cols, d, a, b);
+    NceGemmArgs& g = L.g;
+    g.row_offset = exclude_partner ? row_offset : -((int64_t)1 << 40);      // no row has a partner on any tile
+    g.topk_part = part; g.topk = k; g.topk_kp = kp;
+    launch_gemm<OP_ROW, OP_ROW, EPI_TOPK, MAP_2D>(g, L.blocks, s);
 }
 
 }  // namespace aecf

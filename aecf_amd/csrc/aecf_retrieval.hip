@@ -14,6 +14,13 @@
 // unpacks and adds them in a fixed order.  Partials were taken over vector atomics onto zeroed outputs: it is what the sums of
 // the two losses do, needs no memset in front of the GEMM and no atomics contended by the 256 tiles of a row; being integer
 // sums, either way gives the same counts in any order.
+//
+// Top-k retrieval (aecf_retrieval_topk): for every row of a its k <= 16 best columns of b under the total order "higher score
+// first, lower column first among equal scores, NaN (all equal) below -inf".  The same logits pass with the EPI_TOPK epilogue
+// leaves, per 256 x 256 tile and row, a sorted list of the tile's best k candidates in the workspace [C / 256][Rp][KP] (KP: k
+// rounded up to a power of two), each candidate one 64-bit key whose unsigned order IS that order (high word: integer image of
+// the score, low word: inverted column; 0 = no candidate).  topk_merge_kernel below takes the best k of a row's lists.  Keys
+// are distinct, so the result is the same set in the same order whatever the tile, block or rank arrangement.
 #include "aecf_kernels.h"
 
 namespace aecf {
@@ -72,6 +79,51 @@ __global__ __launch_bounds__(256) void rank_counts_kernel(const int* row_part, c
     }
 }
 
+// values [R, k] / indices [R, k] = the k largest keys of row i's n_tiles lists, decoded.  One wave per row: a lane takes the tiles
+// lane, lane + 64, .. and inserts their candidates into a sorted list of 16 registers (a tile's list is sorted, so its first
+// candidate that does not enter ends the tile); then the wave pops the largest of the 64 heads k times.
+__global__ __launch_bounds__(256) void topk_merge_kernel(const unsigned long long* part, int n_tiles, int64_t Rp, int kp, int k,
+                                                         int64_t rows, float* values, int32_t* indices) {
+    typedef unsigned long long u64;
+    const int lane = lane_id();
+    const int64_t row = (int64_t)blockIdx.x * 4 + wave_id();
+    if (row >= rows) return;
+    u64 L[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) L[j] = 0ull;
+    for (int t = lane; t < n_tiles; t += 64) {
+        const u64* src = part + ((int64_t)t * Rp + row) * kp;
+        for (int s = 0; s < k; ++s) {
+            u64 x = src[s];
+            if (x <= L[15]) break;                      // (the sentinel 0 never enters)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const u64 hi = x > L[j] ? x : L[j], lo = x > L[j] ? L[j] : x;
+                L[j] = hi; x = lo;
+            }
+        }
+    }
+    for (int t = 0; t < k; ++t) {
+        u64 win = L[0];
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const u64 o = __shfl_xor(win, m, 64);
+            win = o > win ? o : win;
+        }
+        if (lane == 0) {
+            // the image back to the float: sign bit set = a non-negative score, else the complement; 1 = NaN
+            const unsigned int u = (unsigned int)(win >> 32);
+            const unsigned int bits = u == 1u ? 0x7fc00000u : ((u & 0x80000000u) ? u ^ 0x80000000u : ~u);
+            values[row * k + t] = __uint_as_float(bits);
+            indices[row * k + t] = (int32_t)(~(unsigned int)win);
+        }
+        const bool mine = L[0] == win;
+#pragma unroll
+        for (int j = 0; j < 15; ++j) L[j] = mine ? L[j + 1] : L[j];
+        L[15] = mine ? 0ull : L[15];
+    }
+}
+
 struct RankWs {
     int* row_part;                      // [n_tiles][Rp]
     int* col_part;                      // [m_tiles][Cp]
@@ -110,6 +162,28 @@ void launch_retrieval_ranks(int64_t rows, int64_t cols, int64_t row_offset, int 
     const int64_t elems = pos_col ? Rp + Cp : Rp;       // the column blocks come after the row blocks: leave them out
     rank_counts_kernel<<<dim3((unsigned)(elems / 64)), dim3(256), 0, s>>>(w.row_part, w.col_part, (int)(Rp / BT), (int)(Cp / BT), rows,
                                                                            cols, row_greater, row_equal, col_greater, col_equal);
+}
+
+bool retrieval_topk_supported(int d, int k) { return retrieval_supported(d) && k >= 1 && k <= 16; }
+
+static int topk_pitch(int k) {
+    int kp = 1;
+    while (kp < k) kp *= 2;
+    return kp;
+}
+
+size_t retrieval_topk_workspace_bytes(int64_t rows, int64_t cols, int d, int k) {
+    (void)d;
+    return al256((size_t)(up256(cols) / BT) * (size_t)up256(rows) * (size_t)topk_pitch(k) * 8);
+}
+
+void launch_retrieval_topk(int64_t rows, int64_t cols, int64_t row_offset, int d, int k, int exclude_partner, const void* a,
+                           const void* b, float* values, int32_t* indices, void* workspace, hipStream_t s) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int kp = topk_pitch(k);
+    unsigned long long* part = (unsigned long long*)workspace;
+    launch_topk_gemm(rows, cols, row_offset, d, k, kp, exclude_partner, a, b, part, s);
+    topk_merge_kernel<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s>>>(part, (int)(Cp / BT), Rp, kp, k, rows, values, indices);
 }
 
 }  // namespace aecf

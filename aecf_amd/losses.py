@@ -675,6 +675,75 @@ def retrieval_metrics(za: torch.Tensor, zb: torch.Tensor, ks: Sequence[int] = (1
     return {f"{side}_{n}": vec[i * len(names) + j] for i, side in enumerate(("a2b", "b2a")) for j, n in enumerate(names)}
 
 
+class RetrievalTopK(NamedTuple):
+    """What ``retrieval_topk`` returns: for each of this rank's queries the scores (``values``, float32 [b_local, k], best
+    first) and the positions (``indices``, int64 [b_local, k]) of its k best keys; a position indexes the keys of every rank in
+    all-gather order (rank r's key j is ``r * b_k + j``)."""
+    values: torch.Tensor
+    indices: torch.Tensor
+
+
+def retrieval_topk(queries: torch.Tensor, keys: torch.Tensor, k: int, group=None, normalize: bool = True,
+                   exclude_partner: bool = False) -> RetrievalTopK:
+    """The k best keys of every query, from ONE logits pass that stores nothing of size b_local x b_all (aecf_retrieval_topk):
+    hard negatives between steps, kNN evaluation, a look at what a query retrieves, the input of a re-ranking stage.
+    ``queries``: [b_q, d], ``keys``: [b_k, d], bfloat16 on a ROCm device, d % 64 == 0, 64 <= d <= 4096, 1 <= k <= 16, the same
+    row counts on every rank.  b_q and b_k may differ unless ``exclude_partner`` is set.
+
+    With s_ij = q_i . key_j (float32 accumulation) over the keys of every rank of ``group``, row i of the result lists the k
+    first keys of row i of s in a fixed total order: the higher score first; among equal scores the lower index first; NaN
+    scores, all equal to each other, after -inf.  The order is total, so the answer does not depend on how the keys are dealt
+    over ranks.  ``exclude_partner=True`` (shapes must be equal) leaves out the query's own partner, global key
+    ``rank * b_local + i`` for local row i -- what hard-negative mining wants.  k may not exceed the keys that remain.
+
+    One direction per call: for the best queries of every key swap the arguments.  ``normalize=True`` brings the rows to unit
+    norm with the library's kernel first; ``False`` takes them as given.  Nothing is rounded to bfloat16 on the way in -- a
+    ranking is the one output where that would change answers -- so other dtypes are refused.  Runs without a graph (inputs
+    detached, outputs carry none) and without a host read: it captures on one rank.  Data parallel: one all-gather of the keys
+    and nothing else; each rank answers for its own queries."""
+    _require_device(queries, "queries")
+    _require_device(keys, "keys")
+    if queries.dim() != 2 or keys.dim() != 2 or queries.shape[1] != keys.shape[1]:
+        raise ValueError(f"retrieval_topk expects queries [b_q, d] and keys [b_k, d], got {tuple(queries.shape)} and {tuple(keys.shape)}")
+    if exclude_partner and queries.shape != keys.shape:
+        raise ValueError(f"retrieval_topk with exclude_partner expects two [b, d] tensors of equal shape, got {tuple(queries.shape)} "
+                         f"and {tuple(keys.shape)}")
+    if isinstance(k, bool) or not isinstance(k, int) or k <= 0:
+        raise ValueError(f"aecf_amd: retrieval_topk needs a positive integer k, got {k!r}")
+    if queries.dtype != torch.bfloat16 or keys.dtype != torch.bfloat16:
+        raise NotImplementedError(f"aecf_amd: retrieval_topk takes bfloat16 rows only (nothing is rounded on the way in); got "
+                                  f"{queries.dtype} and {keys.dtype}")
+    rows, d = queries.shape
+    if d % 64 != 0 or not 64 <= d <= 4096:
+        raise NotImplementedError(f"aecf_amd: retrieval_topk needs d % 64 == 0 and 64 <= d <= 4096, got d = {d}")
+    if k > 16:
+        raise NotImplementedError(f"aecf_amd: retrieval_topk serves k <= 16, got k = {k}")
+    rank, world = dp.world_info(group)
+    b_k = keys.shape[0]
+    cols, offset = b_k * world, rank * rows
+    left = cols - (1 if exclude_partner else 0)
+    if rows == 0 or k > left:
+        raise ValueError(f"aecf_amd: retrieval_topk needs at least one query and k <= the {left} keys to choose from, got "
+                         f"{rows} queries and k = {k}")
+    lib = _lib.load()
+    ws_bytes = lib.aecf_retrieval_topk_workspace_bytes(rows, cols, d, k)
+    if ws_bytes == 0:
+        raise NotImplementedError(f"aecf_amd: retrieval_topk does not serve {rows} x {cols} x {d}, k = {k}")
+    with torch.no_grad():
+        a, b = queries.detach(), keys.detach()
+        if normalize:
+            a, b = l2_normalize(a), l2_normalize(b)
+        a, b = a.contiguous(), b.contiguous()
+        b_all = dp.all_gather_rows(b, group, sizes=[b_k] * world).contiguous() if world > 1 else b
+        dev = queries.device
+        values = torch.empty(rows, k, dtype=torch.float32, device=dev)
+        indices = torch.empty(rows, k, dtype=torch.int32, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.aecf_retrieval_topk(rows, cols, offset, d, k, 1 if exclude_partner else 0, _ptr(a), _ptr(b_all), _ptr(values),
+                                           _ptr(indices), _ptr(ws), ws_bytes, _stream()), "aecf_retrieval_topk")
+        return RetrievalTopK(values, indices.to(torch.int64))
+
+
 def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMasking], entropy: Optional[torch.Tensor],
                      za: Optional[torch.Tensor] = None, zb: Optional[torch.Tensor] = None, entropy_weight: float = 0.01,
                      contrastive_weight: float = 1.0, temperature: Union[float, torch.Tensor] = 0.07, group=None,

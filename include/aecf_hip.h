@@ -654,6 +654,31 @@ int aecf_retrieval_ranks(int64_t rows, int64_t cols, int64_t row_offset, int32_t
                          int32_t* row_equal, int32_t* col_greater, int32_t* col_equal, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- top-k retrieval: the best k keys of every query (build-defined like the retrieval ranks above: the reference has no
+ * contrastive term and no retrieval evaluation, so there are no reference lines to cite) ----
+ * Rows a [rows,d] against rows b [cols,d], bf16, d % 64 == 0, 64 <= d <= 4096, 1 <= k <= 16, cols < 2^31, any row and column
+ * counts; the rows are taken as given (unit norm or not) and need not pair with each other.  With s_ij = a_i . b_j accumulated
+ * in float32, row i of the outputs holds the k first columns of row i of s in this total order:
+ *   1. the higher score first;  2. among equal scores (-0 == +0) the lower column index first;
+ *   3. every NaN score is equal to every other NaN score and comes after -inf.
+ *   values  [rows,k] float32   the scores, in that order         indices [rows,k] int32   their columns, 0 <= index < cols
+ * The order is total, so the result does not depend on tile, block or rank arrangement.  exclude_partner != 0 removes the one
+ * element (i, row_offset + i) from row i (the row's own partner among the gathered keys) and needs
+ * 0 <= row_offset, row_offset + rows <= cols; with exclude_partner == 0 row_offset is ignored.  k may not exceed the columns
+ * that remain (cols, or cols - 1 with exclude_partner), so no padding ever surfaces.  For the other direction swap a and b.
+ * One logits pass (2 rows cols d MFMA flops) whose epilogue selects, per 256 x 256 tile and row, the tile's best k candidates
+ * -- nothing of size rows x cols is stored -- and one small kernel that merges a row's lists.
+ * Workspace: 8 KP Rp ceil(cols / 256) bytes (KP: k rounded up to a power of two, Rp: rows rounded up to 256), at most 4096 more
+ * for alignment; aecf_retrieval_topk_workspace_bytes answers 0 where the shape or k is not served.  Outputs are WRITTEN; the
+ * same inputs give the same bits.  Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on
+ * the host.  Checks before any launch and before any pointer is read: sizes -- rows, cols, k <= 0, k beyond the columns left,
+ * with exclude_partner row_offset < 0 or row_offset + rows > cols -- (AECF_ERR_BAD_DIMS), then d or k > 16
+ * (AECF_ERR_UNSUPPORTED), then NULL pointers (AECF_ERR_NULL_POINTER), then the workspace size (AECF_ERR_WORKSPACE). */
+size_t aecf_retrieval_topk_workspace_bytes(int64_t rows, int64_t cols, int32_t d, int32_t k);      /* 0: not served */
+int aecf_retrieval_topk(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t k, int32_t exclude_partner,
+                        const void* a, const void* b, float* values, int32_t* indices, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
