@@ -191,6 +191,11 @@ _SYMBOLS = [
     ("aecf_sig_stream_fwd_bwd", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # supervised contrastive loss, streaming: device temperature, int64 labels of the local rows and of the gathered keys
+    ("aecf_supcon_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
+    ("aecf_supcon_fwd_bwd", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     # retrieval ranks: positives, then greater / equal counts per row and per column
     ("aecf_retrieval_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
     ("aecf_retrieval_positive", c_int, [c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -313,6 +313,15 @@ void launch_sig_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, con
                       const void* a, const void* b, float* loss_rows, float* d_bias, float* da, float* db, void* workspace,
                       hipStream_t s);
 
+// Supervised contrastive loss, streaming (aecf_supcon_flash.hip): every key that carries the query's int64 label is a positive
+// beside the partner at row_offset + i; workspace O(rows d).  Writes loss_rows; with dq / dk (both or neither) also the gradients
+// at upstream 1 and dt.d_t (NULL = not wanted).
+bool supcon_flash_supported(int d);
+size_t supcon_flash_workspace_bytes(int64_t rows, int64_t cols, int d);
+void launch_supcon_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef, const void* q,
+                         const void* k, const int64_t* q_labels, const int64_t* k_labels, float* loss_rows, float* dq, float* dk,
+                         void* workspace, hipStream_t s);
+
 // Retrieval ranks of the contrastive views (aecf_retrieval.hip; the counting pass is the EPI_RANK epilogue of the logits GEMM in
 // aecf_nce_gemm.hip): pos[i] = a_i . b_(row_offset + i), then per row / per column how many other logits are greater than / equal
 // to the positive's.  Nothing of size rows x cols exists; the workspace is (rows + cols) x tiles int32 partials.

@@ -501,9 +501,17 @@ class _AllGatherRows(torch.autograd.Function):
             out = torch.empty(world * zc.shape[0], *zc.shape[1:], dtype=z.dtype, device=z.device)
             dist.all_gather_into_tensor(out, zc, group=group)
             return out
-        parts = [torch.empty(s, *zc.shape[1:], dtype=z.dtype, device=z.device) for s in ctx.sizes]
-        dist.all_gather(parts, zc, group=group)
-        return torch.cat(parts, 0)
+        if dist.get_backend(group) == "nccl":
+            parts = [torch.empty(s, *zc.shape[1:], dtype=z.dtype, device=z.device) for s in ctx.sizes]
+            dist.all_gather(parts, zc, group=group)
+            return torch.cat(parts, 0)
+        # other backends (gloo) gather equal shapes only: every rank pads its rows to the longest shard
+        top = max(ctx.sizes)
+        padded = torch.zeros(top, *zc.shape[1:], dtype=z.dtype, device=z.device)
+        padded[:zc.shape[0]] = zc
+        out = torch.empty(world * top, *zc.shape[1:], dtype=z.dtype, device=z.device)
+        dist.all_gather_into_tensor(out, padded, group=group)
+        return torch.cat([out[r * top:r * top + s] for r, s in enumerate(ctx.sizes)], 0)
 
     @staticmethod
     def backward(ctx, dz_all):
@@ -523,7 +531,9 @@ class _AllGatherRows(torch.autograd.Function):
 
 def all_gather_rows(z: torch.Tensor, group=None, sizes=None) -> torch.Tensor:
     """Autograd-aware all-gather of fused embeddings (cross-batch contrastive negatives).  ``sizes`` (every rank's row count,
-    rank order) skips the small exchange + host read that otherwise finds them out on every call."""
+    rank order) skips the small exchange + host read that otherwise finds them out on every call.  Uneven row counts are
+    gathered as they are on "nccl"; every other backend (gloo gathers equal shapes only) pads each shard to the longest one
+    first and drops the padding after the gather: correct, at the cost of one copy."""
     return _AllGatherRows.apply(z, group, sizes)
 
 

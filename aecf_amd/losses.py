@@ -579,6 +579,128 @@ def sigmoid_contrastive(za: torch.Tensor, zb: torch.Tensor, temperature: Union[f
     return scaled + (total - scaled.detach())
 
 
+SUPCON_WIDTHS = (128, 256, 384, 512, 768, 1024)         # the widths aecf_supcon_workspace_bytes answers for
+
+
+def _labels_arg(labels, z: torch.Tensor) -> torch.Tensor:
+    """``labels`` of ``supervised_contrastive``, checked against the embeddings ``z`` [b_local, d]: one int64 or int32 class per
+    local row, on z's device (a negative class = unlabeled).  Returns them as they are: the caller widens int32 on the device."""
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError(f"aecf_amd: labels must be a tensor of int64 or int32 classes, got {type(labels).__name__}")
+    if labels.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"aecf_amd: labels must be int64 or int32, got {labels.dtype}")
+    if labels.dim() != 1 or labels.shape[0] != z.shape[0]:
+        raise ValueError(f"aecf_amd: labels must hold one class per local row, shape ({z.shape[0]},); got {tuple(labels.shape)}")
+    if labels.device != z.device:
+        raise ValueError(f"aecf_amd: the labels live on {labels.device}, the embeddings on {z.device}")
+    return labels
+
+
+class _SupConDirection(torch.autograd.Function):
+    """aecf_supcon_fwd_bwd: sum_i [logsumexp_j(q_i.k_j/T) - mean over the positives of q_i.k_j/T] * coef for local unit-norm q
+    against all k, the positives of row i being its partner ``row_offset + i`` and every key that carries its (non-negative)
+    label.  Modelled on ``_NceDirection``: the forward makes the one call with the gradients at upstream 1 and saves them
+    (float32), the backward multiplies them by the gradient that arrives, on the device.  ``grads`` False (decided by the caller:
+    grad mode is off inside a forward) takes the call's loss-only mode: the same loss bits, no gradient buffers.  The temperature
+    is a one-element float32 device tensor."""
+
+    @staticmethod
+    def forward(ctx, q, k_all, q_labels, k_labels, row_offset, temperature, coef, min_temperature, grads):
+        lib = _lib.load()
+        rows, d = q.shape
+        cols = k_all.shape[0]
+        dev = q.device
+        ws_bytes = lib.aecf_supcon_workspace_bytes(rows, cols, d) if q.dtype == torch.bfloat16 and k_all.dtype == torch.bfloat16 else 0
+        if ws_bytes == 0:
+            raise NotImplementedError(f"aecf_amd: the supervised contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; "
+                                      f"got {q.dtype}, d = {d}")
+        qc, kc = q.detach().contiguous(), k_all.detach().contiguous()
+        lq, lk = q_labels.contiguous(), k_labels.contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        loss_rows = torch.empty(rows, **f32)
+        dq = dk = d_t = None
+        if grads:
+            dq, dk = torch.empty(rows, d, **f32), torch.empty(cols, d, **f32)
+            d_t = torch.empty(1, **f32) if ctx.needs_input_grad[5] else None
+        _lib.check(lib.aecf_supcon_fwd_bwd(rows, cols, int(row_offset), d, _ptr(temperature.detach()), float(min_temperature),
+                                           float(coef), _ptr(qc), _ptr(kc), _ptr(lq), _ptr(lk), _ptr(loss_rows), _ptr(dq), _ptr(dk),
+                                           _ptr(d_t), _ptr(ws), ws_bytes, _stream()), "aecf_supcon_fwd_bwd")
+        ctx.save_for_backward(dq, dk, d_t)
+        ctx.meta = (q.dtype, k_all.dtype, temperature.shape)
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        dq, dk, d_t = ctx.saved_tensors
+        qd, kd, t_shape = ctx.meta
+        g = d_loss.detach().to(torch.float32)
+        g_t = (d_t * g).reshape(t_shape) if d_t is not None else None
+        return (dq * g).to(qd), (dk * g).to(kd), None, None, None, g_t, None, None, None
+
+
+def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Tensor, temperature: Union[float, torch.Tensor] = 0.07,
+                           group=None, min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
+    """Symmetric supervised contrastive loss (Khosla et al. 2020, "L_out") between the local rows of two views, keys from every
+    rank of ``group``: the positives of row i of one view are row i of the other view and every row of the other view that
+    carries the same label,
+
+        L = 0.5 / B_all * sum over both directions and rows i of [ logsumexp_j x_ij - mean_{j in positives(i)} x_ij ],
+        x_ij = na_i . nb_j / max(T, min_temperature)
+
+    ``za``, ``zb``: [b_local, d] bfloat16 on a ROCm device, d in 128, 256, 384, 512, 768, 1024 (anything else is refused: there is
+    no torch fallback).  ``labels``: [b_local] int64 or int32 (widened on the device) on the same device, one class per local
+    row, shared by both views; a negative class marks an unlabeled row, whose only positive is its partner (two unlabeled rows
+    never match).  With all labels negative or all distinct this is ``info_nce``.  Labels carry no gradient.
+
+    Both directions run the streaming kernels (aecf_supcon_fwd_bwd): neither the b_local x b_all logits nor a match mask ever
+    exists; the workspace is O(b_local d).  ``temperature``: a Python float (filled into a one-element device tensor) or a
+    learnable one-element float32 tensor on za's device, read by the kernels as ``max(T, min_temperature)`` with no host read --
+    on one rank the call captures into a graph and replays the current temperature and labels -- and given its gradient by the
+    same kernels (zero where ``T < min_temperature``; any positive ``min_temperature`` is legal).  Under ``torch.no_grad()``, or
+    when no input requires a gradient, only the loss passes run and no gradient buffer is allocated.
+
+    Data parallel: both views, the labels and the row counts are all-gathered; the convention is ``info_nce``'s -- the returned
+    value is the global loss on every rank and the local term carries ``world`` for an averaging gradient reduce."""
+    _require_device(za, "za")
+    _require_device(zb, "zb")
+    if za.shape != zb.shape or za.dim() != 2:
+        raise ValueError(f"supervised_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+    labels = _labels_arg(labels, za)
+    if za.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16 or za.shape[1] not in SUPCON_WIDTHS:
+        raise NotImplementedError(f"aecf_amd: the supervised contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; got "
+                                  f"{za.dtype} and {zb.dtype}, d = {za.shape[1]}")
+    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
+        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
+    t = _temperature_arg(temperature, za, min_temperature)
+    if not isinstance(t, torch.Tensor):
+        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    rank, world = dp.world_info(group)
+    lab = labels.detach().to(torch.int64)
+    na, nb = l2_normalize(za), l2_normalize(zb)
+    if world > 1:
+        n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
+        got = [torch.zeros_like(n) for _ in range(world)]
+        torch.distributed.all_gather(got, n, group=group)
+        sizes = [int(v.item()) for v in got]
+        offset = sum(sizes[:rank])
+        na_all, nb_all = dp.all_gather_rows(na, group, sizes=sizes), dp.all_gather_rows(nb, group, sizes=sizes)
+        lab_all = dp.all_gather_rows(lab, group, sizes=sizes)
+    else:
+        offset, na_all, nb_all, lab_all = 0, na, nb, lab
+    coef = 0.5 / float(nb_all.shape[0])
+    grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb, t))
+    l_ab = _SupConDirection.apply(na, nb_all, lab, lab_all, offset, t, coef, float(min_temperature), grads)
+    l_ba = _SupConDirection.apply(nb, na_all, lab, lab_all, offset, t, coef, float(min_temperature), grads)
+    share = l_ab + l_ba                  # this rank's rows' share of the global objective
+    if world == 1:
+        return share
+    total = share.detach().clone()
+    torch.distributed.all_reduce(total, group=group)
+    scaled = share * world
+    return scaled + (total - scaled.detach())
+
+
 class RetrievalRanks(NamedTuple):
     """What ``retrieval_ranks`` returns: for each of this rank's rows, how many OTHER rows of the other view score higher than
     (``greater``) or exactly as high as (``equal``) its partner; int32 [b_local] each."""
@@ -748,18 +870,26 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
                      za: Optional[torch.Tensor] = None, zb: Optional[torch.Tensor] = None, entropy_weight: float = 0.01,
                      contrastive_weight: float = 1.0, temperature: Union[float, torch.Tensor] = 0.07, group=None,
                      min_temperature: float = MIN_TEMPERATURE, contrastive: str = "info_nce",
-                     bias: Union[None, float, torch.Tensor] = None, low_memory: Optional[bool] = None) -> torch.Tensor:
+                     bias: Union[None, float, torch.Tensor] = None, low_memory: Optional[bool] = None,
+                     labels: Optional[torch.Tensor] = None) -> torch.Tensor:
     """task + entropy_weight * entropy_loss(entropy) [ref README.md:205-208] + contrastive_weight * info_nce(za, zb)
     (``temperature`` / ``min_temperature``: as for ``info_nce``).  ``contrastive="sigmoid"`` takes ``sigmoid_contrastive(za, zb,
     temperature, bias)`` as the contrastive term instead (``bias``: None = its default of -10; ``low_memory``: its choice of
-    implementation, ignored for ``info_nce``)."""
-    if contrastive not in ("info_nce", "sigmoid"):
-        raise ValueError(f"aecf_amd: contrastive must be 'info_nce' or 'sigmoid', got {contrastive!r}")
+    implementation, ignored for ``info_nce``); ``contrastive="supervised"`` takes ``supervised_contrastive(za, zb, labels,
+    temperature)`` and is the only form that takes ``labels``."""
+    if contrastive not in ("info_nce", "sigmoid", "supervised"):
+        raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid' or 'supervised', got {contrastive!r}")
+    if contrastive == "supervised" and labels is None:
+        raise ValueError("aecf_amd: contrastive='supervised' needs labels")
+    if contrastive != "supervised" and labels is not None:
+        raise ValueError(f"aecf_amd: labels are taken by contrastive='supervised' only, got contrastive={contrastive!r}")
     total = task_loss
     if masking is not None and entropy is not None:
         total = _plus(total, entropy_weight * masking.entropy_loss(entropy))
     if za is not None and zb is not None:
-        if contrastive == "sigmoid":
+        if contrastive == "supervised":
+            term = supervised_contrastive(za, zb, labels, temperature, group, min_temperature)
+        elif contrastive == "sigmoid":
             term = sigmoid_contrastive(za, zb, temperature, -10.0 if bias is None else bias, group, min_temperature, low_memory)
         else:
             term = info_nce(za, zb, temperature, group, min_temperature)

@@ -626,6 +626,42 @@ int aecf_sig_stream_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int3
                             float* loss_rows, float* d_bias, float* d_temperature, float* da, float* db,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- supervised contrastive loss (Khosla et al. 2020, the "L_out" form; build-defined like the InfoNCE term) ----
+ * One direction: local unit-norm bf16 rows q [rows,d] (global indices row_offset .. row_offset + rows) against all gathered
+ * unit-norm bf16 rows k [cols,d] of the other view, d in {128, 256, 384, 512, 768, 1024}, with int64 DEVICE labels q_labels [rows]
+ * and k_labels [cols].  Every key that carries the query's label is a positive beside the partner:
+ *   match(i, j) = (j == row_offset + i) or (q_labels[i] >= 0 and q_labels[i] == k_labels[j])
+ *                 a negative label = unlabeled: the partner only, and two unlabeled rows never match; all 64 bits are compared;
+ *                 the partner counts by INDEX, whatever the two labels say
+ *   n_i    = sum_j match(i, j)   (>= 1)        Tc = max(*temperature, min_temperature)   (a DEVICE float32 scalar, as above)
+ *   x_ij   = (q_i . k_j) / Tc                  lse_i = logsumexp_j x_ij
+ *   loss_rows[i] = lse_i - (1 / n_i) sum_j match(i, j) x_ij                  float32 [rows], WITHOUT coef
+ *   G      = softmax_j(x) - match / n_i
+ *   dq = coef/Tc G k   float32 [rows,d]        dk = coef/Tc G^T q   float32 [cols,d] (this rank's share)        at upstream 1
+ *   d_temperature[0] = -(1/Tc) sum_i q_i . dq_i    (0 where *temperature < min_temperature; WRITTEN, may be NULL = not wanted)
+ * With every label negative, or all labels distinct, this is the InfoNCE direction of aecf_nce_fwd_bwd_dt.
+ * Three passes of the streaming loop, nothing of size rows x cols anywhere (neither logits nor a match mask): statistics
+ * (running maximum and sum, the count and the float32 sum of the matched x per row; the key range split over blocks, the live
+ * splits merged in a fixed order into lse, 1 / n and loss_rows), then dq (the same split; weights coef/Tc (exp(x - lse) - match /
+ * n), partial sums per live split added in a fixed order) and dk (one pass, no partials).  The normaliser is known before either
+ * gradient pass, so no accumulator is ever rescaled.  A weight is rounded to bf16 once, as the operand of the gradient products.
+ * No float atomics: the same inputs give the same bits.
+ * Loss-only mode: dq == dk == NULL runs the statistics and the merge alone; d_temperature must then be NULL too; loss_rows has the
+ * same bits as with gradients.
+ * Workspace, in order, with splits the rule's count (<= 64, does not grow with cols beyond that): [splits, rows, d] float32 dq
+ * partials | [splits, rows] m | l | count (int32) | matched-x sums | [rows] lse | 1 / n | q_i . dq_i, + 1024 bytes:
+ * (splits * rows * (d + 4) + 3 * rows) * 4 + 1024.  aecf_supcon_workspace_bytes answers 0 where the width is not served.
+ * Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host (the call captures into a
+ * graph), nothing read from the workspace before it is written.  Checks before any launch: sizes (rows, cols, d > 0,
+ * cols < 2^31, min_temperature > 0, 0 <= row_offset, row_offset + rows <= cols: AECF_ERR_BAD_DIMS), then the width (AECF_ERR_UNSUPPORTED),
+ * then NULL among temperature, q, k, q_labels, k_labels, loss_rows, workspace, exactly one of dq / dk NULL, or d_temperature
+ * given without dq / dk (AECF_ERR_NULL_POINTER), then the workspace size (AECF_ERR_WORKSPACE). */
+size_t aecf_supcon_workspace_bytes(int64_t rows, int64_t cols, int32_t d);      /* 0: not served */
+int aecf_supcon_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                        float min_temperature, float coef, const void* q, const void* k, const int64_t* q_labels,
+                        const int64_t* k_labels, float* loss_rows, float* dq, float* dk, float* d_temperature,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- retrieval ranks of the contrastive views (build-defined like the contrastive terms they evaluate: the reference has no
  * contrastive term and no retrieval evaluation, so there are no reference lines to cite) ----
  * Local rows a [rows,d] (global indices row_offset .. row_offset + rows) against all gathered rows b [cols,d] of the other view,
