@@ -17,6 +17,9 @@ AECF_ABI_VERSION = 10
 AECF_BF16 = 0
 AECF_F32 = 1
 AECF_F16 = 2
+AECF_SETS_U8 = 3            # aecf_label_sets_pack: one byte per class (torch bool / uint8)
+AECF_SETS_OVERLAP = 0
+AECF_SETS_JACCARD = 1
 AECF_PRECISE = 1
 AECF_DRAW_UNIFORMS = 2
 AECF_HILO_GRADS = 4
@@ -196,6 +199,12 @@ _SYMBOLS = [
     ("aecf_supcon_fwd_bwd", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # multi-label supervised contrastive loss: uint64 class sets in place of the labels, a weighting; the packing of multi-hot rows
+    ("aecf_supcon_ml_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
+    ("aecf_supcon_ml_fwd_bwd", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("aecf_label_sets_pack", c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     # retrieval ranks: positives, then greater / equal counts per row and per column
     ("aecf_retrieval_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
     ("aecf_retrieval_positive", c_int, [c_int64, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

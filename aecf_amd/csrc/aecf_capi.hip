@@ -951,6 +951,39 @@ int aecf_supcon_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t 
     return launch_status();
 }
 
+// ---- multi-label supervised contrastive loss (include/aecf_hip.h, "multi-label supervised contrastive loss")
+
+size_t aecf_supcon_ml_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !supcon_ml_flash_supported(d)) return 0;
+    return supcon_ml_flash_workspace_bytes(rows, cols, d);
+}
+
+int aecf_supcon_ml_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                           float coef, const void* q, const void* k, const uint64_t* q_sets, const uint64_t* k_sets, int32_t weighting,
+                           float* loss_rows, float* dq, float* dk, float* d_temperature, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!supcon_ml_flash_supported(d)) return AECF_ERR_UNSUPPORTED;
+    if (weighting != AECF_SETS_OVERLAP && weighting != AECF_SETS_JACCARD) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !q || !k || !q_sets || !k_sets || !loss_rows || !workspace || (dq == nullptr) != (dk == nullptr))
+        return AECF_ERR_NULL_POINTER;
+    if (!dq && d_temperature) return AECF_ERR_NULL_POINTER;      // the loss-only mode forms no gradient to take dT from
+    if (workspace_bytes < supcon_ml_flash_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    launch_supcon_ml_flash(rows, cols, row_offset, d, dt, coef, q, k, q_sets, k_sets, weighting == AECF_SETS_JACCARD ? 1 : 0,
+                           loss_rows, dq, dk, workspace, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_label_sets_pack(int64_t rows, int32_t classes, int32_t kind, const void* multi_hot, uint64_t* sets, void* stream) {
+    if (rows <= 0 || classes <= 0 || classes > 64) return AECF_ERR_BAD_DIMS;
+    if (kind != AECF_BF16 && kind != AECF_F32 && kind != AECF_F16 && kind != AECF_SETS_U8) return AECF_ERR_UNSUPPORTED;
+    if (!multi_hot || !sets) return AECF_ERR_NULL_POINTER;
+    launch_label_sets_pack(rows, classes, kind, multi_hot, sets, (hipStream_t)stream);
+    return launch_status();
+}
+
 // ---- retrieval ranks of the contrastive views (include/aecf_hip.h, "retrieval ranks")
 
 size_t aecf_retrieval_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {

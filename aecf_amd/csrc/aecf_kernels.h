@@ -322,6 +322,17 @@ void launch_supcon_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, 
                          const void* k, const int64_t* q_labels, const int64_t* k_labels, float* loss_rows, float* dq, float* dk,
                          void* workspace, hipStream_t s);
 
+// Multi-label supervised contrastive loss, streaming (aecf_supcon_ml_flash.hip): a set of classes per row as one uint64 (bit c =
+// class c); a key counts with weight 1 (the partner), [sets overlap] (jaccard 0) or |and| / |or| (jaccard 1).  The same passes,
+// workspace layout and outputs as launch_supcon_flash.  launch_label_sets_pack: multi-hot rows [rows, classes <= 64] of kind
+// 0 bf16, 1 float32, 2 float16, 3 uint8 -> the words (value != 0 = member).
+bool supcon_ml_flash_supported(int d);
+size_t supcon_ml_flash_workspace_bytes(int64_t rows, int64_t cols, int d);
+void launch_supcon_ml_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef, const void* q,
+                            const void* k, const uint64_t* q_sets, const uint64_t* k_sets, int jaccard, float* loss_rows, float* dq,
+                            float* dk, void* workspace, hipStream_t s);
+void launch_label_sets_pack(int64_t rows, int classes, int kind, const void* multi_hot, uint64_t* sets, hipStream_t s);
+
 // Retrieval ranks of the contrastive views (aecf_retrieval.hip; the counting pass is the EPI_RANK epilogue of the logits GEMM in
 // aecf_nce_gemm.hip): pos[i] = a_i . b_(row_offset + i), then per row / per column how many other logits are greater than / equal
 // to the positive's.  Nothing of size rows x cols exists; the workspace is (rows + cols) x tiles int32 partials.

@@ -701,6 +701,170 @@ def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Ten
     return scaled + (total - scaled.detach())
 
 
+SET_CLASSES = 64                                        # one uint64 per row: the most classes a label set can name
+SET_WEIGHTINGS = {"overlap": _lib.AECF_SETS_OVERLAP, "jaccard": _lib.AECF_SETS_JACCARD}
+_SET_KINDS = {torch.bool: _lib.AECF_SETS_U8, torch.uint8: _lib.AECF_SETS_U8, torch.bfloat16: _lib.AECF_BF16,
+              torch.float16: _lib.AECF_F16, torch.float32: _lib.AECF_F32}
+
+
+def _multi_hot_arg(multi_hot) -> torch.Tensor:
+    """a multi-hot tensor [b, C] of ``pack_label_sets``, checked: bool, uint8, bfloat16, float16 or float32, 1 <= C <= 64"""
+    if not isinstance(multi_hot, torch.Tensor):
+        raise TypeError(f"aecf_amd: label sets must be a tensor, got {type(multi_hot).__name__}")
+    if multi_hot.dtype not in _SET_KINDS:
+        raise TypeError(f"aecf_amd: multi-hot label sets must be bool, uint8, bfloat16, float16 or float32, got {multi_hot.dtype}")
+    if multi_hot.dim() != 2 or multi_hot.shape[0] < 1 or multi_hot.shape[1] < 1:
+        raise ValueError(f"aecf_amd: multi-hot label sets must have shape [b, C] with b, C >= 1, got {tuple(multi_hot.shape)}")
+    if multi_hot.shape[1] > SET_CLASSES:
+        raise NotImplementedError(f"aecf_amd: label sets hold at most {SET_CLASSES} classes (one 64-bit mask per row), got "
+                                  f"C = {multi_hot.shape[1]}")
+    return multi_hot
+
+
+def _label_sets_arg(label_sets, z: torch.Tensor) -> torch.Tensor:
+    """``label_sets`` of ``multilabel_contrastive``, checked against the embeddings ``z`` [b_local, d]: ready int64 masks
+    [b_local] (bit c = class c) or a multi-hot tensor [b_local, C <= 64], on z's device.  Returns them as they are: the caller
+    packs a multi-hot tensor on the device."""
+    if not isinstance(label_sets, torch.Tensor):
+        raise TypeError(f"aecf_amd: label sets must be a tensor, got {type(label_sets).__name__}")
+    if label_sets.dim() == 1:
+        if label_sets.dtype != torch.int64:
+            raise TypeError(f"aecf_amd: ready label sets (one mask per row) must be int64, got {label_sets.dtype}")
+    else:
+        _multi_hot_arg(label_sets)
+    if label_sets.shape[0] != z.shape[0]:
+        raise ValueError(f"aecf_amd: label sets must hold one set per local row ({z.shape[0]} rows), got shape {tuple(label_sets.shape)}")
+    if label_sets.device != z.device:
+        raise ValueError(f"aecf_amd: the label sets live on {label_sets.device}, the embeddings on {z.device}")
+    return label_sets
+
+
+def pack_label_sets(multi_hot: torch.Tensor) -> torch.Tensor:
+    """Multi-hot rows ``[b, C]`` (bool, uint8, bfloat16, float16 or float32 on a ROCm device, C <= 64; nonzero = member) ->
+    ``[b]`` int64 masks, bit c = class c (aecf_label_sets_pack: one wave per row, one ballot).  Class 63 is the sign bit of the
+    int64: a row that holds it reads as a negative number, which is expected -- the kernels take the word as unsigned."""
+    _multi_hot_arg(multi_hot)
+    _require_device(multi_hot, "multi_hot")
+    rows, classes = multi_hot.shape
+    src = multi_hot.detach().contiguous()
+    sets = torch.empty(rows, dtype=torch.int64, device=multi_hot.device)
+    _lib.check(_lib.load().aecf_label_sets_pack(rows, classes, _SET_KINDS[multi_hot.dtype], _ptr(src), _ptr(sets), _stream()),
+               "aecf_label_sets_pack")
+    return sets
+
+
+class _SupConMlDirection(torch.autograd.Function):
+    """aecf_supcon_ml_fwd_bwd: sum_i [logsumexp_j(q_i.k_j/T) - the w-weighted mean of q_i.k_j/T] * coef for local unit-norm q
+    against all k, w(i, j) = 1 for the partner ``row_offset + i`` and the overlap or Jaccard weight of the two rows' class sets
+    (int64 masks) otherwise.  ``_SupConDirection`` with sets for labels: the forward makes the one call with the gradients at
+    upstream 1 and saves them (float32), the backward multiplies them by the gradient that arrives, on the device; ``grads``
+    False takes the call's loss-only mode.  The temperature is a one-element float32 device tensor."""
+
+    @staticmethod
+    def forward(ctx, q, k_all, q_sets, k_sets, weighting, row_offset, temperature, coef, min_temperature, grads):
+        lib = _lib.load()
+        rows, d = q.shape
+        cols = k_all.shape[0]
+        dev = q.device
+        ws_bytes = lib.aecf_supcon_ml_workspace_bytes(rows, cols, d) if q.dtype == torch.bfloat16 and k_all.dtype == torch.bfloat16 else 0
+        if ws_bytes == 0:
+            raise NotImplementedError(f"aecf_amd: the multi-label contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; "
+                                      f"got {q.dtype}, d = {d}")
+        qc, kc = q.detach().contiguous(), k_all.detach().contiguous()
+        sq, sk = q_sets.contiguous(), k_sets.contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        loss_rows = torch.empty(rows, **f32)
+        dq = dk = d_t = None
+        if grads:
+            dq, dk = torch.empty(rows, d, **f32), torch.empty(cols, d, **f32)
+            d_t = torch.empty(1, **f32) if ctx.needs_input_grad[6] else None
+        _lib.check(lib.aecf_supcon_ml_fwd_bwd(rows, cols, int(row_offset), d, _ptr(temperature.detach()), float(min_temperature),
+                                              float(coef), _ptr(qc), _ptr(kc), _ptr(sq), _ptr(sk), int(weighting), _ptr(loss_rows),
+                                              _ptr(dq), _ptr(dk), _ptr(d_t), _ptr(ws), ws_bytes, _stream()), "aecf_supcon_ml_fwd_bwd")
+        ctx.save_for_backward(dq, dk, d_t)
+        ctx.meta = (q.dtype, k_all.dtype, temperature.shape)
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        dq, dk, d_t = ctx.saved_tensors
+        qd, kd, t_shape = ctx.meta
+        g = d_loss.detach().to(torch.float32)
+        g_t = (d_t * g).reshape(t_shape) if d_t is not None else None
+        return (dq * g).to(qd), (dk * g).to(kd), None, None, None, None, g_t, None, None, None
+
+
+def multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets: torch.Tensor, weighting: str = "overlap",
+                           temperature: Union[float, torch.Tensor] = 0.07, group=None,
+                           min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
+    """Symmetric multi-label supervised contrastive loss between the local rows of two views, keys from every rank of ``group``:
+    every row carries a SET of classes, and a row of the other view counts as a positive of row i with a weight
+
+        w(i, j) = 1 for the partner (row i of the other view, by index, whatever the sets say), else
+                  [A_i and B_j share a class]          weighting="overlap"
+                  |A_i & B_j| / |A_i | B_j|            weighting="jaccard"
+
+        L = 0.5 / B_all * sum over both directions and rows i of [ logsumexp_j x_ij - sum_j w(i, j) x_ij / sum_j w(i, j) ],
+        x_ij = na_i . nb_j / max(T, min_temperature)
+
+    ``za``, ``zb``: [b_local, d] bfloat16 on a ROCm device, d in 128, 256, 384, 512, 768, 1024 (anything else is refused: there is
+    no torch fallback).  ``label_sets``, shared by both views, on the same device: a multi-hot tensor [b_local, C] of bool, uint8,
+    bfloat16, float16 or float32 with C <= 64 (nonzero = member; packed on the device by ``pack_label_sets``), or ready int64
+    masks [b_local] (bit c = class c; class 63 is the sign bit).  An empty set marks an unlabeled row: its only positive is its
+    partner and it is nobody's positive by label.  With one-hot sets both weightings are ``supervised_contrastive``; with all
+    sets empty or pairwise disjoint they are ``info_nce``.  Sets carry no gradient.
+
+    Both directions run the streaming kernels (aecf_supcon_ml_fwd_bwd): neither the b_local x b_all logits nor a weight matrix
+    ever exists; the workspace is O(b_local d).  ``temperature``: a Python float or a learnable one-element float32 tensor on
+    za's device, read as ``max(T, min_temperature)`` with no host read -- on one rank the call captures into a graph and replays
+    the current temperature and sets -- and given its gradient by the same kernels.  Under ``torch.no_grad()``, or when no input
+    requires a gradient, only the loss passes run and no gradient buffer is allocated.
+
+    Data parallel: both views, the packed sets and the row counts are all-gathered; the convention is ``info_nce``'s -- the
+    returned value is the global loss on every rank and the local term carries ``world`` for an averaging gradient reduce."""
+    if weighting not in SET_WEIGHTINGS:
+        raise ValueError(f"aecf_amd: weighting must be 'overlap' or 'jaccard', got {weighting!r}")
+    _require_device(za, "za")
+    _require_device(zb, "zb")
+    if za.shape != zb.shape or za.dim() != 2:
+        raise ValueError(f"multilabel_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+    label_sets = _label_sets_arg(label_sets, za)
+    if za.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16 or za.shape[1] not in SUPCON_WIDTHS:
+        raise NotImplementedError(f"aecf_amd: the multi-label contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; got "
+                                  f"{za.dtype} and {zb.dtype}, d = {za.shape[1]}")
+    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
+        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
+    t = _temperature_arg(temperature, za, min_temperature)
+    if not isinstance(t, torch.Tensor):
+        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    rank, world = dp.world_info(group)
+    sets = label_sets.detach() if label_sets.dim() == 1 else pack_label_sets(label_sets)
+    na, nb = l2_normalize(za), l2_normalize(zb)
+    if world > 1:
+        n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
+        got = [torch.zeros_like(n) for _ in range(world)]
+        torch.distributed.all_gather(got, n, group=group)
+        sizes = [int(v.item()) for v in got]
+        offset = sum(sizes[:rank])
+        na_all, nb_all = dp.all_gather_rows(na, group, sizes=sizes), dp.all_gather_rows(nb, group, sizes=sizes)
+        sets_all = dp.all_gather_rows(sets, group, sizes=sizes)
+    else:
+        offset, na_all, nb_all, sets_all = 0, na, nb, sets
+    coef = 0.5 / float(nb_all.shape[0])
+    w = SET_WEIGHTINGS[weighting]
+    grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb, t))
+    l_ab = _SupConMlDirection.apply(na, nb_all, sets, sets_all, w, offset, t, coef, float(min_temperature), grads)
+    l_ba = _SupConMlDirection.apply(nb, na_all, sets, sets_all, w, offset, t, coef, float(min_temperature), grads)
+    share = l_ab + l_ba                  # this rank's rows' share of the global objective
+    if world == 1:
+        return share
+    total = share.detach().clone()
+    torch.distributed.all_reduce(total, group=group)
+    scaled = share * world
+    return scaled + (total - scaled.detach())
+
+
 class RetrievalRanks(NamedTuple):
     """What ``retrieval_ranks`` returns: for each of this rank's rows, how many OTHER rows of the other view score higher than
     (``greater``) or exactly as high as (``equal``) its partner; int32 [b_local] each."""
@@ -871,23 +1035,29 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
                      contrastive_weight: float = 1.0, temperature: Union[float, torch.Tensor] = 0.07, group=None,
                      min_temperature: float = MIN_TEMPERATURE, contrastive: str = "info_nce",
                      bias: Union[None, float, torch.Tensor] = None, low_memory: Optional[bool] = None,
-                     labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     labels: Optional[torch.Tensor] = None, label_weighting: str = "overlap") -> torch.Tensor:
     """task + entropy_weight * entropy_loss(entropy) [ref README.md:205-208] + contrastive_weight * info_nce(za, zb)
     (``temperature`` / ``min_temperature``: as for ``info_nce``).  ``contrastive="sigmoid"`` takes ``sigmoid_contrastive(za, zb,
     temperature, bias)`` as the contrastive term instead (``bias``: None = its default of -10; ``low_memory``: its choice of
     implementation, ignored for ``info_nce``); ``contrastive="supervised"`` takes ``supervised_contrastive(za, zb, labels,
-    temperature)`` and is the only form that takes ``labels``."""
-    if contrastive not in ("info_nce", "sigmoid", "supervised"):
-        raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid' or 'supervised', got {contrastive!r}")
-    if contrastive == "supervised" and labels is None:
-        raise ValueError("aecf_amd: contrastive='supervised' needs labels")
-    if contrastive != "supervised" and labels is not None:
-        raise ValueError(f"aecf_amd: labels are taken by contrastive='supervised' only, got contrastive={contrastive!r}")
+    temperature)`` and ``contrastive="multilabel"`` takes ``multilabel_contrastive(za, zb, labels, label_weighting,
+    temperature)`` with ``labels`` the label sets (multi-hot rows or int64 masks); these two are the only forms that take
+    ``labels``, and ``label_weighting`` ("overlap" or "jaccard") is read by the multi-label form alone."""
+    if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel"):
+        raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid', 'supervised' or 'multilabel', got {contrastive!r}")
+    if contrastive in ("supervised", "multilabel") and labels is None:
+        raise ValueError(f"aecf_amd: contrastive={contrastive!r} needs labels")
+    if contrastive not in ("supervised", "multilabel") and labels is not None:
+        raise ValueError(f"aecf_amd: labels are taken by contrastive='supervised' and 'multilabel' only, got contrastive={contrastive!r}")
+    if label_weighting not in SET_WEIGHTINGS:
+        raise ValueError(f"aecf_amd: label_weighting must be 'overlap' or 'jaccard', got {label_weighting!r}")
     total = task_loss
     if masking is not None and entropy is not None:
         total = _plus(total, entropy_weight * masking.entropy_loss(entropy))
     if za is not None and zb is not None:
-        if contrastive == "supervised":
+        if contrastive == "multilabel":
+            term = multilabel_contrastive(za, zb, labels, label_weighting, temperature, group, min_temperature)
+        elif contrastive == "supervised":
             term = supervised_contrastive(za, zb, labels, temperature, group, min_temperature)
         elif contrastive == "sigmoid":
             term = sigmoid_contrastive(za, zb, temperature, -10.0 if bias is None else bias, group, min_temperature, low_memory)

@@ -662,6 +662,51 @@ int aecf_supcon_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t 
                         const int64_t* k_labels, float* loss_rows, float* dq, float* dk, float* d_temperature,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- multi-label supervised contrastive loss (build-defined like the supervised term above, whose contract this one repeats) ----
+ * One direction as above, with a SET of classes per row instead of one class: q_sets [rows] and k_sets [cols] are DEVICE arrays of
+ * one uint64 per row, bit c = class c, C <= 64 classes (aecf_label_sets_pack makes them from multi-hot rows).  A key counts with a
+ * weight in [0, 1]:
+ *   A_i = q_sets[i], B_j = k_sets[j]
+ *   w(i, j) = 1                                    if j == row_offset + i   (the partner counts by INDEX, whatever the sets say)
+ *           = [ A_i & B_j != 0 ]                   weighting AECF_SETS_OVERLAP (0)
+ *           = popcount(A_i & B_j) / popcount(A_i | B_j)   weighting AECF_SETS_JACCARD (1): all 64 bits, a float32 division;
+ *                                                  0 when the union is empty
+ *   an empty set = an unlabeled row: the partner only, and it is nobody's positive by label
+ *   W_i    = sum_j w(i, j)   (>= 1)        Tc = max(*temperature, min_temperature)   (a DEVICE float32 scalar, as above)
+ *   x_ij   = (q_i . k_j) / Tc              lse_i = logsumexp_j x_ij
+ *   loss_rows[i] = lse_i - (1 / W_i) sum_j w(i, j) x_ij                      float32 [rows], WITHOUT coef
+ *   G      = softmax_j(x) - w / W_i
+ *   dq = coef/Tc G k   float32 [rows,d]        dk = coef/Tc G^T q   float32 [cols,d] (this rank's share)        at upstream 1
+ *   d_temperature[0] = -(1/Tc) sum_i q_i . dq_i    (0 where *temperature < min_temperature; WRITTEN, may be NULL = not wanted)
+ * With one-hot sets (class c < 64 <-> bit c, unlabeled <-> 0) both weightings give the bits of aecf_supcon_fwd_bwd; with all sets
+ * empty or pairwise disjoint they are the InfoNCE direction.
+ * The three passes of aecf_supcon_fwd_bwd with the weight in place of the match: the statistics pass keeps float32 sums of w and
+ * of w x per row (merged over the live splits in a fixed order into lse, 1 / W and loss_rows); the gradient passes use the weights
+ * coef/Tc (exp(x - lse) - w / W), rounded to bf16 once.  No float atomics: the same inputs give the same bits.
+ * Loss-only mode: dq == dk == NULL runs the statistics and the merge alone; d_temperature must then be NULL too; loss_rows has the
+ * same bits as with gradients.
+ * Workspace: the layout and size of aecf_supcon_workspace_bytes, the count slot holding the float32 weight sum:
+ * (splits * rows * (d + 4) + 3 * rows) * 4 + 1024.  aecf_supcon_ml_workspace_bytes answers 0 where the width is not served.
+ * Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host (the call captures into a
+ * graph), nothing read from the workspace before it is written.  Checks before any launch: sizes (rows, cols, d > 0,
+ * cols < 2^31, min_temperature > 0, 0 <= row_offset, row_offset + rows <= cols: AECF_ERR_BAD_DIMS), then the width and the weighting
+ * (AECF_ERR_UNSUPPORTED), then NULL among temperature, q, k, q_sets, k_sets, loss_rows, workspace, exactly one of dq / dk NULL, or
+ * d_temperature given without dq / dk (AECF_ERR_NULL_POINTER), then the workspace size (AECF_ERR_WORKSPACE).
+ *
+ * aecf_label_sets_pack: multi_hot is a contiguous DEVICE array [rows, classes], 1 <= classes <= 64, of kind AECF_BF16, AECF_F32,
+ * AECF_F16 or AECF_SETS_U8 (one byte per class: torch bool / uint8); sets[i] gets bit c where multi_hot[i, c] != 0 (-0.0 is no
+ * member), the bits from `classes` up stay 0.  One wave per row, one 64-lane ballot.  Checks: rows <= 0 or classes outside 1..64
+ * (AECF_ERR_BAD_DIMS), then the kind (AECF_ERR_UNSUPPORTED), then NULL (AECF_ERR_NULL_POINTER). */
+#define AECF_SETS_OVERLAP 0
+#define AECF_SETS_JACCARD 1
+#define AECF_SETS_U8 3
+size_t aecf_supcon_ml_workspace_bytes(int64_t rows, int64_t cols, int32_t d);      /* 0: not served */
+int aecf_supcon_ml_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                           float min_temperature, float coef, const void* q, const void* k, const uint64_t* q_sets,
+                           const uint64_t* k_sets, int32_t weighting, float* loss_rows, float* dq, float* dk,
+                           float* d_temperature, void* workspace, size_t workspace_bytes, void* stream);
+int aecf_label_sets_pack(int64_t rows, int32_t classes, int32_t kind, const void* multi_hot, uint64_t* sets, void* stream);
+
 /* ---- retrieval ranks of the contrastive views (build-defined like the contrastive terms they evaluate: the reference has no
  * contrastive term and no retrieval evaluation, so there are no reference lines to cite) ----
  * Local rows a [rows,d] (global indices row_offset .. row_offset + rows) against all gathered rows b [cols,d] of the other view,
