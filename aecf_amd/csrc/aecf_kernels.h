@@ -322,6 +322,19 @@ void launch_supcon_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, 
                          const void* k, const int64_t* q_labels, const int64_t* k_labels, float* loss_rows, float* dq, float* dk,
                          void* workspace, hipStream_t s);
 
+// Supervised contrastive loss on the tile GEMMs (aecf_nce_gemm.hip): both directions of the symmetric loss from ONE block of
+// logits, labels shared by the two views.  The logits pass (EPI_SUP) is InfoNCE's plus the count and the float32 raw-score sum of
+// the label matches per row and per column; col_stats [3][cols] (column sums of E | counts | matched sums) is what ranks exchange.
+bool supcon_gemm_supported(int d, float min_temperature, int64_t cols);
+size_t supcon_gemm_workspace_bytes(int64_t rows, int64_t cols, int d);
+void launch_supcon_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a, const void* b,
+                              const int64_t* row_labels, const int64_t* col_labels, void* workspace, float* col_stats, hipStream_t s);
+void launch_supcon_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a, const void* b,
+                             const float* col_stats, void* workspace, float* loss_rows, hipStream_t s);
+void launch_supcon_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef, const void* a,
+                              const void* b, const int64_t* row_labels, const int64_t* col_labels, void* workspace,
+                              const float* upstream, int out_bf16, void* da, void* db, hipStream_t s);
+
 // Multi-label supervised contrastive loss, streaming (aecf_supcon_ml_flash.hip): a set of classes per row as one uint64 (bit c =
 // class c); a key counts with weight 1 (the partner), [sets overlap] (jaccard 0) or |and| / |or| (jaccard 1).  The same passes,
 // workspace layout and outputs as launch_supcon_flash.  launch_label_sets_pack: multi-hot rows [rows, classes <= 64] of kind

@@ -57,6 +57,24 @@
 // merges the 4 waves' lists into the tile's list [k] of the workspace [n_tiles][Rp][KP].  The accumulators are consumed rt by
 // rt: 32 key registers at a time next to them, no scratch.  The excluded partner and the padding become the sentinel -- a
 // select that only the tiles holding such elements run, as above.
+//
+// The symmetric supervised contrastive loss (aecf_supcon_sym_pass1 / _loss / _grads) is a sixth epilogue, EPI_SUP, plus label-aware
+// variants of the three small kernels.  Both views share the labels, so one match matrix m_ij = [j = off + i] or [lr_i = lc_j >= 0]
+// serves both directions, and the positives of the labels are a sparse correction to InfoNCE's weights:
+//   W_ij = ct (E_ij (1/l_i + 1/c_j) - m_ij (1/n_i + 1/nc_j)),   n_i = sum_j m_ij,  nc_j = sum_i m_ij.
+// EPI_SUP is EPI_EXP_DT to the bit (E, its row and column sums) and adds, per row and per column of the tile, the count and the
+// float32 sum of the raw accumulators of the matches BY LABEL -- the partner is excluded (tiles on its band and on the ragged edge
+// take the block-uniform `special` branch) and joins later from its own float32 dot, as in InfoNCE.  A lane reads the labels of
+// its 8 rows and 16 columns once, in front of the exponentials, and keeps them as 32-bit keys (24 registers; the int64 labels
+// themselves would take 48 beside the 128 accumulators and spill): the tile is searched with two VALU operations per element
+// and no compare mask, and only a row group with a key hit somewhere in the wave reads its labels again, compares all 64 bits and
+// sums -- at about 6 matches in 65536 columns most groups skip it, and a skipped group stores the zeros it would have summed.
+// The column sums of the matches gather in LDS, in the slots of the lanes that own them, not in 32 more registers.
+// The partials leave as the sums of E do ([n_tiles][Rp] / [m_tiles][Cp], fixed order, no atomics); sup_sums_kernel reduces three
+// quantities where nce_sums_kernel reduces one, counts as float32 so that ONE all-reduce of [3][cols] carries what ranks
+// exchange; sup_finalize_kernel puts the mean of the positives' scores where InfoNCE has the partner's, and sup_weights_kernel
+// forms m again from the labels (8 bytes per column, L2-resident) and subtracts 1/n_i + 1/nc_j -- exactly 2.0f where no label is
+// shared, so that every output then has InfoNCE's bits.  The gradient products are launch_grad_products, unchanged.
 #include <math.h>
 #include <type_traits>
 
@@ -75,7 +93,10 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // n tile; EPI_OUT_S / EPI_OUT_TD_S: EPI_OUT / EPI_OUT_TD with the float32 accumulator multiplied by coef / Tc * upstream first
 // EPI_RANK (retrieval ranks, logits pass): nothing stored; per-tile counts of acc > / == the row's and the column's threshold
 // EPI_TOPK (top-k retrieval, logits pass): nothing stored; per-tile sorted lists of the k best (score, column) keys of every row
-enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8 };
+// EPI_SUP (supervised contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the count and the float32
+// sum of the raw accumulators of the elements that match by label (the partner and the padding excluded)
+enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8,
+       EPI_SUP = 9 };
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -124,7 +145,29 @@ struct NceGemmArgs {
     // EPI_TOPK (also reads row_offset: the excluded partner of output row i is column row_offset + i)
     unsigned long long* topk_part;      // [n_tiles][m_tiles 256][topk_kp]  keys, best first; slots >= topk are not written
     int topk, topk_kp;                  // k <= 16 and the list pitch (k rounded up to a power of two)
+    // EPI_SUP (also reads temp / min_temp / row_offset and writes E and its sums as EPI_EXP_DT)
+    const long long* lab_row;           // [m_valid]  int64 class of output row i (negative: unlabeled)
+    const long long* lab_col;           // [n_valid]  int64 class of output column j
+    float* rowcnt_part;                 // [n_tiles][m_tiles 256]  matches by label per row of the tile, as float32
+    float* rowsx_part;                  // [n_tiles][m_tiles 256]  float32 sum of their accumulators
+    float* colcnt_part;                 // [m_tiles][n_tiles 256]  the same per column
+    float* colsx_part;                  // [m_tiles][n_tiles 256]
 };
+
+// The match by label of the supervised contrastive loss: the same non-negative class, all 64 bits compared.  The ONE place that
+// decides it (the logits epilogue and the weights pass both call it): a set-valued form would put its overlap or Jaccard weight
+// here.  The partner (column row_offset + i) is a positive by index and is handled by the callers.
+// label k of a [n <= 2^24] int64 array through a 32-bit byte offset: one address register per load beside a uniform base
+__device__ __forceinline__ long long sup_label_at(const long long* labels, int k) {
+    return *reinterpret_cast<const long long*>(reinterpret_cast<const char*>(labels) + ((unsigned int)k << 3));
+}
+__device__ __forceinline__ bool sup_label_match(long long row_label, long long col_label) {
+    return row_label >= 0 && row_label == col_label;
+}
+// a 31-bit key of a class for the epilogue's search: equal classes have equal keys (the converse is decided by sup_label_match)
+__device__ __forceinline__ unsigned int sup_label_key(long long label) {
+    return ((unsigned int)label ^ ((unsigned int)((unsigned long long)label >> 32) * 0x9e3779b1u)) & 0x7fffffffu;
+}
 
 // sigmoid(x) and the pieces of softplus(x) for x = n ln 2, two elements: u = 2^min(n, 126), t = 1 + u, r = 1 / t;
 //   sigmoid = u r,   softplus = ln 2 * lg2 + corr with lg2 = log2 t + (n - min(n, 126)) and corr = (u - (t - 1)) r:
@@ -700,7 +743,28 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
             }
         } else {
             float scale2 = p.scale2, shift2 = p.shift2;
-            if (EPI == EPI_EXP_DT) {
+            // EPI_SUP: the labels of the lane's 8 rows and 16 columns are read here (their latency passes behind the exponentials)
+            // and kept as 32-bit keys: equal classes have equal keys; a row that can match nothing (unlabeled or padding, which
+            // re-reads the last label) gets a key no column has, and the other way round.  24 registers beside the accumulators
+            // where the int64 labels would take 48 and spill.
+            unsigned int kr[8], kc[16];
+            if (EPI == EPI_SUP) {
+#pragma unroll
+                for (int rt = 0; rt < 8; ++rt) {
+                    const int i = (int)gi0 + 16 * rt;
+                    const bool iok = i < p.m_valid;
+                    const long long l = sup_label_at(p.lab_row, iok ? i : p.m_valid - 1);
+                    kr[rt] = (iok && l >= 0) ? sup_label_key(l) : 0xffffffffu;
+                }
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const int j = gj0 + 16 * (c >> 2) + (c & 3);
+                    const bool jok = j < p.n_valid;
+                    const long long l = sup_label_at(p.lab_col, jok ? j : p.n_valid - 1);
+                    kc[c] = (jok && l >= 0) ? sup_label_key(l) : 0xfffffffeu;
+                }
+            }
+            if (EPI == EPI_EXP_DT || EPI == EPI_SUP) {
                 scale2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f;
                 shift2 = scale2;
             }
@@ -758,13 +822,91 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                     const float v = reduce_r16(cs[ct][r]);      // over the wave's 128 rows
                     if (r16 == 0) lcs[wm * BT + 64 * wn + 16 * ct + 4 * lg + r] = v;
                 }
+            float* lrn = lcs + 2 * BT;                          // EPI_SUP: [4][256] row counts | [4][256] row sums |
+            float* lrx = lrn + 4 * BT;                          //          [2][256] column counts | [2][256] column sums
+            float* lcn = lrx + 4 * BT;
+            float* lcx = lcn + 2 * BT;
+            if (EPI == EPI_SUP) {
+                // block-uniform: only tiles on the band of partners or on the ragged edge pay for the index tests
+                const int64_t p0 = p.row_offset + (int64_t)BT * mi;
+                const bool special = edge || (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
+                auto label_stats = [&](auto special_c) {
+                    constexpr bool SP = decltype(special_c)::value;
+                    // Matches are sparse, so the tile is first searched with the 32-bit keys: two VALU operations per element and
+                    // no compare mask.  Only a row group (rt) with a key hit somewhere in the wave reads its int64 labels again
+                    // (from L1 / L2) and forms the 64-bit matches and the sums -- a vote that changes no bit: a group without a
+                    // match would have summed zeros.
+                    // the column sums gather in LDS, in the slots of the lanes that own them (r16 == 0: one lane per column and
+                    // wave), row group after row group: 32 accumulators less beside the 128 of the tile
+                    float* wcn = lcn + wm * BT + 64 * wn + 4 * lg;
+                    float* wcx = lcx + wm * BT + 64 * wn + 4 * lg;
+                    if (r16 == 0) {
+#pragma unroll
+                        for (int c = 0; c < 16; ++c) wcn[16 * (c >> 2) + (c & 3)] = wcx[16 * (c >> 2) + (c & 3)] = 0.f;
+                    }
+#pragma unroll
+                    for (int rt = 0; rt < 8; ++rt) {
+                        unsigned int nearest = 0xffffffffu;
+#pragma unroll
+                        for (int c = 0; c < 16; ++c) {
+                            const unsigned int x = kr[rt] ^ kc[c];
+                            nearest = x < nearest ? x : nearest;
+                        }
+                        float rn = 0.f, rx = 0.f;
+                        if (__any(nearest == 0u)) {
+                            // (opaque: nothing this rare branch needs -- indices, addresses, the labels themselves -- may be
+                            // formed in front of it or kept from the reads in front of the exponentials: it would sit in scratch)
+                            int i = (int)gi0 + 16 * rt, gj = gj0;
+                            const long long* lab_row = p.lab_row;
+                            const long long* lab_col = p.lab_col;
+                            asm volatile("" : "+v"(i), "+v"(gj), "+s"(lab_row), "+s"(lab_col));
+                            const long long lr = sup_label_at(lab_row, i < p.m_valid ? i : p.m_valid - 1);
+                            // SP: the partner counts by index, not here; its column relative to gj (-1: not in this lane's 64)
+                            const int64_t rel = p.row_offset + i - gj;
+                            const int jpr = (rel >= 0 && rel < 64) ? (int)rel : -1;
+#pragma unroll
+                            for (int c = 0; c < 16; ++c) {
+                                const int j = gj + 16 * (c >> 2) + (c & 3);
+                                // (the keys carry the padding: an equal key is a row and a column that exist)
+                                bool m = (kr[rt] == kc[c]) & sup_label_match(lr, sup_label_at(lab_col, j < p.n_valid ? j : p.n_valid - 1));
+                                if (SP) m = m & (jpr != 16 * (c >> 2) + (c & 3));
+                                const float one = m ? 1.f : 0.f, sv = m ? acc[rt][c >> 2][c & 3] : 0.f;
+                                rn += one; rx += sv;
+                                const float c1 = reduce_r16(one), c2 = reduce_r16(sv);      // over the group's 16 rows
+                                if (r16 == 0) {
+                                    wcn[16 * (c >> 2) + (c & 3)] += c1;
+                                    wcx[16 * (c >> 2) + (c & 3)] += c2;
+                                }
+                            }
+                            rn = reduce_lg(rn);                 // over the wave's 64 columns
+                            rx = reduce_lg(rx);
+                        }
+                        if (lg == 0) {
+                            lrn[wn * BT + 128 * wm + 16 * rt + r16] = rn;
+                            lrx[wn * BT + 128 * wm + 16 * rt + r16] = rx;
+                        }
+                    }
+                };
+                if (special) label_stats(std::integral_constant<bool, true>{});
+                else label_stats(std::integral_constant<bool, false>{});
+            }
             __syncthreads();
             const int tdx = threadIdx.x;
             if (tdx < BT) {
-                p.rowsum_part[((int64_t)ni * p.m_tiles + mi) * BT + tdx] = (lrs[tdx] + lrs[BT + tdx]) + (lrs[2 * BT + tdx] + lrs[3 * BT + tdx]);
+                const int64_t o = ((int64_t)ni * p.m_tiles + mi) * BT + tdx;
+                p.rowsum_part[o] = (lrs[tdx] + lrs[BT + tdx]) + (lrs[2 * BT + tdx] + lrs[3 * BT + tdx]);
+                if (EPI == EPI_SUP) {
+                    p.rowcnt_part[o] = (lrn[tdx] + lrn[BT + tdx]) + (lrn[2 * BT + tdx] + lrn[3 * BT + tdx]);
+                    p.rowsx_part[o] = (lrx[tdx] + lrx[BT + tdx]) + (lrx[2 * BT + tdx] + lrx[3 * BT + tdx]);
+                }
             } else {
                 const int c = tdx - BT;
-                p.colsum_part[((int64_t)mi * p.n_tiles + ni) * BT + c] = lcs[c] + lcs[BT + c];
+                const int64_t o = ((int64_t)mi * p.n_tiles + ni) * BT + c;
+                p.colsum_part[o] = lcs[c] + lcs[BT + c];
+                if (EPI == EPI_SUP) {
+                    p.colcnt_part[o] = lcn[c] + lcn[BT + c];
+                    p.colsx_part[o] = lcx[c] + lcx[BT + c];
+                }
             }
         }
     }
@@ -817,6 +959,20 @@ struct NceFinArgs {
     float min_temp;
 };
 
+// The two terms of a loss row, log(sum) + 1/T - s/T with s the positive's score (InfoNCE) or the mean of the positives' scores
+// (supervised loss), with their roundings pinned: the row term takes s/T in one fused multiply-add, the column term subtracts the
+// rounded product.  Written out so that both losses round alike whatever the compiler would contract: with no label shared the
+// supervised loss has InfoNCE's bits.
+__device__ __forceinline__ float nce_row_term(float sum, float inv_temp, float s) {
+#pragma clang fp contract(off)
+    return fmaf(-inv_temp, s, logf(sum) + inv_temp);
+}
+__device__ __forceinline__ float nce_col_term(float sum, float inv_temp, float s) {
+#pragma clang fp contract(off)
+    const float scaled = inv_temp * s;
+    return (logf(sum) + inv_temp) - scaled;
+}
+
 // one wave per local row: u_i, the positive logit a_i.b_pos, loss_i = log l_i + 1/T - s_ii/T (+ log c_pos + 1/T - s_ii/T);
 // the waves past the rows fill v; block 0 also carries CurriculumMasking.entropy_loss (ref aecf/AECFLayer.py:285-314)
 template <bool DT>
@@ -834,8 +990,8 @@ __global__ __launch_bounds__(256) void nce_finalize_kernel(NceFinArgs p) {
             const float li = p.l[i];
             p.u[i] = 1.0f / li;
             p.ediag[i] = __builtin_amdgcn_exp2f((dot - 1.0f) * p.inv_temp * 1.4426950408889634f);
-            float loss = logf(li) + p.inv_temp - dot * p.inv_temp;
-            if (p.sym) loss += logf(p.c[p.row_offset + i]) + p.inv_temp - dot * p.inv_temp;
+            float loss = nce_row_term(li, p.inv_temp, dot);
+            if (p.sym) loss += nce_col_term(p.c[p.row_offset + i], p.inv_temp, dot);
             p.loss_rows[i] = loss;
         }
     } else if (i < p.Rp) {
@@ -886,6 +1042,132 @@ __global__ __launch_bounds__(256) void nce_weights_dt_kernel(unsigned short* e, 
                                                              float coef, float npos, const float* upstream, const float* temp,
                                                              float min_temp) {
     nce_weights_body(e, e_tiles, m_tiles, u, v, ediag, rows, row_offset, coef * nce_dev_inv_temp(temp, min_temp), npos, upstream);
+}
+
+// ---- supervised contrastive loss: the label-aware variants of the three kernels above ----------------------------------
+
+// nce_sums_kernel over three quantities (blockIdx.y: 0 the sums of E, 1 the counts, 2 the sums of the matched accumulators):
+// row_part [3][n_tiles][Rp] -> row_stats [3][Rp], col_part [3][m_tiles][Cp] -> col_stats [3][cols]; the same four strided
+// partial sums per element, added in order
+__global__ __launch_bounds__(256) void sup_sums_kernel(const float* row_part, const float* col_part, int m_tiles, int n_tiles,
+                                                       int64_t rows, int64_t cols, float* row_stats, float* col_stats) {
+    __shared__ float red[4][64];
+    const int e = threadIdx.x & 63, part = threadIdx.x >> 6;
+    const int64_t Rp = (int64_t)m_tiles * BT, Cp = (int64_t)n_tiles * BT;
+    const int64_t q = blockIdx.y;
+    int64_t id = (int64_t)blockIdx.x * 64 + e;                  // Rp is a multiple of 64: a block is all rows or all columns
+    const bool is_row = id < Rp;
+    if (!is_row) id -= Rp;
+    const float* src = is_row ? row_part + q * n_tiles * Rp : col_part + q * m_tiles * Cp;
+    const int nt = is_row ? n_tiles : m_tiles, other = is_row ? m_tiles : n_tiles;
+    float s = 0.f;
+    for (int t = part; t < nt; t += 4) s += src[((int64_t)t * other + id / BT) * BT + id % BT];
+    red[part][e] = s;
+    __syncthreads();
+    if (part == 0) {
+        const float v = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
+        if (is_row) { if (id < rows) row_stats[q * Rp + id] = v; }
+        else if (id < cols) col_stats[q * cols + id] = v;
+    }
+}
+
+struct SupFinArgs {
+    const unsigned short* a;            // [rows, d]
+    const unsigned short* b;            // [cols, d]
+    const float* row_stats;             // [3][Rp]    l | count | matched sum of this rank's rows
+    const float* col_stats;             // [3][cols]  c | count | matched sum, all ranks
+    float* u;                           // [Rp]  1 / l     (0 in the padding)
+    float* rn;                          // [Rp]  1 / n
+    float* v;                           // [Cp]  1 / c
+    float* rnc;                         // [Cp]  1 / nc
+    float* loss_rows;                   // [rows]
+    float* ediag;                       // [rows]
+    int64_t rows, cols, row_offset, Rp, Cp;
+    int d;
+    const float* temp;
+    float min_temp;
+};
+
+// nce_finalize_kernel with the positives of the labels: one wave per local row.  The partner keeps its own float32 dot; n = 1 +
+// count, the mean of the positives' raw scores is (dot + matched sum) / n in both directions, and 1 / Tc meets it once, in the
+// expression InfoNCE has for its one positive (count == 0: its bits).
+__global__ __launch_bounds__(256) void sup_finalize_kernel(SupFinArgs p) {
+    const float inv_temp = nce_dev_inv_temp(p.temp, p.min_temp);
+    const int lane = lane_id();
+    const int64_t i = (int64_t)blockIdx.x * 4 + wave_id();
+    if (i < p.rows) {
+        const unsigned short* ap = p.a + i * p.d;
+        const unsigned short* bp = p.b + (p.row_offset + i) * p.d;
+        float dot = 0.f;
+        for (int k = lane; k < p.d; k += 64) dot = fmaf(Tr<BF16>::to_f32(ap[k]), Tr<BF16>::to_f32(bp[k]), dot);
+        dot = reduce_wave(dot);
+        if (lane == 0) {
+            const int64_t pc = p.row_offset + i;
+            const float li = p.row_stats[i];
+            p.u[i] = 1.0f / li;
+            p.ediag[i] = __builtin_amdgcn_exp2f((dot - 1.0f) * inv_temp * 1.4426950408889634f);
+            const float rni = 1.0f / (1.0f + p.row_stats[p.Rp + i]);
+            p.rn[i] = rni;
+            const float mean_r = (dot + p.row_stats[2 * p.Rp + i]) * rni;
+            const float mean_c = (dot + p.col_stats[2 * p.cols + pc]) * (1.0f / (1.0f + p.col_stats[p.cols + pc]));
+            p.loss_rows[i] = nce_row_term(li, inv_temp, mean_r) + nce_col_term(p.col_stats[pc], inv_temp, mean_c);
+        }
+    } else if (i < p.Rp) {
+        if (lane == 0) { p.u[i] = 0.f; p.rn[i] = 0.f; }
+    }
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.Cp; j += (int64_t)gridDim.x * 256) {
+        p.v[j] = j < p.cols ? 1.0f / p.col_stats[j] : 0.f;
+        p.rnc[j] = j < p.cols ? 1.0f / (1.0f + p.col_stats[p.cols + j]) : 0.f;
+    }
+}
+
+// nce_weights_dt_kernel with the positives of the labels: W = ct (E (u_i + v_j) - m_ij (rn_i + rnc_j)) in place over the tiled E.
+// m is formed again from the labels (1 row label and 8 column labels per thread; the column labels stay in L2).  The partner's
+// weight is ediag_i (u_i + v_p) - (rn_i + rnc_p): with no label shared the subtrahend is exactly 2 and every element has the
+// bits of nce_weights_dt_kernel.
+__global__ __launch_bounds__(256) void sup_weights_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
+                                                          const float* v, const float* rn, const float* rnc, const float* ediag,
+                                                          const long long* lab_row, const long long* lab_col, int64_t rows,
+                                                          int64_t cols, int64_t row_offset, float coef, const float* upstream,
+                                                          const float* temp, float min_temp) {
+    float ct = coef * nce_dev_inv_temp(temp, min_temp);
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;         // 16-byte chunk: 2048 per tile, 8 per tile row
+    if (id >= m_tiles * e_tiles * 2048) return;
+    const int64_t tile = id >> 11;
+    const int within = (int)(id & 2047);
+    const int64_t i = (tile / e_tiles) * BT + (within >> 3), j0 = (tile % e_tiles) * 64 + 8 * (within & 7);
+    u32x4* ptr = reinterpret_cast<u32x4*>(e) + id;
+    const u32x4 raw = *ptr;
+    const float ui = u[i];
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(v + j0), v1 = *reinterpret_cast<const f32x4*>(v + j0 + 4);
+    const bool iok = i < rows;
+    const long long lr = lab_row[iok ? i : rows - 1];
+    const int64_t jp = iok ? row_offset + i - j0 : -1;
+    unsigned int mm = 0;                                        // bit k: element k is a positive (by label or the partner)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int64_t j = j0 + k;
+        const long long lck = lab_col[j < cols ? j : cols - 1];
+        if (iok && j < cols && (sup_label_match(lr, lck) || jp == k)) mm |= 1u << k;
+    }
+    float x[8];
+    Tr<BF16>::unpack(raw, x);
+    const float vv[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    float rni = 0.f, rc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (mm) {
+        rni = rn[i];
+        const f32x4 r0 = *reinterpret_cast<const f32x4*>(rnc + j0), r1 = *reinterpret_cast<const f32x4*>(rnc + j0 + 4);
+        rc[0] = r0[0]; rc[1] = r0[1]; rc[2] = r0[2]; rc[3] = r0[3]; rc[4] = r1[0]; rc[5] = r1[1]; rc[6] = r1[2]; rc[7] = r1[3];
+    }
+    if (upstream) ct *= upstream[0];                           // d loss / d (this call's term): a device scalar, no host read
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float wv = x[k] * (ui + vv[k]);
+        if (jp == k) wv = ediag[i] * (ui + vv[k]) - (rni + rc[k]);
+        else if ((mm >> k) & 1u) wv = x[k] * (ui + vv[k]) - (rni + rc[k]);
+        x[k] = ct * wv;
+    }
+    *ptr = Tr<BF16>::pack(x);
 }
 
 // out[i] = sum_s slab[s][i], float4 (rounded once to bf16 when the caller wants the gradient in that dtype)
@@ -1158,6 +1440,99 @@ void launch_nce_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d
     // and n_tiles <= 16, so the splits m_tiles n_tiles partials fit in its Cp m_tiles floats); this rank's rows, both directions
     // when sym.  The weights carry every scalar: the epilogues scale nothing.
     launch_grad_products<EPI_OUT, EPI_OUT_TD>(rows, cols, d, NceGemmArgs{}, w.e, w.slabs, w.rowsum_part, dt, a, b, out_bf16, da, db, s);
+}
+
+// ---- supervised contrastive loss on the same GEMMs, both directions from one block (include/aecf_hip.h) ---------------------
+
+namespace {
+
+// workspace carve of the supervised loss
+struct SupWs {
+    unsigned short* e;                  // [Rp][Cp] bf16, tiled as E
+    float* row_part;                    // [3][n_tiles][Rp]  sums of E | counts | matched sums
+    float* col_part;                    // [3][m_tiles][Cp]
+    float* row_stats;                   // [3][Rp]  l | count | matched sum
+    float* u;                           // [Rp]
+    float* rn;                          // [Rp]
+    float* v;                           // [Cp]
+    float* rnc;                         // [Cp]
+    float* ediag;                       // [Rp]
+    float* slabs;                       // [splits][rows][d]
+    size_t bytes;
+};
+
+SupWs sup_carve(void* ws, int64_t rows, int64_t cols, int d) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t mt = Rp / BT, nt = Cp / BT;
+    SupWs w;
+    char* p = (char*)ws;
+    size_t off = 0;
+    auto take = [&](size_t n) { char* r = p + off; off += al256(n); return r; };
+    w.e = (unsigned short*)take((size_t)Rp * Cp * 2);
+    w.row_part = (float*)take((size_t)3 * nt * Rp * 4);
+    w.col_part = (float*)take((size_t)3 * mt * Cp * 4);
+    w.row_stats = (float*)take((size_t)3 * Rp * 4);
+    w.u = (float*)take((size_t)Rp * 4);
+    w.rn = (float*)take((size_t)Rp * 4);
+    w.v = (float*)take((size_t)Cp * 4);
+    w.rnc = (float*)take((size_t)Cp * 4);
+    w.ediag = (float*)take((size_t)Rp * 4);
+    w.slabs = (float*)take((size_t)da_splits(Rp, Cp, d) * rows * d * 4);
+    w.bytes = off;
+    return w;
+}
+
+}  // namespace
+
+// counts travel as float32 (exact below 2^24) so that one all-reduce carries the three column statistics
+bool supcon_gemm_supported(int d, float min_temperature, int64_t cols) {
+    return nce_gemm_supported(0, d, min_temperature) && cols <= ((int64_t)1 << 24);
+}
+
+size_t supcon_gemm_workspace_bytes(int64_t rows, int64_t cols, int d) { return sup_carve(nullptr, rows, cols, d).bytes + 256; }
+
+// pass 1: E, the row statistics (workspace) and this rank's column statistics col_stats [3][cols]
+void launch_supcon_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a, const void* b,
+                              const int64_t* row_labels, const int64_t* col_labels, void* workspace, float* col_stats, hipStream_t s) {
+    const SupWs w = sup_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    LogitsLaunch L = logits_args(rows, cols, d, a, b);
+    NceGemmArgs& g = L.g;
+    g.e = w.e; g.e_tiles = Cp / 64;
+    g.temp = dt.t; g.min_temp = dt.min_t; g.row_offset = row_offset;
+    g.lab_row = (const long long*)row_labels; g.lab_col = (const long long*)col_labels;
+    const int64_t rplane = (int64_t)g.n_tiles * Rp, cplane = (int64_t)g.m_tiles * Cp;
+    g.rowsum_part = w.row_part; g.rowcnt_part = w.row_part + rplane; g.rowsx_part = w.row_part + 2 * rplane;
+    g.colsum_part = w.col_part; g.colcnt_part = w.col_part + cplane; g.colsx_part = w.col_part + 2 * cplane;
+    launch_gemm<OP_ROW, OP_ROW, EPI_SUP, MAP_2D>(g, L.blocks, s);
+    sup_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64), 3), dim3(256), 0, s>>>(w.row_part, w.col_part, g.m_tiles, g.n_tiles, rows, cols,
+                                                                              w.row_stats, col_stats);
+}
+
+// normalisers + loss rows from the column statistics of all ranks
+void launch_supcon_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a, const void* b,
+                             const float* col_stats, void* workspace, float* loss_rows, hipStream_t s) {
+    const SupWs w = sup_carve(workspace, rows, cols, d);
+    SupFinArgs f = {};
+    f.a = (const unsigned short*)a; f.b = (const unsigned short*)b; f.row_stats = w.row_stats; f.col_stats = col_stats;
+    f.u = w.u; f.rn = w.rn; f.v = w.v; f.rnc = w.rnc; f.loss_rows = loss_rows; f.ediag = w.ediag;
+    f.rows = rows; f.cols = cols; f.row_offset = row_offset; f.Rp = up256(rows); f.Cp = up256(cols); f.d = d;
+    f.temp = dt.t; f.min_temp = dt.min_t;
+    sup_finalize_kernel<<<dim3((unsigned)((f.Rp + 3) / 4)), dim3(256), 0, s>>>(f);
+}
+
+// gradients: weights in place over E, da = W b, db = W^T a, dt.d_t; launch_supcon_gemm_loss must have run on this workspace
+void launch_supcon_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef, const void* a,
+                              const void* b, const int64_t* row_labels, const int64_t* col_labels, void* workspace,
+                              const float* upstream, int out_bf16, void* da, void* db, hipStream_t s) {
+    const SupWs w = sup_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t chunks = Rp * (Cp / 8);
+    sup_weights_kernel<<<dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s>>>(
+        w.e, Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, (const long long*)row_labels, (const long long*)col_labels, rows, cols,
+        row_offset, coef, upstream, dt.t, dt.min_t);
+    // the tdot partials go into the first plane of the row partials (dead since the sums launch), as in launch_nce_gemm_grads
+    launch_grad_products<EPI_OUT, EPI_OUT_TD>(rows, cols, d, NceGemmArgs{}, w.e, w.slabs, w.row_part, &dt, a, b, out_bf16, da, db, s);
 }
 
 // ---- sigmoid (SigLIP) loss on the same GEMMs ---------------------------------------------------------------------------

@@ -639,8 +639,84 @@ class _SupConDirection(torch.autograd.Function):
         return (dq * g).to(qd), (dk * g).to(kd), None, None, None, g_t, None, None, None
 
 
+class _SupConSymmetric(torch.autograd.Function):
+    """aecf_supcon_sym_pass1 / _loss / _grads: BOTH directions of the symmetric supervised contrastive loss from one block of
+    logits (local rows of view a against the gathered rows of view b), the labels shared by the two views.  Modelled on
+    ``_NceSymmetric`` without the entropy rider: the column statistics [3, cols] (sums of the exponentials, counts and raw-score
+    sums of the label matches) are the one thing ranks exchange, one all-reduce between pass 1 and the loss; the gradient on the
+    gathered keys is this rank's share.  The forward runs the logits pass and the loss; the backward runs the weights pass and the
+    two gradient products, scaled on the device by the gradient that arrives and written in the inputs' dtype.  The temperature
+    is a one-element float32 device tensor; the backward returns this rank's share of dL/dT."""
+
+    @staticmethod
+    def forward(ctx, a, b_all, row_labels, col_labels, row_offset, temperature, coef, group, min_temperature):
+        lib = _lib.load()
+        rows, d = a.shape
+        cols = b_all.shape[0]
+        dev = a.device
+        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
+        lr, lc = row_labels.contiguous(), col_labels.contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws_bytes = lib.aecf_supcon_sym_workspace_bytes(rows, cols, d)
+        if ws_bytes == 0:
+            raise NotImplementedError(f"aecf_amd: the tile form of the supervised contrastive loss needs d % 64 == 0, 64 <= d <= "
+                                      f"4096 and at most 2^24 gathered rows; got d = {d}, {cols} rows")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        col_stats = torch.empty(3, cols, **f32)
+        t = temperature.detach()
+        tp, t_min = _ptr(t), float(min_temperature)
+        _lib.check(lib.aecf_supcon_sym_pass1(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(lr), _ptr(lc), _ptr(ws),
+                                             ws_bytes, _ptr(col_stats), _stream()), "aecf_supcon_sym_pass1")
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(col_stats, group=group)
+        loss_rows = torch.empty(rows, **f32)
+        _lib.check(lib.aecf_supcon_sym_loss(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(col_stats), _ptr(ws),
+                                            ws_bytes, _ptr(loss_rows), _stream()), "aecf_supcon_sym_loss")
+        ctx.save_for_backward(ac, bc, lr, lc, ws, t)
+        ctx.meta = (a.dtype, b_all.dtype, temperature.shape, (rows, cols, int(row_offset), d, float(coef), t_min, ws_bytes))
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = _lib.load()
+        ac, bc, lr, lc, ws, t = ctx.saved_tensors
+        ad, bd, t_shape, (rows, cols, row_offset, d, coef, t_min, ws_bytes) = ctx.meta
+        if getattr(ctx, "_spent", False):
+            raise RuntimeError("aecf_amd: the symmetric supervised contrastive backward runs once per forward (it consumes the "
+                               "stored logits)")
+        ctx._spent = True
+        gdt = torch.bfloat16 if (ad == torch.bfloat16 and bd == torch.bfloat16) else torch.float32
+        da = torch.empty(rows, d, dtype=gdt, device=ac.device)
+        db = torch.empty(cols, d, dtype=gdt, device=ac.device)
+        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
+        d_t = torch.empty(1, dtype=torch.float32, device=ac.device) if ctx.needs_input_grad[5] else None
+        _lib.check(lib.aecf_supcon_sym_grads(rows, cols, row_offset, d, _ptr(t), t_min, coef, _ptr(ac), _ptr(bc), _ptr(lr), _ptr(lc),
+                                             _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt], _ptr(da), _ptr(db), _ptr(d_t), _stream()),
+                   "aecf_supcon_sym_grads")
+        g_t = d_t.reshape(t_shape) if d_t is not None else None
+        return da.to(ad), db.to(bd), None, None, None, g_t, None, None, None
+
+
+def _supcon_tile_refusal(z: torch.Tensor, zb: torch.Tensor, cols: int, min_temperature: float) -> Optional[str]:
+    """None where the tile form of the supervised contrastive loss runs; else what stands against it.  The memory test (the
+    b_local x b_all bfloat16 block within 0.6 of the free device memory) is skipped while a graph is being captured."""
+    rows, d = z.shape
+    if z.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16:
+        return f"bfloat16 rows (got {z.dtype} and {zb.dtype})"
+    if d % 64 != 0 or not 64 <= d <= 4096:
+        return f"d % 64 == 0 with 64 <= d <= 4096 (got d = {d})"
+    if not float(min_temperature) >= MIN_TEMPERATURE:
+        return f"min_temperature >= {MIN_TEMPERATURE} (got {min_temperature}): 1 / T is the constant shift of every exponential"
+    need = _lib.load().aecf_supcon_sym_workspace_bytes(rows, cols, d)
+    if need == 0:
+        return f"at most 2^24 gathered rows (got {cols})"
+    if not _capturing() and need > 0.6 * torch.cuda.mem_get_info(z.device)[0]:
+        return f"a workspace (b_local x b_all bfloat16, {need} bytes here) within 0.6 of the free device memory"
+    return None
+
+
 def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Tensor, temperature: Union[float, torch.Tensor] = 0.07,
-                           group=None, min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
+                           group=None, min_temperature: float = MIN_TEMPERATURE, low_memory: Optional[bool] = True) -> torch.Tensor:
     """Symmetric supervised contrastive loss (Khosla et al. 2020, "L_out") between the local rows of two views, keys from every
     rank of ``group``: the positives of row i of one view are row i of the other view and every row of the other view that
     carries the same label,
@@ -653,46 +729,76 @@ def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Ten
     row, shared by both views; a negative class marks an unlabeled row, whose only positive is its partner (two unlabeled rows
     never match).  With all labels negative or all distinct this is ``info_nce``.  Labels carry no gradient.
 
-    Both directions run the streaming kernels (aecf_supcon_fwd_bwd): neither the b_local x b_all logits nor a match mask ever
-    exists; the workspace is O(b_local d).  ``temperature``: a Python float (filled into a one-element device tensor) or a
+    ``low_memory``: which of the two implementations runs.  ``True`` (the default): both directions run the streaming kernels
+    (aecf_supcon_fwd_bwd): neither the b_local x b_all logits nor a match mask ever exists; the workspace is O(b_local d).
+    ``False``: the tile-GEMM form (aecf_supcon_sym_pass1 / _loss / _grads), both directions from ONE block of logits kept as
+    b_local x b_all bfloat16 exponentials between forward and backward -- 6 rows cols d matrix flops against the streaming
+    form's 16, the labels a sparse correction to InfoNCE's weights.  It needs bfloat16 rows, d % 64 == 0 (64 to 4096),
+    ``min_temperature >= 0.025`` and that block within 0.6 of the free device memory (not tested while capturing), and raises
+    NotImplementedError naming the limit otherwise; its backward runs once per forward.  ``None``: the tile form wherever it
+    runs, the streaming form otherwise.  Under data parallel the ranks agree on one form (they exchange different things).
+    ``temperature``: a Python float (filled into a one-element device tensor) or a
     learnable one-element float32 tensor on za's device, read by the kernels as ``max(T, min_temperature)`` with no host read --
     on one rank the call captures into a graph and replays the current temperature and labels -- and given its gradient by the
     same kernels (zero where ``T < min_temperature``; any positive ``min_temperature`` is legal).  Under ``torch.no_grad()``, or
     when no input requires a gradient, only the loss passes run and no gradient buffer is allocated.
 
-    Data parallel: both views, the labels and the row counts are all-gathered; the convention is ``info_nce``'s -- the returned
-    value is the global loss on every rank and the local term carries ``world`` for an averaging gradient reduce."""
+    Data parallel: the streaming form all-gathers both views, the labels and the row counts; the tile form gathers view b, the
+    labels and the row counts only and all-reduces the [3, b_all] column statistics between its passes.  The convention is
+    ``info_nce``'s -- the returned value is the global loss on every rank and the local term carries ``world`` for an averaging
+    gradient reduce."""
     _require_device(za, "za")
     _require_device(zb, "zb")
     if za.shape != zb.shape or za.dim() != 2:
         raise ValueError(f"supervised_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
     labels = _labels_arg(labels, za)
-    if za.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16 or za.shape[1] not in SUPCON_WIDTHS:
+    if low_memory not in (True, False, None):
+        raise ValueError(f"aecf_amd: low_memory must be True, False or None, got {low_memory!r}")
+    streams = za.dtype == torch.bfloat16 and zb.dtype == torch.bfloat16 and za.shape[1] in SUPCON_WIDTHS
+    if low_memory is True and not streams:
         raise NotImplementedError(f"aecf_amd: the supervised contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; got "
                                   f"{za.dtype} and {zb.dtype}, d = {za.shape[1]}")
     if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
         raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
-    t = _temperature_arg(temperature, za, min_temperature)
-    if not isinstance(t, torch.Tensor):
-        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
     rank, world = dp.world_info(group)
-    lab = labels.detach().to(torch.int64)
-    na, nb = l2_normalize(za), l2_normalize(zb)
     if world > 1:
         n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
         got = [torch.zeros_like(n) for _ in range(world)]
         torch.distributed.all_gather(got, n, group=group)
         sizes = [int(v.item()) for v in got]
-        offset = sum(sizes[:rank])
-        na_all, nb_all = dp.all_gather_rows(na, group, sizes=sizes), dp.all_gather_rows(nb, group, sizes=sizes)
-        lab_all = dp.all_gather_rows(lab, group, sizes=sizes)
+        offset, b_all = sum(sizes[:rank]), sum(sizes)
     else:
-        offset, na_all, nb_all, lab_all = 0, na, nb, lab
-    coef = 0.5 / float(nb_all.shape[0])
-    grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb, t))
-    l_ab = _SupConDirection.apply(na, nb_all, lab, lab_all, offset, t, coef, float(min_temperature), grads)
-    l_ba = _SupConDirection.apply(nb, na_all, lab, lab_all, offset, t, coef, float(min_temperature), grads)
-    share = l_ab + l_ba                  # this rank's rows' share of the global objective
+        sizes, offset, b_all = None, 0, za.shape[0]
+    tile = False
+    if low_memory is not True:
+        refusal = _supcon_tile_refusal(za, zb, b_all, min_temperature)
+        tile = refusal is None
+        if world > 1:                               # every rank must take the same form (they exchange different things)
+            flag = torch.tensor([1 if tile else 0], device=za.device)
+            torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
+            if tile and not bool(int(flag.item())):
+                tile, refusal = False, "the same on every rank (another rank refused it)"
+        if not tile and (low_memory is False or not streams):
+            raise NotImplementedError("aecf_amd: the tile form of the supervised contrastive loss needs " + refusal
+                                      + ("" if low_memory is False else f"; the streaming form needs bfloat16 rows with d in "
+                                         f"{SUPCON_WIDTHS}, got {za.dtype} and {zb.dtype}, d = {za.shape[1]}"))
+    t = _temperature_arg(temperature, za, min_temperature)
+    if not isinstance(t, torch.Tensor):
+        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    lab = labels.detach().to(torch.int64)
+    na, nb = l2_normalize(za), l2_normalize(zb)
+    nb_all = dp.all_gather_rows(nb, group, sizes=sizes) if world > 1 else nb
+    lab_all = dp.all_gather_rows(lab, group, sizes=sizes) if world > 1 else lab
+    coef = 0.5 / float(b_all)
+    if tile:
+        # both directions from the one block of logits this rank owns: view a is never gathered
+        share = _SupConSymmetric.apply(na, nb_all, lab, lab_all, offset, t, coef, group, float(min_temperature))
+    else:
+        na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
+        grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb, t))
+        l_ab = _SupConDirection.apply(na, nb_all, lab, lab_all, offset, t, coef, float(min_temperature), grads)
+        l_ba = _SupConDirection.apply(nb, na_all, lab, lab_all, offset, t, coef, float(min_temperature), grads)
+        share = l_ab + l_ba              # this rank's rows' share of the global objective
     if world == 1:
         return share
     total = share.detach().clone()
@@ -1040,7 +1146,8 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
     (``temperature`` / ``min_temperature``: as for ``info_nce``).  ``contrastive="sigmoid"`` takes ``sigmoid_contrastive(za, zb,
     temperature, bias)`` as the contrastive term instead (``bias``: None = its default of -10; ``low_memory``: its choice of
     implementation, ignored for ``info_nce``); ``contrastive="supervised"`` takes ``supervised_contrastive(za, zb, labels,
-    temperature)`` and ``contrastive="multilabel"`` takes ``multilabel_contrastive(za, zb, labels, label_weighting,
+    temperature)`` -- handed ``low_memory`` when it is not None (False: the tile-GEMM form), its own default (the streaming form)
+    otherwise -- and ``contrastive="multilabel"`` takes ``multilabel_contrastive(za, zb, labels, label_weighting,
     temperature)`` with ``labels`` the label sets (multi-hot rows or int64 masks); these two are the only forms that take
     ``labels``, and ``label_weighting`` ("overlap" or "jaccard") is read by the multi-label form alone."""
     if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel"):
@@ -1058,7 +1165,10 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
         if contrastive == "multilabel":
             term = multilabel_contrastive(za, zb, labels, label_weighting, temperature, group, min_temperature)
         elif contrastive == "supervised":
-            term = supervised_contrastive(za, zb, labels, temperature, group, min_temperature)
+            if low_memory is None:
+                term = supervised_contrastive(za, zb, labels, temperature, group, min_temperature)
+            else:
+                term = supervised_contrastive(za, zb, labels, temperature, group, min_temperature, low_memory)
         elif contrastive == "sigmoid":
             term = sigmoid_contrastive(za, zb, temperature, -10.0 if bias is None else bias, group, min_temperature, low_memory)
         else:

@@ -662,6 +662,59 @@ int aecf_supcon_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t 
                         const int64_t* k_labels, float* loss_rows, float* dq, float* dk, float* d_temperature,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- supervised contrastive loss, tile-GEMM form: BOTH directions of the symmetric loss from ONE block of logits ----
+ * The symmetric loss gives both views the same labels, so the match relation is symmetric and one match matrix serves both
+ * directions.  This rank owns its local rows a [rows,d] of one view (global indices row_offset .. row_offset + rows) against all
+ * gathered rows b [cols,d] of the other view, unit-norm bf16 rows, with int64 DEVICE labels row_labels [rows], col_labels [cols]:
+ *   m_ij  = (j == row_offset + i) or (row_labels[i] >= 0 and row_labels[i] == col_labels[j])
+ *           all 64 bits compared; a negative label = unlabeled, never a match; the partner counts by INDEX, whatever the labels say
+ *   x_ij  = a_i . b_j / Tc,  Tc = max(*temperature, min_temperature),  E_ij = exp(x_ij - 1/Tc)   (the shift of the InfoNCE tile form)
+ *   l_i   = sum_j E_ij      n_i  = sum_j m_ij      s_i  = sum_j m_ij x_ij        row statistics, this rank's rows
+ *   c_j   = sum_i E_ij      nc_j = sum_i m_ij      sc_j = sum_i m_ij x_ij        column statistics, summed over the ranks
+ *   loss_rows[i] = [log l_i + 1/Tc - s_i / n_i] + [log c_p + 1/Tc - sc_p / nc_p],   p = row_offset + i        WITHOUT coef
+ *   W_ij  = coef/Tc * upstream * ( E_ij (1/l_i + 1/c_j) - m_ij (1/n_i + 1/nc_j) )
+ *   da = W b [rows,d]      db = W^T a [cols,d] (this rank's share)      dT = -(1/Tc) sum_i a_i . da_i  (0 where *temperature < min_temperature)
+ * The column direction is DEFINED on the transposed match matrix of the same call, and every column counts its partner once:
+ * nc = 1 + the matches by label.  With labels shared by the views this is the sum of two aecf_supcon_fwd_bwd directions (a against
+ * b and b against a); with every label negative, or all labels distinct, every output has the bits of aecf_nce_sym_pass1_dt /
+ * _loss_dt / _grads_dt on the same inputs.
+ *   pass1: the logits GEMM.  Its epilogue writes E once as bf16 (workspace), leaves the row and column sums of E exactly as the
+ *          InfoNCE form does, and the count and float32 sum of the raw scores a_i . b_j of the matches BY LABEL (the partner
+ *          excluded: it is added from its own float32 dot later) per row and per column of every tile; fixed-order partials, no
+ *          atomics.  col_stats [3][cols] float32 gets this rank's column statistics: c | count | raw-score sum.  Counts travel
+ *          as float32 (exact: cols <= 2^24), so ONE all-reduce carries all three.
+ *   caller: all-reduce (sum) of col_stats over the ranks (nothing to do on one rank)
+ *   loss:  loss_rows [rows] from the summed col_stats, with n = 1 + count and s = (dot + sum) / Tc in both directions; prepares
+ *          1/l, 1/n (rows) and 1/c, 1/nc (columns) in the workspace.
+ *   grads: the weights in place over E (m formed again from the labels), then da and this rank's share of db as in
+ *          aecf_nce_sym_grads_dt: float32 or -- one rounding of the float32 sums -- bf16 (grad_dtype), multiplied by upstream[0]
+ *          (a DEVICE float32 scalar, NULL = 1); d_temperature (may be NULL) is WRITTEN with this rank's share of dL/dT times
+ *          upstream[0].  It consumes the stored block: it runs once per pass1.
+ * Served: bf16 rows, d % 64 == 0, 64 <= d <= 4096, min_temperature >= 0.025 (1/Tc is the constant shift of every exponential),
+ * cols <= 2^24.  6 rows cols d MFMA flops for both directions against 16 for two streaming calls.
+ * Workspace, in order, each piece rounded up to 256 bytes, Rp / Cp = rows / cols rounded up to 256, + 256 bytes:
+ *   E [Rp][Cp] bf16 | row partials [3][Cp/256][Rp] | column partials [3][Rp/256][Cp] | row statistics [3][Rp] | 1/l [Rp] |
+ *   1/n [Rp] | 1/c [Cp] | 1/nc [Cp] | the partner's exponential [Rp] | da slabs [splits][rows][d]   (float32 but E; splits: the K
+ *   split of da = W b, as in the InfoNCE form).  The query answers 0 where the shape is not served (d, cols > 2^24).
+ * Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host (the calls capture into a
+ * graph), nothing read from the workspace before it is written; no float atomics: the same inputs give the same bits.  Checks
+ * before any launch, as for the streaming call: sizes (rows, cols, d > 0, cols < 2^31, min_temperature > 0, 0 <= row_offset,
+ * row_offset + rows <= cols: AECF_ERR_BAD_DIMS), then d, min_temperature < 0.025, cols > 2^24 or a grad_dtype other than bf16 /
+ * float32 (AECF_ERR_UNSUPPORTED), then NULL pointers (AECF_ERR_NULL_POINTER; upstream and d_temperature may be NULL), then the
+ * workspace size (AECF_ERR_WORKSPACE). */
+size_t aecf_supcon_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d);      /* 0: not served */
+int aecf_supcon_sym_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                          float min_temperature, const void* a, const void* b, const int64_t* row_labels,
+                          const int64_t* col_labels, void* workspace, size_t workspace_bytes,
+                          float* col_stats /* [3][cols] */, void* stream);
+int aecf_supcon_sym_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                         float min_temperature, const void* a, const void* b, const float* col_stats /* summed over ranks */,
+                         void* workspace, size_t workspace_bytes, float* loss_rows, void* stream);
+int aecf_supcon_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                          float min_temperature, float coef, const void* a, const void* b, const int64_t* row_labels,
+                          const int64_t* col_labels, void* workspace, size_t workspace_bytes, const float* upstream,
+                          int32_t grad_dtype, void* da, void* db, float* d_temperature, void* stream);
+
 /* ---- multi-label supervised contrastive loss (build-defined like the supervised term above, whose contract this one repeats) ----
  * One direction as above, with a SET of classes per row instead of one class: q_sets [rows] and k_sets [cols] are DEVICE arrays of
  * one uint64 per row, bit c = class c, C <= 64 classes (aecf_label_sets_pack makes them from multi-hot rows).  A key counts with a
