@@ -209,6 +209,16 @@ _SYMBOLS = [
     ("aecf_supcon_sym_grads", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
       c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # multi-label contrastive loss, symmetric, on the tile GEMMs: class sets and a weighting in place of the labels
+    ("aecf_supcon_ml_sym_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
+    ("aecf_supcon_ml_sym_pass1", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t,
+      c_void_p, c_void_p]),
+    ("aecf_supcon_ml_sym_loss", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("aecf_supcon_ml_sym_grads", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+      c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     # multi-label supervised contrastive loss: uint64 class sets in place of the labels, a weighting; the packing of multi-hot rows
     ("aecf_supcon_ml_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
     ("aecf_supcon_ml_fwd_bwd", c_int,

@@ -335,6 +335,16 @@ void launch_supcon_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, in
                               const void* b, const int64_t* row_labels, const int64_t* col_labels, void* workspace,
                               const float* upstream, int out_bf16, void* da, void* db, hipStream_t s);
 
+// The same with class sets (one uint64 per row) and the overlap (jaccard 0) or Jaccard (jaccard 1) weight in place of the match:
+// dense weights, so a dense epilogue of its own (EPI_SETS_OV / EPI_SETS_JAC) and set_weights_kernel; workspace, supported shapes
+// and loss pass are those above (col_stats: column sums of E | sums of w | sums of w * raw score).
+void launch_supcon_ml_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a,
+                                 const void* b, const uint64_t* row_sets, const uint64_t* col_sets, int jaccard, void* workspace,
+                                 float* col_stats, hipStream_t s);
+void launch_supcon_ml_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef,
+                                 const void* a, const void* b, const uint64_t* row_sets, const uint64_t* col_sets, int jaccard,
+                                 void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s);
+
 // Multi-label supervised contrastive loss, streaming (aecf_supcon_ml_flash.hip): a set of classes per row as one uint64 (bit c =
 // class c); a key counts with weight 1 (the partner), [sets overlap] (jaccard 0) or |and| / |or| (jaccard 1).  The same passes,
 // workspace layout and outputs as launch_supcon_flash.  launch_label_sets_pack: multi-hot rows [rows, classes <= 64] of kind

@@ -75,6 +75,27 @@
 // exchange; sup_finalize_kernel puts the mean of the positives' scores where InfoNCE has the partner's, and sup_weights_kernel
 // forms m again from the labels (8 bytes per column, L2-resident) and subtracts 1/n_i + 1/nc_j -- exactly 2.0f where no label is
 // shared, so that every output then has InfoNCE's bits.  The gradient products are launch_grad_products, unchanged.
+//
+// The multi-label form (aecf_supcon_ml_sym_pass1 / _loss / _grads) gives every row a SET of classes, one uint64 (bit c = class c),
+// and a weight w_ij in [0, 1] where the single-label form has a match: [A_i & B_j != 0] (overlap) or |A_i & B_j| / |A_i | B_j|
+// (Jaccard), 1 for the partner by index.  The weights are dense -- thousands of positives per row -- so the sparse vote of EPI_SUP
+// has no place: EPI_SETS_OV / EPI_SETS_JAC (the weighting is a template parameter) run a dense sweep over every tile.
+//   * The E loop is EPI_EXP_DT's, untouched: E and its row and column sums keep their bits.
+//   * The block's 256 row words and 256 column words (4 KiB; the padding as the empty set, which weighs 0 against everything) are
+//     read in front of the exponentials and staged in the LDS the operand stages have vacated; the sweep reads them from there,
+//     so no set lives in a register across the E loop.
+//   * The sweep runs AFTER the E loop, when its 24 sum registers are dead, column group (ct) by column group: a lane holds the 4
+//     column words of the group (and, Jaccard, their popcounts), 8 column accumulators and 16 row accumulators, and reads the row
+//     word of each of its 8 row groups from LDS.  Jaccard takes ONE 64-bit popcount per element (the intersection; the union is
+//     pa + pb - inter from the per-word popcounts) and one correctly rounded float32 division.
+//   * Summation order, the same for the sum of w and for the sum of w * accumulator (each product fused into its addition, one
+//     rounding): a ROW's statistic is a chain over the lane's 16 elements of the row, ct-major (16 additions), then the 4 lane
+//     groups (xor 16, xor 32: 2), the block's 4 column waves ((w0 + w1) + (w2 + w3): 2), then sup_sums_kernel over the n tiles
+//     (ceil(n_tiles / 4) + 2).  A COLUMN's is a chain over the lane's 8 row groups (8), the 16 lanes of the group (4), the 2 row
+//     waves (1), then sup_sums_kernel over the m tiles (ceil(m_tiles / 4) + 2).  The partner is excluded by index on the tiles
+//     of its band (the block-uniform `special` branch) and joins later from its own float32 dot with weight 1.
+// sup_sums_kernel and sup_finalize_kernel serve unchanged (the weight sums stand where the counts stood); set_weights_kernel forms
+// w again from the words next to sup_weights_kernel.
 #include <math.h>
 #include <type_traits>
 
@@ -96,7 +117,10 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // EPI_SUP (supervised contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the count and the float32
 // sum of the raw accumulators of the elements that match by label (the partner and the padding excluded)
 enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8,
-       EPI_SUP = 9 };
+       EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11 };
+// EPI_SETS_OV / EPI_SETS_JAC (multi-label contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the
+// float32 sums of w and of w * raw accumulator, w the overlap / Jaccard weight of the two class sets (partner and padding excluded)
+constexpr bool epi_is_sets(int epi) { return epi == EPI_SETS_OV || epi == EPI_SETS_JAC; }
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -152,6 +176,8 @@ struct NceGemmArgs {
     float* rowsx_part;                  // [n_tiles][m_tiles 256]  float32 sum of their accumulators
     float* colcnt_part;                 // [m_tiles][n_tiles 256]  the same per column
     float* colsx_part;                  // [m_tiles][n_tiles 256]
+    // EPI_SETS_OV / EPI_SETS_JAC: lab_row / lab_col hold the uint64 class sets of the rows / columns (bit c = class c), the four
+    // partials above the sums of w and of w * accumulator
 };
 
 // The match by label of the supervised contrastive loss: the same non-negative class, all 64 bits compared.  The ONE place that
@@ -167,6 +193,17 @@ __device__ __forceinline__ bool sup_label_match(long long row_label, long long c
 // a 31-bit key of a class for the epilogue's search: equal classes have equal keys (the converse is decided by sup_label_match)
 __device__ __forceinline__ unsigned int sup_label_key(long long label) {
     return ((unsigned int)label ^ ((unsigned int)((unsigned long long)label >> 32) * 0x9e3779b1u)) & 0x7fffffffu;
+}
+
+// The weight of two class sets (multi-label form): JAC false: 1 where they share a class; true: |A & B| / |A | B| over all 64 bits,
+// ONE correctly rounded float32 division, 0 for an empty union.  pa / pb: the popcounts of the two words (read by JAC only).  The
+// ONE place that decides it: the logits epilogue and the weights pass both call it.
+template <bool JAC>
+__device__ __forceinline__ float set_weight(unsigned long long a, unsigned long long b, int pa, int pb) {
+    const unsigned long long both = a & b;
+    if (!JAC) return both != 0ull ? 1.f : 0.f;
+    const int inter = __popcll(both), uni = pa + pb - inter;
+    return __fdiv_rn((float)inter, (float)(uni > 0 ? uni : 1));
 }
 
 // sigmoid(x) and the pieces of softplus(x) for x = n ln 2, two elements: u = 2^min(n, 126), t = 1 + u, r = 1 / t;
@@ -764,12 +801,24 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                     kc[c] = (jok && l >= 0) ? sup_label_key(l) : 0xfffffffeu;
                 }
             }
-            if (EPI == EPI_EXP_DT || EPI == EPI_SUP) {
+            // EPI_SETS_*: thread t < 256 reads the word of the block's row t, thread 256 + t that of its column t (the padding: the
+            // empty set); they go to LDS behind the barrier
+            unsigned long long my_set = 0ull;
+            if (epi_is_sets(EPI)) {
+                const int t = threadIdx.x & (BT - 1);
+                const bool is_row = threadIdx.x < BT;
+                const int k = BT * (is_row ? mi : ni) + t;
+                const unsigned long long* src = reinterpret_cast<const unsigned long long*>(is_row ? p.lab_row : p.lab_col);
+                if (k < (is_row ? p.m_valid : p.n_valid)) my_set = src[k];
+            }
+            if (EPI == EPI_EXP_DT || EPI == EPI_SUP || epi_is_sets(EPI)) {
                 scale2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f;
                 shift2 = scale2;
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
+            if (epi_is_sets(EPI))                               // [256] row words | [256] column words, behind the 18 float planes
+                reinterpret_cast<unsigned long long*>(smem + 18 * BT * 4)[threadIdx.x] = my_set;
             // E = exp2(acc scale - shift): 4 consecutive columns per lane, 8-byte stores (16 rows x 32 B per wave-instruction).
             // The sums run as packed float32 adds (both halves from their own registers); masking only on edge tiles.
             float rs[8];
@@ -890,12 +939,76 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                 if (special) label_stats(std::integral_constant<bool, true>{});
                 else label_stats(std::integral_constant<bool, false>{});
             }
+            if (epi_is_sets(EPI)) {
+                constexpr bool JAC = EPI == EPI_SETS_JAC;
+                typedef unsigned long long u64;
+                __syncthreads();                                // the staged words are in place
+                const u64* lsr = reinterpret_cast<const u64*>(smem + 18 * BT * 4) + 128 * wm + r16;            // + 16 rt
+                const u64* lsc = reinterpret_cast<const u64*>(smem + 18 * BT * 4) + BT + 64 * wn + 4 * lg;     // + 16 ct + r
+                // block-uniform: only the tiles on the band of partners pay for the index test (the padding weighs 0 by its sets)
+                const int64_t p0 = p.row_offset + (int64_t)BT * mi;
+                const bool special = p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni;
+                // the partner of the lane's row of group rt is its element 16 ct + r where rel == 16 (ct - rt) + r
+                const int64_t rel64 = p.row_offset + gi0 - gj0;
+                const int rel = (rel64 > -512 && rel64 < 512) ? (int)rel64 : -4096;
+                auto set_stats = [&](auto special_c) {
+                    constexpr bool SP = decltype(special_c)::value;
+                    float rw[8], rx[8];
+#pragma unroll
+                    for (int rt = 0; rt < 8; ++rt) rw[rt] = rx[rt] = 0.f;
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+                        u64 B[4];
+                        int pb[4];
+                        float cw[4], cx[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            B[r] = lsc[16 * ct + r];
+                            pb[r] = JAC ? __popcll(B[r]) : 0;
+                            cw[r] = cx[r] = 0.f;
+                        }
+#pragma unroll
+                        for (int rt = 0; rt < 8; ++rt) {
+                            const u64 A = lsr[16 * rt];
+                            const int pa = JAC ? __popcll(A) : 0;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                float wt = set_weight<JAC>(A, B[r], pa, pb[r]);
+                                if (SP) wt = rel == 16 * (ct - rt) + r ? 0.f : wt;
+                                const float sv = acc[rt][ct][r];
+                                rw[rt] += wt;
+                                rx[rt] = fmaf(wt, sv, rx[rt]);
+                                cw[r] += wt;
+                                cx[r] = fmaf(wt, sv, cx[r]);
+                            }
+                        }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float c1 = reduce_r16(cw[r]), c2 = reduce_r16(cx[r]);     // over the wave's 128 rows
+                            if (r16 == 0) {
+                                lcn[wm * BT + 64 * wn + 16 * ct + 4 * lg + r] = c1;
+                                lcx[wm * BT + 64 * wn + 16 * ct + 4 * lg + r] = c2;
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int rt = 0; rt < 8; ++rt) {
+                        const float r1 = reduce_lg(rw[rt]), r2 = reduce_lg(rx[rt]);         // over the wave's 64 columns
+                        if (lg == 0) {
+                            lrn[wn * BT + 128 * wm + 16 * rt + r16] = r1;
+                            lrx[wn * BT + 128 * wm + 16 * rt + r16] = r2;
+                        }
+                    }
+                };
+                if (special) set_stats(std::integral_constant<bool, true>{});
+                else set_stats(std::integral_constant<bool, false>{});
+            }
             __syncthreads();
             const int tdx = threadIdx.x;
             if (tdx < BT) {
                 const int64_t o = ((int64_t)ni * p.m_tiles + mi) * BT + tdx;
                 p.rowsum_part[o] = (lrs[tdx] + lrs[BT + tdx]) + (lrs[2 * BT + tdx] + lrs[3 * BT + tdx]);
-                if (EPI == EPI_SUP) {
+                if (EPI == EPI_SUP || epi_is_sets(EPI)) {
                     p.rowcnt_part[o] = (lrn[tdx] + lrn[BT + tdx]) + (lrn[2 * BT + tdx] + lrn[3 * BT + tdx]);
                     p.rowsx_part[o] = (lrx[tdx] + lrx[BT + tdx]) + (lrx[2 * BT + tdx] + lrx[3 * BT + tdx]);
                 }
@@ -903,7 +1016,7 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                 const int c = tdx - BT;
                 const int64_t o = ((int64_t)mi * p.n_tiles + ni) * BT + c;
                 p.colsum_part[o] = lcs[c] + lcs[BT + c];
-                if (EPI == EPI_SUP) {
+                if (EPI == EPI_SUP || epi_is_sets(EPI)) {
                     p.colcnt_part[o] = lcn[c] + lcn[BT + c];
                     p.colsx_part[o] = lcx[c] + lcx[BT + c];
                 }
@@ -1165,6 +1278,60 @@ __global__ __launch_bounds__(256) void sup_weights_kernel(unsigned short* e, int
         float wv = x[k] * (ui + vv[k]);
         if (jp == k) wv = ediag[i] * (ui + vv[k]) - (rni + rc[k]);
         else if ((mm >> k) & 1u) wv = x[k] * (ui + vv[k]) - (rni + rc[k]);
+        x[k] = ct * wv;
+    }
+    *ptr = Tr<BF16>::pack(x);
+}
+
+// sup_weights_kernel with class sets: W = ct (E (u_i + v_j) - w_ij (rn_i + rnc_j)) in place over the tiled E, w formed again from
+// the words (1 row word and 8 column words per 16-byte chunk; the column words stay in L2), the product w (rn + rnc) fused into
+// the subtraction (one rounding).  The partner's weight is ediag_i (u_i + v_p) - (rn_i + rnc_p), w = 1 by index: with no set
+// weight anywhere in its row and column the subtrahend is exactly 2; an element with w = 0 takes InfoNCE's expression.
+template <bool JAC>
+__global__ __launch_bounds__(256) void set_weights_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
+                                                          const float* v, const float* rn, const float* rnc, const float* ediag,
+                                                          const unsigned long long* set_row, const unsigned long long* set_col,
+                                                          int64_t rows, int64_t cols, int64_t row_offset, float coef,
+                                                          const float* upstream, const float* temp, float min_temp) {
+#pragma clang fp contract(off)
+    float ct = coef * nce_dev_inv_temp(temp, min_temp);
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;         // 16-byte chunk: 2048 per tile, 8 per tile row
+    if (id >= m_tiles * e_tiles * 2048) return;
+    const int64_t tile = id >> 11;
+    const int within = (int)(id & 2047);
+    const int64_t i = (tile / e_tiles) * BT + (within >> 3), j0 = (tile % e_tiles) * 64 + 8 * (within & 7);
+    u32x4* ptr = reinterpret_cast<u32x4*>(e) + id;
+    const u32x4 raw = *ptr;
+    const float ui = u[i];
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(v + j0), v1 = *reinterpret_cast<const f32x4*>(v + j0 + 4);
+    const bool iok = i < rows;
+    const unsigned long long A = iok ? set_row[i] : 0ull;       // the padding: the empty set, weight 0
+    const int pa = JAC ? __popcll(A) : 0;
+    const int64_t jp = iok ? row_offset + i - j0 : -1;
+    float wt[8];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int64_t j = j0 + k;
+        const unsigned long long B = j < cols ? set_col[j] : 0ull;
+        wt[k] = jp == k ? 1.f : set_weight<JAC>(A, B, pa, JAC ? __popcll(B) : 0);
+        any = any || wt[k] != 0.f;
+    }
+    float x[8];
+    Tr<BF16>::unpack(raw, x);
+    const float vv[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    float rni = 0.f, rc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (any) {
+        rni = rn[i];
+        const f32x4 r0 = *reinterpret_cast<const f32x4*>(rnc + j0), r1 = *reinterpret_cast<const f32x4*>(rnc + j0 + 4);
+        rc[0] = r0[0]; rc[1] = r0[1]; rc[2] = r0[2]; rc[3] = r0[3]; rc[4] = r1[0]; rc[5] = r1[1]; rc[6] = r1[2]; rc[7] = r1[3];
+    }
+    if (upstream) ct *= upstream[0];                           // d loss / d (this call's term): a device scalar, no host read
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float wv = x[k] * (ui + vv[k]);
+        if (jp == k) wv = fmaf(ediag[i], ui + vv[k], -(rni + rc[k]));
+        else if (wt[k] != 0.f) wv = fmaf(-wt[k], rni + rc[k], wv);
         x[k] = ct * wv;
     }
     *ptr = Tr<BF16>::pack(x);
@@ -1531,6 +1698,47 @@ void launch_supcon_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, in
     sup_weights_kernel<<<dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s>>>(
         w.e, Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, (const long long*)row_labels, (const long long*)col_labels, rows, cols,
         row_offset, coef, upstream, dt.t, dt.min_t);
+    // the tdot partials go into the first plane of the row partials (dead since the sums launch), as in launch_nce_gemm_grads
+    launch_grad_products<EPI_OUT, EPI_OUT_TD>(rows, cols, d, NceGemmArgs{}, w.e, w.slabs, w.row_part, &dt, a, b, out_bf16, da, db, s);
+}
+
+// ---- multi-label contrastive loss on the same GEMMs: class sets and a weighting in place of the labels (include/aecf_hip.h).
+// The workspace is SupWs (the weight sums where the counts stand); the loss pass is launch_supcon_gemm_loss.
+
+void launch_supcon_ml_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a,
+                                 const void* b, const uint64_t* row_sets, const uint64_t* col_sets, int jaccard, void* workspace,
+                                 float* col_stats, hipStream_t s) {
+    const SupWs w = sup_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    LogitsLaunch L = logits_args(rows, cols, d, a, b);
+    NceGemmArgs& g = L.g;
+    g.e = w.e; g.e_tiles = Cp / 64;
+    g.temp = dt.t; g.min_temp = dt.min_t; g.row_offset = row_offset;
+    g.lab_row = (const long long*)row_sets; g.lab_col = (const long long*)col_sets;
+    const int64_t rplane = (int64_t)g.n_tiles * Rp, cplane = (int64_t)g.m_tiles * Cp;
+    g.rowsum_part = w.row_part; g.rowcnt_part = w.row_part + rplane; g.rowsx_part = w.row_part + 2 * rplane;
+    g.colsum_part = w.col_part; g.colcnt_part = w.col_part + cplane; g.colsx_part = w.col_part + 2 * cplane;
+    if (jaccard) launch_gemm<OP_ROW, OP_ROW, EPI_SETS_JAC, MAP_2D>(g, L.blocks, s);
+    else launch_gemm<OP_ROW, OP_ROW, EPI_SETS_OV, MAP_2D>(g, L.blocks, s);
+    sup_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64), 3), dim3(256), 0, s>>>(w.row_part, w.col_part, g.m_tiles, g.n_tiles, rows, cols,
+                                                                              w.row_stats, col_stats);
+}
+
+void launch_supcon_ml_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef,
+                                 const void* a, const void* b, const uint64_t* row_sets, const uint64_t* col_sets, int jaccard,
+                                 void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s) {
+    const SupWs w = sup_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t chunks = Rp * (Cp / 8);
+    const dim3 grid((unsigned)((chunks + 255) / 256));
+    const unsigned long long* sr = (const unsigned long long*)row_sets;
+    const unsigned long long* sc = (const unsigned long long*)col_sets;
+    if (jaccard)
+        set_weights_kernel<true><<<grid, dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, sr, sc, rows, cols,
+                                                            row_offset, coef, upstream, dt.t, dt.min_t);
+    else
+        set_weights_kernel<false><<<grid, dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, sr, sc, rows, cols,
+                                                             row_offset, coef, upstream, dt.t, dt.min_t);
     // the tdot partials go into the first plane of the row partials (dead since the sums launch), as in launch_nce_gemm_grads
     launch_grad_products<EPI_OUT, EPI_OUT_TD>(rows, cols, d, NceGemmArgs{}, w.e, w.slabs, w.row_part, &dt, a, b, out_bf16, da, db, s);
 }

@@ -901,9 +901,66 @@ class _SupConMlDirection(torch.autograd.Function):
         return (dq * g).to(qd), (dk * g).to(kd), None, None, None, None, g_t, None, None, None
 
 
+class _SupConMlSymmetric(torch.autograd.Function):
+    """aecf_supcon_ml_sym_pass1 / _loss / _grads: BOTH directions of the symmetric multi-label contrastive loss from one block of
+    logits (local rows of view a against the gathered rows of view b), the class sets (int64 masks) shared by the two views.
+    ``_SupConSymmetric`` with sets and a weighting for the labels: the column statistics [3, cols] (sums of the exponentials, of
+    the set weights and of weight times raw score) are the one thing ranks exchange, one all-reduce between pass 1 and the loss;
+    the gradient on the gathered keys is this rank's share.  The backward runs the weights pass and the two gradient products
+    once per forward.  The temperature is a one-element float32 device tensor; the backward returns this rank's share of dL/dT."""
+
+    @staticmethod
+    def forward(ctx, a, b_all, row_sets, col_sets, weighting, row_offset, temperature, coef, group, min_temperature):
+        lib = _lib.load()
+        rows, d = a.shape
+        cols = b_all.shape[0]
+        dev = a.device
+        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
+        sr, sc = row_sets.contiguous(), col_sets.contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws_bytes = lib.aecf_supcon_ml_sym_workspace_bytes(rows, cols, d)
+        if ws_bytes == 0:
+            raise NotImplementedError(f"aecf_amd: the tile form of the multi-label contrastive loss needs d % 64 == 0, 64 <= d <= "
+                                      f"4096 and at most 2^24 gathered rows; got d = {d}, {cols} rows")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        col_stats = torch.empty(3, cols, **f32)
+        t = temperature.detach()
+        tp, t_min, w = _ptr(t), float(min_temperature), int(weighting)
+        _lib.check(lib.aecf_supcon_ml_sym_pass1(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(sr), _ptr(sc), w,
+                                                _ptr(ws), ws_bytes, _ptr(col_stats), _stream()), "aecf_supcon_ml_sym_pass1")
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(col_stats, group=group)
+        loss_rows = torch.empty(rows, **f32)
+        _lib.check(lib.aecf_supcon_ml_sym_loss(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(col_stats), _ptr(ws),
+                                               ws_bytes, _ptr(loss_rows), _stream()), "aecf_supcon_ml_sym_loss")
+        ctx.save_for_backward(ac, bc, sr, sc, ws, t)
+        ctx.meta = (a.dtype, b_all.dtype, temperature.shape, (rows, cols, int(row_offset), d, float(coef), t_min, ws_bytes, w))
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = _lib.load()
+        ac, bc, sr, sc, ws, t = ctx.saved_tensors
+        ad, bd, t_shape, (rows, cols, row_offset, d, coef, t_min, ws_bytes, w) = ctx.meta
+        if getattr(ctx, "_spent", False):
+            raise RuntimeError("aecf_amd: the symmetric multi-label contrastive backward runs once per forward (it consumes the "
+                               "stored logits)")
+        ctx._spent = True
+        gdt = torch.bfloat16 if (ad == torch.bfloat16 and bd == torch.bfloat16) else torch.float32
+        da = torch.empty(rows, d, dtype=gdt, device=ac.device)
+        db = torch.empty(cols, d, dtype=gdt, device=ac.device)
+        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
+        d_t = torch.empty(1, dtype=torch.float32, device=ac.device) if ctx.needs_input_grad[6] else None
+        _lib.check(lib.aecf_supcon_ml_sym_grads(rows, cols, row_offset, d, _ptr(t), t_min, coef, _ptr(ac), _ptr(bc), _ptr(sr), _ptr(sc),
+                                                w, _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt], _ptr(da), _ptr(db), _ptr(d_t),
+                                                _stream()), "aecf_supcon_ml_sym_grads")
+        g_t = d_t.reshape(t_shape) if d_t is not None else None
+        return da.to(ad), db.to(bd), None, None, None, None, g_t, None, None, None
+
+
 def multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets: torch.Tensor, weighting: str = "overlap",
                            temperature: Union[float, torch.Tensor] = 0.07, group=None,
-                           min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
+                           min_temperature: float = MIN_TEMPERATURE, low_memory: Optional[bool] = True) -> torch.Tensor:
     """Symmetric multi-label supervised contrastive loss between the local rows of two views, keys from every rank of ``group``:
     every row carries a SET of classes, and a row of the other view counts as a positive of row i with a weight
 
@@ -921,14 +978,23 @@ def multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets: torch
     partner and it is nobody's positive by label.  With one-hot sets both weightings are ``supervised_contrastive``; with all
     sets empty or pairwise disjoint they are ``info_nce``.  Sets carry no gradient.
 
-    Both directions run the streaming kernels (aecf_supcon_ml_fwd_bwd): neither the b_local x b_all logits nor a weight matrix
-    ever exists; the workspace is O(b_local d).  ``temperature``: a Python float or a learnable one-element float32 tensor on
+    ``low_memory``: which of the two implementations runs.  ``True`` (the default): both directions run the streaming kernels
+    (aecf_supcon_ml_fwd_bwd): neither the b_local x b_all logits nor a weight matrix ever exists; the workspace is O(b_local d).
+    ``False``: the tile-GEMM form (aecf_supcon_ml_sym_pass1 / _loss / _grads), both directions from ONE block of logits kept as
+    b_local x b_all bfloat16 exponentials between forward and backward, the set weights formed in a dense epilogue of the logits
+    GEMM and again in the weights pass.  It needs bfloat16 rows, d % 64 == 0 (64 to 4096, so it serves widths the streaming form
+    does not), ``min_temperature >= 0.025`` and that block within 0.6 of the free device memory (not tested while capturing), and
+    raises NotImplementedError naming the limit otherwise; its backward runs once per forward.  ``None``: the tile form wherever
+    it runs, the streaming form otherwise.  Under data parallel the ranks agree on one form (they exchange different things).
+    ``temperature``: a Python float or a learnable one-element float32 tensor on
     za's device, read as ``max(T, min_temperature)`` with no host read -- on one rank the call captures into a graph and replays
     the current temperature and sets -- and given its gradient by the same kernels.  Under ``torch.no_grad()``, or when no input
-    requires a gradient, only the loss passes run and no gradient buffer is allocated.
+    requires a gradient, only the loss passes of the streaming form run and no gradient buffer is allocated.
 
-    Data parallel: both views, the packed sets and the row counts are all-gathered; the convention is ``info_nce``'s -- the
-    returned value is the global loss on every rank and the local term carries ``world`` for an averaging gradient reduce."""
+    Data parallel: the streaming form all-gathers both views, the packed sets and the row counts; the tile form gathers view b, the
+    packed sets and the row counts only and all-reduces the [3, b_all] column statistics between its passes.  The convention is
+    ``info_nce``'s -- the returned value is the global loss on every rank and the local term carries ``world`` for an averaging
+    gradient reduce."""
     if weighting not in SET_WEIGHTINGS:
         raise ValueError(f"aecf_amd: weighting must be 'overlap' or 'jaccard', got {weighting!r}")
     _require_device(za, "za")
@@ -936,33 +1002,55 @@ def multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets: torch
     if za.shape != zb.shape or za.dim() != 2:
         raise ValueError(f"multilabel_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
     label_sets = _label_sets_arg(label_sets, za)
-    if za.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16 or za.shape[1] not in SUPCON_WIDTHS:
+    if low_memory not in (True, False, None):
+        raise ValueError(f"aecf_amd: low_memory must be True, False or None, got {low_memory!r}")
+    streams = za.dtype == torch.bfloat16 and zb.dtype == torch.bfloat16 and za.shape[1] in SUPCON_WIDTHS
+    if low_memory is True and not streams:
         raise NotImplementedError(f"aecf_amd: the multi-label contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; got "
                                   f"{za.dtype} and {zb.dtype}, d = {za.shape[1]}")
     if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
         raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
-    t = _temperature_arg(temperature, za, min_temperature)
-    if not isinstance(t, torch.Tensor):
-        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
     rank, world = dp.world_info(group)
-    sets = label_sets.detach() if label_sets.dim() == 1 else pack_label_sets(label_sets)
-    na, nb = l2_normalize(za), l2_normalize(zb)
     if world > 1:
         n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
         got = [torch.zeros_like(n) for _ in range(world)]
         torch.distributed.all_gather(got, n, group=group)
         sizes = [int(v.item()) for v in got]
-        offset = sum(sizes[:rank])
-        na_all, nb_all = dp.all_gather_rows(na, group, sizes=sizes), dp.all_gather_rows(nb, group, sizes=sizes)
-        sets_all = dp.all_gather_rows(sets, group, sizes=sizes)
+        offset, b_all = sum(sizes[:rank]), sum(sizes)
     else:
-        offset, na_all, nb_all, sets_all = 0, na, nb, sets
-    coef = 0.5 / float(nb_all.shape[0])
+        sizes, offset, b_all = None, 0, za.shape[0]
+    tile = False
+    if low_memory is not True:
+        # (the two tile forms share their served shapes and their workspace)
+        refusal = _supcon_tile_refusal(za, zb, b_all, min_temperature)
+        tile = refusal is None
+        if world > 1:                               # every rank must take the same form (they exchange different things)
+            flag = torch.tensor([1 if tile else 0], device=za.device)
+            torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
+            if tile and not bool(int(flag.item())):
+                tile, refusal = False, "the same on every rank (another rank refused it)"
+        if not tile and (low_memory is False or not streams):
+            raise NotImplementedError("aecf_amd: the tile form of the multi-label contrastive loss needs " + refusal
+                                      + ("" if low_memory is False else f"; the streaming form needs bfloat16 rows with d in "
+                                         f"{SUPCON_WIDTHS}, got {za.dtype} and {zb.dtype}, d = {za.shape[1]}"))
+    t = _temperature_arg(temperature, za, min_temperature)
+    if not isinstance(t, torch.Tensor):
+        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    sets = label_sets.detach() if label_sets.dim() == 1 else pack_label_sets(label_sets)
+    na, nb = l2_normalize(za), l2_normalize(zb)
+    nb_all = dp.all_gather_rows(nb, group, sizes=sizes) if world > 1 else nb
+    sets_all = dp.all_gather_rows(sets, group, sizes=sizes) if world > 1 else sets
+    coef = 0.5 / float(b_all)
     w = SET_WEIGHTINGS[weighting]
-    grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb, t))
-    l_ab = _SupConMlDirection.apply(na, nb_all, sets, sets_all, w, offset, t, coef, float(min_temperature), grads)
-    l_ba = _SupConMlDirection.apply(nb, na_all, sets, sets_all, w, offset, t, coef, float(min_temperature), grads)
-    share = l_ab + l_ba                  # this rank's rows' share of the global objective
+    if tile:
+        # both directions from the one block of logits this rank owns: view a is never gathered
+        share = _SupConMlSymmetric.apply(na, nb_all, sets, sets_all, w, offset, t, coef, group, float(min_temperature))
+    else:
+        na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
+        grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb, t))
+        l_ab = _SupConMlDirection.apply(na, nb_all, sets, sets_all, w, offset, t, coef, float(min_temperature), grads)
+        l_ba = _SupConMlDirection.apply(nb, na_all, sets, sets_all, w, offset, t, coef, float(min_temperature), grads)
+        share = l_ab + l_ba              # this rank's rows' share of the global objective
     if world == 1:
         return share
     total = share.detach().clone()
@@ -1148,7 +1236,7 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
     implementation, ignored for ``info_nce``); ``contrastive="supervised"`` takes ``supervised_contrastive(za, zb, labels,
     temperature)`` -- handed ``low_memory`` when it is not None (False: the tile-GEMM form), its own default (the streaming form)
     otherwise -- and ``contrastive="multilabel"`` takes ``multilabel_contrastive(za, zb, labels, label_weighting,
-    temperature)`` with ``labels`` the label sets (multi-hot rows or int64 masks); these two are the only forms that take
+    temperature)``, handed ``low_memory`` in the same way, with ``labels`` the label sets (multi-hot rows or int64 masks); these two are the only forms that take
     ``labels``, and ``label_weighting`` ("overlap" or "jaccard") is read by the multi-label form alone."""
     if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel"):
         raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid', 'supervised' or 'multilabel', got {contrastive!r}")
@@ -1163,7 +1251,10 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
         total = _plus(total, entropy_weight * masking.entropy_loss(entropy))
     if za is not None and zb is not None:
         if contrastive == "multilabel":
-            term = multilabel_contrastive(za, zb, labels, label_weighting, temperature, group, min_temperature)
+            if low_memory is None:
+                term = multilabel_contrastive(za, zb, labels, label_weighting, temperature, group, min_temperature)
+            else:
+                term = multilabel_contrastive(za, zb, labels, label_weighting, temperature, group, min_temperature, low_memory)
         elif contrastive == "supervised":
             if low_memory is None:
                 term = supervised_contrastive(za, zb, labels, temperature, group, min_temperature)

@@ -760,6 +760,61 @@ int aecf_supcon_ml_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32
                            float* d_temperature, void* workspace, size_t workspace_bytes, void* stream);
 int aecf_label_sets_pack(int64_t rows, int32_t classes, int32_t kind, const void* multi_hot, uint64_t* sets, void* stream);
 
+/* ---- multi-label contrastive loss, tile-GEMM form: BOTH directions of the symmetric loss from ONE block of logits ----
+ * aecf_supcon_sym_* with a SET of classes per row in place of its label: row_sets [rows] and col_sets [cols] are DEVICE arrays of
+ * one uint64 per row, bit c = class c (aecf_label_sets_pack makes them).  This rank's local rows a [rows,d] of one view (global
+ * indices row_offset .. row_offset + rows) run against all gathered rows b [cols,d] of the other view, unit-norm bf16 rows:
+ *   w_ij  = 1                                            if j == row_offset + i   (the partner, by INDEX, whatever the sets say)
+ *         = [A_i & B_j != 0]                             weighting AECF_SETS_OVERLAP
+ *         = popcount(A_i & B_j) / popcount(A_i | B_j)    weighting AECF_SETS_JACCARD: all 64 bits, ONE correctly rounded float32
+ *                                                        division, 0 for an empty union; an empty set is nobody's positive by label
+ *   x_ij  = a_i . b_j / Tc,  Tc = max(*temperature, min_temperature),  E_ij = exp(x_ij - 1/Tc)   (the shift of the InfoNCE tile form)
+ *   l_i = sum_j E_ij    Wr_i = sum_j w_ij   Xr_i = sum_j w_ij x_ij      rows of this rank
+ *   c_j = sum_i E_ij    Wc_j = sum_i w_ij   Xc_j = sum_i w_ij x_ij      columns, summed over the ranks
+ *   loss_rows[i] = [log l_i + 1/Tc - Xr_i / Wr_i] + [log c_p + 1/Tc - Xc_p / Wc_p],   p = row_offset + i        WITHOUT coef
+ *   W_ij  = coef/Tc * upstream * ( E_ij (1/l_i + 1/c_j) - w_ij (1/Wr_i + 1/Wc_j) )
+ *   da = W b [rows,d]      db = W^T a [cols,d] (this rank's share)      dT = -(1/Tc) sum_i a_i . da_i  (0 where *temperature < min_temperature)
+ * Both weightings are symmetric in (A, B), so one weight matrix serves both directions; the column direction is DEFINED on the
+ * transpose of the same call's matrix.  With sets shared by the views this is the sum of two aecf_supcon_ml_fwd_bwd directions;
+ * with all sets empty or pairwise disjoint every output has the bits of aecf_nce_sym_pass1_dt / _loss_dt / _grads_dt; with one-hot
+ * sets both weightings give the same bits, the column sums of E and of w those of aecf_supcon_sym_pass1 on the matching labels.
+ *   pass1: the logits GEMM with a dense set epilogue, one instance per weighting.  It writes E once as bf16 (workspace) and leaves
+ *          the row and column sums of E exactly as the InfoNCE form does; then every tile runs a sweep over its accumulators that
+ *          adds, per row and per column, the float32 sum of w and the float32 sum of w * raw score a_i . b_j (each product fused
+ *          into its addition), the partner and the padding excluded: the partner joins later from its own float32 dot with weight
+ *          1.  Fixed-order partials, no atomics.  col_stats [3][cols] float32 gets this rank's column statistics:
+ *          c | sum of the label weights | sum of w * raw score.
+ *   caller: all-reduce (sum) of col_stats over the ranks (nothing to do on one rank)
+ *   loss:  loss_rows [rows] from the summed col_stats, with W = 1 + weight sum and X = (dot + sum) / Tc in both directions;
+ *          prepares 1/l, 1/Wr (rows) and 1/c, 1/Wc (columns) in the workspace.
+ *   grads: the weights in place over E (w formed again from the words), then da and this rank's share of db as in
+ *          aecf_supcon_sym_grads: float32 or bf16 (grad_dtype), multiplied by upstream[0] (a DEVICE float32 scalar, NULL = 1);
+ *          d_temperature (may be NULL) is WRITTEN with this rank's share of dL/dT times upstream[0].  It consumes the stored
+ *          block: it runs once per pass1.
+ * Served: the shapes of aecf_supcon_sym_*: bf16 rows, d % 64 == 0, 64 <= d <= 4096, min_temperature >= 0.025, cols <= 2^24.
+ * Workspace: the layout and size of aecf_supcon_sym_workspace_bytes, the weight sums in the count slots:
+ *   E [Rp][Cp] bf16 | row partials [3][Cp/256][Rp] | column partials [3][Rp/256][Cp] | row statistics [3][Rp] | 1/l [Rp] |
+ *   1/Wr [Rp] | 1/c [Cp] | 1/Wc [Cp] | the partner's exponential [Rp] | da slabs [splits][rows][d], each piece rounded up to 256
+ *   bytes, + 256 bytes.  The query answers 0 where the shape is not served.
+ * Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host (the calls capture into a
+ * graph), nothing read from the workspace before it is written; no float atomics, fixed-order partial sums: the same inputs give
+ * the same bits.  Checks before any launch, in the order of aecf_supcon_sym_*: sizes (AECF_ERR_BAD_DIMS), then d,
+ * min_temperature < 0.025, cols > 2^24, an unknown weighting, or a grad_dtype other than bf16 / float32 (AECF_ERR_UNSUPPORTED),
+ * then NULL pointers (AECF_ERR_NULL_POINTER; upstream and d_temperature may be NULL), then the workspace size
+ * (AECF_ERR_WORKSPACE). */
+size_t aecf_supcon_ml_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d);      /* 0: not served */
+int aecf_supcon_ml_sym_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                             float min_temperature, const void* a, const void* b, const uint64_t* row_sets,
+                             const uint64_t* col_sets, int32_t weighting, void* workspace, size_t workspace_bytes,
+                             float* col_stats /* [3][cols] */, void* stream);
+int aecf_supcon_ml_sym_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                            float min_temperature, const void* a, const void* b, const float* col_stats /* summed over ranks */,
+                            void* workspace, size_t workspace_bytes, float* loss_rows, void* stream);
+int aecf_supcon_ml_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                             float min_temperature, float coef, const void* a, const void* b, const uint64_t* row_sets,
+                             const uint64_t* col_sets, int32_t weighting, void* workspace, size_t workspace_bytes,
+                             const float* upstream, int32_t grad_dtype, void* da, void* db, float* d_temperature, void* stream);
+
 /* ---- retrieval ranks of the contrastive views (build-defined like the contrastive terms they evaluate: the reference has no
  * contrastive term and no retrieval evaluation, so there are no reference lines to cite) ----
  * Local rows a [rows,d] (global indices row_offset .. row_offset + rows) against all gathered rows b [cols,d] of the other view,
