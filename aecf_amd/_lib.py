@@ -199,6 +199,10 @@ _SYMBOLS = [
     ("aecf_supcon_fwd_bwd", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # the pooled form (NT-Xent, SupCon over both views): the same call with the key at self_offset + i excluded for row i
+    ("aecf_supcon_pool_fwd_bwd", c_int,
+     [c_int64, c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     # supervised contrastive loss, symmetric, on the tile GEMMs: pass 1 (column statistics out), loss, gradients
     ("aecf_supcon_sym_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
     ("aecf_supcon_sym_pass1", c_int,

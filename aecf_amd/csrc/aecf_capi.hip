@@ -951,6 +951,24 @@ int aecf_supcon_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t 
     return launch_status();
 }
 
+int aecf_supcon_pool_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int64_t self_offset, int32_t d, const float* temperature,
+                             float min_temperature, float coef, const void* q, const void* k, const int64_t* q_labels,
+                             const int64_t* k_labels, float* loss_rows, float* dq, float* dk, float* d_temperature, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (self_offset < 0 || self_offset + rows > cols || self_offset == row_offset) return AECF_ERR_BAD_DIMS;
+    if (!supcon_flash_supported(d)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !q || !k || !q_labels || !k_labels || !loss_rows || !workspace || (dq == nullptr) != (dk == nullptr))
+        return AECF_ERR_NULL_POINTER;
+    if (!dq && d_temperature) return AECF_ERR_NULL_POINTER;      // the loss-only mode forms no gradient to take dT from
+    if (workspace_bytes < supcon_flash_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    launch_supcon_pool_flash(rows, cols, row_offset, self_offset, d, dt, coef, q, k, q_labels, k_labels, loss_rows, dq, dk, workspace,
+                             (hipStream_t)stream);
+    return launch_status();
+}
+
 // ---- the same loss, symmetric, on the tile GEMMs (include/aecf_hip.h, "supervised contrastive loss, tile-GEMM form")
 
 size_t aecf_supcon_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {

@@ -321,6 +321,11 @@ size_t supcon_flash_workspace_bytes(int64_t rows, int64_t cols, int d);
 void launch_supcon_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef, const void* q,
                          const void* k, const int64_t* q_labels, const int64_t* k_labels, float* loss_rows, float* dq, float* dk,
                          void* workspace, hipStream_t s);
+// The pooled form (NT-Xent, SupCon over both views): the same passes with key self_offset + i excluded for local row i -- from the
+// maximum, the sum, the positives and both gradient products.  Workspace as launch_supcon_flash.
+void launch_supcon_pool_flash(int64_t rows, int64_t cols, int64_t row_offset, int64_t self_offset, int d, const NceDevTemp& dt,
+                              float coef, const void* q, const void* k, const int64_t* q_labels, const int64_t* k_labels,
+                              float* loss_rows, float* dq, float* dk, void* workspace, hipStream_t s);
 
 // Supervised contrastive loss on the tile GEMMs (aecf_nce_gemm.hip): both directions of the symmetric loss from ONE block of
 // logits, labels shared by the two views.  The logits pass (EPI_SUP) is InfoNCE's plus the count and the float32 raw-score sum of

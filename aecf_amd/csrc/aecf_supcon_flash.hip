@@ -25,6 +25,23 @@
 // and a few scalars beside what the no-rescale roles of the other forms hold, and still fit where InfoNCE's DK role fits: the
 // output columns come from one launch up to d = 768 (252 / 254 VGPRs + 196 AGPRs there) and from two at d = 1024 (CSPLIT, S
 // formed in each), every instance free of scratch.
+//
+// The pooled forms (aecf_supcon_pool_fwd_bwd: NT-Xent, the supervised contrastive loss over both views).  The keys are one pool
+// that holds the anchors themselves, and key self_offset + i is EXCLUDED for local row i: the three roles have a compile-time
+// SELF variant (sup_pool_kernel; sup_flash_kernel is the body with SELF = false, its instances and their bits as before).
+//   match(i, j) = j != self_offset + i and ((j == row_offset + i) or (lq[i] >= 0 and lq[i] == lk[j]))
+//   lse_i, the softmax and G run over j != self_offset + i; dk[self_offset + i] gets nothing from row i
+// The exclusion comes before the label compare -- in real use the excluded key IS the anchor: it carries the anchor's label and
+// the highest score there is, 1/T.  STATS gives it x = -inf (nothing for m, l, the count or the sum of the matched x), DQ and DK
+// give it weight 0 (a select, not a product: its exponential may overflow); in DK the test is "streamed row a == stationary key
+// b - self_offset", the mirror of pos_t.
+// An all -inf sub-tile: with an exclusion a sub-tile, or a whole split, can hold one valid key that is excluded for a row (the
+// split rule cuts where it likes), so that row reaches the sum with tmax = -inf while run_m is still -inf, and exp(pv - run_m)
+// would be exp(-inf + inf) = NaN.  SELF shifts by 0 instead of run_m in that state: every term is exp(-inf) = 0, and a split that
+// never sees another key leaves (m = -inf, l = 0, count = 0, psum = 0), which sup_rows_kernel merges as nothing.  Some split holds
+// the partner (self_offset != row_offset), so the merged maximum is finite and n >= 1.
+// Registers (profiles/supcon_pool_resources.txt): one more per-lane index; the gradient roles at d = 768 / 1024 go from 252 - 255
+// to 251 - 256 VGPRs, no scratch, the same CSPLIT.
 #include <math.h>
 
 #include "aecf_flash_stream.h"
@@ -62,13 +79,27 @@ __device__ __forceinline__ bool sup_same(int64_t mine, int64_t other) {
     return (MINE_IS_QUERY ? mine : other) >= 0 && mine == other;
 }
 
+// S / T rounded to float32 as the STATS role stores it (its x enters a maximum), never fused into the subtraction of lse: the SELF
+// gradient roles form their exponent from it, so a row whose only key is its partner has x - lse = 0 and a weight of exactly 0.
+// (The instances without an exclusion keep their contracted form and their bits.)
+template <bool SELF>
+__device__ __forceinline__ float sup_scaled(float s, float inv_temp) {
+    if constexpr (SELF) {
+#pragma clang fp contract(off)
+        return s * inv_temp;
+    } else {
+        return s * inv_temp;
+    }
+}
+
 // STATS: online softmax statistics of stationary row b = r16 (replicated over lg) and this lane's share of its matches
+template <bool SELF>
 struct SupStatsTerm {
     static constexpr bool FENCED = false;
     float inv_temp;
     const int64_t* lab;             // of the range's first streamed row
     int64_t mine;
-    int pos_t;
+    int pos_t, self_t;
     float run_m = -INFINITY, run_l = 0.f, psum = 0.f;
     int count = 0;
     template <int NC>
@@ -78,7 +109,7 @@ struct SupStatsTerm {
         for (int r = 0; r < 4; ++r) {
             const int a = a0 + 4 * lg + r;
             float x = -INFINITY;
-            if (a < len) {
+            if (a < len && !(SELF && a == self_t)) {              // the excluded key: x = -inf, never a positive
                 x = sacc[r] * inv_temp;
                 if (a == pos_t || sup_same<true>(mine, lab[a])) {
                     psum += x;
@@ -95,9 +126,12 @@ struct SupStatsTerm {
             run_l *= (run_m == -INFINITY) ? 0.f : expf(run_m - new_m);
             run_m = new_m;
         }
+        // SELF: a row whose only valid keys so far were its excluded one still has run_m = -inf; every pv is -inf then, and
+        // exp(-inf - 0) = 0 where exp(-inf + inf) is NaN.  (Without an exclusion the first sub-tile has a finite maximum.)
+        const float shift = SELF && run_m == -INFINITY ? 0.f : run_m;
         float ts_ = 0.f;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) ts_ += expf(pv[r] - run_m);
+        for (int r = 0; r < 4; ++r) ts_ += expf(pv[r] - shift);
         ts_ += __shfl_xor(ts_, 16, 64);
         ts_ += __shfl_xor(ts_, 32, 64);
         run_l += ts_;
@@ -105,20 +139,21 @@ struct SupStatsTerm {
 };
 
 // DQ: the weight of key a for the lane's query b from that query's lse and 1 / n
+template <bool SELF>
 struct SupDqTerm {
     static constexpr bool FENCED = false;
     float inv_temp, ct, lse_b, inv_n_b;
     const int64_t* lab;             // key labels, of the range's first streamed row
     int64_t mine;
-    int pos_t;
+    int pos_t, self_t;
     template <int NC>
     __device__ __forceinline__ void weights(const f32x4& sacc, int a0, int lg, int r16, int len, f32x4 (&oacc)[NC], float (&pv)[4]) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int a = a0 + 4 * lg + r;                        // key
             float v = 0.f;
-            if (a < len) {
-                v = expf(sacc[r] * inv_temp - lse_b);
+            if (a < len && !(SELF && a == self_t)) {              // the excluded key: weight 0 (its exp may overflow)
+                v = expf(sup_scaled<SELF>(sacc[r], inv_temp) - lse_b);
                 if (a == pos_t || sup_same<true>(mine, lab[a])) v -= inv_n_b;
                 v *= ct;
             }
@@ -128,6 +163,7 @@ struct SupDqTerm {
 };
 
 // DK: the same weight for the lane's key b and local query a: lse, 1 / n and the label are the streamed row's
+template <bool SELF>
 struct SupDkTerm {
     static constexpr bool FENCED = false;
     float inv_temp, ct;
@@ -135,15 +171,15 @@ struct SupDkTerm {
     const float* inv_n;
     const int64_t* lab;
     int64_t mine;
-    int pos_t;
+    int pos_t, self_t;
     template <int NC>
     __device__ __forceinline__ void weights(const f32x4& sacc, int a0, int lg, int r16, int len, f32x4 (&oacc)[NC], float (&pv)[4]) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int a = a0 + 4 * lg + r;                        // local q row
             float v = 0.f;
-            if (a < len) {
-                v = expf(sacc[r] * inv_temp - lse[a]);
+            if (a < len && !(SELF && a == self_t)) {              // the query this key is excluded for: weight 0
+                v = expf(sup_scaled<SELF>(sacc[r], inv_temp) - lse[a]);
                 if (a == pos_t || sup_same<false>(mine, lab[a])) v -= inv_n[a];
                 v *= ct;
             }
@@ -153,8 +189,8 @@ struct SupDkTerm {
 };
 
 // CSPLIT > 1: the output columns come from CSPLIT launches of D / CSPLIT columns each (cpart = which), every one forming S
-template <int KT, int ROLE, int CSPLIT>
-__global__ __launch_bounds__(256, 1) void sup_flash_kernel(SupFlashArgs p, int cpart) {
+template <int KT, int ROLE, int CSPLIT, bool SELF>
+__device__ __forceinline__ void sup_flash_body(const SupFlashArgs& p, int cpart, int64_t self_offset) {
     constexpr int D = 32 * KT, NC = ROLE == SUP_STATS ? 1 : D / 16 / CSPLIT;
     const float inv_temp = nce_dev_inv_temp(p.temp, p.min_temp);
     const int c_first = cpart * NC;
@@ -165,9 +201,10 @@ __global__ __launch_bounds__(256, 1) void sup_flash_kernel(SupFlashArgs p, int c
     const int64_t mine = live ? p.stat_lab[b] : (int64_t)-1;
     f32x4 oacc[NC];
     if constexpr (ROLE == SUP_STATS) {
-        SupStatsTerm term;
+        SupStatsTerm<SELF> term;
         term.inv_temp = inv_temp; term.lab = p.strm_lab + f.m_beg; term.mine = mine;
         term.pos_t = flash_rel(p.row_offset + b, f);
+        if constexpr (SELF) term.self_t = flash_rel(self_offset + b, f);
         flash_stream<KT, 1, false>(term, f, p.stat, p.ns, p.strm, 0, smem, oacc);
         float ps = term.psum;                                     // a lane holds a quarter of row b's matches
         int cnt = term.count;
@@ -183,21 +220,35 @@ __global__ __launch_bounds__(256, 1) void sup_flash_kernel(SupFlashArgs p, int c
             p.part_ps[o] = ps;
         }
     } else if constexpr (ROLE == SUP_DQ) {
-        SupDqTerm term;
+        SupDqTerm<SELF> term;
         term.inv_temp = inv_temp; term.ct = p.coef * inv_temp; term.lab = p.strm_lab + f.m_beg; term.mine = mine;
         // (a lane past the last row is never stored; lse = +inf gives it weight 0 instead of exp(S/T), which overflows at low T)
         term.lse_b = live ? p.lse[b] : INFINITY; term.inv_n_b = live ? p.inv_n[b] : 0.f;
         term.pos_t = flash_rel(p.row_offset + b, f);
+        if constexpr (SELF) term.self_t = flash_rel(self_offset + b, f);
         flash_stream<KT, NC, true>(term, f, p.stat, p.ns, p.strm, c_first, smem, oacc);
         if (live) flash_store<NC, false>(p.part_o + ((int64_t)f.split * p.ns + b) * D, c_first, f.lg, oacc);
     } else {
-        SupDkTerm term;
+        SupDkTerm<SELF> term;
         term.inv_temp = inv_temp; term.ct = p.coef * inv_temp; term.lse = p.lse + f.m_beg; term.inv_n = p.inv_n + f.m_beg;
         term.lab = p.strm_lab + f.m_beg; term.mine = mine;
         term.pos_t = flash_rel(b - p.row_offset, f);
+        if constexpr (SELF) term.self_t = flash_rel(b - self_offset, f);
         flash_stream<KT, NC, true>(term, f, p.stat, p.ns, p.strm, c_first, smem, oacc);
         if (live) flash_store<NC, false>(p.out + b * D, c_first, f.lg, oacc);
     }
+}
+
+template <int KT, int ROLE, int CSPLIT>
+__global__ __launch_bounds__(256, 1) void sup_flash_kernel(SupFlashArgs p, int cpart) {
+    sup_flash_body<KT, ROLE, CSPLIT, false>(p, cpart, 0);
+}
+
+// the pooled form (aecf_supcon_pool_fwd_bwd): key self_offset + i is excluded for local row i (an argument of its own: the
+// argument block of the instances above stays what it was)
+template <int KT, int ROLE, int CSPLIT>
+__global__ __launch_bounds__(256, 1) void sup_pool_kernel(SupFlashArgs p, int cpart, int64_t self_offset) {
+    sup_flash_body<KT, ROLE, CSPLIT, true>(p, cpart, self_offset);
 }
 
 // the live splits of a row merged in order: m* = max m_s, l* = sum l_s e^(m_s - m*), n = sum count_s, psum = sum psum_s;
@@ -241,14 +292,20 @@ __global__ __launch_bounds__(256) void sup_dq_kernel(const unsigned short* q, co
     if (lane == 0) tq[i] = t;
 }
 
-template <int KT, int ROLE>
-void launch_sup_role(const SupFlashArgs& a, int blocks, hipStream_t s) {
+template <int KT, int ROLE, bool SELF>
+void launch_sup_role(const SupFlashArgs& a, int64_t self_offset, int blocks, hipStream_t s) {
     constexpr int D = 32 * KT;
     constexpr int CSPLIT = ROLE != SUP_STATS && KT >= 32 ? 2 : 1;
     const size_t smem = (size_t)2 * 32 * 2 * D;
-    auto kern = sup_flash_kernel<KT, ROLE, CSPLIT>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    for (int cpart = 0; cpart < CSPLIT; ++cpart) kern<<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a, cpart);
+    if constexpr (SELF) {
+        auto kern = sup_pool_kernel<KT, ROLE, CSPLIT>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        for (int cpart = 0; cpart < CSPLIT; ++cpart) kern<<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a, cpart, self_offset);
+    } else {
+        auto kern = sup_flash_kernel<KT, ROLE, CSPLIT>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        for (int cpart = 0; cpart < CSPLIT; ++cpart) kern<<<dim3((unsigned)blocks), dim3(256), smem, s>>>(a, cpart);
+    }
 }
 
 }  // namespace
@@ -262,9 +319,12 @@ size_t supcon_flash_workspace_bytes(int64_t rows, int64_t cols, int d) {
     return ((size_t)ks * rows * (d + 4) + (size_t)3 * rows) * sizeof(float) + 1024;
 }
 
-void launch_supcon_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef, const void* q,
-                         const void* k, const int64_t* q_labels, const int64_t* k_labels, float* loss_rows, float* dq, float* dk,
-                         void* workspace, hipStream_t s) {
+namespace {
+
+template <bool SELF>
+void launch_sup_passes(int64_t rows, int64_t cols, int64_t row_offset, int64_t self_offset, int d, const NceDevTemp& dt, float coef,
+                       const void* q, const void* k, const int64_t* q_labels, const int64_t* k_labels, float* loss_rows, float* dq,
+                       float* dk, void* workspace, hipStream_t s) {
     const FlashSplit sp = flash_split(rows, cols);
     float* ws = reinterpret_cast<float*>(workspace);
     float* part_o = ws;
@@ -286,15 +346,29 @@ void launch_supcon_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, 
     const int q_blocks = (int)(((rows + 63) / 64) * sp.live), k_blocks = (int)((cols + 63) / 64);
     dispatch_kt(d, [&](auto kt) {
         constexpr int KT = decltype(kt)::value;
-        launch_sup_role<KT, SUP_STATS>(a, q_blocks, s);
+        launch_sup_role<KT, SUP_STATS, SELF>(a, self_offset, q_blocks, s);
         sup_rows_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s>>>(part_m, part_l, a.part_cnt, part_ps, rows, sp.live,
                                                                                    lse, inv_n, loss_rows);
         if (!dq) return;
-        launch_sup_role<KT, SUP_DQ>(a, q_blocks, s);
+        launch_sup_role<KT, SUP_DQ, SELF>(a, self_offset, q_blocks, s);
         sup_dq_kernel<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s>>>((const unsigned short*)q, part_o, rows, d, sp.live, dq, tq);
-        launch_sup_role<KT, SUP_DK>(b, k_blocks, s);
+        launch_sup_role<KT, SUP_DK, SELF>(b, self_offset, k_blocks, s);
     });
     if (dq && dt.d_t) launch_nce_dtemp(tq, rows, 1, dt, s);
+}
+
+}  // namespace
+
+void launch_supcon_flash(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef, const void* q,
+                         const void* k, const int64_t* q_labels, const int64_t* k_labels, float* loss_rows, float* dq, float* dk,
+                         void* workspace, hipStream_t s) {
+    launch_sup_passes<false>(rows, cols, row_offset, 0, d, dt, coef, q, k, q_labels, k_labels, loss_rows, dq, dk, workspace, s);
+}
+
+void launch_supcon_pool_flash(int64_t rows, int64_t cols, int64_t row_offset, int64_t self_offset, int d, const NceDevTemp& dt,
+                              float coef, const void* q, const void* k, const int64_t* q_labels, const int64_t* k_labels,
+                              float* loss_rows, float* dq, float* dk, void* workspace, hipStream_t s) {
+    launch_sup_passes<true>(rows, cols, row_offset, self_offset, d, dt, coef, q, k, q_labels, k_labels, loss_rows, dq, dk, workspace, s);
 }
 
 }  // namespace aecf

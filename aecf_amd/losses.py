@@ -639,6 +639,48 @@ class _SupConDirection(torch.autograd.Function):
         return (dq * g).to(qd), (dk * g).to(kd), None, None, None, g_t, None, None, None
 
 
+class _SupConPoolDirection(torch.autograd.Function):
+    """aecf_supcon_pool_fwd_bwd: ``_SupConDirection`` over a pool of keys that holds the anchors themselves.  ``k_all`` is the one
+    key buffer of both views; local row i has its partner at ``row_offset + i`` and itself at ``self_offset + i``, and that key is
+    left out of the log-sum-exp, of the positives and of both gradients.  Forward, backward, ``grads`` and the temperature: as
+    ``_SupConDirection``; the gradient on ``k_all`` is the whole pool's, so autograd splits it over the two views."""
+
+    @staticmethod
+    def forward(ctx, q, k_all, q_labels, k_labels, row_offset, self_offset, temperature, coef, min_temperature, grads):
+        lib = _lib.load()
+        rows, d = q.shape
+        cols = k_all.shape[0]
+        dev = q.device
+        ws_bytes = lib.aecf_supcon_workspace_bytes(rows, cols, d) if q.dtype == torch.bfloat16 and k_all.dtype == torch.bfloat16 else 0
+        if ws_bytes == 0:
+            raise NotImplementedError(f"aecf_amd: the pooled contrastive losses need bfloat16 rows with d in {SUPCON_WIDTHS}; "
+                                      f"got {q.dtype}, d = {d}")
+        qc, kc = q.detach().contiguous(), k_all.detach().contiguous()
+        lq, lk = q_labels.contiguous(), k_labels.contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        loss_rows = torch.empty(rows, **f32)
+        dq = dk = d_t = None
+        if grads:
+            dq, dk = torch.empty(rows, d, **f32), torch.empty(cols, d, **f32)
+            d_t = torch.empty(1, **f32) if ctx.needs_input_grad[6] else None
+        _lib.check(lib.aecf_supcon_pool_fwd_bwd(rows, cols, int(row_offset), int(self_offset), d, _ptr(temperature.detach()),
+                                                float(min_temperature), float(coef), _ptr(qc), _ptr(kc), _ptr(lq), _ptr(lk),
+                                                _ptr(loss_rows), _ptr(dq), _ptr(dk), _ptr(d_t), _ptr(ws), ws_bytes, _stream()),
+                   "aecf_supcon_pool_fwd_bwd")
+        ctx.save_for_backward(dq, dk, d_t)
+        ctx.meta = (q.dtype, k_all.dtype, temperature.shape)
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        dq, dk, d_t = ctx.saved_tensors
+        qd, kd, t_shape = ctx.meta
+        g = d_loss.detach().to(torch.float32)
+        g_t = (d_t * g).reshape(t_shape) if d_t is not None else None
+        return (dq * g).to(qd), (dk * g).to(kd), None, None, None, None, g_t, None, None, None
+
+
 class _SupConSymmetric(torch.autograd.Function):
     """aecf_supcon_sym_pass1 / _loss / _grads: BOTH directions of the symmetric supervised contrastive loss from one block of
     logits (local rows of view a against the gathered rows of view b), the labels shared by the two views.  Modelled on
@@ -716,7 +758,8 @@ def _supcon_tile_refusal(z: torch.Tensor, zb: torch.Tensor, cols: int, min_tempe
 
 
 def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Tensor, temperature: Union[float, torch.Tensor] = 0.07,
-                           group=None, min_temperature: float = MIN_TEMPERATURE, low_memory: Optional[bool] = True) -> torch.Tensor:
+                           group=None, min_temperature: float = MIN_TEMPERATURE, low_memory: Optional[bool] = True,
+                           intra_view: bool = False) -> torch.Tensor:
     """Symmetric supervised contrastive loss (Khosla et al. 2020, "L_out") between the local rows of two views, keys from every
     rank of ``group``: the positives of row i of one view are row i of the other view and every row of the other view that
     carries the same label,
@@ -746,7 +789,22 @@ def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Ten
     Data parallel: the streaming form all-gathers both views, the labels and the row counts; the tile form gathers view b, the
     labels and the row counts only and all-reduces the [3, b_all] column statistics between its passes.  The convention is
     ``info_nce``'s -- the returned value is the global loss on every rank and the local term carries ``world`` for an averaging
-    gradient reduce."""
+    gradient reduce.
+
+    ``intra_view``: ``False`` (the default) is the cross-view loss above.  ``True`` is the loss as published, over ONE pool of
+    the 2 B_all rows of both views: every row is an anchor against the other 2 B_all - 1 rows, itself left out,
+
+        L = 1 / (2 B_all) * sum over the 2 B_all anchors of [ logsumexp_{k != self} x - mean_{k in positives} x ],
+
+    the positives being the partner and every row of EITHER view with the same non-negative label, the anchor excepted.  It
+    differs from the reference code of Khosla et al. (``SupConLoss``) only by that code's ``T / base_T`` factor.  Both
+    directions run the streaming kernels (aecf_supcon_pool_fwd_bwd) against one key buffer, the gathered rows of view b then
+    those of view a; it needs bfloat16 rows, d in 128 .. 1024 as above and 2 B_all < 2^31; ``low_memory`` True or None take
+    it, ``False`` raises NotImplementedError (the tile form has no intra-view keys).  With every label negative it is
+    ``nt_xent``."""
+    if intra_view and low_memory is False:
+        raise NotImplementedError("aecf_amd: the tile form of the supervised contrastive loss has no intra-view keys (it forms "
+                                  "the a x b block only); intra_view=True runs the streaming form, low_memory=True or None")
     _require_device(za, "za")
     _require_device(zb, "zb")
     if za.shape != zb.shape or za.dim() != 2:
@@ -755,6 +813,8 @@ def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Ten
     if low_memory not in (True, False, None):
         raise ValueError(f"aecf_amd: low_memory must be True, False or None, got {low_memory!r}")
     streams = za.dtype == torch.bfloat16 and zb.dtype == torch.bfloat16 and za.shape[1] in SUPCON_WIDTHS
+    if intra_view:
+        low_memory = True
     if low_memory is True and not streams:
         raise NotImplementedError(f"aecf_amd: the supervised contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; got "
                                   f"{za.dtype} and {zb.dtype}, d = {za.shape[1]}")
@@ -790,7 +850,16 @@ def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Ten
     nb_all = dp.all_gather_rows(nb, group, sizes=sizes) if world > 1 else nb
     lab_all = dp.all_gather_rows(lab, group, sizes=sizes) if world > 1 else lab
     coef = 0.5 / float(b_all)
-    if tile:
+    if intra_view:
+        if 2 * b_all >= 2 ** 31:
+            raise NotImplementedError(f"aecf_amd: the pooled supervised contrastive loss needs 2 b_all < 2^31 keys, got b_all = {b_all}")
+        na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
+        pool, lab_pool = torch.cat([nb_all, na_all]), torch.cat([lab_all, lab_all])
+        grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb, t))
+        l_a = _SupConPoolDirection.apply(na, pool, lab, lab_pool, offset, b_all + offset, t, coef, float(min_temperature), grads)
+        l_b = _SupConPoolDirection.apply(nb, pool, lab, lab_pool, b_all + offset, offset, t, coef, float(min_temperature), grads)
+        share = l_a + l_b                # this rank's anchors' share of the global objective
+    elif tile:
         # both directions from the one block of logits this rank owns: view a is never gathered
         share = _SupConSymmetric.apply(na, nb_all, lab, lab_all, offset, t, coef, group, float(min_temperature))
     else:
@@ -805,6 +874,22 @@ def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Ten
     torch.distributed.all_reduce(total, group=group)
     scaled = share * world
     return scaled + (total - scaled.detach())
+
+
+def nt_xent(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch.Tensor] = 0.07, group=None,
+            min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
+    """NT-Xent (SimCLR, Chen et al. 2020) between the local rows of two views, keys from every rank of ``group``: the 2 B_all
+    rows of both views are one pool, and every row is an anchor whose positive is its partner and whose negatives are the other
+    2 B_all - 2 rows of BOTH views,
+
+        L = 1 / (2 B_all) * sum over the 2 B_all anchors of [ logsumexp_{k != self} x_k - x_partner ],   x = n . n_k / max(T, min_temperature)
+
+    ``supervised_contrastive(za, zb, labels = all -1, ..., intra_view=True)``: the same streaming kernels
+    (aecf_supcon_pool_fwd_bwd), the same requirements (bfloat16 on a ROCm device, d in 128, 256, 384, 512, 768, 1024, no torch
+    fallback), and the same temperature, ``torch.no_grad()`` and data-parallel behaviour."""
+    _require_device(za, "za")
+    labels = torch.full((za.shape[0],), -1, dtype=torch.int64, device=za.device)
+    return supervised_contrastive(za, zb, labels, temperature, group, min_temperature, True, True)
 
 
 SET_CLASSES = 64                                        # one uint64 per row: the most classes a label set can name
@@ -1229,7 +1314,8 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
                      contrastive_weight: float = 1.0, temperature: Union[float, torch.Tensor] = 0.07, group=None,
                      min_temperature: float = MIN_TEMPERATURE, contrastive: str = "info_nce",
                      bias: Union[None, float, torch.Tensor] = None, low_memory: Optional[bool] = None,
-                     labels: Optional[torch.Tensor] = None, label_weighting: str = "overlap") -> torch.Tensor:
+                     labels: Optional[torch.Tensor] = None, label_weighting: str = "overlap",
+                     intra_view: bool = False) -> torch.Tensor:
     """task + entropy_weight * entropy_loss(entropy) [ref README.md:205-208] + contrastive_weight * info_nce(za, zb)
     (``temperature`` / ``min_temperature``: as for ``info_nce``).  ``contrastive="sigmoid"`` takes ``sigmoid_contrastive(za, zb,
     temperature, bias)`` as the contrastive term instead (``bias``: None = its default of -10; ``low_memory``: its choice of
@@ -1237,9 +1323,12 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
     temperature)`` -- handed ``low_memory`` when it is not None (False: the tile-GEMM form), its own default (the streaming form)
     otherwise -- and ``contrastive="multilabel"`` takes ``multilabel_contrastive(za, zb, labels, label_weighting,
     temperature)``, handed ``low_memory`` in the same way, with ``labels`` the label sets (multi-hot rows or int64 masks); these two are the only forms that take
-    ``labels``, and ``label_weighting`` ("overlap" or "jaccard") is read by the multi-label form alone."""
-    if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel"):
-        raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid', 'supervised' or 'multilabel', got {contrastive!r}")
+    ``labels``, and ``label_weighting`` ("overlap" or "jaccard") is read by the multi-label form alone.  ``contrastive="nt_xent"``
+    takes ``nt_xent(za, zb, temperature)``, the pool of both views without labels; ``intra_view`` is handed to the supervised
+    form (True: the same pool with label positives from either view) and read by no other."""
+    if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel", "nt_xent"):
+        raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid', 'supervised', 'multilabel' or 'nt_xent', got "
+                         f"{contrastive!r}")
     if contrastive in ("supervised", "multilabel") and labels is None:
         raise ValueError(f"aecf_amd: contrastive={contrastive!r} needs labels")
     if contrastive not in ("supervised", "multilabel") and labels is not None:
@@ -1257,11 +1346,13 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
                 term = multilabel_contrastive(za, zb, labels, label_weighting, temperature, group, min_temperature, low_memory)
         elif contrastive == "supervised":
             if low_memory is None:
-                term = supervised_contrastive(za, zb, labels, temperature, group, min_temperature)
+                term = supervised_contrastive(za, zb, labels, temperature, group, min_temperature, intra_view=intra_view)
             else:
-                term = supervised_contrastive(za, zb, labels, temperature, group, min_temperature, low_memory)
+                term = supervised_contrastive(za, zb, labels, temperature, group, min_temperature, low_memory, intra_view)
         elif contrastive == "sigmoid":
             term = sigmoid_contrastive(za, zb, temperature, -10.0 if bias is None else bias, group, min_temperature, low_memory)
+        elif contrastive == "nt_xent":
+            term = nt_xent(za, zb, temperature, group, min_temperature)
         else:
             term = info_nce(za, zb, temperature, group, min_temperature)
         total = _plus(total, contrastive_weight * term)

@@ -662,6 +662,30 @@ int aecf_supcon_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int32_t 
                         const int64_t* k_labels, float* loss_rows, float* dq, float* dk, float* d_temperature,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the pooled forms: NT-Xent (SimCLR) and the supervised contrastive loss over BOTH views ----
+ * aecf_supcon_fwd_bwd with ONE key excluded per row.  The caller puts both views into one key buffer k [cols,d] (the Python layer:
+ * the gathered rows of view b, then those of view a) with their labels k_labels [cols]; local row i (a row of either view) has its
+ * partner at row_offset + i and ITSELF at self_offset + i, and the latter takes no part in anything:
+ *   match(i, j) = j != self_offset + i and ((j == row_offset + i) or (q_labels[i] >= 0 and q_labels[i] == k_labels[j]))
+ *                 the exclusion comes first: the excluded key usually carries the row's own label and the highest score, 1/Tc
+ *   n_i    = sum_j match(i, j)   (>= 1: the partner)                  x_ij = (q_i . k_j) / Tc
+ *   lse_i  = logsumexp over j != self_offset + i of x_ij
+ *   loss_rows[i] = lse_i - (1 / n_i) sum_j match(i, j) x_ij            float32 [rows], WITHOUT coef
+ *   G_ij   = softmax over j != self_offset + i of x_ij - match / n_i,  G_ij = 0 at j = self_offset + i
+ *   dq = coef/Tc G k        dk = coef/Tc G^T q  (dk[self_offset + i] gets nothing from row i, and the other rows' shares)
+ *   d_temperature[0] = -(1/Tc) sum_i q_i . dq_i    (0 where *temperature < min_temperature; WRITTEN, may be NULL = not wanted)
+ * With every label negative this is one half of NT-Xent: 2 B anchors, each against the other 2 B - 1 rows of both views.
+ * The same three passes, SELF instances of the same kernels: the excluded key's x is -inf in the statistics pass (a sub-tile or a
+ * whole split whose only valid key is excluded for a row leaves that row at m = -inf, l = 0, count = 0, sum = 0, which the merge
+ * skips) and its weight is 0 in both gradient passes.  Loss-only mode, the workspace (layout and size: aecf_supcon_workspace_bytes
+ * answers for both calls), no atomics, no host read, capturable: all as aecf_supcon_fwd_bwd.  Checks, in its order: sizes (those
+ * of aecf_supcon_fwd_bwd, and 0 <= self_offset, self_offset + rows <= cols, self_offset != row_offset: AECF_ERR_BAD_DIMS), the
+ * width (AECF_ERR_UNSUPPORTED), the pointers (AECF_ERR_NULL_POINTER), the workspace size (AECF_ERR_WORKSPACE). */
+int aecf_supcon_pool_fwd_bwd(int64_t rows, int64_t cols, int64_t row_offset, int64_t self_offset, int32_t d,
+                             const float* temperature, float min_temperature, float coef, const void* q, const void* k,
+                             const int64_t* q_labels, const int64_t* k_labels, float* loss_rows, float* dq, float* dk,
+                             float* d_temperature, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- supervised contrastive loss, tile-GEMM form: BOTH directions of the symmetric loss from ONE block of logits ----
  * The symmetric loss gives both views the same labels, so the match relation is symmetric and one match matrix serves both
  * directions.  This rank owns its local rows a [rows,d] of one view (global indices row_offset .. row_offset + rows) against all
