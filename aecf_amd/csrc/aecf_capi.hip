@@ -1018,6 +1018,56 @@ int aecf_supcon_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_
     return launch_status();
 }
 
+// ---- NT-Xent on the tile GEMMs (include/aecf_hip.h, "NT-Xent, tile-GEMM form")
+
+size_t aecf_ntxent_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || rows > cols || cols > 0x7fffffff || !ntxent_gemm_supported(d, 0.025f)) return 0;
+    return ntxent_gemm_workspace_bytes(rows, cols, d);
+}
+
+int aecf_ntxent_sym_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                          const void* a_loc, const void* b_loc, const void* a_all, const void* b_all, void* workspace,
+                          size_t workspace_bytes, float* col_sums, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!ntxent_gemm_supported(d, min_temperature)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_loc || !a_all || !b_all || !workspace || !col_sums) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < ntxent_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_ntxent_gemm_pass1(rows, cols, row_offset, d, dt, a_loc, b_loc, a_all, b_all, workspace, col_sums, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_ntxent_sym_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                         const void* a_loc, const void* b_all, const float* col_sums, void* workspace, size_t workspace_bytes,
+                         float* loss_rows, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!ntxent_gemm_supported(d, min_temperature)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_all || !col_sums || !workspace || !loss_rows) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < ntxent_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_ntxent_gemm_loss(rows, cols, row_offset, d, dt, a_loc, b_all, col_sums, workspace, loss_rows, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_ntxent_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                          float coef, const void* a_loc, const void* b_loc, const void* a_all, const void* b_all, void* workspace,
+                          size_t workspace_bytes, const float* upstream, int32_t grad_dtype, void* d_a_loc, void* d_b_loc,
+                          void* d_a_all, void* d_b_all, float* d_temperature, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!ntxent_gemm_supported(d, min_temperature)) return AECF_ERR_UNSUPPORTED;
+    if (grad_dtype != AECF_BF16 && grad_dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_loc || !a_all || !b_all || !workspace || !d_a_loc || !d_b_loc || !d_a_all || !d_b_all)
+        return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < ntxent_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    launch_ntxent_gemm_grads(rows, cols, row_offset, d, dt, coef, a_loc, b_loc, a_all, b_all, workspace, upstream,
+                             grad_dtype == AECF_BF16 ? 1 : 0, d_a_loc, d_b_loc, d_a_all, d_b_all, (hipStream_t)stream);
+    return launch_status();
+}
+
 // ---- multi-label supervised contrastive loss (include/aecf_hip.h, "multi-label supervised contrastive loss")
 
 size_t aecf_supcon_ml_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {

@@ -350,6 +350,19 @@ void launch_supcon_ml_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset,
                                  const void* a, const void* b, const uint64_t* row_sets, const uint64_t* col_sets, int jaccard,
                                  void* workspace, const float* upstream, int out_bf16, void* da, void* db, hipStream_t s);
 
+// NT-Xent on the tile GEMMs (aecf_nce_gemm.hip): the 2 rows anchors of one rank from three logits blocks -- X = a_loc . b_all^T
+// (InfoNCE's pass 1), Y = a_loc . a_all^T and Z = b_loc . b_all^T with the anchor itself (column row_offset + i) left out by index
+// (EPI_EXP_SELF).  col_sums [cols] (the column sums of X, plus the row sums of Z on this rank's own range) is what ranks exchange.
+bool ntxent_gemm_supported(int d, float min_temperature);
+size_t ntxent_gemm_workspace_bytes(int64_t rows, int64_t cols, int d);
+void launch_ntxent_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                              const void* b_loc, const void* a_all, const void* b_all, void* workspace, float* col_sums, hipStream_t s);
+void launch_ntxent_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                             const void* b_all, const float* col_sums, void* workspace, float* loss_rows, hipStream_t s);
+void launch_ntxent_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef, const void* a_loc,
+                              const void* b_loc, const void* a_all, const void* b_all, void* workspace, const float* upstream,
+                              int out_bf16, void* d_a_loc, void* d_b_loc, void* d_a_all, void* d_b_all, hipStream_t s);
+
 // Multi-label supervised contrastive loss, streaming (aecf_supcon_ml_flash.hip): a set of classes per row as one uint64 (bit c =
 // class c); a key counts with weight 1 (the partner), [sets overlap] (jaccard 0) or |and| / |or| (jaccard 1).  The same passes,
 // workspace layout and outputs as launch_supcon_flash.  launch_label_sets_pack: multi-hot rows [rows, classes <= 64] of kind

@@ -96,6 +96,18 @@
 //     of its band (the block-uniform `special` branch) and joins later from its own float32 dot with weight 1.
 // sup_sums_kernel and sup_finalize_kernel serve unchanged (the weight sums stand where the counts stood); set_weights_kernel forms
 // w again from the words next to sup_weights_kernel.
+//
+// NT-Xent (aecf_ntxent_sym_pass1 / _loss / _grads) is the pool of both views -- every row of either view an anchor against the other
+// 2 C - 1 rows -- on THREE logits blocks of one rank: X = a_loc . b_all^T is the InfoNCE pass above, unchanged (EPI_EXP_DT); Y = a_loc .
+// a_all^T and Z = b_loc . b_all^T hold the anchor itself at column row_offset + i, and EPI_EXP_SELF leaves it out: E = 0 in the stored
+// tile and in the row sum, by index (exp((a.a - 1) / T) is about 1 beside sums that may total 1e-10: it cannot be subtracted later,
+// and a bit-identical row elsewhere in the view is a legitimate key).  It is EPI_EXP_DT's E loop; the tiles the band of excluded
+// keys crosses take the block-uniform branch of the ragged edge, and the column sums, which nobody needs, are not formed.  The
+// b x a block is X^T.  Da = lX + lY is local; Db = the ranks' column sums of X plus lZ of the row's owner: ntx_combine_kernel adds a
+// rank's lZ into its own range of its column sums before the ONE all-reduce.  nce_finalize_kernel and nce_weights_dt_kernel serve
+// unchanged (l := Da, c := Db; Y and Z with v = 0, Z with u_i = 1 / Db_(off + i) from ntx_prep_kernel), and the six gradient products
+// are the da / db launchers: two da products leave their slabs behind one another for one slab sum (d a_loc), two db products a
+// float32 stage (d b_all) -- one rounding per output.  18 R C d flops against 64 for two pooled streaming directions.
 #include <math.h>
 #include <type_traits>
 
@@ -117,10 +129,13 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // EPI_SUP (supervised contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the count and the float32
 // sum of the raw accumulators of the elements that match by label (the partner and the padding excluded)
 enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8,
-       EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11 };
+       EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11, EPI_EXP_SELF = 12 };
 // EPI_SETS_OV / EPI_SETS_JAC (multi-label contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the
 // float32 sums of w and of w * raw accumulator, w the overlap / Jaccard weight of the two class sets (partner and padding excluded)
 constexpr bool epi_is_sets(int epi) { return epi == EPI_SETS_OV || epi == EPI_SETS_JAC; }
+// EPI_EXP_SELF (NT-Xent, the a x a and b x b blocks of the logits pass): EPI_EXP_DT with ONE key per row left out BY INDEX -- the
+// element of row i at column row_offset + i (the anchor itself in the gathered rows of its own view) is E = 0 in the stored tile
+// and in the row sum, whatever its value; only the row sums leave the block (no column partials)
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -811,7 +826,7 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                 const unsigned long long* src = reinterpret_cast<const unsigned long long*>(is_row ? p.lab_row : p.lab_col);
                 if (k < (is_row ? p.m_valid : p.n_valid)) my_set = src[k];
             }
-            if (EPI == EPI_EXP_DT || EPI == EPI_SUP || epi_is_sets(EPI)) {
+            if (EPI == EPI_EXP_DT || EPI == EPI_SUP || epi_is_sets(EPI) || EPI == EPI_EXP_SELF) {
                 scale2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f;
                 shift2 = scale2;
             }
@@ -827,7 +842,13 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
             for (int ct = 0; ct < 4; ++ct) cs2[ct][0] = cs2[ct][1] = f32x2{0.f, 0.f};
             float* lrs = reinterpret_cast<float*>(smem);        // [4][256] row sums | [2][256] column sums
             float* lcs = lrs + 4 * BT;
-            const bool edge = BT * (mi + 1) > p.m_valid || BT * (ni + 1) > p.n_valid;      // block-uniform
+            bool edge = BT * (mi + 1) > p.m_valid || BT * (ni + 1) > p.n_valid;            // block-uniform
+            if (EPI == EPI_EXP_SELF) {
+                // the band of excluded keys (column row_offset + i of row i) crosses this tile: it takes the branch of the ragged
+                // edge, so only the tiles that hold such an element pay for the index test
+                const int64_t p0 = p.row_offset + (int64_t)BT * mi;
+                edge = edge || (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
+            }
             unsigned short* etile = p.e + ((int64_t)mi * p.e_tiles + 4 * ni + wn) * (BT * 64) + (128 * wm + r16) * 64 + 4 * lg;
 #pragma unroll
             for (int rt = 0; rt < 8; ++rt) {
@@ -843,14 +864,19 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                     e23[1] = __builtin_amdgcn_exp2f(acc[rt][ct][3] * scale2 - shift2);
                     if (edge) {
                         const bool iok = i < p.m_valid;
-                        e01[0] = (iok && j + 0 < p.n_valid) ? e01[0] : 0.f;
-                        e01[1] = (iok && j + 1 < p.n_valid) ? e01[1] : 0.f;
-                        e23[0] = (iok && j + 2 < p.n_valid) ? e23[0] : 0.f;
-                        e23[1] = (iok && j + 3 < p.n_valid) ? e23[1] : 0.f;
+                        // EPI_EXP_SELF: the excluded key by its index (a row that exists has row_offset + i < n_valid < 2^31; unsigned,
+                        // so that the padding rows past it wrap instead of overflowing)
+                        const unsigned int js = EPI == EPI_EXP_SELF ? (unsigned)p.row_offset + (unsigned)i : 0u;
+                        e01[0] = (iok && j + 0 < p.n_valid && (EPI != EPI_EXP_SELF || (unsigned)j + 0u != js)) ? e01[0] : 0.f;
+                        e01[1] = (iok && j + 1 < p.n_valid && (EPI != EPI_EXP_SELF || (unsigned)j + 1u != js)) ? e01[1] : 0.f;
+                        e23[0] = (iok && j + 2 < p.n_valid && (EPI != EPI_EXP_SELF || (unsigned)j + 2u != js)) ? e23[0] : 0.f;
+                        e23[1] = (iok && j + 3 < p.n_valid && (EPI != EPI_EXP_SELF || (unsigned)j + 3u != js)) ? e23[1] : 0.f;
                     }
                     s2 += e01 + e23;
-                    cs2[ct][0] += e01;
-                    cs2[ct][1] += e23;
+                    if (EPI != EPI_EXP_SELF) {
+                        cs2[ct][0] += e01;
+                        cs2[ct][1] += e23;
+                    }
                     // tile (mi, 4 ni + wn) of E: row 128 wm + 16 rt + r16, columns 16 ct + 4 lg .. + 3 of its 64 -- the four
                     // stores of a row group fill whole 128-byte lines of one 32 KB tile
                     *reinterpret_cast<u32x2*>(etile + (16 * rt) * 64 + 16 * ct) = u32x2{pack_bf16x2(e01[0], e01[1]), pack_bf16x2(e23[0], e23[1])};
@@ -864,13 +890,15 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
 #pragma unroll
                 for (int rt = 0; rt < 8; ++rt) lrs[wn * BT + 128 * wm + 16 * rt + r16] = rs[rt];
             }
+            if (EPI != EPI_EXP_SELF) {
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct)
+                for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = reduce_r16(cs[ct][r]);      // over the wave's 128 rows
-                    if (r16 == 0) lcs[wm * BT + 64 * wn + 16 * ct + 4 * lg + r] = v;
-                }
+                    for (int r = 0; r < 4; ++r) {
+                        const float v = reduce_r16(cs[ct][r]);  // over the wave's 128 rows
+                        if (r16 == 0) lcs[wm * BT + 64 * wn + 16 * ct + 4 * lg + r] = v;
+                    }
+            }
             float* lrn = lcs + 2 * BT;                          // EPI_SUP: [4][256] row counts | [4][256] row sums |
             float* lrx = lrn + 4 * BT;                          //          [2][256] column counts | [2][256] column sums
             float* lcn = lrx + 4 * BT;
@@ -1012,7 +1040,7 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                     p.rowcnt_part[o] = (lrn[tdx] + lrn[BT + tdx]) + (lrn[2 * BT + tdx] + lrn[3 * BT + tdx]);
                     p.rowsx_part[o] = (lrx[tdx] + lrx[BT + tdx]) + (lrx[2 * BT + tdx] + lrx[3 * BT + tdx]);
                 }
-            } else {
+            } else if (EPI != EPI_EXP_SELF) {
                 const int c = tdx - BT;
                 const int64_t o = ((int64_t)mi * p.n_tiles + ni) * BT + c;
                 p.colsum_part[o] = lcs[c] + lcs[BT + c];
@@ -1494,50 +1522,75 @@ LogitsLaunch logits_args(int64_t rows, int64_t cols, int d, const void* a, const
 // K = local rows) over the tiled bf16 weights wt [Rp][Cp]; outputs float32 or -- one rounding of the float32 sums -- bf16.
 // g0: the epilogue's scalar fields (coef / upstream / temp), everything else zero.  dt with d_t: dL/dT = -(1/T) sum_i a_i.da_i
 // from per-block partials of the float32 da products (EPI_TD) in tdot_part [splits m_tiles n_tiles].
+//
+// The da product alone: its float32 slabs go to `slabs` [splits][rows][d]; with `direct` and no K split the GEMM stores its own
+// output there (float32 or bf16) instead.  want_td: the EPI_TD instance, a's rows as tdot_src, partials into tdot_part.  Returns
+// the number of slabs written (0: stored directly); the caller sums them and reduces the partials.
+template <int EPI_PLAIN, int EPI_TD>
+int launch_da_product(int64_t rows, int64_t cols, int d, const NceGemmArgs& g0, const unsigned short* wt, float* slabs, float* tdot_part,
+                      bool want_td, const void* a, const void* b, int out_bf16, void* direct, hipStream_t s) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int n_tiles_d = (d + BT - 1) / BT;
+    NceGemmArgs g = g0;
+    g.a = (const char*)wt; g.lda = 128; g.a_rows = (int)Rp;           // tile (mi, t) of W: [256][128 B], contiguous
+    g.a_sm = (Cp / 64) * (int64_t)32768; g.a_st = 32768;
+    g.b = (const char*)b; g.ldb = 2u * (unsigned)d; g.b_rows = (int)cols; g.b_cbytes = 2 * d;
+    g.m_tiles = (int)(Rp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Cp / 64);
+    g.splits = da_splits(Rp, Cp, d);
+    g.steps_per_split = (g.k_steps + g.splits - 1) / g.splits;
+    g.m_valid = (int)rows; g.n_valid = d;
+    const bool to_slabs = g.splits > 1 || !direct;
+    g.out = to_slabs ? (void*)slabs : direct; g.ldo = d; g.slab_stride = rows * (int64_t)d;
+    g.out_bf16 = to_slabs ? 0 : out_bf16;
+    const unsigned int units = (unsigned)(g.m_tiles * g.splits);
+    const unsigned int bx = 8u * g.m_tiles * g.n_tiles, bu = ((units + 7) / 8) * 8 * g.n_tiles;
+    if (want_td) {
+        g.tdot_src = (const unsigned short*)a; g.tdot_part = tdot_part;
+        if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_TD, MAP_SPLITX>(g, bx, s);
+        else launch_gemm<OP_ROW, OP_COL, EPI_TD, MAP_UNITS>(g, bu, s);
+    } else {
+        if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_PLAIN, MAP_SPLITX>(g, bx, s);
+        else launch_gemm<OP_ROW, OP_COL, EPI_PLAIN, MAP_UNITS>(g, bu, s);
+    }
+    return to_slabs ? g.splits : 0;
+}
+
+// the partials one da product leaves in tdot_part
+inline int64_t da_tdot_count(int64_t rows, int64_t cols, int d) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    return (int64_t)da_splits(Rp, Cp, d) * (Rp / BT) * ((d + BT - 1) / BT);
+}
+
+inline void launch_slab_sum(const float* slabs, int n_slabs, int64_t n, void* out, int out_bf16, hipStream_t s) {
+    const int64_t n4 = n / 4;
+    nce_slab_sum_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s>>>(slabs, n_slabs, n4, n, out, out_bf16);
+}
+
+// The db product alone: db [cols][d] stored by the GEMM itself (no K split), float32 or bf16.
+template <int EPI_PLAIN>
+void launch_db_product(int64_t rows, int64_t cols, int d, const NceGemmArgs& g0, const unsigned short* wt, const void* a, int out_bf16,
+                       void* db, hipStream_t s) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    NceGemmArgs g = g0;
+    g.a = (const char*)wt; g.lda = 128; g.a_rows = (int)Rp; g.a_cbytes = 0; g.a_sm = Cp / 64;
+    g.b = (const char*)a; g.ldb = 2u * (unsigned)d; g.b_rows = (int)rows; g.b_cbytes = 2 * d;
+    g.m_tiles = (int)(Cp / BT); g.n_tiles = (d + BT - 1) / BT; g.k_steps = (int)(Rp / 64);
+    g.splits = 1; g.steps_per_split = g.k_steps;
+    g.m_valid = (int)cols; g.n_valid = d;
+    g.out = db; g.ldo = d; g.slab_stride = 0; g.out_bf16 = out_bf16;
+    const unsigned int units = (unsigned)g.m_tiles;
+    launch_gemm<OP_COLB, OP_COL, EPI_PLAIN, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
+}
+
 template <int EPI_PLAIN, int EPI_TD>
 void launch_grad_products(int64_t rows, int64_t cols, int d, const NceGemmArgs& g0, const unsigned short* wt, float* slabs,
                           float* tdot_part, const NceDevTemp* dt, const void* a, const void* b, int out_bf16, void* da, void* db,
                           hipStream_t s) {
-    const int64_t Rp = up256(rows), Cp = up256(cols);
-    const int n_tiles_d = (d + BT - 1) / BT;
-    {
-        NceGemmArgs g = g0;
-        g.a = (const char*)wt; g.lda = 128; g.a_rows = (int)Rp;           // tile (mi, t) of W: [256][128 B], contiguous
-        g.a_sm = (Cp / 64) * (int64_t)32768; g.a_st = 32768;
-        g.b = (const char*)b; g.ldb = 2u * (unsigned)d; g.b_rows = (int)cols; g.b_cbytes = 2 * d;
-        g.m_tiles = (int)(Rp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Cp / 64);
-        g.splits = da_splits(Rp, Cp, d);
-        g.steps_per_split = (g.k_steps + g.splits - 1) / g.splits;
-        g.m_valid = (int)rows; g.n_valid = d;
-        g.out = g.splits > 1 ? (void*)slabs : da; g.ldo = d; g.slab_stride = rows * (int64_t)d;
-        g.out_bf16 = g.splits > 1 ? 0 : out_bf16;
-        const unsigned int units = (unsigned)(g.m_tiles * g.splits);
-        const unsigned int bx = 8u * g.m_tiles * g.n_tiles, bu = ((units + 7) / 8) * 8 * g.n_tiles;
-        if (dt && dt->d_t) {
-            g.tdot_src = (const unsigned short*)a; g.tdot_part = tdot_part;
-            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_TD, MAP_SPLITX>(g, bx, s);
-            else launch_gemm<OP_ROW, OP_COL, EPI_TD, MAP_UNITS>(g, bu, s);
-        } else {
-            if (g.splits == 8) launch_gemm<OP_ROW, OP_COL, EPI_PLAIN, MAP_SPLITX>(g, bx, s);
-            else launch_gemm<OP_ROW, OP_COL, EPI_PLAIN, MAP_UNITS>(g, bu, s);
-        }
-        if (g.splits > 1) {
-            const int64_t n4 = rows * (int64_t)d / 4;
-            nce_slab_sum_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s>>>(slabs, g.splits, n4, g.slab_stride, da, out_bf16);
-        }
-        if (dt && dt->d_t) launch_nce_dtemp(tdot_part, (int64_t)g.splits * g.m_tiles * g.n_tiles, 1, *dt, s);
-    }
-    {
-        NceGemmArgs g = g0;
-        g.a = (const char*)wt; g.lda = 128; g.a_rows = (int)Rp; g.a_cbytes = 0; g.a_sm = Cp / 64;
-        g.b = (const char*)a; g.ldb = 2u * (unsigned)d; g.b_rows = (int)rows; g.b_cbytes = 2 * d;
-        g.m_tiles = (int)(Cp / BT); g.n_tiles = n_tiles_d; g.k_steps = (int)(Rp / 64);
-        g.splits = 1; g.steps_per_split = g.k_steps;
-        g.m_valid = (int)cols; g.n_valid = d;
-        g.out = db; g.ldo = d; g.slab_stride = 0; g.out_bf16 = out_bf16;
-        const unsigned int units = (unsigned)g.m_tiles;
-        launch_gemm<OP_COLB, OP_COL, EPI_PLAIN, MAP_UNITS>(g, ((units + 7) / 8) * 8 * g.n_tiles, s);
-    }
+    const bool want_td = dt && dt->d_t;
+    const int n_slabs = launch_da_product<EPI_PLAIN, EPI_TD>(rows, cols, d, g0, wt, slabs, tdot_part, want_td, a, b, out_bf16, da, s);
+    if (n_slabs) launch_slab_sum(slabs, n_slabs, rows * (int64_t)d, da, out_bf16, s);
+    if (want_td) launch_nce_dtemp(tdot_part, da_tdot_count(rows, cols, d), 1, *dt, s);
+    launch_db_product<EPI_PLAIN>(rows, cols, d, g0, wt, a, out_bf16, db, s);
 }
 
 }  // namespace
@@ -1741,6 +1794,160 @@ void launch_supcon_ml_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset,
                                                              row_offset, coef, upstream, dt.t, dt.min_t);
     // the tdot partials go into the first plane of the row partials (dead since the sums launch), as in launch_nce_gemm_grads
     launch_grad_products<EPI_OUT, EPI_OUT_TD>(rows, cols, d, NceGemmArgs{}, w.e, w.slabs, w.row_part, &dt, a, b, out_bf16, da, db, s);
+}
+
+// ---- NT-Xent on the same GEMMs: three logits blocks of one rank, one exchange (include/aecf_hip.h) -------------------------------
+//   X = a_loc . b_all^T (EPI_EXP_DT, InfoNCE's pass 1 to the bit: row sums lX, this rank's column sums cX)
+//   Y = a_loc . a_all^T, Z = b_loc . b_all^T (EPI_EXP_SELF: the anchor itself, column row_offset + i, left out by index; row sums)
+// Da = lX + lY is local; Db = sum over ranks of cX, plus lZ on the owner's range: each rank adds its lZ into its own range of
+// col_sums before the ONE all-reduce.  The b x a block is X^T and is never formed.  Loss and weights are InfoNCE's kernels with
+// l := Da, c := Db; Y and Z take the weights body with v = 0 (Z with u_i = 1 / Db_(off + i)) and nothing at the excluded key.
+
+namespace {
+
+// Da_i = lX_i + lY_i in place over l; col_sums[off + i] += lZ_i: one thread per local row, one float32 addition each, no atomics
+__global__ __launch_bounds__(256) void ntx_combine_kernel(float* l, const float* ly, const float* lz, float* col_sums, int64_t rows,
+                                                          int64_t row_offset) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    l[i] = l[i] + ly[i];
+    col_sums[row_offset + i] = col_sums[row_offset + i] + lz[i];
+}
+
+// what the weights of Y and Z read: uz_i = 1 / Db_(off + i) (the v of its column; 0 in the padding) and a vector of zeros [Cp]
+// that stands for v and for the float32 exponential at the excluded key
+__global__ __launch_bounds__(256) void ntx_prep_kernel(const float* v, float* uz, float* zero, int64_t rows, int64_t row_offset,
+                                                       int64_t Rp, int64_t Cp) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < Cp) zero[k] = 0.f;
+    if (k < Rp) uz[k] = k < rows ? v[row_offset + k] : 0.f;
+}
+
+struct NtxWs {
+    unsigned short* e[3];               // X | Y | Z, each [Rp][Cp] bf16, tiled as E
+    float* rowsum_part;                 // [n_tiles][Rp]   one block after the other
+    float* colsum_part;                 // [m_tiles][Cp]   block X
+    float* l;                           // [Rp]  lX, then Da
+    float* ly;                          // [Rp]
+    float* lz;                          // [Rp]
+    float* u;                           // [Rp]  1 / Da
+    float* v;                           // [Cp]  1 / Db
+    float* uz;                          // [Rp]  1 / Db_(off + i)
+    float* ediag;                       // [Rp]
+    float* zero;                        // [Cp]
+    float* tdot_part;                   // [3][splits <= 32][m_tiles][n_tiles_d <= 16]
+    float* slabs;                       // [2 splits][rows][d]: the slabs of W_X b_all, behind them those of W_Y a_all
+    float* stage;                       // [2][cols][d]: W_X^T a_loc | W_Z^T b_loc in float32
+    size_t bytes;
+};
+
+NtxWs ntx_carve(void* ws, int64_t rows, int64_t cols, int d) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t mt = Rp / BT, nt = Cp / BT;
+    NtxWs w;
+    char* p = (char*)ws;
+    size_t off = 0;
+    auto take = [&](size_t n) { char* r = p + off; off += al256(n); return r; };
+    for (int k = 0; k < 3; ++k) w.e[k] = (unsigned short*)take((size_t)Rp * Cp * 2);
+    w.rowsum_part = (float*)take((size_t)nt * Rp * 4);
+    w.colsum_part = (float*)take((size_t)mt * Cp * 4);
+    w.l = (float*)take((size_t)Rp * 4);
+    w.ly = (float*)take((size_t)Rp * 4);
+    w.lz = (float*)take((size_t)Rp * 4);
+    w.u = (float*)take((size_t)Rp * 4);
+    w.v = (float*)take((size_t)Cp * 4);
+    w.uz = (float*)take((size_t)Rp * 4);
+    w.ediag = (float*)take((size_t)Rp * 4);
+    w.zero = (float*)take((size_t)Cp * 4);
+    w.tdot_part = (float*)take((size_t)3 * 32 * 16 * mt * 4);
+    w.slabs = (float*)take((size_t)2 * da_splits(Rp, Cp, d) * rows * d * 4);
+    w.stage = (float*)take((size_t)2 * cols * d * 4);
+    w.bytes = off;
+    return w;
+}
+
+}  // namespace
+
+bool ntxent_gemm_supported(int d, float min_temperature) { return nce_gemm_supported(0, d, min_temperature); }
+
+size_t ntxent_gemm_workspace_bytes(int64_t rows, int64_t cols, int d) { return ntx_carve(nullptr, rows, cols, d).bytes + 256; }
+
+// pass 1: the three blocks, Da (workspace) and col_sums [cols] = this rank's cX, plus lZ on [row_offset, row_offset + rows)
+void launch_ntxent_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                              const void* b_loc, const void* a_all, const void* b_all, void* workspace, float* col_sums, hipStream_t s) {
+    const NtxWs w = ntx_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    {
+        LogitsLaunch L = logits_args(rows, cols, d, a_loc, b_all);
+        NceGemmArgs& g = L.g;
+        g.e = w.e[0]; g.e_tiles = Cp / 64;
+        g.rowsum_part = w.rowsum_part; g.colsum_part = w.colsum_part;
+        g.temp = dt.t; g.min_temp = dt.min_t;
+        launch_gemm<OP_ROW, OP_ROW, EPI_EXP_DT, MAP_2D>(g, L.blocks, s);
+        nce_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64)), dim3(256), 0, s>>>(w.rowsum_part, w.colsum_part, g.m_tiles, g.n_tiles, rows, cols,
+                                                                               w.l, col_sums);
+    }
+    for (int k = 1; k < 3; ++k) {
+        LogitsLaunch L = logits_args(rows, cols, d, k == 1 ? a_loc : b_loc, k == 1 ? a_all : b_all);
+        NceGemmArgs& g = L.g;
+        g.e = w.e[k]; g.e_tiles = Cp / 64;
+        g.rowsum_part = w.rowsum_part;
+        g.temp = dt.t; g.min_temp = dt.min_t; g.row_offset = row_offset;
+        launch_gemm<OP_ROW, OP_ROW, EPI_EXP_SELF, MAP_2D>(g, L.blocks, s);
+        // the row blocks of the sums launch alone: this block leaves no column partials
+        nce_sums_kernel<<<dim3((unsigned)(Rp / 64)), dim3(256), 0, s>>>(w.rowsum_part, nullptr, g.m_tiles, g.n_tiles, rows, cols,
+                                                                        k == 1 ? w.ly : w.lz, nullptr);
+    }
+    ntx_combine_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s>>>(w.l, w.ly, w.lz, col_sums, rows, row_offset);
+}
+
+// normalisers + loss rows of this rank's 2 rows anchors from the col_sums of all ranks: InfoNCE's finalize with l := Da, c := Db
+void launch_ntxent_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                             const void* b_all, const float* col_sums, void* workspace, float* loss_rows, hipStream_t s) {
+    const NtxWs w = ntx_carve(workspace, rows, cols, d);
+    NceFinArgs f = {};
+    f.a = (const unsigned short*)a_loc; f.b = (const unsigned short*)b_all; f.l = w.l; f.c = col_sums;
+    f.u = w.u; f.v = w.v; f.ediag = w.ediag; f.loss_rows = loss_rows; f.rows = rows; f.cols = cols; f.row_offset = row_offset;
+    f.Rp = up256(rows); f.Cp = up256(cols); f.d = d; f.sym = 1;
+    f.temp = dt.t; f.min_temp = dt.min_t;
+    nce_finalize_kernel<true><<<dim3((unsigned)((f.Rp + 3) / 4)), dim3(256), 0, s>>>(f);
+}
+
+// gradients: the three weights passes in place, then
+//   d_a_loc = W_X b_all + W_Y a_all (one slab sum over both products' slabs)      d_b_loc = W_Z b_all
+//   d_a_all = W_Y^T a_loc                                                         d_b_all = W_X^T a_loc + W_Z^T b_loc (float32 stage)
+// every output rounded once from its float32 sum; dt.d_t from the partials of the three da products, one fixed-order reduction
+void launch_ntxent_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef, const void* a_loc,
+                              const void* b_loc, const void* a_all, const void* b_all, void* workspace, const float* upstream,
+                              int out_bf16, void* d_a_loc, void* d_b_loc, void* d_a_all, void* d_b_all, hipStream_t s) {
+    const NtxWs w = ntx_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t chunks = Rp * (Cp / 8);
+    const dim3 wgrid((unsigned)((chunks + 255) / 256));
+    ntx_prep_kernel<<<dim3((unsigned)(Cp / 256)), dim3(256), 0, s>>>(w.v, w.uz, w.zero, rows, row_offset, Rp, Cp);
+    nce_weights_dt_kernel<<<wgrid, dim3(256), 0, s>>>(w.e[0], Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset, coef, 2.0f, upstream,
+                                                      dt.t, dt.min_t);
+    nce_weights_dt_kernel<<<wgrid, dim3(256), 0, s>>>(w.e[1], Cp / 64, Rp / BT, w.u, w.zero, w.zero, rows, row_offset, coef, 0.0f, upstream,
+                                                      dt.t, dt.min_t);
+    nce_weights_dt_kernel<<<wgrid, dim3(256), 0, s>>>(w.e[2], Cp / 64, Rp / BT, w.uz, w.zero, w.zero, rows, row_offset, coef, 0.0f, upstream,
+                                                      dt.t, dt.min_t);
+    const bool want_td = dt.d_t != nullptr;
+    const int64_t n_td = da_tdot_count(rows, cols, d), n_loc = rows * (int64_t)d, n_all = cols * (int64_t)d;
+    const NceGemmArgs g0 = {};
+    // both products always leave float32 slabs, those of W_Y a_all behind those of W_X b_all: one sum, one rounding
+    const int sx = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[0], w.slabs, w.tdot_part, want_td, a_loc, b_all, 0,
+                                                          nullptr, s);
+    const int sy = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[1], w.slabs + sx * n_loc, w.tdot_part + n_td, want_td,
+                                                          a_loc, a_all, 0, nullptr, s);
+    launch_slab_sum(w.slabs, sx + sy, n_loc, d_a_loc, out_bf16, s);
+    const int sz = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[2], w.slabs, w.tdot_part + 2 * n_td, want_td, b_loc,
+                                                          b_all, out_bf16, d_b_loc, s);
+    if (sz) launch_slab_sum(w.slabs, sz, n_loc, d_b_loc, out_bf16, s);
+    if (want_td) launch_nce_dtemp(w.tdot_part, 3 * n_td, 1, dt, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[1], a_loc, out_bf16, d_a_all, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[0], a_loc, 0, w.stage, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[2], b_loc, 0, w.stage + n_all, s);
+    launch_slab_sum(w.stage, 2, n_all, d_b_all, out_bf16, s);
 }
 
 // ---- sigmoid (SigLIP) loss on the same GEMMs ---------------------------------------------------------------------------

@@ -739,6 +739,60 @@ int aecf_supcon_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_
                           const int64_t* col_labels, void* workspace, size_t workspace_bytes, const float* upstream,
                           int32_t grad_dtype, void* da, void* db, float* d_temperature, void* stream);
 
+/* ---- NT-Xent, tile-GEMM form (build-defined; the pooled loss of aecf_supcon_pool_fwd_bwd with every label negative) ----
+ * NT-Xent (SimCLR) over ONE pool of the 2 cols rows of both views: every row is an anchor, its positive is its partner in the other
+ * view, its negatives are the other 2 cols - 2 rows of BOTH views, itself left out.  A rank holds its local rows a_loc, b_loc
+ * [rows,d] (global rows row_offset .. row_offset + rows) and the gathered a_all, b_all [cols,d], unit-norm bf16 rows; a_all / b_all
+ * may alias a_loc / b_loc on one rank.  Tc = max(*temperature, min_temperature), E(s) = exp((s - 1) / Tc).  Three logits blocks:
+ *   X = a_loc . b_all^T   partner at column row_offset + i              row sums lX_i, this rank's column sums cX_j
+ *   Y = a_loc . a_all^T   the anchor itself at column row_offset + i, EXCLUDED BY INDEX (E = 0 stored and summed)   row sums lY_i
+ *   Z = b_loc . b_all^T   the same                                                                                   row sums lZ_i
+ * The b x a block is X^T and is never formed.  Denominators: anchors of view a, Da_i = lX_i + lY_i (local); anchors of view b,
+ * Db_j = sum over ranks of cX_j, plus lZ of the rank that owns row j.  With s_i = a_i . b_(row_offset + i):
+ *   loss_rows[i] = [log Da_i + 1/Tc - s_i/Tc] + [log Db_(row_offset + i) + 1/Tc - s_i/Tc]         both anchors of pair i, WITHOUT coef
+ *   W_X = ct (E_X (1/Da_i + 1/Db_j) - 2 [j == row_offset + i])    W_Y = ct E_Y / Da_i    W_Z = ct E_Z / Db_(row_offset + i)
+ *         ct = coef / Tc * upstream; W_Y and W_Z are 0 at the excluded key
+ *   d_a_loc = W_X b_all + W_Y a_all [rows,d]     d_b_loc = W_Z b_all [rows,d]
+ *   d_a_all = W_Y^T a_loc [cols,d]               d_b_all = W_X^T a_loc + W_Z^T b_loc [cols,d]        (this rank's shares)
+ *   dT = -(1/Tc) [ sum_i a_i . d_a_loc_i + sum_i b_i . d_b_loc_i ]   (0 where *temperature < min_temperature)
+ * The shares of the ranks sum to the global gradients.
+ *   pass1: the three logits GEMMs.  X is aecf_nce_sym_pass1_dt to the bit; Y and Z run an epilogue of their own that leaves the
+ *          excluded key out by its index, never by its value, and writes row sums only.  Then Da = lX + lY (workspace) and
+ *          col_sums [cols] float32 = this rank's cX, plus lZ on its own range [row_offset, row_offset + rows): one float32
+ *          addition each, fixed order, no atomics.
+ *   caller: all-reduce (sum) of col_sums over the ranks (nothing to do on one rank): it then holds Db.
+ *   loss:  loss_rows [rows] from Da and the summed col_sums; prepares 1/Da and 1/Db in the workspace.
+ *   grads: the three weights passes in place over the blocks, then the six products.  Where two products land on one output
+ *          (d_a_loc, d_b_all) they are summed in float32 and rounded ONCE to grad_dtype (float32 or bf16); everything is multiplied
+ *          by upstream[0] (a DEVICE float32 scalar, NULL = 1); d_temperature (may be NULL) is WRITTEN with this rank's share of
+ *          dL/dT times upstream[0], reduced in a fixed order from float32 partials.  It consumes the stored blocks: it runs once
+ *          per pass1.
+ * Only the device-temperature form exists.  Served: bf16 rows, d % 64 == 0, 64 <= d <= 4096, min_temperature >= 0.025 (1/Tc is
+ * the constant shift of every exponential), rows <= cols.  18 rows cols d MFMA flops (three logits blocks and six gradient
+ * products of 2 rows cols d each) against 64 for the two pooled streaming directions.
+ * Workspace, in order, each piece rounded up to 256 bytes, Rp / Cp = rows / cols rounded up to 256, + 256 bytes:
+ *   E_X | E_Y | E_Z, each [Rp][Cp] bf16 | row partials [Cp/256][Rp] | column partials [Rp/256][Cp] | Da [Rp] | lY [Rp] | lZ [Rp] |
+ *   1/Da [Rp] | 1/Db [Cp] | 1/Db at the partner [Rp] | the partner's exponential [Rp] | zeros [Cp] |
+ *   dT partials [3][32][16][Rp/256] | da slabs [2 splits][rows][d] | d_b_all stage [2][cols][d]
+ *   (float32 but E; splits: the K split of da = W b, as in the InfoNCE form).  The query answers 0 where the shape is not served.
+ * Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host, nothing read from the
+ * workspace before it is written; no float atomics: the same inputs give the same bits.  Checks before any launch, in the order
+ * of the supervised tile form: sizes (rows, cols, d > 0, cols < 2^31, min_temperature > 0, 0 <= row_offset, row_offset + rows <=
+ * cols: AECF_ERR_BAD_DIMS), then d, min_temperature < 0.025 or a grad_dtype other than bf16 / float32 (AECF_ERR_UNSUPPORTED),
+ * then NULL pointers (AECF_ERR_NULL_POINTER; upstream and d_temperature may be NULL), then the workspace size
+ * (AECF_ERR_WORKSPACE). */
+size_t aecf_ntxent_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d);      /* 0: not served */
+int aecf_ntxent_sym_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                          float min_temperature, const void* a_loc, const void* b_loc, const void* a_all, const void* b_all,
+                          void* workspace, size_t workspace_bytes, float* col_sums /* [cols] */, void* stream);
+int aecf_ntxent_sym_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                         float min_temperature, const void* a_loc, const void* b_all, const float* col_sums /* summed over ranks */,
+                         void* workspace, size_t workspace_bytes, float* loss_rows, void* stream);
+int aecf_ntxent_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                          float min_temperature, float coef, const void* a_loc, const void* b_loc, const void* a_all,
+                          const void* b_all, void* workspace, size_t workspace_bytes, const float* upstream, int32_t grad_dtype,
+                          void* d_a_loc, void* d_b_loc, void* d_a_all, void* d_b_all, float* d_temperature, void* stream);
+
 /* ---- multi-label supervised contrastive loss (build-defined like the supervised term above, whose contract this one repeats) ----
  * One direction as above, with a SET of classes per row instead of one class: q_sets [rows] and k_sets [cols] are DEVICE arrays of
  * one uint64 per row, bit c = class c, C <= 64 classes (aecf_label_sets_pack makes them from multi-hot rows).  A key counts with a
