@@ -223,6 +223,16 @@ _SYMBOLS = [
     ("aecf_ntxent_sym_grads", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
       c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # pooled supervised contrastive loss on the tile GEMMs: NT-Xent's three blocks with labels, one all-reduce of [3][cols]
+    ("aecf_supcon_pool_sym_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
+    ("aecf_supcon_pool_sym_pass1", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_size_t, c_void_p, c_void_p]),
+    ("aecf_supcon_pool_sym_loss", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("aecf_supcon_pool_sym_grads", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # multi-label contrastive loss, symmetric, on the tile GEMMs: class sets and a weighting in place of the labels
     ("aecf_supcon_ml_sym_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
     ("aecf_supcon_ml_sym_pass1", c_int,

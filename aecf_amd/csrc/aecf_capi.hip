@@ -1068,6 +1068,61 @@ int aecf_ntxent_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_
     return launch_status();
 }
 
+// ---- pooled supervised contrastive loss on the tile GEMMs (include/aecf_hip.h, "pooled supervised contrastive loss, tile-GEMM form")
+
+size_t aecf_supcon_pool_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || rows > cols || cols > 0x7fffffff || !supcon_pool_gemm_supported(d, 0.025f, cols)) return 0;
+    return supcon_pool_gemm_workspace_bytes(rows, cols, d);
+}
+
+int aecf_supcon_pool_sym_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                               float min_temperature, const void* a_loc, const void* b_loc, const void* a_all, const void* b_all,
+                               const int64_t* row_labels, const int64_t* col_labels, void* workspace, size_t workspace_bytes,
+                               float* col_stats, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!supcon_pool_gemm_supported(d, min_temperature, cols)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_loc || !a_all || !b_all || !row_labels || !col_labels || !workspace || !col_stats)
+        return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < supcon_pool_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_supcon_pool_gemm_pass1(rows, cols, row_offset, d, dt, a_loc, b_loc, a_all, b_all, row_labels, col_labels, workspace, col_stats,
+                                  (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_supcon_pool_sym_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                              float min_temperature, const void* a_loc, const void* b_all, const float* col_stats, void* workspace,
+                              size_t workspace_bytes, float* loss_rows, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!supcon_pool_gemm_supported(d, min_temperature, cols)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_all || !col_stats || !workspace || !loss_rows) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < supcon_pool_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_supcon_pool_gemm_loss(rows, cols, row_offset, d, dt, a_loc, b_all, col_stats, workspace, loss_rows, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_supcon_pool_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                               float min_temperature, float coef, const void* a_loc, const void* b_loc, const void* a_all,
+                               const void* b_all, const int64_t* row_labels, const int64_t* col_labels, void* workspace,
+                               size_t workspace_bytes, const float* upstream, int32_t grad_dtype, void* d_a_loc, void* d_b_loc,
+                               void* d_a_all, void* d_b_all, float* d_temperature, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!supcon_pool_gemm_supported(d, min_temperature, cols)) return AECF_ERR_UNSUPPORTED;
+    if (grad_dtype != AECF_BF16 && grad_dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_loc || !a_all || !b_all || !row_labels || !col_labels || !workspace || !d_a_loc || !d_b_loc ||
+        !d_a_all || !d_b_all)
+        return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < supcon_pool_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    launch_supcon_pool_gemm_grads(rows, cols, row_offset, d, dt, coef, a_loc, b_loc, a_all, b_all, row_labels, col_labels, workspace,
+                                  upstream, grad_dtype == AECF_BF16 ? 1 : 0, d_a_loc, d_b_loc, d_a_all, d_b_all, (hipStream_t)stream);
+    return launch_status();
+}
+
 // ---- multi-label supervised contrastive loss (include/aecf_hip.h, "multi-label supervised contrastive loss")
 
 size_t aecf_supcon_ml_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {

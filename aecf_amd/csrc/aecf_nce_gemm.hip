@@ -108,6 +108,14 @@
 // unchanged (l := Da, c := Db; Y and Z with v = 0, Z with u_i = 1 / Db_(off + i) from ntx_prep_kernel), and the six gradient products
 // are the da / db launchers: two da products leave their slabs behind one another for one slab sum (d a_loc), two db products a
 // float32 stage (d b_all) -- one rounding per output.  18 R C d flops against 64 for two pooled streaming directions.
+//
+// The pooled supervised contrastive loss (aecf_supcon_pool_sym_pass1 / _loss / _grads; Khosla et al.: every row of either view an
+// anchor, its positives the partner and every row of the pool with its label) is NT-Xent's three blocks with the label statistics of
+// the supervised loss on each: X runs EPI_SUP unchanged, Y and Z a seventh epilogue, EPI_SUP_SELF -- EPI_EXP_SELF's E loop and the ROW
+// half of EPI_SUP's label search (the anchor excluded by index where X excludes the partner), without the 32 column accumulators of
+// E and the LDS column slots of the matches.  sup_pool_combine_kernel adds X's and Y's row statistics (anchor a_i) and puts Z's into
+// the rank's own range of col_stats [3][cols] before the one all-reduce (anchor b_g); sup_finalize_kernel and sup_weights_kernel serve
+// unchanged, Y and Z take the SELF variant of the weights (v = rnc = 0, nothing at the excluded key).  Products as NT-Xent's.
 #include <math.h>
 #include <type_traits>
 
@@ -129,13 +137,18 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // EPI_SUP (supervised contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the count and the float32
 // sum of the raw accumulators of the elements that match by label (the partner and the padding excluded)
 enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8,
-       EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11, EPI_EXP_SELF = 12 };
+       EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11, EPI_EXP_SELF = 12, EPI_SUP_SELF = 13 };
 // EPI_SETS_OV / EPI_SETS_JAC (multi-label contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the
 // float32 sums of w and of w * raw accumulator, w the overlap / Jaccard weight of the two class sets (partner and padding excluded)
 constexpr bool epi_is_sets(int epi) { return epi == EPI_SETS_OV || epi == EPI_SETS_JAC; }
 // EPI_EXP_SELF (NT-Xent, the a x a and b x b blocks of the logits pass): EPI_EXP_DT with ONE key per row left out BY INDEX -- the
 // element of row i at column row_offset + i (the anchor itself in the gathered rows of its own view) is E = 0 in the stored tile
 // and in the row sum, whatever its value; only the row sums leave the block (no column partials)
+// EPI_SUP_SELF (pooled supervised contrastive loss, the a x a and b x b blocks): EPI_EXP_SELF's E loop, then the ROW half of EPI_SUP's
+// label search -- count and float32 raw-score sum of the matches by label per row, the anchor itself (column row_offset + i) left
+// out by index where EPI_SUP leaves the partner out; no column sums, counts or partials of any kind
+constexpr bool epi_is_self(int epi) { return epi == EPI_EXP_SELF || epi == EPI_SUP_SELF; }
+constexpr bool epi_has_labels(int epi) { return epi == EPI_SUP || epi == EPI_SUP_SELF; }
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -800,7 +813,7 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
             // re-reads the last label) gets a key no column has, and the other way round.  24 registers beside the accumulators
             // where the int64 labels would take 48 and spill.
             unsigned int kr[8], kc[16];
-            if (EPI == EPI_SUP) {
+            if (epi_has_labels(EPI)) {
 #pragma unroll
                 for (int rt = 0; rt < 8; ++rt) {
                     const int i = (int)gi0 + 16 * rt;
@@ -826,7 +839,7 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                 const unsigned long long* src = reinterpret_cast<const unsigned long long*>(is_row ? p.lab_row : p.lab_col);
                 if (k < (is_row ? p.m_valid : p.n_valid)) my_set = src[k];
             }
-            if (EPI == EPI_EXP_DT || EPI == EPI_SUP || epi_is_sets(EPI) || EPI == EPI_EXP_SELF) {
+            if (EPI == EPI_EXP_DT || epi_has_labels(EPI) || epi_is_sets(EPI) || EPI == EPI_EXP_SELF) {
                 scale2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f;
                 shift2 = scale2;
             }
@@ -843,7 +856,7 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
             float* lrs = reinterpret_cast<float*>(smem);        // [4][256] row sums | [2][256] column sums
             float* lcs = lrs + 4 * BT;
             bool edge = BT * (mi + 1) > p.m_valid || BT * (ni + 1) > p.n_valid;            // block-uniform
-            if (EPI == EPI_EXP_SELF) {
+            if (epi_is_self(EPI)) {
                 // the band of excluded keys (column row_offset + i of row i) crosses this tile: it takes the branch of the ragged
                 // edge, so only the tiles that hold such an element pay for the index test
                 const int64_t p0 = p.row_offset + (int64_t)BT * mi;
@@ -866,14 +879,14 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                         const bool iok = i < p.m_valid;
                         // EPI_EXP_SELF: the excluded key by its index (a row that exists has row_offset + i < n_valid < 2^31; unsigned,
                         // so that the padding rows past it wrap instead of overflowing)
-                        const unsigned int js = EPI == EPI_EXP_SELF ? (unsigned)p.row_offset + (unsigned)i : 0u;
-                        e01[0] = (iok && j + 0 < p.n_valid && (EPI != EPI_EXP_SELF || (unsigned)j + 0u != js)) ? e01[0] : 0.f;
-                        e01[1] = (iok && j + 1 < p.n_valid && (EPI != EPI_EXP_SELF || (unsigned)j + 1u != js)) ? e01[1] : 0.f;
-                        e23[0] = (iok && j + 2 < p.n_valid && (EPI != EPI_EXP_SELF || (unsigned)j + 2u != js)) ? e23[0] : 0.f;
-                        e23[1] = (iok && j + 3 < p.n_valid && (EPI != EPI_EXP_SELF || (unsigned)j + 3u != js)) ? e23[1] : 0.f;
+                        const unsigned int js = epi_is_self(EPI) ? (unsigned)p.row_offset + (unsigned)i : 0u;
+                        e01[0] = (iok && j + 0 < p.n_valid && (!epi_is_self(EPI) || (unsigned)j + 0u != js)) ? e01[0] : 0.f;
+                        e01[1] = (iok && j + 1 < p.n_valid && (!epi_is_self(EPI) || (unsigned)j + 1u != js)) ? e01[1] : 0.f;
+                        e23[0] = (iok && j + 2 < p.n_valid && (!epi_is_self(EPI) || (unsigned)j + 2u != js)) ? e23[0] : 0.f;
+                        e23[1] = (iok && j + 3 < p.n_valid && (!epi_is_self(EPI) || (unsigned)j + 3u != js)) ? e23[1] : 0.f;
                     }
                     s2 += e01 + e23;
-                    if (EPI != EPI_EXP_SELF) {
+                    if (!epi_is_self(EPI)) {
                         cs2[ct][0] += e01;
                         cs2[ct][1] += e23;
                     }
@@ -890,7 +903,7 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
 #pragma unroll
                 for (int rt = 0; rt < 8; ++rt) lrs[wn * BT + 128 * wm + 16 * rt + r16] = rs[rt];
             }
-            if (EPI != EPI_EXP_SELF) {
+            if (!epi_is_self(EPI)) {
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
@@ -903,7 +916,8 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
             float* lrx = lrn + 4 * BT;                          //          [2][256] column counts | [2][256] column sums
             float* lcn = lrx + 4 * BT;
             float* lcx = lcn + 2 * BT;
-            if (EPI == EPI_SUP) {
+            if (epi_has_labels(EPI)) {
+                constexpr bool COLS = EPI == EPI_SUP;           // EPI_SUP_SELF: the row half alone
                 // block-uniform: only tiles on the band of partners or on the ragged edge pay for the index tests
                 const int64_t p0 = p.row_offset + (int64_t)BT * mi;
                 const bool special = edge || (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
@@ -917,7 +931,7 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                     // wave), row group after row group: 32 accumulators less beside the 128 of the tile
                     float* wcn = lcn + wm * BT + 64 * wn + 4 * lg;
                     float* wcx = lcx + wm * BT + 64 * wn + 4 * lg;
-                    if (r16 == 0) {
+                    if (COLS && r16 == 0) {
 #pragma unroll
                         for (int c = 0; c < 16; ++c) wcn[16 * (c >> 2) + (c & 3)] = wcx[16 * (c >> 2) + (c & 3)] = 0.f;
                     }
@@ -949,10 +963,12 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                                 if (SP) m = m & (jpr != 16 * (c >> 2) + (c & 3));
                                 const float one = m ? 1.f : 0.f, sv = m ? acc[rt][c >> 2][c & 3] : 0.f;
                                 rn += one; rx += sv;
-                                const float c1 = reduce_r16(one), c2 = reduce_r16(sv);      // over the group's 16 rows
-                                if (r16 == 0) {
-                                    wcn[16 * (c >> 2) + (c & 3)] += c1;
-                                    wcx[16 * (c >> 2) + (c & 3)] += c2;
+                                if (COLS) {
+                                    const float c1 = reduce_r16(one), c2 = reduce_r16(sv);  // over the group's 16 rows
+                                    if (r16 == 0) {
+                                        wcn[16 * (c >> 2) + (c & 3)] += c1;
+                                        wcx[16 * (c >> 2) + (c & 3)] += c2;
+                                    }
                                 }
                             }
                             rn = reduce_lg(rn);                 // over the wave's 64 columns
@@ -1036,11 +1052,11 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
             if (tdx < BT) {
                 const int64_t o = ((int64_t)ni * p.m_tiles + mi) * BT + tdx;
                 p.rowsum_part[o] = (lrs[tdx] + lrs[BT + tdx]) + (lrs[2 * BT + tdx] + lrs[3 * BT + tdx]);
-                if (EPI == EPI_SUP || epi_is_sets(EPI)) {
+                if (epi_has_labels(EPI) || epi_is_sets(EPI)) {
                     p.rowcnt_part[o] = (lrn[tdx] + lrn[BT + tdx]) + (lrn[2 * BT + tdx] + lrn[3 * BT + tdx]);
                     p.rowsx_part[o] = (lrx[tdx] + lrx[BT + tdx]) + (lrx[2 * BT + tdx] + lrx[3 * BT + tdx]);
                 }
-            } else if (EPI != EPI_EXP_SELF) {
+            } else if (!epi_is_self(EPI)) {
                 const int c = tdx - BT;
                 const int64_t o = ((int64_t)mi * p.n_tiles + ni) * BT + c;
                 p.colsum_part[o] = lcs[c] + lcs[BT + c];
@@ -1266,6 +1282,10 @@ __global__ __launch_bounds__(256) void sup_finalize_kernel(SupFinArgs p) {
 // m is formed again from the labels (1 row label and 8 column labels per thread; the column labels stay in L2).  The partner's
 // weight is ediag_i (u_i + v_p) - (rn_i + rnc_p): with no label shared the subtrahend is exactly 2 and every element has the
 // bits of nce_weights_dt_kernel.
+// SELF (blocks Y and Z of the pooled loss): the element at column row_offset + i is the anchor itself -- no positive, its weight
+// exactly ct * 0 (ediag is not read); the callers pass a vector of zeros for v and rnc, so that a chunk without a match has the
+// bits of nce_weights_dt_kernel at v = 0 and a match is E u_i - rn_i.
+template <bool SELF>
 __global__ __launch_bounds__(256) void sup_weights_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
                                                           const float* v, const float* rn, const float* rnc, const float* ediag,
                                                           const long long* lab_row, const long long* lab_col, int64_t rows,
@@ -1289,7 +1309,8 @@ __global__ __launch_bounds__(256) void sup_weights_kernel(unsigned short* e, int
     for (int k = 0; k < 8; ++k) {
         const int64_t j = j0 + k;
         const long long lck = lab_col[j < cols ? j : cols - 1];
-        if (iok && j < cols && (sup_label_match(lr, lck) || jp == k)) mm |= 1u << k;
+        if (SELF) { if (iok && j < cols && sup_label_match(lr, lck) && jp != k) mm |= 1u << k; }
+        else if (iok && j < cols && (sup_label_match(lr, lck) || jp == k)) mm |= 1u << k;
     }
     float x[8];
     Tr<BF16>::unpack(raw, x);
@@ -1304,7 +1325,7 @@ __global__ __launch_bounds__(256) void sup_weights_kernel(unsigned short* e, int
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         float wv = x[k] * (ui + vv[k]);
-        if (jp == k) wv = ediag[i] * (ui + vv[k]) - (rni + rc[k]);
+        if (jp == k) wv = SELF ? 0.f : ediag[i] * (ui + vv[k]) - (rni + rc[k]);
         else if ((mm >> k) & 1u) wv = x[k] * (ui + vv[k]) - (rni + rc[k]);
         x[k] = ct * wv;
     }
@@ -1748,7 +1769,7 @@ void launch_supcon_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, in
     const SupWs w = sup_carve(workspace, rows, cols, d);
     const int64_t Rp = up256(rows), Cp = up256(cols);
     const int64_t chunks = Rp * (Cp / 8);
-    sup_weights_kernel<<<dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s>>>(
+    sup_weights_kernel<false><<<dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s>>>(
         w.e, Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, (const long long*)row_labels, (const long long*)col_labels, rows, cols,
         row_offset, coef, upstream, dt.t, dt.min_t);
     // the tdot partials go into the first plane of the row partials (dead since the sums launch), as in launch_nce_gemm_grads
@@ -1931,6 +1952,187 @@ void launch_ntxent_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, in
                                                       dt.t, dt.min_t);
     nce_weights_dt_kernel<<<wgrid, dim3(256), 0, s>>>(w.e[2], Cp / 64, Rp / BT, w.uz, w.zero, w.zero, rows, row_offset, coef, 0.0f, upstream,
                                                       dt.t, dt.min_t);
+    const bool want_td = dt.d_t != nullptr;
+    const int64_t n_td = da_tdot_count(rows, cols, d), n_loc = rows * (int64_t)d, n_all = cols * (int64_t)d;
+    const NceGemmArgs g0 = {};
+    // both products always leave float32 slabs, those of W_Y a_all behind those of W_X b_all: one sum, one rounding
+    const int sx = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[0], w.slabs, w.tdot_part, want_td, a_loc, b_all, 0,
+                                                          nullptr, s);
+    const int sy = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[1], w.slabs + sx * n_loc, w.tdot_part + n_td, want_td,
+                                                          a_loc, a_all, 0, nullptr, s);
+    launch_slab_sum(w.slabs, sx + sy, n_loc, d_a_loc, out_bf16, s);
+    const int sz = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[2], w.slabs, w.tdot_part + 2 * n_td, want_td, b_loc,
+                                                          b_all, out_bf16, d_b_loc, s);
+    if (sz) launch_slab_sum(w.slabs, sz, n_loc, d_b_loc, out_bf16, s);
+    if (want_td) launch_nce_dtemp(w.tdot_part, 3 * n_td, 1, dt, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[1], a_loc, out_bf16, d_a_all, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[0], a_loc, 0, w.stage, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[2], b_loc, 0, w.stage + n_all, s);
+    launch_slab_sum(w.stage, 2, n_all, d_b_all, out_bf16, s);
+}
+
+// ---- pooled supervised contrastive loss (Khosla et al.: one pool of both views) on the same GEMMs: NT-Xent's three logits blocks
+// with the label statistics of the supervised loss on each (include/aecf_hip.h) ------------------------------------------------------
+//   X = a_loc . b_all^T (EPI_SUP, the cross-view pass 1 to the bit: row statistics and this rank's column statistics; the partner is
+//       excluded from the matches and joins by index from its own float32 dot)
+//   Y = a_loc . a_all^T, Z = b_loc . b_all^T (EPI_SUP_SELF: the anchor itself, column row_offset + i, is no key and no positive; row
+//       statistics alone)
+// Anchor a_i: (Da, ka, sa) = X's row statistics + Y's; anchor b_g: (Db, kb, sb) = the ranks' column statistics of X plus Z's row
+// statistics of the row's owner -- sup_pool_combine_kernel adds a rank's Z statistics into its own range of col_stats before the ONE
+// all-reduce of [3][cols].  sup_finalize_kernel serves unchanged on the combined statistics; W_X is sup_weights_kernel's, W_Y and W_Z
+// its SELF variant (v = rnc = 0; Z with u and rn gathered at off + i); the six gradient products are those of NT-Xent.
+
+namespace {
+
+// ntx_combine_kernel over the three quantities q (sums of E | counts | matched sums): row_stats[q][i] = X[q][i] + Y[q][i] in place
+// over X's, col_stats[q][off + i] += Z[q][i]; one thread per local row, one float32 addition per quantity and side, no atomics
+__global__ __launch_bounds__(256) void sup_pool_combine_kernel(float* row_stats, const float* y_stats, const float* z_stats,
+                                                               float* col_stats, int64_t rows, int64_t cols, int64_t row_offset,
+                                                               int64_t Rp) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        row_stats[q * Rp + i] = row_stats[q * Rp + i] + y_stats[q * Rp + i];
+        col_stats[q * cols + row_offset + i] = col_stats[q * cols + row_offset + i] + z_stats[q * Rp + i];
+    }
+}
+
+// what the weights of Y and Z read: uz_i = 1 / Db_(off + i) and rnz_i = 1 / nb_(off + i) (the v and rnc of the row's own column; 0 in
+// the padding) and a vector of zeros [Cp] that stands for v and rnc
+__global__ __launch_bounds__(256) void sup_pool_prep_kernel(const float* v, const float* rnc, float* uz, float* rnz, float* zero,
+                                                            int64_t rows, int64_t row_offset, int64_t Rp, int64_t Cp) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < Cp) zero[k] = 0.f;
+    if (k < Rp) {
+        uz[k] = k < rows ? v[row_offset + k] : 0.f;
+        rnz[k] = k < rows ? rnc[row_offset + k] : 0.f;
+    }
+}
+
+struct SupPoolWs {
+    unsigned short* e[3];               // X | Y | Z, each [Rp][Cp] bf16, tiled as E
+    float* row_part;                    // [3][n_tiles][Rp]  sums of E | counts | matched sums, one block after the other
+    float* col_part;                    // [3][m_tiles][Cp]  block X
+    float* row_stats;                   // [3][Rp]  X's, then the combined Da | ka | sa
+    float* y_stats;                     // [3][Rp]
+    float* z_stats;                     // [3][Rp]
+    float* u;                           // [Rp]  1 / Da
+    float* rn;                          // [Rp]  1 / na
+    float* v;                           // [Cp]  1 / Db
+    float* rnc;                         // [Cp]  1 / nb
+    float* uz;                          // [Rp]  1 / Db_(off + i)
+    float* rnz;                         // [Rp]  1 / nb_(off + i)
+    float* ediag;                       // [Rp]
+    float* zero;                        // [Cp]
+    float* tdot_part;                   // [3][splits <= 32][m_tiles][n_tiles_d <= 16]
+    float* slabs;                       // [2 splits][rows][d]: the slabs of W_X b_all, behind them those of W_Y a_all
+    float* stage;                       // [2][cols][d]: W_X^T a_loc | W_Z^T b_loc in float32
+    size_t bytes;
+};
+
+SupPoolWs sup_pool_carve(void* ws, int64_t rows, int64_t cols, int d) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t mt = Rp / BT, nt = Cp / BT;
+    SupPoolWs w;
+    char* p = (char*)ws;
+    size_t off = 0;
+    auto take = [&](size_t n) { char* r = p + off; off += al256(n); return r; };
+    for (int k = 0; k < 3; ++k) w.e[k] = (unsigned short*)take((size_t)Rp * Cp * 2);
+    w.row_part = (float*)take((size_t)3 * nt * Rp * 4);
+    w.col_part = (float*)take((size_t)3 * mt * Cp * 4);
+    w.row_stats = (float*)take((size_t)3 * Rp * 4);
+    w.y_stats = (float*)take((size_t)3 * Rp * 4);
+    w.z_stats = (float*)take((size_t)3 * Rp * 4);
+    w.u = (float*)take((size_t)Rp * 4);
+    w.rn = (float*)take((size_t)Rp * 4);
+    w.v = (float*)take((size_t)Cp * 4);
+    w.rnc = (float*)take((size_t)Cp * 4);
+    w.uz = (float*)take((size_t)Rp * 4);
+    w.rnz = (float*)take((size_t)Rp * 4);
+    w.ediag = (float*)take((size_t)Rp * 4);
+    w.zero = (float*)take((size_t)Cp * 4);
+    w.tdot_part = (float*)take((size_t)3 * 32 * 16 * mt * 4);
+    w.slabs = (float*)take((size_t)2 * da_splits(Rp, Cp, d) * rows * d * 4);
+    w.stage = (float*)take((size_t)2 * cols * d * 4);
+    w.bytes = off;
+    return w;
+}
+
+}  // namespace
+
+// An anchor's count adds the matches of two blocks, each at most cols - 1 (the partner / the anchor excluded): 1 + ka <= 2 cols - 1
+// has to stay exact in float32, so cols <= 2^23 -- half the bound of the cross-view form.
+bool supcon_pool_gemm_supported(int d, float min_temperature, int64_t cols) {
+    return nce_gemm_supported(0, d, min_temperature) && cols <= ((int64_t)1 << 23);
+}
+
+size_t supcon_pool_gemm_workspace_bytes(int64_t rows, int64_t cols, int d) { return sup_pool_carve(nullptr, rows, cols, d).bytes + 256; }
+
+// pass 1: the three blocks, the combined row statistics (workspace) and col_stats [3][cols] = this rank's column statistics of X, plus
+// the row statistics of Z on [row_offset, row_offset + rows)
+void launch_supcon_pool_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                   const void* b_loc, const void* a_all, const void* b_all, const int64_t* row_labels,
+                                   const int64_t* col_labels, void* workspace, float* col_stats, hipStream_t s) {
+    const SupPoolWs w = sup_pool_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    for (int k = 0; k < 3; ++k) {
+        LogitsLaunch L = logits_args(rows, cols, d, k == 2 ? b_loc : a_loc, k == 1 ? a_all : b_all);
+        NceGemmArgs& g = L.g;
+        g.e = w.e[k]; g.e_tiles = Cp / 64;
+        g.temp = dt.t; g.min_temp = dt.min_t; g.row_offset = row_offset;
+        g.lab_row = (const long long*)row_labels; g.lab_col = (const long long*)col_labels;
+        const int64_t rplane = (int64_t)g.n_tiles * Rp, cplane = (int64_t)g.m_tiles * Cp;
+        g.rowsum_part = w.row_part; g.rowcnt_part = w.row_part + rplane; g.rowsx_part = w.row_part + 2 * rplane;
+        if (k == 0) {
+            g.colsum_part = w.col_part; g.colcnt_part = w.col_part + cplane; g.colsx_part = w.col_part + 2 * cplane;
+            launch_gemm<OP_ROW, OP_ROW, EPI_SUP, MAP_2D>(g, L.blocks, s);
+            sup_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64), 3), dim3(256), 0, s>>>(w.row_part, w.col_part, g.m_tiles, g.n_tiles, rows,
+                                                                                      cols, w.row_stats, col_stats);
+        } else {
+            launch_gemm<OP_ROW, OP_ROW, EPI_SUP_SELF, MAP_2D>(g, L.blocks, s);
+            // the row blocks of the sums launch alone: this block leaves no column partials
+            sup_sums_kernel<<<dim3((unsigned)(Rp / 64), 3), dim3(256), 0, s>>>(w.row_part, nullptr, g.m_tiles, g.n_tiles, rows, cols,
+                                                                               k == 1 ? w.y_stats : w.z_stats, nullptr);
+        }
+    }
+    sup_pool_combine_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s>>>(w.row_stats, w.y_stats, w.z_stats, col_stats, rows,
+                                                                                       cols, row_offset, Rp);
+}
+
+// normalisers + loss rows of this rank's 2 rows anchors from the col_stats of all ranks: sup_finalize_kernel on the combined statistics
+void launch_supcon_pool_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                  const void* b_all, const float* col_stats, void* workspace, float* loss_rows, hipStream_t s) {
+    const SupPoolWs w = sup_pool_carve(workspace, rows, cols, d);
+    SupFinArgs f = {};
+    f.a = (const unsigned short*)a_loc; f.b = (const unsigned short*)b_all; f.row_stats = w.row_stats; f.col_stats = col_stats;
+    f.u = w.u; f.rn = w.rn; f.v = w.v; f.rnc = w.rnc; f.loss_rows = loss_rows; f.ediag = w.ediag;
+    f.rows = rows; f.cols = cols; f.row_offset = row_offset; f.Rp = up256(rows); f.Cp = up256(cols); f.d = d;
+    f.temp = dt.t; f.min_temp = dt.min_t;
+    sup_finalize_kernel<<<dim3((unsigned)((f.Rp + 3) / 4)), dim3(256), 0, s>>>(f);
+}
+
+// gradients: the three weights passes in place, then the six products in the arrangement of launch_ntxent_gemm_grads
+//   d_a_loc = W_X b_all + W_Y a_all (one slab sum over both products' slabs)      d_b_loc = W_Z b_all
+//   d_a_all = W_Y^T a_loc                                                         d_b_all = W_X^T a_loc + W_Z^T b_loc (float32 stage)
+// every output rounded once from its float32 sum; dt.d_t from the partials of the three da products, one fixed-order reduction
+void launch_supcon_pool_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef,
+                                   const void* a_loc, const void* b_loc, const void* a_all, const void* b_all, const int64_t* row_labels,
+                                   const int64_t* col_labels, void* workspace, const float* upstream, int out_bf16, void* d_a_loc,
+                                   void* d_b_loc, void* d_a_all, void* d_b_all, hipStream_t s) {
+    const SupPoolWs w = sup_pool_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t chunks = Rp * (Cp / 8);
+    const dim3 wgrid((unsigned)((chunks + 255) / 256));
+    const long long* lr = (const long long*)row_labels;
+    const long long* lc = (const long long*)col_labels;
+    sup_pool_prep_kernel<<<dim3((unsigned)(Cp / 256)), dim3(256), 0, s>>>(w.v, w.rnc, w.uz, w.rnz, w.zero, rows, row_offset, Rp, Cp);
+    sup_weights_kernel<false><<<wgrid, dim3(256), 0, s>>>(w.e[0], Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, lr, lc, rows, cols,
+                                                          row_offset, coef, upstream, dt.t, dt.min_t);
+    sup_weights_kernel<true><<<wgrid, dim3(256), 0, s>>>(w.e[1], Cp / 64, Rp / BT, w.u, w.zero, w.rn, w.zero, nullptr, lr, lc, rows, cols,
+                                                         row_offset, coef, upstream, dt.t, dt.min_t);
+    sup_weights_kernel<true><<<wgrid, dim3(256), 0, s>>>(w.e[2], Cp / 64, Rp / BT, w.uz, w.zero, w.rnz, w.zero, nullptr, lr, lc, rows, cols,
+                                                         row_offset, coef, upstream, dt.t, dt.min_t);
     const bool want_td = dt.d_t != nullptr;
     const int64_t n_td = da_tdot_count(rows, cols, d), n_loc = rows * (int64_t)d, n_all = cols * (int64_t)d;
     const NceGemmArgs g0 = {};

@@ -800,8 +800,8 @@ def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Ten
     differs from the reference code of Khosla et al. (``SupConLoss``) only by that code's ``T / base_T`` factor.  Both
     directions run the streaming kernels (aecf_supcon_pool_fwd_bwd) against one key buffer, the gathered rows of view b then
     those of view a; it needs bfloat16 rows, d in 128 .. 1024 as above and 2 B_all < 2^31; ``low_memory`` True or None take
-    it, ``False`` raises NotImplementedError (the tile form has no intra-view keys).  With every label negative it is
-    ``nt_xent``."""
+    it, ``False`` raises NotImplementedError: the tile form of the pooled loss is a function of its own,
+    ``pooled_supervised_contrastive(..., low_memory=False)``.  With every label negative it is ``nt_xent``."""
     if intra_view and low_memory is False:
         raise NotImplementedError("aecf_amd: the tile form of the supervised contrastive loss has no intra-view keys (it forms "
                                   "the a x b block only); intra_view=True runs the streaming form, low_memory=True or None")
@@ -1025,6 +1025,171 @@ def nt_xent(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch.
         if out is not None:
             return out
     labels = torch.full((za.shape[0],), -1, dtype=torch.int64, device=za.device)
+    return supervised_contrastive(za, zb, labels, temperature, group, min_temperature, True, True)
+
+
+class _SupConPoolSymmetric(torch.autograd.Function):
+    """aecf_supcon_pool_sym_pass1 / _loss / _grads: the 2 b_local anchors of this rank's pooled supervised contrastive loss from
+    three blocks of logits (a_loc x b_all, a_loc x a_all, b_loc x b_all; the anchor itself left out of the last two by index), the
+    labels shared by the two views.  Modelled on ``_NtXentSymmetric``: the [3, cols] column statistics -- those of the a x b
+    block, plus the b x b row statistics on this rank's own range -- are the one thing ranks exchange, one all-reduce between pass
+    1 and the loss; the gradients on the gathered rows are this rank's shares.  The backward runs the three weights passes and
+    the six gradient products once, scaled on the device by the gradient that arrives and written in the inputs' dtype.  The
+    temperature is a one-element float32 device tensor; the backward returns this rank's share of dL/dT."""
+
+    @staticmethod
+    def forward(ctx, a, b, a_all, b_all, row_labels, col_labels, row_offset, temperature, coef, group, min_temperature):
+        lib = _lib.load()
+        rows, d = a.shape
+        cols = b_all.shape[0]
+        dev = a.device
+        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b.detach().to(torch.bfloat16).contiguous()
+        aa, ba = a_all.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
+        lr, lc = row_labels.contiguous(), col_labels.contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws_bytes = lib.aecf_supcon_pool_sym_workspace_bytes(rows, cols, d)
+        if ws_bytes == 0:
+            raise NotImplementedError(f"aecf_amd: the tile form of the pooled supervised contrastive loss needs d % 64 == 0, 64 <= d "
+                                      f"<= 4096 and at most 2^23 gathered rows; got d = {d}, {cols} rows")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        col_stats = torch.empty(3, cols, **f32)
+        t = temperature.detach()
+        tp, t_min = _ptr(t), float(min_temperature)
+        _lib.check(lib.aecf_supcon_pool_sym_pass1(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(aa), _ptr(ba),
+                                                  _ptr(lr), _ptr(lc), _ptr(ws), ws_bytes, _ptr(col_stats), _stream()),
+                   "aecf_supcon_pool_sym_pass1")
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(col_stats, group=group)
+        loss_rows = torch.empty(rows, **f32)
+        _lib.check(lib.aecf_supcon_pool_sym_loss(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(ba), _ptr(col_stats), _ptr(ws),
+                                                 ws_bytes, _ptr(loss_rows), _stream()), "aecf_supcon_pool_sym_loss")
+        ctx.save_for_backward(ac, bc, aa, ba, lr, lc, ws, t)
+        ctx.meta = ((a.dtype, b.dtype, a_all.dtype, b_all.dtype), temperature.shape,
+                    (rows, cols, int(row_offset), d, float(coef), t_min, ws_bytes))
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = _lib.load()
+        ac, bc, aa, ba, lr, lc, ws, t = ctx.saved_tensors
+        dts, t_shape, (rows, cols, row_offset, d, coef, t_min, ws_bytes) = ctx.meta
+        if getattr(ctx, "_spent", False):
+            raise RuntimeError("aecf_amd: the tile-form pooled supervised contrastive backward runs once per forward (it consumes "
+                               "the stored logits)")
+        ctx._spent = True
+        gdt = torch.bfloat16 if all(x == torch.bfloat16 for x in dts) else torch.float32
+        dev = ac.device
+        d_a, d_b = torch.empty(rows, d, dtype=gdt, device=dev), torch.empty(rows, d, dtype=gdt, device=dev)
+        d_aa, d_ba = torch.empty(cols, d, dtype=gdt, device=dev), torch.empty(cols, d, dtype=gdt, device=dev)
+        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
+        d_t = torch.empty(1, dtype=torch.float32, device=dev) if ctx.needs_input_grad[7] else None
+        _lib.check(lib.aecf_supcon_pool_sym_grads(rows, cols, row_offset, d, _ptr(t), t_min, coef, _ptr(ac), _ptr(bc), _ptr(aa), _ptr(ba),
+                                                  _ptr(lr), _ptr(lc), _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt], _ptr(d_a), _ptr(d_b),
+                                                  _ptr(d_aa), _ptr(d_ba), _ptr(d_t), _stream()), "aecf_supcon_pool_sym_grads")
+        g_t = d_t.reshape(t_shape) if d_t is not None else None
+        return d_a.to(dts[0]), d_b.to(dts[1]), d_aa.to(dts[2]), d_ba.to(dts[3]), None, None, None, g_t, None, None, None
+
+
+def _supcon_pool_tile_refusal(z: torch.Tensor, zb: torch.Tensor, cols: int, min_temperature: float) -> Optional[str]:
+    """None where the tile form of the pooled supervised contrastive loss runs; else what stands against it.  The memory test
+    (three b_local x b_all bfloat16 blocks and the float32 staging within 0.6 of the free device memory) is skipped while a graph
+    is being captured."""
+    rows, d = z.shape
+    if z.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16:
+        return f"bfloat16 rows (got {z.dtype} and {zb.dtype})"
+    if d % 64 != 0 or not 64 <= d <= 4096:
+        return f"d % 64 == 0 with 64 <= d <= 4096 (got d = {d})"
+    if not float(min_temperature) >= MIN_TEMPERATURE:
+        return f"min_temperature >= {MIN_TEMPERATURE} (got {min_temperature}): 1 / T is the constant shift of every exponential"
+    need = _lib.load().aecf_supcon_pool_sym_workspace_bytes(rows, cols, d)
+    if need == 0:
+        return f"at most 2^23 gathered rows (got {cols}): the counts of two blocks add in float32"
+    if not _capturing() and need > 0.6 * torch.cuda.mem_get_info(z.device)[0]:
+        return f"a workspace (three b_local x b_all bfloat16 blocks, {need} bytes here) within 0.6 of the free device memory"
+    return None
+
+
+def _supcon_pool_tile(za: torch.Tensor, zb: torch.Tensor, labels: torch.Tensor, temperature, group, min_temperature: float,
+                      required: bool):
+    """The tile form of ``pooled_supervised_contrastive``, or None where it does not run and ``required`` is False (the caller
+    then streams)."""
+    if za.shape != zb.shape or za.dim() != 2:
+        raise ValueError(f"pooled_supervised_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and "
+                         f"{tuple(zb.shape)}")
+    labels = _labels_arg(labels, za)
+    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
+        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
+    rank, world = dp.world_info(group)
+    if world > 1:
+        n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
+        got = [torch.zeros_like(n) for _ in range(world)]
+        torch.distributed.all_gather(got, n, group=group)
+        sizes = [int(v.item()) for v in got]
+        offset, b_all = sum(sizes[:rank]), sum(sizes)
+    else:
+        sizes, offset, b_all = None, 0, za.shape[0]
+    refusal = _supcon_pool_tile_refusal(za, zb, b_all, min_temperature)
+    tile = refusal is None
+    if world > 1:                                   # every rank must take the same form (they exchange different things)
+        flag = torch.tensor([1 if tile else 0], device=za.device)
+        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
+        if tile and not bool(int(flag.item())):
+            tile, refusal = False, "the same on every rank (another rank refused it)"
+    if not tile:
+        if required:
+            raise NotImplementedError("aecf_amd: the tile form of the pooled supervised contrastive loss needs " + refusal)
+        return None
+    t = _temperature_arg(temperature, za, min_temperature)
+    if not isinstance(t, torch.Tensor):
+        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    lab = labels.detach().to(torch.int64)
+    na, nb = l2_normalize(za), l2_normalize(zb)
+    na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
+    nb_all = dp.all_gather_rows(nb, group, sizes=sizes) if world > 1 else nb
+    lab_all = dp.all_gather_rows(lab, group, sizes=sizes) if world > 1 else lab
+    share = _SupConPoolSymmetric.apply(na, nb, na_all, nb_all, lab, lab_all, offset, t, 0.5 / float(b_all), group,
+                                       float(min_temperature))
+    if world == 1:
+        return share
+    total = share.detach().clone()
+    torch.distributed.all_reduce(total, group=group)
+    scaled = share * world
+    return scaled + (total - scaled.detach())
+
+
+def pooled_supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Tensor,
+                                  temperature: Union[float, torch.Tensor] = 0.07, group=None,
+                                  min_temperature: float = MIN_TEMPERATURE, low_memory: Optional[bool] = True) -> torch.Tensor:
+    """The supervised contrastive loss as published (Khosla et al. 2020) between the local rows of two views, keys from every rank
+    of ``group``: the 2 B_all rows of both views are one pool, every row is an anchor against the other 2 B_all - 1 rows, and its
+    positives are its partner and every row of EITHER view with the same non-negative label,
+
+        L = 1 / (2 B_all) * sum over the 2 B_all anchors of [ logsumexp_{k != self} x_k - mean_{k in positives} x_k ],
+        x = n . n_k / max(T, min_temperature)
+
+    ``labels``: as for ``supervised_contrastive``.  ``low_memory``: which of the two implementations runs.  ``True`` (the
+    default) is ``supervised_contrastive(za, zb, labels, ..., intra_view=True)``: the same streaming kernels
+    (aecf_supcon_pool_fwd_bwd), bits, messages and requirements.  ``False``: the tile-GEMM form (aecf_supcon_pool_sym_pass1 /
+    _loss / _grads): the three blocks of logits of ``nt_xent``'s tile form (a_loc x b_all, a_loc x a_all, b_loc x b_all, the
+    anchor itself left out by index) kept as bfloat16 exponentials between forward and backward, the label positives a sparse
+    correction to NT-Xent's weights whose statistics are combined over the three blocks -- 18 rows cols d matrix flops against
+    the streaming form's 64.  It needs bfloat16 rows, d % 64 == 0 (64 to 4096), ``min_temperature >= 0.025``, at most 2^23
+    gathered rows and its workspace (those three blocks plus float32 staging) within 0.6 of the free device memory (not tested
+    while capturing), and raises NotImplementedError naming the limit otherwise; its backward runs once per forward.  With every
+    label negative it has the bits of ``nt_xent(low_memory=False)``.  ``None``: the tile form wherever it runs, the streaming
+    form otherwise (at 8192 x 65536 x 768 the tile form's whole range of times lies below the streaming form's, 11.0 ms against
+    53.8 ms: profiles/supcon_pool_tile_time.txt).  Under data parallel the tile form gathers both views and the labels,
+    the ranks agree on one form (a MIN all-reduce) and all-reduce the [3, b_all] column statistics between the passes; the
+    returned value follows ``info_nce``'s convention.  ``temperature``: as for ``supervised_contrastive`` (a float or a learnable
+    one-element device tensor, no host read: on one rank the call captures into a graph)."""
+    if low_memory not in (True, False, None):
+        raise ValueError(f"aecf_amd: low_memory must be True, False or None, got {low_memory!r}")
+    if low_memory is not True:
+        _require_device(za, "za")
+        _require_device(zb, "zb")
+        out = _supcon_pool_tile(za, zb, labels, temperature, group, min_temperature, required=low_memory is False)
+        if out is not None:
+            return out
     return supervised_contrastive(za, zb, labels, temperature, group, min_temperature, True, True)
 
 
@@ -1458,18 +1623,22 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
     implementation, ignored for ``info_nce``); ``contrastive="supervised"`` takes ``supervised_contrastive(za, zb, labels,
     temperature)`` -- handed ``low_memory`` when it is not None (False: the tile-GEMM form), its own default (the streaming form)
     otherwise -- and ``contrastive="multilabel"`` takes ``multilabel_contrastive(za, zb, labels, label_weighting,
-    temperature)``, handed ``low_memory`` in the same way, with ``labels`` the label sets (multi-hot rows or int64 masks); these two are the only forms that take
+    temperature)``, handed ``low_memory`` in the same way, with ``labels`` the label sets (multi-hot rows or int64 masks); these two and ``supervised_pool`` are the only forms that take
     ``labels``, and ``label_weighting`` ("overlap" or "jaccard") is read by the multi-label form alone.  ``contrastive="nt_xent"``
     takes ``nt_xent(za, zb, temperature)``, the pool of both views without labels, handed ``low_memory`` when it is not None
     (False: its tile-GEMM form) and its own default (the streaming form) otherwise; ``intra_view`` is handed to the supervised
-    form (True: the same pool with label positives from either view) and read by no other."""
-    if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel", "nt_xent"):
-        raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid', 'supervised', 'multilabel' or 'nt_xent', got "
-                         f"{contrastive!r}")
-    if contrastive in ("supervised", "multilabel") and labels is None:
+    form (True: the same pool with label positives from either view) and read by no other.
+    ``contrastive="supervised_pool"`` takes ``pooled_supervised_contrastive(za, zb, labels, temperature)``, that pooled loss
+    under a name of its own, handed ``low_memory`` when it is not None (False: its tile-GEMM form) and its own default (the
+    streaming form) otherwise; it takes ``labels`` and ignores ``intra_view``."""
+    if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel", "nt_xent", "supervised_pool"):
+        raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid', 'supervised', 'multilabel', 'nt_xent' or "
+                         f"'supervised_pool', got {contrastive!r}")
+    if contrastive in ("supervised", "multilabel", "supervised_pool") and labels is None:
         raise ValueError(f"aecf_amd: contrastive={contrastive!r} needs labels")
-    if contrastive not in ("supervised", "multilabel") and labels is not None:
-        raise ValueError(f"aecf_amd: labels are taken by contrastive='supervised' and 'multilabel' only, got contrastive={contrastive!r}")
+    if contrastive not in ("supervised", "multilabel", "supervised_pool") and labels is not None:
+        raise ValueError(f"aecf_amd: labels are taken by contrastive='supervised', 'multilabel' and 'supervised_pool' only, got "
+                         f"contrastive={contrastive!r}")
     if label_weighting not in SET_WEIGHTINGS:
         raise ValueError(f"aecf_amd: label_weighting must be 'overlap' or 'jaccard', got {label_weighting!r}")
     total = task_loss
@@ -1493,6 +1662,11 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
                 term = nt_xent(za, zb, temperature, group, min_temperature)
             else:
                 term = nt_xent(za, zb, temperature, group, min_temperature, low_memory)
+        elif contrastive == "supervised_pool":
+            if low_memory is None:
+                term = pooled_supervised_contrastive(za, zb, labels, temperature, group, min_temperature)
+            else:
+                term = pooled_supervised_contrastive(za, zb, labels, temperature, group, min_temperature, low_memory)
         else:
             term = info_nce(za, zb, temperature, group, min_temperature)
         total = _plus(total, contrastive_weight * term)

@@ -793,6 +793,70 @@ int aecf_ntxent_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_
                           const void* b_all, void* workspace, size_t workspace_bytes, const float* upstream, int32_t grad_dtype,
                           void* d_a_loc, void* d_b_loc, void* d_a_all, void* d_b_all, float* d_temperature, void* stream);
 
+/* ---- pooled supervised contrastive loss, tile-GEMM form (build-defined; aecf_supcon_pool_fwd_bwd's loss over both anchor halves) ----
+ * The supervised contrastive loss of Khosla et al. over ONE pool of the 2 cols rows of both views: every row is an anchor, its
+ * keys are the other 2 cols - 1 rows, its positives among them its partner in the other view (by INDEX) and every row of either
+ * view with its label.  Buffers as in the NT-Xent tile form (a_loc, b_loc [rows,d], a_all, b_all [cols,d], unit-norm bf16 rows;
+ * a_all / b_all may alias a_loc / b_loc on one rank), labels as in the supervised tile form: int64 DEVICE arrays row_labels [rows],
+ * col_labels [cols], SHARED by the views, a negative label = unlabeled.  m_ij = [row_labels[i] == col_labels[j] >= 0], all 64 bits
+ * compared.  Tc = max(*temperature, min_temperature), E(s) = exp((s - 1) / Tc).  Three logits blocks, per row i of the rank:
+ *   X = a_loc . b_all^T   the partner (column row_offset + i) excluded from m, counted by index     lX, nX, sX   and columns cX, ncX, scX
+ *   Y = a_loc . a_all^T   the anchor itself (column row_offset + i) excluded by INDEX: no key, no positive      lY, nY, sY
+ *   Z = b_loc . b_all^T   the same                                                                              lZ, nZ, sZ
+ * (l: sum of E, n: matches by label, s: float32 sum of their raw scores.)  Anchor a_i: Da = lX + lY, ka = nX + nY, sa = sX + sY,
+ * local.  Anchor b_g, g = row_offset + i: Db_g = sum over ranks of cX_g + lZ_g, kb_g = sum ncX_g + nZ_g, sb_g = sum scX_g + sZ_g
+ * (Z of the rank that owns row g).  With dot_i = a_i . b_g, na = 1 + ka, nb = 1 + kb:
+ *   loss_rows[i] = [log Da_i + 1/Tc - (dot_i + sa_i) / na_i / Tc] + [log Db_g + 1/Tc - (dot_i + sb_g) / nb_g / Tc]      WITHOUT coef
+ *   W_X = ct (E_X (1/Da_i + 1/Db_j) - m_ij (1/na_i + 1/nb_j)), the partner a positive by index with its float32 exponential
+ *   W_Y = ct (E_Y / Da_i - m_ij / na_i)       W_Z = ct (E_Z / Db_g - m_ij / nb_g)       both exactly 0 at the excluded key
+ *         ct = coef / Tc * upstream
+ *   d_a_loc = W_X b_all + W_Y a_all [rows,d]     d_b_loc = W_Z b_all [rows,d]
+ *   d_a_all = W_Y^T a_loc [cols,d]               d_b_all = W_X^T a_loc + W_Z^T b_loc [cols,d]        (this rank's shares)
+ *   dT = -(1/Tc) [ sum_i a_i . d_a_loc_i + sum_i b_i . d_b_loc_i ]   (0 where *temperature < min_temperature)
+ * The shares of the ranks sum to the global gradients.  With every label negative, or all labels distinct, every output has the
+ * bits of aecf_ntxent_sym_pass1 / _loss / _grads on the same inputs (col_stats[0] those of col_sums).
+ *   pass1: the three logits GEMMs.  X is aecf_supcon_sym_pass1 to the bit; Y and Z run an epilogue of their own (the E loop of the
+ *          NT-Xent blocks, the row half of X's label search with the anchor excluded by index, no column statistics).  Then the
+ *          combined row statistics (workspace) and col_stats [3][cols] float32 = this rank's column statistics of X (c | count |
+ *          raw-score sum), plus Z's row statistics on its own range [row_offset, row_offset + rows): one float32 addition per
+ *          quantity and side, fixed order, no atomics.
+ *   caller: all-reduce (sum) of col_stats over the ranks (nothing to do on one rank): it then holds Db | kb | sb.
+ *   loss:  loss_rows [rows]; prepares 1/Da, 1/na (rows) and 1/Db, 1/nb (columns) in the workspace.
+ *   grads: the three weights passes in place over the blocks (m formed again from the labels), then the six products as in
+ *          aecf_ntxent_sym_grads: two products on one output are summed in float32 and rounded ONCE to grad_dtype; everything is
+ *          multiplied by upstream[0] (a DEVICE float32 scalar, NULL = 1); d_temperature (may be NULL) is WRITTEN with this rank's
+ *          share of dL/dT times upstream[0].  It consumes the stored blocks: it runs once per pass1.
+ * Served: bf16 rows, d % 64 == 0, 64 <= d <= 4096, min_temperature >= 0.025, rows <= cols, cols <= 2^23: counts travel as float32
+ * and an anchor's count adds two blocks' (each at most cols - 1), so na = 1 + ka <= 2 cols - 1 is exact in float32 up to
+ * cols = 2^23, half the bound of the cross-view form.  18 rows cols d MFMA flops.
+ * Workspace, in order, each piece rounded up to 256 bytes, Rp / Cp = rows / cols rounded up to 256, + 256 bytes:
+ *   E_X | E_Y | E_Z, each [Rp][Cp] bf16 | row partials [3][Cp/256][Rp] | column partials [3][Rp/256][Cp] |
+ *   row statistics [3][Rp] (X's, then combined) | Y's [3][Rp] | Z's [3][Rp] | 1/Da [Rp] | 1/na [Rp] | 1/Db [Cp] | 1/nb [Cp] |
+ *   1/Db at the partner [Rp] | 1/nb at the partner [Rp] | the partner's exponential [Rp] | zeros [Cp] |
+ *   dT partials [3][32][16][Rp/256] | da slabs [2 splits][rows][d] | d_b_all stage [2][cols][d]
+ *   (float32 but E; splits: the K split of da = W b, as in the InfoNCE form).  The query answers 0 where the shape is not served
+ *   (d, rows > cols, cols > 2^23).
+ * Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host, nothing read from the
+ * workspace before it is written; no float atomics: the same inputs give the same bits.  Checks before any launch, in the order
+ * of the supervised tile form: sizes (rows, cols, d > 0, cols < 2^31, min_temperature > 0, 0 <= row_offset, row_offset + rows <=
+ * cols: AECF_ERR_BAD_DIMS), then d, min_temperature < 0.025, cols > 2^23 or a grad_dtype other than bf16 / float32
+ * (AECF_ERR_UNSUPPORTED), then NULL pointers (AECF_ERR_NULL_POINTER; upstream and d_temperature may be NULL), then the workspace
+ * size (AECF_ERR_WORKSPACE). */
+size_t aecf_supcon_pool_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d);      /* 0: not served */
+int aecf_supcon_pool_sym_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                               float min_temperature, const void* a_loc, const void* b_loc, const void* a_all, const void* b_all,
+                               const int64_t* row_labels, const int64_t* col_labels, void* workspace, size_t workspace_bytes,
+                               float* col_stats /* [3][cols] */, void* stream);
+int aecf_supcon_pool_sym_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                              float min_temperature, const void* a_loc, const void* b_all,
+                              const float* col_stats /* summed over ranks */, void* workspace, size_t workspace_bytes,
+                              float* loss_rows, void* stream);
+int aecf_supcon_pool_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                               float min_temperature, float coef, const void* a_loc, const void* b_loc, const void* a_all,
+                               const void* b_all, const int64_t* row_labels, const int64_t* col_labels, void* workspace,
+                               size_t workspace_bytes, const float* upstream, int32_t grad_dtype, void* d_a_loc, void* d_b_loc,
+                               void* d_a_all, void* d_b_all, float* d_temperature, void* stream);
+
 /* ---- multi-label supervised contrastive loss (build-defined like the supervised term above, whose contract this one repeats) ----
  * One direction as above, with a SET of classes per row instead of one class: q_sets [rows] and k_sets [cols] are DEVICE arrays of
  * one uint64 per row, bit c = class c, C <= 64 classes (aecf_label_sets_pack makes them from multi-hot rows).  A key counts with a
