@@ -233,6 +233,16 @@ _SYMBOLS = [
     ("aecf_supcon_pool_sym_grads", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
       c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # pooled multi-label contrastive loss on the tile GEMMs: the pooled form with class sets and a weighting in place of the labels
+    ("aecf_supcon_ml_pool_sym_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
+    ("aecf_supcon_ml_pool_sym_pass1", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+      c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("aecf_supcon_ml_pool_sym_loss", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("aecf_supcon_ml_pool_sym_grads", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_int32, c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # multi-label contrastive loss, symmetric, on the tile GEMMs: class sets and a weighting in place of the labels
     ("aecf_supcon_ml_sym_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
     ("aecf_supcon_ml_sym_pass1", c_int,

@@ -1194,6 +1194,64 @@ int aecf_supcon_ml_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int
     return launch_status();
 }
 
+// ---- the pooled form with class sets (include/aecf_hip.h, "pooled multi-label contrastive loss, tile-GEMM form")
+
+size_t aecf_supcon_ml_pool_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || rows > cols || cols > 0x7fffffff || !supcon_ml_pool_gemm_supported(d, 0.025f, cols)) return 0;
+    return supcon_ml_pool_gemm_workspace_bytes(rows, cols, d);
+}
+
+int aecf_supcon_ml_pool_sym_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                                  float min_temperature, const void* a_loc, const void* b_loc, const void* a_all, const void* b_all,
+                                  const int64_t* row_sets, const int64_t* col_sets, int32_t weighting, void* workspace,
+                                  size_t workspace_bytes, float* col_stats, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!supcon_ml_pool_gemm_supported(d, min_temperature, cols)) return AECF_ERR_UNSUPPORTED;
+    if (weighting != AECF_SETS_OVERLAP && weighting != AECF_SETS_JACCARD) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_loc || !a_all || !b_all || !row_sets || !col_sets || !workspace || !col_stats)
+        return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < supcon_ml_pool_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_supcon_ml_pool_gemm_pass1(rows, cols, row_offset, d, dt, a_loc, b_loc, a_all, b_all, row_sets, col_sets,
+                                     weighting == AECF_SETS_JACCARD ? 1 : 0, workspace, col_stats, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_supcon_ml_pool_sym_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                                 float min_temperature, const void* a_loc, const void* b_all, const float* col_stats, void* workspace,
+                                 size_t workspace_bytes, float* loss_rows, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!supcon_ml_pool_gemm_supported(d, min_temperature, cols)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_all || !col_stats || !workspace || !loss_rows) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < supcon_ml_pool_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_supcon_ml_pool_gemm_loss(rows, cols, row_offset, d, dt, a_loc, b_all, col_stats, workspace, loss_rows, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_supcon_ml_pool_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                                  float min_temperature, float coef, const void* a_loc, const void* b_loc, const void* a_all,
+                                  const void* b_all, const int64_t* row_sets, const int64_t* col_sets, int32_t weighting,
+                                  void* workspace, size_t workspace_bytes, const float* upstream, int32_t grad_dtype, void* d_a_loc,
+                                  void* d_b_loc, void* d_a_all, void* d_b_all, float* d_temperature, void* stream) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!supcon_ml_pool_gemm_supported(d, min_temperature, cols)) return AECF_ERR_UNSUPPORTED;
+    if (weighting != AECF_SETS_OVERLAP && weighting != AECF_SETS_JACCARD) return AECF_ERR_UNSUPPORTED;
+    if (grad_dtype != AECF_BF16 && grad_dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_loc || !a_all || !b_all || !row_sets || !col_sets || !workspace || !d_a_loc || !d_b_loc ||
+        !d_a_all || !d_b_all)
+        return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < supcon_ml_pool_gemm_workspace_bytes(rows, cols, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    launch_supcon_ml_pool_gemm_grads(rows, cols, row_offset, d, dt, coef, a_loc, b_loc, a_all, b_all, row_sets, col_sets,
+                                     weighting == AECF_SETS_JACCARD ? 1 : 0, workspace, upstream, grad_dtype == AECF_BF16 ? 1 : 0,
+                                     d_a_loc, d_b_loc, d_a_all, d_b_all, (hipStream_t)stream);
+    return launch_status();
+}
+
 int aecf_label_sets_pack(int64_t rows, int32_t classes, int32_t kind, const void* multi_hot, uint64_t* sets, void* stream) {
     if (rows <= 0 || classes <= 0 || classes > 64) return AECF_ERR_BAD_DIMS;
     if (kind != AECF_BF16 && kind != AECF_F32 && kind != AECF_F16 && kind != AECF_SETS_U8) return AECF_ERR_UNSUPPORTED;

@@ -378,6 +378,22 @@ void launch_supcon_pool_gemm_grads(int64_t rows, int64_t cols, int64_t row_offse
                                    const int64_t* col_labels, void* workspace, const float* upstream, int out_bf16, void* d_a_loc,
                                    void* d_b_loc, void* d_a_all, void* d_b_all, hipStream_t s);
 
+// Pooled multi-label contrastive loss on the tile GEMMs (aecf_nce_gemm.hip): the pooled form above with class sets (one 64-bit word
+// per row, bit c = class c) and the overlap (jaccard 0) or Jaccard (jaccard 1) weight in place of the match -- X runs EPI_SETS_OV /
+// EPI_SETS_JAC, Y and Z EPI_SETS_OV_SELF / EPI_SETS_JAC_SELF (rows only, the anchor's own key weighs 0 by index).  Workspace,
+// supported shapes and col_stats [3][cols] (column sums of E | sums of w | sums of w * raw score) are those of the pooled form.
+bool supcon_ml_pool_gemm_supported(int d, float min_temperature, int64_t cols);
+size_t supcon_ml_pool_gemm_workspace_bytes(int64_t rows, int64_t cols, int d);
+void launch_supcon_ml_pool_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                      const void* b_loc, const void* a_all, const void* b_all, const int64_t* row_sets,
+                                      const int64_t* col_sets, int jaccard, void* workspace, float* col_stats, hipStream_t s);
+void launch_supcon_ml_pool_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                     const void* b_all, const float* col_stats, void* workspace, float* loss_rows, hipStream_t s);
+void launch_supcon_ml_pool_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef,
+                                      const void* a_loc, const void* b_loc, const void* a_all, const void* b_all, const int64_t* row_sets,
+                                      const int64_t* col_sets, int jaccard, void* workspace, const float* upstream, int out_bf16,
+                                      void* d_a_loc, void* d_b_loc, void* d_a_all, void* d_b_all, hipStream_t s);
+
 // Multi-label supervised contrastive loss, streaming (aecf_supcon_ml_flash.hip): a set of classes per row as one uint64 (bit c =
 // class c); a key counts with weight 1 (the partner), [sets overlap] (jaccard 0) or |and| / |or| (jaccard 1).  The same passes,
 // workspace layout and outputs as launch_supcon_flash.  launch_label_sets_pack: multi-hot rows [rows, classes <= 64] of kind

@@ -116,6 +116,15 @@
 // E and the LDS column slots of the matches.  sup_pool_combine_kernel adds X's and Y's row statistics (anchor a_i) and puts Z's into
 // the rank's own range of col_stats [3][cols] before the one all-reduce (anchor b_g); sup_finalize_kernel and sup_weights_kernel serve
 // unchanged, Y and Z take the SELF variant of the weights (v = rnc = 0, nothing at the excluded key).  Products as NT-Xent's.
+//
+// The pooled multi-label form (aecf_supcon_ml_pool_sym_pass1 / _loss / _grads) is that pooled loss with the dense set weights of the
+// multi-label form: X runs EPI_SETS_OV / EPI_SETS_JAC unchanged, Y and Z two further epilogues, EPI_SETS_OV_SELF / EPI_SETS_JAC_SELF --
+// EPI_EXP_SELF's E loop, the words staged in LDS as EPI_SETS_* stage them, then the ROW half of the dense sweep in the same chain
+// order (ct-major over the lane's 16 elements of a row, the lane groups, the four column waves, sup_sums_kernel), the anchor's own
+// element weighing 0 BY INDEX on the tiles the band crosses (a bit-identical row with the same set elsewhere in the view is a
+// positive).  No column accumulators, LDS column slots or column partials: neither instance needs scratch.  Workspace, combine, prep,
+// finalize and the products are the pooled form's; set_weights_kernel's SELF variant (W = ct (E u_i - w rn_i), v = rnc = 0, w := 0 at
+// the anchor's own key) serves Y and Z.  Two blocks' overlap weight sums add in float32: cols <= 2^23.
 #include <math.h>
 #include <type_traits>
 
@@ -137,7 +146,8 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // EPI_SUP (supervised contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the count and the float32
 // sum of the raw accumulators of the elements that match by label (the partner and the padding excluded)
 enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8,
-       EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11, EPI_EXP_SELF = 12, EPI_SUP_SELF = 13 };
+       EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11, EPI_EXP_SELF = 12, EPI_SUP_SELF = 13,
+       EPI_SETS_OV_SELF = 14, EPI_SETS_JAC_SELF = 15 };
 // EPI_SETS_OV / EPI_SETS_JAC (multi-label contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the
 // float32 sums of w and of w * raw accumulator, w the overlap / Jaccard weight of the two class sets (partner and padding excluded)
 constexpr bool epi_is_sets(int epi) { return epi == EPI_SETS_OV || epi == EPI_SETS_JAC; }
@@ -147,7 +157,12 @@ constexpr bool epi_is_sets(int epi) { return epi == EPI_SETS_OV || epi == EPI_SE
 // EPI_SUP_SELF (pooled supervised contrastive loss, the a x a and b x b blocks): EPI_EXP_SELF's E loop, then the ROW half of EPI_SUP's
 // label search -- count and float32 raw-score sum of the matches by label per row, the anchor itself (column row_offset + i) left
 // out by index where EPI_SUP leaves the partner out; no column sums, counts or partials of any kind
-constexpr bool epi_is_self(int epi) { return epi == EPI_EXP_SELF || epi == EPI_SUP_SELF; }
+// EPI_SETS_OV_SELF / EPI_SETS_JAC_SELF (pooled multi-label contrastive loss, the a x a and b x b blocks): EPI_EXP_SELF's E loop, then
+// the ROW half of the dense sweep of EPI_SETS_* -- the float32 sums of w and of w * raw accumulator per row, the anchor itself
+// (column row_offset + i) with weight 0 by index where EPI_SETS_* leave the partner out; no column sums or partials of any kind
+constexpr bool epi_is_sets_self(int epi) { return epi == EPI_SETS_OV_SELF || epi == EPI_SETS_JAC_SELF; }
+constexpr bool epi_has_sets(int epi) { return epi_is_sets(epi) || epi_is_sets_self(epi); }    // the class words are staged in LDS
+constexpr bool epi_is_self(int epi) { return epi == EPI_EXP_SELF || epi == EPI_SUP_SELF || epi_is_sets_self(epi); }
 constexpr bool epi_has_labels(int epi) { return epi == EPI_SUP || epi == EPI_SUP_SELF; }
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
@@ -832,20 +847,20 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
             // EPI_SETS_*: thread t < 256 reads the word of the block's row t, thread 256 + t that of its column t (the padding: the
             // empty set); they go to LDS behind the barrier
             unsigned long long my_set = 0ull;
-            if (epi_is_sets(EPI)) {
+            if (epi_has_sets(EPI)) {
                 const int t = threadIdx.x & (BT - 1);
                 const bool is_row = threadIdx.x < BT;
                 const int k = BT * (is_row ? mi : ni) + t;
                 const unsigned long long* src = reinterpret_cast<const unsigned long long*>(is_row ? p.lab_row : p.lab_col);
                 if (k < (is_row ? p.m_valid : p.n_valid)) my_set = src[k];
             }
-            if (EPI == EPI_EXP_DT || epi_has_labels(EPI) || epi_is_sets(EPI) || EPI == EPI_EXP_SELF) {
+            if (EPI == EPI_EXP_DT || epi_has_labels(EPI) || epi_has_sets(EPI) || EPI == EPI_EXP_SELF) {
                 scale2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f;
                 shift2 = scale2;
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
-            if (epi_is_sets(EPI))                               // [256] row words | [256] column words, behind the 18 float planes
+            if (epi_has_sets(EPI))                              // [256] row words | [256] column words, behind the 18 float planes
                 reinterpret_cast<unsigned long long*>(smem + 18 * BT * 4)[threadIdx.x] = my_set;
             // E = exp2(acc scale - shift): 4 consecutive columns per lane, 8-byte stores (16 rows x 32 B per wave-instruction).
             // The sums run as packed float32 adds (both halves from their own registers); masking only on edge tiles.
@@ -1047,12 +1062,66 @@ __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
                 if (special) set_stats(std::integral_constant<bool, true>{});
                 else set_stats(std::integral_constant<bool, false>{});
             }
+            if (epi_is_sets_self(EPI)) {
+                // the ROW half of the sweep above, chain for chain (ct-major over the lane's 16 elements of a row, then the lane
+                // groups): 16 row accumulators and the 4 column words of the group, no column accumulators and no LDS column slots
+                constexpr bool JAC = EPI == EPI_SETS_JAC_SELF;
+                typedef unsigned long long u64;
+                __syncthreads();                                // the staged words are in place
+                const u64* lsr = reinterpret_cast<const u64*>(smem + 18 * BT * 4) + 128 * wm + r16;            // + 16 rt
+                const u64* lsc = reinterpret_cast<const u64*>(smem + 18 * BT * 4) + BT + 64 * wn + 4 * lg;     // + 16 ct + r
+                // block-uniform: only the tiles the band of anchors crosses pay for the index test (the padding weighs 0 by its sets)
+                const int64_t p0 = p.row_offset + (int64_t)BT * mi;
+                const bool special = p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni;
+                // the anchor of the lane's row of group rt is its element 16 ct + r where rel == 16 (ct - rt) + r: weight 0 by INDEX,
+                // never by its set or its value (a bit-identical row with the same set elsewhere in the view is a positive)
+                const int64_t rel64 = p.row_offset + gi0 - gj0;
+                const int rel = (rel64 > -512 && rel64 < 512) ? (int)rel64 : -4096;
+                auto set_row_stats = [&](auto special_c) {
+                    constexpr bool SP = decltype(special_c)::value;
+                    float rw[8], rx[8];
+#pragma unroll
+                    for (int rt = 0; rt < 8; ++rt) rw[rt] = rx[rt] = 0.f;
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+                        u64 B[4];
+                        int pb[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            B[r] = lsc[16 * ct + r];
+                            pb[r] = JAC ? __popcll(B[r]) : 0;
+                        }
+#pragma unroll
+                        for (int rt = 0; rt < 8; ++rt) {
+                            const u64 A = lsr[16 * rt];
+                            const int pa = JAC ? __popcll(A) : 0;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                float wt = set_weight<JAC>(A, B[r], pa, pb[r]);
+                                if (SP) wt = rel == 16 * (ct - rt) + r ? 0.f : wt;
+                                rw[rt] += wt;
+                                rx[rt] = fmaf(wt, acc[rt][ct][r], rx[rt]);
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int rt = 0; rt < 8; ++rt) {
+                        const float r1 = reduce_lg(rw[rt]), r2 = reduce_lg(rx[rt]);         // over the wave's 64 columns
+                        if (lg == 0) {
+                            lrn[wn * BT + 128 * wm + 16 * rt + r16] = r1;
+                            lrx[wn * BT + 128 * wm + 16 * rt + r16] = r2;
+                        }
+                    }
+                };
+                if (special) set_row_stats(std::integral_constant<bool, true>{});
+                else set_row_stats(std::integral_constant<bool, false>{});
+            }
             __syncthreads();
             const int tdx = threadIdx.x;
             if (tdx < BT) {
                 const int64_t o = ((int64_t)ni * p.m_tiles + mi) * BT + tdx;
                 p.rowsum_part[o] = (lrs[tdx] + lrs[BT + tdx]) + (lrs[2 * BT + tdx] + lrs[3 * BT + tdx]);
-                if (epi_has_labels(EPI) || epi_is_sets(EPI)) {
+                if (epi_has_labels(EPI) || epi_has_sets(EPI)) {
                     p.rowcnt_part[o] = (lrn[tdx] + lrn[BT + tdx]) + (lrn[2 * BT + tdx] + lrn[3 * BT + tdx]);
                     p.rowsx_part[o] = (lrx[tdx] + lrx[BT + tdx]) + (lrx[2 * BT + tdx] + lrx[3 * BT + tdx]);
                 }
@@ -1336,7 +1405,10 @@ __global__ __launch_bounds__(256) void sup_weights_kernel(unsigned short* e, int
 // the words (1 row word and 8 column words per 16-byte chunk; the column words stay in L2), the product w (rn + rnc) fused into
 // the subtraction (one rounding).  The partner's weight is ediag_i (u_i + v_p) - (rn_i + rnc_p), w = 1 by index: with no set
 // weight anywhere in its row and column the subtrahend is exactly 2; an element with w = 0 takes InfoNCE's expression.
-template <bool JAC>
+// SELF (blocks Y and Z of the pooled multi-label loss): the element at column row_offset + i is the anchor itself -- w := 0 by index
+// and E is stored as 0 there, so its weight is exactly ct * 0 (ediag is not read); the callers pass a vector of zeros for v and
+// rnc, so that W = ct (E u_i - w_ij rn_i) and a chunk without a weight has the bits of nce_weights_dt_kernel at v = 0.
+template <bool JAC, bool SELF>
 __global__ __launch_bounds__(256) void set_weights_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
                                                           const float* v, const float* rn, const float* rnc, const float* ediag,
                                                           const unsigned long long* set_row, const unsigned long long* set_col,
@@ -1363,7 +1435,7 @@ __global__ __launch_bounds__(256) void set_weights_kernel(unsigned short* e, int
     for (int k = 0; k < 8; ++k) {
         const int64_t j = j0 + k;
         const unsigned long long B = j < cols ? set_col[j] : 0ull;
-        wt[k] = jp == k ? 1.f : set_weight<JAC>(A, B, pa, JAC ? __popcll(B) : 0);
+        wt[k] = jp == k ? (SELF ? 0.f : 1.f) : set_weight<JAC>(A, B, pa, JAC ? __popcll(B) : 0);
         any = any || wt[k] != 0.f;
     }
     float x[8];
@@ -1379,7 +1451,7 @@ __global__ __launch_bounds__(256) void set_weights_kernel(unsigned short* e, int
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         float wv = x[k] * (ui + vv[k]);
-        if (jp == k) wv = fmaf(ediag[i], ui + vv[k], -(rni + rc[k]));
+        if (jp == k) wv = SELF ? 0.f : fmaf(ediag[i], ui + vv[k], -(rni + rc[k]));
         else if (wt[k] != 0.f) wv = fmaf(-wt[k], rni + rc[k], wv);
         x[k] = ct * wv;
     }
@@ -1808,11 +1880,11 @@ void launch_supcon_ml_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset,
     const unsigned long long* sr = (const unsigned long long*)row_sets;
     const unsigned long long* sc = (const unsigned long long*)col_sets;
     if (jaccard)
-        set_weights_kernel<true><<<grid, dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, sr, sc, rows, cols,
-                                                            row_offset, coef, upstream, dt.t, dt.min_t);
+        set_weights_kernel<true, false><<<grid, dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, sr, sc, rows,
+                                                                   cols, row_offset, coef, upstream, dt.t, dt.min_t);
     else
-        set_weights_kernel<false><<<grid, dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, sr, sc, rows, cols,
-                                                             row_offset, coef, upstream, dt.t, dt.min_t);
+        set_weights_kernel<false, false><<<grid, dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, sr, sc, rows,
+                                                                    cols, row_offset, coef, upstream, dt.t, dt.min_t);
     // the tdot partials go into the first plane of the row partials (dead since the sums launch), as in launch_nce_gemm_grads
     launch_grad_products<EPI_OUT, EPI_OUT_TD>(rows, cols, d, NceGemmArgs{}, w.e, w.slabs, w.row_part, &dt, a, b, out_bf16, da, db, s);
 }
@@ -2112,6 +2184,35 @@ void launch_supcon_pool_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset
     sup_finalize_kernel<<<dim3((unsigned)((f.Rp + 3) / 4)), dim3(256), 0, s>>>(f);
 }
 
+namespace {
+
+// the six products, two slab sums and the dT reduction over the three weighted blocks
+//   d_a_loc = W_X b_all + W_Y a_all (one slab sum over both products' slabs)      d_b_loc = W_Z b_all
+//   d_a_all = W_Y^T a_loc                                                         d_b_all = W_X^T a_loc + W_Z^T b_loc (float32 stage)
+void sup_pool_products(const SupPoolWs& w, int64_t rows, int64_t cols, int d, const NceDevTemp& dt, const void* a_loc, const void* b_loc,
+                       const void* a_all, const void* b_all, int out_bf16, void* d_a_loc, void* d_b_loc, void* d_a_all, void* d_b_all,
+                       hipStream_t s) {
+    const bool want_td = dt.d_t != nullptr;
+    const int64_t n_td = da_tdot_count(rows, cols, d), n_loc = rows * (int64_t)d, n_all = cols * (int64_t)d;
+    const NceGemmArgs g0 = {};
+    // both products always leave float32 slabs, those of W_Y a_all behind those of W_X b_all: one sum, one rounding
+    const int sx = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[0], w.slabs, w.tdot_part, want_td, a_loc, b_all, 0,
+                                                          nullptr, s);
+    const int sy = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[1], w.slabs + sx * n_loc, w.tdot_part + n_td, want_td,
+                                                          a_loc, a_all, 0, nullptr, s);
+    launch_slab_sum(w.slabs, sx + sy, n_loc, d_a_loc, out_bf16, s);
+    const int sz = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[2], w.slabs, w.tdot_part + 2 * n_td, want_td, b_loc,
+                                                          b_all, out_bf16, d_b_loc, s);
+    if (sz) launch_slab_sum(w.slabs, sz, n_loc, d_b_loc, out_bf16, s);
+    if (want_td) launch_nce_dtemp(w.tdot_part, 3 * n_td, 1, dt, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[1], a_loc, out_bf16, d_a_all, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[0], a_loc, 0, w.stage, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[2], b_loc, 0, w.stage + n_all, s);
+    launch_slab_sum(w.stage, 2, n_all, d_b_all, out_bf16, s);
+}
+
+}  // namespace
+
 // gradients: the three weights passes in place, then the six products in the arrangement of launch_ntxent_gemm_grads
 //   d_a_loc = W_X b_all + W_Y a_all (one slab sum over both products' slabs)      d_b_loc = W_Z b_all
 //   d_a_all = W_Y^T a_loc                                                         d_b_all = W_X^T a_loc + W_Z^T b_loc (float32 stage)
@@ -2133,23 +2234,90 @@ void launch_supcon_pool_gemm_grads(int64_t rows, int64_t cols, int64_t row_offse
                                                          row_offset, coef, upstream, dt.t, dt.min_t);
     sup_weights_kernel<true><<<wgrid, dim3(256), 0, s>>>(w.e[2], Cp / 64, Rp / BT, w.uz, w.zero, w.rnz, w.zero, nullptr, lr, lc, rows, cols,
                                                          row_offset, coef, upstream, dt.t, dt.min_t);
-    const bool want_td = dt.d_t != nullptr;
-    const int64_t n_td = da_tdot_count(rows, cols, d), n_loc = rows * (int64_t)d, n_all = cols * (int64_t)d;
-    const NceGemmArgs g0 = {};
-    // both products always leave float32 slabs, those of W_Y a_all behind those of W_X b_all: one sum, one rounding
-    const int sx = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[0], w.slabs, w.tdot_part, want_td, a_loc, b_all, 0,
-                                                          nullptr, s);
-    const int sy = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[1], w.slabs + sx * n_loc, w.tdot_part + n_td, want_td,
-                                                          a_loc, a_all, 0, nullptr, s);
-    launch_slab_sum(w.slabs, sx + sy, n_loc, d_a_loc, out_bf16, s);
-    const int sz = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[2], w.slabs, w.tdot_part + 2 * n_td, want_td, b_loc,
-                                                          b_all, out_bf16, d_b_loc, s);
-    if (sz) launch_slab_sum(w.slabs, sz, n_loc, d_b_loc, out_bf16, s);
-    if (want_td) launch_nce_dtemp(w.tdot_part, 3 * n_td, 1, dt, s);
-    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[1], a_loc, out_bf16, d_a_all, s);
-    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[0], a_loc, 0, w.stage, s);
-    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[2], b_loc, 0, w.stage + n_all, s);
-    launch_slab_sum(w.stage, 2, n_all, d_b_all, out_bf16, s);
+    sup_pool_products(w, rows, cols, d, dt, a_loc, b_loc, a_all, b_all, out_bf16, d_a_loc, d_b_loc, d_a_all, d_b_all, s);
+}
+
+// ---- pooled multi-label contrastive loss: the pooled form above with class sets and a weighting in place of the labels
+// (include/aecf_hip.h).  X runs EPI_SETS_OV / EPI_SETS_JAC unchanged, Y and Z their row-only SELF forms (the anchor's own key weighs
+// 0 by index); workspace (SupPoolWs, the weight sums where the counts stand), combine, prep, the loss pass and the six products are
+// those of the pooled single-label form, the weights passes set_weights_kernel's (Y and Z its SELF variant, v = rnc = 0).
+
+// An anchor's weight sum adds two blocks' (each at most cols - 1): the overlap sums are integers and stay exact in float32 up to
+// cols = 2^23; Jaccard keeps the same bound.
+bool supcon_ml_pool_gemm_supported(int d, float min_temperature, int64_t cols) {
+    return supcon_pool_gemm_supported(d, min_temperature, cols);
+}
+
+size_t supcon_ml_pool_gemm_workspace_bytes(int64_t rows, int64_t cols, int d) { return supcon_pool_gemm_workspace_bytes(rows, cols, d); }
+
+void launch_supcon_ml_pool_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                      const void* b_loc, const void* a_all, const void* b_all, const int64_t* row_sets,
+                                      const int64_t* col_sets, int jaccard, void* workspace, float* col_stats, hipStream_t s) {
+    const SupPoolWs w = sup_pool_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    for (int k = 0; k < 3; ++k) {
+        LogitsLaunch L = logits_args(rows, cols, d, k == 2 ? b_loc : a_loc, k == 1 ? a_all : b_all);
+        NceGemmArgs& g = L.g;
+        g.e = w.e[k]; g.e_tiles = Cp / 64;
+        g.temp = dt.t; g.min_temp = dt.min_t; g.row_offset = row_offset;
+        g.lab_row = (const long long*)row_sets; g.lab_col = (const long long*)col_sets;
+        const int64_t rplane = (int64_t)g.n_tiles * Rp, cplane = (int64_t)g.m_tiles * Cp;
+        g.rowsum_part = w.row_part; g.rowcnt_part = w.row_part + rplane; g.rowsx_part = w.row_part + 2 * rplane;
+        if (k == 0) {
+            g.colsum_part = w.col_part; g.colcnt_part = w.col_part + cplane; g.colsx_part = w.col_part + 2 * cplane;
+            if (jaccard) launch_gemm<OP_ROW, OP_ROW, EPI_SETS_JAC, MAP_2D>(g, L.blocks, s);
+            else launch_gemm<OP_ROW, OP_ROW, EPI_SETS_OV, MAP_2D>(g, L.blocks, s);
+            sup_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64), 3), dim3(256), 0, s>>>(w.row_part, w.col_part, g.m_tiles, g.n_tiles, rows,
+                                                                                      cols, w.row_stats, col_stats);
+        } else {
+            if (jaccard) launch_gemm<OP_ROW, OP_ROW, EPI_SETS_JAC_SELF, MAP_2D>(g, L.blocks, s);
+            else launch_gemm<OP_ROW, OP_ROW, EPI_SETS_OV_SELF, MAP_2D>(g, L.blocks, s);
+            // the row blocks of the sums launch alone: this block leaves no column partials
+            sup_sums_kernel<<<dim3((unsigned)(Rp / 64), 3), dim3(256), 0, s>>>(w.row_part, nullptr, g.m_tiles, g.n_tiles, rows, cols,
+                                                                               k == 1 ? w.y_stats : w.z_stats, nullptr);
+        }
+    }
+    sup_pool_combine_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s>>>(w.row_stats, w.y_stats, w.z_stats, col_stats, rows,
+                                                                                       cols, row_offset, Rp);
+}
+
+// sup_finalize_kernel on the combined statistics, the weight sums where the counts stood
+void launch_supcon_ml_pool_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                     const void* b_all, const float* col_stats, void* workspace, float* loss_rows, hipStream_t s) {
+    launch_supcon_pool_gemm_loss(rows, cols, row_offset, d, dt, a_loc, b_all, col_stats, workspace, loss_rows, s);
+}
+
+namespace {
+
+template <bool JAC>
+void set_pool_weights(const SupPoolWs& w, int64_t rows, int64_t cols, int64_t row_offset, float coef, const int64_t* row_sets,
+                      const int64_t* col_sets, const float* upstream, const NceDevTemp& dt, hipStream_t s) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t chunks = Rp * (Cp / 8);
+    const dim3 wgrid((unsigned)((chunks + 255) / 256));
+    const unsigned long long* sr = (const unsigned long long*)row_sets;
+    const unsigned long long* sc = (const unsigned long long*)col_sets;
+    set_weights_kernel<JAC, false><<<wgrid, dim3(256), 0, s>>>(w.e[0], Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, sr, sc, rows, cols,
+                                                               row_offset, coef, upstream, dt.t, dt.min_t);
+    set_weights_kernel<JAC, true><<<wgrid, dim3(256), 0, s>>>(w.e[1], Cp / 64, Rp / BT, w.u, w.zero, w.rn, w.zero, nullptr, sr, sc, rows, cols,
+                                                              row_offset, coef, upstream, dt.t, dt.min_t);
+    set_weights_kernel<JAC, true><<<wgrid, dim3(256), 0, s>>>(w.e[2], Cp / 64, Rp / BT, w.uz, w.zero, w.rnz, w.zero, nullptr, sr, sc, rows,
+                                                              cols, row_offset, coef, upstream, dt.t, dt.min_t);
+}
+
+}  // namespace
+
+// gradients: sup_pool_prep_kernel, the three set weights passes in place, then the products of launch_supcon_pool_gemm_grads
+void launch_supcon_ml_pool_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef,
+                                      const void* a_loc, const void* b_loc, const void* a_all, const void* b_all, const int64_t* row_sets,
+                                      const int64_t* col_sets, int jaccard, void* workspace, const float* upstream, int out_bf16,
+                                      void* d_a_loc, void* d_b_loc, void* d_a_all, void* d_b_all, hipStream_t s) {
+    const SupPoolWs w = sup_pool_carve(workspace, rows, cols, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    sup_pool_prep_kernel<<<dim3((unsigned)(Cp / 256)), dim3(256), 0, s>>>(w.v, w.rnc, w.uz, w.rnz, w.zero, rows, row_offset, Rp, Cp);
+    if (jaccard) set_pool_weights<true>(w, rows, cols, row_offset, coef, row_sets, col_sets, upstream, dt, s);
+    else set_pool_weights<false>(w, rows, cols, row_offset, coef, row_sets, col_sets, upstream, dt, s);
+    sup_pool_products(w, rows, cols, d, dt, a_loc, b_loc, a_all, b_all, out_bf16, d_a_loc, d_b_loc, d_a_all, d_b_all, s);
 }
 
 // ---- sigmoid (SigLIP) loss on the same GEMMs ---------------------------------------------------------------------------

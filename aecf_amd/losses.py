@@ -1445,6 +1445,147 @@ def multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets: torch
     return scaled + (total - scaled.detach())
 
 
+class _SupConMlPoolSymmetric(torch.autograd.Function):
+    """aecf_supcon_ml_pool_sym_pass1 / _loss / _grads: the 2 b_local anchors of this rank's pooled multi-label contrastive loss
+    from three blocks of logits (a_loc x b_all, a_loc x a_all, b_loc x b_all; the anchor itself left out of the last two by index),
+    the class sets (int64 masks) shared by the two views.  ``_SupConPoolSymmetric`` with sets and a weighting for the labels: the
+    [3, cols] column statistics -- those of the a x b block, plus the b x b row statistics on this rank's own range -- are the one
+    thing ranks exchange, one all-reduce between pass 1 and the loss; the gradients on the gathered rows are this rank's shares.
+    The backward runs the three weights passes and the six gradient products once, scaled on the device by the gradient that
+    arrives and written in the inputs' dtype.  The temperature is a one-element float32 device tensor; the backward returns this
+    rank's share of dL/dT."""
+
+    @staticmethod
+    def forward(ctx, a, b, a_all, b_all, row_sets, col_sets, weighting, row_offset, temperature, coef, group, min_temperature):
+        lib = _lib.load()
+        rows, d = a.shape
+        cols = b_all.shape[0]
+        dev = a.device
+        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b.detach().to(torch.bfloat16).contiguous()
+        aa, ba = a_all.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
+        sr, sc = row_sets.contiguous(), col_sets.contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws_bytes = lib.aecf_supcon_ml_pool_sym_workspace_bytes(rows, cols, d)
+        if ws_bytes == 0:
+            raise NotImplementedError(f"aecf_amd: the pooled multi-label contrastive loss needs d % 64 == 0, 64 <= d <= 4096 and at "
+                                      f"most 2^23 gathered rows; got d = {d}, {cols} rows")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        col_stats = torch.empty(3, cols, **f32)
+        t = temperature.detach()
+        tp, t_min, w = _ptr(t), float(min_temperature), int(weighting)
+        _lib.check(lib.aecf_supcon_ml_pool_sym_pass1(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(aa), _ptr(ba),
+                                                     _ptr(sr), _ptr(sc), w, _ptr(ws), ws_bytes, _ptr(col_stats), _stream()),
+                   "aecf_supcon_ml_pool_sym_pass1")
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(col_stats, group=group)
+        loss_rows = torch.empty(rows, **f32)
+        _lib.check(lib.aecf_supcon_ml_pool_sym_loss(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(ba), _ptr(col_stats),
+                                                    _ptr(ws), ws_bytes, _ptr(loss_rows), _stream()), "aecf_supcon_ml_pool_sym_loss")
+        ctx.save_for_backward(ac, bc, aa, ba, sr, sc, ws, t)
+        ctx.meta = ((a.dtype, b.dtype, a_all.dtype, b_all.dtype), temperature.shape,
+                    (rows, cols, int(row_offset), d, float(coef), t_min, ws_bytes, w))
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = _lib.load()
+        ac, bc, aa, ba, sr, sc, ws, t = ctx.saved_tensors
+        dts, t_shape, (rows, cols, row_offset, d, coef, t_min, ws_bytes, w) = ctx.meta
+        if getattr(ctx, "_spent", False):
+            raise RuntimeError("aecf_amd: the pooled multi-label contrastive backward runs once per forward (it consumes the stored "
+                               "logits)")
+        ctx._spent = True
+        gdt = torch.bfloat16 if all(x == torch.bfloat16 for x in dts) else torch.float32
+        dev = ac.device
+        d_a, d_b = torch.empty(rows, d, dtype=gdt, device=dev), torch.empty(rows, d, dtype=gdt, device=dev)
+        d_aa, d_ba = torch.empty(cols, d, dtype=gdt, device=dev), torch.empty(cols, d, dtype=gdt, device=dev)
+        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
+        d_t = torch.empty(1, dtype=torch.float32, device=dev) if ctx.needs_input_grad[8] else None
+        _lib.check(lib.aecf_supcon_ml_pool_sym_grads(rows, cols, row_offset, d, _ptr(t), t_min, coef, _ptr(ac), _ptr(bc), _ptr(aa),
+                                                     _ptr(ba), _ptr(sr), _ptr(sc), w, _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt],
+                                                     _ptr(d_a), _ptr(d_b), _ptr(d_aa), _ptr(d_ba), _ptr(d_t), _stream()),
+                   "aecf_supcon_ml_pool_sym_grads")
+        g_t = d_t.reshape(t_shape) if d_t is not None else None
+        return d_a.to(dts[0]), d_b.to(dts[1]), d_aa.to(dts[2]), d_ba.to(dts[3]), None, None, None, None, g_t, None, None, None
+
+
+def pooled_multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets: torch.Tensor, weighting: str = "overlap",
+                                  temperature: Union[float, torch.Tensor] = 0.07, group=None,
+                                  min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
+    """The supervised contrastive loss as published (Khosla et al. 2020) with a SET of classes per row, between the local rows of
+    two views, keys from every rank of ``group``: the 2 B_all rows of both views are one pool, every row is an anchor against the
+    other 2 B_all - 1 rows (itself left out by index), and a key of EITHER view counts as its positive with a weight
+
+        w = 1 for the partner (the same row of the other view, by index, whatever the sets say), else
+            [A and B share a class]          weighting="overlap"
+            |A & B| / |A | B|                weighting="jaccard"
+
+        L = 0.5 / B_all * sum over the 2 B_all anchors of [ logsumexp_{k != self} x_k - sum_k w_k x_k / sum_k w_k ],
+        x = n . n_k / max(T, min_temperature)
+
+    ``label_sets``: as for ``multilabel_contrastive`` (a multi-hot tensor [b_local, C <= 64] or ready int64 masks [b_local], shared
+    by both views); an empty set marks an unlabeled row: its only positive is its partner and it is nobody's positive by label.
+    With all sets empty or pairwise disjoint it has the bits of ``nt_xent(low_memory=False)``; with one-hot sets both weightings
+    are ``pooled_supervised_contrastive``.  Sets carry no gradient.
+
+    There is one implementation, the tile-GEMM form (aecf_supcon_ml_pool_sym_pass1 / _loss / _grads): the three blocks of logits
+    of ``nt_xent``'s tile form (a_loc x b_all, a_loc x a_all, b_loc x b_all) kept as bfloat16 exponentials between forward and
+    backward, the set weights formed in a dense epilogue of each logits GEMM and again in the weights passes, their statistics
+    combined over the three blocks.  It needs bfloat16 rows, d % 64 == 0 (64 to 4096), ``min_temperature >= 0.025``, at most 2^23
+    gathered rows and its workspace (those three blocks plus float32 staging) within 0.6 of the free device memory (not tested
+    while capturing), and raises NotImplementedError naming the limit otherwise: there is no streaming form and no torch fallback.
+    Its backward runs once per forward.  ``temperature``: a float or a learnable one-element float32 device tensor, no host read:
+    on one rank the call captures into a graph and replays the current temperature and sets.
+
+    Data parallel: both views, the packed sets and the row counts are gathered, the ranks agree on refusal (a MIN all-reduce) and
+    all-reduce the [3, b_all] column statistics between the passes; the returned value follows ``info_nce``'s convention -- the
+    global loss on every rank, the local term carrying ``world`` for an averaging gradient reduce."""
+    if weighting not in SET_WEIGHTINGS:
+        raise ValueError(f"aecf_amd: weighting must be 'overlap' or 'jaccard', got {weighting!r}")
+    _require_device(za, "za")
+    _require_device(zb, "zb")
+    if za.shape != zb.shape or za.dim() != 2:
+        raise ValueError(f"pooled_multilabel_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and "
+                         f"{tuple(zb.shape)}")
+    label_sets = _label_sets_arg(label_sets, za)
+    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
+        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
+    rank, world = dp.world_info(group)
+    if world > 1:
+        n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
+        got = [torch.zeros_like(n) for _ in range(world)]
+        torch.distributed.all_gather(got, n, group=group)
+        sizes = [int(v.item()) for v in got]
+        offset, b_all = sum(sizes[:rank]), sum(sizes)
+    else:
+        sizes, offset, b_all = None, 0, za.shape[0]
+    # (the two pooled tile forms share their served shapes and their workspace)
+    refusal = _supcon_pool_tile_refusal(za, zb, b_all, min_temperature)
+    if world > 1:                                   # every rank must agree (a rank that refused would leave the others waiting)
+        flag = torch.tensor([1 if refusal is None else 0], device=za.device)
+        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
+        if refusal is None and not bool(int(flag.item())):
+            refusal = "the same on every rank (another rank refused it)"
+    if refusal is not None:
+        raise NotImplementedError("aecf_amd: the pooled multi-label contrastive loss (a tile form only) needs " + refusal)
+    t = _temperature_arg(temperature, za, min_temperature)
+    if not isinstance(t, torch.Tensor):
+        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    sets = label_sets.detach() if label_sets.dim() == 1 else pack_label_sets(label_sets)
+    na, nb = l2_normalize(za), l2_normalize(zb)
+    na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
+    nb_all = dp.all_gather_rows(nb, group, sizes=sizes) if world > 1 else nb
+    sets_all = dp.all_gather_rows(sets, group, sizes=sizes) if world > 1 else sets
+    share = _SupConMlPoolSymmetric.apply(na, nb, na_all, nb_all, sets, sets_all, SET_WEIGHTINGS[weighting], offset, t,
+                                         0.5 / float(b_all), group, float(min_temperature))
+    if world == 1:
+        return share
+    total = share.detach().clone()
+    torch.distributed.all_reduce(total, group=group)
+    scaled = share * world
+    return scaled + (total - scaled.detach())
+
+
 class RetrievalRanks(NamedTuple):
     """What ``retrieval_ranks`` returns: for each of this rank's rows, how many OTHER rows of the other view score higher than
     (``greater``) or exactly as high as (``equal``) its partner; int32 [b_local] each."""
@@ -1623,22 +1764,27 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
     implementation, ignored for ``info_nce``); ``contrastive="supervised"`` takes ``supervised_contrastive(za, zb, labels,
     temperature)`` -- handed ``low_memory`` when it is not None (False: the tile-GEMM form), its own default (the streaming form)
     otherwise -- and ``contrastive="multilabel"`` takes ``multilabel_contrastive(za, zb, labels, label_weighting,
-    temperature)``, handed ``low_memory`` in the same way, with ``labels`` the label sets (multi-hot rows or int64 masks); these two and ``supervised_pool`` are the only forms that take
-    ``labels``, and ``label_weighting`` ("overlap" or "jaccard") is read by the multi-label form alone.  ``contrastive="nt_xent"``
+    temperature)``, handed ``low_memory`` in the same way, with ``labels`` the label sets (multi-hot rows or int64 masks); these two, ``supervised_pool`` and ``multilabel_pool`` are the only forms that take
+    ``labels``, and ``label_weighting`` ("overlap" or "jaccard") is read by the multi-label forms alone.  ``contrastive="nt_xent"``
     takes ``nt_xent(za, zb, temperature)``, the pool of both views without labels, handed ``low_memory`` when it is not None
     (False: its tile-GEMM form) and its own default (the streaming form) otherwise; ``intra_view`` is handed to the supervised
     form (True: the same pool with label positives from either view) and read by no other.
     ``contrastive="supervised_pool"`` takes ``pooled_supervised_contrastive(za, zb, labels, temperature)``, that pooled loss
     under a name of its own, handed ``low_memory`` when it is not None (False: its tile-GEMM form) and its own default (the
-    streaming form) otherwise; it takes ``labels`` and ignores ``intra_view``."""
-    if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel", "nt_xent", "supervised_pool"):
-        raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid', 'supervised', 'multilabel', 'nt_xent' or "
-                         f"'supervised_pool', got {contrastive!r}")
-    if contrastive in ("supervised", "multilabel", "supervised_pool") and labels is None:
+    streaming form) otherwise; it takes ``labels`` and ignores ``intra_view``.
+    ``contrastive="multilabel_pool"`` takes ``pooled_multilabel_contrastive(za, zb, labels, label_weighting, temperature)``, the
+    same pool with label sets: it takes ``labels`` (the sets) and ``label_weighting`` and ignores ``intra_view``; ``low_memory``
+    None or False select its one implementation, the tile-GEMM form, and True raises NotImplementedError (there is no streaming
+    form)."""
+    with_labels = ("supervised", "multilabel", "supervised_pool", "multilabel_pool")
+    if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel", "nt_xent", "supervised_pool", "multilabel_pool"):
+        raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid', 'supervised', 'multilabel', 'nt_xent', "
+                         f"'supervised_pool' or 'multilabel_pool', got {contrastive!r}")
+    if contrastive in with_labels and labels is None:
         raise ValueError(f"aecf_amd: contrastive={contrastive!r} needs labels")
-    if contrastive not in ("supervised", "multilabel", "supervised_pool") and labels is not None:
-        raise ValueError(f"aecf_amd: labels are taken by contrastive='supervised', 'multilabel' and 'supervised_pool' only, got "
-                         f"contrastive={contrastive!r}")
+    if contrastive not in with_labels and labels is not None:
+        raise ValueError(f"aecf_amd: labels are taken by contrastive='supervised', 'multilabel', 'supervised_pool' and "
+                         f"'multilabel_pool' only, got contrastive={contrastive!r}")
     if label_weighting not in SET_WEIGHTINGS:
         raise ValueError(f"aecf_amd: label_weighting must be 'overlap' or 'jaccard', got {label_weighting!r}")
     total = task_loss
@@ -1667,6 +1813,11 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
                 term = pooled_supervised_contrastive(za, zb, labels, temperature, group, min_temperature)
             else:
                 term = pooled_supervised_contrastive(za, zb, labels, temperature, group, min_temperature, low_memory)
+        elif contrastive == "multilabel_pool":
+            if low_memory is True:
+                raise NotImplementedError("aecf_amd: contrastive='multilabel_pool' has no streaming form (low_memory=True); "
+                                          "low_memory=None or False take its tile-GEMM form")
+            term = pooled_multilabel_contrastive(za, zb, labels, label_weighting, temperature, group, min_temperature)
         else:
             term = info_nce(za, zb, temperature, group, min_temperature)
         total = _plus(total, contrastive_weight * term)

@@ -957,6 +957,71 @@ int aecf_supcon_ml_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int
                              const uint64_t* col_sets, int32_t weighting, void* workspace, size_t workspace_bytes,
                              const float* upstream, int32_t grad_dtype, void* da, void* db, float* d_temperature, void* stream);
 
+/* ---- pooled multi-label contrastive loss, tile-GEMM form: aecf_supcon_pool_sym_* with a SET of classes per row ----
+ * The supervised contrastive loss of Khosla et al. over ONE pool of the 2 cols rows of both views, with class sets where
+ * aecf_supcon_pool_sym_* has one label: every row is an anchor, its keys are the other 2 cols - 1 rows (itself left out by INDEX),
+ * and a key of either view counts with the weight of aecf_supcon_ml_sym_*.  Buffers as in the pooled form (a_loc, b_loc [rows,d],
+ * a_all, b_all [cols,d], unit-norm bf16 rows; a_all / b_all may alias a_loc / b_loc on one rank).  row_sets [rows] and col_sets
+ * [cols] are DEVICE arrays of one 64-bit word per row, SHARED by the views, bit c = class c (aecf_label_sets_pack makes them; all
+ * 64 bits count, the sign bit is class 63); the empty set marks an unlabeled row: its only positive is its partner and it is
+ * nobody's positive by label.
+ *   w(A, B) = [A & B != 0]                          weighting AECF_SETS_OVERLAP
+ *           = popcount(A & B) / popcount(A | B)     weighting AECF_SETS_JACCARD: ONE correctly rounded float32 division, 0 for an
+ *                                                   empty union
+ * Tc = max(*temperature, min_temperature), E(s) = exp((s - 1) / Tc).  Three logits blocks, per row i of the rank, g = row_offset + i:
+ *   X = a_loc . b_all^T   the partner (column g) excluded from the sweep, weight 1 by index          lX, wX, sX   and columns cX, wcX, scX
+ *   Y = a_loc . a_all^T   the anchor itself (column g) excluded by INDEX: no key, weight 0, whatever its set and value   lY, wY, sY
+ *   Z = b_loc . b_all^T   the same                                                                                       lZ, wZ, sZ
+ * (l: sum of E, w: float32 sum of the weights, s: float32 sum of weight * raw score, each product fused into its addition.)
+ * Anchor a_i: Da = lX + lY, ka = wX + wY, sa = sX + sY, local.  Anchor b_g: Db_g = sum over ranks of cX_g + lZ_g, kb_g = sum wcX_g
+ * + wZ_g, sb_g = sum scX_g + sZ_g (Z of the rank that owns row g).  With dot_i = a_i . b_g, na = 1 + ka, nb = 1 + kb:
+ *   loss_rows[i] = [log Da_i + 1/Tc - (dot_i + sa_i) / na_i / Tc] + [log Db_g + 1/Tc - (dot_i + sb_g) / nb_g / Tc]      WITHOUT coef
+ *   W_X = ct (E_X (1/Da_i + 1/Db_j) - w_ij (1/na_i + 1/nb_j)), the partner with w = 1 by index and its float32 exponential
+ *   W_Y = ct (E_Y / Da_i - w_ij / na_i)       W_Z = ct (E_Z / Db_g - w_ij / nb_g)       both exactly 0 at the excluded key
+ *         ct = coef / Tc * upstream
+ *   d_a_loc = W_X b_all + W_Y a_all [rows,d]     d_b_loc = W_Z b_all [rows,d]
+ *   d_a_all = W_Y^T a_loc [cols,d]               d_b_all = W_X^T a_loc + W_Z^T b_loc [cols,d]        (this rank's shares)
+ *   dT = -(1/Tc) [ sum_i a_i . d_a_loc_i + sum_i b_i . d_b_loc_i ]   (0 where *temperature < min_temperature)
+ * The shares of the ranks sum to the global gradients.  With all sets empty or pairwise disjoint every output has the bits of
+ * aecf_ntxent_sym_pass1 / _loss / _grads on the same inputs (col_stats[0] those of col_sums); outside the rank's own range
+ * col_stats has the bits of aecf_supcon_ml_sym_pass1.
+ *   pass1: the three logits GEMMs.  X is aecf_supcon_ml_sym_pass1 to the bit; Y and Z run a row-only form of its dense epilogue
+ *          (the E loop of the NT-Xent blocks, then the row half of the set sweep in the same summation order, the anchor's own
+ *          element with weight 0 by index, no column statistics).  Then the combined row statistics (workspace) and col_stats
+ *          [3][cols] float32 = this rank's column statistics of X (c | sum of w | sum of w * raw score), plus Z's row statistics
+ *          on its own range [row_offset, row_offset + rows): one float32 addition per quantity and side, fixed order, no atomics.
+ *   caller: all-reduce (sum) of col_stats over the ranks (nothing to do on one rank): it then holds Db | kb | sb.
+ *   loss:  loss_rows [rows]; prepares 1/Da, 1/na (rows) and 1/Db, 1/nb (columns) in the workspace.
+ *   grads: the three weights passes in place over the blocks (w formed again from the words), then the six products as in
+ *          aecf_supcon_pool_sym_grads: two products on one output are summed in float32 and rounded ONCE to grad_dtype;
+ *          everything is multiplied by upstream[0] (a DEVICE float32 scalar, NULL = 1); d_temperature (may be NULL) is WRITTEN
+ *          with this rank's share of dL/dT times upstream[0].  It consumes the stored blocks: it runs once per pass1.
+ * Served: the shapes of aecf_supcon_pool_sym_*: bf16 rows, d % 64 == 0, 64 <= d <= 4096, min_temperature >= 0.025, rows <= cols,
+ * cols <= 2^23: an anchor's overlap weight sum adds two blocks' (each at most cols - 1) and stays an exact float32 integer up to
+ * there; Jaccard keeps the same bound.  18 rows cols d MFMA flops.
+ * Workspace: the layout and size of aecf_supcon_pool_sym_workspace_bytes, the weight sums in the count slots.  The query answers 0
+ * where the shape is not served (d, rows > cols, cols > 2^23).
+ * Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host (the calls capture into a
+ * graph), nothing read from the workspace before it is written; no float atomics: the same inputs give the same bits.  Checks
+ * before any launch, in the order of the two families this one joins: sizes (rows, cols, d > 0, cols < 2^31, min_temperature > 0,
+ * 0 <= row_offset, row_offset + rows <= cols: AECF_ERR_BAD_DIMS), then d, min_temperature < 0.025, cols > 2^23, an unknown
+ * weighting or a grad_dtype other than bf16 / float32 (AECF_ERR_UNSUPPORTED), then NULL pointers (AECF_ERR_NULL_POINTER; upstream
+ * and d_temperature may be NULL), then the workspace size (AECF_ERR_WORKSPACE). */
+size_t aecf_supcon_ml_pool_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d);      /* 0: not served */
+int aecf_supcon_ml_pool_sym_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                                  float min_temperature, const void* a_loc, const void* b_loc, const void* a_all, const void* b_all,
+                                  const int64_t* row_sets, const int64_t* col_sets, int32_t weighting, void* workspace,
+                                  size_t workspace_bytes, float* col_stats /* [3][cols] */, void* stream);
+int aecf_supcon_ml_pool_sym_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                                 float min_temperature, const void* a_loc, const void* b_all,
+                                 const float* col_stats /* summed over ranks */, void* workspace, size_t workspace_bytes,
+                                 float* loss_rows, void* stream);
+int aecf_supcon_ml_pool_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                                  float min_temperature, float coef, const void* a_loc, const void* b_loc, const void* a_all,
+                                  const void* b_all, const int64_t* row_sets, const int64_t* col_sets, int32_t weighting,
+                                  void* workspace, size_t workspace_bytes, const float* upstream, int32_t grad_dtype, void* d_a_loc,
+                                  void* d_b_loc, void* d_a_all, void* d_b_all, float* d_temperature, void* stream);
+
 /* ---- retrieval ranks of the contrastive views (build-defined like the contrastive terms they evaluate: the reference has no
  * contrastive term and no retrieval evaluation, so there are no reference lines to cite) ----
  * Local rows a [rows,d] (global indices row_offset .. row_offset + rows) against all gathered rows b [cols,d] of the other view,
