@@ -223,6 +223,16 @@ _SYMBOLS = [
     ("aecf_ntxent_sym_grads", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
       c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # multi-view InfoNCE on the tile GEMMs: every pair of views of x [rows][views][d] in place, one all-reduce of [P][cols]
+    ("aecf_nce_multi_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32]),
+    ("aecf_nce_multi_pass1", c_int,
+     [c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("aecf_nce_multi_loss", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+      c_void_p, c_void_p]),
+    ("aecf_nce_multi_grads", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
+      c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     # pooled supervised contrastive loss on the tile GEMMs: NT-Xent's three blocks with labels, one all-reduce of [3][cols]
     ("aecf_supcon_pool_sym_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
     ("aecf_supcon_pool_sym_pass1", c_int,

@@ -1068,6 +1068,62 @@ int aecf_ntxent_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_
     return launch_status();
 }
 
+// ---- multi-view InfoNCE on the tile GEMMs (include/aecf_hip.h, "multi-view InfoNCE, tile-GEMM form")
+
+namespace {
+bool nce_multi_bad_dims(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor, float min_temperature) {
+    return rows <= 0 || cols <= 0 || d <= 0 || !(min_temperature > 0.f) || cols > 0x7fffffff || rows > cols || views < 2 || views > 8 ||
+           anchor < -1 || anchor >= views;
+}
+}  // namespace
+
+size_t aecf_nce_multi_workspace_bytes(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, 0.025f) || !nce_multi_supported(d, 0.025f, cols, views, anchor)) return 0;
+    return nce_multi_workspace_bytes(rows, cols, d, views, anchor);
+}
+
+int aecf_nce_multi_pass1(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor, const float* temperature,
+                         float min_temperature, const void* x_loc, const void* x_all, void* workspace, size_t workspace_bytes,
+                         float* col_sums, void* stream) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, min_temperature)) return AECF_ERR_BAD_DIMS;
+    if (!nce_multi_supported(d, min_temperature, cols, views, anchor)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !x_loc || !x_all || !workspace || !col_sums) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_multi_workspace_bytes(rows, cols, d, views, anchor)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_nce_multi_pass1(rows, cols, d, views, anchor, dt, x_loc, x_all, workspace, col_sums, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_nce_multi_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                        const float* temperature, float min_temperature, const void* x_loc, const void* x_all, const float* col_sums,
+                        void* workspace, size_t workspace_bytes, float* loss_rows, void* stream) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, min_temperature)) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!nce_multi_supported(d, min_temperature, cols, views, anchor)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !x_loc || !x_all || !col_sums || !workspace || !loss_rows) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_multi_workspace_bytes(rows, cols, d, views, anchor)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_nce_multi_loss(rows, cols, row_offset, d, views, anchor, dt, x_loc, x_all, col_sums, workspace, loss_rows,
+                          (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                         const float* temperature, float min_temperature, float coef, const void* x_loc, const void* x_all,
+                         void* workspace, size_t workspace_bytes, const float* upstream, int32_t grad_dtype, void* dx_loc, void* dx_all,
+                         float* d_temperature, void* stream) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, min_temperature)) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!nce_multi_supported(d, min_temperature, cols, views, anchor)) return AECF_ERR_UNSUPPORTED;
+    if (grad_dtype != AECF_BF16 && grad_dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !x_loc || !x_all || !workspace || !dx_loc || !dx_all) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_multi_workspace_bytes(rows, cols, d, views, anchor)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    launch_nce_multi_grads(rows, cols, row_offset, d, views, anchor, dt, coef, x_loc, x_all, workspace, upstream,
+                           grad_dtype == AECF_BF16 ? 1 : 0, dx_loc, dx_all, (hipStream_t)stream);
+    return launch_status();
+}
+
 // ---- pooled supervised contrastive loss on the tile GEMMs (include/aecf_hip.h, "pooled supervised contrastive loss, tile-GEMM form")
 
 size_t aecf_supcon_pool_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {

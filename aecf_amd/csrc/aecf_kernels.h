@@ -363,6 +363,20 @@ void launch_ntxent_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, in
                               const void* b_loc, const void* a_all, const void* b_all, void* workspace, const float* upstream,
                               int out_bf16, void* d_a_loc, void* d_b_loc, void* d_a_all, void* d_b_all, hipStream_t s);
 
+// Multi-view InfoNCE on the tile GEMMs (aecf_nce_gemm.hip): the symmetric InfoNCE of every pair of views (anchor < 0) or of every
+// pair with the anchor view, read in place from x_loc [rows][views][d] / x_all [cols][views][d]; one launch per stage for all
+// pairs, gradient products with K through every partner block of a view.  col_sums [P][cols] is what ranks exchange.
+bool nce_multi_supported(int d, float min_temperature, int64_t cols, int views, int anchor);
+size_t nce_multi_workspace_bytes(int64_t rows, int64_t cols, int d, int views, int anchor);
+void launch_nce_multi_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
+                            const void* x_all, void* workspace, float* col_sums, hipStream_t s);
+void launch_nce_multi_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                           const void* x_loc, const void* x_all, const float* col_sums, void* workspace, float* loss_rows,
+                           hipStream_t s);
+void launch_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                            float coef, const void* x_loc, const void* x_all, void* workspace, const float* upstream, int out_bf16,
+                            void* dx_loc, void* dx_all, hipStream_t s);
+
 // Pooled supervised contrastive loss on the tile GEMMs (aecf_nce_gemm.hip): NT-Xent's three blocks with the label statistics of the
 // supervised loss -- X runs EPI_SUP, Y and Z EPI_SUP_SELF (rows only, the anchor excluded by index).  col_stats [3][cols] (X's column
 // statistics, plus Z's row statistics on this rank's own range) is what ranks exchange.

@@ -125,6 +125,23 @@
 // positive).  No column accumulators, LDS column slots or column partials: neither instance needs scratch.  Workspace, combine, prep,
 // finalize and the products are the pooled form's; set_weights_kernel's SELF variant (W = ct (E u_i - w rn_i), v = rnc = 0, w := 0 at
 // the anchor's own key) serves Y and Z.  Two blocks' overlap weight sums add in float32: cols <= 2^23.
+//
+// Multi-view InfoNCE (aecf_nce_multi_pass1 / _loss / _grads) is the symmetric InfoNCE above over P pairs of the views that lie side
+// by side in x [rows][views][d] -- every pair m < n, or every pair with one anchor view -- with ONE launch per stage.  Operands are
+// read in place: lda = ldb = views d 2 bytes, a view's origin d 2 bytes behind the previous one.  The logits pass is
+// nce_multi_logits_kernel: block b is tile b % blocks_per_pair of pair b / blocks_per_pair (blocks_per_pair is a multiple of 8, so a
+// tile keeps its XCD and its MAP_2D patch), a pair table in the kernel arguments gives the two origins, and E, the partials, the
+// sums and the normalisers of pair p lie p strides behind pair 0's in the workspace; the epilogue is EPI_EXP_DT, so every pair has
+// the bits of a two-view call on contiguous copies.  Sums, finalize and weights kernels take the pair from blockIdx.y.  The
+// gradient products are nce_multi_product_kernel: block b works for slot b / blocks_per_view, a view that has the role, and its K
+// loop runs through the tiles of EVERY partner block of that view -- da: [W_(m,n1) | W_(m,n2) | ..] [x_all[:, n1]; x_all[:, n2]; ..],
+// db: sum over m of W_(m,n)^T x_loc[:, m] -- so an output element is one float32 sum over all partners (K split into slabs and the
+// fixed-order slab sum as before for da, stored by the GEMM for db) and is rounded once; there is no per-pair stage.  A segment is
+// named by 8 bits (pair, partner view) of one 64-bit word per slot; inside the K loop a scalar cursor (segment, K-step in it, the
+// two operand origins) moves one step per copy: adds and a compare, a shift at a segment switch -- no barrier, no load and no
+// division in a step (aecf_nce_gemm_body.h).  dT comes from the EPI_OUT_TD partials of all da slots in one nce_dtemp_kernel, and
+// nce_multi_finish_kernel sums the slabs into dx_loc and writes the zeros of the views that have no role.  With views = 2 the
+// three calls give the bits of aecf_nce_sym_*_dt.
 #include <math.h>
 #include <type_traits>
 
@@ -346,805 +363,89 @@ __device__ __forceinline__ bool nce_tile_of(const NceGemmArgs& p, unsigned int v
     }
 }
 
+// nce_gemm_kernel and the multi-view kernels below share their body as text (aecf_nce_gemm_body.h says why).
+//
+// The segments of a multi-view gradient product (MULTI): K runs through the partner blocks of one view, seg_steps K-steps each.
+// Field s of `fields` (8 bits) names segment s: bits 0..4 the pair whose weights block is the m operand (a_stride bytes apart
+// in the workspace), bits 5..7 the view whose rows are the n operand (view_bytes apart inside a row of x).
+struct NceSegs {
+    unsigned long long fields;
+    int seg_steps;
+    int64_t a_stride;
+    unsigned int view_bytes;
+};
+
 template <int AM, int BM, int EPI, int MAP>
 __global__ __launch_bounds__(512, 2) void nce_gemm_kernel(NceGemmArgs p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = lane_id(), r16 = lane & 15, lg = lane >> 4;
-    const int w = __builtin_amdgcn_readfirstlane(wave_id());
-    const int wm = w >> 2, wn = w & 3;
+    constexpr bool MULTI = false;
+    const unsigned int vblock = blockIdx.x;
+    const NceSegs ms = {};
+#include "aecf_nce_gemm_body.h"
+}
 
-    // ---- fragment addresses
-    int a_row[2], b_row[2];             // OP_ROW: per K-step of 32
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        const int ch = ((4 * ks + lg) ^ (r16 >> 1)) & 7;
-        a_row[ks] = (128 * wm + r16) * 128 + (ch << 4);
-        b_row[ks] = (64 * wn + r16) * 128 + (ch << 4);
+// ---- multi-view InfoNCE: all pair blocks in one launch (include/aecf_hip.h, "multi-view InfoNCE") ----------------------------
+//
+// The logits pass of P pairs: block b works on pair b / blocks_per_pair, tile b % blocks_per_pair of that pair's own MAP_2D
+// map (blocks_per_pair is a multiple of 8, so a tile keeps the XCD it has in a launch of its own).  The pair table supplies the
+// two operand origins inside the rows of x; E and the partials of pair p lie p strides behind those of pair 0.  Everything
+// else is the kernel above.
+constexpr int MV_MAX_VIEWS = 8, MV_MAX_PAIRS = 28;
+
+struct NceMultiLogits {
+    unsigned char m[MV_MAX_PAIRS], n[MV_MAX_PAIRS];     // pair p = (view m[p]: the local rows, view n[p]: the gathered keys)
+    unsigned int blocks_per_pair, view_bytes;
+    int64_t e_stride, rowsum_stride, colsum_stride;     // elements
+};
+
+template <int EPI>
+__global__ __launch_bounds__(512, 2) void nce_multi_logits_kernel(NceGemmArgs p, NceMultiLogits mv) {
+    const unsigned int pair = blockIdx.x / mv.blocks_per_pair;
+    p.a += mv.m[pair] * mv.view_bytes;
+    p.b += mv.n[pair] * mv.view_bytes;
+    p.e += pair * mv.e_stride;
+    p.rowsum_part += pair * mv.rowsum_stride;
+    p.colsum_part += pair * mv.colsum_stride;
+    constexpr int AM = OP_ROW, BM = OP_ROW, MAP = MAP_2D;
+    constexpr bool MULTI = false;
+    const unsigned int vblock = blockIdx.x - pair * mv.blocks_per_pair;
+    const NceSegs ms = {};
+#include "aecf_nce_gemm_body.h"
+}
+
+// A gradient product of every view that has the role, one launch: block b works on slot b / blocks_per_view (a view with at
+// least one pair in the role) and walks the K ranges of ALL its partner blocks, so an output element is one float32 sum.
+struct NceMultiProduct {
+    unsigned long long fields[MV_MAX_VIEWS];            // NceSegs::fields of the slot
+    int n_segs[MV_MAX_VIEWS];
+    int out_view[MV_MAX_VIEWS];                         // the view whose gradient the slot forms
+    unsigned int blocks_per_view, view_bytes;
+    int seg_steps, out_elem_bytes;
+    int64_t a_stride, tdot_stride;
+};
+
+template <int AM, int BM, int EPI, int MAP>
+__global__ __launch_bounds__(512, 2) void nce_multi_product_kernel(NceGemmArgs p, NceMultiProduct mv) {
+    const unsigned int slot = blockIdx.x / mv.blocks_per_view;
+    const int view = mv.out_view[slot];
+    p.k_steps = mv.n_segs[slot] * mv.seg_steps;
+    p.steps_per_split = (p.k_steps + p.splits - 1) / p.splits;
+    p.out = reinterpret_cast<char*>(p.out) + (int64_t)view * p.n_valid * mv.out_elem_bytes;
+    if (EPI == EPI_OUT_TD) {
+        p.tdot_src += (int64_t)view * p.n_valid;
+        p.tdot_part += slot * mv.tdot_stride;
     }
-    // OP_COL: lane 4 q + pp of group lg reads row 32 ks + 8 lg + 4 hh + q, columns 4 pp .. 4 pp + 3 of 16-column block blk:
-    //   8192 ks + 2048 lg + 512 (blk >> 1) + 256 hh + 64 q + 16 ((2 (blk & 1) + (pp >> 1)) ^ (2 (lg & 1) + hh)) + 8 (pp & 1)
-    const int q = r16 >> 2, pp = r16 & 3;
-    int tx[2][2];
-#pragma unroll
-    for (int b1 = 0; b1 < 2; ++b1)
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh)
-            tx[b1][hh] = 2048 * lg + 64 * q + 8 * (pp & 1) + 256 * hh + 16 * ((2 * b1 + (pp >> 1)) ^ (2 * (lg & 1) + hh));
-    const int a_img = 16384 * wm;                               // m blocks 8 wm + rt: image wm, block rt
-    const int b_img = 16384 * (wn >> 1) + 512 * (2 * (wn & 1)); // n blocks 4 wn + ct: image wn >> 1, block 4 (wn & 1) + ct
-
-    // operand tile of K-step t of output tile (mi, ni)
-    auto src_a = [&](int t, int mi) -> OperandSrc {
-        if (AM == OP_ROW) return OperandSrc{p.a + mi * p.a_sm + t * p.a_st, p.a_rows - BT * mi};
-        if (AM == OP_COLB)      // K rows 64 t .. of tile row t / 4, columns of tiles 4 mi .. 4 mi + 3
-            return OperandSrc{p.a + ((int64_t)(t >> 2) * p.a_sm + 4 * (int64_t)mi) * 32768 + (t & 3) * 8192, 64};
-        const int k0 = 64 * t < p.a_rows ? 64 * t : p.a_rows - 1;
-        return OperandSrc{p.a + (int64_t)k0 * p.lda + 512 * (int64_t)mi, 64 * t < p.a_rows ? p.a_rows - 64 * t : 1};
-    };
-    auto src_b = [&](int t, int ni) -> OperandSrc {
-        if (BM == OP_ROW) return OperandSrc{p.b + (int64_t)BT * ni * p.ldb + 128 * (int64_t)t, p.b_rows - BT * ni};
-        const int k0 = 64 * t < p.b_rows ? 64 * t : p.b_rows - 1;
-        return OperandSrc{p.b + (int64_t)k0 * p.ldb + 512 * (int64_t)ni, 64 * t < p.b_rows ? p.b_rows - 64 * t : 1};
-    };
-#define NCE_PIECE(P_, oa_, ob_, stage_, mi_, ni_)                                                                       \
-    do {                                                                                                                \
-        if ((P_) < 4) issue_piece<AM, (P_) & 3>(oa_, p.lda, p.a_cbytes - 512 * (mi_), smem + (stage_) * STAGE);          \
-        else issue_piece<BM, (P_) & 3>(ob_, p.ldb, p.b_cbytes - 512 * (ni_), smem + (stage_) * STAGE + OPB);             \
-    } while (0)
-    // fragment of slot sl = 8 ks + rt (m operand) / of (ks, ct) (n operand) from the tile at lds
-    auto read_a = [&](const char* la, int sl) -> u32x4 {
-        const int ks = sl >> 3, rt = sl & 7;
-        if (AM == OP_ROW) return *reinterpret_cast<const u32x4*>(la + a_row[ks] + 2048 * rt);
-        const int o = a_img + 8192 * ks + 512 * (rt >> 1);
-        return tr_frag16(la, o + tx[rt & 1][0], o + tx[rt & 1][1]);
-    };
-    auto read_b = [&](const char* lb, int ks, int ct) -> u32x4 {
-        if (BM == OP_ROW) return *reinterpret_cast<const u32x4*>(lb + b_row[ks] + 2048 * ct);
-        const int o = b_img + 8192 * ks + 512 * (ct >> 1);
-        return tr_frag16(lb, o + tx[ct & 1][0], o + tx[ct & 1][1]);
-    };
-    auto k_range = [&](int split, int& t_beg, int& t_end) {
-        t_beg = split * p.steps_per_split;
-        t_end = t_beg + p.steps_per_split < p.k_steps ? t_beg + p.steps_per_split : p.k_steps;
-    };
-    OperandSrc pa = {nullptr, 1}, pb = {nullptr, 1};            // the copy whose pieces 3..7 are still to be issued
-    // first copies of an output tile: step t_beg whole into stage 0, the first 3 pieces of step t_beg + 1 into stage 1
-    auto issue_first = [&](int mi, int ni, int t_beg, int t_end) {
-        if (t_beg >= t_end) return;
-        const OperandSrc oa = src_a(t_beg, mi), ob = src_b(t_beg, ni);
-        NCE_PIECE(0, oa, ob, 0, mi, ni); NCE_PIECE(1, oa, ob, 0, mi, ni); NCE_PIECE(2, oa, ob, 0, mi, ni);
-        NCE_PIECE(3, oa, ob, 0, mi, ni); NCE_PIECE(4, oa, ob, 0, mi, ni); NCE_PIECE(5, oa, ob, 0, mi, ni);
-        NCE_PIECE(6, oa, ob, 0, mi, ni); NCE_PIECE(7, oa, ob, 0, mi, ni);
-        if (t_beg + 1 < t_end) {
-            pa = src_a(t_beg + 1, mi); pb = src_b(t_beg + 1, ni);
-            NCE_PIECE(0, pa, pb, 1, mi, ni); NCE_PIECE(1, pa, pb, 1, mi, ni); NCE_PIECE(2, pa, pb, 1, mi, ni);
-        }
-    };
-
-    int mi = 0, ni = 0, split = 0, t_beg = 0, t_end = 0;
-    if (!nce_tile_of<MAP>(p, blockIdx.x, mi, ni, split)) return;
-    k_range(split, t_beg, t_end);
-    issue_first(mi, ni, t_beg, t_end);
-    {
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int rt = 0; rt < 8; ++rt)
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-        // ---- main loop.  A K-step is 16 slots of 4 MFMAs (slot = (ks, rt): one m fragment against the 4 n fragments); the m
-        // fragments run through a ring of 4 registers, read 3 slots ahead.  ONE barrier per K-step, at slot 13: by then every
-        // read of this step's stage has been issued (and is waited for), and the copy of step t + 1 -- issued a full step
-        // earlier -- is waited for, so behind the barrier (a) slots 13..15 read the first fragments of step t + 1 from the
-        // other stage (no bubble at the step boundary) and (b) the copy of step t + 2 into THIS stage starts.  The 8
-        // wave-instructions of a copy are spread over 8 slots (3 behind the barrier, 5 at the start of the next step) so that
-        // their issue cost hides behind MFMAs instead of stacking up in front of them.
-        u32x4 af[4], bf0[4], bf1[4];
-        if (t_beg < t_end) {
-            // younger than the first step's 8 pieces: the 3 pieces of the second step
-            if (t_beg + 1 < t_end) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            af[0] = read_a(smem, 0); af[1] = read_a(smem, 1); af[2] = read_a(smem, 2);
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) bf0[ct] = read_b(smem + OPB, 0, ct);
-        }
-        int st = 0;
-        // one K-step; H1 / H2: steps t + 1 / t + 2 exist (compile-time: the steady-state body has no branches)
-        auto kstep = [&](int t, auto h1, auto h2) {
-            constexpr bool H1 = decltype(h1)::value, H2 = decltype(h2)::value;
-            const char* cur = smem + st * STAGE;
-            const char* nxt = smem + (st ^ 1) * STAGE;
-            OperandSrc qa = {nullptr, 1}, qb = {nullptr, 1};
-#pragma unroll
-            for (int sl = 0; sl < 16; ++sl) {
-                if (sl == 13 && H1) {
-                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    if (H2) { qa = src_a(t + 2, mi); qb = src_b(t + 2, ni); }
-                }
-                if (sl < 5 && H1) {
-                    switch (sl) {
-                        case 0: NCE_PIECE(3, pa, pb, st ^ 1, mi, ni); break;
-                        case 1: NCE_PIECE(4, pa, pb, st ^ 1, mi, ni); break;
-                        case 2: NCE_PIECE(5, pa, pb, st ^ 1, mi, ni); break;
-                        case 3: NCE_PIECE(6, pa, pb, st ^ 1, mi, ni); break;
-                        default: NCE_PIECE(7, pa, pb, st ^ 1, mi, ni); break;
-                    }
-                }
-                if (sl >= 13 && H2) {
-                    switch (sl) {
-                        case 13: NCE_PIECE(0, qa, qb, st, mi, ni); break;
-                        case 14: NCE_PIECE(1, qa, qb, st, mi, ni); break;
-                        default: NCE_PIECE(2, qa, qb, st, mi, ni); break;
-                    }
-                }
-                if (sl <= 12) af[(sl + 3) & 3] = read_a(cur, sl + 3);
-                else if (H1) af[(sl + 3) & 3] = read_a(nxt, sl - 13);
-                if (sl >= 4 && sl <= 7) bf1[sl - 4] = read_b(cur + OPB, 1, sl - 4);
-                if (sl >= 13 && H1) {
-                    bf0[sl - 13] = read_b(nxt + OPB, 0, sl - 13);
-                    if (sl == 15) bf0[3] = read_b(nxt + OPB, 0, 3);
-                }
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct)
-                    acc[sl & 7][ct] = Tr<BF16>::mma(sl < 8 ? bf0[ct] : bf1[ct], af[sl & 3], acc[sl & 7][ct]);
-                __builtin_amdgcn_sched_barrier(0);              // the slot order IS the schedule
-            }
-            pa = qa; pb = qb;
-            st ^= 1;
-        };
-        {
-            using T_ = std::integral_constant<bool, true>;
-            using F_ = std::integral_constant<bool, false>;
-            int t = t_beg;
-            for (; t + 2 < t_end; ++t) kstep(t, T_{}, T_{});
-            if (t + 1 < t_end) { kstep(t, T_{}, F_{}); ++t; }
-            if (t < t_end) kstep(t, F_{}, F_{});
-        }
-
-        // ---- epilogue: lane (r16, lg) holds C[m = 128 wm + 16 rt + r16][n = 64 wn + 16 ct + 4 lg + r], r = 0..3
-        const int64_t gi0 = (int64_t)BT * mi + 128 * wm + r16;
-        const int gj0 = BT * ni + 64 * wn + 4 * lg;
-        if (EPI == EPI_OUT || EPI == EPI_OUT_TD || EPI == EPI_OUT_S || EPI == EPI_OUT_TD_S) {
-            if (EPI == EPI_OUT_S || EPI == EPI_OUT_TD_S) {
-                // g is stored unscaled: coef / Tc and the gradient arriving at the loss meet the float32 sums here
-                float osc = p.coef * nce_dev_inv_temp(p.temp, p.min_temp);
-                if (p.upstream) osc *= p.upstream[0];
-#pragma unroll
-                for (int rt = 0; rt < 8; ++rt)
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) acc[rt][ct] *= osc;
-            }
-            float* o = reinterpret_cast<float*>(p.out) + (int64_t)split * p.slab_stride;
-            unsigned short* ob = reinterpret_cast<unsigned short*>(p.out);
-#pragma unroll
-            for (int rt = 0; rt < 8; ++rt) {
-                const int64_t i = gi0 + 16 * rt;
-                if (i < p.m_valid) {
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) {
-                        const int j = gj0 + 16 * ct;
-                        if (j < p.n_valid) {
-                            if (p.out_bf16)
-                                *reinterpret_cast<u32x2*>(ob + i * p.ldo + j) =
-                                    u32x2{pack_bf16x2(acc[rt][ct][0], acc[rt][ct][1]), pack_bf16x2(acc[rt][ct][2], acc[rt][ct][3])};
-                            else *reinterpret_cast<f32x4*>(o + i * p.ldo + j) = acc[rt][ct];
-                        }
-                    }
-                }
-            }
-            if (EPI == EPI_OUT_TD || EPI == EPI_OUT_TD_S) {
-                float td = 0.f;
-#pragma unroll
-                for (int rt = 0; rt < 8; ++rt) {
-                    const int64_t i = gi0 + 16 * rt;
-                    if (i < p.m_valid) {
-#pragma unroll
-                        for (int ct = 0; ct < 4; ++ct) {
-                            const int j = gj0 + 16 * ct;
-                            if (j < p.n_valid) {
-                                const u32x2 x = *reinterpret_cast<const u32x2*>(p.tdot_src + i * p.ldo + j);
-                                td = fmaf(acc[rt][ct][0], __uint_as_float(x[0] << 16), td);
-                                td = fmaf(acc[rt][ct][1], __uint_as_float(x[0] & 0xffff0000u), td);
-                                td = fmaf(acc[rt][ct][2], __uint_as_float(x[1] << 16), td);
-                                td = fmaf(acc[rt][ct][3], __uint_as_float(x[1] & 0xffff0000u), td);
-                            }
-                        }
-                    }
-                }
-                td = reduce_wave(td);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();                   // every wave is past its last read of the stages
-                float* red = reinterpret_cast<float*>(smem);
-                if (lane == 0) red[w] = td;
-                __syncthreads();
-                if (threadIdx.x == 0)
-                    p.tdot_part[((int64_t)split * p.m_tiles + mi) * p.n_tiles + ni] =
-                        ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
-            }
-        } else if (EPI == EPI_SIG) {
-            // n = l log2(e) straight from the accumulator: l = acc / Tc + bias is never formed
-            const float s2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f, b2 = p.bias[0] * 1.4426950408889634f;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
-            float* lsp = reinterpret_cast<float*>(smem);        // [4][256] softplus sums | [4][256] g sums
-            float* lsg = lsp + 4 * BT;
-            // block-uniform: only tiles on the band of positives or on the ragged edge pay for the selects
-            const int64_t p0 = p.row_offset + (int64_t)BT * mi;
-            const bool special = BT * (mi + 1) > p.m_valid || BT * (ni + 1) > p.n_valid ||
-                                 (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
-            unsigned short* gtile = p.e + ((int64_t)mi * p.e_tiles + 4 * ni + wn) * (BT * 64) + (128 * wm + r16) * 64 + 4 * lg;
-            float rsp[8], rsg[8];
-            auto rows8 = [&](auto special_c) {
-                constexpr bool SP = decltype(special_c)::value;
-#pragma unroll
-                for (int rt = 0; rt < 8; ++rt) {
-                    const int64_t i = gi0 + 16 * rt;
-                    const bool iok = i < p.m_valid;
-                    const int64_t jp = p.row_offset + i;
-                    f32x2 sl = f32x2{0.f, 0.f}, sc = f32x2{0.f, 0.f}, sg = f32x2{0.f, 0.f};
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) {
-                        const int j = gj0 + 16 * ct;
-                        f32x2 g[2];
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            const f32x2 n = f32x2{acc[rt][ct][2 * h], acc[rt][ct][2 * h + 1]} * f32x2{s2, s2} + f32x2{b2, b2};
-                            SigTerms x = sig_terms(n);
-                            if (SP) {
-                                // the positive: softplus(-l) and -sigmoid(-l), formed from -n (not as differences)
-                                const SigTerms y = sig_terms(-n);
-#pragma unroll
-                                for (int k = 0; k < 2; ++k) {
-                                    const int col = j + 2 * h + k;
-                                    const bool pos = col == jp, ok = iok && col < p.n_valid;
-                                    x.sig[k] = ok ? (pos ? -y.sig[k] : x.sig[k]) : 0.f;
-                                    x.lg2[k] = ok ? (pos ? y.lg2[k] : x.lg2[k]) : 0.f;
-                                    x.corr[k] = ok ? (pos ? y.corr[k] : x.corr[k]) : 0.f;
-                                }
-                            }
-                            sl += x.lg2; sc += x.corr; sg += x.sig;
-                            g[h] = x.sig;
-                        }
-                        // tile (mi, 4 ni + wn) of g: row 128 wm + 16 rt + r16, columns 16 ct + 4 lg .. + 3 of its 64
-                        *reinterpret_cast<u32x2*>(gtile + (16 * rt) * 64 + 16 * ct) = u32x2{pack_bf16x2(g[0][0], g[0][1]), pack_bf16x2(g[1][0], g[1][1])};
-                    }
-                    rsp[rt] = reduce_lg(fmaf(sl[0] + sl[1], 0.6931471805599453f, sc[0] + sc[1]));     // over the wave's 64 columns
-                    rsg[rt] = reduce_lg(sg[0] + sg[1]);
-                }
-            };
-            if (special) rows8(std::integral_constant<bool, true>{});
-            else rows8(std::integral_constant<bool, false>{});
-            if (lg == 0) {
-#pragma unroll
-                for (int rt = 0; rt < 8; ++rt) {
-                    lsp[wn * BT + 128 * wm + 16 * rt + r16] = rsp[rt];
-                    lsg[wn * BT + 128 * wm + 16 * rt + r16] = rsg[rt];
-                }
-            }
-            __syncthreads();
-            const int tdx = threadIdx.x & (BT - 1);
-            const float* src = threadIdx.x < BT ? lsp : lsg;
-            (threadIdx.x < BT ? p.sp_part : p.sg_part)[((int64_t)ni * p.m_tiles + mi) * BT + tdx] =
-                (src[tdx] + src[BT + tdx]) + (src[2 * BT + tdx] + src[3 * BT + tdx]);
-        } else if (EPI == EPI_RANK) {
-            // row thresholds first (their latency passes while the other waves arrive); padding re-reads the last one
-            const bool cols_on = p.pos_col != nullptr;                  // block-uniform
-            float pr[8];
-#pragma unroll
-            for (int rt = 0; rt < 8; ++rt) {
-                const int64_t i = gi0 + 16 * rt;
-                pr[rt] = p.pos_row[i < p.m_valid ? i : p.m_valid - 1];
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
-            int* lrow = reinterpret_cast<int*>(smem);           // [4][256] row counts | [2][256] column counts
-            int* lcol = lrow + 4 * BT;
-            // block-uniform: only tiles on the band of positives or on the ragged edge pay for the selects
-            const int64_t p0 = p.row_offset + (int64_t)BT * mi;
-            const bool special = BT * (mi + 1) > p.m_valid || BT * (ni + 1) > p.n_valid ||
-                                 (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
-            // the accumulator of (rt, ct, r); SP: the positive and the padding become a NaN -- one select, and every comparison
-            // with it is false.  The empty asm keeps the value opaque: comparisons that the variants below have in common would
-            // otherwise be hoisted in front of the branch, hundreds of masks at once, and spill.
-            auto elem = [&](auto special_c, int rt, int ct, int r) -> float {
-                constexpr bool SP = decltype(special_c)::value;
-                float sv = acc[rt][ct][r];
-                asm volatile("" : "+v"(sv));
-                if (SP) {
-                    const int64_t i = gi0 + 16 * rt;
-                    const int col = gj0 + 16 * ct + r;
-                    sv = ((i < p.m_valid) & (col < p.n_valid) & (col != p.row_offset + i)) ? sv : __builtin_nanf("");
-                }
-                return sv;
-            };
-            // rows: greater | equal << 16 over the wave's 64 columns (<= 64 in either half), then over the 4 lane groups
-            auto count_rows = [&](auto special_c) {
-#pragma unroll
-                for (int rt = 0; rt < 8; ++rt) {
-                    int rg = 0, re = 0;
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float sv = elem(special_c, rt, ct, r);
-                            rg += (int)(sv > pr[rt]);
-                            re += (int)(sv == pr[rt]);
-                        }
-                    }
-                    int v = rg | (re << 16);
-                    v += __shfl_xor(v, 16, 64);
-                    v += __shfl_xor(v, 32, 64);
-                    if (lg == 0) lrow[wn * BT + 128 * wm + 16 * rt + r16] = v;
-                }
-            };
-            // columns: the same over the wave's 128 rows (<= 128 in either half), then over the 16 lanes of a group
-            auto count_cols = [&](auto special_c) {
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    float pc[4];
-                    int cg[4], ce[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int j = gj0 + 16 * ct + r;
-                        pc[r] = p.pos_col[j < p.n_valid ? j : p.n_valid - 1];
-                        cg[r] = ce[r] = 0;
-                    }
-#pragma unroll
-                    for (int rt = 0; rt < 8; ++rt) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float sv = elem(special_c, rt, ct, r);
-                            cg[r] += (int)(sv > pc[r]);
-                            ce[r] += (int)(sv == pc[r]);
-                        }
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        int v = cg[r] | (ce[r] << 16);
-                        v += __shfl_xor(v, 1, 64);
-                        v += __shfl_xor(v, 2, 64);
-                        v += __shfl_xor(v, 4, 64);
-                        v += __shfl_xor(v, 8, 64);
-                        if (r16 == 0) lcol[wm * BT + 64 * wn + 16 * ct + 4 * lg + r] = v;
-                    }
-                }
-            };
-            using T_ = std::integral_constant<bool, true>;
-            using F_ = std::integral_constant<bool, false>;
-            if (special) {
-                count_rows(T_{});
-                if (cols_on) count_cols(T_{});
-            } else {
-                count_rows(F_{});
-                if (cols_on) count_cols(F_{});
-            }
-            __syncthreads();
-            const int tdx = threadIdx.x;
-            if (tdx < BT) {
-                p.rank_row_part[((int64_t)ni * p.m_tiles + mi) * BT + tdx] = (lrow[tdx] + lrow[BT + tdx]) + (lrow[2 * BT + tdx] + lrow[3 * BT + tdx]);
-            } else if (cols_on) {
-                const int c = tdx - BT;
-                p.rank_col_part[((int64_t)mi * p.n_tiles + ni) * BT + c] = lcol[c] + lcol[BT + c];
-            }
-        } else if (EPI == EPI_TOPK) {
-            typedef unsigned long long u64;
-            const int kk = p.topk;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
-            u64* lst = reinterpret_cast<u64*>(smem);            // [4 wn][16 slots][256 rows] keys: the 128 KB of the stages
-            // block-uniform: only tiles holding an excluded partner or a ragged edge pay for the selects
-            const int64_t p0 = p.row_offset + (int64_t)BT * mi;
-            const bool special = BT * (mi + 1) > p.m_valid || BT * (ni + 1) > p.n_valid ||
-                                 (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
-            const unsigned int inv0 = ~(unsigned)gj0;           // inverted column of (ct, r): inv0 - (16 ct + r)
-            auto rows8 = [&](auto special_c) {
-                constexpr bool SP = decltype(special_c)::value;
-#pragma unroll
-                for (int rt = 0; rt < 8; ++rt) {
-                    const int64_t i = gi0 + 16 * rt;
-                    u64 K[16];
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float sv = acc[rt][ct][r];
-                            asm volatile("" : "+v"(sv));        // (opaque: keeps the two variants' common work behind the branch)
-                            sv += 0.f;                          // -0 -> +0: equal scores have one image
-                            const unsigned int b = __float_as_uint(sv);
-                            unsigned int u = b ^ ((unsigned)((int)b >> 31) | 0x80000000u);
-                            u = sv != sv ? 1u : u;
-                            u64 key = ((u64)u << 32) | (u64)(inv0 - (unsigned)(16 * ct + r));
-                            if (SP) {
-                                const int col = gj0 + 16 * ct + r;
-                                key = ((i < p.m_valid) & (col < p.n_valid) & (col != p.row_offset + i)) ? key : 0ull;
-                            }
-                            K[4 * ct + r] = key;
-                        }
-                    }
-                    // the lane's 16 keys, best first: Batcher's merge exchange, 63 compare-exchanges
-#define TOPK_CE(x_, y_)                                                                                                 \
-    do {                                                                                                                \
-        const u64 hi_ = K[x_] > K[y_] ? K[x_] : K[y_], lo_ = K[x_] > K[y_] ? K[y_] : K[x_];                             \
-        K[x_] = hi_; K[y_] = lo_;                                                                                       \
-    } while (0)
-                    TOPK_CE(0, 1); TOPK_CE(2, 3); TOPK_CE(4, 5); TOPK_CE(6, 7); TOPK_CE(8, 9); TOPK_CE(10, 11); TOPK_CE(12, 13); TOPK_CE(14, 15);
-                    TOPK_CE(0, 2); TOPK_CE(1, 3); TOPK_CE(4, 6); TOPK_CE(5, 7); TOPK_CE(8, 10); TOPK_CE(9, 11); TOPK_CE(12, 14); TOPK_CE(13, 15);
-                    TOPK_CE(1, 2); TOPK_CE(5, 6); TOPK_CE(9, 10); TOPK_CE(13, 14);
-                    TOPK_CE(0, 4); TOPK_CE(1, 5); TOPK_CE(2, 6); TOPK_CE(3, 7); TOPK_CE(8, 12); TOPK_CE(9, 13); TOPK_CE(10, 14); TOPK_CE(11, 15);
-                    TOPK_CE(2, 4); TOPK_CE(3, 5); TOPK_CE(10, 12); TOPK_CE(11, 13);
-                    TOPK_CE(1, 2); TOPK_CE(3, 4); TOPK_CE(5, 6); TOPK_CE(9, 10); TOPK_CE(11, 12); TOPK_CE(13, 14);
-                    TOPK_CE(0, 8); TOPK_CE(1, 9); TOPK_CE(2, 10); TOPK_CE(3, 11); TOPK_CE(4, 12); TOPK_CE(5, 13); TOPK_CE(6, 14); TOPK_CE(7, 15);
-                    TOPK_CE(4, 8); TOPK_CE(5, 9); TOPK_CE(6, 10); TOPK_CE(7, 11);
-                    TOPK_CE(2, 4); TOPK_CE(3, 5); TOPK_CE(6, 8); TOPK_CE(7, 9); TOPK_CE(10, 12); TOPK_CE(11, 13);
-                    TOPK_CE(1, 2); TOPK_CE(3, 4); TOPK_CE(5, 6); TOPK_CE(7, 8); TOPK_CE(9, 10); TOPK_CE(11, 12); TOPK_CE(13, 14);
-#undef TOPK_CE
-                    // the wave's 64 columns of the row lie in 4 lane groups: pop the largest of the 4 heads k times
-                    u64* dst = lst + (wn * 16) * BT + 128 * wm + 16 * rt + r16;
-                    for (int t = 0; t < kk; ++t) {
-                        u64 win = K[0];
-                        u64 o = __shfl_xor(win, 16, 64);
-                        win = o > win ? o : win;
-                        o = __shfl_xor(win, 32, 64);
-                        win = o > win ? o : win;
-                        if (lg == 0) dst[t * BT] = win;
-                        const bool mine = K[0] == win;          // keys are distinct (only sentinels repeat)
-#pragma unroll
-                        for (int j = 0; j < 15; ++j) K[j] = mine ? K[j + 1] : K[j];
-                        K[15] = mine ? 0ull : K[15];
-                    }
-                }
-            };
-            if (special) rows8(std::integral_constant<bool, true>{});
-            else rows8(std::integral_constant<bool, false>{});
-            __syncthreads();
-            if (threadIdx.x < BT) {
-                // one thread per row: the 4 waves' sorted lists into the tile's list
-                const u64* l0 = lst + threadIdx.x;
-                u64* out = p.topk_part + (((int64_t)ni * p.m_tiles + mi) * BT + threadIdx.x) * p.topk_kp;
-                u64 h[4];
-                int c[4];
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) { h[q4] = l0[(q4 * 16) * BT]; c[q4] = 0; }
-                for (int t = 0; t < kk; ++t) {
-                    const u64 h01 = h[0] > h[1] ? h[0] : h[1], h23 = h[2] > h[3] ? h[2] : h[3];
-                    const u64 best = h01 > h23 ? h01 : h23;
-                    out[t] = best;
-#pragma unroll
-                    for (int q4 = 0; q4 < 4; ++q4) {
-                        const bool won = h[q4] == best;
-                        c[q4] += (int)won;
-                        const bool more = c[q4] < kk;
-                        const u64 nx = l0[(q4 * 16 + (more ? c[q4] : 0)) * BT];
-                        h[q4] = won ? (more ? nx : 0ull) : h[q4];
-                    }
-                }
-            }
-        } else {
-            float scale2 = p.scale2, shift2 = p.shift2;
-            // EPI_SUP: the labels of the lane's 8 rows and 16 columns are read here (their latency passes behind the exponentials)
-            // and kept as 32-bit keys: equal classes have equal keys; a row that can match nothing (unlabeled or padding, which
-            // re-reads the last label) gets a key no column has, and the other way round.  24 registers beside the accumulators
-            // where the int64 labels would take 48 and spill.
-            unsigned int kr[8], kc[16];
-            if (epi_has_labels(EPI)) {
-#pragma unroll
-                for (int rt = 0; rt < 8; ++rt) {
-                    const int i = (int)gi0 + 16 * rt;
-                    const bool iok = i < p.m_valid;
-                    const long long l = sup_label_at(p.lab_row, iok ? i : p.m_valid - 1);
-                    kr[rt] = (iok && l >= 0) ? sup_label_key(l) : 0xffffffffu;
-                }
-#pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    const int j = gj0 + 16 * (c >> 2) + (c & 3);
-                    const bool jok = j < p.n_valid;
-                    const long long l = sup_label_at(p.lab_col, jok ? j : p.n_valid - 1);
-                    kc[c] = (jok && l >= 0) ? sup_label_key(l) : 0xfffffffeu;
-                }
-            }
-            // EPI_SETS_*: thread t < 256 reads the word of the block's row t, thread 256 + t that of its column t (the padding: the
-            // empty set); they go to LDS behind the barrier
-            unsigned long long my_set = 0ull;
-            if (epi_has_sets(EPI)) {
-                const int t = threadIdx.x & (BT - 1);
-                const bool is_row = threadIdx.x < BT;
-                const int k = BT * (is_row ? mi : ni) + t;
-                const unsigned long long* src = reinterpret_cast<const unsigned long long*>(is_row ? p.lab_row : p.lab_col);
-                if (k < (is_row ? p.m_valid : p.n_valid)) my_set = src[k];
-            }
-            if (EPI == EPI_EXP_DT || epi_has_labels(EPI) || epi_has_sets(EPI) || EPI == EPI_EXP_SELF) {
-                scale2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f;
-                shift2 = scale2;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
-            if (epi_has_sets(EPI))                              // [256] row words | [256] column words, behind the 18 float planes
-                reinterpret_cast<unsigned long long*>(smem + 18 * BT * 4)[threadIdx.x] = my_set;
-            // E = exp2(acc scale - shift): 4 consecutive columns per lane, 8-byte stores (16 rows x 32 B per wave-instruction).
-            // The sums run as packed float32 adds (both halves from their own registers); masking only on edge tiles.
-            float rs[8];
-            f32x2 cs2[4][2];
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) cs2[ct][0] = cs2[ct][1] = f32x2{0.f, 0.f};
-            float* lrs = reinterpret_cast<float*>(smem);        // [4][256] row sums | [2][256] column sums
-            float* lcs = lrs + 4 * BT;
-            bool edge = BT * (mi + 1) > p.m_valid || BT * (ni + 1) > p.n_valid;            // block-uniform
-            if (epi_is_self(EPI)) {
-                // the band of excluded keys (column row_offset + i of row i) crosses this tile: it takes the branch of the ragged
-                // edge, so only the tiles that hold such an element pay for the index test
-                const int64_t p0 = p.row_offset + (int64_t)BT * mi;
-                edge = edge || (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
-            }
-            unsigned short* etile = p.e + ((int64_t)mi * p.e_tiles + 4 * ni + wn) * (BT * 64) + (128 * wm + r16) * 64 + 4 * lg;
-#pragma unroll
-            for (int rt = 0; rt < 8; ++rt) {
-                const int64_t i = gi0 + 16 * rt;
-                f32x2 s2 = f32x2{0.f, 0.f};
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    const int j = gj0 + 16 * ct;
-                    f32x2 e01, e23;
-                    e01[0] = __builtin_amdgcn_exp2f(acc[rt][ct][0] * scale2 - shift2);
-                    e01[1] = __builtin_amdgcn_exp2f(acc[rt][ct][1] * scale2 - shift2);
-                    e23[0] = __builtin_amdgcn_exp2f(acc[rt][ct][2] * scale2 - shift2);
-                    e23[1] = __builtin_amdgcn_exp2f(acc[rt][ct][3] * scale2 - shift2);
-                    if (edge) {
-                        const bool iok = i < p.m_valid;
-                        // EPI_EXP_SELF: the excluded key by its index (a row that exists has row_offset + i < n_valid < 2^31; unsigned,
-                        // so that the padding rows past it wrap instead of overflowing)
-                        const unsigned int js = epi_is_self(EPI) ? (unsigned)p.row_offset + (unsigned)i : 0u;
-                        e01[0] = (iok && j + 0 < p.n_valid && (!epi_is_self(EPI) || (unsigned)j + 0u != js)) ? e01[0] : 0.f;
-                        e01[1] = (iok && j + 1 < p.n_valid && (!epi_is_self(EPI) || (unsigned)j + 1u != js)) ? e01[1] : 0.f;
-                        e23[0] = (iok && j + 2 < p.n_valid && (!epi_is_self(EPI) || (unsigned)j + 2u != js)) ? e23[0] : 0.f;
-                        e23[1] = (iok && j + 3 < p.n_valid && (!epi_is_self(EPI) || (unsigned)j + 3u != js)) ? e23[1] : 0.f;
-                    }
-                    s2 += e01 + e23;
-                    if (!epi_is_self(EPI)) {
-                        cs2[ct][0] += e01;
-                        cs2[ct][1] += e23;
-                    }
-                    // tile (mi, 4 ni + wn) of E: row 128 wm + 16 rt + r16, columns 16 ct + 4 lg .. + 3 of its 64 -- the four
-                    // stores of a row group fill whole 128-byte lines of one 32 KB tile
-                    *reinterpret_cast<u32x2*>(etile + (16 * rt) * 64 + 16 * ct) = u32x2{pack_bf16x2(e01[0], e01[1]), pack_bf16x2(e23[0], e23[1])};
-                }
-                rs[rt] = reduce_lg(s2[0] + s2[1]);              // over the wave's 64 columns
-            }
-            float cs[4][4];
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) { cs[ct][0] = cs2[ct][0][0]; cs[ct][1] = cs2[ct][0][1]; cs[ct][2] = cs2[ct][1][0]; cs[ct][3] = cs2[ct][1][1]; }
-            if (lg == 0) {
-#pragma unroll
-                for (int rt = 0; rt < 8; ++rt) lrs[wn * BT + 128 * wm + 16 * rt + r16] = rs[rt];
-            }
-            if (!epi_is_self(EPI)) {
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float v = reduce_r16(cs[ct][r]);  // over the wave's 128 rows
-                        if (r16 == 0) lcs[wm * BT + 64 * wn + 16 * ct + 4 * lg + r] = v;
-                    }
-            }
-            float* lrn = lcs + 2 * BT;                          // EPI_SUP: [4][256] row counts | [4][256] row sums |
-            float* lrx = lrn + 4 * BT;                          //          [2][256] column counts | [2][256] column sums
-            float* lcn = lrx + 4 * BT;
-            float* lcx = lcn + 2 * BT;
-            if (epi_has_labels(EPI)) {
-                constexpr bool COLS = EPI == EPI_SUP;           // EPI_SUP_SELF: the row half alone
-                // block-uniform: only tiles on the band of partners or on the ragged edge pay for the index tests
-                const int64_t p0 = p.row_offset + (int64_t)BT * mi;
-                const bool special = edge || (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
-                auto label_stats = [&](auto special_c) {
-                    constexpr bool SP = decltype(special_c)::value;
-                    // Matches are sparse, so the tile is first searched with the 32-bit keys: two VALU operations per element and
-                    // no compare mask.  Only a row group (rt) with a key hit somewhere in the wave reads its int64 labels again
-                    // (from L1 / L2) and forms the 64-bit matches and the sums -- a vote that changes no bit: a group without a
-                    // match would have summed zeros.
-                    // the column sums gather in LDS, in the slots of the lanes that own them (r16 == 0: one lane per column and
-                    // wave), row group after row group: 32 accumulators less beside the 128 of the tile
-                    float* wcn = lcn + wm * BT + 64 * wn + 4 * lg;
-                    float* wcx = lcx + wm * BT + 64 * wn + 4 * lg;
-                    if (COLS && r16 == 0) {
-#pragma unroll
-                        for (int c = 0; c < 16; ++c) wcn[16 * (c >> 2) + (c & 3)] = wcx[16 * (c >> 2) + (c & 3)] = 0.f;
-                    }
-#pragma unroll
-                    for (int rt = 0; rt < 8; ++rt) {
-                        unsigned int nearest = 0xffffffffu;
-#pragma unroll
-                        for (int c = 0; c < 16; ++c) {
-                            const unsigned int x = kr[rt] ^ kc[c];
-                            nearest = x < nearest ? x : nearest;
-                        }
-                        float rn = 0.f, rx = 0.f;
-                        if (__any(nearest == 0u)) {
-                            // (opaque: nothing this rare branch needs -- indices, addresses, the labels themselves -- may be
-                            // formed in front of it or kept from the reads in front of the exponentials: it would sit in scratch)
-                            int i = (int)gi0 + 16 * rt, gj = gj0;
-                            const long long* lab_row = p.lab_row;
-                            const long long* lab_col = p.lab_col;
-                            asm volatile("" : "+v"(i), "+v"(gj), "+s"(lab_row), "+s"(lab_col));
-                            const long long lr = sup_label_at(lab_row, i < p.m_valid ? i : p.m_valid - 1);
-                            // SP: the partner counts by index, not here; its column relative to gj (-1: not in this lane's 64)
-                            const int64_t rel = p.row_offset + i - gj;
-                            const int jpr = (rel >= 0 && rel < 64) ? (int)rel : -1;
-#pragma unroll
-                            for (int c = 0; c < 16; ++c) {
-                                const int j = gj + 16 * (c >> 2) + (c & 3);
-                                // (the keys carry the padding: an equal key is a row and a column that exist)
-                                bool m = (kr[rt] == kc[c]) & sup_label_match(lr, sup_label_at(lab_col, j < p.n_valid ? j : p.n_valid - 1));
-                                if (SP) m = m & (jpr != 16 * (c >> 2) + (c & 3));
-                                const float one = m ? 1.f : 0.f, sv = m ? acc[rt][c >> 2][c & 3] : 0.f;
-                                rn += one; rx += sv;
-                                if (COLS) {
-                                    const float c1 = reduce_r16(one), c2 = reduce_r16(sv);  // over the group's 16 rows
-                                    if (r16 == 0) {
-                                        wcn[16 * (c >> 2) + (c & 3)] += c1;
-                                        wcx[16 * (c >> 2) + (c & 3)] += c2;
-                                    }
-                                }
-                            }
-                            rn = reduce_lg(rn);                 // over the wave's 64 columns
-                            rx = reduce_lg(rx);
-                        }
-                        if (lg == 0) {
-                            lrn[wn * BT + 128 * wm + 16 * rt + r16] = rn;
-                            lrx[wn * BT + 128 * wm + 16 * rt + r16] = rx;
-                        }
-                    }
-                };
-                if (special) label_stats(std::integral_constant<bool, true>{});
-                else label_stats(std::integral_constant<bool, false>{});
-            }
-            if (epi_is_sets(EPI)) {
-                constexpr bool JAC = EPI == EPI_SETS_JAC;
-                typedef unsigned long long u64;
-                __syncthreads();                                // the staged words are in place
-                const u64* lsr = reinterpret_cast<const u64*>(smem + 18 * BT * 4) + 128 * wm + r16;            // + 16 rt
-                const u64* lsc = reinterpret_cast<const u64*>(smem + 18 * BT * 4) + BT + 64 * wn + 4 * lg;     // + 16 ct + r
-                // block-uniform: only the tiles on the band of partners pay for the index test (the padding weighs 0 by its sets)
-                const int64_t p0 = p.row_offset + (int64_t)BT * mi;
-                const bool special = p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni;
-                // the partner of the lane's row of group rt is its element 16 ct + r where rel == 16 (ct - rt) + r
-                const int64_t rel64 = p.row_offset + gi0 - gj0;
-                const int rel = (rel64 > -512 && rel64 < 512) ? (int)rel64 : -4096;
-                auto set_stats = [&](auto special_c) {
-                    constexpr bool SP = decltype(special_c)::value;
-                    float rw[8], rx[8];
-#pragma unroll
-                    for (int rt = 0; rt < 8; ++rt) rw[rt] = rx[rt] = 0.f;
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) {
-                        u64 B[4];
-                        int pb[4];
-                        float cw[4], cx[4];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            B[r] = lsc[16 * ct + r];
-                            pb[r] = JAC ? __popcll(B[r]) : 0;
-                            cw[r] = cx[r] = 0.f;
-                        }
-#pragma unroll
-                        for (int rt = 0; rt < 8; ++rt) {
-                            const u64 A = lsr[16 * rt];
-                            const int pa = JAC ? __popcll(A) : 0;
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                float wt = set_weight<JAC>(A, B[r], pa, pb[r]);
-                                if (SP) wt = rel == 16 * (ct - rt) + r ? 0.f : wt;
-                                const float sv = acc[rt][ct][r];
-                                rw[rt] += wt;
-                                rx[rt] = fmaf(wt, sv, rx[rt]);
-                                cw[r] += wt;
-                                cx[r] = fmaf(wt, sv, cx[r]);
-                            }
-                        }
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float c1 = reduce_r16(cw[r]), c2 = reduce_r16(cx[r]);     // over the wave's 128 rows
-                            if (r16 == 0) {
-                                lcn[wm * BT + 64 * wn + 16 * ct + 4 * lg + r] = c1;
-                                lcx[wm * BT + 64 * wn + 16 * ct + 4 * lg + r] = c2;
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int rt = 0; rt < 8; ++rt) {
-                        const float r1 = reduce_lg(rw[rt]), r2 = reduce_lg(rx[rt]);         // over the wave's 64 columns
-                        if (lg == 0) {
-                            lrn[wn * BT + 128 * wm + 16 * rt + r16] = r1;
-                            lrx[wn * BT + 128 * wm + 16 * rt + r16] = r2;
-                        }
-                    }
-                };
-                if (special) set_stats(std::integral_constant<bool, true>{});
-                else set_stats(std::integral_constant<bool, false>{});
-            }
-            if (epi_is_sets_self(EPI)) {
-                // the ROW half of the sweep above, chain for chain (ct-major over the lane's 16 elements of a row, then the lane
-                // groups): 16 row accumulators and the 4 column words of the group, no column accumulators and no LDS column slots
-                constexpr bool JAC = EPI == EPI_SETS_JAC_SELF;
-                typedef unsigned long long u64;
-                __syncthreads();                                // the staged words are in place
-                const u64* lsr = reinterpret_cast<const u64*>(smem + 18 * BT * 4) + 128 * wm + r16;            // + 16 rt
-                const u64* lsc = reinterpret_cast<const u64*>(smem + 18 * BT * 4) + BT + 64 * wn + 4 * lg;     // + 16 ct + r
-                // block-uniform: only the tiles the band of anchors crosses pay for the index test (the padding weighs 0 by its sets)
-                const int64_t p0 = p.row_offset + (int64_t)BT * mi;
-                const bool special = p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni;
-                // the anchor of the lane's row of group rt is its element 16 ct + r where rel == 16 (ct - rt) + r: weight 0 by INDEX,
-                // never by its set or its value (a bit-identical row with the same set elsewhere in the view is a positive)
-                const int64_t rel64 = p.row_offset + gi0 - gj0;
-                const int rel = (rel64 > -512 && rel64 < 512) ? (int)rel64 : -4096;
-                auto set_row_stats = [&](auto special_c) {
-                    constexpr bool SP = decltype(special_c)::value;
-                    float rw[8], rx[8];
-#pragma unroll
-                    for (int rt = 0; rt < 8; ++rt) rw[rt] = rx[rt] = 0.f;
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) {
-                        u64 B[4];
-                        int pb[4];
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            B[r] = lsc[16 * ct + r];
-                            pb[r] = JAC ? __popcll(B[r]) : 0;
-                        }
-#pragma unroll
-                        for (int rt = 0; rt < 8; ++rt) {
-                            const u64 A = lsr[16 * rt];
-                            const int pa = JAC ? __popcll(A) : 0;
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                float wt = set_weight<JAC>(A, B[r], pa, pb[r]);
-                                if (SP) wt = rel == 16 * (ct - rt) + r ? 0.f : wt;
-                                rw[rt] += wt;
-                                rx[rt] = fmaf(wt, acc[rt][ct][r], rx[rt]);
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int rt = 0; rt < 8; ++rt) {
-                        const float r1 = reduce_lg(rw[rt]), r2 = reduce_lg(rx[rt]);         // over the wave's 64 columns
-                        if (lg == 0) {
-                            lrn[wn * BT + 128 * wm + 16 * rt + r16] = r1;
-                            lrx[wn * BT + 128 * wm + 16 * rt + r16] = r2;
-                        }
-                    }
-                };
-                if (special) set_row_stats(std::integral_constant<bool, true>{});
-                else set_row_stats(std::integral_constant<bool, false>{});
-            }
-            __syncthreads();
-            const int tdx = threadIdx.x;
-            if (tdx < BT) {
-                const int64_t o = ((int64_t)ni * p.m_tiles + mi) * BT + tdx;
-                p.rowsum_part[o] = (lrs[tdx] + lrs[BT + tdx]) + (lrs[2 * BT + tdx] + lrs[3 * BT + tdx]);
-                if (epi_has_labels(EPI) || epi_has_sets(EPI)) {
-                    p.rowcnt_part[o] = (lrn[tdx] + lrn[BT + tdx]) + (lrn[2 * BT + tdx] + lrn[3 * BT + tdx]);
-                    p.rowsx_part[o] = (lrx[tdx] + lrx[BT + tdx]) + (lrx[2 * BT + tdx] + lrx[3 * BT + tdx]);
-                }
-            } else if (!epi_is_self(EPI)) {
-                const int c = tdx - BT;
-                const int64_t o = ((int64_t)mi * p.n_tiles + ni) * BT + c;
-                p.colsum_part[o] = lcs[c] + lcs[BT + c];
-                if (EPI == EPI_SUP || epi_is_sets(EPI)) {
-                    p.colcnt_part[o] = lcn[c] + lcn[BT + c];
-                    p.colsx_part[o] = lcx[c] + lcx[BT + c];
-                }
-            }
-        }
-    }
-#undef NCE_PIECE
+    const NceSegs ms = {mv.fields[slot], mv.seg_steps, mv.a_stride, mv.view_bytes};
+    constexpr bool MULTI = true;
+    const unsigned int vblock = blockIdx.x - slot * mv.blocks_per_view;
+#include "aecf_nce_gemm_body.h"
 }
 
 // ---- small kernels around the GEMMs ------------------------------------------------------------------------------------
 
 // l[i] = sum over the column tiles' partials, c[j] = sum over the row tiles' (fixed order: four strided partial sums per
 // element, added in order).  Block = 64 elements x 4 parts.
-__global__ __launch_bounds__(256) void nce_sums_kernel(const float* rowsum_part, const float* colsum_part, int m_tiles, int n_tiles,
-                                                       int64_t rows, int64_t cols, float* l, float* c) {
+__device__ __forceinline__ void nce_sums_body(const float* rowsum_part, const float* colsum_part, int m_tiles, int n_tiles,
+                                              int64_t rows, int64_t cols, float* l, float* c) {
     __shared__ float red[4][64];
     const int e = threadIdx.x & 63, part = threadIdx.x >> 6;
     const int64_t Rp = (int64_t)m_tiles * BT;
@@ -1162,6 +463,19 @@ __global__ __launch_bounds__(256) void nce_sums_kernel(const float* rowsum_part,
         if (is_row) { if (id < rows) l[id] = v; }
         else if (id < cols && c) c[id] = v;
     }
+}
+
+__global__ __launch_bounds__(256) void nce_sums_kernel(const float* rowsum_part, const float* colsum_part, int m_tiles, int n_tiles,
+                                                       int64_t rows, int64_t cols, float* l, float* c) {
+    nce_sums_body(rowsum_part, colsum_part, m_tiles, n_tiles, rows, cols, l, c);
+}
+
+// multi-view: the sums of pair blockIdx.y, in the order nce_sums_kernel has; l [P][Rp], c [P][cols]
+__global__ __launch_bounds__(256) void nce_multi_sums_kernel(const float* rowsum_part, const float* colsum_part, int m_tiles,
+                                                             int n_tiles, int64_t rows, int64_t cols, float* l, float* c) {
+    const int64_t pair = blockIdx.y, Rp = (int64_t)m_tiles * BT, Cp = (int64_t)n_tiles * BT;
+    nce_sums_body(rowsum_part + pair * n_tiles * Rp, colsum_part + pair * m_tiles * Cp, m_tiles, n_tiles, rows, cols, l + pair * Rp,
+                  c + pair * cols);
 }
 
 struct NceFinArgs {
@@ -1228,6 +542,39 @@ __global__ __launch_bounds__(256) void nce_finalize_kernel(NceFinArgs p) {
     if (blockIdx.x == 0 && p.n_ent > 0) entropy_rider(p.ent, p.n_ent, p.ent_target, p.ent_scale, p.d_ent, p.ent_loss);
 }
 
+// multi-view: nce_finalize_kernel<true> (sym, no rider) for pair blockIdx.y = (view m, view n) of the table, operation for
+// operation; the rows of a view lie `views` d apart inside x.  l, u, ediag [P][Rp], c [P][cols], v [P][Cp], loss_rows [P][rows]
+struct NceMultiFin {
+    unsigned char m[MV_MAX_PAIRS], n[MV_MAX_PAIRS];
+    int views;
+};
+__global__ __launch_bounds__(256) void nce_multi_finalize_kernel(NceFinArgs p, NceMultiFin mv) {
+    const int64_t pair = blockIdx.y, ld = (int64_t)mv.views * p.d;
+    const float inv_temp = nce_dev_inv_temp(p.temp, p.min_temp);
+    const float* c = p.c + pair * p.cols;
+    const int lane = lane_id();
+    const int64_t i = (int64_t)blockIdx.x * 4 + wave_id();
+    if (i < p.rows) {
+        const unsigned short* ap = p.a + i * ld + mv.m[pair] * p.d;
+        const unsigned short* bp = p.b + (p.row_offset + i) * ld + mv.n[pair] * p.d;
+        float dot = 0.f;
+        for (int k = lane; k < p.d; k += 64) dot = fmaf(Tr<BF16>::to_f32(ap[k]), Tr<BF16>::to_f32(bp[k]), dot);
+        dot = reduce_wave(dot);
+        if (lane == 0) {
+            const float li = p.l[pair * p.Rp + i];
+            p.u[pair * p.Rp + i] = 1.0f / li;
+            p.ediag[pair * p.Rp + i] = __builtin_amdgcn_exp2f((dot - 1.0f) * inv_temp * 1.4426950408889634f);
+            float loss = nce_row_term(li, inv_temp, dot);
+            loss += nce_col_term(c[p.row_offset + i], inv_temp, dot);
+            p.loss_rows[pair * p.rows + i] = loss;
+        }
+    } else if (i < p.Rp) {
+        if (lane == 0) p.u[pair * p.Rp + i] = 0.f;
+    }
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.Cp; j += (int64_t)gridDim.x * 256)
+        p.v[pair * p.Cp + j] = j < p.cols ? 1.0f / c[j] : 0.f;
+}
+
 // W = ct (E (u_i + v_j) - npos [j = off + i]) in place over the tiled E, 8 elements per thread.  The positive's weight is a
 // small difference of O(1) terms (softmax weight minus one): it is formed from the float32 exponential, not from the bf16 one.
 __device__ __forceinline__ void nce_weights_body(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u, const float* v,
@@ -1268,6 +615,44 @@ __global__ __launch_bounds__(256) void nce_weights_dt_kernel(unsigned short* e, 
                                                              float coef, float npos, const float* upstream, const float* temp,
                                                              float min_temp) {
     nce_weights_body(e, e_tiles, m_tiles, u, v, ediag, rows, row_offset, coef * nce_dev_inv_temp(temp, min_temp), npos, upstream);
+}
+
+// multi-view: the weights of pair blockIdx.y over its own E block; u, ediag [P][Rp], v [P][Cp]
+__global__ __launch_bounds__(256) void nce_multi_weights_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
+                                                                const float* v, const float* ediag, int64_t rows, int64_t row_offset,
+                                                                float coef, const float* upstream, const float* temp, float min_temp) {
+    const int64_t pair = blockIdx.y, Rp = m_tiles * BT, Cp = e_tiles * 64;
+    nce_weights_body(e + pair * Rp * Cp, e_tiles, m_tiles, u + pair * Rp, v + pair * Cp, ediag + pair * Rp, rows, row_offset,
+                     coef * nce_dev_inv_temp(temp, min_temp), 2.0f, upstream);
+}
+
+// multi-view: dx_loc = the fixed-order sum of the da slabs [splits][rows][views d] where the view has the a role and 0 where it has
+// none (bit v of da_mask), rounded once; and the zeros of the views of dx_all [cols][views d] that have no b role (db_mask) --
+// the db product stores the others itself.  One thread per 4 elements of dx_loc, then of dx_all.
+__global__ __launch_bounds__(256) void nce_multi_finish_kernel(const float* slabs, int splits, int64_t rows, int64_t cols, int views, int d,
+                                                               unsigned int da_mask, unsigned int db_mask, void* dx_loc, void* dx_all,
+                                                               int out_bf16) {
+    const int64_t pitch4 = (int64_t)views * d / 4, n_loc = rows * pitch4;
+    int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= n_loc + cols * pitch4) return;
+    const bool loc = id < n_loc;
+    if (!loc) id -= n_loc;
+    const int view = (int)((id % pitch4) * 4 / d);
+    f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (loc) {
+        if ((da_mask >> view) & 1u) {
+            s = *reinterpret_cast<const f32x4*>(slabs + 4 * id);
+            for (int k = 1; k < splits; ++k) {
+                const f32x4 t = *reinterpret_cast<const f32x4*>(slabs + (int64_t)k * 4 * n_loc + 4 * id);
+                s[0] += t[0]; s[1] += t[1]; s[2] += t[2]; s[3] += t[3];
+            }
+        }
+    } else if ((db_mask >> view) & 1u) {
+        return;
+    }
+    void* out = loc ? dx_loc : dx_all;
+    if (out_bf16) *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(out) + 4 * id) = u32x2{pack_bf16x2(s[0], s[1]), pack_bf16x2(s[2], s[3])};
+    else *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + 4 * id) = s;
 }
 
 // ---- supervised contrastive loss: the label-aware variants of the three kernels above ----------------------------------
@@ -1753,6 +1138,201 @@ void launch_nce_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d
     // and n_tiles <= 16, so the splits m_tiles n_tiles partials fit in its Cp m_tiles floats); this rank's rows, both directions
     // when sym.  The weights carry every scalar: the epilogues scale nothing.
     launch_grad_products<EPI_OUT, EPI_OUT_TD>(rows, cols, d, NceGemmArgs{}, w.e, w.slabs, w.rowsum_part, dt, a, b, out_bf16, da, db, s);
+}
+
+// ---- multi-view InfoNCE: every pair of views (or every pair with one anchor view) of x [rows][views][d] (include/aecf_hip.h) ----
+
+namespace {
+
+// the pairs in the order of the definition: anchor < 0 every m < n, lexicographic; else (min(k, n), max(k, n)) for n != k, rising
+struct MvPairs {
+    int count;
+    unsigned char m[MV_MAX_PAIRS], n[MV_MAX_PAIRS];
+};
+
+MvPairs mv_pairs(int views, int anchor) {
+    MvPairs t = {};
+    for (int m = 0; m < views; ++m)
+        for (int n = anchor < 0 ? m + 1 : 0; n < views; ++n) {
+            if (anchor >= 0 && (m != anchor || n == anchor)) continue;
+            t.m[t.count] = (unsigned char)(m < n ? m : n);
+            t.n[t.count] = (unsigned char)(m < n ? n : m);
+            ++t.count;
+        }
+    return t;
+}
+
+// workspace carve of the multi-view form: the two-view arrays once per pair, pair after pair, and one set of slabs
+struct MvWs {
+    unsigned short* e;                  // [P][Rp][Cp] bf16, each block tiled as E
+    float* rowsum_part;                 // [P][n_tiles][Rp]
+    float* colsum_part;                 // [P][m_tiles][Cp]
+    float* l;                           // [P][Rp]
+    float* u;                           // [P][Rp]
+    float* v;                           // [P][Cp]
+    float* ediag;                       // [P][Rp]
+    float* slabs;                       // [splits][rows][views][d]
+    size_t bytes;
+};
+
+MvWs mv_carve(void* ws, int64_t rows, int64_t cols, int d, int views, int pairs) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t mt = Rp / BT, nt = Cp / BT;
+    const size_t P = (size_t)pairs;
+    MvWs w;
+    char* p = (char*)ws;
+    size_t off = 0;
+    auto take = [&](size_t n) { char* r = p + off; off += al256(n); return r; };
+    w.e = (unsigned short*)take(P * Rp * Cp * 2);
+    w.rowsum_part = (float*)take(P * nt * Rp * 4);
+    w.colsum_part = (float*)take(P * mt * Cp * 4);
+    w.l = (float*)take(P * Rp * 4);
+    w.u = (float*)take(P * Rp * 4);
+    w.v = (float*)take(P * Cp * 4);
+    w.ediag = (float*)take(P * Rp * 4);
+    w.slabs = (float*)take((size_t)da_splits(Rp, Cp, d) * rows * views * d * 4);
+    w.bytes = off;
+    return w;
+}
+
+// the slots of one role: a view with at least one pair in it, and its partner blocks in pair order.  role_b false: the views
+// that supply local rows (da: the partner is the pair's n view); true: the views that supply keys (db: the partner is its m view)
+void mv_slots(const MvPairs& t, int views, bool role_b, NceMultiProduct& mv, int& slots, unsigned int& mask) {
+    slots = 0;
+    mask = 0;
+    for (int v = 0; v < views; ++v) {
+        unsigned long long f = 0;
+        int k = 0;
+        for (int p = 0; p < t.count; ++p)
+            if ((role_b ? t.n[p] : t.m[p]) == v) f |= (unsigned long long)(p | ((role_b ? t.m[p] : t.n[p]) << 5)) << (8 * k++);
+        if (!k) continue;
+        mv.fields[slots] = f; mv.n_segs[slots] = k; mv.out_view[slots] = v;
+        ++slots;
+        mask |= 1u << v;
+    }
+}
+
+template <int AM, int BM, int EPI, int MAP>
+void launch_multi_product(const NceGemmArgs& a, const NceMultiProduct& mv, unsigned int blocks, hipStream_t s) {
+    auto kern = nce_multi_product_kernel<AM, BM, EPI, MAP>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE);
+    kern<<<dim3(blocks), dim3(512), 2 * STAGE, s>>>(a, mv);
+}
+
+}  // namespace
+
+bool nce_multi_supported(int d, float min_temperature, int64_t cols, int views, int anchor) {
+    return nce_gemm_supported(0, d, min_temperature) && cols <= 0x7fffffff && views >= 2 && views <= MV_MAX_VIEWS && anchor >= -1 &&
+           anchor < views;
+}
+
+size_t nce_multi_workspace_bytes(int64_t rows, int64_t cols, int d, int views, int anchor) {
+    return mv_carve(nullptr, rows, cols, d, views, mv_pairs(views, anchor).count).bytes + 256;
+}
+
+// pass 1 of all pairs: one logits launch, one sums launch; col_sums [P][cols] are this rank's
+void launch_nce_multi_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
+                            const void* x_all, void* workspace, float* col_sums, hipStream_t s) {
+    const MvPairs t = mv_pairs(views, anchor);
+    const MvWs w = mv_carve(workspace, rows, cols, d, views, t.count);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    LogitsLaunch L = logits_args(rows, cols, d, x_loc, x_all);
+    NceGemmArgs& g = L.g;
+    g.lda = g.ldb = 2u * (unsigned)d * (unsigned)views;             // the views lie side by side in a row of x
+    g.a_sm = (int64_t)BT * g.lda;
+    g.e = w.e; g.e_tiles = Cp / 64;
+    g.rowsum_part = w.rowsum_part; g.colsum_part = w.colsum_part;
+    g.temp = dt.t; g.min_temp = dt.min_t;
+    NceMultiLogits mv = {};
+    for (int p = 0; p < t.count; ++p) { mv.m[p] = t.m[p]; mv.n[p] = t.n[p]; }
+    mv.blocks_per_pair = L.blocks; mv.view_bytes = 2u * (unsigned)d;
+    mv.e_stride = Rp * Cp; mv.rowsum_stride = (int64_t)g.n_tiles * Rp; mv.colsum_stride = (int64_t)g.m_tiles * Cp;
+    auto kern = nce_multi_logits_kernel<EPI_EXP_DT>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE);
+    kern<<<dim3(L.blocks * (unsigned)t.count), dim3(512), 2 * STAGE, s>>>(g, mv);
+    nce_multi_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64), (unsigned)t.count), dim3(256), 0, s>>>(
+        w.rowsum_part, w.colsum_part, g.m_tiles, g.n_tiles, rows, cols, w.l, col_sums);
+}
+
+// normalisers and loss rows [P][rows] of all pairs in one launch; col_sums [P][cols]: all ranks' sums
+void launch_nce_multi_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                           const void* x_loc, const void* x_all, const float* col_sums, void* workspace, float* loss_rows,
+                           hipStream_t s) {
+    const MvPairs t = mv_pairs(views, anchor);
+    const MvWs w = mv_carve(workspace, rows, cols, d, views, t.count);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    NceFinArgs f = {};
+    f.a = (const unsigned short*)x_loc; f.b = (const unsigned short*)x_all; f.l = w.l; f.c = col_sums;
+    f.u = w.u; f.v = w.v; f.ediag = w.ediag; f.loss_rows = loss_rows; f.rows = rows; f.cols = cols; f.row_offset = row_offset; f.Rp = Rp; f.Cp = Cp;
+    f.d = d; f.sym = 1; f.temp = dt.t; f.min_temp = dt.min_t;
+    NceMultiFin mv = {};
+    for (int p = 0; p < t.count; ++p) { mv.m[p] = t.m[p]; mv.n[p] = t.n[p]; }
+    mv.views = views;
+    nce_multi_finalize_kernel<<<dim3((unsigned)((Rp + 3) / 4), (unsigned)t.count), dim3(256), 0, s>>>(f, mv);
+}
+
+// gradients: the weights of all pairs in place (one launch), then ONE da launch (every view with the a role; K through all its
+// partner blocks, float32 slabs) and ONE db launch (every view with the b role, stored by the GEMM), then the slab sum, which
+// also writes the zeros of the views without a role.  launch_nce_multi_loss must have run on this workspace.
+void launch_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                            float coef, const void* x_loc, const void* x_all, void* workspace, const float* upstream, int out_bf16,
+                            void* dx_loc, void* dx_all, hipStream_t s) {
+    const MvPairs t = mv_pairs(views, anchor);
+    const MvWs w = mv_carve(workspace, rows, cols, d, views, t.count);
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t chunks = Rp * (Cp / 8);
+    nce_multi_weights_kernel<<<dim3((unsigned)((chunks + 255) / 256), (unsigned)t.count), dim3(256), 0, s>>>(
+        w.e, Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset, coef, upstream, dt.t, dt.min_t);
+    const int n_tiles_d = (d + BT - 1) / BT;
+    const unsigned int pitch = 2u * (unsigned)d * (unsigned)views;
+    unsigned int da_mask = 0, db_mask = 0;
+    int splits = 0;
+    {   // da: launch_da_product's arrangement per view; the partials of the dT sum go where the two-view form puts them
+        NceGemmArgs g = {};
+        g.a = (const char*)w.e; g.lda = 128; g.a_rows = (int)Rp;
+        g.a_sm = (Cp / 64) * (int64_t)32768; g.a_st = 32768;
+        g.b = (const char*)x_all; g.ldb = pitch; g.b_rows = (int)cols; g.b_cbytes = 2 * d;
+        g.m_tiles = (int)(Rp / BT); g.n_tiles = n_tiles_d;
+        g.splits = splits = da_splits(Rp, Cp, d);
+        g.m_valid = (int)rows; g.n_valid = d;
+        g.out = w.slabs; g.ldo = (int64_t)views * d; g.slab_stride = rows * g.ldo; g.out_bf16 = 0;
+        g.tdot_src = (const unsigned short*)x_loc; g.tdot_part = w.rowsum_part;
+        NceMultiProduct mv = {};
+        int slots = 0;
+        mv_slots(t, views, false, mv, slots, da_mask);
+        mv.view_bytes = 2u * (unsigned)d; mv.seg_steps = (int)(Cp / 64); mv.out_elem_bytes = 4;
+        mv.a_stride = Rp * Cp * 2; mv.tdot_stride = (int64_t)g.splits * g.m_tiles * g.n_tiles;
+        const unsigned int units = (unsigned)(g.m_tiles * g.splits);
+        mv.blocks_per_view = g.splits == 8 ? 8u * g.m_tiles * g.n_tiles : ((units + 7) / 8) * 8 * g.n_tiles;
+        const unsigned int blocks = mv.blocks_per_view * (unsigned)slots;
+        if (dt.d_t) {
+            if (g.splits == 8) launch_multi_product<OP_ROW, OP_COL, EPI_OUT_TD, MAP_SPLITX>(g, mv, blocks, s);
+            else launch_multi_product<OP_ROW, OP_COL, EPI_OUT_TD, MAP_UNITS>(g, mv, blocks, s);
+            launch_nce_dtemp(w.rowsum_part, slots * mv.tdot_stride, 1, dt, s);          // views in slot order, then a fixed tree
+        } else {
+            if (g.splits == 8) launch_multi_product<OP_ROW, OP_COL, EPI_OUT, MAP_SPLITX>(g, mv, blocks, s);
+            else launch_multi_product<OP_ROW, OP_COL, EPI_OUT, MAP_UNITS>(g, mv, blocks, s);
+        }
+    }
+    {   // db: launch_db_product's arrangement per view, stored straight into its columns of dx_all
+        NceGemmArgs g = {};
+        g.a = (const char*)w.e; g.lda = 128; g.a_rows = (int)Rp; g.a_cbytes = 0; g.a_sm = Cp / 64;
+        g.b = (const char*)x_loc; g.ldb = pitch; g.b_rows = (int)rows; g.b_cbytes = 2 * d;
+        g.m_tiles = (int)(Cp / BT); g.n_tiles = n_tiles_d;
+        g.splits = 1;
+        g.m_valid = (int)cols; g.n_valid = d;
+        g.out = dx_all; g.ldo = (int64_t)views * d; g.slab_stride = 0; g.out_bf16 = out_bf16;
+        NceMultiProduct mv = {};
+        int slots = 0;
+        mv_slots(t, views, true, mv, slots, db_mask);
+        mv.view_bytes = 2u * (unsigned)d; mv.seg_steps = (int)(Rp / 64); mv.out_elem_bytes = out_bf16 ? 2 : 4;
+        mv.a_stride = Rp * Cp * 2;
+        mv.blocks_per_view = (((unsigned)g.m_tiles + 7) / 8) * 8 * g.n_tiles;
+        launch_multi_product<OP_COLB, OP_COL, EPI_OUT, MAP_UNITS>(g, mv, mv.blocks_per_view * (unsigned)slots, s);
+    }
+    const int64_t n4 = (rows + cols) * ((int64_t)views * d / 4);
+    nce_multi_finish_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s>>>(w.slabs, splits, rows, cols, views, d, da_mask, db_mask,
+                                                                                     dx_loc, dx_all, out_bf16);
 }
 
 // ---- supervised contrastive loss on the same GEMMs, both directions from one block (include/aecf_hip.h) ---------------------

@@ -399,6 +399,168 @@ def info_nce(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch
     return scaled + (total - scaled.detach())
 
 
+MULTIVIEW_MAX_VIEWS = 8     # the pair table of the logits launch holds the 28 pairs of 8 views
+
+
+def multiview_pairs(views: int, anchor: Optional[int] = None):
+    """The pairs (m, n), m < n, of ``multiview_info_nce`` in the order the library walks them: every pair in lexicographic
+    order, or -- with an anchor view k -- (min(k, n), max(k, n)) for every n != k, n rising."""
+    if anchor is None:
+        return [(m, n) for m in range(views) for n in range(m + 1, views)]
+    return [(min(anchor, n), max(anchor, n)) for n in range(views) if n != anchor]
+
+
+class _NceMultiView(torch.autograd.Function):
+    """aecf_nce_multi_pass1 / _loss / _grads: the symmetric InfoNCE of every pair of views of x [rows, M, d] (unit-norm bf16 rows,
+    read in place), modelled on ``_NceSymmetric``.  One logits launch for all P pair blocks; the [P, cols] column sums are the
+    one thing ranks exchange (one all-reduce); the backward runs the weights pass and ONE gradient product per role, whose K loop
+    walks every partner block of a view: a gradient element is one float32 sum over all its partners, rounded once.  The
+    gradient on the gathered rows is this rank's share.  The temperature is a one-element float32 device tensor; the backward
+    returns this rank's share of dL/dT."""
+
+    @staticmethod
+    def forward(ctx, x, x_all, row_offset, temperature, coef, group, min_temperature, anchor):
+        lib = _lib.load()
+        rows, views, d = x.shape
+        cols = x_all.shape[0]
+        dev = x.device
+        xc, xa = x.detach().contiguous(), x_all.detach().contiguous()
+        pairs = len(multiview_pairs(views, None if anchor < 0 else anchor))
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws_bytes = lib.aecf_nce_multi_workspace_bytes(rows, cols, d, views, anchor)
+        if ws_bytes == 0:
+            raise NotImplementedError(f"aecf_amd: multi-view InfoNCE needs d % 64 == 0, 64 <= d <= 4096, 2 to 8 views and fewer than "
+                                      f"2^31 gathered rows; got d = {d}, {views} views, {cols} rows")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        col_sums = torch.empty(pairs, cols, **f32)
+        t = temperature.detach()
+        tp, t_min = _ptr(t), float(min_temperature)
+        _lib.check(lib.aecf_nce_multi_pass1(rows, cols, d, views, anchor, tp, t_min, _ptr(xc), _ptr(xa), _ptr(ws), ws_bytes,
+                                            _ptr(col_sums), _stream()), "aecf_nce_multi_pass1")
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(col_sums, group=group)
+        loss_rows = torch.empty(pairs, rows, **f32)
+        _lib.check(lib.aecf_nce_multi_loss(rows, cols, int(row_offset), d, views, anchor, tp, t_min, _ptr(xc), _ptr(xa), _ptr(col_sums),
+                                           _ptr(ws), ws_bytes, _ptr(loss_rows), _stream()), "aecf_nce_multi_loss")
+        ctx.save_for_backward(xc, xa, ws, t)
+        ctx.meta = (temperature.shape, (rows, cols, int(row_offset), d, views, anchor, float(coef), t_min, ws_bytes))
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = _lib.load()
+        xc, xa, ws, t = ctx.saved_tensors
+        t_shape, (rows, cols, row_offset, d, views, anchor, coef, t_min, ws_bytes) = ctx.meta
+        if getattr(ctx, "_spent", False):
+            raise RuntimeError("aecf_amd: the multi-view InfoNCE backward runs once per forward (it consumes the stored logits)")
+        ctx._spent = True
+        dev = xc.device
+        dx = torch.empty(rows, views, d, dtype=torch.bfloat16, device=dev)
+        dx_all = torch.empty(cols, views, d, dtype=torch.bfloat16, device=dev)
+        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
+        d_t = torch.empty(1, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
+        _lib.check(lib.aecf_nce_multi_grads(rows, cols, row_offset, d, views, anchor, _ptr(t), t_min, coef, _ptr(xc), _ptr(xa), _ptr(ws),
+                                            ws_bytes, _ptr(up), _DTYPES[torch.bfloat16], _ptr(dx), _ptr(dx_all), _ptr(d_t), _stream()),
+                   "aecf_nce_multi_grads")
+        g_t = d_t.reshape(t_shape) if d_t is not None else None
+        return dx, dx_all, None, g_t, None, None, None, None
+
+
+def _multiview_refusal(x: torch.Tensor, cols: int, min_temperature: float, anchor: int) -> Optional[str]:
+    """None where multi-view InfoNCE runs; else the limit that stands against it.  The memory test (P blocks of b_local x b_all
+    bfloat16 and the float32 slabs within 0.6 of the free device memory) is skipped while a graph is being captured."""
+    rows, views, d = x.shape
+    if x.dtype != torch.bfloat16:
+        return f"bfloat16 rows (got {x.dtype})"
+    if d % 64 != 0 or not 64 <= d <= 4096:
+        return f"d % 64 == 0 with 64 <= d <= 4096 (got d = {d})"
+    if not float(min_temperature) >= MIN_TEMPERATURE:
+        return f"min_temperature >= {MIN_TEMPERATURE} (got {min_temperature}): 1 / T is the constant shift of every exponential"
+    need = _lib.load().aecf_nce_multi_workspace_bytes(rows, cols, d, views, anchor)
+    if need == 0:
+        return f"fewer than 2^31 gathered rows (got {cols})"
+    if not _capturing() and need > 0.6 * torch.cuda.mem_get_info(x.device)[0]:
+        return f"a workspace (one b_local x b_all bfloat16 block per pair, {need} bytes here) within 0.6 of the free device memory"
+    return None
+
+
+def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=None, min_temperature: float = MIN_TEMPERATURE,
+                       anchor: Optional[int] = None) -> torch.Tensor:
+    """Symmetric InfoNCE over the pairs of M views, negatives from every rank of ``group``:
+
+        L = (1 / P) * sum over the pairs (m, n) of info_nce(x[:, m], x[:, n], temperature, group, min_temperature)
+
+    ``x``: [b_local, M, d] bfloat16 on a ROCm device, 2 <= M <= 8 -- the layout the fusion pool takes; the views are read where
+    they lie.  A sequence of M [b_local, d] tensors is accepted too: it is stacked once, which costs a copy of every view.
+    ``anchor=None``: every pair m < n, P = M (M - 1) / 2.  ``anchor=k``: the pairs that hold view k (the ImageBind arrangement),
+    P = M - 1.  In pair (m, n), m < n, view m supplies this rank's rows and view n the gathered keys.
+
+    One normalisation launch over all b_local M rows, one all-gather of the normalised block, ONE logits launch for all P pair
+    blocks, one all-reduce of [P, b_all] column sums; in the backward one gradient product per role whose K loop runs through
+    every partner block of a view, so a gradient element is one float32 sum over all its partners, rounded once (a loop of
+    ``info_nce`` rounds every pair's gradient to bfloat16 and adds them afterwards).  ``temperature`` as in ``info_nce``: a
+    float (placed in a device scalar) or a learnable one-element float32 device tensor, read as ``max(T, min_temperature)``
+    with no host read, its gradient formed by the kernels; one temperature and one weight for all pairs.  The return and
+    gradient conventions under data parallel are ``info_nce``'s.  The backward runs once per forward.
+
+    Needs bfloat16, d % 64 == 0 (64 to 4096), ``min_temperature >= 0.025`` and a workspace (P blocks of b_local x b_all
+    bfloat16 plus float32 slabs) within 0.6 of the free device memory (not tested while capturing); otherwise raises
+    NotImplementedError naming the limit -- a loop of ``info_nce`` over the pairs serves such inputs.  No fallback."""
+    if isinstance(x, (list, tuple)):
+        views = list(x)
+        if not all(isinstance(v, torch.Tensor) and v.dim() == 2 for v in views) or any(v.shape != views[0].shape for v in views):
+            raise ValueError("multiview_info_nce expects [b, M, d] or a sequence of [b, d] views of equal shape, got "
+                             f"{[tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__ for v in views]}")
+        if not 2 <= len(views) <= MULTIVIEW_MAX_VIEWS:
+            raise ValueError(f"multiview_info_nce serves 2 to {MULTIVIEW_MAX_VIEWS} views, got {len(views)}")
+        for k, v in enumerate(views):
+            _require_device(v, f"view {k}")
+        x = torch.stack(views, dim=1)
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError("multiview_info_nce expects [b, M, d] or a sequence of [b, d] views of equal shape, got "
+                         f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    b_local, views, d = x.shape
+    if not 2 <= views <= MULTIVIEW_MAX_VIEWS:
+        raise ValueError(f"multiview_info_nce serves 2 to {MULTIVIEW_MAX_VIEWS} views, got {views}")
+    if anchor is not None and not (isinstance(anchor, int) and not isinstance(anchor, bool) and 0 <= anchor < views):
+        raise ValueError(f"multiview_info_nce: anchor must be None or a view index in 0..{views - 1}, got {anchor!r}")
+    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
+        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
+    _require_device(x, "x")
+    k = -1 if anchor is None else int(anchor)
+    rank, world = dp.world_info(group)
+    if world > 1:
+        n = torch.tensor([b_local], device=x.device, dtype=torch.int64)
+        got = [torch.zeros_like(n) for _ in range(world)]
+        torch.distributed.all_gather(got, n, group=group)
+        sizes = [int(v.item()) for v in got]
+        offset, b_all = sum(sizes[:rank]), sum(sizes)
+    else:
+        sizes, offset, b_all = None, 0, b_local
+    refusal = _multiview_refusal(x, b_all, min_temperature, k)
+    if world > 1:                                   # every rank must refuse together (they exchange between the passes)
+        flag = torch.tensor([1 if refusal is None else 0], device=x.device)
+        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
+        if refusal is None and not bool(int(flag.item())):
+            refusal = "the same on every rank (another rank refused it)"
+    if refusal is not None:
+        raise NotImplementedError("aecf_amd: multi-view InfoNCE needs " + refusal + "; a loop of info_nce over the pairs serves "
+                                  "such inputs")
+    t = _temperature_arg(temperature, x, min_temperature)
+    if not isinstance(t, torch.Tensor):
+        t = torch.full((1,), t, dtype=torch.float32, device=x.device)
+    nx = l2_normalize(x.reshape(b_local * views, d)).reshape(b_local, views, d)
+    nx_all = dp.all_gather_rows(nx.reshape(b_local, views * d), group, sizes=sizes).reshape(b_all, views, d) if world > 1 else nx
+    pairs = len(multiview_pairs(views, anchor))
+    share = _NceMultiView.apply(nx, nx_all, offset, t, 0.5 / float(b_all) / float(pairs), group, float(min_temperature), k)
+    if world == 1:
+        return share
+    total = share.detach().clone()
+    torch.distributed.all_reduce(total, group=group)
+    scaled = share * world
+    return scaled + (total - scaled.detach())
+
+
 def _sig_scalar_arg(value, z: torch.Tensor, what: str):
     """``temperature`` / ``bias`` of ``sigmoid_contrastive``: a Python number -> float; a tensor -> itself, checked like
     ``_temperature_arg`` (one float32 element on z's device: the kernels read it there)."""

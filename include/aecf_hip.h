@@ -1022,6 +1022,57 @@ int aecf_supcon_ml_pool_sym_grads(int64_t rows, int64_t cols, int64_t row_offset
                                   void* workspace, size_t workspace_bytes, const float* upstream, int32_t grad_dtype, void* d_a_loc,
                                   void* d_b_loc, void* d_a_all, void* d_b_all, float* d_temperature, void* stream);
 
+/* ---- multi-view InfoNCE, tile-GEMM form (build-defined; the symmetric InfoNCE of aecf_nce_sym_*_dt over several pairs of views) ----
+ * x holds `views` views side by side: x_loc [rows][views][d] are a rank's local rows (global rows row_offset .. row_offset + rows),
+ * x_all [cols][views][d] the gathered ones, unit-norm bf16 rows read IN PLACE with a row pitch of views * d * 2 bytes; x_all may
+ * alias x_loc on one rank.  The pairs, in this order (p = 0 .. P - 1):
+ *   anchor = -1      every (m, n) with m < n, lexicographic: (0,1) (0,2) .. (1,2) ..            P = views (views - 1) / 2
+ *   anchor = k >= 0  (min(k, n), max(k, n)) for every n != k, n rising                         P = views - 1
+ * In pair (m, n) view m supplies the local rows (the a role) and view n the keys (the b role); the positive of local row i is
+ * key row_offset + i.  Every pair is the symmetric InfoNCE of aecf_nce_sym_*_dt on x_loc[:, m] and x_all[:, n], all pairs at ONE
+ * Tc = max(*temperature, min_temperature) and with the SAME coef (the caller folds 1 / P into it):
+ *   pass1: ONE logits launch over the P blocks (the block index selects pair and tile), one sums launch: E_p in the workspace,
+ *          col_sums [P][cols] float32 = this rank's column sums of every pair.
+ *   caller: all-reduce (sum) of col_sums over the ranks (nothing to do on one rank).
+ *   loss:  loss_rows [P][rows], WITHOUT coef; prepares the normalisers of every pair, one launch.
+ *   grads: the weights of all pairs in place (one launch), then
+ *            dx_loc[:, m] = sum over the pairs (m, n) of W_(m,n) x_all[:, n]          [rows][views][d]   the a-role products of view m
+ *            dx_all[:, n] = sum over the pairs (m, n) of W_(m,n)^T x_loc[:, m]        [cols][views][d]   the b-role products of view n
+ *          (dx_all: this rank's share; the shares of the ranks sum to the global gradient).  Each is ONE GEMM launch for all views
+ *          whose K loop runs through every partner block of the view: an element is one float32 sum over all partners, rounded
+ *          ONCE to grad_dtype (float32 or bf16) -- no per-pair stage, no add pass.  A view with no pair in a role is written as
+ *          zeros: every element of both outputs is written on every call.  Everything is multiplied by upstream[0] (a DEVICE
+ *          float32 scalar, NULL = 1); d_temperature (may be NULL) is WRITTEN with dL/dT = -(1/Tc) sum_m sum_i x_loc[i, m] .
+ *          dx_loc[i, m] from the float32 accumulators, views in rising order, fixed order (0 where *temperature <
+ *          min_temperature).  It consumes the stored blocks: it runs once per pass1.
+ * For every pair, col_sums[p] and loss_rows[p] have the bits of aecf_nce_sym_pass1_dt / aecf_nce_sym_loss_dt on contiguous copies
+ * of the two views; with views = 2 every output (dx_loc[:, 0] = da, dx_all[:, 1] = db, dT included) has the bits of
+ * aecf_nce_sym_*_dt at the same coef.
+ * Served: bf16 rows, d % 64 == 0, 64 <= d <= 4096, min_temperature >= 0.025, 2 <= views <= 8, -1 <= anchor < views, rows <= cols,
+ * cols < 2^31.  Workspace, in order, each piece rounded up to 256 bytes, Rp / Cp = rows / cols rounded up to 256, + 256 bytes:
+ *   E [P][Rp][Cp] bf16 (each block in the tiles of the InfoNCE form) | row partials [P][Cp/256][Rp] | column partials
+ *   [P][Rp/256][Cp] | row sums [P][Rp] | 1/l [P][Rp] | 1/c [P][Cp] | the positive's exponential [P][Rp] |
+ *   da slabs [splits][rows][views][d]        (float32 but E; splits: the K split of da = W b, as in the InfoNCE form)
+ * The query answers 0 where the shape is not served.  Caller-owned buffers, a stream argument, no allocation, no synchronisation,
+ * nothing read on the host, no float atomics: the same inputs give the same bits.  Checks before any launch: sizes (rows, cols,
+ * d > 0, cols < 2^31, rows <= cols, min_temperature > 0, 0 <= row_offset, row_offset + rows <= cols, 2 <= views <= 8, -1 <= anchor
+ * < views: AECF_ERR_BAD_DIMS), then d, min_temperature < 0.025 or a grad_dtype other than bf16 / float32 (AECF_ERR_UNSUPPORTED),
+ * then NULL pointers (AECF_ERR_NULL_POINTER; upstream and d_temperature may be NULL), then the workspace size
+ * (AECF_ERR_WORKSPACE). */
+size_t aecf_nce_multi_workspace_bytes(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor);      /* 0: not served */
+int aecf_nce_multi_pass1(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor, const float* temperature,
+                         float min_temperature, const void* x_loc, const void* x_all, void* workspace, size_t workspace_bytes,
+                         float* col_sums /* [P][cols] */, void* stream);
+int aecf_nce_multi_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                        const float* temperature, float min_temperature, const void* x_loc, const void* x_all,
+                        const float* col_sums /* summed over ranks */, void* workspace, size_t workspace_bytes,
+                        float* loss_rows /* [P][rows] */, void* stream);
+int aecf_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                         const float* temperature, float min_temperature, float coef, const void* x_loc, const void* x_all,
+                         void* workspace, size_t workspace_bytes, const float* upstream, int32_t grad_dtype,
+                         void* dx_loc /* [rows][views][d] */, void* dx_all /* [cols][views][d], this rank's share */,
+                         float* d_temperature, void* stream);
+
 /* ---- retrieval ranks of the contrastive views (build-defined like the contrastive terms they evaluate: the reference has no
  * contrastive term and no retrieval evaluation, so there are no reference lines to cite) ----
  * Local rows a [rows,d] (global indices row_offset .. row_offset + rows) against all gathered rows b [cols,d] of the other view,
