@@ -233,6 +233,21 @@ _SYMBOLS = [
     ("aecf_nce_multi_grads", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
       c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # multi-view InfoNCE with missing views: presence bytes per row, per-pair coefficients formed on the device
+    ("aecf_nce_multi_masked_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32]),
+    ("aecf_nce_multi_masked_pair_coef", c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    ("aecf_nce_multi_masked_pass1", c_int,
+     [c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+      c_void_p, c_void_p]),
+    ("aecf_nce_multi_masked_loss", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("aecf_nce_multi_masked_grads", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("aecf_l2norm_masked_forward", c_int,
+     [c_int64, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("aecf_l2norm_masked_backward", c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # pooled supervised contrastive loss on the tile GEMMs: NT-Xent's three blocks with labels, one all-reduce of [3][cols]
     ("aecf_supcon_pool_sym_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32]),
     ("aecf_supcon_pool_sym_pass1", c_int,

@@ -1124,6 +1124,65 @@ int aecf_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t
     return launch_status();
 }
 
+// ---- multi-view InfoNCE with missing views (include/aecf_hip.h, "multi-view InfoNCE with missing views")
+
+size_t aecf_nce_multi_masked_workspace_bytes(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor) {
+    return aecf_nce_multi_workspace_bytes(rows, cols, d, views, anchor);
+}
+
+int aecf_nce_multi_masked_pair_coef(int64_t cols, int32_t views, int32_t anchor, const uint8_t* pres_all, float* pair_coef,
+                                    void* stream) {
+    if (cols <= 0 || cols > 0x7fffffff || views < 2 || views > 8 || anchor < -1 || anchor >= views) return AECF_ERR_BAD_DIMS;
+    if (!pres_all || !pair_coef) return AECF_ERR_NULL_POINTER;
+    launch_nce_multi_pair_coef(cols, views, anchor, pres_all, pair_coef, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_nce_multi_masked_pass1(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor, const float* temperature,
+                                float min_temperature, const void* x_loc, const void* x_all, const uint8_t* pres_loc,
+                                const uint8_t* pres_all, void* workspace, size_t workspace_bytes, float* col_sums, void* stream) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, min_temperature)) return AECF_ERR_BAD_DIMS;
+    if (!nce_multi_supported(d, min_temperature, cols, views, anchor)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !x_loc || !x_all || !pres_loc || !pres_all || !workspace || !col_sums) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_multi_workspace_bytes(rows, cols, d, views, anchor)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_nce_multi_masked_pass1(rows, cols, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, workspace, col_sums,
+                                  (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_nce_multi_masked_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                               const float* temperature, float min_temperature, const void* x_loc, const void* x_all,
+                               const uint8_t* pres_loc, const uint8_t* pres_all, const float* col_sums, void* workspace,
+                               size_t workspace_bytes, float* loss_rows, void* stream) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, min_temperature)) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!nce_multi_supported(d, min_temperature, cols, views, anchor)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !x_loc || !x_all || !pres_loc || !pres_all || !col_sums || !workspace || !loss_rows) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_multi_workspace_bytes(rows, cols, d, views, anchor)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_nce_multi_masked_loss(rows, cols, row_offset, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, col_sums, workspace,
+                                 loss_rows, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_nce_multi_masked_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                                const float* temperature, float min_temperature, const float* pair_coef, const void* x_loc,
+                                const void* x_all, const uint8_t* pres_loc, void* workspace, size_t workspace_bytes,
+                                const float* upstream, int32_t grad_dtype, void* dx_loc, void* dx_all, float* d_temperature,
+                                void* stream) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, min_temperature)) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!nce_multi_supported(d, min_temperature, cols, views, anchor)) return AECF_ERR_UNSUPPORTED;
+    if (grad_dtype != AECF_BF16 && grad_dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !pair_coef || !x_loc || !x_all || !pres_loc || !workspace || !dx_loc || !dx_all) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_multi_workspace_bytes(rows, cols, d, views, anchor)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    launch_nce_multi_masked_grads(rows, cols, row_offset, d, views, anchor, dt, pair_coef, pres_loc, x_loc, x_all, workspace, upstream,
+                                  grad_dtype == AECF_BF16 ? 1 : 0, dx_loc, dx_all, (hipStream_t)stream);
+    return launch_status();
+}
+
 // ---- pooled supervised contrastive loss on the tile GEMMs (include/aecf_hip.h, "pooled supervised contrastive loss, tile-GEMM form")
 
 size_t aecf_supcon_pool_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {
@@ -1525,6 +1584,24 @@ int aecf_l2norm_backward(int64_t n, int32_t d, int32_t dtype, const void* zn, co
     if (dtype != AECF_BF16 && dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
     if (!zn || !inv_norm || !dzn || !dz) return AECF_ERR_NULL_POINTER;
     launch_l2norm_bwd(dtype, n, d, zn, inv_norm, dzn, dz, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_l2norm_masked_forward(int64_t n, int32_t d, int32_t views, int32_t dtype, float eps, const void* z, const uint8_t* mask,
+                               void* zn, float* inv_norm, uint8_t* presence, void* stream) {
+    if (n <= 0 || d <= 0 || views < 1 || views > 8 || n % views != 0) return AECF_ERR_BAD_DIMS;
+    if (dtype != AECF_BF16 && dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!z || !mask || !zn || !inv_norm) return AECF_ERR_NULL_POINTER;
+    launch_l2norm_masked_fwd(dtype, n, d, views, eps, z, mask, zn, inv_norm, presence, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_l2norm_masked_backward(int64_t n, int32_t d, int32_t dtype, const void* zn, const float* inv_norm, const float* dzn,
+                                const uint8_t* mask, void* dz, void* stream) {
+    if (n <= 0 || d <= 0) return AECF_ERR_BAD_DIMS;
+    if (dtype != AECF_BF16 && dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!zn || !inv_norm || !dzn || !mask || !dz) return AECF_ERR_NULL_POINTER;
+    launch_l2norm_masked_bwd(dtype, n, d, zn, inv_norm, dzn, mask, dz, (hipStream_t)stream);
     return launch_status();
 }
 

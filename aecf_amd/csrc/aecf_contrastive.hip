@@ -44,6 +44,61 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(int64_t n, int d, const
         dz[row * d + e] = X::from_f32((dzn[row * d + e] - X::to_f32(zn[row * d + e]) * dot) * inv);
 }
 
+// l2norm_fwd_kernel over the n = rows * views slots of x [rows][views][d] with a padding mask [n] (non-zero: the slot is absent).
+// A present slot is l2norm_fwd_kernel's, operation for operation.  An absent slot is not read: its row is written as +0 and its
+// inverse norm as 0, whatever it holds (NaN, inf), so that a zero weight times its key is a zero in the gradient products.  The
+// wave of a row's first slot also packs the row's presence byte (bit v: view v present; pres may be NULL).
+template <typename T>
+__global__ __launch_bounds__(256) void l2norm_masked_fwd_kernel(int64_t n, int d, int views, float eps,
+                                                                const typename Tr<T>::elem* __restrict__ z,
+                                                                const unsigned char* __restrict__ mask,
+                                                                typename Tr<T>::elem* __restrict__ zn, float* __restrict__ inv_norm,
+                                                                unsigned char* __restrict__ pres) {
+    using X = Tr<T>;
+    const int64_t row = (int64_t)blockIdx.x * 4 + wave_id();
+    if (row >= n) return;
+    const int lane = lane_id();
+    const int64_t first = row / views;
+    if (pres && first * views == row) {                         // wave-uniform: lane v reads the byte of view v, one vote packs them
+        const bool here = lane < views && mask[row + (lane < views ? lane : 0)] == 0;
+        const unsigned long long bits = __ballot(here);
+        if (lane == 0) pres[first] = (unsigned char)bits;
+    }
+    if (mask[row]) {
+        for (int e = lane; e < d; e += 64) zn[row * d + e] = X::from_f32(0.f);
+        if (lane == 0) inv_norm[row] = 0.f;
+        return;
+    }
+    float ss = 0.f;
+    for (int e = lane; e < d; e += 64) { const float v = X::to_f32(z[row * d + e]); ss = fmaf(v, v, ss); }
+    ss = reduce_wave(ss);
+    const float inv = 1.0f / fmaxf(sqrtf(ss), eps);
+    for (int e = lane; e < d; e += 64) zn[row * d + e] = X::from_f32(X::to_f32(z[row * d + e]) * inv);
+    if (lane == 0) inv_norm[row] = inv;
+}
+
+// l2norm_bwd_kernel with the same mask: the gradient of an absent slot is written as +0, whatever arrives
+template <typename T>
+__global__ __launch_bounds__(256) void l2norm_masked_bwd_kernel(int64_t n, int d, const typename Tr<T>::elem* __restrict__ zn,
+                                                                const float* __restrict__ inv_norm, const float* __restrict__ dzn,
+                                                                const unsigned char* __restrict__ mask,
+                                                                typename Tr<T>::elem* __restrict__ dz) {
+    using X = Tr<T>;
+    const int64_t row = (int64_t)blockIdx.x * 4 + wave_id();
+    if (row >= n) return;
+    const int lane = lane_id();
+    if (mask[row]) {
+        for (int e = lane; e < d; e += 64) dz[row * d + e] = X::from_f32(0.f);
+        return;
+    }
+    float dot = 0.f;
+    for (int e = lane; e < d; e += 64) dot = fmaf(dzn[row * d + e], X::to_f32(zn[row * d + e]), dot);
+    dot = reduce_wave(dot);
+    const float inv = inv_norm[row];
+    for (int e = lane; e < d; e += 64)
+        dz[row * d + e] = X::from_f32((dzn[row * d + e] - X::to_f32(zn[row * d + e]) * dot) * inv);
+}
+
 __device__ __forceinline__ float block_reduce_max(float v, float* red) {
     v = fmaxf(v, __shfl_xor(v, 1, 64)); v = fmaxf(v, __shfl_xor(v, 2, 64)); v = fmaxf(v, __shfl_xor(v, 4, 64));
     v = fmaxf(v, __shfl_xor(v, 8, 64)); v = fmaxf(v, __shfl_xor(v, 16, 64)); v = fmaxf(v, __shfl_xor(v, 32, 64));
@@ -129,6 +184,22 @@ void launch_l2norm_fwd(int dtype, int64_t n, int d, float eps, const void* z, vo
     dim3 grid((unsigned)((n + 3) / 4)), block(256);
     if (dtype == 0) l2norm_fwd_kernel<BF16><<<grid, block, 0, s>>>(n, d, eps, (const unsigned short*)z, (unsigned short*)zn, inv_norm);
     else l2norm_fwd_kernel<F32><<<grid, block, 0, s>>>(n, d, eps, (const float*)z, (float*)zn, inv_norm);
+}
+
+void launch_l2norm_masked_fwd(int dtype, int64_t n, int d, int views, float eps, const void* z, const unsigned char* mask, void* zn,
+                              float* inv_norm, unsigned char* pres, hipStream_t s) {
+    dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    if (dtype == 0)
+        l2norm_masked_fwd_kernel<BF16><<<grid, block, 0, s>>>(n, d, views, eps, (const unsigned short*)z, mask, (unsigned short*)zn, inv_norm, pres);
+    else l2norm_masked_fwd_kernel<F32><<<grid, block, 0, s>>>(n, d, views, eps, (const float*)z, mask, (float*)zn, inv_norm, pres);
+}
+
+void launch_l2norm_masked_bwd(int dtype, int64_t n, int d, const void* zn, const float* inv_norm, const float* dzn,
+                              const unsigned char* mask, void* dz, hipStream_t s) {
+    dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    if (dtype == 0)
+        l2norm_masked_bwd_kernel<BF16><<<grid, block, 0, s>>>(n, d, (const unsigned short*)zn, inv_norm, dzn, mask, (unsigned short*)dz);
+    else l2norm_masked_bwd_kernel<F32><<<grid, block, 0, s>>>(n, d, (const float*)zn, inv_norm, dzn, mask, (float*)dz);
 }
 
 void launch_l2norm_bwd(int dtype, int64_t n, int d, const void* zn, const float* inv_norm, const float* dzn, void* dz,

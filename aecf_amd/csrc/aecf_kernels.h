@@ -257,6 +257,13 @@ void launch_nce_dtemp(const float* part, int64_t n, int64_t stride, const NceDev
 void launch_l2norm_fwd(int dtype, int64_t n, int d, float eps, const void* z, void* zn, float* inv_norm, hipStream_t s);
 void launch_l2norm_bwd(int dtype, int64_t n, int d, const void* zn, const float* inv_norm, const float* dzn, void* dz,
                        hipStream_t s);
+// the same over the n = rows * views slots of [rows][views][d] with a padding mask [n] (non-zero: absent): an absent slot comes out
+// as a row of +0 with inverse norm 0 (forward) and a gradient of +0 (backward) whatever it holds; pres [n / views] (may be NULL)
+// receives the presence byte of every row, bit v = view v present
+void launch_l2norm_masked_fwd(int dtype, int64_t n, int d, int views, float eps, const void* z, const unsigned char* mask, void* zn,
+                              float* inv_norm, unsigned char* pres, hipStream_t s);
+void launch_l2norm_masked_bwd(int dtype, int64_t n, int d, const void* zn, const float* inv_norm, const float* dzn,
+                              const unsigned char* mask, void* dz, hipStream_t s);
 // per local row i: logits = S[i,:] * inv_temp; loss_rows[i] = logsumexp - logits[row_offset + i];
 // G[i,:] = (softmax - onehot) * coef * inv_temp   (dtype)
 // dt != NULL: inv_temp comes from the device; with dt->d_t, the rows' sums_j G_ij S_ij go to tdot_scratch [rows] and d_t is
@@ -376,6 +383,19 @@ void launch_nce_multi_loss(int64_t rows, int64_t cols, int64_t row_offset, int d
 void launch_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
                             float coef, const void* x_loc, const void* x_all, void* workspace, const float* upstream, int out_bf16,
                             void* dx_loc, void* dx_all, hipStream_t s);
+// The same with missing views: pres_loc [rows] (by the local row) / pres_all [cols] (by the global column) hold one byte per row,
+// bit v = view v present; pair p runs over the rows that hold both its views, with pair_coef[p] = 0.5 / n_p / P' from
+// launch_nce_multi_pair_coef (one small launch over pres_all).  The workspace is nce_multi_workspace_bytes'.
+void launch_nce_multi_pair_coef(int64_t cols, int views, int anchor, const unsigned char* pres_all, float* pair_coef, hipStream_t s);
+void launch_nce_multi_masked_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
+                                   const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all, void* workspace,
+                                   float* col_sums, hipStream_t s);
+void launch_nce_multi_masked_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                                  const void* x_loc, const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all,
+                                  const float* col_sums, void* workspace, float* loss_rows, hipStream_t s);
+void launch_nce_multi_masked_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                                   const float* pair_coef, const unsigned char* pres_loc, const void* x_loc, const void* x_all,
+                                   void* workspace, const float* upstream, int out_bf16, void* dx_loc, void* dx_all, hipStream_t s);
 
 // Pooled supervised contrastive loss on the tile GEMMs (aecf_nce_gemm.hip): NT-Xent's three blocks with the label statistics of the
 // supervised loss -- X runs EPI_SUP, Y and Z EPI_SUP_SELF (rows only, the anchor excluded by index).  col_stats [3][cols] (X's column

@@ -142,6 +142,22 @@
 // division in a step (aecf_nce_gemm_body.h).  dT comes from the EPI_OUT_TD partials of all da slots in one nce_dtemp_kernel, and
 // nce_multi_finish_kernel sums the slabs into dx_loc and writes the zeros of the views that have no role.  With views = 2 the
 // three calls give the bits of aecf_nce_sym_*_dt.
+//
+// Multi-view InfoNCE with missing views (aecf_nce_multi_masked_pair_coef / _pass1 / _loss / _grads) is that form where a row may lack
+// views: one presence byte per row (bit v: view v present; pres_loc by the local row, pres_all by the global column), and pair
+// (m, n) runs over V_p, the rows that hold both bits, on both sides.  The logits pass is a further epilogue on
+// nce_multi_logits_kernel, EPI_EXP_MASK: each of the block's 512 threads loads one of its 256 row bytes or 256 column bytes (the
+// way EPI_SETS_* load class words), the flags go to LDS and one vote tells the block whether all 512 hold the pair -- then it
+// runs EPI_EXP_DT's tile, bit for bit; otherwise it takes the block-uniform branch of the ragged edge with the flags in place of
+// the `iok` / `j < n_valid` selects, so E = 0 in the stored tile, the row sum and the column sum wherever the row or the column
+// is outside V_p -- by a select on the byte, never by value.  nce_multi_sums_kernel serves unchanged (a zero adds nothing).
+// nce_multi_pair_coef_kernel counts every n_p from pres_all with integers and writes pair_coef[p] = 0.5 / n_p / P' (float64,
+// rounded once; 0 for an empty pair; P' = the pairs that have a row): nothing is read on the host.  The masked finalize kernel
+// gives a row outside V_p u = 0, ediag = 0 and a loss row of 0 and a column outside V_p v = 0 -- no log of an empty sum, no 1 / 0;
+// the masked weights kernel takes coef from pair_coef[blockIdx.y] and applies the partner term to the rows of V_p alone.  The
+// gradient products (nce_multi_product_kernel), nce_dtemp_kernel and nce_multi_finish_kernel are reused as they are: an excluded
+// weight is a zero, and the caller's normalised rows hold zeros in the absent slots (aecf_l2norm_masked_forward), so 0 * key = 0.
+// No K loop is skipped: a masked pair costs a full pair (a compacting form is not built).
 #include <math.h>
 #include <type_traits>
 
@@ -164,7 +180,7 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // sum of the raw accumulators of the elements that match by label (the partner and the padding excluded)
 enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8,
        EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11, EPI_EXP_SELF = 12, EPI_SUP_SELF = 13,
-       EPI_SETS_OV_SELF = 14, EPI_SETS_JAC_SELF = 15 };
+       EPI_SETS_OV_SELF = 14, EPI_SETS_JAC_SELF = 15, EPI_EXP_MASK = 16 };
 // EPI_SETS_OV / EPI_SETS_JAC (multi-label contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the
 // float32 sums of w and of w * raw accumulator, w the overlap / Jaccard weight of the two class sets (partner and padding excluded)
 constexpr bool epi_is_sets(int epi) { return epi == EPI_SETS_OV || epi == EPI_SETS_JAC; }
@@ -181,6 +197,10 @@ constexpr bool epi_is_sets_self(int epi) { return epi == EPI_SETS_OV_SELF || epi
 constexpr bool epi_has_sets(int epi) { return epi_is_sets(epi) || epi_is_sets_self(epi); }    // the class words are staged in LDS
 constexpr bool epi_is_self(int epi) { return epi == EPI_EXP_SELF || epi == EPI_SUP_SELF || epi_is_sets_self(epi); }
 constexpr bool epi_has_labels(int epi) { return epi == EPI_SUP || epi == EPI_SUP_SELF; }
+// EPI_EXP_MASK (multi-view InfoNCE with missing views, logits pass): EPI_EXP_DT with E = 0 -- in the stored tile, the row sum and
+// the column sum -- wherever the row or the column lacks a view of the block's pair: pres_row / pres_col hold one byte per row /
+// column (bit v = view v present), pres_need the two bits of the pair.  Excluded by a select on the byte, never by value.  A block
+// whose 256 rows and 256 columns all hold both views runs EPI_EXP_DT's path; the others take the branch of the ragged edge.
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -238,6 +258,10 @@ struct NceGemmArgs {
     float* colsx_part;                  // [m_tiles][n_tiles 256]
     // EPI_SETS_OV / EPI_SETS_JAC: lab_row / lab_col hold the uint64 class sets of the rows / columns (bit c = class c), the four
     // partials above the sums of w and of w * accumulator
+    // EPI_EXP_MASK (also reads temp / min_temp and writes E and its sums as EPI_EXP_DT)
+    const unsigned char* pres_row;      // [m_valid]  presence byte of output row i (bit v: view v present)
+    const unsigned char* pres_col;      // [n_valid]  presence byte of output column j
+    unsigned int pres_need;             // the bits a row and a column must both hold: the two views of the pair
 };
 
 // The match by label of the supervised contrastive loss: the same non-negative class, all 64 bits compared.  The ONE place that
@@ -405,6 +429,7 @@ __global__ __launch_bounds__(512, 2) void nce_multi_logits_kernel(NceGemmArgs p,
     p.e += pair * mv.e_stride;
     p.rowsum_part += pair * mv.rowsum_stride;
     p.colsum_part += pair * mv.colsum_stride;
+    if (EPI == EPI_EXP_MASK) p.pres_need = (1u << mv.m[pair]) | (1u << mv.n[pair]);
     constexpr int AM = OP_ROW, BM = OP_ROW, MAP = MAP_2D;
     constexpr bool MULTI = false;
     const unsigned int vblock = blockIdx.x - pair * mv.blocks_per_pair;
@@ -624,6 +649,107 @@ __global__ __launch_bounds__(256) void nce_multi_weights_kernel(unsigned short* 
     const int64_t pair = blockIdx.y, Rp = m_tiles * BT, Cp = e_tiles * 64;
     nce_weights_body(e + pair * Rp * Cp, e_tiles, m_tiles, u + pair * Rp, v + pair * Cp, ediag + pair * Rp, rows, row_offset,
                      coef * nce_dev_inv_temp(temp, min_temp), 2.0f, upstream);
+}
+
+// ---- multi-view InfoNCE with missing views: the small kernels around the EPI_EXP_MASK logits pass.  A presence byte per row
+// (bit v: view v present); pair p = (m, n) counts the rows that hold both bits -- V_p, n_p of them over all ranks.
+
+// pair_coef[p] = 0.5 / n_p / P' in float32 (formed in float64 and rounded once, as the host forms the unmasked coef), 0 where
+// n_p = 0; P' = the pairs with n_p > 0.  One block: an integer histogram of the 256 byte values of pres_all (integer atomics in
+// LDS: the counts do not depend on the order), then thread p sums the bins that hold both bits of pair p.
+__global__ __launch_bounds__(256) void nce_multi_pair_coef_kernel(const unsigned char* pres_all, int64_t cols, NceMultiFin mv, int pairs,
+                                                                  float* pair_coef) {
+    __shared__ int hist[256];
+    __shared__ int n_p[MV_MAX_PAIRS];
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    for (int64_t j = threadIdx.x; j < cols; j += 256) atomicAdd(&hist[pres_all[j]], 1);
+    __syncthreads();
+    if ((int)threadIdx.x < pairs) {
+        const unsigned int need = (1u << mv.m[threadIdx.x]) | (1u << mv.n[threadIdx.x]);
+        int n = 0;
+        for (unsigned int b = 0; b < 256; ++b) n += (b & need) == need ? hist[b] : 0;
+        n_p[threadIdx.x] = n;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < pairs) {
+        int live = 0;
+        for (int q = 0; q < pairs; ++q) live += n_p[q] > 0 ? 1 : 0;
+        const int n = n_p[threadIdx.x];
+        pair_coef[threadIdx.x] = n > 0 ? (float)(0.5 / (double)n / (double)live) : 0.f;
+    }
+}
+
+// nce_multi_finalize_kernel with the presence bytes: a local row outside V_p gets u = 0, ediag = 0 and a loss row of 0 (no log of
+// an empty sum, no 1 / 0, and its slots of x are not read); a column outside V_p gets v = 0.  A row of V_p is the unmasked kernel's,
+// operation for operation.  pres_loc [rows] by the local row, pres_all [cols] by the global column.
+__global__ __launch_bounds__(256) void nce_multi_masked_finalize_kernel(NceFinArgs p, NceMultiFin mv, const unsigned char* pres_loc,
+                                                                        const unsigned char* pres_all) {
+    const int64_t pair = blockIdx.y, ld = (int64_t)mv.views * p.d;
+    const unsigned int need = (1u << mv.m[pair]) | (1u << mv.n[pair]);
+    const float inv_temp = nce_dev_inv_temp(p.temp, p.min_temp);
+    const float* c = p.c + pair * p.cols;
+    const int lane = lane_id();
+    const int64_t i = (int64_t)blockIdx.x * 4 + wave_id();
+    if (i < p.rows && (pres_loc[i] & need) == need) {
+        const unsigned short* ap = p.a + i * ld + mv.m[pair] * p.d;
+        const unsigned short* bp = p.b + (p.row_offset + i) * ld + mv.n[pair] * p.d;
+        float dot = 0.f;
+        for (int k = lane; k < p.d; k += 64) dot = fmaf(Tr<BF16>::to_f32(ap[k]), Tr<BF16>::to_f32(bp[k]), dot);
+        dot = reduce_wave(dot);
+        if (lane == 0) {
+            const float li = p.l[pair * p.Rp + i];
+            p.u[pair * p.Rp + i] = 1.0f / li;
+            p.ediag[pair * p.Rp + i] = __builtin_amdgcn_exp2f((dot - 1.0f) * inv_temp * 1.4426950408889634f);
+            float loss = nce_row_term(li, inv_temp, dot);
+            loss += nce_col_term(c[p.row_offset + i], inv_temp, dot);
+            p.loss_rows[pair * p.rows + i] = loss;
+        }
+    } else if (i < p.Rp) {
+        if (lane == 0) {
+            p.u[pair * p.Rp + i] = 0.f;
+            p.ediag[pair * p.Rp + i] = 0.f;
+            if (i < p.rows) p.loss_rows[pair * p.rows + i] = 0.f;
+        }
+    }
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.Cp; j += (int64_t)gridDim.x * 256)
+        p.v[pair * p.Cp + j] = (j < p.cols && (pres_all[j] & need) == need) ? 1.0f / c[j] : 0.f;
+}
+
+// nce_multi_weights_kernel with the presence bytes: coef of pair blockIdx.y from pair_coef (0 for an empty pair: its block comes
+// out as zeros), and the partner term -2 [j = off + i] for the rows of V_p alone -- elsewhere E = 0 and u = 0 give W = 0.  The
+// arithmetic of a row of V_p is nce_weights_body's.
+__global__ __launch_bounds__(256) void nce_multi_masked_weights_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
+                                                                       const float* v, const float* ediag, int64_t rows,
+                                                                       int64_t row_offset, const float* pair_coef, const NceMultiFin mv,
+                                                                       const unsigned char* pres_loc, const float* upstream,
+                                                                       const float* temp, float min_temp) {
+    const int64_t pair = blockIdx.y, Rp = m_tiles * BT, Cp = e_tiles * 64;
+    const unsigned int need = (1u << mv.m[pair]) | (1u << mv.n[pair]);
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;         // 16-byte chunk: 2048 per tile, 8 per tile row
+    if (id >= m_tiles * e_tiles * 2048) return;
+    e += pair * Rp * Cp; u += pair * Rp; v += pair * Cp; ediag += pair * Rp;
+    float ct = pair_coef[pair] * nce_dev_inv_temp(temp, min_temp);
+    const int64_t tile = id >> 11;
+    const int within = (int)(id & 2047);
+    const int64_t i = (tile / e_tiles) * BT + (within >> 3), j0 = (tile % e_tiles) * 64 + 8 * (within & 7);
+    u32x4* ptr = reinterpret_cast<u32x4*>(e) + id;
+    const u32x4 raw = *ptr;
+    const float ui = u[i];
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(v + j0), v1 = *reinterpret_cast<const f32x4*>(v + j0 + 4);
+    float x[8];
+    Tr<BF16>::unpack(raw, x);
+    const float vv[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    const bool in_pair = i < rows && (pres_loc[i < rows ? i : 0] & need) == need;
+    const int64_t jp = in_pair ? row_offset + i - j0 : -1;
+    if (upstream) ct *= upstream[0];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float wv = x[k] * (ui + vv[k]);
+        if (jp == k) wv = ediag[i] * (ui + vv[k]) - 2.0f;
+        x[k] = ct * wv;
+    }
+    *ptr = Tr<BF16>::pack(x);
 }
 
 // multi-view: dx_loc = the fixed-order sum of the da slabs [splits][rows][views d] where the view has the a role and 0 where it has
@@ -1230,9 +1356,11 @@ size_t nce_multi_workspace_bytes(int64_t rows, int64_t cols, int d, int views, i
     return mv_carve(nullptr, rows, cols, d, views, mv_pairs(views, anchor).count).bytes + 256;
 }
 
-// pass 1 of all pairs: one logits launch, one sums launch; col_sums [P][cols] are this rank's
-void launch_nce_multi_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
-                            const void* x_all, void* workspace, float* col_sums, hipStream_t s) {
+namespace {
+// pass 1 of all pairs: one logits launch, one sums launch; col_sums [P][cols] are this rank's.  pres_loc / pres_all non-NULL: the
+// form with missing views (EPI_EXP_MASK); the sums kernel serves both -- an excluded element is an exact zero in every partial
+void mv_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc, const void* x_all,
+              const unsigned char* pres_loc, const unsigned char* pres_all, void* workspace, float* col_sums, hipStream_t s) {
     const MvPairs t = mv_pairs(views, anchor);
     const MvWs w = mv_carve(workspace, rows, cols, d, views, t.count);
     const int64_t Rp = up256(rows), Cp = up256(cols);
@@ -1247,17 +1375,40 @@ void launch_nce_multi_pass1(int64_t rows, int64_t cols, int d, int views, int an
     for (int p = 0; p < t.count; ++p) { mv.m[p] = t.m[p]; mv.n[p] = t.n[p]; }
     mv.blocks_per_pair = L.blocks; mv.view_bytes = 2u * (unsigned)d;
     mv.e_stride = Rp * Cp; mv.rowsum_stride = (int64_t)g.n_tiles * Rp; mv.colsum_stride = (int64_t)g.m_tiles * Cp;
-    auto kern = nce_multi_logits_kernel<EPI_EXP_DT>;
+    g.pres_row = pres_loc; g.pres_col = pres_all;
+    auto kern = pres_loc ? nce_multi_logits_kernel<EPI_EXP_MASK> : nce_multi_logits_kernel<EPI_EXP_DT>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE);
     kern<<<dim3(L.blocks * (unsigned)t.count), dim3(512), 2 * STAGE, s>>>(g, mv);
     nce_multi_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64), (unsigned)t.count), dim3(256), 0, s>>>(
         w.rowsum_part, w.colsum_part, g.m_tiles, g.n_tiles, rows, cols, w.l, col_sums);
 }
+}  // namespace
 
+void launch_nce_multi_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
+                            const void* x_all, void* workspace, float* col_sums, hipStream_t s) {
+    mv_pass1(rows, cols, d, views, anchor, dt, x_loc, x_all, nullptr, nullptr, workspace, col_sums, s);
+}
+
+void launch_nce_multi_masked_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
+                                   const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all, void* workspace,
+                                   float* col_sums, hipStream_t s) {
+    mv_pass1(rows, cols, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, workspace, col_sums, s);
+}
+
+// pair_coef [P] of the form with missing views from the gathered presence bytes: one small launch, nothing read on the host
+void launch_nce_multi_pair_coef(int64_t cols, int views, int anchor, const unsigned char* pres_all, float* pair_coef, hipStream_t s) {
+    const MvPairs t = mv_pairs(views, anchor);
+    NceMultiFin mv = {};
+    for (int p = 0; p < t.count; ++p) { mv.m[p] = t.m[p]; mv.n[p] = t.n[p]; }
+    mv.views = views;
+    nce_multi_pair_coef_kernel<<<dim3(1), dim3(256), 0, s>>>(pres_all, cols, mv, t.count, pair_coef);
+}
+
+namespace {
 // normalisers and loss rows [P][rows] of all pairs in one launch; col_sums [P][cols]: all ranks' sums
-void launch_nce_multi_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
-                           const void* x_loc, const void* x_all, const float* col_sums, void* workspace, float* loss_rows,
-                           hipStream_t s) {
+void mv_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
+             const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all, const float* col_sums, void* workspace,
+             float* loss_rows, hipStream_t s) {
     const MvPairs t = mv_pairs(views, anchor);
     const MvWs w = mv_carve(workspace, rows, cols, d, views, t.count);
     const int64_t Rp = up256(rows), Cp = up256(cols);
@@ -1268,21 +1419,48 @@ void launch_nce_multi_loss(int64_t rows, int64_t cols, int64_t row_offset, int d
     NceMultiFin mv = {};
     for (int p = 0; p < t.count; ++p) { mv.m[p] = t.m[p]; mv.n[p] = t.n[p]; }
     mv.views = views;
-    nce_multi_finalize_kernel<<<dim3((unsigned)((Rp + 3) / 4), (unsigned)t.count), dim3(256), 0, s>>>(f, mv);
+    const dim3 grid((unsigned)((Rp + 3) / 4), (unsigned)t.count);
+    if (pres_loc) nce_multi_masked_finalize_kernel<<<grid, dim3(256), 0, s>>>(f, mv, pres_loc, pres_all);
+    else nce_multi_finalize_kernel<<<grid, dim3(256), 0, s>>>(f, mv);
+}
+}  // namespace
+
+void launch_nce_multi_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                           const void* x_loc, const void* x_all, const float* col_sums, void* workspace, float* loss_rows,
+                           hipStream_t s) {
+    mv_loss(rows, cols, row_offset, d, views, anchor, dt, x_loc, x_all, nullptr, nullptr, col_sums, workspace, loss_rows, s);
+}
+
+void launch_nce_multi_masked_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                                  const void* x_loc, const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all,
+                                  const float* col_sums, void* workspace, float* loss_rows, hipStream_t s) {
+    mv_loss(rows, cols, row_offset, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, col_sums, workspace, loss_rows, s);
 }
 
 // gradients: the weights of all pairs in place (one launch), then ONE da launch (every view with the a role; K through all its
 // partner blocks, float32 slabs) and ONE db launch (every view with the b role, stored by the GEMM), then the slab sum, which
-// also writes the zeros of the views without a role.  launch_nce_multi_loss must have run on this workspace.
-void launch_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
-                            float coef, const void* x_loc, const void* x_all, void* workspace, const float* upstream, int out_bf16,
-                            void* dx_loc, void* dx_all, hipStream_t s) {
+// also writes the zeros of the views without a role.  launch_nce_multi_loss must have run on this workspace.  pair_coef / pres_loc
+// non-NULL: the form with missing views -- its weights kernel, then the SAME products, dT sum and slab sum: an excluded element of
+// W is a zero, and the normalised rows of an absent slot are zeros, so every product is right as it stands.
+namespace {
+void mv_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt, float coef,
+              const float* pair_coef, const unsigned char* pres_loc, const void* x_loc, const void* x_all, void* workspace,
+              const float* upstream, int out_bf16, void* dx_loc, void* dx_all, hipStream_t s) {
     const MvPairs t = mv_pairs(views, anchor);
     const MvWs w = mv_carve(workspace, rows, cols, d, views, t.count);
     const int64_t Rp = up256(rows), Cp = up256(cols);
     const int64_t chunks = Rp * (Cp / 8);
-    nce_multi_weights_kernel<<<dim3((unsigned)((chunks + 255) / 256), (unsigned)t.count), dim3(256), 0, s>>>(
-        w.e, Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset, coef, upstream, dt.t, dt.min_t);
+    const dim3 wgrid((unsigned)((chunks + 255) / 256), (unsigned)t.count);
+    if (pair_coef) {
+        NceMultiFin pm = {};
+        for (int p = 0; p < t.count; ++p) { pm.m[p] = t.m[p]; pm.n[p] = t.n[p]; }
+        pm.views = views;
+        nce_multi_masked_weights_kernel<<<wgrid, dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset, pair_coef,
+                                                                    pm, pres_loc, upstream, dt.t, dt.min_t);
+    } else {
+        nce_multi_weights_kernel<<<wgrid, dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset, coef, upstream,
+                                                             dt.t, dt.min_t);
+    }
     const int n_tiles_d = (d + BT - 1) / BT;
     const unsigned int pitch = 2u * (unsigned)d * (unsigned)views;
     unsigned int da_mask = 0, db_mask = 0;
@@ -1333,6 +1511,21 @@ void launch_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int 
     const int64_t n4 = (rows + cols) * ((int64_t)views * d / 4);
     nce_multi_finish_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s>>>(w.slabs, splits, rows, cols, views, d, da_mask, db_mask,
                                                                                      dx_loc, dx_all, out_bf16);
+}
+}  // namespace
+
+void launch_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                            float coef, const void* x_loc, const void* x_all, void* workspace, const float* upstream, int out_bf16,
+                            void* dx_loc, void* dx_all, hipStream_t s) {
+    mv_grads(rows, cols, row_offset, d, views, anchor, dt, coef, nullptr, nullptr, x_loc, x_all, workspace, upstream, out_bf16, dx_loc,
+             dx_all, s);
+}
+
+void launch_nce_multi_masked_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                                   const float* pair_coef, const unsigned char* pres_loc, const void* x_loc, const void* x_all,
+                                   void* workspace, const float* upstream, int out_bf16, void* dx_loc, void* dx_all, hipStream_t s) {
+    mv_grads(rows, cols, row_offset, d, views, anchor, dt, 0.f, pair_coef, pres_loc, x_loc, x_all, workspace, upstream, out_bf16, dx_loc,
+             dx_all, s);
 }
 
 // ---- supervised contrastive loss on the same GEMMs, both directions from one block (include/aecf_hip.h) ---------------------

@@ -107,6 +107,16 @@
     int mi = 0, ni = 0, split = 0, t_beg = 0, t_end = 0;
     if (!nce_tile_of<MAP>(p, vblock, mi, ni, split)) return;
     k_range(split, t_beg, t_end);
+    // EPI_EXP_MASK: thread t < 256 reads the presence byte of the block's row t, thread 256 + t that of its column t (the padding:
+    // no bit set).  Issued HERE, older than every operand copy, so that the copies' vmcnt counts stand and its latency passes
+    // behind the K loop.
+    unsigned int my_byte = 0;
+    if (EPI == EPI_EXP_MASK) {
+        const int t = threadIdx.x & (BT - 1);
+        const bool is_row = threadIdx.x < BT;
+        const int k = BT * (is_row ? mi : ni) + t;
+        if (k < (is_row ? p.m_valid : p.n_valid)) my_byte = (is_row ? p.pres_row : p.pres_col)[k];
+    }
     issue_first(mi, ni, t_beg, t_end);
     {
         f32x4 acc[8][4];
@@ -537,7 +547,10 @@
                 const unsigned long long* src = reinterpret_cast<const unsigned long long*>(is_row ? p.lab_row : p.lab_col);
                 if (k < (is_row ? p.m_valid : p.n_valid)) my_set = src[k];
             }
-            if (EPI == EPI_EXP_DT || epi_has_labels(EPI) || epi_has_sets(EPI) || EPI == EPI_EXP_SELF) {
+            // EPI_EXP_MASK: whether the thread's row or column (read in front of the K loop) holds both views of the pair; the flags
+            // go to LDS behind the barrier
+            const bool my_pres = EPI == EPI_EXP_MASK && (my_byte & p.pres_need) == p.pres_need;
+            if (EPI == EPI_EXP_DT || epi_has_labels(EPI) || epi_has_sets(EPI) || EPI == EPI_EXP_SELF || EPI == EPI_EXP_MASK) {
                 scale2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f;
                 shift2 = scale2;
             }
@@ -545,6 +558,19 @@
             __builtin_amdgcn_s_barrier();                       // every wave is past its last read of the stages
             if (epi_has_sets(EPI))                              // [256] row words | [256] column words, behind the 18 float planes
                 reinterpret_cast<unsigned long long*>(smem + 18 * BT * 4)[threadIdx.x] = my_set;
+            // EPI_EXP_MASK: [256] row flags | [256] column flags (bytes) | [8] the waves' votes, behind the 6 float planes in use
+            const unsigned char* pflag = reinterpret_cast<const unsigned char*>(smem + 18 * BT * 4);
+            bool all_present = true;
+            if (EPI == EPI_EXP_MASK) {
+                reinterpret_cast<unsigned char*>(smem + 18 * BT * 4)[threadIdx.x] = my_pres ? 1 : 0;
+                const int vote = __all(my_pres ? 1 : 0);
+                int* votes = reinterpret_cast<int*>(smem + 18 * BT * 4 + 2 * BT);
+                if (lane == 0) votes[w] = vote;
+                __syncthreads();
+                // ONE step tells the block whether its 512 rows and columns all hold the pair: then it is EPI_EXP_DT's tile
+                all_present = __builtin_amdgcn_readfirstlane(((votes[0] & votes[1]) & (votes[2] & votes[3])) &
+                                                             ((votes[4] & votes[5]) & (votes[6] & votes[7]))) != 0;
+            }
             // E = exp2(acc scale - shift): 4 consecutive columns per lane, 8-byte stores (16 rows x 32 B per wave-instruction).
             // The sums run as packed float32 adds (both halves from their own registers); masking only on edge tiles.
             float rs[8];
@@ -560,6 +586,8 @@
                 const int64_t p0 = p.row_offset + (int64_t)BT * mi;
                 edge = edge || (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
             }
+            // EPI_EXP_MASK: a tile with an absent row or column (the padding included) takes that branch too, block-uniform
+            if (EPI == EPI_EXP_MASK) edge = !all_present;
             unsigned short* etile = p.e + ((int64_t)mi * p.e_tiles + 4 * ni + wn) * (BT * 64) + (128 * wm + r16) * 64 + 4 * lg;
 #pragma unroll
             for (int rt = 0; rt < 8; ++rt) {
@@ -573,7 +601,18 @@
                     e01[1] = __builtin_amdgcn_exp2f(acc[rt][ct][1] * scale2 - shift2);
                     e23[0] = __builtin_amdgcn_exp2f(acc[rt][ct][2] * scale2 - shift2);
                     e23[1] = __builtin_amdgcn_exp2f(acc[rt][ct][3] * scale2 - shift2);
-                    if (edge) {
+                    if (EPI == EPI_EXP_MASK) {
+                        if (edge) {
+                            // the flags carry the padding: a row or column that does not exist is absent.  Selects on the flags
+                            // alone -- what an absent slot's score holds (NaN, inf) never reaches a sum
+                            const bool iok = pflag[128 * wm + 16 * rt + r16] != 0;
+                            const unsigned int cw = *reinterpret_cast<const unsigned int*>(pflag + BT + 64 * wn + 16 * ct + 4 * lg);
+                            e01[0] = (iok && (cw & 0x000000ffu)) ? e01[0] : 0.f;
+                            e01[1] = (iok && (cw & 0x0000ff00u)) ? e01[1] : 0.f;
+                            e23[0] = (iok && (cw & 0x00ff0000u)) ? e23[0] : 0.f;
+                            e23[1] = (iok && (cw & 0xff000000u)) ? e23[1] : 0.f;
+                        }
+                    } else if (edge) {
                         const bool iok = i < p.m_valid;
                         // EPI_EXP_SELF: the excluded key by its index (a row that exists has row_offset + i < n_valid < 2^31; unsigned,
                         // so that the padding rows past it wrap instead of overflowing)

@@ -466,6 +466,95 @@ class _NceMultiView(torch.autograd.Function):
         return dx, dx_all, None, g_t, None, None, None, None
 
 
+class _L2NormMaskedSlots(torch.autograd.Function):
+    """aecf_l2norm_masked_forward / _backward over the slots of x [rows * views, d]: a present slot is ``_L2Norm``'s, an absent one
+    (``mask`` [rows * views] uint8, non-zero) comes out as zeros whatever it holds and gets a zero gradient.  Also returns the
+    presence byte of every row (bit v: view v present), packed in the same launch."""
+
+    @staticmethod
+    def forward(ctx, z, mask, views, eps):
+        lib = _lib.load()
+        n, d = z.shape
+        zc = z.contiguous()
+        zn = torch.empty_like(zc)
+        inv = torch.empty(n, dtype=torch.float32, device=z.device)
+        pres = torch.empty(n // views, dtype=torch.uint8, device=z.device)
+        _lib.check(lib.aecf_l2norm_masked_forward(n, d, views, _DTYPES[z.dtype], eps, _ptr(zc), _ptr(mask), _ptr(zn), _ptr(inv), _ptr(pres),
+                                                  _stream()), "aecf_l2norm_masked_forward")
+        ctx.save_for_backward(zn, inv, mask)
+        ctx.mark_non_differentiable(pres)
+        return zn, pres
+
+    @staticmethod
+    def backward(ctx, dzn, _):
+        lib = _lib.load()
+        zn, inv, mask = ctx.saved_tensors
+        n, d = zn.shape
+        g = dzn.to(torch.float32).contiguous()
+        dz = torch.empty_like(zn)
+        _lib.check(lib.aecf_l2norm_masked_backward(n, d, _DTYPES[zn.dtype], _ptr(zn), _ptr(inv), _ptr(g), _ptr(mask), _ptr(dz), _stream()),
+                   "aecf_l2norm_masked_backward")
+        return dz, None, None, None
+
+
+class _NceMultiViewMasked(torch.autograd.Function):
+    """aecf_nce_multi_masked_pair_coef / _pass1 / _loss / _grads: ``_NceMultiView`` where a row may lack views.  ``pres`` [rows] /
+    ``pres_all`` [cols] are the presence bytes (bit v: view v present); pair p runs over the rows holding both its views and
+    weighs 0.5 / n_p / P', formed on the device from the gathered bytes -- nothing is read on the host.  The gradient products,
+    the dT sum and the slab sum are ``_NceMultiView``'s kernels."""
+
+    @staticmethod
+    def forward(ctx, x, x_all, pres, pres_all, row_offset, temperature, group, min_temperature, anchor):
+        lib = _lib.load()
+        rows, views, d = x.shape
+        cols = x_all.shape[0]
+        dev = x.device
+        xc, xa = x.detach().contiguous(), x_all.detach().contiguous()
+        pairs = len(multiview_pairs(views, None if anchor < 0 else anchor))
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws_bytes = lib.aecf_nce_multi_masked_workspace_bytes(rows, cols, d, views, anchor)
+        if ws_bytes == 0:
+            raise NotImplementedError(f"aecf_amd: multi-view InfoNCE needs d % 64 == 0, 64 <= d <= 4096, 2 to 8 views and fewer than "
+                                      f"2^31 gathered rows; got d = {d}, {views} views, {cols} rows")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        col_sums = torch.empty(pairs, cols, **f32)
+        pair_coef = torch.empty(pairs, **f32)
+        t = temperature.detach()
+        tp, t_min = _ptr(t), float(min_temperature)
+        _lib.check(lib.aecf_nce_multi_masked_pair_coef(cols, views, anchor, _ptr(pres_all), _ptr(pair_coef), _stream()),
+                   "aecf_nce_multi_masked_pair_coef")
+        _lib.check(lib.aecf_nce_multi_masked_pass1(rows, cols, d, views, anchor, tp, t_min, _ptr(xc), _ptr(xa), _ptr(pres), _ptr(pres_all),
+                                                   _ptr(ws), ws_bytes, _ptr(col_sums), _stream()), "aecf_nce_multi_masked_pass1")
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(col_sums, group=group)
+        loss_rows = torch.empty(pairs, rows, **f32)
+        _lib.check(lib.aecf_nce_multi_masked_loss(rows, cols, int(row_offset), d, views, anchor, tp, t_min, _ptr(xc), _ptr(xa), _ptr(pres),
+                                                  _ptr(pres_all), _ptr(col_sums), _ptr(ws), ws_bytes, _ptr(loss_rows), _stream()),
+                   "aecf_nce_multi_masked_loss")
+        ctx.save_for_backward(xc, xa, ws, t, pair_coef, pres)
+        ctx.meta = (temperature.shape, (rows, cols, int(row_offset), d, views, anchor, t_min, ws_bytes))
+        return (loss_rows.sum(dim=1) * pair_coef).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = _lib.load()
+        xc, xa, ws, t, pair_coef, pres = ctx.saved_tensors
+        t_shape, (rows, cols, row_offset, d, views, anchor, t_min, ws_bytes) = ctx.meta
+        if getattr(ctx, "_spent", False):
+            raise RuntimeError("aecf_amd: the multi-view InfoNCE backward runs once per forward (it consumes the stored logits)")
+        ctx._spent = True
+        dev = xc.device
+        dx = torch.empty(rows, views, d, dtype=torch.bfloat16, device=dev)
+        dx_all = torch.empty(cols, views, d, dtype=torch.bfloat16, device=dev)
+        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
+        d_t = torch.empty(1, dtype=torch.float32, device=dev) if ctx.needs_input_grad[5] else None
+        _lib.check(lib.aecf_nce_multi_masked_grads(rows, cols, row_offset, d, views, anchor, _ptr(t), t_min, _ptr(pair_coef), _ptr(xc),
+                                                   _ptr(xa), _ptr(pres), _ptr(ws), ws_bytes, _ptr(up), _DTYPES[torch.bfloat16], _ptr(dx),
+                                                   _ptr(dx_all), _ptr(d_t), _stream()), "aecf_nce_multi_masked_grads")
+        g_t = d_t.reshape(t_shape) if d_t is not None else None
+        return dx, dx_all, None, None, None, g_t, None, None, None
+
+
 def _multiview_refusal(x: torch.Tensor, cols: int, min_temperature: float, anchor: int) -> Optional[str]:
     """None where multi-view InfoNCE runs; else the limit that stands against it.  The memory test (P blocks of b_local x b_all
     bfloat16 and the float32 slabs within 0.6 of the free device memory) is skipped while a graph is being captured."""
@@ -485,7 +574,7 @@ def _multiview_refusal(x: torch.Tensor, cols: int, min_temperature: float, ancho
 
 
 def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=None, min_temperature: float = MIN_TEMPERATURE,
-                       anchor: Optional[int] = None) -> torch.Tensor:
+                       anchor: Optional[int] = None, key_padding_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Symmetric InfoNCE over the pairs of M views, negatives from every rank of ``group``:
 
         L = (1 / P) * sum over the pairs (m, n) of info_nce(x[:, m], x[:, n], temperature, group, min_temperature)
@@ -505,7 +594,21 @@ def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=
 
     Needs bfloat16, d % 64 == 0 (64 to 4096), ``min_temperature >= 0.025`` and a workspace (P blocks of b_local x b_all
     bfloat16 plus float32 slabs) within 0.6 of the free device memory (not tested while capturing); otherwise raises
-    NotImplementedError naming the limit -- a loop of ``info_nce`` over the pairs serves such inputs.  No fallback."""
+    NotImplementedError naming the limit -- a loop of ``info_nce`` over the pairs serves such inputs.  No fallback.
+
+    ``key_padding_mask`` (None: every row holds every view -- the code path, launches and bits above): [b_local, M], bool or uint8,
+    on x's device, True / non-zero where view m of row i is ABSENT -- the fusion pool's convention, so one tensor serves both
+    calls.  A row may keep all views, some, one or none.  Pair (m, n) then runs over V = the rows, of every rank, that hold both
+    views: only they are anchors, only they are keys, in both directions,
+
+        L = (1 / P') * sum over the pairs with a row of info_nce(x[V, m], x[V, n], ...),   P' = the number of such pairs
+
+    (0 with zero gradients where no pair has a row; a pair with one row adds 0).  What an absent slot holds -- zeros, stale data,
+    inf, NaN -- does not matter: it is excluded by the mask and by index, never by value; its gradient is an exact zero.  The
+    mask is read on the device (no host read; a captured step replays the mask's current contents); the row counts of the
+    pairs and their weights 0.5 / n / P' are formed there.  Data parallel adds one all-gather of b_local presence bytes beside
+    the all-gather of the rows; every rank derives the counts from the gathered bytes.  A masked pair costs a full pair: absent
+    rows are zeroed, not skipped."""
     if isinstance(x, (list, tuple)):
         views = list(x)
         if not all(isinstance(v, torch.Tensor) and v.dim() == 2 for v in views) or any(v.shape != views[0].shape for v in views):
@@ -526,6 +629,15 @@ def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=
         raise ValueError(f"multiview_info_nce: anchor must be None or a view index in 0..{views - 1}, got {anchor!r}")
     if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
         raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
+    if key_padding_mask is not None:
+        if not isinstance(key_padding_mask, torch.Tensor) or key_padding_mask.dim() != 2 or \
+                tuple(key_padding_mask.shape) != (b_local, views):
+            raise ValueError(f"multiview_info_nce: key_padding_mask must be a [b, M] = [{b_local}, {views}] tensor, got "
+                             f"{tuple(key_padding_mask.shape) if isinstance(key_padding_mask, torch.Tensor) else type(key_padding_mask).__name__}")
+        if key_padding_mask.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"multiview_info_nce: key_padding_mask must be bool or uint8, got {key_padding_mask.dtype}")
+        if key_padding_mask.device != x.device:
+            raise ValueError(f"multiview_info_nce: the key_padding_mask lives on {key_padding_mask.device}, the embeddings on {x.device}")
     _require_device(x, "x")
     k = -1 if anchor is None else int(anchor)
     rank, world = dp.world_info(group)
@@ -549,10 +661,22 @@ def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=
     t = _temperature_arg(temperature, x, min_temperature)
     if not isinstance(t, torch.Tensor):
         t = torch.full((1,), t, dtype=torch.float32, device=x.device)
-    nx = l2_normalize(x.reshape(b_local * views, d)).reshape(b_local, views, d)
-    nx_all = dp.all_gather_rows(nx.reshape(b_local, views * d), group, sizes=sizes).reshape(b_all, views, d) if world > 1 else nx
-    pairs = len(multiview_pairs(views, anchor))
-    share = _NceMultiView.apply(nx, nx_all, offset, t, 0.5 / float(b_all) / float(pairs), group, float(min_temperature), k)
+    if key_padding_mask is not None:
+        absent = key_padding_mask.detach().contiguous().view(torch.uint8).reshape(b_local * views)      # a view: read at replay
+        nx, pres = _L2NormMaskedSlots.apply(x.reshape(b_local * views, d), absent, views, 1e-12)
+        nx = nx.reshape(b_local, views, d)
+        if world > 1:
+            nx_all = dp.all_gather_rows(nx.reshape(b_local, views * d), group, sizes=sizes).reshape(b_all, views, d)
+            with torch.no_grad():                   # the one exchange the mask adds: b_local bytes per rank
+                pres_all = dp.all_gather_rows(pres.reshape(b_local, 1), group, sizes=sizes).reshape(b_all).contiguous()
+        else:
+            nx_all, pres_all = nx, pres
+        share = _NceMultiViewMasked.apply(nx, nx_all, pres, pres_all, offset, t, group, float(min_temperature), k)
+    else:
+        nx = l2_normalize(x.reshape(b_local * views, d)).reshape(b_local, views, d)
+        nx_all = dp.all_gather_rows(nx.reshape(b_local, views * d), group, sizes=sizes).reshape(b_all, views, d) if world > 1 else nx
+        pairs = len(multiview_pairs(views, anchor))
+        share = _NceMultiView.apply(nx, nx_all, offset, t, 0.5 / float(b_all) / float(pairs), group, float(min_temperature), k)
     if world == 1:
         return share
     total = share.detach().clone()

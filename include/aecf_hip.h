@@ -462,6 +462,15 @@ int aecf_l2norm_forward(int64_t n, int32_t d, int32_t dtype, float eps, const vo
                         float* inv_norm, void* stream);
 int aecf_l2norm_backward(int64_t n, int32_t d, int32_t dtype, const void* zn, const float* inv_norm,
                          const float* dzn, void* dz, void* stream);
+/* The same over the n = rows * views slots of x [rows][views][d] with a padding mask [n] (uint8, non-zero = the slot is ABSENT, the
+ * fusion pool's key_padding_mask row by row).  A present slot has the bits of aecf_l2norm_forward / _backward.  An absent slot is
+ * never read: forward writes its row of zn as +0 and its inv_norm as 0, backward writes its row of dz as +0 -- whatever z or dzn
+ * hold there (NaN, inf).  presence [n / views] (may be NULL) receives one byte per row, bit v set = view v present: the bytes the
+ * aecf_nce_multi_masked_* calls read.  1 <= views <= 8, n % views == 0 (AECF_ERR_BAD_DIMS), then dtype, then NULL pointers. */
+int aecf_l2norm_masked_forward(int64_t n, int32_t d, int32_t views, int32_t dtype, float eps, const void* z, const uint8_t* mask,
+                               void* zn, float* inv_norm, uint8_t* presence, void* stream);
+int aecf_l2norm_masked_backward(int64_t n, int32_t d, int32_t dtype, const void* zn, const float* inv_norm, const float* dzn,
+                                const uint8_t* mask, void* dz, void* stream);
 /* One InfoNCE direction, forward + backward in one call: local unit-norm queries q [rows,d] against all
  * (all-gathered) unit-norm keys k [cols,d]; the positive of local row i is key row_offset + i.
  *   loss_rows[i] = logsumexp_j(q_i.k_j / T) - q_i.k_pos / T                       float32 [rows]
@@ -1072,6 +1081,45 @@ int aecf_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t
                          void* workspace, size_t workspace_bytes, const float* upstream, int32_t grad_dtype,
                          void* dx_loc /* [rows][views][d] */, void* dx_all /* [cols][views][d], this rank's share */,
                          float* d_temperature, void* stream);
+
+/* ---- multi-view InfoNCE with missing views (build-defined; aecf_nce_multi_* where a row may lack views) ----
+ * pres_loc [rows] (indexed by the LOCAL row) and pres_all [cols] (indexed by the GLOBAL row / column) hold one byte per row, bit v
+ * set = view v of that row is present (aecf_l2norm_masked_forward packs them; pres_all[row_offset + i] == pres_loc[i]).  For pair
+ * p = (m, n) of the pair list above, V_p = the global rows that hold both views, n_p = |V_p| over all ranks.  Pair p is the symmetric
+ * InfoNCE of aecf_nce_multi_* restricted to V_p on both sides -- only rows of V_p are anchors, only rows of V_p are keys, down
+ * the columns too -- and the total is the mean over the P' pairs with n_p > 0:
+ *   L = sum_p pair_coef[p] sum_i loss_rows[p][i],   pair_coef[p] = 0.5 / n_p / P'  (0 where n_p = 0; L = 0 where P' = 0).
+ * Exclusion is by the bytes and by index, with selects, never by value: x_loc / x_all must hold FINITE rows at absent slots (the
+ * masked normalisation writes zeros there), and then no output depends on what the caller's unnormalised input held.
+ *   pair_coef: ONE small launch over pres_all: integer counts of every n_p, pair_coef [P] float32 = 0.5 / n_p / P' formed in
+ *          float64 and rounded once (with every view present: the float32 the unmasked form is handed as coef).
+ *   pass1: aecf_nce_multi_pass1 with E = 0 -- in the stored block, its row sums and its column sums -- wherever the row or the
+ *          column is outside V_p.  A 256 x 256 tile whose rows and columns are all in V_p runs the unmasked tile's code.
+ *   loss:  a local row outside V_p: loss_rows[p][i] = 0, normaliser 0 (no log of an empty sum, no 1 / 0); a column outside V_p:
+ *          normaliser 0.  loss_rows are WITHOUT pair_coef.
+ *   grads: the weights with pair_coef[p] per pair and the partner term for the rows of V_p alone; then the gradient products, the
+ *          dT sum and the slab sum of aecf_nce_multi_grads UNCHANGED: an excluded weight is a zero.  The gradient at an absent
+ *          (row, view) is an exact zero; an empty pair contributes zeros.
+ * With every view present col_sums, loss_rows, dx_loc, dx_all and d_temperature have the bits of aecf_nce_multi_* at
+ * coef = 0.5 / cols / P.  Served shapes, workspace (the query returns aecf_nce_multi_workspace_bytes' value and layout), checks and
+ * their order: as aecf_nce_multi_*; pres_loc, pres_all and pair_coef may not be NULL (AECF_ERR_NULL_POINTER).  pair_coef checks
+ * cols, views and anchor (AECF_ERR_BAD_DIMS), then NULL pointers.  Nothing is read on the host; no float atomics. */
+size_t aecf_nce_multi_masked_workspace_bytes(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor);   /* 0: not served */
+int aecf_nce_multi_masked_pair_coef(int64_t cols, int32_t views, int32_t anchor, const uint8_t* pres_all,
+                                    float* pair_coef /* [P] */, void* stream);
+int aecf_nce_multi_masked_pass1(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor, const float* temperature,
+                                float min_temperature, const void* x_loc, const void* x_all, const uint8_t* pres_loc,
+                                const uint8_t* pres_all, void* workspace, size_t workspace_bytes, float* col_sums /* [P][cols] */,
+                                void* stream);
+int aecf_nce_multi_masked_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                               const float* temperature, float min_temperature, const void* x_loc, const void* x_all,
+                               const uint8_t* pres_loc, const uint8_t* pres_all, const float* col_sums /* summed over ranks */,
+                               void* workspace, size_t workspace_bytes, float* loss_rows /* [P][rows] */, void* stream);
+int aecf_nce_multi_masked_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                                const float* temperature, float min_temperature, const float* pair_coef, const void* x_loc,
+                                const void* x_all, const uint8_t* pres_loc, void* workspace, size_t workspace_bytes,
+                                const float* upstream, int32_t grad_dtype, void* dx_loc, void* dx_all, float* d_temperature,
+                                void* stream);
 
 /* ---- retrieval ranks of the contrastive views (build-defined like the contrastive terms they evaluate: the reference has no
  * contrastive term and no retrieval evaluation, so there are no reference lines to cite) ----
