@@ -46,9 +46,75 @@ def _temperature_arg(temperature, z: torch.Tensor, min_temperature: float):
         raise ValueError(f"aecf_amd: a tensor temperature must hold one element, got shape {tuple(temperature.shape)}")
     if temperature.device != z.device:
         raise ValueError(f"aecf_amd: the temperature lives on {temperature.device}, the embeddings on {z.device}")
+    _check_min_temperature(min_temperature)
+    return temperature
+
+
+def _check_min_temperature(min_temperature) -> None:
     if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
         raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
-    return temperature
+
+
+def _check_two_views(name: str, za: torch.Tensor, zb: torch.Tensor) -> None:
+    if za.shape != zb.shape or za.dim() != 2:
+        raise ValueError(f"{name} expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+
+
+def _device_scalar(value, z: torch.Tensor) -> torch.Tensor:
+    """A checked temperature or bias as the kernels read it: a tensor as it is, a float filled into one float32 element on z's
+    device."""
+    return value if isinstance(value, torch.Tensor) else torch.full((1,), value, dtype=torch.float32, device=z.device)
+
+
+def _temperature_scalar(temperature, z: torch.Tensor, min_temperature: float) -> torch.Tensor:
+    return _device_scalar(_temperature_arg(temperature, z, min_temperature), z)
+
+
+# The data-parallel policy of the contrastive drivers.  Every rank of ``group`` must issue the same collectives in the same
+# order -- a rank that took another form, or raised where the others went on, would leave them waiting -- so the drivers
+# exchange their row counts, gather rows, agree on a refusal and form their return value through these.  (``info_nce`` keeps
+# the count exchange it had: it gathers first and sends a default-dtype count, and that sequence is part of its behaviour.)
+
+def _row_ranges(b_local: int, device, group):
+    """``(sizes, offset, b_all)``: every rank's row count in rank order, this rank's first row among the gathered rows and their
+    total, from one all-gather of an int64 element.  One rank: ``(None, 0, b_local)``, no collective."""
+    rank, world = dp.world_info(group)
+    if world == 1:
+        return None, 0, b_local
+    n = torch.tensor([b_local], device=device, dtype=torch.int64)
+    got = [torch.zeros_like(n) for _ in range(world)]
+    torch.distributed.all_gather(got, n, group=group)
+    sizes = [int(v.item()) for v in got]
+    return sizes, sum(sizes[:rank]), sum(sizes)
+
+
+def _all_rows(x: torch.Tensor, group, sizes) -> torch.Tensor:
+    """The rows of every rank (``sizes`` of ``_row_ranges``); on one rank x itself, with no copy."""
+    return x if sizes is None else dp.all_gather_rows(x, group, sizes=sizes)
+
+
+def _agreed_refusal(refusal: Optional[str], device, group) -> Optional[str]:
+    """This rank's refusal of a form (None: it would run it) -> the group's: a MIN all-reduce of one flag, after which a rank
+    that would have run while another refused refuses too.  One rank: the refusal as it came."""
+    if dp.world_info(group)[1] > 1:
+        flag = torch.tensor([1 if refusal is None else 0], device=device)
+        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
+        if refusal is None and not bool(int(flag.item())):
+            refusal = "the same on every rank (another rank refused it)"
+    return refusal
+
+
+def _dp_value(share: torch.Tensor, group) -> torch.Tensor:
+    """This rank's rows' share of a global objective -> what the driver returns."""
+    world = dp.world_info(group)[1]
+    if world == 1:
+        return share
+    # Data-parallel convention (dp.FlatGradBucket.all_reduce(average=True)): gradients are AVERAGED over ranks, so
+    # the local term carries a factor `world`; the returned VALUE is the global loss on every rank.
+    total = share.detach().clone()
+    torch.distributed.all_reduce(total, group=group)
+    scaled = share * world
+    return scaled + (total - scaled.detach())
 
 
 class _L2Norm(torch.autograd.Function):
@@ -355,8 +421,7 @@ def info_nce(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch
     The form is chosen from the dtype, d, memory and ``min_temperature`` (below 0.025: the streaming form), never from T."""
     _require_device(za, "za")
     _require_device(zb, "zb")
-    if za.shape != zb.shape or za.dim() != 2:
-        raise ValueError(f"info_nce expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+    _check_two_views("info_nce", za, zb)
     if za.dtype not in _DTYPES:
         raise NotImplementedError(f"aecf_amd: dtype {za.dtype} is not supported (bfloat16 / float32 only)")
     t = _temperature_arg(temperature, za, min_temperature)
@@ -364,11 +429,8 @@ def info_nce(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch
     na, nb = l2_normalize(za), l2_normalize(zb)
     nb_all = dp.all_gather_rows(nb, group) if world > 1 else nb
     b_all = nb_all.shape[0]
-    sym = _sym_supported(za, t, b_all, min_temperature)
-    if world > 1:                                   # every rank must take the same form (they exchange different things)
-        flag = torch.tensor([1 if sym else 0], device=za.device)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
-        sym = bool(int(flag.item()))
+    # every rank must take the same form (they exchange different things)
+    sym = _agreed_refusal(None if _sym_supported(za, t, b_all, min_temperature) else "no symmetric form", za.device, group) is None
     if world > 1:
         sizes = torch.tensor([za.shape[0]], device=za.device)
         all_sizes = [torch.zeros_like(sizes) for _ in range(world)]
@@ -389,14 +451,7 @@ def info_nce(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch
         l_ab = _NceDirection.apply(na, nb_all, offset, t, coef, low, min_temperature)
         l_ba = _NceDirection.apply(nb, na_all, offset, t, coef, low, min_temperature)
         share = l_ab + l_ba              # this rank's rows' share of the global objective
-    if world == 1:
-        return share
-    # Data-parallel convention (dp.FlatGradBucket.all_reduce(average=True)): gradients are AVERAGED over ranks, so
-    # the local term carries a factor `world`; the returned VALUE is the global loss on every rank.
-    total = share.detach().clone()
-    torch.distributed.all_reduce(total, group=group)
-    scaled = share * world
-    return scaled + (total - scaled.detach())
+    return _dp_value(share, group)
 
 
 MULTIVIEW_MAX_VIEWS = 8     # the pair table of the logits launch holds the 28 pairs of 8 views
@@ -408,6 +463,37 @@ def multiview_pairs(views: int, anchor: Optional[int] = None):
     if anchor is None:
         return [(m, n) for m in range(views) for n in range(m + 1, views)]
     return [(min(anchor, n), max(anchor, n)) for n in range(views) if n != anchor]
+
+
+def _spend(ctx, what: str) -> None:
+    """The backward of a tile form overwrites the logits its forward stored: it runs once, a second call is refused."""
+    if getattr(ctx, "_spent", False):
+        raise RuntimeError(f"aecf_amd: the {what} backward runs once per forward (it consumes the stored logits)")
+    ctx._spent = True
+
+
+def _multiview_buffers(workspace_bytes, x: torch.Tensor, x_all: torch.Tensor, anchor: int):
+    """What the two multi-view forwards hand their launches: ``(xc, xa, ws, ws_bytes, col_sums, loss_rows)`` -- the rows as the
+    kernels read them, the workspace the library's query asks for, the [P, cols] column sums and the [P, rows] loss rows."""
+    rows, views, d = x.shape
+    cols = x_all.shape[0]
+    pairs = len(multiview_pairs(views, None if anchor < 0 else anchor))
+    f32 = dict(dtype=torch.float32, device=x.device)
+    ws_bytes = workspace_bytes(rows, cols, d, views, anchor)
+    if ws_bytes == 0:
+        raise NotImplementedError(f"aecf_amd: multi-view InfoNCE needs d % 64 == 0, 64 <= d <= 4096, 2 to 8 views and fewer than "
+                                  f"2^31 gathered rows; got d = {d}, {views} views, {cols} rows")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    return (x.detach().contiguous(), x_all.detach().contiguous(), ws, ws_bytes, torch.empty(pairs, cols, **f32),
+            torch.empty(pairs, rows, **f32))
+
+
+def _multiview_grad_buffers(ctx, xc: torch.Tensor, xa: torch.Tensor, d_loss: torch.Tensor, wants_dt: bool):
+    """What the two multi-view backwards hand their one call, which runs once per forward: ``(dx, dx_all, up, d_t)``."""
+    _spend(ctx, "multi-view InfoNCE")
+    dx, dx_all = torch.empty_like(xc, dtype=torch.bfloat16), torch.empty_like(xa, dtype=torch.bfloat16)
+    up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
+    return dx, dx_all, up, torch.empty(1, dtype=torch.float32, device=xc.device) if wants_dt else None
 
 
 class _NceMultiView(torch.autograd.Function):
@@ -423,23 +509,13 @@ class _NceMultiView(torch.autograd.Function):
         lib = _lib.load()
         rows, views, d = x.shape
         cols = x_all.shape[0]
-        dev = x.device
-        xc, xa = x.detach().contiguous(), x_all.detach().contiguous()
-        pairs = len(multiview_pairs(views, None if anchor < 0 else anchor))
-        f32 = dict(dtype=torch.float32, device=dev)
-        ws_bytes = lib.aecf_nce_multi_workspace_bytes(rows, cols, d, views, anchor)
-        if ws_bytes == 0:
-            raise NotImplementedError(f"aecf_amd: multi-view InfoNCE needs d % 64 == 0, 64 <= d <= 4096, 2 to 8 views and fewer than "
-                                      f"2^31 gathered rows; got d = {d}, {views} views, {cols} rows")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        col_sums = torch.empty(pairs, cols, **f32)
+        xc, xa, ws, ws_bytes, col_sums, loss_rows = _multiview_buffers(lib.aecf_nce_multi_workspace_bytes, x, x_all, anchor)
         t = temperature.detach()
         tp, t_min = _ptr(t), float(min_temperature)
         _lib.check(lib.aecf_nce_multi_pass1(rows, cols, d, views, anchor, tp, t_min, _ptr(xc), _ptr(xa), _ptr(ws), ws_bytes,
                                             _ptr(col_sums), _stream()), "aecf_nce_multi_pass1")
         if dp.world_info(group)[1] > 1:
             torch.distributed.all_reduce(col_sums, group=group)
-        loss_rows = torch.empty(pairs, rows, **f32)
         _lib.check(lib.aecf_nce_multi_loss(rows, cols, int(row_offset), d, views, anchor, tp, t_min, _ptr(xc), _ptr(xa), _ptr(col_sums),
                                            _ptr(ws), ws_bytes, _ptr(loss_rows), _stream()), "aecf_nce_multi_loss")
         ctx.save_for_backward(xc, xa, ws, t)
@@ -451,14 +527,7 @@ class _NceMultiView(torch.autograd.Function):
         lib = _lib.load()
         xc, xa, ws, t = ctx.saved_tensors
         t_shape, (rows, cols, row_offset, d, views, anchor, coef, t_min, ws_bytes) = ctx.meta
-        if getattr(ctx, "_spent", False):
-            raise RuntimeError("aecf_amd: the multi-view InfoNCE backward runs once per forward (it consumes the stored logits)")
-        ctx._spent = True
-        dev = xc.device
-        dx = torch.empty(rows, views, d, dtype=torch.bfloat16, device=dev)
-        dx_all = torch.empty(cols, views, d, dtype=torch.bfloat16, device=dev)
-        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
-        d_t = torch.empty(1, dtype=torch.float32, device=dev) if ctx.needs_input_grad[3] else None
+        dx, dx_all, up, d_t = _multiview_grad_buffers(ctx, xc, xa, d_loss, ctx.needs_input_grad[3])
         _lib.check(lib.aecf_nce_multi_grads(rows, cols, row_offset, d, views, anchor, _ptr(t), t_min, coef, _ptr(xc), _ptr(xa), _ptr(ws),
                                             ws_bytes, _ptr(up), _DTYPES[torch.bfloat16], _ptr(dx), _ptr(dx_all), _ptr(d_t), _stream()),
                    "aecf_nce_multi_grads")
@@ -508,17 +577,8 @@ class _NceMultiViewMasked(torch.autograd.Function):
         lib = _lib.load()
         rows, views, d = x.shape
         cols = x_all.shape[0]
-        dev = x.device
-        xc, xa = x.detach().contiguous(), x_all.detach().contiguous()
-        pairs = len(multiview_pairs(views, None if anchor < 0 else anchor))
-        f32 = dict(dtype=torch.float32, device=dev)
-        ws_bytes = lib.aecf_nce_multi_masked_workspace_bytes(rows, cols, d, views, anchor)
-        if ws_bytes == 0:
-            raise NotImplementedError(f"aecf_amd: multi-view InfoNCE needs d % 64 == 0, 64 <= d <= 4096, 2 to 8 views and fewer than "
-                                      f"2^31 gathered rows; got d = {d}, {views} views, {cols} rows")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        col_sums = torch.empty(pairs, cols, **f32)
-        pair_coef = torch.empty(pairs, **f32)
+        xc, xa, ws, ws_bytes, col_sums, loss_rows = _multiview_buffers(lib.aecf_nce_multi_masked_workspace_bytes, x, x_all, anchor)
+        pair_coef = torch.empty(col_sums.shape[0], dtype=torch.float32, device=x.device)
         t = temperature.detach()
         tp, t_min = _ptr(t), float(min_temperature)
         _lib.check(lib.aecf_nce_multi_masked_pair_coef(cols, views, anchor, _ptr(pres_all), _ptr(pair_coef), _stream()),
@@ -527,7 +587,6 @@ class _NceMultiViewMasked(torch.autograd.Function):
                                                    _ptr(ws), ws_bytes, _ptr(col_sums), _stream()), "aecf_nce_multi_masked_pass1")
         if dp.world_info(group)[1] > 1:
             torch.distributed.all_reduce(col_sums, group=group)
-        loss_rows = torch.empty(pairs, rows, **f32)
         _lib.check(lib.aecf_nce_multi_masked_loss(rows, cols, int(row_offset), d, views, anchor, tp, t_min, _ptr(xc), _ptr(xa), _ptr(pres),
                                                   _ptr(pres_all), _ptr(col_sums), _ptr(ws), ws_bytes, _ptr(loss_rows), _stream()),
                    "aecf_nce_multi_masked_loss")
@@ -540,14 +599,7 @@ class _NceMultiViewMasked(torch.autograd.Function):
         lib = _lib.load()
         xc, xa, ws, t, pair_coef, pres = ctx.saved_tensors
         t_shape, (rows, cols, row_offset, d, views, anchor, t_min, ws_bytes) = ctx.meta
-        if getattr(ctx, "_spent", False):
-            raise RuntimeError("aecf_amd: the multi-view InfoNCE backward runs once per forward (it consumes the stored logits)")
-        ctx._spent = True
-        dev = xc.device
-        dx = torch.empty(rows, views, d, dtype=torch.bfloat16, device=dev)
-        dx_all = torch.empty(cols, views, d, dtype=torch.bfloat16, device=dev)
-        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
-        d_t = torch.empty(1, dtype=torch.float32, device=dev) if ctx.needs_input_grad[5] else None
+        dx, dx_all, up, d_t = _multiview_grad_buffers(ctx, xc, xa, d_loss, ctx.needs_input_grad[5])
         _lib.check(lib.aecf_nce_multi_masked_grads(rows, cols, row_offset, d, views, anchor, _ptr(t), t_min, _ptr(pair_coef), _ptr(xc),
                                                    _ptr(xa), _ptr(pres), _ptr(ws), ws_bytes, _ptr(up), _DTYPES[torch.bfloat16], _ptr(dx),
                                                    _ptr(dx_all), _ptr(d_t), _stream()), "aecf_nce_multi_masked_grads")
@@ -627,8 +679,7 @@ def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=
         raise ValueError(f"multiview_info_nce serves 2 to {MULTIVIEW_MAX_VIEWS} views, got {views}")
     if anchor is not None and not (isinstance(anchor, int) and not isinstance(anchor, bool) and 0 <= anchor < views):
         raise ValueError(f"multiview_info_nce: anchor must be None or a view index in 0..{views - 1}, got {anchor!r}")
-    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
-        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
+    _check_min_temperature(min_temperature)
     if key_padding_mask is not None:
         if not isinstance(key_padding_mask, torch.Tensor) or key_padding_mask.dim() != 2 or \
                 tuple(key_padding_mask.shape) != (b_local, views):
@@ -640,27 +691,14 @@ def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=
             raise ValueError(f"multiview_info_nce: the key_padding_mask lives on {key_padding_mask.device}, the embeddings on {x.device}")
     _require_device(x, "x")
     k = -1 if anchor is None else int(anchor)
-    rank, world = dp.world_info(group)
-    if world > 1:
-        n = torch.tensor([b_local], device=x.device, dtype=torch.int64)
-        got = [torch.zeros_like(n) for _ in range(world)]
-        torch.distributed.all_gather(got, n, group=group)
-        sizes = [int(v.item()) for v in got]
-        offset, b_all = sum(sizes[:rank]), sum(sizes)
-    else:
-        sizes, offset, b_all = None, 0, b_local
-    refusal = _multiview_refusal(x, b_all, min_temperature, k)
-    if world > 1:                                   # every rank must refuse together (they exchange between the passes)
-        flag = torch.tensor([1 if refusal is None else 0], device=x.device)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
-        if refusal is None and not bool(int(flag.item())):
-            refusal = "the same on every rank (another rank refused it)"
+    world = dp.world_info(group)[1]
+    sizes, offset, b_all = _row_ranges(b_local, x.device, group)
+    # every rank must refuse together (they exchange between the passes)
+    refusal = _agreed_refusal(_multiview_refusal(x, b_all, min_temperature, k), x.device, group)
     if refusal is not None:
         raise NotImplementedError("aecf_amd: multi-view InfoNCE needs " + refusal + "; a loop of info_nce over the pairs serves "
                                   "such inputs")
-    t = _temperature_arg(temperature, x, min_temperature)
-    if not isinstance(t, torch.Tensor):
-        t = torch.full((1,), t, dtype=torch.float32, device=x.device)
+    t = _temperature_scalar(temperature, x, min_temperature)
     if key_padding_mask is not None:
         absent = key_padding_mask.detach().contiguous().view(torch.uint8).reshape(b_local * views)      # a view: read at replay
         nx, pres = _L2NormMaskedSlots.apply(x.reshape(b_local * views, d), absent, views, 1e-12)
@@ -677,12 +715,7 @@ def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=
         nx_all = dp.all_gather_rows(nx.reshape(b_local, views * d), group, sizes=sizes).reshape(b_all, views, d) if world > 1 else nx
         pairs = len(multiview_pairs(views, anchor))
         share = _NceMultiView.apply(nx, nx_all, offset, t, 0.5 / float(b_all) / float(pairs), group, float(min_temperature), k)
-    if world == 1:
-        return share
-    total = share.detach().clone()
-    torch.distributed.all_reduce(total, group=group)
-    scaled = share * world
-    return scaled + (total - scaled.detach())
+    return _dp_value(share, group)
 
 
 def _sig_scalar_arg(value, z: torch.Tensor, what: str):
@@ -700,8 +733,7 @@ def _sig_scalar_arg(value, z: torch.Tensor, what: str):
 
 
 def _sig_args(temperature, bias, z: torch.Tensor, min_temperature):
-    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
-        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
+    _check_min_temperature(min_temperature)
     return _sig_scalar_arg(temperature, z, "temperature"), _sig_scalar_arg(bias, z, "bias")
 
 
@@ -819,8 +851,7 @@ def sigmoid_contrastive(za: torch.Tensor, zb: torch.Tensor, temperature: Union[f
     included."""
     _require_device(za, "za")
     _require_device(zb, "zb")
-    if za.shape != zb.shape or za.dim() != 2:
-        raise ValueError(f"sigmoid_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+    _check_two_views("sigmoid_contrastive", za, zb)
     t, b = _sig_args(temperature, bias, za, min_temperature)
     rank, world = dp.world_info(group)
     rows, d = za.shape
@@ -846,10 +877,7 @@ def sigmoid_contrastive(za: torch.Tensor, zb: torch.Tensor, temperature: Union[f
                                           f"memory (the tile form) or d in {SIG_STREAM_WIDTHS} (the streaming form); got "
                                           f"{za.dtype}, d = {d}")
             form = _SigmoidStream
-    if not isinstance(t, torch.Tensor):
-        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
-    if not isinstance(b, torch.Tensor):
-        b = torch.full((1,), b, dtype=torch.float32, device=za.device)
+    t, b = _device_scalar(t, za), _device_scalar(b, za)
     na, nb = l2_normalize(za), l2_normalize(zb)
     nb_all = dp.all_gather_rows(nb, group, sizes=[rows] * world) if world > 1 else nb
     if form is _SigmoidStream:
@@ -857,12 +885,7 @@ def sigmoid_contrastive(za: torch.Tensor, zb: torch.Tensor, temperature: Union[f
         share = form.apply(na, nb_all, t, b, rank * rows, 1.0 / float(cols), float(min_temperature), grads)
     else:
         share = form.apply(na, nb_all, t, b, rank * rows, 1.0 / float(cols), float(min_temperature))
-    if world == 1:
-        return share
-    total = share.detach().clone()
-    torch.distributed.all_reduce(total, group=group)
-    scaled = share * world
-    return scaled + (total - scaled.detach())
+    return _dp_value(share, group)
 
 
 SUPCON_WIDTHS = (128, 256, 384, 512, 768, 1024)         # the widths aecf_supcon_workspace_bytes answers for
@@ -882,152 +905,193 @@ def _labels_arg(labels, z: torch.Tensor) -> torch.Tensor:
     return labels
 
 
-class _SupConDirection(torch.autograd.Function):
-    """aecf_supcon_fwd_bwd: sum_i [logsumexp_j(q_i.k_j/T) - mean over the positives of q_i.k_j/T] * coef for local unit-norm q
-    against all k, the positives of row i being its partner ``row_offset + i`` and every key that carries its (non-negative)
-    label.  Modelled on ``_NceDirection``: the forward makes the one call with the gradients at upstream 1 and saves them
+class _StreamForm(NamedTuple):
+    """One streaming direction as data.  The operator takes ``apply(q, k_all, *riders, *options, *offsets, temperature, coef,
+    min_temperature, grads)`` and the library's call ``(rows, cols, *offsets, d, T, min T, coef, q, k_all, *riders, *options,
+    loss rows, dq, dk, dT, workspace, its bytes, stream)``."""
+    call: str                   # the entry point that forms the loss and both gradients
+    workspace_bytes: str        # its workspace query: 0 where the width is not served
+    riders: tuple               # the int64 tensors beside q and k_all
+    options: tuple              # the integers handed on after them
+    offsets: tuple              # where local row i finds its partner (and itself) among the keys
+    needs: str                  # "<the loss> needs", as the refusal opens
+
+
+class _StreamDirection(torch.autograd.Function):
+    """One direction of a label-aware contrastive loss on the streaming kernels, the call named by ``form`` (a subclass sets
+    it).  Modelled on ``_NceDirection``: the forward makes the one call with the gradients at upstream 1 and saves them
     (float32), the backward multiplies them by the gradient that arrives, on the device.  ``grads`` False (decided by the caller:
     grad mode is off inside a forward) takes the call's loss-only mode: the same loss bits, no gradient buffers.  The temperature
     is a one-element float32 device tensor."""
+    form: _StreamForm
 
-    @staticmethod
-    def forward(ctx, q, k_all, q_labels, k_labels, row_offset, temperature, coef, min_temperature, grads):
+    @classmethod                # (not torch's usual staticmethod: the class ``apply`` was called on carries the form)
+    def forward(cls, ctx, q, k_all, *args):
+        form = cls.form
+        n_riders = len(form.riders)
+        n_options = n_riders + len(form.options)
+        n_plain = n_options + len(form.offsets)             # (the temperature follows q, k_all and these)
+        riders, options, offsets = args[:n_riders], args[n_riders:n_options], args[n_options:n_plain]
+        temperature, coef, min_temperature, grads = args[n_plain:]
         lib = _lib.load()
         rows, d = q.shape
         cols = k_all.shape[0]
         dev = q.device
-        ws_bytes = lib.aecf_supcon_workspace_bytes(rows, cols, d) if q.dtype == torch.bfloat16 and k_all.dtype == torch.bfloat16 else 0
+        bf16 = q.dtype == torch.bfloat16 and k_all.dtype == torch.bfloat16
+        ws_bytes = getattr(lib, form.workspace_bytes)(rows, cols, d) if bf16 else 0
         if ws_bytes == 0:
-            raise NotImplementedError(f"aecf_amd: the supervised contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; "
-                                      f"got {q.dtype}, d = {d}")
+            raise NotImplementedError(f"aecf_amd: {form.needs} bfloat16 rows with d in {SUPCON_WIDTHS}; got {q.dtype}, d = {d}")
         qc, kc = q.detach().contiguous(), k_all.detach().contiguous()
-        lq, lk = q_labels.contiguous(), k_labels.contiguous()
+        riders = [r.contiguous() for r in riders]
         f32 = dict(dtype=torch.float32, device=dev)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         loss_rows = torch.empty(rows, **f32)
         dq = dk = d_t = None
         if grads:
             dq, dk = torch.empty(rows, d, **f32), torch.empty(cols, d, **f32)
-            d_t = torch.empty(1, **f32) if ctx.needs_input_grad[5] else None
-        _lib.check(lib.aecf_supcon_fwd_bwd(rows, cols, int(row_offset), d, _ptr(temperature.detach()), float(min_temperature),
-                                           float(coef), _ptr(qc), _ptr(kc), _ptr(lq), _ptr(lk), _ptr(loss_rows), _ptr(dq), _ptr(dk),
-                                           _ptr(d_t), _ptr(ws), ws_bytes, _stream()), "aecf_supcon_fwd_bwd")
+            d_t = torch.empty(1, **f32) if ctx.needs_input_grad[2 + n_plain] else None
+        _lib.check(getattr(lib, form.call)(rows, cols, *map(int, offsets), d, _ptr(temperature.detach()), float(min_temperature),
+                                           float(coef), _ptr(qc), _ptr(kc), *map(_ptr, riders), *map(int, options), _ptr(loss_rows),
+                                           _ptr(dq), _ptr(dk), _ptr(d_t), _ptr(ws), ws_bytes, _stream()), form.call)
         ctx.save_for_backward(dq, dk, d_t)
-        ctx.meta = (q.dtype, k_all.dtype, temperature.shape)
+        ctx.meta = (q.dtype, k_all.dtype, temperature.shape, n_plain)
         return loss_rows.sum() * coef
 
     @staticmethod
     def backward(ctx, d_loss):
         dq, dk, d_t = ctx.saved_tensors
-        qd, kd, t_shape = ctx.meta
+        qd, kd, t_shape, n_plain = ctx.meta
         g = d_loss.detach().to(torch.float32)
         g_t = (d_t * g).reshape(t_shape) if d_t is not None else None
-        return (dq * g).to(qd), (dk * g).to(kd), None, None, None, g_t, None, None, None
+        return ((dq * g).to(qd), (dk * g).to(kd), *[None] * n_plain, g_t, None, None, None)
 
 
-class _SupConPoolDirection(torch.autograd.Function):
+class _SupConDirection(_StreamDirection):
+    """aecf_supcon_fwd_bwd: sum_i [logsumexp_j(q_i.k_j/T) - mean over the positives of q_i.k_j/T] * coef for local unit-norm q
+    against all k, the positives of row i being its partner ``row_offset + i`` and every key that carries its (non-negative)
+    label.  Forward, backward, ``grads`` and the temperature: ``_StreamDirection``'s."""
+    form = _StreamForm("aecf_supcon_fwd_bwd", "aecf_supcon_workspace_bytes", riders=("q_labels", "k_labels"), options=(),
+                       offsets=("row_offset",), needs="the supervised contrastive loss needs")
+
+
+class _SupConPoolDirection(_StreamDirection):
     """aecf_supcon_pool_fwd_bwd: ``_SupConDirection`` over a pool of keys that holds the anchors themselves.  ``k_all`` is the one
     key buffer of both views; local row i has its partner at ``row_offset + i`` and itself at ``self_offset + i``, and that key is
-    left out of the log-sum-exp, of the positives and of both gradients.  Forward, backward, ``grads`` and the temperature: as
-    ``_SupConDirection``; the gradient on ``k_all`` is the whole pool's, so autograd splits it over the two views."""
+    left out of the log-sum-exp, of the positives and of both gradients.  The gradient on ``k_all`` is the whole pool's, so
+    autograd splits it over the two views."""
+    form = _StreamForm("aecf_supcon_pool_fwd_bwd", "aecf_supcon_workspace_bytes", riders=("q_labels", "k_labels"), options=(),
+                       offsets=("row_offset", "self_offset"), needs="the pooled contrastive losses need")
 
-    @staticmethod
-    def forward(ctx, q, k_all, q_labels, k_labels, row_offset, self_offset, temperature, coef, min_temperature, grads):
+
+class _TileForm(NamedTuple):
+    """One two-view tile form as data.  The operator takes ``apply(*operands, *riders, *options, row_offset, temperature, coef,
+    group, min_temperature)``; the library's three calls take the operands, riders and options in that order:
+    ``<prefix>_pass1(rows, cols, offset, d, T, min T, *operands, *riders, *options, workspace, its bytes, column statistics, stream)``,
+    ``<prefix>_loss(rows, cols, offset, d, T, min T, first operand, last operand, column statistics, workspace, its bytes, loss
+    rows, stream)`` and ``<prefix>_grads(rows, cols, offset, d, T, min T, coef, *operands, *riders, *options, workspace, its bytes,
+    upstream, gradient dtype, one gradient per operand, dT, stream)``."""
+    prefix: str                 # the symbols are <prefix>_workspace_bytes / _pass1 / _loss / _grads
+    operands: tuple             # unit-norm rows: (a, b_all) -- one block of logits -- or (a, b, a_all, b_all) -- three
+    riders: tuple               # the int64 tensors that say which keys are positives
+    options: tuple              # the integers handed on after them
+    stats: tuple                # the column statistics ranks all-reduce are [*stats, cols] float32
+    needs: str                  # "<the loss> needs <its limits>", as the forward refuses a shape the library does not serve
+    backward: str               # the backward, as the refusal of its second run names it
+
+
+class _TileSymmetric(torch.autograd.Function):
+    """Every anchor of this rank's two-view contrastive loss from the block (or blocks) of logits this rank owns, the calls
+    named by ``form`` (a subclass sets it).  Modelled on ``_NceSymmetric`` without the entropy rider: the column statistics are
+    the one thing ranks exchange, one all-reduce between pass 1 and the loss; the gradients on gathered rows are this rank's
+    shares.  The forward runs the logits pass and the loss; the backward runs the weights passes and the gradient products once,
+    scaled on the device by the gradient that arrives and written in the inputs' dtype (bfloat16 where every operand was, else
+    float32).  The temperature is a one-element float32 device tensor; the backward returns this rank's share of dL/dT."""
+    form: _TileForm
+
+    @classmethod                # (not torch's usual staticmethod: the class ``apply`` was called on carries the form)
+    def forward(cls, ctx, *args):
+        form = cls.form
+        n_operands = len(form.operands)
+        n_riders = n_operands + len(form.riders)
+        n_options = n_riders + len(form.options)
+        operands, riders, options = args[:n_operands], args[n_operands:n_riders], args[n_riders:n_options]
+        row_offset, temperature, coef, group, min_temperature = args[n_options:]
         lib = _lib.load()
-        rows, d = q.shape
-        cols = k_all.shape[0]
-        dev = q.device
-        ws_bytes = lib.aecf_supcon_workspace_bytes(rows, cols, d) if q.dtype == torch.bfloat16 and k_all.dtype == torch.bfloat16 else 0
-        if ws_bytes == 0:
-            raise NotImplementedError(f"aecf_amd: the pooled contrastive losses need bfloat16 rows with d in {SUPCON_WIDTHS}; "
-                                      f"got {q.dtype}, d = {d}")
-        qc, kc = q.detach().contiguous(), k_all.detach().contiguous()
-        lq, lk = q_labels.contiguous(), k_labels.contiguous()
+        rows, d = operands[0].shape
+        cols = operands[-1].shape[0]
+        dev = operands[0].device
+        dtypes = [x.dtype for x in operands]
+        operands = [x.detach().to(torch.bfloat16).contiguous() for x in operands]
+        riders = [r.contiguous() for r in riders]
         f32 = dict(dtype=torch.float32, device=dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        loss_rows = torch.empty(rows, **f32)
-        dq = dk = d_t = None
-        if grads:
-            dq, dk = torch.empty(rows, d, **f32), torch.empty(cols, d, **f32)
-            d_t = torch.empty(1, **f32) if ctx.needs_input_grad[6] else None
-        _lib.check(lib.aecf_supcon_pool_fwd_bwd(rows, cols, int(row_offset), int(self_offset), d, _ptr(temperature.detach()),
-                                                float(min_temperature), float(coef), _ptr(qc), _ptr(kc), _ptr(lq), _ptr(lk),
-                                                _ptr(loss_rows), _ptr(dq), _ptr(dk), _ptr(d_t), _ptr(ws), ws_bytes, _stream()),
-                   "aecf_supcon_pool_fwd_bwd")
-        ctx.save_for_backward(dq, dk, d_t)
-        ctx.meta = (q.dtype, k_all.dtype, temperature.shape)
-        return loss_rows.sum() * coef
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        dq, dk, d_t = ctx.saved_tensors
-        qd, kd, t_shape = ctx.meta
-        g = d_loss.detach().to(torch.float32)
-        g_t = (d_t * g).reshape(t_shape) if d_t is not None else None
-        return (dq * g).to(qd), (dk * g).to(kd), None, None, None, None, g_t, None, None, None
-
-
-class _SupConSymmetric(torch.autograd.Function):
-    """aecf_supcon_sym_pass1 / _loss / _grads: BOTH directions of the symmetric supervised contrastive loss from one block of
-    logits (local rows of view a against the gathered rows of view b), the labels shared by the two views.  Modelled on
-    ``_NceSymmetric`` without the entropy rider: the column statistics [3, cols] (sums of the exponentials, counts and raw-score
-    sums of the label matches) are the one thing ranks exchange, one all-reduce between pass 1 and the loss; the gradient on the
-    gathered keys is this rank's share.  The forward runs the logits pass and the loss; the backward runs the weights pass and the
-    two gradient products, scaled on the device by the gradient that arrives and written in the inputs' dtype.  The temperature
-    is a one-element float32 device tensor; the backward returns this rank's share of dL/dT."""
-
-    @staticmethod
-    def forward(ctx, a, b_all, row_labels, col_labels, row_offset, temperature, coef, group, min_temperature):
-        lib = _lib.load()
-        rows, d = a.shape
-        cols = b_all.shape[0]
-        dev = a.device
-        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
-        lr, lc = row_labels.contiguous(), col_labels.contiguous()
-        f32 = dict(dtype=torch.float32, device=dev)
-        ws_bytes = lib.aecf_supcon_sym_workspace_bytes(rows, cols, d)
+        ws_bytes = getattr(lib, form.prefix + "_workspace_bytes")(rows, cols, d)
         if ws_bytes == 0:
-            raise NotImplementedError(f"aecf_amd: the tile form of the supervised contrastive loss needs d % 64 == 0, 64 <= d <= "
-                                      f"4096 and at most 2^24 gathered rows; got d = {d}, {cols} rows")
+            raise NotImplementedError(f"aecf_amd: {form.needs}; got d = {d}, {cols} rows")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        col_stats = torch.empty(3, cols, **f32)
+        col_stats = torch.empty(*form.stats, cols, **f32)
         t = temperature.detach()
-        tp, t_min = _ptr(t), float(min_temperature)
-        _lib.check(lib.aecf_supcon_sym_pass1(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(lr), _ptr(lc), _ptr(ws),
-                                             ws_bytes, _ptr(col_stats), _stream()), "aecf_supcon_sym_pass1")
+        dims, t_min, options = (rows, cols, int(row_offset), d), float(min_temperature), tuple(map(int, options))
+        _lib.check(getattr(lib, form.prefix + "_pass1")(*dims, _ptr(t), t_min, *map(_ptr, operands), *map(_ptr, riders), *options,
+                                                        _ptr(ws), ws_bytes, _ptr(col_stats), _stream()), form.prefix + "_pass1")
         if dp.world_info(group)[1] > 1:
             torch.distributed.all_reduce(col_stats, group=group)
         loss_rows = torch.empty(rows, **f32)
-        _lib.check(lib.aecf_supcon_sym_loss(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(col_stats), _ptr(ws),
-                                            ws_bytes, _ptr(loss_rows), _stream()), "aecf_supcon_sym_loss")
-        ctx.save_for_backward(ac, bc, lr, lc, ws, t)
-        ctx.meta = (a.dtype, b_all.dtype, temperature.shape, (rows, cols, int(row_offset), d, float(coef), t_min, ws_bytes))
+        _lib.check(getattr(lib, form.prefix + "_loss")(*dims, _ptr(t), t_min, _ptr(operands[0]), _ptr(operands[-1]), _ptr(col_stats),
+                                                       _ptr(ws), ws_bytes, _ptr(loss_rows), _stream()), form.prefix + "_loss")
+        ctx.save_for_backward(t, ws, *operands, *riders)
+        ctx.meta = (dtypes, temperature.shape, dims, t_min, float(coef), options, ws_bytes)
         return loss_rows.sum() * coef
 
-    @staticmethod
-    def backward(ctx, d_loss):
+    @classmethod
+    def backward(cls, ctx, d_loss):
+        form = cls.form
         lib = _lib.load()
-        ac, bc, lr, lc, ws, t = ctx.saved_tensors
-        ad, bd, t_shape, (rows, cols, row_offset, d, coef, t_min, ws_bytes) = ctx.meta
-        if getattr(ctx, "_spent", False):
-            raise RuntimeError("aecf_amd: the symmetric supervised contrastive backward runs once per forward (it consumes the "
-                               "stored logits)")
-        ctx._spent = True
-        gdt = torch.bfloat16 if (ad == torch.bfloat16 and bd == torch.bfloat16) else torch.float32
-        da = torch.empty(rows, d, dtype=gdt, device=ac.device)
-        db = torch.empty(cols, d, dtype=gdt, device=ac.device)
+        t, ws, *rows_and_riders = ctx.saved_tensors
+        n_operands = len(form.operands)
+        t_index = n_operands + len(form.riders) + len(form.options) + 1     # (row_offset stands between them and the temperature)
+        dtypes, t_shape, dims, t_min, coef, options, ws_bytes = ctx.meta
+        _spend(ctx, form.backward)
+        gdt = torch.bfloat16 if dtypes.count(torch.bfloat16) == n_operands else torch.float32
+        grads = [torch.empty_like(x, dtype=gdt) for x in rows_and_riders[:n_operands]]
         up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
-        d_t = torch.empty(1, dtype=torch.float32, device=ac.device) if ctx.needs_input_grad[5] else None
-        _lib.check(lib.aecf_supcon_sym_grads(rows, cols, row_offset, d, _ptr(t), t_min, coef, _ptr(ac), _ptr(bc), _ptr(lr), _ptr(lc),
-                                             _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt], _ptr(da), _ptr(db), _ptr(d_t), _stream()),
-                   "aecf_supcon_sym_grads")
+        d_t = torch.empty(1, dtype=torch.float32, device=ws.device) if ctx.needs_input_grad[t_index] else None
+        _lib.check(getattr(lib, form.prefix + "_grads")(*dims, _ptr(t), t_min, coef, *map(_ptr, rows_and_riders), *options, _ptr(ws),
+                                                        ws_bytes, _ptr(up), _DTYPES[gdt], *map(_ptr, grads), _ptr(d_t), _stream()),
+                   form.prefix + "_grads")
         g_t = d_t.reshape(t_shape) if d_t is not None else None
-        return da.to(ad), db.to(bd), None, None, None, g_t, None, None, None
+        return (*[g.to(x) for g, x in zip(grads, dtypes)], *[None] * (t_index - n_operands), g_t, None, None, None)
 
 
-def _supcon_tile_refusal(z: torch.Tensor, zb: torch.Tensor, cols: int, min_temperature: float) -> Optional[str]:
-    """None where the tile form of the supervised contrastive loss runs; else what stands against it.  The memory test (the
-    b_local x b_all bfloat16 block within 0.6 of the free device memory) is skipped while a graph is being captured."""
+class _SupConSymmetric(_TileSymmetric):
+    """aecf_supcon_sym_pass1 / _loss / _grads: BOTH directions of the symmetric supervised contrastive loss from one block of
+    logits (local rows of view a against the gathered rows of view b), the labels shared by the two views.  The column statistics
+    [3, cols] are the sums of the exponentials and the counts and raw-score sums of the label matches."""
+    form = _TileForm("aecf_supcon_sym", operands=("a", "b_all"), riders=("row_labels", "col_labels"), options=(), stats=(3,),
+                     needs="the tile form of the supervised contrastive loss needs d % 64 == 0, 64 <= d <= 4096 and at most "
+                           "2^24 gathered rows",
+                     backward="symmetric supervised contrastive")
+
+
+class _TileLimits(NamedTuple):
+    """What differs between the tile forms' refusals: ``_tile_refusal``."""
+    workspace_bytes: str        # the library's workspace query: 0 for more gathered rows than the form serves
+    row_limit: str              # ... which is then said with this, {cols} filled in
+    workspace: str              # what the workspace holds
+
+
+_SUPCON_LIMITS = _TileLimits("aecf_supcon_sym_workspace_bytes", "at most 2^24 gathered rows (got {cols})",
+                             "b_local x b_all bfloat16")
+_NTXENT_LIMITS = _TileLimits("aecf_ntxent_sym_workspace_bytes", "fewer than 2^31 gathered rows (got {cols})",
+                             "three b_local x b_all bfloat16 blocks")
+_POOL_LIMITS = _TileLimits("aecf_supcon_pool_sym_workspace_bytes",
+                           "at most 2^23 gathered rows (got {cols}): the counts of two blocks add in float32",
+                           "three b_local x b_all bfloat16 blocks")
+
+
+def _tile_refusal(limits: _TileLimits, z: torch.Tensor, zb: torch.Tensor, cols: int, min_temperature: float) -> Optional[str]:
+    """None where a two-view tile form runs; else what stands against it.  The memory test (the workspace -- the block or blocks
+    of b_local x b_all bfloat16 exponentials and their float32 staging -- within 0.6 of the free device memory) is skipped while
+    a graph is being captured."""
     rows, d = z.shape
     if z.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16:
         return f"bfloat16 rows (got {z.dtype} and {zb.dtype})"
@@ -1035,11 +1099,11 @@ def _supcon_tile_refusal(z: torch.Tensor, zb: torch.Tensor, cols: int, min_tempe
         return f"d % 64 == 0 with 64 <= d <= 4096 (got d = {d})"
     if not float(min_temperature) >= MIN_TEMPERATURE:
         return f"min_temperature >= {MIN_TEMPERATURE} (got {min_temperature}): 1 / T is the constant shift of every exponential"
-    need = _lib.load().aecf_supcon_sym_workspace_bytes(rows, cols, d)
+    need = getattr(_lib.load(), limits.workspace_bytes)(rows, cols, d)
     if need == 0:
-        return f"at most 2^24 gathered rows (got {cols})"
+        return limits.row_limit.format(cols=cols)
     if not _capturing() and need > 0.6 * torch.cuda.mem_get_info(z.device)[0]:
-        return f"a workspace (b_local x b_all bfloat16, {need} bytes here) within 0.6 of the free device memory"
+        return f"a workspace ({limits.workspace}, {need} bytes here) within 0.6 of the free device memory"
     return None
 
 
@@ -1093,8 +1157,7 @@ def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Ten
                                   "the a x b block only); intra_view=True runs the streaming form, low_memory=True or None")
     _require_device(za, "za")
     _require_device(zb, "zb")
-    if za.shape != zb.shape or za.dim() != 2:
-        raise ValueError(f"supervised_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+    _check_two_views("supervised_contrastive", za, zb)
     labels = _labels_arg(labels, za)
     if low_memory not in (True, False, None):
         raise ValueError(f"aecf_amd: low_memory must be True, False or None, got {low_memory!r}")
@@ -1104,42 +1167,27 @@ def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Ten
     if low_memory is True and not streams:
         raise NotImplementedError(f"aecf_amd: the supervised contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; got "
                                   f"{za.dtype} and {zb.dtype}, d = {za.shape[1]}")
-    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
-        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
-    rank, world = dp.world_info(group)
-    if world > 1:
-        n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
-        got = [torch.zeros_like(n) for _ in range(world)]
-        torch.distributed.all_gather(got, n, group=group)
-        sizes = [int(v.item()) for v in got]
-        offset, b_all = sum(sizes[:rank]), sum(sizes)
-    else:
-        sizes, offset, b_all = None, 0, za.shape[0]
+    _check_min_temperature(min_temperature)
+    sizes, offset, b_all = _row_ranges(za.shape[0], za.device, group)
     tile = False
     if low_memory is not True:
-        refusal = _supcon_tile_refusal(za, zb, b_all, min_temperature)
+        # every rank must take the same form (they exchange different things)
+        refusal = _agreed_refusal(_tile_refusal(_SUPCON_LIMITS, za, zb, b_all, min_temperature), za.device, group)
         tile = refusal is None
-        if world > 1:                               # every rank must take the same form (they exchange different things)
-            flag = torch.tensor([1 if tile else 0], device=za.device)
-            torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
-            if tile and not bool(int(flag.item())):
-                tile, refusal = False, "the same on every rank (another rank refused it)"
         if not tile and (low_memory is False or not streams):
             raise NotImplementedError("aecf_amd: the tile form of the supervised contrastive loss needs " + refusal
                                       + ("" if low_memory is False else f"; the streaming form needs bfloat16 rows with d in "
                                          f"{SUPCON_WIDTHS}, got {za.dtype} and {zb.dtype}, d = {za.shape[1]}"))
-    t = _temperature_arg(temperature, za, min_temperature)
-    if not isinstance(t, torch.Tensor):
-        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    t = _temperature_scalar(temperature, za, min_temperature)
     lab = labels.detach().to(torch.int64)
     na, nb = l2_normalize(za), l2_normalize(zb)
-    nb_all = dp.all_gather_rows(nb, group, sizes=sizes) if world > 1 else nb
-    lab_all = dp.all_gather_rows(lab, group, sizes=sizes) if world > 1 else lab
+    nb_all = _all_rows(nb, group, sizes)
+    lab_all = _all_rows(lab, group, sizes)
     coef = 0.5 / float(b_all)
     if intra_view:
         if 2 * b_all >= 2 ** 31:
             raise NotImplementedError(f"aecf_amd: the pooled supervised contrastive loss needs 2 b_all < 2^31 keys, got b_all = {b_all}")
-        na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
+        na_all = _all_rows(na, group, sizes)
         pool, lab_pool = torch.cat([nb_all, na_all]), torch.cat([lab_all, lab_all])
         grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb, t))
         l_a = _SupConPoolDirection.apply(na, pool, lab, lab_pool, offset, b_all + offset, t, coef, float(min_temperature), grads)
@@ -1149,135 +1197,41 @@ def supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Ten
         # both directions from the one block of logits this rank owns: view a is never gathered
         share = _SupConSymmetric.apply(na, nb_all, lab, lab_all, offset, t, coef, group, float(min_temperature))
     else:
-        na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
+        na_all = _all_rows(na, group, sizes)
         grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb, t))
         l_ab = _SupConDirection.apply(na, nb_all, lab, lab_all, offset, t, coef, float(min_temperature), grads)
         l_ba = _SupConDirection.apply(nb, na_all, lab, lab_all, offset, t, coef, float(min_temperature), grads)
         share = l_ab + l_ba              # this rank's rows' share of the global objective
-    if world == 1:
-        return share
-    total = share.detach().clone()
-    torch.distributed.all_reduce(total, group=group)
-    scaled = share * world
-    return scaled + (total - scaled.detach())
+    return _dp_value(share, group)
 
 
-class _NtXentSymmetric(torch.autograd.Function):
+class _NtXentSymmetric(_TileSymmetric):
     """aecf_ntxent_sym_pass1 / _loss / _grads: the 2 b_local anchors of this rank's NT-Xent from three blocks of logits (a_loc x
-    b_all, a_loc x a_all, b_loc x b_all; the anchor itself left out of the last two by index).  Modelled on ``_SupConSymmetric``:
-    the [cols] column sums -- those of the a x b block, plus the b x b row sums on this rank's own range -- are the one thing
-    ranks exchange, one all-reduce between pass 1 and the loss; the gradients on the gathered rows are this rank's shares.  The
-    backward runs the three weights passes and the six gradient products once, scaled on the device by the gradient that arrives
-    and written in the inputs' dtype.  The temperature is a one-element float32 device tensor; the backward returns this rank's
-    share of dL/dT."""
-
-    @staticmethod
-    def forward(ctx, a, b, a_all, b_all, row_offset, temperature, coef, group, min_temperature):
-        lib = _lib.load()
-        rows, d = a.shape
-        cols = b_all.shape[0]
-        dev = a.device
-        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b.detach().to(torch.bfloat16).contiguous()
-        aa, ba = a_all.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
-        f32 = dict(dtype=torch.float32, device=dev)
-        ws_bytes = lib.aecf_ntxent_sym_workspace_bytes(rows, cols, d)
-        if ws_bytes == 0:
-            raise NotImplementedError(f"aecf_amd: the tile form of NT-Xent needs d % 64 == 0, 64 <= d <= 4096 and fewer than 2^31 "
-                                      f"gathered rows; got d = {d}, {cols} rows")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        col_sums = torch.empty(cols, **f32)
-        t = temperature.detach()
-        tp, t_min = _ptr(t), float(min_temperature)
-        _lib.check(lib.aecf_ntxent_sym_pass1(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(aa), _ptr(ba), _ptr(ws),
-                                             ws_bytes, _ptr(col_sums), _stream()), "aecf_ntxent_sym_pass1")
-        if dp.world_info(group)[1] > 1:
-            torch.distributed.all_reduce(col_sums, group=group)
-        loss_rows = torch.empty(rows, **f32)
-        _lib.check(lib.aecf_ntxent_sym_loss(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(ba), _ptr(col_sums), _ptr(ws),
-                                            ws_bytes, _ptr(loss_rows), _stream()), "aecf_ntxent_sym_loss")
-        ctx.save_for_backward(ac, bc, aa, ba, ws, t)
-        ctx.meta = ((a.dtype, b.dtype, a_all.dtype, b_all.dtype), temperature.shape,
-                    (rows, cols, int(row_offset), d, float(coef), t_min, ws_bytes))
-        return loss_rows.sum() * coef
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        lib = _lib.load()
-        ac, bc, aa, ba, ws, t = ctx.saved_tensors
-        dts, t_shape, (rows, cols, row_offset, d, coef, t_min, ws_bytes) = ctx.meta
-        if getattr(ctx, "_spent", False):
-            raise RuntimeError("aecf_amd: the tile-form NT-Xent backward runs once per forward (it consumes the stored logits)")
-        ctx._spent = True
-        gdt = torch.bfloat16 if all(x == torch.bfloat16 for x in dts) else torch.float32
-        dev = ac.device
-        d_a, d_b = torch.empty(rows, d, dtype=gdt, device=dev), torch.empty(rows, d, dtype=gdt, device=dev)
-        d_aa, d_ba = torch.empty(cols, d, dtype=gdt, device=dev), torch.empty(cols, d, dtype=gdt, device=dev)
-        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
-        d_t = torch.empty(1, dtype=torch.float32, device=dev) if ctx.needs_input_grad[5] else None
-        _lib.check(lib.aecf_ntxent_sym_grads(rows, cols, row_offset, d, _ptr(t), t_min, coef, _ptr(ac), _ptr(bc), _ptr(aa), _ptr(ba),
-                                             _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt], _ptr(d_a), _ptr(d_b), _ptr(d_aa), _ptr(d_ba),
-                                             _ptr(d_t), _stream()), "aecf_ntxent_sym_grads")
-        g_t = d_t.reshape(t_shape) if d_t is not None else None
-        return d_a.to(dts[0]), d_b.to(dts[1]), d_aa.to(dts[2]), d_ba.to(dts[3]), None, g_t, None, None, None
-
-
-def _ntxent_tile_refusal(z: torch.Tensor, zb: torch.Tensor, cols: int, min_temperature: float) -> Optional[str]:
-    """None where the tile form of NT-Xent runs; else what stands against it.  The memory test (three b_local x b_all bfloat16
-    blocks and the float32 staging within 0.6 of the free device memory) is skipped while a graph is being captured."""
-    rows, d = z.shape
-    if z.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16:
-        return f"bfloat16 rows (got {z.dtype} and {zb.dtype})"
-    if d % 64 != 0 or not 64 <= d <= 4096:
-        return f"d % 64 == 0 with 64 <= d <= 4096 (got d = {d})"
-    if not float(min_temperature) >= MIN_TEMPERATURE:
-        return f"min_temperature >= {MIN_TEMPERATURE} (got {min_temperature}): 1 / T is the constant shift of every exponential"
-    need = _lib.load().aecf_ntxent_sym_workspace_bytes(rows, cols, d)
-    if need == 0:
-        return f"fewer than 2^31 gathered rows (got {cols})"
-    if not _capturing() and need > 0.6 * torch.cuda.mem_get_info(z.device)[0]:
-        return f"a workspace (three b_local x b_all bfloat16 blocks, {need} bytes here) within 0.6 of the free device memory"
-    return None
+    b_all, a_loc x a_all, b_loc x b_all; the anchor itself left out of the last two by index).  The [cols] column sums are those
+    of the a x b block plus the b x b row sums on this rank's own range; the backward runs the three weights passes and the six
+    gradient products."""
+    form = _TileForm("aecf_ntxent_sym", operands=("a", "b", "a_all", "b_all"), riders=(), options=(), stats=(),
+                     needs="the tile form of NT-Xent needs d % 64 == 0, 64 <= d <= 4096 and fewer than 2^31 gathered rows",
+                     backward="tile-form NT-Xent")
 
 
 def _ntxent_tile(za: torch.Tensor, zb: torch.Tensor, temperature, group, min_temperature: float, required: bool):
     """The tile form of ``nt_xent``, or None where it does not run and ``required`` is False (the caller then streams)."""
-    if za.shape != zb.shape or za.dim() != 2:
-        raise ValueError(f"nt_xent expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
-    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
-        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
-    rank, world = dp.world_info(group)
-    if world > 1:
-        n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
-        got = [torch.zeros_like(n) for _ in range(world)]
-        torch.distributed.all_gather(got, n, group=group)
-        sizes = [int(v.item()) for v in got]
-        offset, b_all = sum(sizes[:rank]), sum(sizes)
-    else:
-        sizes, offset, b_all = None, 0, za.shape[0]
-    refusal = _ntxent_tile_refusal(za, zb, b_all, min_temperature)
-    tile = refusal is None
-    if world > 1:                                   # every rank must take the same form (they exchange different things)
-        flag = torch.tensor([1 if tile else 0], device=za.device)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
-        if tile and not bool(int(flag.item())):
-            tile, refusal = False, "the same on every rank (another rank refused it)"
-    if not tile:
+    _check_two_views("nt_xent", za, zb)
+    _check_min_temperature(min_temperature)
+    sizes, offset, b_all = _row_ranges(za.shape[0], za.device, group)
+    # every rank must take the same form (they exchange different things)
+    refusal = _agreed_refusal(_tile_refusal(_NTXENT_LIMITS, za, zb, b_all, min_temperature), za.device, group)
+    if refusal is not None:
         if required:
             raise NotImplementedError("aecf_amd: the tile form of NT-Xent needs " + refusal)
         return None
-    t = _temperature_arg(temperature, za, min_temperature)
-    if not isinstance(t, torch.Tensor):
-        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    t = _temperature_scalar(temperature, za, min_temperature)
     na, nb = l2_normalize(za), l2_normalize(zb)
-    na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
-    nb_all = dp.all_gather_rows(nb, group, sizes=sizes) if world > 1 else nb
+    na_all = _all_rows(na, group, sizes)
+    nb_all = _all_rows(nb, group, sizes)
     share = _NtXentSymmetric.apply(na, nb, na_all, nb_all, offset, t, 0.5 / float(b_all), group, float(min_temperature))
-    if world == 1:
-        return share
-    total = share.detach().clone()
-    torch.distributed.all_reduce(total, group=group)
-    scaled = share * world
-    return scaled + (total - scaled.detach())
+    return _dp_value(share, group)
 
 
 def nt_xent(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch.Tensor] = 0.07, group=None,
@@ -1314,133 +1268,40 @@ def nt_xent(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch.
     return supervised_contrastive(za, zb, labels, temperature, group, min_temperature, True, True)
 
 
-class _SupConPoolSymmetric(torch.autograd.Function):
+class _SupConPoolSymmetric(_TileSymmetric):
     """aecf_supcon_pool_sym_pass1 / _loss / _grads: the 2 b_local anchors of this rank's pooled supervised contrastive loss from
-    three blocks of logits (a_loc x b_all, a_loc x a_all, b_loc x b_all; the anchor itself left out of the last two by index), the
-    labels shared by the two views.  Modelled on ``_NtXentSymmetric``: the [3, cols] column statistics -- those of the a x b
-    block, plus the b x b row statistics on this rank's own range -- are the one thing ranks exchange, one all-reduce between pass
-    1 and the loss; the gradients on the gathered rows are this rank's shares.  The backward runs the three weights passes and
-    the six gradient products once, scaled on the device by the gradient that arrives and written in the inputs' dtype.  The
-    temperature is a one-element float32 device tensor; the backward returns this rank's share of dL/dT."""
-
-    @staticmethod
-    def forward(ctx, a, b, a_all, b_all, row_labels, col_labels, row_offset, temperature, coef, group, min_temperature):
-        lib = _lib.load()
-        rows, d = a.shape
-        cols = b_all.shape[0]
-        dev = a.device
-        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b.detach().to(torch.bfloat16).contiguous()
-        aa, ba = a_all.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
-        lr, lc = row_labels.contiguous(), col_labels.contiguous()
-        f32 = dict(dtype=torch.float32, device=dev)
-        ws_bytes = lib.aecf_supcon_pool_sym_workspace_bytes(rows, cols, d)
-        if ws_bytes == 0:
-            raise NotImplementedError(f"aecf_amd: the tile form of the pooled supervised contrastive loss needs d % 64 == 0, 64 <= d "
-                                      f"<= 4096 and at most 2^23 gathered rows; got d = {d}, {cols} rows")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        col_stats = torch.empty(3, cols, **f32)
-        t = temperature.detach()
-        tp, t_min = _ptr(t), float(min_temperature)
-        _lib.check(lib.aecf_supcon_pool_sym_pass1(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(aa), _ptr(ba),
-                                                  _ptr(lr), _ptr(lc), _ptr(ws), ws_bytes, _ptr(col_stats), _stream()),
-                   "aecf_supcon_pool_sym_pass1")
-        if dp.world_info(group)[1] > 1:
-            torch.distributed.all_reduce(col_stats, group=group)
-        loss_rows = torch.empty(rows, **f32)
-        _lib.check(lib.aecf_supcon_pool_sym_loss(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(ba), _ptr(col_stats), _ptr(ws),
-                                                 ws_bytes, _ptr(loss_rows), _stream()), "aecf_supcon_pool_sym_loss")
-        ctx.save_for_backward(ac, bc, aa, ba, lr, lc, ws, t)
-        ctx.meta = ((a.dtype, b.dtype, a_all.dtype, b_all.dtype), temperature.shape,
-                    (rows, cols, int(row_offset), d, float(coef), t_min, ws_bytes))
-        return loss_rows.sum() * coef
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        lib = _lib.load()
-        ac, bc, aa, ba, lr, lc, ws, t = ctx.saved_tensors
-        dts, t_shape, (rows, cols, row_offset, d, coef, t_min, ws_bytes) = ctx.meta
-        if getattr(ctx, "_spent", False):
-            raise RuntimeError("aecf_amd: the tile-form pooled supervised contrastive backward runs once per forward (it consumes "
-                               "the stored logits)")
-        ctx._spent = True
-        gdt = torch.bfloat16 if all(x == torch.bfloat16 for x in dts) else torch.float32
-        dev = ac.device
-        d_a, d_b = torch.empty(rows, d, dtype=gdt, device=dev), torch.empty(rows, d, dtype=gdt, device=dev)
-        d_aa, d_ba = torch.empty(cols, d, dtype=gdt, device=dev), torch.empty(cols, d, dtype=gdt, device=dev)
-        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
-        d_t = torch.empty(1, dtype=torch.float32, device=dev) if ctx.needs_input_grad[7] else None
-        _lib.check(lib.aecf_supcon_pool_sym_grads(rows, cols, row_offset, d, _ptr(t), t_min, coef, _ptr(ac), _ptr(bc), _ptr(aa), _ptr(ba),
-                                                  _ptr(lr), _ptr(lc), _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt], _ptr(d_a), _ptr(d_b),
-                                                  _ptr(d_aa), _ptr(d_ba), _ptr(d_t), _stream()), "aecf_supcon_pool_sym_grads")
-        g_t = d_t.reshape(t_shape) if d_t is not None else None
-        return d_a.to(dts[0]), d_b.to(dts[1]), d_aa.to(dts[2]), d_ba.to(dts[3]), None, None, None, g_t, None, None, None
-
-
-def _supcon_pool_tile_refusal(z: torch.Tensor, zb: torch.Tensor, cols: int, min_temperature: float) -> Optional[str]:
-    """None where the tile form of the pooled supervised contrastive loss runs; else what stands against it.  The memory test
-    (three b_local x b_all bfloat16 blocks and the float32 staging within 0.6 of the free device memory) is skipped while a graph
-    is being captured."""
-    rows, d = z.shape
-    if z.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16:
-        return f"bfloat16 rows (got {z.dtype} and {zb.dtype})"
-    if d % 64 != 0 or not 64 <= d <= 4096:
-        return f"d % 64 == 0 with 64 <= d <= 4096 (got d = {d})"
-    if not float(min_temperature) >= MIN_TEMPERATURE:
-        return f"min_temperature >= {MIN_TEMPERATURE} (got {min_temperature}): 1 / T is the constant shift of every exponential"
-    need = _lib.load().aecf_supcon_pool_sym_workspace_bytes(rows, cols, d)
-    if need == 0:
-        return f"at most 2^23 gathered rows (got {cols}): the counts of two blocks add in float32"
-    if not _capturing() and need > 0.6 * torch.cuda.mem_get_info(z.device)[0]:
-        return f"a workspace (three b_local x b_all bfloat16 blocks, {need} bytes here) within 0.6 of the free device memory"
-    return None
+    the three blocks of logits of ``_NtXentSymmetric``, the labels shared by the two views.  The [3, cols] column statistics are
+    those of the a x b block plus the b x b row statistics on this rank's own range."""
+    form = _TileForm("aecf_supcon_pool_sym", operands=("a", "b", "a_all", "b_all"), riders=("row_labels", "col_labels"), options=(),
+                     stats=(3,),
+                     needs="the tile form of the pooled supervised contrastive loss needs d % 64 == 0, 64 <= d <= 4096 and at "
+                           "most 2^23 gathered rows",
+                     backward="tile-form pooled supervised contrastive")
 
 
 def _supcon_pool_tile(za: torch.Tensor, zb: torch.Tensor, labels: torch.Tensor, temperature, group, min_temperature: float,
                       required: bool):
     """The tile form of ``pooled_supervised_contrastive``, or None where it does not run and ``required`` is False (the caller
     then streams)."""
-    if za.shape != zb.shape or za.dim() != 2:
-        raise ValueError(f"pooled_supervised_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and "
-                         f"{tuple(zb.shape)}")
+    _check_two_views("pooled_supervised_contrastive", za, zb)
     labels = _labels_arg(labels, za)
-    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
-        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
-    rank, world = dp.world_info(group)
-    if world > 1:
-        n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
-        got = [torch.zeros_like(n) for _ in range(world)]
-        torch.distributed.all_gather(got, n, group=group)
-        sizes = [int(v.item()) for v in got]
-        offset, b_all = sum(sizes[:rank]), sum(sizes)
-    else:
-        sizes, offset, b_all = None, 0, za.shape[0]
-    refusal = _supcon_pool_tile_refusal(za, zb, b_all, min_temperature)
-    tile = refusal is None
-    if world > 1:                                   # every rank must take the same form (they exchange different things)
-        flag = torch.tensor([1 if tile else 0], device=za.device)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
-        if tile and not bool(int(flag.item())):
-            tile, refusal = False, "the same on every rank (another rank refused it)"
-    if not tile:
+    _check_min_temperature(min_temperature)
+    sizes, offset, b_all = _row_ranges(za.shape[0], za.device, group)
+    # every rank must take the same form (they exchange different things)
+    refusal = _agreed_refusal(_tile_refusal(_POOL_LIMITS, za, zb, b_all, min_temperature), za.device, group)
+    if refusal is not None:
         if required:
             raise NotImplementedError("aecf_amd: the tile form of the pooled supervised contrastive loss needs " + refusal)
         return None
-    t = _temperature_arg(temperature, za, min_temperature)
-    if not isinstance(t, torch.Tensor):
-        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    t = _temperature_scalar(temperature, za, min_temperature)
     lab = labels.detach().to(torch.int64)
     na, nb = l2_normalize(za), l2_normalize(zb)
-    na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
-    nb_all = dp.all_gather_rows(nb, group, sizes=sizes) if world > 1 else nb
-    lab_all = dp.all_gather_rows(lab, group, sizes=sizes) if world > 1 else lab
+    na_all = _all_rows(na, group, sizes)
+    nb_all = _all_rows(nb, group, sizes)
+    lab_all = _all_rows(lab, group, sizes)
     share = _SupConPoolSymmetric.apply(na, nb, na_all, nb_all, lab, lab_all, offset, t, 0.5 / float(b_all), group,
                                        float(min_temperature))
-    if world == 1:
-        return share
-    total = share.detach().clone()
-    torch.distributed.all_reduce(total, group=group)
-    scaled = share * world
-    return scaled + (total - scaled.detach())
+    return _dp_value(share, group)
 
 
 def pooled_supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Tensor,
@@ -1531,103 +1392,24 @@ def pack_label_sets(multi_hot: torch.Tensor) -> torch.Tensor:
     return sets
 
 
-class _SupConMlDirection(torch.autograd.Function):
+class _SupConMlDirection(_StreamDirection):
     """aecf_supcon_ml_fwd_bwd: sum_i [logsumexp_j(q_i.k_j/T) - the w-weighted mean of q_i.k_j/T] * coef for local unit-norm q
     against all k, w(i, j) = 1 for the partner ``row_offset + i`` and the overlap or Jaccard weight of the two rows' class sets
-    (int64 masks) otherwise.  ``_SupConDirection`` with sets for labels: the forward makes the one call with the gradients at
-    upstream 1 and saves them (float32), the backward multiplies them by the gradient that arrives, on the device; ``grads``
-    False takes the call's loss-only mode.  The temperature is a one-element float32 device tensor."""
-
-    @staticmethod
-    def forward(ctx, q, k_all, q_sets, k_sets, weighting, row_offset, temperature, coef, min_temperature, grads):
-        lib = _lib.load()
-        rows, d = q.shape
-        cols = k_all.shape[0]
-        dev = q.device
-        ws_bytes = lib.aecf_supcon_ml_workspace_bytes(rows, cols, d) if q.dtype == torch.bfloat16 and k_all.dtype == torch.bfloat16 else 0
-        if ws_bytes == 0:
-            raise NotImplementedError(f"aecf_amd: the multi-label contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; "
-                                      f"got {q.dtype}, d = {d}")
-        qc, kc = q.detach().contiguous(), k_all.detach().contiguous()
-        sq, sk = q_sets.contiguous(), k_sets.contiguous()
-        f32 = dict(dtype=torch.float32, device=dev)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        loss_rows = torch.empty(rows, **f32)
-        dq = dk = d_t = None
-        if grads:
-            dq, dk = torch.empty(rows, d, **f32), torch.empty(cols, d, **f32)
-            d_t = torch.empty(1, **f32) if ctx.needs_input_grad[6] else None
-        _lib.check(lib.aecf_supcon_ml_fwd_bwd(rows, cols, int(row_offset), d, _ptr(temperature.detach()), float(min_temperature),
-                                              float(coef), _ptr(qc), _ptr(kc), _ptr(sq), _ptr(sk), int(weighting), _ptr(loss_rows),
-                                              _ptr(dq), _ptr(dk), _ptr(d_t), _ptr(ws), ws_bytes, _stream()), "aecf_supcon_ml_fwd_bwd")
-        ctx.save_for_backward(dq, dk, d_t)
-        ctx.meta = (q.dtype, k_all.dtype, temperature.shape)
-        return loss_rows.sum() * coef
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        dq, dk, d_t = ctx.saved_tensors
-        qd, kd, t_shape = ctx.meta
-        g = d_loss.detach().to(torch.float32)
-        g_t = (d_t * g).reshape(t_shape) if d_t is not None else None
-        return (dq * g).to(qd), (dk * g).to(kd), None, None, None, None, g_t, None, None, None
+    (int64 masks) otherwise: ``_SupConDirection`` with sets for labels."""
+    form = _StreamForm("aecf_supcon_ml_fwd_bwd", "aecf_supcon_ml_workspace_bytes", riders=("q_sets", "k_sets"),
+                       options=("weighting",), offsets=("row_offset",), needs="the multi-label contrastive loss needs")
 
 
-class _SupConMlSymmetric(torch.autograd.Function):
+class _SupConMlSymmetric(_TileSymmetric):
     """aecf_supcon_ml_sym_pass1 / _loss / _grads: BOTH directions of the symmetric multi-label contrastive loss from one block of
-    logits (local rows of view a against the gathered rows of view b), the class sets (int64 masks) shared by the two views.
-    ``_SupConSymmetric`` with sets and a weighting for the labels: the column statistics [3, cols] (sums of the exponentials, of
-    the set weights and of weight times raw score) are the one thing ranks exchange, one all-reduce between pass 1 and the loss;
-    the gradient on the gathered keys is this rank's share.  The backward runs the weights pass and the two gradient products
-    once per forward.  The temperature is a one-element float32 device tensor; the backward returns this rank's share of dL/dT."""
-
-    @staticmethod
-    def forward(ctx, a, b_all, row_sets, col_sets, weighting, row_offset, temperature, coef, group, min_temperature):
-        lib = _lib.load()
-        rows, d = a.shape
-        cols = b_all.shape[0]
-        dev = a.device
-        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
-        sr, sc = row_sets.contiguous(), col_sets.contiguous()
-        f32 = dict(dtype=torch.float32, device=dev)
-        ws_bytes = lib.aecf_supcon_ml_sym_workspace_bytes(rows, cols, d)
-        if ws_bytes == 0:
-            raise NotImplementedError(f"aecf_amd: the tile form of the multi-label contrastive loss needs d % 64 == 0, 64 <= d <= "
-                                      f"4096 and at most 2^24 gathered rows; got d = {d}, {cols} rows")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        col_stats = torch.empty(3, cols, **f32)
-        t = temperature.detach()
-        tp, t_min, w = _ptr(t), float(min_temperature), int(weighting)
-        _lib.check(lib.aecf_supcon_ml_sym_pass1(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(sr), _ptr(sc), w,
-                                                _ptr(ws), ws_bytes, _ptr(col_stats), _stream()), "aecf_supcon_ml_sym_pass1")
-        if dp.world_info(group)[1] > 1:
-            torch.distributed.all_reduce(col_stats, group=group)
-        loss_rows = torch.empty(rows, **f32)
-        _lib.check(lib.aecf_supcon_ml_sym_loss(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(col_stats), _ptr(ws),
-                                               ws_bytes, _ptr(loss_rows), _stream()), "aecf_supcon_ml_sym_loss")
-        ctx.save_for_backward(ac, bc, sr, sc, ws, t)
-        ctx.meta = (a.dtype, b_all.dtype, temperature.shape, (rows, cols, int(row_offset), d, float(coef), t_min, ws_bytes, w))
-        return loss_rows.sum() * coef
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        lib = _lib.load()
-        ac, bc, sr, sc, ws, t = ctx.saved_tensors
-        ad, bd, t_shape, (rows, cols, row_offset, d, coef, t_min, ws_bytes, w) = ctx.meta
-        if getattr(ctx, "_spent", False):
-            raise RuntimeError("aecf_amd: the symmetric multi-label contrastive backward runs once per forward (it consumes the "
-                               "stored logits)")
-        ctx._spent = True
-        gdt = torch.bfloat16 if (ad == torch.bfloat16 and bd == torch.bfloat16) else torch.float32
-        da = torch.empty(rows, d, dtype=gdt, device=ac.device)
-        db = torch.empty(cols, d, dtype=gdt, device=ac.device)
-        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
-        d_t = torch.empty(1, dtype=torch.float32, device=ac.device) if ctx.needs_input_grad[6] else None
-        _lib.check(lib.aecf_supcon_ml_sym_grads(rows, cols, row_offset, d, _ptr(t), t_min, coef, _ptr(ac), _ptr(bc), _ptr(sr), _ptr(sc),
-                                                w, _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt], _ptr(da), _ptr(db), _ptr(d_t),
-                                                _stream()), "aecf_supcon_ml_sym_grads")
-        g_t = d_t.reshape(t_shape) if d_t is not None else None
-        return da.to(ad), db.to(bd), None, None, None, None, g_t, None, None, None
+    logits (local rows of view a against the gathered rows of view b), the class sets (int64 masks) shared by the two views:
+    ``_SupConSymmetric`` with sets and a weighting for the labels.  The column statistics [3, cols] are the sums of the
+    exponentials, of the set weights and of weight times raw score."""
+    form = _TileForm("aecf_supcon_ml_sym", operands=("a", "b_all"), riders=("row_sets", "col_sets"), options=("weighting",),
+                     stats=(3,),
+                     needs="the tile form of the multi-label contrastive loss needs d % 64 == 0, 64 <= d <= 4096 and at most "
+                           "2^24 gathered rows",
+                     backward="symmetric multi-label contrastive")
 
 
 def multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets: torch.Tensor, weighting: str = "overlap",
@@ -1671,8 +1453,7 @@ def multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets: torch
         raise ValueError(f"aecf_amd: weighting must be 'overlap' or 'jaccard', got {weighting!r}")
     _require_device(za, "za")
     _require_device(zb, "zb")
-    if za.shape != zb.shape or za.dim() != 2:
-        raise ValueError(f"multilabel_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and {tuple(zb.shape)}")
+    _check_two_views("multilabel_contrastive", za, zb)
     label_sets = _label_sets_arg(label_sets, za)
     if low_memory not in (True, False, None):
         raise ValueError(f"aecf_amd: low_memory must be True, False or None, got {low_memory!r}")
@@ -1680,119 +1461,46 @@ def multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets: torch
     if low_memory is True and not streams:
         raise NotImplementedError(f"aecf_amd: the multi-label contrastive loss needs bfloat16 rows with d in {SUPCON_WIDTHS}; got "
                                   f"{za.dtype} and {zb.dtype}, d = {za.shape[1]}")
-    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
-        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
-    rank, world = dp.world_info(group)
-    if world > 1:
-        n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
-        got = [torch.zeros_like(n) for _ in range(world)]
-        torch.distributed.all_gather(got, n, group=group)
-        sizes = [int(v.item()) for v in got]
-        offset, b_all = sum(sizes[:rank]), sum(sizes)
-    else:
-        sizes, offset, b_all = None, 0, za.shape[0]
+    _check_min_temperature(min_temperature)
+    sizes, offset, b_all = _row_ranges(za.shape[0], za.device, group)
     tile = False
     if low_memory is not True:
-        # (the two tile forms share their served shapes and their workspace)
-        refusal = _supcon_tile_refusal(za, zb, b_all, min_temperature)
+        # every rank must take the same form (they exchange different things); the single-label limits: the two tile forms
+        # share their served shapes and their workspace
+        refusal = _agreed_refusal(_tile_refusal(_SUPCON_LIMITS, za, zb, b_all, min_temperature), za.device, group)
         tile = refusal is None
-        if world > 1:                               # every rank must take the same form (they exchange different things)
-            flag = torch.tensor([1 if tile else 0], device=za.device)
-            torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
-            if tile and not bool(int(flag.item())):
-                tile, refusal = False, "the same on every rank (another rank refused it)"
         if not tile and (low_memory is False or not streams):
             raise NotImplementedError("aecf_amd: the tile form of the multi-label contrastive loss needs " + refusal
                                       + ("" if low_memory is False else f"; the streaming form needs bfloat16 rows with d in "
                                          f"{SUPCON_WIDTHS}, got {za.dtype} and {zb.dtype}, d = {za.shape[1]}"))
-    t = _temperature_arg(temperature, za, min_temperature)
-    if not isinstance(t, torch.Tensor):
-        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    t = _temperature_scalar(temperature, za, min_temperature)
     sets = label_sets.detach() if label_sets.dim() == 1 else pack_label_sets(label_sets)
     na, nb = l2_normalize(za), l2_normalize(zb)
-    nb_all = dp.all_gather_rows(nb, group, sizes=sizes) if world > 1 else nb
-    sets_all = dp.all_gather_rows(sets, group, sizes=sizes) if world > 1 else sets
+    nb_all = _all_rows(nb, group, sizes)
+    sets_all = _all_rows(sets, group, sizes)
     coef = 0.5 / float(b_all)
     w = SET_WEIGHTINGS[weighting]
     if tile:
         # both directions from the one block of logits this rank owns: view a is never gathered
         share = _SupConMlSymmetric.apply(na, nb_all, sets, sets_all, w, offset, t, coef, group, float(min_temperature))
     else:
-        na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
+        na_all = _all_rows(na, group, sizes)
         grads = torch.is_grad_enabled() and any(x.requires_grad for x in (na, nb, t))
         l_ab = _SupConMlDirection.apply(na, nb_all, sets, sets_all, w, offset, t, coef, float(min_temperature), grads)
         l_ba = _SupConMlDirection.apply(nb, na_all, sets, sets_all, w, offset, t, coef, float(min_temperature), grads)
         share = l_ab + l_ba              # this rank's rows' share of the global objective
-    if world == 1:
-        return share
-    total = share.detach().clone()
-    torch.distributed.all_reduce(total, group=group)
-    scaled = share * world
-    return scaled + (total - scaled.detach())
+    return _dp_value(share, group)
 
 
-class _SupConMlPoolSymmetric(torch.autograd.Function):
+class _SupConMlPoolSymmetric(_TileSymmetric):
     """aecf_supcon_ml_pool_sym_pass1 / _loss / _grads: the 2 b_local anchors of this rank's pooled multi-label contrastive loss
-    from three blocks of logits (a_loc x b_all, a_loc x a_all, b_loc x b_all; the anchor itself left out of the last two by index),
-    the class sets (int64 masks) shared by the two views.  ``_SupConPoolSymmetric`` with sets and a weighting for the labels: the
-    [3, cols] column statistics -- those of the a x b block, plus the b x b row statistics on this rank's own range -- are the one
-    thing ranks exchange, one all-reduce between pass 1 and the loss; the gradients on the gathered rows are this rank's shares.
-    The backward runs the three weights passes and the six gradient products once, scaled on the device by the gradient that
-    arrives and written in the inputs' dtype.  The temperature is a one-element float32 device tensor; the backward returns this
-    rank's share of dL/dT."""
-
-    @staticmethod
-    def forward(ctx, a, b, a_all, b_all, row_sets, col_sets, weighting, row_offset, temperature, coef, group, min_temperature):
-        lib = _lib.load()
-        rows, d = a.shape
-        cols = b_all.shape[0]
-        dev = a.device
-        ac, bc = a.detach().to(torch.bfloat16).contiguous(), b.detach().to(torch.bfloat16).contiguous()
-        aa, ba = a_all.detach().to(torch.bfloat16).contiguous(), b_all.detach().to(torch.bfloat16).contiguous()
-        sr, sc = row_sets.contiguous(), col_sets.contiguous()
-        f32 = dict(dtype=torch.float32, device=dev)
-        ws_bytes = lib.aecf_supcon_ml_pool_sym_workspace_bytes(rows, cols, d)
-        if ws_bytes == 0:
-            raise NotImplementedError(f"aecf_amd: the pooled multi-label contrastive loss needs d % 64 == 0, 64 <= d <= 4096 and at "
-                                      f"most 2^23 gathered rows; got d = {d}, {cols} rows")
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        col_stats = torch.empty(3, cols, **f32)
-        t = temperature.detach()
-        tp, t_min, w = _ptr(t), float(min_temperature), int(weighting)
-        _lib.check(lib.aecf_supcon_ml_pool_sym_pass1(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(bc), _ptr(aa), _ptr(ba),
-                                                     _ptr(sr), _ptr(sc), w, _ptr(ws), ws_bytes, _ptr(col_stats), _stream()),
-                   "aecf_supcon_ml_pool_sym_pass1")
-        if dp.world_info(group)[1] > 1:
-            torch.distributed.all_reduce(col_stats, group=group)
-        loss_rows = torch.empty(rows, **f32)
-        _lib.check(lib.aecf_supcon_ml_pool_sym_loss(rows, cols, int(row_offset), d, tp, t_min, _ptr(ac), _ptr(ba), _ptr(col_stats),
-                                                    _ptr(ws), ws_bytes, _ptr(loss_rows), _stream()), "aecf_supcon_ml_pool_sym_loss")
-        ctx.save_for_backward(ac, bc, aa, ba, sr, sc, ws, t)
-        ctx.meta = ((a.dtype, b.dtype, a_all.dtype, b_all.dtype), temperature.shape,
-                    (rows, cols, int(row_offset), d, float(coef), t_min, ws_bytes, w))
-        return loss_rows.sum() * coef
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        lib = _lib.load()
-        ac, bc, aa, ba, sr, sc, ws, t = ctx.saved_tensors
-        dts, t_shape, (rows, cols, row_offset, d, coef, t_min, ws_bytes, w) = ctx.meta
-        if getattr(ctx, "_spent", False):
-            raise RuntimeError("aecf_amd: the pooled multi-label contrastive backward runs once per forward (it consumes the stored "
-                               "logits)")
-        ctx._spent = True
-        gdt = torch.bfloat16 if all(x == torch.bfloat16 for x in dts) else torch.float32
-        dev = ac.device
-        d_a, d_b = torch.empty(rows, d, dtype=gdt, device=dev), torch.empty(rows, d, dtype=gdt, device=dev)
-        d_aa, d_ba = torch.empty(cols, d, dtype=gdt, device=dev), torch.empty(cols, d, dtype=gdt, device=dev)
-        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
-        d_t = torch.empty(1, dtype=torch.float32, device=dev) if ctx.needs_input_grad[8] else None
-        _lib.check(lib.aecf_supcon_ml_pool_sym_grads(rows, cols, row_offset, d, _ptr(t), t_min, coef, _ptr(ac), _ptr(bc), _ptr(aa),
-                                                     _ptr(ba), _ptr(sr), _ptr(sc), w, _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt],
-                                                     _ptr(d_a), _ptr(d_b), _ptr(d_aa), _ptr(d_ba), _ptr(d_t), _stream()),
-                   "aecf_supcon_ml_pool_sym_grads")
-        g_t = d_t.reshape(t_shape) if d_t is not None else None
-        return d_a.to(dts[0]), d_b.to(dts[1]), d_aa.to(dts[2]), d_ba.to(dts[3]), None, None, None, None, g_t, None, None, None
+    from the three blocks of logits of ``_NtXentSymmetric``, the class sets (int64 masks) shared by the two views:
+    ``_SupConPoolSymmetric`` with sets and a weighting for the labels."""
+    form = _TileForm("aecf_supcon_ml_pool_sym", operands=("a", "b", "a_all", "b_all"), riders=("row_sets", "col_sets"),
+                     options=("weighting",), stats=(3,),
+                     needs="the pooled multi-label contrastive loss needs d % 64 == 0, 64 <= d <= 4096 and at most 2^23 gathered "
+                           "rows",
+                     backward="pooled multi-label contrastive")
 
 
 def pooled_multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets: torch.Tensor, weighting: str = "overlap",
@@ -1830,46 +1538,24 @@ def pooled_multilabel_contrastive(za: torch.Tensor, zb: torch.Tensor, label_sets
         raise ValueError(f"aecf_amd: weighting must be 'overlap' or 'jaccard', got {weighting!r}")
     _require_device(za, "za")
     _require_device(zb, "zb")
-    if za.shape != zb.shape or za.dim() != 2:
-        raise ValueError(f"pooled_multilabel_contrastive expects two [b, d] tensors of equal shape, got {tuple(za.shape)} and "
-                         f"{tuple(zb.shape)}")
+    _check_two_views("pooled_multilabel_contrastive", za, zb)
     label_sets = _label_sets_arg(label_sets, za)
-    if not (isinstance(min_temperature, (int, float)) and float(min_temperature) > 0.0):
-        raise ValueError(f"aecf_amd: min_temperature must be a positive float, got {min_temperature!r}")
-    rank, world = dp.world_info(group)
-    if world > 1:
-        n = torch.tensor([za.shape[0]], device=za.device, dtype=torch.int64)
-        got = [torch.zeros_like(n) for _ in range(world)]
-        torch.distributed.all_gather(got, n, group=group)
-        sizes = [int(v.item()) for v in got]
-        offset, b_all = sum(sizes[:rank]), sum(sizes)
-    else:
-        sizes, offset, b_all = None, 0, za.shape[0]
-    # (the two pooled tile forms share their served shapes and their workspace)
-    refusal = _supcon_pool_tile_refusal(za, zb, b_all, min_temperature)
-    if world > 1:                                   # every rank must agree (a rank that refused would leave the others waiting)
-        flag = torch.tensor([1 if refusal is None else 0], device=za.device)
-        torch.distributed.all_reduce(flag, op=torch.distributed.ReduceOp.MIN, group=group)
-        if refusal is None and not bool(int(flag.item())):
-            refusal = "the same on every rank (another rank refused it)"
+    _check_min_temperature(min_temperature)
+    sizes, offset, b_all = _row_ranges(za.shape[0], za.device, group)
+    # every rank must agree (a rank that refused would leave the others waiting); the single-label limits: the two pooled tile
+    # forms share their served shapes and their workspace
+    refusal = _agreed_refusal(_tile_refusal(_POOL_LIMITS, za, zb, b_all, min_temperature), za.device, group)
     if refusal is not None:
         raise NotImplementedError("aecf_amd: the pooled multi-label contrastive loss (a tile form only) needs " + refusal)
-    t = _temperature_arg(temperature, za, min_temperature)
-    if not isinstance(t, torch.Tensor):
-        t = torch.full((1,), t, dtype=torch.float32, device=za.device)
+    t = _temperature_scalar(temperature, za, min_temperature)
     sets = label_sets.detach() if label_sets.dim() == 1 else pack_label_sets(label_sets)
     na, nb = l2_normalize(za), l2_normalize(zb)
-    na_all = dp.all_gather_rows(na, group, sizes=sizes) if world > 1 else na
-    nb_all = dp.all_gather_rows(nb, group, sizes=sizes) if world > 1 else nb
-    sets_all = dp.all_gather_rows(sets, group, sizes=sizes) if world > 1 else sets
+    na_all = _all_rows(na, group, sizes)
+    nb_all = _all_rows(nb, group, sizes)
+    sets_all = _all_rows(sets, group, sizes)
     share = _SupConMlPoolSymmetric.apply(na, nb, na_all, nb_all, sets, sets_all, SET_WEIGHTINGS[weighting], offset, t,
                                          0.5 / float(b_all), group, float(min_temperature))
-    if world == 1:
-        return share
-    total = share.detach().clone()
-    torch.distributed.all_reduce(total, group=group)
-    scaled = share * world
-    return scaled + (total - scaled.detach())
+    return _dp_value(share, group)
 
 
 class RetrievalRanks(NamedTuple):
