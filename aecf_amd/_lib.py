@@ -245,6 +245,18 @@ _SYMBOLS = [
     ("aecf_nce_multi_masked_grads", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
       c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # multi-view InfoNCE with a temperature and a weight per pair (pres pointers NULL: no view is missing)
+    ("aecf_nce_multi_pp_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32]),
+    ("aecf_nce_multi_pp_pair_coef", c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("aecf_nce_multi_pp_pass1", c_int,
+     [c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+      c_size_t, c_void_p, c_void_p]),
+    ("aecf_nce_multi_pp_loss", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("aecf_nce_multi_pp_grads", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("aecf_l2norm_masked_forward", c_int,
      [c_int64, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("aecf_l2norm_masked_backward", c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1183,6 +1183,66 @@ int aecf_nce_multi_masked_grads(int64_t rows, int64_t cols, int64_t row_offset, 
     return launch_status();
 }
 
+// ---- multi-view InfoNCE with a temperature and a weight per pair (include/aecf_hip.h, "multi-view InfoNCE, per pair")
+
+size_t aecf_nce_multi_pp_workspace_bytes(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, 0.025f) || !nce_multi_supported(d, 0.025f, cols, views, anchor)) return 0;
+    return nce_multi_pp_workspace_bytes(rows, cols, d, views, anchor);
+}
+
+int aecf_nce_multi_pp_pair_coef(int64_t cols, int32_t views, int32_t anchor, const uint8_t* pres_all, const float* pair_weights,
+                                float* pair_coef, void* stream) {
+    if (cols <= 0 || cols > 0x7fffffff || views < 2 || views > 8 || anchor < -1 || anchor >= views) return AECF_ERR_BAD_DIMS;
+    if (!pair_coef) return AECF_ERR_NULL_POINTER;
+    launch_nce_multi_pp_pair_coef(cols, views, anchor, pres_all, pair_weights, pair_coef, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_nce_multi_pp_pass1(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor, const float* temperatures,
+                            float min_temperature, const void* x_loc, const void* x_all, const uint8_t* pres_loc,
+                            const uint8_t* pres_all, int32_t with_dt, void* workspace, size_t workspace_bytes, float* col_sums,
+                            void* stream) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, min_temperature)) return AECF_ERR_BAD_DIMS;
+    if (!nce_multi_supported(d, min_temperature, cols, views, anchor)) return AECF_ERR_UNSUPPORTED;
+    if (!temperatures || !x_loc || !x_all || !workspace || !col_sums || !pres_loc != !pres_all) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_multi_pp_workspace_bytes(rows, cols, d, views, anchor)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperatures, min_temperature, nullptr};
+    launch_nce_multi_pp_pass1(rows, cols, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, with_dt, workspace, col_sums,
+                              (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_nce_multi_pp_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                           const float* temperatures, float min_temperature, const void* x_loc, const void* x_all,
+                           const uint8_t* pres_loc, const uint8_t* pres_all, const float* col_sums, void* workspace,
+                           size_t workspace_bytes, float* loss_rows, void* stream) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, min_temperature)) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!nce_multi_supported(d, min_temperature, cols, views, anchor)) return AECF_ERR_UNSUPPORTED;
+    if (!temperatures || !x_loc || !x_all || !col_sums || !workspace || !loss_rows || !pres_loc != !pres_all) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_multi_pp_workspace_bytes(rows, cols, d, views, anchor)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperatures, min_temperature, nullptr};
+    launch_nce_multi_pp_loss(rows, cols, row_offset, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, col_sums, workspace,
+                             loss_rows, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_nce_multi_pp_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                            const float* temperatures, float min_temperature, const float* pair_coef, const void* x_loc,
+                            const void* x_all, const uint8_t* pres_loc, void* workspace, size_t workspace_bytes, const float* upstream,
+                            int32_t grad_dtype, void* dx_loc, void* dx_all, float* d_temperatures, void* stream) {
+    if (nce_multi_bad_dims(rows, cols, d, views, anchor, min_temperature)) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset + rows > cols) return AECF_ERR_BAD_DIMS;
+    if (!nce_multi_supported(d, min_temperature, cols, views, anchor)) return AECF_ERR_UNSUPPORTED;
+    if (grad_dtype != AECF_BF16 && grad_dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!temperatures || !pair_coef || !x_loc || !x_all || !workspace || !dx_loc || !dx_all) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < nce_multi_pp_workspace_bytes(rows, cols, d, views, anchor)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperatures, min_temperature, d_temperatures};
+    launch_nce_multi_pp_grads(rows, cols, row_offset, d, views, anchor, dt, pair_coef, pres_loc, x_loc, x_all, workspace, upstream,
+                              grad_dtype == AECF_BF16 ? 1 : 0, dx_loc, dx_all, (hipStream_t)stream);
+    return launch_status();
+}
+
 // ---- pooled supervised contrastive loss on the tile GEMMs (include/aecf_hip.h, "pooled supervised contrastive loss, tile-GEMM form")
 
 size_t aecf_supcon_pool_sym_workspace_bytes(int64_t rows, int64_t cols, int32_t d) {

@@ -396,6 +396,21 @@ void launch_nce_multi_masked_loss(int64_t rows, int64_t cols, int64_t row_offset
 void launch_nce_multi_masked_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
                                    const float* pair_coef, const unsigned char* pres_loc, const void* x_loc, const void* x_all,
                                    void* workspace, const float* upstream, int out_bf16, void* dx_loc, void* dx_all, hipStream_t s);
+// The same with a temperature and a weight PER PAIR: dt.t and dt.d_t are [P] arrays in pair order, pair_coef [P] comes from
+// launch_nce_multi_pp_pair_coef (weights NULL: uniform; pres_all NULL: no view is missing), pres_loc / pres_all may be NULL (every
+// row holds every view).  with_dt: pass 1 also leaves the per-pair dT sums that launch_nce_multi_pp_grads needs to write dt.d_t.
+size_t nce_multi_pp_workspace_bytes(int64_t rows, int64_t cols, int d, int views, int anchor);
+void launch_nce_multi_pp_pair_coef(int64_t cols, int views, int anchor, const unsigned char* pres_all, const float* weights,
+                                   float* pair_coef, hipStream_t s);
+void launch_nce_multi_pp_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
+                               const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all, int with_dt,
+                               void* workspace, float* col_sums, hipStream_t s);
+void launch_nce_multi_pp_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                              const void* x_loc, const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all,
+                              const float* col_sums, void* workspace, float* loss_rows, hipStream_t s);
+void launch_nce_multi_pp_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                               const float* pair_coef, const unsigned char* pres_loc, const void* x_loc, const void* x_all,
+                               void* workspace, const float* upstream, int out_bf16, void* dx_loc, void* dx_all, hipStream_t s);
 
 // Pooled supervised contrastive loss on the tile GEMMs (aecf_nce_gemm.hip): NT-Xent's three blocks with the label statistics of the
 // supervised loss -- X runs EPI_SUP, Y and Z EPI_SUP_SELF (rows only, the anchor excluded by index).  col_stats [3][cols] (X's column

@@ -158,6 +158,22 @@
 // gradient products (nce_multi_product_kernel), nce_dtemp_kernel and nce_multi_finish_kernel are reused as they are: an excluded
 // weight is a zero, and the caller's normalised rows hold zeros in the absent slots (aecf_l2norm_masked_forward), so 0 * key = 0.
 // No K loop is skipped: a masked pair costs a full pair (a compacting form is not built).
+//
+// Multi-view InfoNCE with a temperature and a weight per pair (aecf_nce_multi_pp_pair_coef / _pass1 / _loss / _grads) is either form
+// above (presence bytes given or NULL) with temp [P] and pair_coef [P] in place of one T and one coef.  The logits pass is
+// nce_multi_pp_logits_kernel -- nce_multi_logits_kernel with p.temp advanced by the pair, so scale2 / shift2 are the pair's; equal
+// bits of T give the bits of the one-temperature pass.  nce_multi_pp_pair_coef_kernel normalises the weights over the pairs that
+// have a row (0.5 / n_p / (W / w_p), float64, rounded once: equal weights give 0.5 / n_p / P' to the bit; zeros by select, no
+// 0 / 0); finalize and weights kernels of their own read temp[pair] and pair_coef[pair].  W_p carries coef_p / T_p, so the gradient
+// products and the slab sum are reused as they are, da in its plain EPI_OUT form: dT cannot come from it, because its K loop has
+// summed over every partner block of a view.  dT per pair instead: where the temperatures want a gradient the logits pass runs
+// EPI_EXP_DTS / EPI_EXP_MASK_S, which sweep the float32 accumulators once more IN FRONT of the E sweep and leave partials of
+// RS_i = sum_j E_ij (s_ij - 1) and CS_j = sum_i E_ij (s_ij - 1) laid out like the partials of E (E the float32 exponential, excluded
+// elements by the same selects); nce_multi_sums_kernel reduces them in a second launch, the finalize kernel keeps s_ii - 1, and
+// nce_multi_pp_dtemp_kernel (one block per pair, fixed order) forms
+//   dL/dT_p = -(coef_p upstream / T_p^2) [ sum_i RS_i / l_i + sum_j CS_j / c_j - 2 sum_i (s_ii - 1) ]
+// with c the all-reduced column sums: a rank's local column partials times the global 1 / c, so the ranks' shares add up to the
+// gradient with no further exchange.  Nothing is recovered from the stored bf16 E.
 #include <math.h>
 #include <type_traits>
 
@@ -180,7 +196,7 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // sum of the raw accumulators of the elements that match by label (the partner and the padding excluded)
 enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8,
        EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11, EPI_EXP_SELF = 12, EPI_SUP_SELF = 13,
-       EPI_SETS_OV_SELF = 14, EPI_SETS_JAC_SELF = 15, EPI_EXP_MASK = 16 };
+       EPI_SETS_OV_SELF = 14, EPI_SETS_JAC_SELF = 15, EPI_EXP_MASK = 16, EPI_EXP_DTS = 17, EPI_EXP_MASK_S = 18 };
 // EPI_SETS_OV / EPI_SETS_JAC (multi-label contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the
 // float32 sums of w and of w * raw accumulator, w the overlap / Jaccard weight of the two class sets (partner and padding excluded)
 constexpr bool epi_is_sets(int epi) { return epi == EPI_SETS_OV || epi == EPI_SETS_JAC; }
@@ -201,6 +217,11 @@ constexpr bool epi_has_labels(int epi) { return epi == EPI_SUP || epi == EPI_SUP
 // the column sum -- wherever the row or the column lacks a view of the block's pair: pres_row / pres_col hold one byte per row /
 // column (bit v = view v present), pres_need the two bits of the pair.  Excluded by a select on the byte, never by value.  A block
 // whose 256 rows and 256 columns all hold both views runs EPI_EXP_DT's path; the others take the branch of the ragged edge.
+// EPI_EXP_DTS / EPI_EXP_MASK_S (multi-view InfoNCE with a temperature per pair that wants its gradient, logits pass): EPI_EXP_DT /
+// EPI_EXP_MASK to the bit, then a second sweep over the accumulators that leaves the float32 sums of E_ij (s_ij - 1) per row and
+// per column of the tile in rowsx_part / colsx_part (laid out like rowsum_part / colsum_part): the dT sums of that pair.
+constexpr bool epi_is_mask(int epi) { return epi == EPI_EXP_MASK || epi == EPI_EXP_MASK_S; }
+constexpr bool epi_has_ts(int epi) { return epi == EPI_EXP_DTS || epi == EPI_EXP_MASK_S; }
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -430,6 +451,31 @@ __global__ __launch_bounds__(512, 2) void nce_multi_logits_kernel(NceGemmArgs p,
     p.rowsum_part += pair * mv.rowsum_stride;
     p.colsum_part += pair * mv.colsum_stride;
     if (EPI == EPI_EXP_MASK) p.pres_need = (1u << mv.m[pair]) | (1u << mv.n[pair]);
+    constexpr int AM = OP_ROW, BM = OP_ROW, MAP = MAP_2D;
+    constexpr bool MULTI = false;
+    const unsigned int vblock = blockIdx.x - pair * mv.blocks_per_pair;
+    const NceSegs ms = {};
+#include "aecf_nce_gemm_body.h"
+}
+
+// The logits pass with a temperature PER PAIR (aecf_nce_multi_pp_*): nce_multi_logits_kernel with p.temp advanced to the pair's
+// own element, so the epilogue derives scale2 / shift2 from that pair's T -- equal bits of T give the bits of the kernel above.
+// EPI_EXP_DT / EPI_EXP_MASK: nothing else.  EPI_EXP_DTS / EPI_EXP_MASK_S: the partials of the dT sums too, pair p's behind pair 0's
+// by the strides of the partials of E.  A kernel of its own: the one above keeps its code.
+template <int EPI>
+__global__ __launch_bounds__(512, 2) void nce_multi_pp_logits_kernel(NceGemmArgs p, NceMultiLogits mv) {
+    const unsigned int pair = blockIdx.x / mv.blocks_per_pair;
+    p.a += mv.m[pair] * mv.view_bytes;
+    p.b += mv.n[pair] * mv.view_bytes;
+    p.e += pair * mv.e_stride;
+    p.rowsum_part += pair * mv.rowsum_stride;
+    p.colsum_part += pair * mv.colsum_stride;
+    p.temp += pair;
+    if (epi_has_ts(EPI)) {
+        p.rowsx_part += pair * mv.rowsum_stride;
+        p.colsx_part += pair * mv.colsum_stride;
+    }
+    if (epi_is_mask(EPI)) p.pres_need = (1u << mv.m[pair]) | (1u << mv.n[pair]);
     constexpr int AM = OP_ROW, BM = OP_ROW, MAP = MAP_2D;
     constexpr bool MULTI = false;
     const unsigned int vblock = blockIdx.x - pair * mv.blocks_per_pair;
@@ -750,6 +796,152 @@ __global__ __launch_bounds__(256) void nce_multi_masked_weights_kernel(unsigned 
         x[k] = ct * wv;
     }
     *ptr = Tr<BF16>::pack(x);
+}
+
+// ---- multi-view InfoNCE with a temperature and a weight per pair (aecf_nce_multi_pp_*): the small kernels.  They have bodies of
+// their own; the kernels of the one-temperature forms above keep their code.
+
+// pair_coef[p] = 0.5 / n_p * w_p / W in float32, W = the sum of the weights of the pairs with n_p > 0 (pair order, float64); formed
+// as 0.5 / n_p / (W / w_p) in float64 and rounded once, so equal weights give the 0.5 / n_p / P' of nce_multi_pair_coef_kernel to
+// the bit.  0 where n_p = 0, where w_p = 0 and where W = 0 (no 0 / 0).  pres_all NULL: every row holds every view, n_p = cols.
+// weights NULL: every w_p = 1.  One block; the counts are nce_multi_pair_coef_kernel's integer histogram.
+__global__ __launch_bounds__(256) void nce_multi_pp_pair_coef_kernel(const unsigned char* pres_all, int64_t cols, NceMultiFin mv, int pairs,
+                                                                     const float* weights, float* pair_coef) {
+    __shared__ int hist[256];
+    __shared__ int n_p[MV_MAX_PAIRS];
+    hist[threadIdx.x] = 0;
+    __syncthreads();
+    if (pres_all)
+        for (int64_t j = threadIdx.x; j < cols; j += 256) atomicAdd(&hist[pres_all[j]], 1);
+    __syncthreads();
+    if ((int)threadIdx.x < pairs) {
+        const unsigned int need = (1u << mv.m[threadIdx.x]) | (1u << mv.n[threadIdx.x]);
+        int n = (int)cols;
+        if (pres_all) {
+            n = 0;
+            for (unsigned int b = 0; b < 256; ++b) n += (b & need) == need ? hist[b] : 0;
+        }
+        n_p[threadIdx.x] = n;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < pairs) {
+        double total = 0.0;
+        for (int q = 0; q < pairs; ++q) total += n_p[q] > 0 ? (weights ? (double)weights[q] : 1.0) : 0.0;
+        const int n = n_p[threadIdx.x];
+        const double wp = weights ? (double)weights[threadIdx.x] : 1.0;
+        pair_coef[threadIdx.x] = (n > 0 && wp > 0.0 && total > 0.0) ? (float)(0.5 / (double)n / (total / wp)) : 0.f;
+    }
+}
+
+// nce_multi_finalize_kernel / nce_multi_masked_finalize_kernel (pres_loc NULL / not) at the pair's own temperature temp[pair],
+// operation for operation; sdiag [P][Rp] (may be NULL) takes s_ii - 1 of every row of the pair in float32, 0 outside V_p: the
+// positives' term of the dT sums.
+__global__ __launch_bounds__(256) void nce_multi_pp_finalize_kernel(NceFinArgs p, NceMultiFin mv, const unsigned char* pres_loc,
+                                                                    const unsigned char* pres_all, float* sdiag) {
+    const int64_t pair = blockIdx.y, ld = (int64_t)mv.views * p.d;
+    const unsigned int need = (1u << mv.m[pair]) | (1u << mv.n[pair]);
+    const float inv_temp = nce_dev_inv_temp(p.temp + pair, p.min_temp);
+    const float* c = p.c + pair * p.cols;
+    const int lane = lane_id();
+    const int64_t i = (int64_t)blockIdx.x * 4 + wave_id();
+    if (i < p.rows && (!pres_loc || (pres_loc[i] & need) == need)) {
+        const unsigned short* ap = p.a + i * ld + mv.m[pair] * p.d;
+        const unsigned short* bp = p.b + (p.row_offset + i) * ld + mv.n[pair] * p.d;
+        float dot = 0.f;
+        for (int k = lane; k < p.d; k += 64) dot = fmaf(Tr<BF16>::to_f32(ap[k]), Tr<BF16>::to_f32(bp[k]), dot);
+        dot = reduce_wave(dot);
+        if (lane == 0) {
+            const float li = p.l[pair * p.Rp + i];
+            p.u[pair * p.Rp + i] = 1.0f / li;
+            p.ediag[pair * p.Rp + i] = __builtin_amdgcn_exp2f((dot - 1.0f) * inv_temp * 1.4426950408889634f);
+            float loss = nce_row_term(li, inv_temp, dot);
+            loss += nce_col_term(c[p.row_offset + i], inv_temp, dot);
+            p.loss_rows[pair * p.rows + i] = loss;
+            if (sdiag) sdiag[pair * p.Rp + i] = dot - 1.0f;
+        }
+    } else if (i < p.Rp) {
+        if (lane == 0) {
+            p.u[pair * p.Rp + i] = 0.f;
+            p.ediag[pair * p.Rp + i] = 0.f;
+            if (i < p.rows) p.loss_rows[pair * p.rows + i] = 0.f;
+            if (sdiag) sdiag[pair * p.Rp + i] = 0.f;
+        }
+    }
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.Cp; j += (int64_t)gridDim.x * 256)
+        p.v[pair * p.Cp + j] = (j < p.cols && (!pres_all || (pres_all[j] & need) == need)) ? 1.0f / c[j] : 0.f;
+}
+
+// nce_multi_masked_weights_kernel at the pair's own temperature: ct = pair_coef[pair] / max(temp[pair], min_temp), the partner term
+// for the rows of V_p alone (pres_loc NULL: every row).  The arithmetic of an element is nce_weights_body's.
+__global__ __launch_bounds__(256) void nce_multi_pp_weights_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
+                                                                   const float* v, const float* ediag, int64_t rows, int64_t row_offset,
+                                                                   const float* pair_coef, const NceMultiFin mv,
+                                                                   const unsigned char* pres_loc, const float* upstream,
+                                                                   const float* temp, float min_temp) {
+    const int64_t pair = blockIdx.y, Rp = m_tiles * BT, Cp = e_tiles * 64;
+    const unsigned int need = (1u << mv.m[pair]) | (1u << mv.n[pair]);
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;         // 16-byte chunk: 2048 per tile, 8 per tile row
+    if (id >= m_tiles * e_tiles * 2048) return;
+    e += pair * Rp * Cp; u += pair * Rp; v += pair * Cp; ediag += pair * Rp;
+    float ct = pair_coef[pair] * nce_dev_inv_temp(temp + pair, min_temp);
+    const int64_t tile = id >> 11;
+    const int within = (int)(id & 2047);
+    const int64_t i = (tile / e_tiles) * BT + (within >> 3), j0 = (tile % e_tiles) * 64 + 8 * (within & 7);
+    u32x4* ptr = reinterpret_cast<u32x4*>(e) + id;
+    const u32x4 raw = *ptr;
+    const float ui = u[i];
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(v + j0), v1 = *reinterpret_cast<const f32x4*>(v + j0 + 4);
+    float x[8];
+    Tr<BF16>::unpack(raw, x);
+    const float vv[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    const bool in_pair = i < rows && (!pres_loc || (pres_loc[i] & need) == need);
+    const int64_t jp = in_pair ? row_offset + i - j0 : -1;
+    if (upstream) ct *= upstream[0];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        float wv = x[k] * (ui + vv[k]);
+        if (jp == k) wv = ediag[i] * (ui + vv[k]) - 2.0f;
+        x[k] = ct * wv;
+    }
+    *ptr = Tr<BF16>::pack(x);
+}
+
+// d_temp[p] for pair blockIdx.x, this rank's share:
+//   dL/dT_p = -(coef_p upstream / Tc_p^2) [ sum_i u_i RS_i + sum_j v_j CS_j - 2 sum_i (s_ii - 1) ],   0 where temp[p] < min_temp
+// RS [P][Rp] / CS [P][cols]: this rank's row / column sums of E (s - 1) (the reduced partials of EPI_EXP_DTS); u, sdiag [P][Rp],
+// v [P][Cp] -- v from the all-reduced column sums.  Rows and columns outside the pair (padding, absent views) hold u = 0 / v = 0 and
+// zero sums.  Every term float32, never the stored bf16 E.  Fixed order: 256 strided sums per term, then a fixed tree; a pair with
+// coef_p = 0 is written as an exact 0 by a select.
+__global__ __launch_bounds__(256) void nce_multi_pp_dtemp_kernel(const float* rs, const float* cs, const float* u, const float* v,
+                                                                 const float* sdiag, int64_t rows, int64_t cols, int64_t Rp, int64_t Cp,
+                                                                 const float* pair_coef, const float* upstream, const float* temp,
+                                                                 float min_temp, float* d_temp) {
+    __shared__ float red[3][256];
+    const int64_t pair = blockIdx.x;
+    rs += pair * Rp; u += pair * Rp; sdiag += pair * Rp; cs += pair * cols; v += pair * Cp;
+    float sr = 0.f, sc = 0.f, sd = 0.f;
+    for (int64_t i = threadIdx.x; i < rows; i += 256) {
+        sr = fmaf(u[i], rs[i], sr);
+        sd += sdiag[i];
+    }
+    for (int64_t j = threadIdx.x; j < cols; j += 256) sc = fmaf(v[j], cs[j], sc);
+    red[0][threadIdx.x] = sr; red[1][threadIdx.x] = sc; red[2][threadIdx.x] = sd;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+            red[2][threadIdx.x] += red[2][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float tv = temp[pair], tc = fmaxf(tv, min_temp), coef = pair_coef[pair];
+        float g = coef / (tc * tc);
+        if (upstream) g *= upstream[0];
+        const float sum = (red[0][0] + red[1][0]) - 2.0f * red[2][0];
+        d_temp[pair] = (tv >= min_temp && coef != 0.f) ? -g * sum : 0.f;
+    }
 }
 
 // multi-view: dx_loc = the fixed-order sum of the da slabs [splits][rows][views d] where the view has the a role and 0 where it has
@@ -1321,6 +1513,35 @@ MvWs mv_carve(void* ws, int64_t rows, int64_t cols, int d, int views, int pairs)
     return w;
 }
 
+// the per-pair form (aecf_nce_multi_pp_*): the carve above, then the arrays of the dT sums
+struct MvPpWs {
+    MvWs w;
+    float* rowsx_part;                  // [P][n_tiles][Rp]  partials of the row sums of E (s - 1)
+    float* colsx_part;                  // [P][m_tiles][Cp]  partials of the column sums
+    float* rs;                          // [P][Rp]
+    float* cs;                          // [P][cols]         this rank's
+    float* sdiag;                       // [P][Rp]           s_ii - 1
+    size_t bytes;
+};
+
+MvPpWs mv_pp_carve(void* ws, int64_t rows, int64_t cols, int d, int views, int pairs) {
+    const int64_t Rp = up256(rows), Cp = up256(cols);
+    const int64_t mt = Rp / BT, nt = Cp / BT;
+    const size_t P = (size_t)pairs;
+    MvPpWs o;
+    o.w = mv_carve(ws, rows, cols, d, views, pairs);
+    char* p = (char*)ws;
+    size_t off = o.w.bytes;
+    auto take = [&](size_t n) { char* r = p + off; off += al256(n); return r; };
+    o.rowsx_part = (float*)take(P * nt * Rp * 4);
+    o.colsx_part = (float*)take(P * mt * Cp * 4);
+    o.rs = (float*)take(P * Rp * 4);
+    o.cs = (float*)take(P * cols * 4);
+    o.sdiag = (float*)take(P * Rp * 4);
+    o.bytes = off;
+    return o;
+}
+
 // the slots of one role: a view with at least one pair in it, and its partner blocks in pair order.  role_b false: the views
 // that supply local rows (da: the partner is the pair's n view); true: the views that supply keys (db: the partner is its m view)
 void mv_slots(const MvPairs& t, int views, bool role_b, NceMultiProduct& mv, int& slots, unsigned int& mask) {
@@ -1356,11 +1577,18 @@ size_t nce_multi_workspace_bytes(int64_t rows, int64_t cols, int d, int views, i
     return mv_carve(nullptr, rows, cols, d, views, mv_pairs(views, anchor).count).bytes + 256;
 }
 
+size_t nce_multi_pp_workspace_bytes(int64_t rows, int64_t cols, int d, int views, int anchor) {
+    return mv_pp_carve(nullptr, rows, cols, d, views, mv_pairs(views, anchor).count).bytes + 256;
+}
+
 namespace {
 // pass 1 of all pairs: one logits launch, one sums launch; col_sums [P][cols] are this rank's.  pres_loc / pres_all non-NULL: the
-// form with missing views (EPI_EXP_MASK); the sums kernel serves both -- an excluded element is an exact zero in every partial
+// form with missing views (EPI_EXP_MASK); the sums kernel serves both -- an excluded element is an exact zero in every partial.
+// per_pair: 0 one temperature (dt.t [1]); 1 a temperature per pair (dt.t [P], the workspace of nce_multi_pp_workspace_bytes); 2 that
+// and the dT sums of every pair: the EPI_EXP_DTS / EPI_EXP_MASK_S instance and a second sums launch over its partials
 void mv_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc, const void* x_all,
-              const unsigned char* pres_loc, const unsigned char* pres_all, void* workspace, float* col_sums, hipStream_t s) {
+              const unsigned char* pres_loc, const unsigned char* pres_all, int per_pair, void* workspace, float* col_sums,
+              hipStream_t s) {
     const MvPairs t = mv_pairs(views, anchor);
     const MvWs w = mv_carve(workspace, rows, cols, d, views, t.count);
     const int64_t Rp = up256(rows), Cp = up256(cols);
@@ -1377,22 +1605,48 @@ void mv_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const Nc
     mv.e_stride = Rp * Cp; mv.rowsum_stride = (int64_t)g.n_tiles * Rp; mv.colsum_stride = (int64_t)g.m_tiles * Cp;
     g.pres_row = pres_loc; g.pres_col = pres_all;
     auto kern = pres_loc ? nce_multi_logits_kernel<EPI_EXP_MASK> : nce_multi_logits_kernel<EPI_EXP_DT>;
+    MvPpWs pw = {};
+    if (per_pair) {
+        pw = mv_pp_carve(workspace, rows, cols, d, views, t.count);
+        g.rowsx_part = pw.rowsx_part; g.colsx_part = pw.colsx_part;
+        if (per_pair == 2) kern = pres_loc ? nce_multi_pp_logits_kernel<EPI_EXP_MASK_S> : nce_multi_pp_logits_kernel<EPI_EXP_DTS>;
+        else kern = pres_loc ? nce_multi_pp_logits_kernel<EPI_EXP_MASK> : nce_multi_pp_logits_kernel<EPI_EXP_DT>;
+    }
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE);
     kern<<<dim3(L.blocks * (unsigned)t.count), dim3(512), 2 * STAGE, s>>>(g, mv);
-    nce_multi_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64), (unsigned)t.count), dim3(256), 0, s>>>(
-        w.rowsum_part, w.colsum_part, g.m_tiles, g.n_tiles, rows, cols, w.l, col_sums);
+    const dim3 sgrid((unsigned)((Rp + Cp) / 64), (unsigned)t.count);
+    nce_multi_sums_kernel<<<sgrid, dim3(256), 0, s>>>(w.rowsum_part, w.colsum_part, g.m_tiles, g.n_tiles, rows, cols, w.l, col_sums);
+    if (per_pair == 2)
+        nce_multi_sums_kernel<<<sgrid, dim3(256), 0, s>>>(pw.rowsx_part, pw.colsx_part, g.m_tiles, g.n_tiles, rows, cols, pw.rs, pw.cs);
 }
 }  // namespace
 
 void launch_nce_multi_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
                             const void* x_all, void* workspace, float* col_sums, hipStream_t s) {
-    mv_pass1(rows, cols, d, views, anchor, dt, x_loc, x_all, nullptr, nullptr, workspace, col_sums, s);
+    mv_pass1(rows, cols, d, views, anchor, dt, x_loc, x_all, nullptr, nullptr, 0, workspace, col_sums, s);
 }
 
 void launch_nce_multi_masked_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
                                    const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all, void* workspace,
                                    float* col_sums, hipStream_t s) {
-    mv_pass1(rows, cols, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, workspace, col_sums, s);
+    mv_pass1(rows, cols, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, 0, workspace, col_sums, s);
+}
+
+void launch_nce_multi_pp_pass1(int64_t rows, int64_t cols, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
+                               const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all, int with_dt,
+                               void* workspace, float* col_sums, hipStream_t s) {
+    mv_pass1(rows, cols, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, with_dt ? 2 : 1, workspace, col_sums, s);
+}
+
+// pair_coef [P] of the per-pair form: the weights normalised over the pairs that have a row, on the device.  pres_all NULL: no
+// view is missing; weights NULL: uniform
+void launch_nce_multi_pp_pair_coef(int64_t cols, int views, int anchor, const unsigned char* pres_all, const float* weights,
+                                   float* pair_coef, hipStream_t s) {
+    const MvPairs t = mv_pairs(views, anchor);
+    NceMultiFin mv = {};
+    for (int p = 0; p < t.count; ++p) { mv.m[p] = t.m[p]; mv.n[p] = t.n[p]; }
+    mv.views = views;
+    nce_multi_pp_pair_coef_kernel<<<dim3(1), dim3(256), 0, s>>>(pres_all, cols, mv, t.count, weights, pair_coef);
 }
 
 // pair_coef [P] of the form with missing views from the gathered presence bytes: one small launch, nothing read on the host
@@ -1407,8 +1661,8 @@ void launch_nce_multi_pair_coef(int64_t cols, int views, int anchor, const unsig
 namespace {
 // normalisers and loss rows [P][rows] of all pairs in one launch; col_sums [P][cols]: all ranks' sums
 void mv_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt, const void* x_loc,
-             const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all, const float* col_sums, void* workspace,
-             float* loss_rows, hipStream_t s) {
+             const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all, bool per_pair, const float* col_sums,
+             void* workspace, float* loss_rows, hipStream_t s) {
     const MvPairs t = mv_pairs(views, anchor);
     const MvWs w = mv_carve(workspace, rows, cols, d, views, t.count);
     const int64_t Rp = up256(rows), Cp = up256(cols);
@@ -1420,7 +1674,10 @@ void mv_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, i
     for (int p = 0; p < t.count; ++p) { mv.m[p] = t.m[p]; mv.n[p] = t.n[p]; }
     mv.views = views;
     const dim3 grid((unsigned)((Rp + 3) / 4), (unsigned)t.count);
-    if (pres_loc) nce_multi_masked_finalize_kernel<<<grid, dim3(256), 0, s>>>(f, mv, pres_loc, pres_all);
+    if (per_pair)       // dt.t [P]; s_ii - 1 of every row goes to the per-pair workspace for the dT sums
+        nce_multi_pp_finalize_kernel<<<grid, dim3(256), 0, s>>>(f, mv, pres_loc, pres_all,
+                                                                mv_pp_carve(workspace, rows, cols, d, views, t.count).sdiag);
+    else if (pres_loc) nce_multi_masked_finalize_kernel<<<grid, dim3(256), 0, s>>>(f, mv, pres_loc, pres_all);
     else nce_multi_finalize_kernel<<<grid, dim3(256), 0, s>>>(f, mv);
 }
 }  // namespace
@@ -1428,13 +1685,19 @@ void mv_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, i
 void launch_nce_multi_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
                            const void* x_loc, const void* x_all, const float* col_sums, void* workspace, float* loss_rows,
                            hipStream_t s) {
-    mv_loss(rows, cols, row_offset, d, views, anchor, dt, x_loc, x_all, nullptr, nullptr, col_sums, workspace, loss_rows, s);
+    mv_loss(rows, cols, row_offset, d, views, anchor, dt, x_loc, x_all, nullptr, nullptr, false, col_sums, workspace, loss_rows, s);
 }
 
 void launch_nce_multi_masked_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
                                   const void* x_loc, const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all,
                                   const float* col_sums, void* workspace, float* loss_rows, hipStream_t s) {
-    mv_loss(rows, cols, row_offset, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, col_sums, workspace, loss_rows, s);
+    mv_loss(rows, cols, row_offset, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, false, col_sums, workspace, loss_rows, s);
+}
+
+void launch_nce_multi_pp_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                              const void* x_loc, const void* x_all, const unsigned char* pres_loc, const unsigned char* pres_all,
+                              const float* col_sums, void* workspace, float* loss_rows, hipStream_t s) {
+    mv_loss(rows, cols, row_offset, d, views, anchor, dt, x_loc, x_all, pres_loc, pres_all, true, col_sums, workspace, loss_rows, s);
 }
 
 // gradients: the weights of all pairs in place (one launch), then ONE da launch (every view with the a role; K through all its
@@ -1444,14 +1707,26 @@ void launch_nce_multi_masked_loss(int64_t rows, int64_t cols, int64_t row_offset
 // W is a zero, and the normalised rows of an absent slot are zeros, so every product is right as it stands.
 namespace {
 void mv_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt, float coef,
-              const float* pair_coef, const unsigned char* pres_loc, const void* x_loc, const void* x_all, void* workspace,
-              const float* upstream, int out_bf16, void* dx_loc, void* dx_all, hipStream_t s) {
+              const float* pair_coef, const unsigned char* pres_loc, bool per_pair, const void* x_loc, const void* x_all,
+              void* workspace, const float* upstream, int out_bf16, void* dx_loc, void* dx_all, hipStream_t s) {
     const MvPairs t = mv_pairs(views, anchor);
     const MvWs w = mv_carve(workspace, rows, cols, d, views, t.count);
     const int64_t Rp = up256(rows), Cp = up256(cols);
     const int64_t chunks = Rp * (Cp / 8);
     const dim3 wgrid((unsigned)((chunks + 255) / 256), (unsigned)t.count);
-    if (pair_coef) {
+    if (per_pair) {     // dt.t, dt.d_t and pair_coef [P]; pres_loc may be NULL.  dT does not come from the da product: its K loop
+                        // has summed over every partner of a view, so the per-pair sums of pass 1 form it (below)
+        NceMultiFin pm = {};
+        for (int p = 0; p < t.count; ++p) { pm.m[p] = t.m[p]; pm.n[p] = t.n[p]; }
+        pm.views = views;
+        nce_multi_pp_weights_kernel<<<wgrid, dim3(256), 0, s>>>(w.e, Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset, pair_coef, pm,
+                                                                pres_loc, upstream, dt.t, dt.min_t);
+        if (dt.d_t) {
+            const MvPpWs pw = mv_pp_carve(workspace, rows, cols, d, views, t.count);
+            nce_multi_pp_dtemp_kernel<<<dim3((unsigned)t.count), dim3(256), 0, s>>>(pw.rs, pw.cs, w.u, w.v, pw.sdiag, rows, cols, Rp, Cp,
+                                                                                    pair_coef, upstream, dt.t, dt.min_t, dt.d_t);
+        }
+    } else if (pair_coef) {
         NceMultiFin pm = {};
         for (int p = 0; p < t.count; ++p) { pm.m[p] = t.m[p]; pm.n[p] = t.n[p]; }
         pm.views = views;
@@ -1483,7 +1758,7 @@ void mv_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, 
         const unsigned int units = (unsigned)(g.m_tiles * g.splits);
         mv.blocks_per_view = g.splits == 8 ? 8u * g.m_tiles * g.n_tiles : ((units + 7) / 8) * 8 * g.n_tiles;
         const unsigned int blocks = mv.blocks_per_view * (unsigned)slots;
-        if (dt.d_t) {
+        if (dt.d_t && !per_pair) {
             if (g.splits == 8) launch_multi_product<OP_ROW, OP_COL, EPI_OUT_TD, MAP_SPLITX>(g, mv, blocks, s);
             else launch_multi_product<OP_ROW, OP_COL, EPI_OUT_TD, MAP_UNITS>(g, mv, blocks, s);
             launch_nce_dtemp(w.rowsum_part, slots * mv.tdot_stride, 1, dt, s);          // views in slot order, then a fixed tree
@@ -1517,15 +1792,22 @@ void mv_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, 
 void launch_nce_multi_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
                             float coef, const void* x_loc, const void* x_all, void* workspace, const float* upstream, int out_bf16,
                             void* dx_loc, void* dx_all, hipStream_t s) {
-    mv_grads(rows, cols, row_offset, d, views, anchor, dt, coef, nullptr, nullptr, x_loc, x_all, workspace, upstream, out_bf16, dx_loc,
+    mv_grads(rows, cols, row_offset, d, views, anchor, dt, coef, nullptr, nullptr, false, x_loc, x_all, workspace, upstream, out_bf16, dx_loc,
              dx_all, s);
 }
 
 void launch_nce_multi_masked_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
                                    const float* pair_coef, const unsigned char* pres_loc, const void* x_loc, const void* x_all,
                                    void* workspace, const float* upstream, int out_bf16, void* dx_loc, void* dx_all, hipStream_t s) {
-    mv_grads(rows, cols, row_offset, d, views, anchor, dt, 0.f, pair_coef, pres_loc, x_loc, x_all, workspace, upstream, out_bf16, dx_loc,
-             dx_all, s);
+    mv_grads(rows, cols, row_offset, d, views, anchor, dt, 0.f, pair_coef, pres_loc, false, x_loc, x_all, workspace, upstream, out_bf16,
+             dx_loc, dx_all, s);
+}
+
+void launch_nce_multi_pp_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, int views, int anchor, const NceDevTemp& dt,
+                               const float* pair_coef, const unsigned char* pres_loc, const void* x_loc, const void* x_all,
+                               void* workspace, const float* upstream, int out_bf16, void* dx_loc, void* dx_all, hipStream_t s) {
+    mv_grads(rows, cols, row_offset, d, views, anchor, dt, 0.f, pair_coef, pres_loc, true, x_loc, x_all, workspace, upstream, out_bf16,
+             dx_loc, dx_all, s);
 }
 
 // ---- supervised contrastive loss on the same GEMMs, both directions from one block (include/aecf_hip.h) ---------------------

@@ -111,7 +111,7 @@
     // no bit set).  Issued HERE, older than every operand copy, so that the copies' vmcnt counts stand and its latency passes
     // behind the K loop.
     unsigned int my_byte = 0;
-    if (EPI == EPI_EXP_MASK) {
+    if (epi_is_mask(EPI)) {
         const int t = threadIdx.x & (BT - 1);
         const bool is_row = threadIdx.x < BT;
         const int k = BT * (is_row ? mi : ni) + t;
@@ -549,8 +549,8 @@
             }
             // EPI_EXP_MASK: whether the thread's row or column (read in front of the K loop) holds both views of the pair; the flags
             // go to LDS behind the barrier
-            const bool my_pres = EPI == EPI_EXP_MASK && (my_byte & p.pres_need) == p.pres_need;
-            if (EPI == EPI_EXP_DT || epi_has_labels(EPI) || epi_has_sets(EPI) || EPI == EPI_EXP_SELF || EPI == EPI_EXP_MASK) {
+            const bool my_pres = epi_is_mask(EPI) && (my_byte & p.pres_need) == p.pres_need;
+            if (EPI == EPI_EXP_DT || epi_has_labels(EPI) || epi_has_sets(EPI) || EPI == EPI_EXP_SELF || epi_is_mask(EPI) || epi_has_ts(EPI)) {
                 scale2 = nce_dev_inv_temp(p.temp, p.min_temp) * 1.4426950408889634f;
                 shift2 = scale2;
             }
@@ -561,7 +561,7 @@
             // EPI_EXP_MASK: [256] row flags | [256] column flags (bytes) | [8] the waves' votes, behind the 6 float planes in use
             const unsigned char* pflag = reinterpret_cast<const unsigned char*>(smem + 18 * BT * 4);
             bool all_present = true;
-            if (EPI == EPI_EXP_MASK) {
+            if (epi_is_mask(EPI)) {
                 reinterpret_cast<unsigned char*>(smem + 18 * BT * 4)[threadIdx.x] = my_pres ? 1 : 0;
                 const int vote = __all(my_pres ? 1 : 0);
                 int* votes = reinterpret_cast<int*>(smem + 18 * BT * 4 + 2 * BT);
@@ -587,7 +587,71 @@
                 edge = edge || (p0 < (int64_t)BT * (ni + 1) && p0 + BT > (int64_t)BT * ni);
             }
             // EPI_EXP_MASK: a tile with an absent row or column (the padding included) takes that branch too, block-uniform
-            if (EPI == EPI_EXP_MASK) edge = !all_present;
+            if (epi_is_mask(EPI)) edge = !all_present;
+            if (epi_has_ts(EPI)) {
+                // EPI_EXP_DTS / EPI_EXP_MASK_S: a sweep of its own over the accumulators, IN FRONT of the E sweep, for the dT sums
+                // of a per-pair temperature: t_ij = E_ij (s_ij - 1) summed per row and per column in float32 (E the float32
+                // exponential the E sweep forms, by the same expression; the product is excluded by the same selects, never by
+                // value).  In front, because the E sweep lets every accumulator go as it stores its row: this sweep holds the 128
+                // accumulators and its 16 column sums and nothing else -- the E sweep's own peak -- and hands its sums to LDS
+                // before the E sweep starts.  The scale and the lane's indices are made opaque HERE so that no exponential is
+                // kept for the E sweep and no address of this sweep is formed in front of the K loop and carried through it.
+                // Partials: the planes behind lcs ([4][256] rows at plane 6, [2][256] columns at plane 14).
+                float* lrn = lrs + 6 * BT;
+                float* lcn = lrs + 14 * BT;
+                float sc2 = scale2, sh2 = shift2;
+                int r16s = r16, lgs = lg;
+                asm volatile("" : "+v"(sc2), "+v"(sh2), "+v"(r16s), "+v"(lgs));
+                const int64_t gi0s = (int64_t)BT * mi + 128 * wm + r16s;
+                const int gj0s = BT * ni + 64 * wn + 4 * lgs;
+                f32x2 ts2[4][2];
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) ts2[ct][0] = ts2[ct][1] = f32x2{0.f, 0.f};
+#pragma unroll
+                for (int rt = 0; rt < 8; ++rt) {
+                    const int64_t i = gi0s + 16 * rt;
+                    f32x2 s2 = f32x2{0.f, 0.f};
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+                        const int j = gj0s + 16 * ct;
+                        const f32x4 sv = acc[rt][ct];
+                        f32x2 t01, t23;
+                        t01[0] = __builtin_amdgcn_exp2f(sv[0] * sc2 - sh2) * (sv[0] - 1.0f);
+                        t01[1] = __builtin_amdgcn_exp2f(sv[1] * sc2 - sh2) * (sv[1] - 1.0f);
+                        t23[0] = __builtin_amdgcn_exp2f(sv[2] * sc2 - sh2) * (sv[2] - 1.0f);
+                        t23[1] = __builtin_amdgcn_exp2f(sv[3] * sc2 - sh2) * (sv[3] - 1.0f);
+                        if (epi_is_mask(EPI)) {
+                            if (edge) {
+                                const bool iok = pflag[128 * wm + 16 * rt + r16s] != 0;
+                                const unsigned int cw = *reinterpret_cast<const unsigned int*>(pflag + BT + 64 * wn + 16 * ct + 4 * lgs);
+                                t01[0] = (iok && (cw & 0x000000ffu)) ? t01[0] : 0.f;
+                                t01[1] = (iok && (cw & 0x0000ff00u)) ? t01[1] : 0.f;
+                                t23[0] = (iok && (cw & 0x00ff0000u)) ? t23[0] : 0.f;
+                                t23[1] = (iok && (cw & 0xff000000u)) ? t23[1] : 0.f;
+                            }
+                        } else if (edge) {
+                            const bool iok = i < p.m_valid;
+                            t01[0] = (iok && j + 0 < p.n_valid) ? t01[0] : 0.f;
+                            t01[1] = (iok && j + 1 < p.n_valid) ? t01[1] : 0.f;
+                            t23[0] = (iok && j + 2 < p.n_valid) ? t23[0] : 0.f;
+                            t23[1] = (iok && j + 3 < p.n_valid) ? t23[1] : 0.f;
+                        }
+                        s2 += t01 + t23;
+                        ts2[ct][0] += t01;
+                        ts2[ct][1] += t23;
+                    }
+                    const float v = reduce_lg(s2[0] + s2[1]);   // over the wave's 64 columns
+                    if (lgs == 0) lrn[wn * BT + 128 * wm + 16 * rt + r16s] = v;
+                }
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float v = reduce_r16(ts2[ct][r >> 1][r & 1]);     // over the wave's 128 rows
+                        if (r16s == 0) lcn[wm * BT + 64 * wn + 16 * ct + 4 * lgs + r] = v;
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+            }
             unsigned short* etile = p.e + ((int64_t)mi * p.e_tiles + 4 * ni + wn) * (BT * 64) + (128 * wm + r16) * 64 + 4 * lg;
 #pragma unroll
             for (int rt = 0; rt < 8; ++rt) {
@@ -601,7 +665,7 @@
                     e01[1] = __builtin_amdgcn_exp2f(acc[rt][ct][1] * scale2 - shift2);
                     e23[0] = __builtin_amdgcn_exp2f(acc[rt][ct][2] * scale2 - shift2);
                     e23[1] = __builtin_amdgcn_exp2f(acc[rt][ct][3] * scale2 - shift2);
-                    if (EPI == EPI_EXP_MASK) {
+                    if (epi_is_mask(EPI)) {
                         if (edge) {
                             // the flags carry the padding: a row or column that does not exist is absent.  Selects on the flags
                             // alone -- what an absent slot's score holds (NaN, inf) never reaches a sum
@@ -843,6 +907,7 @@
             if (tdx < BT) {
                 const int64_t o = ((int64_t)ni * p.m_tiles + mi) * BT + tdx;
                 p.rowsum_part[o] = (lrs[tdx] + lrs[BT + tdx]) + (lrs[2 * BT + tdx] + lrs[3 * BT + tdx]);
+                if (epi_has_ts(EPI)) p.rowsx_part[o] = (lrn[tdx] + lrn[BT + tdx]) + (lrn[2 * BT + tdx] + lrn[3 * BT + tdx]);
                 if (epi_has_labels(EPI) || epi_has_sets(EPI)) {
                     p.rowcnt_part[o] = (lrn[tdx] + lrn[BT + tdx]) + (lrn[2 * BT + tdx] + lrn[3 * BT + tdx]);
                     p.rowsx_part[o] = (lrx[tdx] + lrx[BT + tdx]) + (lrx[2 * BT + tdx] + lrx[3 * BT + tdx]);
@@ -851,6 +916,7 @@
                 const int c = tdx - BT;
                 const int64_t o = ((int64_t)mi * p.n_tiles + ni) * BT + c;
                 p.colsum_part[o] = lcs[c] + lcs[BT + c];
+                if (epi_has_ts(EPI)) p.colsx_part[o] = lcn[c] + lcn[BT + c];
                 if (EPI == EPI_SUP || epi_is_sets(EPI)) {
                     p.colcnt_part[o] = lcn[c] + lcn[BT + c];
                     p.colsx_part[o] = lcx[c] + lcx[BT + c];

@@ -607,7 +607,105 @@ class _NceMultiViewMasked(torch.autograd.Function):
         return dx, dx_all, None, None, None, g_t, None, None, None
 
 
-def _multiview_refusal(x: torch.Tensor, cols: int, min_temperature: float, anchor: int) -> Optional[str]:
+class _NceMultiViewPairwise(torch.autograd.Function):
+    """aecf_nce_multi_pp_pair_coef / _pass1 / _loss / _grads: ``_NceMultiView`` (``pres`` None) or ``_NceMultiViewMasked`` with a
+    temperature and a weight per pair.  ``temperatures`` [P] float32 on the device, read there as ``max(T_p, min_temperature)``;
+    ``weights`` [P] float32 on the device or None (uniform), normalised there over the pairs that have a row.  Where the
+    temperatures want a gradient the logits launch also leaves the per-pair sums of E (s - 1), and the backward forms this rank's
+    share of every dL/dT_p from them -- the gradient products are the one-temperature form's, in their plain form."""
+
+    @staticmethod
+    def forward(ctx, x, x_all, pres, pres_all, row_offset, temperatures, weights, group, min_temperature, anchor):
+        lib = _lib.load()
+        rows, views, d = x.shape
+        cols = x_all.shape[0]
+        xc, xa, ws, ws_bytes, col_sums, loss_rows = _multiview_buffers(lib.aecf_nce_multi_pp_workspace_bytes, x, x_all, anchor)
+        pair_coef = torch.empty(col_sums.shape[0], dtype=torch.float32, device=x.device)
+        t = temperatures.detach().contiguous()
+        tp, t_min, with_dt = _ptr(t), float(min_temperature), int(bool(ctx.needs_input_grad[5]))
+        pl, pa = (_ptr(pres), _ptr(pres_all)) if pres is not None else (None, None)
+        _lib.check(lib.aecf_nce_multi_pp_pair_coef(cols, views, anchor, pa, _ptr(weights), _ptr(pair_coef), _stream()),
+                   "aecf_nce_multi_pp_pair_coef")
+        _lib.check(lib.aecf_nce_multi_pp_pass1(rows, cols, d, views, anchor, tp, t_min, _ptr(xc), _ptr(xa), pl, pa, with_dt, _ptr(ws),
+                                               ws_bytes, _ptr(col_sums), _stream()), "aecf_nce_multi_pp_pass1")
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(col_sums, group=group)
+        _lib.check(lib.aecf_nce_multi_pp_loss(rows, cols, int(row_offset), d, views, anchor, tp, t_min, _ptr(xc), _ptr(xa), pl, pa,
+                                              _ptr(col_sums), _ptr(ws), ws_bytes, _ptr(loss_rows), _stream()), "aecf_nce_multi_pp_loss")
+        ctx.save_for_backward(xc, xa, ws, t, pair_coef, pres)
+        ctx.meta = (temperatures.shape, (rows, cols, int(row_offset), d, views, anchor, t_min, ws_bytes))
+        return (loss_rows.sum(dim=1) * pair_coef).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = _lib.load()
+        xc, xa, ws, t, pair_coef, pres = ctx.saved_tensors
+        t_shape, (rows, cols, row_offset, d, views, anchor, t_min, ws_bytes) = ctx.meta
+        dx, dx_all, up, _ = _multiview_grad_buffers(ctx, xc, xa, d_loss, False)
+        d_t = torch.empty(t.shape, dtype=torch.float32, device=xc.device) if ctx.needs_input_grad[5] else None
+        _lib.check(lib.aecf_nce_multi_pp_grads(rows, cols, row_offset, d, views, anchor, _ptr(t), t_min, _ptr(pair_coef), _ptr(xc), _ptr(xa),
+                                               _ptr(pres), _ptr(ws), ws_bytes, _ptr(up), _DTYPES[torch.bfloat16], _ptr(dx), _ptr(dx_all),
+                                               _ptr(d_t), _stream()), "aecf_nce_multi_pp_grads")
+        g_t = d_t.reshape(t_shape) if d_t is not None else None
+        return dx, dx_all, None, None, None, g_t, None, None, None, None
+
+
+def _pair_order(views: int, anchor: Optional[int]) -> str:
+    pairs = multiview_pairs(views, anchor)
+    return f"P = {len(pairs)} entries in the order of multiview_pairs({views}, {anchor}): {pairs}"
+
+
+def _pair_temperatures(temperature, x: torch.Tensor, views: int, anchor: Optional[int]):
+    """``temperature`` of ``multiview_info_nce`` by its FORM: a number or a one-element tensor -> ``(False, that)`` (one
+    temperature: ``_temperature_scalar`` serves it); a sequence of P numbers or a float32 tensor of P elements on x's device ->
+    ``(True, [P] float32 device tensor)``, the tensor itself so that its gradient reaches it."""
+    pairs = len(multiview_pairs(views, anchor))
+    if isinstance(temperature, torch.Tensor):
+        if temperature.numel() == 1:
+            return False, temperature
+        if temperature.numel() != pairs:
+            raise ValueError(f"multiview_info_nce: a tensor temperature holds 1 element or one per pair, got shape "
+                             f"{tuple(temperature.shape)}; {_pair_order(views, anchor)}")
+        if temperature.dtype != torch.float32:
+            raise TypeError(f"aecf_amd: a tensor temperature must be float32, got {temperature.dtype}")
+        if temperature.device != x.device:
+            raise ValueError(f"aecf_amd: the temperature lives on {temperature.device}, the embeddings on {x.device}")
+        return True, temperature.reshape(pairs)
+    if isinstance(temperature, (list, tuple)):
+        if len(temperature) != pairs:
+            raise ValueError(f"multiview_info_nce: a sequence of temperatures holds one per pair, got {len(temperature)}; "
+                             f"{_pair_order(views, anchor)}")
+        return True, torch.tensor([float(v) for v in temperature], dtype=torch.float32, device=x.device)
+    return False, temperature
+
+
+def _pair_weights(pair_weights, x: torch.Tensor, views: int, anchor: Optional[int]) -> Optional[torch.Tensor]:
+    """``pair_weights`` of ``multiview_info_nce`` as the kernels read them: None, or [P] float32 on x's device.  Host weights are
+    checked here (non-negative, finite); a device tensor is not read on the host -- it is normalised by the pair-coefficient
+    launch."""
+    if pair_weights is None:
+        return None
+    pairs = len(multiview_pairs(views, anchor))
+    if isinstance(pair_weights, torch.Tensor):
+        if pair_weights.numel() != pairs:
+            raise ValueError(f"multiview_info_nce: pair_weights holds one weight per pair, got shape {tuple(pair_weights.shape)}; "
+                             f"{_pair_order(views, anchor)}")
+        if pair_weights.dtype != torch.float32:
+            raise TypeError(f"multiview_info_nce: a tensor of pair_weights must be float32, got {pair_weights.dtype}")
+        if pair_weights.device != x.device:
+            raise ValueError(f"multiview_info_nce: the pair_weights live on {pair_weights.device}, the embeddings on {x.device}")
+        if pair_weights.requires_grad:
+            raise ValueError("multiview_info_nce: pair_weights are not differentiable; pass a tensor that does not require grad")
+        return pair_weights.reshape(pairs).contiguous()
+    if not isinstance(pair_weights, (list, tuple)) or len(pair_weights) != pairs:
+        raise ValueError(f"multiview_info_nce: pair_weights holds one weight per pair, got {pair_weights!r}; {_pair_order(views, anchor)}")
+    host = [float(v) for v in pair_weights]
+    if any(not (v >= 0.0) or v == float("inf") for v in host):
+        raise ValueError(f"multiview_info_nce: pair_weights must be non-negative and finite, got {host}")
+    return torch.tensor(host, dtype=torch.float32, device=x.device)
+
+
+def _multiview_refusal(x: torch.Tensor, cols: int, min_temperature: float, anchor: int, per_pair: bool = False) -> Optional[str]:
     """None where multi-view InfoNCE runs; else the limit that stands against it.  The memory test (P blocks of b_local x b_all
     bfloat16 and the float32 slabs within 0.6 of the free device memory) is skipped while a graph is being captured."""
     rows, views, d = x.shape
@@ -617,7 +715,8 @@ def _multiview_refusal(x: torch.Tensor, cols: int, min_temperature: float, ancho
         return f"d % 64 == 0 with 64 <= d <= 4096 (got d = {d})"
     if not float(min_temperature) >= MIN_TEMPERATURE:
         return f"min_temperature >= {MIN_TEMPERATURE} (got {min_temperature}): 1 / T is the constant shift of every exponential"
-    need = _lib.load().aecf_nce_multi_workspace_bytes(rows, cols, d, views, anchor)
+    lib = _lib.load()
+    need = (lib.aecf_nce_multi_pp_workspace_bytes if per_pair else lib.aecf_nce_multi_workspace_bytes)(rows, cols, d, views, anchor)
     if need == 0:
         return f"fewer than 2^31 gathered rows (got {cols})"
     if not _capturing() and need > 0.6 * torch.cuda.mem_get_info(x.device)[0]:
@@ -626,7 +725,7 @@ def _multiview_refusal(x: torch.Tensor, cols: int, min_temperature: float, ancho
 
 
 def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=None, min_temperature: float = MIN_TEMPERATURE,
-                       anchor: Optional[int] = None, key_padding_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       anchor: Optional[int] = None, pair_weights=None, key_padding_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Symmetric InfoNCE over the pairs of M views, negatives from every rank of ``group``:
 
         L = (1 / P) * sum over the pairs (m, n) of info_nce(x[:, m], x[:, n], temperature, group, min_temperature)
@@ -641,8 +740,23 @@ def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=
     every partner block of a view, so a gradient element is one float32 sum over all its partners, rounded once (a loop of
     ``info_nce`` rounds every pair's gradient to bfloat16 and adds them afterwards).  ``temperature`` as in ``info_nce``: a
     float (placed in a device scalar) or a learnable one-element float32 device tensor, read as ``max(T, min_temperature)``
-    with no host read, its gradient formed by the kernels; one temperature and one weight for all pairs.  The return and
-    gradient conventions under data parallel are ``info_nce``'s.  The backward runs once per forward.
+    with no host read, its gradient formed by the kernels.  The return and gradient conventions under data parallel are
+    ``info_nce``'s.  The backward runs once per forward.
+
+    A temperature and a weight PER PAIR.  ``temperature`` may also be a sequence of P floats or a float32 device tensor of P
+    elements, and ``pair_weights`` a sequence of P non-negative floats or a float32 [P] device tensor that does not require grad
+    (None: uniform); P and the order of the entries are those of ``multiview_pairs(M, anchor)``.  Pair p runs at
+    ``T_p = max(temperature[p], min_temperature)``, read on the device (no host read, capturable), and
+
+        L = sum_p w_p info_nce_p / sum_p w_p
+
+    A [P] temperature that requires grad receives a [P] gradient: the logits launch then also sums E (s - 1) per row and per
+    column of every pair from its float32 accumulators, and one small launch forms every dL/dT_p from those sums in a fixed order
+    (an entry below ``min_temperature`` gets 0, as the scalar does).  A zero weight gives its pair exact-zero gradients, dT_p
+    included; where all weights are zero the loss is 0 with zero gradients.  Device weights are normalised on the device.  The
+    form of the arguments selects the path, never their values: a number or a one-element tensor with ``pair_weights=None`` is the
+    code path, the launches and the bits described above; with ``pair_weights`` given it is spread over the pairs.  A tensor with
+    another element count, or negative or non-finite host weights, raise ValueError.
 
     Needs bfloat16, d % 64 == 0 (64 to 4096), ``min_temperature >= 0.025`` and a workspace (P blocks of b_local x b_all
     bfloat16 plus float32 slabs) within 0.6 of the free device memory (not tested while capturing); otherwise raises
@@ -654,6 +768,9 @@ def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=
     views: only they are anchors, only they are keys, in both directions,
 
         L = (1 / P') * sum over the pairs with a row of info_nce(x[V, m], x[V, n], ...),   P' = the number of such pairs
+
+    (with ``pair_weights``: sum over those pairs of w_p info_nce_p / the sum of their w_p -- a pair without a row drops out of the
+    normalisation, its dT_p is 0)
 
     (0 with zero gradients where no pair has a row; a pair with one row adds 0).  What an absent slot holds -- zeros, stale data,
     inf, NaN -- does not matter: it is excluded by the mask and by index, never by value; its gradient is an exact zero.  The
@@ -689,16 +806,24 @@ def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=
             raise TypeError(f"multiview_info_nce: key_padding_mask must be bool or uint8, got {key_padding_mask.dtype}")
         if key_padding_mask.device != x.device:
             raise ValueError(f"multiview_info_nce: the key_padding_mask lives on {key_padding_mask.device}, the embeddings on {x.device}")
+    per_pair, temperature = _pair_temperatures(temperature, x, views, anchor)
+    weights = _pair_weights(pair_weights, x, views, anchor)
+    per_pair = per_pair or weights is not None
     _require_device(x, "x")
     k = -1 if anchor is None else int(anchor)
     world = dp.world_info(group)[1]
     sizes, offset, b_all = _row_ranges(b_local, x.device, group)
     # every rank must refuse together (they exchange between the passes)
-    refusal = _agreed_refusal(_multiview_refusal(x, b_all, min_temperature, k), x.device, group)
+    refusal = _agreed_refusal(_multiview_refusal(x, b_all, min_temperature, k, per_pair), x.device, group)
     if refusal is not None:
         raise NotImplementedError("aecf_amd: multi-view InfoNCE needs " + refusal + "; a loop of info_nce over the pairs serves "
                                   "such inputs")
-    t = _temperature_scalar(temperature, x, min_temperature)
+    if per_pair:
+        if not (isinstance(temperature, torch.Tensor) and temperature.numel() > 1):     # one temperature, spread over the pairs
+            temperature = _temperature_scalar(temperature, x, min_temperature).reshape(1).expand(len(multiview_pairs(views, anchor)))
+        t = temperature
+    else:
+        t = _temperature_scalar(temperature, x, min_temperature)
     if key_padding_mask is not None:
         absent = key_padding_mask.detach().contiguous().view(torch.uint8).reshape(b_local * views)      # a view: read at replay
         nx, pres = _L2NormMaskedSlots.apply(x.reshape(b_local * views, d), absent, views, 1e-12)
@@ -709,12 +834,18 @@ def multiview_info_nce(x, temperature: Union[float, torch.Tensor] = 0.07, group=
                 pres_all = dp.all_gather_rows(pres.reshape(b_local, 1), group, sizes=sizes).reshape(b_all).contiguous()
         else:
             nx_all, pres_all = nx, pres
-        share = _NceMultiViewMasked.apply(nx, nx_all, pres, pres_all, offset, t, group, float(min_temperature), k)
+        if per_pair:
+            share = _NceMultiViewPairwise.apply(nx, nx_all, pres, pres_all, offset, t, weights, group, float(min_temperature), k)
+        else:
+            share = _NceMultiViewMasked.apply(nx, nx_all, pres, pres_all, offset, t, group, float(min_temperature), k)
     else:
         nx = l2_normalize(x.reshape(b_local * views, d)).reshape(b_local, views, d)
         nx_all = dp.all_gather_rows(nx.reshape(b_local, views * d), group, sizes=sizes).reshape(b_all, views, d) if world > 1 else nx
-        pairs = len(multiview_pairs(views, anchor))
-        share = _NceMultiView.apply(nx, nx_all, offset, t, 0.5 / float(b_all) / float(pairs), group, float(min_temperature), k)
+        if per_pair:
+            share = _NceMultiViewPairwise.apply(nx, nx_all, None, None, offset, t, weights, group, float(min_temperature), k)
+        else:
+            pairs = len(multiview_pairs(views, anchor))
+            share = _NceMultiView.apply(nx, nx_all, offset, t, 0.5 / float(b_all) / float(pairs), group, float(min_temperature), k)
     return _dp_value(share, group)
 
 

@@ -1121,6 +1121,52 @@ int aecf_nce_multi_masked_grads(int64_t rows, int64_t cols, int64_t row_offset, 
                                 const float* upstream, int32_t grad_dtype, void* dx_loc, void* dx_all, float* d_temperature,
                                 void* stream);
 
+/* ---- multi-view InfoNCE, per pair (build-defined; aecf_nce_multi_* / aecf_nce_multi_masked_* with a temperature and a weight for
+ * every pair) ----
+ * One family serves both forms: pres_loc / pres_all as in aecf_nce_multi_masked_*, or BOTH NULL = every row holds every view
+ * (n_p = cols).  temperatures [P] float32 on the device, in the order of the pair list above; pair p runs at
+ * Tc_p = max(temperatures[p], min_temperature), read on the device.  With weights w_p >= 0 (pair_weights [P] float32 on the device,
+ * NULL = all 1) and W = the sum of w_p over the pairs with n_p > 0,
+ *   L = sum_p pair_coef[p] sum_i loss_rows[p][i],   pair_coef[p] = 0.5 / n_p * w_p / W   (0 where n_p = 0, w_p = 0 or W = 0).
+ *   pair_coef: ONE small launch: the integer counts of aecf_nce_multi_masked_pair_coef, then 0.5 / n_p / (W / w_p) in float64,
+ *          rounded once -- equal weights give aecf_nce_multi_masked_pair_coef's bits, and without missing views the float32 that
+ *          aecf_nce_multi_grads is handed as coef = 0.5 / cols / P.  Zeros come from selects: no 0 / 0 is formed.
+ *   pass1: the logits launch of aecf_nce_multi_pass1 / _masked_pass1 with scale and shift of every block from its pair's Tc_p.
+ *          with_dt != 0 (needed where grads is to write d_temperatures): the instance that, after E is stored, sweeps the float32
+ *          accumulators once more and leaves, per pair, this rank's row sums RS_i = sum_j E_ij (s_ij - 1) and column sums
+ *          CS_j = sum_i E_ij (s_ij - 1) in the workspace (E the float32 exponential, never the stored bf16; excluded rows and
+ *          columns by the same selects on the presence bytes).
+ *   loss:  the finalize launch at Tc_p; also keeps s_ii - 1 of every row of V_p for the dT sums.  loss_rows WITHOUT pair_coef.
+ *   grads: the weights W_p = pair_coef[p] upstream / Tc_p (...) per pair, then the gradient products and the slab sum of
+ *          aecf_nce_multi_grads unchanged (da in its plain form: dT does not come from it).  d_temperatures [P] (may be NULL) is
+ *          WRITTEN, this rank's share, by one launch of P blocks in a fixed order:
+ *            dL/dT_p = -(pair_coef[p] upstream / Tc_p^2) [ sum_i RS_i / l_i + sum_j CS_j / c_j - 2 sum_i (s_ii - 1) ]
+ *          with l the row sums and c the ALL-REDUCED column sums of E (so the shares of the ranks sum to the global gradient with
+ *          no further exchange); 0 where temperatures[p] < min_temperature, and an exact 0 where pair_coef[p] = 0.
+ * Where every temperatures[p] holds the bits of one T, col_sums and loss_rows have the bits of aecf_nce_multi_* /
+ * aecf_nce_multi_masked_* at T, and with equal weights dx_loc and dx_all too; the sum of d_temperatures agrees with their
+ * d_temperature to rounding (it is formed by another route).  Served shapes, checks and their order: as aecf_nce_multi_*;
+ * pres_loc and pres_all must be both NULL or both given (pass1, loss: AECF_ERR_NULL_POINTER), pair_coef may not be NULL; pres_all and
+ * pair_weights of pair_coef may be NULL.  Workspace: aecf_nce_multi_workspace_bytes' layout without its trailing 256 bytes, then
+ *   row partials of E (s - 1) [P][Cp/256][Rp] | column partials [P][Rp/256][Cp] | RS [P][Rp] | CS [P][cols] | s_ii - 1 [P][Rp]
+ * (float32, each rounded up to 256 bytes) + 256 bytes.  Nothing is read on the host; no float atomics. */
+size_t aecf_nce_multi_pp_workspace_bytes(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor);       /* 0: not served */
+int aecf_nce_multi_pp_pair_coef(int64_t cols, int32_t views, int32_t anchor, const uint8_t* pres_all /* may be NULL */,
+                                const float* pair_weights /* [P], may be NULL */, float* pair_coef /* [P] */, void* stream);
+int aecf_nce_multi_pp_pass1(int64_t rows, int64_t cols, int32_t d, int32_t views, int32_t anchor, const float* temperatures /* [P] */,
+                            float min_temperature, const void* x_loc, const void* x_all, const uint8_t* pres_loc,
+                            const uint8_t* pres_all, int32_t with_dt, void* workspace, size_t workspace_bytes,
+                            float* col_sums /* [P][cols] */, void* stream);
+int aecf_nce_multi_pp_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                           const float* temperatures, float min_temperature, const void* x_loc, const void* x_all,
+                           const uint8_t* pres_loc, const uint8_t* pres_all, const float* col_sums /* summed over ranks */,
+                           void* workspace, size_t workspace_bytes, float* loss_rows /* [P][rows] */, void* stream);
+int aecf_nce_multi_pp_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, int32_t views, int32_t anchor,
+                            const float* temperatures, float min_temperature, const float* pair_coef, const void* x_loc,
+                            const void* x_all, const uint8_t* pres_loc, void* workspace, size_t workspace_bytes,
+                            const float* upstream, int32_t grad_dtype, void* dx_loc, void* dx_all,
+                            float* d_temperatures /* [P], may be NULL */, void* stream);
+
 /* ---- retrieval ranks of the contrastive views (build-defined like the contrastive terms they evaluate: the reference has no
  * contrastive term and no retrieval evaluation, so there are no reference lines to cite) ----
  * Local rows a [rows,d] (global indices row_offset .. row_offset + rows) against all gathered rows b [cols,d] of the other view,
