@@ -223,6 +223,19 @@ _SYMBOLS = [
     ("aecf_ntxent_sym_grads", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
       c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # symmetric InfoNCE with a key queue on the tile GEMMs: a x b plus two blocks against stored keys (Qa, Qb, capacity, device
+    # count of valid slots), and the ring-buffer push (state = device int64 (cursor, valid))
+    ("aecf_nce_queue_workspace_bytes", c_size_t, [c_int64, c_int64, c_int64, c_int32]),
+    ("aecf_nce_queue_pass1", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+      c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("aecf_nce_queue_loss", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p,
+      c_void_p]),
+    ("aecf_nce_queue_grads", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+      c_void_p, c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("aecf_key_queue_push", c_int, [c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # multi-view InfoNCE on the tile GEMMs: every pair of views of x [rows][views][d] in place, one all-reduce of [P][cols]
     ("aecf_nce_multi_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32]),
     ("aecf_nce_multi_pass1", c_int,

@@ -370,6 +370,26 @@ void launch_ntxent_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, in
                               const void* b_loc, const void* a_all, const void* b_all, void* workspace, const float* upstream,
                               int out_bf16, void* d_a_loc, void* d_b_loc, void* d_a_all, void* d_b_all, hipStream_t s);
 
+// Symmetric InfoNCE with a key queue on the tile GEMMs (aecf_nce_gemm.hip): X = a_loc . b_all^T (InfoNCE's pass 1) and two blocks
+// against stored keys, U = a_loc . Qb^T and W = b_loc . Qa^T, of which the columns below the device count *q_valid are negatives
+// (EPI_EXP_Q: the others left out by index).  col_sums [cols] (the column sums of X, plus the row sums of W on this rank's own
+// range) is what ranks exchange.  The queues take no gradient.  launch_key_queue_push fills the ring buffers on the device:
+// state = (cursor, valid), int64, never read on the host.
+bool nce_queue_gemm_supported(int d, float min_temperature);
+size_t nce_queue_gemm_workspace_bytes(int64_t rows, int64_t cols, int64_t q_cap, int d);
+void launch_nce_queue_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                 const void* b_loc, const void* b_all, const void* qa, const void* qb, int64_t q_cap,
+                                 const int64_t* q_valid, void* workspace, float* col_sums, hipStream_t s);
+void launch_nce_queue_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                const void* b_all, int64_t q_cap, const float* col_sums, void* workspace, float* loss_rows,
+                                hipStream_t s);
+void launch_nce_queue_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef,
+                                 const void* a_loc, const void* b_loc, const void* b_all, const void* qa, const void* qb,
+                                 int64_t q_cap, void* workspace, const float* upstream, int out_bf16, void* d_a_loc, void* d_b_loc,
+                                 void* d_b_all, hipStream_t s);
+void launch_key_queue_push(int64_t q_cap, int d, int64_t n, const void* src_a, const void* src_b, void* qa, void* qb, int64_t* state,
+                           hipStream_t s);
+
 // Multi-view InfoNCE on the tile GEMMs (aecf_nce_gemm.hip): the symmetric InfoNCE of every pair of views (anchor < 0) or of every
 // pair with the anchor view, read in place from x_loc [rows][views][d] / x_all [cols][views][d]; one launch per stage for all
 // pairs, gradient products with K through every partner block of a view.  col_sums [P][cols] is what ranks exchange.

@@ -174,6 +174,19 @@
 //   dL/dT_p = -(coef_p upstream / T_p^2) [ sum_i RS_i / l_i + sum_j CS_j / c_j - 2 sum_i (s_ii - 1) ]
 // with c the all-reduced column sums: a rank's local column partials times the global 1 / c, so the ranks' shares add up to the
 // gradient with no further exchange.  Nothing is recovered from the stored bf16 E.
+//
+// Symmetric InfoNCE with a key queue (aecf_nce_queue_pass1 / _loss / _grads, aecf_key_queue_push) is NT-Xent's arrangement with the
+// two extra blocks taken against STORED keys of past steps: X = a_loc . b_all^T unchanged (EPI_EXP_DT), U = a_loc . Qb^T and W = b_loc .
+// Qa^T over two ring buffers [q_cap, d] of which slots 0 .. V - 1 hold keys, V a DEVICE int64.  EPI_EXP_Q is EPI_EXP_SELF's E loop
+// and row partials with `column < V` where that has the excluded band: V is read once per block in front of the first operand copy;
+// a tile wholly at or above it stores zeros and ends on a block-uniform branch without a K-step, a tile wholly below it runs the
+// unmasked loop, the tile V crosses selects per column -- by index, never by value: what a stale slot holds reaches no sum, a
+// bit-identical twin of a partner below V counts.  Da = lX + lU, Db = the ranks' cX plus lW on the owner's range
+// (ntx_combine_kernel), finalize and weights unchanged (a queue block has no partner element: its weights pass runs with rows =
+// 0).  The queues take no gradient, so four products: d a_loc one float32 sum over the slabs of W_X b_all with those of W_U Qb
+// behind them, d b_loc = W_W Qa, d b_all = W_X^T a_loc.  The products run over all q_cap slots with an exact-zero weight above V
+// (the cost follows q_cap, not V; the slots must hold finite rows).  The ring buffer keeps (cursor, valid) on the device: a copy
+// kernel that reads the old cursor, a one-thread launch behind it that bumps both -- no host read, no atomics, capturable.
 #include <math.h>
 #include <type_traits>
 
@@ -196,7 +209,7 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // sum of the raw accumulators of the elements that match by label (the partner and the padding excluded)
 enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8,
        EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11, EPI_EXP_SELF = 12, EPI_SUP_SELF = 13,
-       EPI_SETS_OV_SELF = 14, EPI_SETS_JAC_SELF = 15, EPI_EXP_MASK = 16, EPI_EXP_DTS = 17, EPI_EXP_MASK_S = 18 };
+       EPI_SETS_OV_SELF = 14, EPI_SETS_JAC_SELF = 15, EPI_EXP_MASK = 16, EPI_EXP_DTS = 17, EPI_EXP_MASK_S = 18, EPI_EXP_Q = 19 };
 // EPI_SETS_OV / EPI_SETS_JAC (multi-label contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the
 // float32 sums of w and of w * raw accumulator, w the overlap / Jaccard weight of the two class sets (partner and padding excluded)
 constexpr bool epi_is_sets(int epi) { return epi == EPI_SETS_OV || epi == EPI_SETS_JAC; }
@@ -222,6 +235,11 @@ constexpr bool epi_has_labels(int epi) { return epi == EPI_SUP || epi == EPI_SUP
 // per column of the tile in rowsx_part / colsx_part (laid out like rowsum_part / colsum_part): the dT sums of that pair.
 constexpr bool epi_is_mask(int epi) { return epi == EPI_EXP_MASK || epi == EPI_EXP_MASK_S; }
 constexpr bool epi_has_ts(int epi) { return epi == EPI_EXP_DTS || epi == EPI_EXP_MASK_S; }
+// EPI_EXP_Q (InfoNCE with a key queue, the blocks of local rows against stored keys): EPI_EXP_SELF's E loop and row partials over
+// the n_valid slots of a ring buffer of which only columns 0 .. *q_valid - 1 hold keys (q_valid: a DEVICE int64, handed over in
+// lab_row and read once per block).  A column at or above it is E = 0 in the stored tile and in the row sum BY INDEX; a tile wholly
+// below it runs the unmasked loop, a tile wholly at or above it stores zeros without running its K loop, and only the tile the
+// count crosses pays for the per-column test.  No column sums or partials of any kind.
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -2096,6 +2114,179 @@ void launch_ntxent_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, in
     launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[0], a_loc, 0, w.stage, s);
     launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[2], b_loc, 0, w.stage + n_all, s);
     launch_slab_sum(w.stage, 2, n_all, d_b_all, out_bf16, s);
+}
+
+// ---- symmetric InfoNCE with a key queue on the same GEMMs: NT-Xent's arrangement with the two extra blocks taken against stored
+// keys (include/aecf_hip.h) -------------------------------------------------------------------------------------------------------
+//   X = a_loc . b_all^T (EPI_EXP_DT, InfoNCE's pass 1 to the bit: row sums lX, this rank's column sums cX)
+//   U = a_loc . Qb^T, W = b_loc . Qa^T (EPI_EXP_Q: the columns at or above *q_valid left out by index; row sums)
+// Da = lX + lU is local; Db = sum over ranks of cX, plus lW on the owner's range: ntx_combine_kernel, before the ONE all-reduce.
+// Loss and weights are InfoNCE's kernels with l := Da, c := Db; U and W take the weights body with v = 0 and NO partner (rows = 0:
+// column row_offset + i of a queue is a negative like any other), W with u_i = 1 / Db_(off + i).  The queues take no gradient: four
+// products, the two on d_a_loc summed from their slabs in one pass.
+
+namespace {
+
+struct QueWs {
+    unsigned short* e[3];               // X [Rp][Cp] | U [Rp][Qp] | W [Rp][Qp] bf16, tiled as E
+    float* rowsum_part;                 // [max(Cp, Qp) / 256][Rp]   one block after the other
+    float* colsum_part;                 // [m_tiles][Cp]   block X
+    float* l;                           // [Rp]  lX, then Da
+    float* lu;                          // [Rp]
+    float* lw;                          // [Rp]
+    float* u;                           // [Rp]  1 / Da
+    float* v;                           // [Cp]  1 / Db
+    float* uz;                          // [Rp]  1 / Db_(off + i)
+    float* ediag;                       // [Rp]
+    float* zero;                        // [max(Cp, Qp)]
+    float* tdot_part;                   // [3][splits <= 32][m_tiles][n_tiles_d <= 16]
+    float* slabs;                       // [splits X + splits Q][rows][d]: the slabs of W_X b_all, behind them those of W_U Qb
+    size_t bytes;
+};
+
+QueWs que_carve(void* ws, int64_t rows, int64_t cols, int64_t q_cap, int d) {
+    const int64_t Rp = up256(rows), Cp = up256(cols), Qp = up256(q_cap), Zp = Cp > Qp ? Cp : Qp;
+    const int64_t mt = Rp / BT;
+    QueWs w;
+    char* p = (char*)ws;
+    size_t off = 0;
+    auto take = [&](size_t n) { char* r = p + off; off += al256(n); return r; };
+    w.e[0] = (unsigned short*)take((size_t)Rp * Cp * 2);
+    for (int k = 1; k < 3; ++k) w.e[k] = (unsigned short*)take((size_t)Rp * Qp * 2);
+    w.rowsum_part = (float*)take((size_t)(Zp / BT) * Rp * 4);
+    w.colsum_part = (float*)take((size_t)mt * Cp * 4);
+    w.l = (float*)take((size_t)Rp * 4);
+    w.lu = (float*)take((size_t)Rp * 4);
+    w.lw = (float*)take((size_t)Rp * 4);
+    w.u = (float*)take((size_t)Rp * 4);
+    w.v = (float*)take((size_t)Cp * 4);
+    w.uz = (float*)take((size_t)Rp * 4);
+    w.ediag = (float*)take((size_t)Rp * 4);
+    w.zero = (float*)take((size_t)Zp * 4);
+    w.tdot_part = (float*)take((size_t)3 * 32 * 16 * mt * 4);
+    w.slabs = (float*)take((size_t)(da_splits(Rp, Cp, d) + da_splits(Rp, Qp, d)) * rows * d * 4);
+    w.bytes = off;
+    return w;
+}
+
+// Ring buffer of past keys.  Row i of the m = min(n, q_cap) LAST source rows goes to slot (cursor + n - m + i) mod q_cap of its
+// queue, 16 bytes per thread; every thread reads the cursor the push found (the bump is a launch of its own behind this one).
+__global__ __launch_bounds__(256) void key_queue_copy_kernel(int64_t q_cap, int chunks, int64_t n, int64_t m, const u32x4* src_a,
+                                                             const u32x4* src_b, u32x4* qa, u32x4* qb, const long long* state) {
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= m * chunks) return;
+    const int64_t i = n - m + id / chunks;
+    const int c = (int)(id % chunks);
+    const long long cur = state[0];
+    const int64_t slot = (int64_t)(((cur < 0 ? 0 : cur) % q_cap + i % q_cap) % q_cap);
+    qa[slot * chunks + c] = src_a[i * chunks + c];
+    qb[slot * chunks + c] = src_b[i * chunks + c];
+}
+
+// cursor = (cursor + n) mod q_cap, valid = min(valid + n, q_cap): one thread, plain vector stores
+__global__ __launch_bounds__(64) void key_queue_bump_kernel(int64_t q_cap, int64_t n, long long* state) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const long long cur = state[0], val = state[1];
+    const long long v0 = val < 0 ? 0 : (val > q_cap ? q_cap : val);
+    state[0] = ((cur < 0 ? 0 : cur) % q_cap + n % q_cap) % q_cap;
+    state[1] = n >= q_cap - v0 ? q_cap : v0 + n;
+}
+
+}  // namespace
+
+bool nce_queue_gemm_supported(int d, float min_temperature) { return nce_gemm_supported(0, d, min_temperature); }
+
+size_t nce_queue_gemm_workspace_bytes(int64_t rows, int64_t cols, int64_t q_cap, int d) {
+    return que_carve(nullptr, rows, cols, q_cap, d).bytes + 256;
+}
+
+void launch_key_queue_push(int64_t q_cap, int d, int64_t n, const void* src_a, const void* src_b, void* qa, void* qb, int64_t* state,
+                           hipStream_t s) {
+    if (n <= 0) return;
+    const int64_t m = n < q_cap ? n : q_cap;
+    const int chunks = d / 8;
+    key_queue_copy_kernel<<<dim3((unsigned)((m * chunks + 255) / 256)), dim3(256), 0, s>>>(
+        q_cap, chunks, n, m, (const u32x4*)src_a, (const u32x4*)src_b, (u32x4*)qa, (u32x4*)qb, (const long long*)state);
+    key_queue_bump_kernel<<<dim3(1), dim3(64), 0, s>>>(q_cap, n, (long long*)state);
+}
+
+// pass 1: the three blocks, Da (workspace) and col_sums [cols] = this rank's cX, plus lW on [row_offset, row_offset + rows)
+void launch_nce_queue_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                 const void* b_loc, const void* b_all, const void* qa, const void* qb, int64_t q_cap,
+                                 const int64_t* q_valid, void* workspace, float* col_sums, hipStream_t s) {
+    const QueWs w = que_carve(workspace, rows, cols, q_cap, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols), Qp = up256(q_cap);
+    {
+        LogitsLaunch L = logits_args(rows, cols, d, a_loc, b_all);
+        NceGemmArgs& g = L.g;
+        g.e = w.e[0]; g.e_tiles = Cp / 64;
+        g.rowsum_part = w.rowsum_part; g.colsum_part = w.colsum_part;
+        g.temp = dt.t; g.min_temp = dt.min_t;
+        launch_gemm<OP_ROW, OP_ROW, EPI_EXP_DT, MAP_2D>(g, L.blocks, s);
+        nce_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64)), dim3(256), 0, s>>>(w.rowsum_part, w.colsum_part, g.m_tiles, g.n_tiles, rows, cols,
+                                                                               w.l, col_sums);
+    }
+    for (int k = 1; k < 3; ++k) {
+        LogitsLaunch L = logits_args(rows, q_cap, d, k == 1 ? a_loc : b_loc, k == 1 ? qb : qa);
+        NceGemmArgs& g = L.g;
+        g.e = w.e[k]; g.e_tiles = Qp / 64;
+        g.rowsum_part = w.rowsum_part;
+        g.temp = dt.t; g.min_temp = dt.min_t;
+        g.lab_row = reinterpret_cast<const long long*>(q_valid);            // EPI_EXP_Q: the device count of valid slots
+        launch_gemm<OP_ROW, OP_ROW, EPI_EXP_Q, MAP_2D>(g, L.blocks, s);
+        // the row blocks of the sums launch alone: this block leaves no column partials
+        nce_sums_kernel<<<dim3((unsigned)(Rp / 64)), dim3(256), 0, s>>>(w.rowsum_part, nullptr, g.m_tiles, g.n_tiles, rows, q_cap,
+                                                                        k == 1 ? w.lu : w.lw, nullptr);
+    }
+    ntx_combine_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s>>>(w.l, w.lu, w.lw, col_sums, rows, row_offset);
+}
+
+// normalisers + loss rows of this rank's pairs from the col_sums of all ranks: InfoNCE's finalize with l := Da, c := Db
+void launch_nce_queue_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                const void* b_all, int64_t q_cap, const float* col_sums, void* workspace, float* loss_rows,
+                                hipStream_t s) {
+    const QueWs w = que_carve(workspace, rows, cols, q_cap, d);
+    NceFinArgs f = {};
+    f.a = (const unsigned short*)a_loc; f.b = (const unsigned short*)b_all; f.l = w.l; f.c = col_sums;
+    f.u = w.u; f.v = w.v; f.ediag = w.ediag; f.loss_rows = loss_rows; f.rows = rows; f.cols = cols; f.row_offset = row_offset;
+    f.Rp = up256(rows); f.Cp = up256(cols); f.d = d; f.sym = 1;
+    f.temp = dt.t; f.min_temp = dt.min_t;
+    nce_finalize_kernel<true><<<dim3((unsigned)((f.Rp + 3) / 4)), dim3(256), 0, s>>>(f);
+}
+
+// gradients: the three weights passes in place, then
+//   d_a_loc = W_X b_all + W_U Qb (one slab sum over both products' slabs)      d_b_loc = W_W Qa      d_b_all = W_X^T a_loc
+// every output rounded once from its float32 sum; dt.d_t from the partials of the three da products, one fixed-order reduction.
+// Every slot of the queues is read (the weight of a slot at or above *q_valid is an exact zero): they must hold finite rows.
+void launch_nce_queue_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef,
+                                 const void* a_loc, const void* b_loc, const void* b_all, const void* qa, const void* qb,
+                                 int64_t q_cap, void* workspace, const float* upstream, int out_bf16, void* d_a_loc, void* d_b_loc,
+                                 void* d_b_all, hipStream_t s) {
+    const QueWs w = que_carve(workspace, rows, cols, q_cap, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols), Qp = up256(q_cap), Zp = Cp > Qp ? Cp : Qp;
+    const dim3 xgrid((unsigned)((Rp * (Cp / 8) + 255) / 256)), qgrid((unsigned)((Rp * (Qp / 8) + 255) / 256));
+    ntx_prep_kernel<<<dim3((unsigned)(Zp / 256)), dim3(256), 0, s>>>(w.v, w.uz, w.zero, rows, row_offset, Rp, Zp);
+    nce_weights_dt_kernel<<<xgrid, dim3(256), 0, s>>>(w.e[0], Cp / 64, Rp / BT, w.u, w.v, w.ediag, rows, row_offset, coef, 2.0f, upstream,
+                                                      dt.t, dt.min_t);
+    // rows = 0: no element of a queue block is a partner
+    nce_weights_dt_kernel<<<qgrid, dim3(256), 0, s>>>(w.e[1], Qp / 64, Rp / BT, w.u, w.zero, w.zero, 0, row_offset, coef, 0.0f, upstream,
+                                                      dt.t, dt.min_t);
+    nce_weights_dt_kernel<<<qgrid, dim3(256), 0, s>>>(w.e[2], Qp / 64, Rp / BT, w.uz, w.zero, w.zero, 0, row_offset, coef, 0.0f, upstream,
+                                                      dt.t, dt.min_t);
+    const bool want_td = dt.d_t != nullptr;
+    const int64_t n_tdx = da_tdot_count(rows, cols, d), n_tdq = da_tdot_count(rows, q_cap, d), n_loc = rows * (int64_t)d;
+    const NceGemmArgs g0 = {};
+    // both products always leave float32 slabs, those of W_U Qb behind those of W_X b_all: one sum, one rounding
+    const int sx = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[0], w.slabs, w.tdot_part, want_td, a_loc, b_all, 0,
+                                                          nullptr, s);
+    const int su = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, q_cap, d, g0, w.e[1], w.slabs + sx * n_loc, w.tdot_part + n_tdx, want_td,
+                                                          a_loc, qb, 0, nullptr, s);
+    launch_slab_sum(w.slabs, sx + su, n_loc, d_a_loc, out_bf16, s);
+    const int sw = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, q_cap, d, g0, w.e[2], w.slabs, w.tdot_part + n_tdx + n_tdq, want_td, b_loc,
+                                                          qa, out_bf16, d_b_loc, s);
+    if (sw) launch_slab_sum(w.slabs, sw, n_loc, d_b_loc, out_bf16, s);
+    if (want_td) launch_nce_dtemp(w.tdot_part, n_tdx + 2 * n_tdq, 1, dt, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[0], a_loc, out_bf16, d_b_all, s);
 }
 
 // ---- pooled supervised contrastive loss (Khosla et al.: one pool of both views) on the same GEMMs: NT-Xent's three logits blocks

@@ -1399,6 +1399,174 @@ def nt_xent(za: torch.Tensor, zb: torch.Tensor, temperature: Union[float, torch.
     return supervised_contrastive(za, zb, labels, temperature, group, min_temperature, True, True)
 
 
+class KeyQueue:
+    """Past keys of the two views as further negatives of ``queued_info_nce`` (MoCo's queue, cross-batch memory): two ring
+    buffers ``keys_a``, ``keys_b`` [capacity, d] bfloat16 (zeros until written) and ``state``, a device int64 pair (cursor,
+    valid).  The state is read and written by kernels alone (aecf_key_queue_push): a push captures into a graph and nothing of it
+    is ever read on the host.  ``version`` counts the pushes on the host: the loss's backward reads the buffers again and
+    refuses to run across a push."""
+
+    def __init__(self, capacity: int, d: int, device):
+        capacity, d = int(capacity), int(d)
+        if not 1 <= capacity < 2 ** 31:
+            raise ValueError(f"aecf_amd: a key queue holds 1 to 2^31 - 1 rows, got capacity = {capacity}")
+        if d <= 0 or d % 8 != 0:
+            raise ValueError(f"aecf_amd: a key queue needs d % 8 == 0 (16-byte row copies), got d = {d}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"aecf_amd: a key queue must be on a ROCm device (got {device}); this package has no CPU path")
+        self.capacity, self.d = capacity, d
+        self.keys_a = torch.zeros(capacity, d, dtype=torch.bfloat16, device=device)
+        self.keys_b = torch.zeros(capacity, d, dtype=torch.bfloat16, device=device)
+        self.state = torch.zeros(2, dtype=torch.int64, device=device)
+        self.valid = self.state[1:]         # what the loss reads as its count of valid slots
+        self.version = 0
+
+    @torch.no_grad()
+    def push(self, za: torch.Tensor, zb: torch.Tensor, group=None, normalize: bool = True) -> None:
+        """Append this step's rows of both views, the oldest slots overwritten first (more rows than the capacity: the last
+        ``capacity`` of them stay).  ``za``, ``zb``: [b_local, d] bfloat16 on the queue's device; ``normalize`` runs
+        ``l2_normalize`` on them first (pass False for rows that are unit-norm already).  No autograd.  Under data parallel the
+        rows of every rank of ``group`` go in, in all-gather order, so that every rank holds the same queue."""
+        _require_device(za, "za")
+        _require_device(zb, "zb")
+        _check_two_views("KeyQueue.push", za, zb)
+        if za.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16 or za.shape[1] != self.d or za.device != self.state.device:
+            raise ValueError(f"aecf_amd: the key queue holds bfloat16 rows of d = {self.d} on {self.state.device}; got {za.dtype} "
+                             f"and {zb.dtype}, d = {za.shape[1]} on {za.device}")
+        na, nb = (l2_normalize(za.detach()), l2_normalize(zb.detach())) if normalize else (za.detach(), zb.detach())
+        sizes, _, _ = _row_ranges(za.shape[0], za.device, group)
+        na, nb = _all_rows(na, group, sizes).contiguous(), _all_rows(nb, group, sizes).contiguous()
+        _lib.check(_lib.load().aecf_key_queue_push(self.capacity, self.d, na.shape[0], _ptr(na), _ptr(nb), _ptr(self.keys_a),
+                                                   _ptr(self.keys_b), _ptr(self.state), _stream()), "aecf_key_queue_push")
+        self.version += 1
+
+
+class _QueuedNce(torch.autograd.Function):
+    """aecf_nce_queue_pass1 / _loss / _grads: both directions of this rank's symmetric InfoNCE from the a_loc x b_all block of
+    logits plus two blocks against the stored keys of a ``KeyQueue`` (a_loc x keys_b, b_loc x keys_a; the slots at or above the
+    queue's device count left out by index).  Modelled on ``_TileSymmetric``: the [cols] column sums (those of the a x b block plus
+    the b x keys_a row sums on this rank's own range) are the one thing ranks exchange; the backward runs the three weights passes
+    and the four gradient products once.  The queues take no gradient, but the products read them again: the backward refuses to
+    run where the queue was pushed to since the forward."""
+
+    @staticmethod
+    def forward(ctx, a, b, b_all, queue, row_offset, temperature, coef, group, min_temperature):
+        lib = _lib.load()
+        rows, d = a.shape
+        cols = b_all.shape[0]
+        dev = a.device
+        operands = [x.detach().to(torch.bfloat16).contiguous() for x in (a, b, b_all)]
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws_bytes = lib.aecf_nce_queue_workspace_bytes(rows, cols, queue.capacity, d)
+        if ws_bytes == 0:
+            raise NotImplementedError("aecf_amd: InfoNCE with a key queue needs d % 64 == 0, 64 <= d <= 4096 and fewer than 2^31 "
+                                      f"gathered rows; got d = {d}, {cols} rows")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        col_sums = torch.empty(cols, **f32)
+        t = temperature.detach()
+        dims, t_min = (rows, cols, int(row_offset), d), float(min_temperature)
+        stored = (_ptr(queue.keys_a), _ptr(queue.keys_b), queue.capacity, _ptr(queue.valid))
+        _lib.check(lib.aecf_nce_queue_pass1(*dims, _ptr(t), t_min, _ptr(operands[0]), _ptr(operands[1]), *stored, _ptr(operands[2]),
+                                            _ptr(ws), ws_bytes, _ptr(col_sums), _stream()), "aecf_nce_queue_pass1")
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(col_sums, group=group)
+        loss_rows = torch.empty(rows, **f32)
+        _lib.check(lib.aecf_nce_queue_loss(*dims, _ptr(t), t_min, _ptr(operands[0]), _ptr(operands[2]), queue.capacity,
+                                           _ptr(col_sums), _ptr(ws), ws_bytes, _ptr(loss_rows), _stream()), "aecf_nce_queue_loss")
+        ctx.save_for_backward(t, ws, *operands)
+        ctx.queue, ctx.queue_version = queue, queue.version
+        ctx.meta = ([x.dtype for x in (a, b, b_all)], temperature.shape, dims, t_min, float(coef), ws_bytes)
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = _lib.load()
+        t, ws, *operands = ctx.saved_tensors
+        dtypes, t_shape, dims, t_min, coef, ws_bytes = ctx.meta
+        queue = ctx.queue
+        if queue.version != ctx.queue_version:
+            raise RuntimeError("aecf_amd: the key queue was pushed to between the forward and the backward of queued_info_nce "
+                               "(the gradient products read the stored keys again): the order is loss, backward, push")
+        _spend(ctx, "queued InfoNCE")
+        gdt = torch.bfloat16 if dtypes.count(torch.bfloat16) == 3 else torch.float32
+        grads = [torch.empty_like(x, dtype=gdt) for x in operands]
+        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
+        d_t = torch.empty(1, dtype=torch.float32, device=ws.device) if ctx.needs_input_grad[5] else None
+        stored = (_ptr(queue.keys_a), _ptr(queue.keys_b), queue.capacity, _ptr(queue.valid))
+        _lib.check(lib.aecf_nce_queue_grads(*dims, _ptr(t), t_min, coef, _ptr(operands[0]), _ptr(operands[1]), *stored,
+                                            _ptr(operands[2]), _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt], *map(_ptr, grads),
+                                            _ptr(d_t), _stream()), "aecf_nce_queue_grads")
+        g_t = d_t.reshape(t_shape) if d_t is not None else None
+        return (*[g.to(x) for g, x in zip(grads, dtypes)], None, None, g_t, None, None, None)
+
+
+def _queue_refusal(z: torch.Tensor, zb: torch.Tensor, cols: int, queue: KeyQueue, min_temperature: float) -> Optional[str]:
+    """``_tile_refusal`` for the queue form: its workspace query takes the queue's capacity, and the queue must fit the rows."""
+    rows, d = z.shape
+    if z.dtype != torch.bfloat16 or zb.dtype != torch.bfloat16:
+        return f"bfloat16 rows (got {z.dtype} and {zb.dtype})"
+    if d % 64 != 0 or not 64 <= d <= 4096:
+        return f"d % 64 == 0 with 64 <= d <= 4096 (got d = {d})"
+    if queue.d != d or queue.state.device != z.device:
+        return f"a key queue of the rows' width and device (the queue holds d = {queue.d} on {queue.state.device}, got d = {d} on {z.device})"
+    if not float(min_temperature) >= MIN_TEMPERATURE:
+        return f"min_temperature >= {MIN_TEMPERATURE} (got {min_temperature}): 1 / T is the constant shift of every exponential"
+    need = _lib.load().aecf_nce_queue_workspace_bytes(rows, cols, queue.capacity, d)
+    if need == 0:
+        return f"fewer than 2^31 gathered rows (got {cols})"
+    if not _capturing() and need > 0.6 * torch.cuda.mem_get_info(z.device)[0]:
+        return (f"a workspace (b_local x b_all and two b_local x capacity bfloat16 blocks, {need} bytes here) within 0.6 of the "
+                "free device memory")
+    return None
+
+
+def queued_info_nce(za: torch.Tensor, zb: torch.Tensor, queue: KeyQueue, temperature: Union[float, torch.Tensor] = 0.07,
+                    group=None, min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
+    """Symmetric InfoNCE between the local rows of two views with the keys of every rank of ``group`` AND the stored keys of
+    ``queue`` as negatives: an anchor of view a sees the gathered rows of view b and the valid slots of ``queue.keys_b``, an
+    anchor of view b the gathered rows of view a and the valid slots of ``queue.keys_a``,
+
+        L = 0.5 / B_all * sum over both directions and rows i of [ log(sum_batch e^x + sum_queue e^x) - x_ii ],
+        x = n . n_k / max(T, min_temperature)
+
+    With an empty queue the three calls give the bits of the symmetric tile form (aecf_nce_sym_*_dt).  ``za``, ``zb``: [b_local, d] bfloat16 on a ROCm device,
+    d % 64 == 0 (64 to 4096), ``min_temperature >= 0.025``, and the workspace (the b_local x b_all block and two b_local x capacity
+    blocks of bfloat16 exponentials plus float32 staging) within 0.6 of the free device memory (not tested while capturing);
+    anything else raises NotImplementedError naming the limit -- there is no streaming form and no torch fallback.
+    ``temperature``: a Python float (filled into a one-element device tensor) or a learnable one-element float32 tensor on za's
+    device, read by the kernels as ``max(T, min_temperature)`` with no host read and given its gradient by the same kernels;
+    there is ONE temperature for batch and queue keys.  The queue's count of valid slots is read on the device too, so a captured
+    step replays against whatever the queue holds then.  The stored keys take no gradient.  Under ``torch.no_grad()`` only the
+    logits pass and the loss run; the backward runs once per forward.
+
+    The function does NOT push.  Its backward reads the stored keys again, so it raises RuntimeError if ``queue.push`` ran
+    between the forward and the backward.  The order of a step is: loss, backward, push --
+
+        loss = queued_info_nce(za, zb, queue, t); loss.backward(); queue.push(za, zb)
+
+    The cost follows the queue's capacity, not its count of valid slots: the logits pass skips the tiles above the count, the
+    gradient products run over every slot with an exact-zero weight.  Under data parallel the queue is replicated on every rank
+    (``push`` gathers), the ranks agree on a refusal and all-reduce the [b_all] column sums between the passes; the returned
+    value follows ``info_nce``'s convention."""
+    _require_device(za, "za")
+    _require_device(zb, "zb")
+    _check_two_views("queued_info_nce", za, zb)
+    if not isinstance(queue, KeyQueue):
+        raise TypeError(f"aecf_amd: queue must be a KeyQueue, got {type(queue).__name__}")
+    _check_min_temperature(min_temperature)
+    sizes, offset, b_all = _row_ranges(za.shape[0], za.device, group)
+    # every rank must raise or run together (the ranks that run all-reduce between their passes)
+    refusal = _agreed_refusal(_queue_refusal(za, zb, b_all, queue, min_temperature), za.device, group)
+    if refusal is not None:
+        raise NotImplementedError("aecf_amd: InfoNCE with a key queue needs " + refusal)
+    t = _temperature_scalar(temperature, za, min_temperature)
+    na, nb = l2_normalize(za), l2_normalize(zb)
+    nb_all = _all_rows(nb, group, sizes)
+    share = _QueuedNce.apply(na, nb, nb_all, queue, offset, t, 0.5 / float(b_all), group, float(min_temperature))
+    return _dp_value(share, group)
+
+
 class _SupConPoolSymmetric(_TileSymmetric):
     """aecf_supcon_pool_sym_pass1 / _loss / _grads: the 2 b_local anchors of this rank's pooled supervised contrastive loss from
     the three blocks of logits of ``_NtXentSymmetric``, the labels shared by the two views.  The [3, cols] column statistics are

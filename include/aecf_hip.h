@@ -802,6 +802,80 @@ int aecf_ntxent_sym_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_
                           const void* b_all, void* workspace, size_t workspace_bytes, const float* upstream, int32_t grad_dtype,
                           void* d_a_loc, void* d_b_loc, void* d_a_all, void* d_b_all, float* d_temperature, void* stream);
 
+/* ---- InfoNCE with a key queue, tile-GEMM form (build-defined; MoCo's queue / cross-batch memory for the symmetric loss) ----
+ * The symmetric InfoNCE of aecf_nce_sym_*_dt with stored keys of past steps as further negatives.  A rank holds its local rows
+ * a_loc, b_loc [rows,d] (global rows row_offset .. row_offset + rows), the gathered b_all [cols,d] (it may alias b_loc on one rank)
+ * and two ring buffers Qa, Qb [q_cap,d] of past keys of view a / view b, all unit-norm bf16 rows.  V = *q_valid is a DEVICE int64
+ * with 0 <= V <= q_cap (clamped into that range): slots 0 .. V - 1 of either queue are keys, negatives of the OTHER view's anchors.
+ * Tc = max(*temperature, min_temperature), E(s) = exp((s - 1) / Tc).  Three logits blocks:
+ *   X = a_loc . b_all^T   partner at column row_offset + i                      row sums lX_i, this rank's column sums cX_j
+ *   U = a_loc . Qb^T      columns j >= V EXCLUDED BY INDEX (E = 0 stored and summed)   row sums lU_i
+ *   W = b_loc . Qa^T      the same                                                     row sums lW_i
+ * Denominators: anchors of view a, Da_i = lX_i + lU_i (local); anchors of view b, Db_j = sum over ranks of cX_j, plus lW of the rank
+ * that owns row j.  With s_i = a_i . b_(row_offset + i):
+ *   loss_rows[i] = [log Da_i + 1/Tc - s_i/Tc] + [log Db_(row_offset + i) + 1/Tc - s_i/Tc]         both anchors of pair i, WITHOUT coef
+ *   W_X = ct (E_X (1/Da_i + 1/Db_j) - 2 [j == row_offset + i])    W_U = ct E_U / Da_i    W_W = ct E_W / Db_(row_offset + i)
+ *         ct = coef / Tc * upstream; a queue block has no partner: its column row_offset + i is a negative like any other
+ *   d_a_loc = W_X b_all + W_U Qb [rows,d]     d_b_loc = W_W Qa [rows,d]     d_b_all = W_X^T a_loc [cols,d]   (this rank's share)
+ *   dT = -(1/Tc) [ sum_i a_i . d_a_loc_i + sum_i b_i . d_b_loc_i ]   (X's column side rides in W_X; 0 where *temperature < min_temperature)
+ * The queues take no gradient and no product is formed for them.  The shares of the ranks sum to the global gradients.
+ *   pass1: the three logits GEMMs.  X is aecf_nce_sym_pass1_dt to the bit.  U and W run an epilogue of their own: V is read from
+ *          the device once per block; a tile wholly below V runs the unmasked tile's code, a tile wholly at or above V stores
+ *          zeros without running its K loop, the tile V crosses tests every column's index.  Exclusion is never by value: what a
+ *          slot at or above V holds cannot reach a sum, a bit-identical twin of a partner below V counts.  Then Da = lX + lU
+ *          (workspace) and col_sums [cols] float32 = this rank's cX, plus lW on its own range [row_offset, row_offset + rows): one
+ *          float32 addition each, fixed order, no atomics.
+ *   caller: all-reduce (sum) of col_sums over the ranks (nothing to do on one rank): it then holds Db.
+ *   loss:  loss_rows [rows] from Da and the summed col_sums; prepares 1/Da and 1/Db in the workspace.
+ *   grads: the three weights passes in place over the blocks, then the four products.  d_a_loc is ONE float32 sum over the slabs of
+ *          W_X b_all with those of W_U Qb behind them, rounded once to grad_dtype (float32 or bf16); everything is multiplied by
+ *          upstream[0] (a DEVICE float32 scalar, NULL = 1); d_temperature (may be NULL) is WRITTEN with this rank's share of dL/dT
+ *          times upstream[0], reduced in a fixed order from the float32 partials of the three da-type products.  It consumes the
+ *          stored blocks: it runs once per pass1.  It reads Qa and Qb again (q_valid is not read: the stored blocks carry it), so
+ *          the queues must not change between pass1 and grads.  The products run over ALL q_cap slots with an exact-zero weight
+ *          on the slots at or above V: those slots MUST HOLD FINITE ROWS (zeros after allocation, past keys after a wrap), or
+ *          0 * inf = NaN reaches the gradients.  The cost therefore follows q_cap, not V, in the products; only the logits pass
+ *          skips the tiles above V.
+ * Only the device-temperature form exists.  Served: bf16 rows, d % 64 == 0, 64 <= d <= 4096, min_temperature >= 0.025 (1/Tc is
+ * the constant shift of every exponential), rows <= cols < 2^31, 1 <= q_cap < 2^31.  With q_cap = cols, 14 rows cols d MFMA flops
+ * (three logits blocks and four gradient products of 2 rows cols d each) against NT-Xent's 18.
+ * Workspace, in order, each piece rounded up to 256 bytes, Rp / Cp / Qp = rows / cols / q_cap rounded up to 256, Zp = max(Cp, Qp),
+ * + 256 bytes:
+ *   E_X [Rp][Cp] bf16 | E_U [Rp][Qp] bf16 | E_W [Rp][Qp] bf16 | row partials [Zp/256][Rp] | column partials [Rp/256][Cp] | Da [Rp] |
+ *   lU [Rp] | lW [Rp] | 1/Da [Rp] | 1/Db [Cp] | 1/Db at the partner [Rp] | the partner's exponential [Rp] | zeros [Zp] |
+ *   dT partials [3][32][16][Rp/256] | da slabs [splits(Cp) + splits(Qp)][rows][d]
+ *   (float32 but E; splits: the K split of da = W b, as in the InfoNCE form).  The query answers 0 where the shape is not served.
+ * Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host, nothing read from the
+ * workspace before it is written; no float atomics: the same inputs give the same bits.  Checks before any launch, in the order
+ * of the NT-Xent tile form: sizes (rows, cols, d, q_cap > 0, cols and q_cap < 2^31, min_temperature > 0, 0 <= row_offset,
+ * row_offset + rows <= cols: AECF_ERR_BAD_DIMS), then d, min_temperature < 0.025 or a grad_dtype other than bf16 / float32
+ * (AECF_ERR_UNSUPPORTED), then NULL pointers (AECF_ERR_NULL_POINTER; upstream and d_temperature may be NULL), then the workspace
+ * size (AECF_ERR_WORKSPACE).
+ *
+ * aecf_key_queue_push fills the two ring buffers on the device.  state is a DEVICE int64[2] = (cursor, valid); row i of the n source
+ * rows src_a / src_b [n,d] goes to slot (cursor + i) mod q_cap of Qa / Qb (n > q_cap: only the last q_cap rows are written, to the
+ * slots they would have ended in); then cursor = (cursor + n) mod q_cap and valid = min(valid + n, q_cap), written by a one-thread
+ * launch behind the copy on the same stream, so every row copy reads the cursor the push found.  &state[1] is the q_valid of the
+ * calls above.  No host read, no atomics, capturable; the same inputs give the same bits.  d % 8 == 0 (16-byte copies), any
+ * 16-byte aligned row type of 2 d bytes; n = 0 launches nothing.  Checks: q_cap, d > 0, q_cap < 2^31, n >= 0 (AECF_ERR_BAD_DIMS),
+ * d % 8 (AECF_ERR_UNSUPPORTED), NULL pointers (AECF_ERR_NULL_POINTER; the sources may be NULL where n == 0). */
+size_t aecf_nce_queue_workspace_bytes(int64_t rows, int64_t cols, int64_t q_cap, int32_t d);      /* 0: not served */
+int aecf_nce_queue_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                         float min_temperature, const void* a_loc, const void* b_loc, const void* Qa, const void* Qb, int64_t q_cap,
+                         const int64_t* q_valid, const void* b_all, void* workspace, size_t workspace_bytes,
+                         float* col_sums /* [cols] */, void* stream);
+int aecf_nce_queue_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                        float min_temperature, const void* a_loc, const void* b_all, int64_t q_cap,
+                        const float* col_sums /* summed over ranks */, void* workspace, size_t workspace_bytes, float* loss_rows,
+                        void* stream);
+int aecf_nce_queue_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                         float min_temperature, float coef, const void* a_loc, const void* b_loc, const void* Qa, const void* Qb,
+                         int64_t q_cap, const int64_t* q_valid, const void* b_all, void* workspace, size_t workspace_bytes,
+                         const float* upstream, int32_t grad_dtype, void* d_a_loc, void* d_b_loc, void* d_b_all,
+                         float* d_temperature, void* stream);
+int aecf_key_queue_push(int64_t q_cap, int32_t d, int64_t n, const void* src_a, const void* src_b, void* Qa, void* Qb,
+                        int64_t* state /* device (cursor, valid) */, void* stream);
+
 /* ---- pooled supervised contrastive loss, tile-GEMM form (build-defined; aecf_supcon_pool_fwd_bwd's loss over both anchor halves) ----
  * The supervised contrastive loss of Khosla et al. over ONE pool of the 2 cols rows of both views: every row is an anchor, its
  * keys are the other 2 cols - 1 rows, its positives among them its partner in the other view (by INDEX) and every row of either
