@@ -236,6 +236,20 @@ _SYMBOLS = [
      [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
       c_void_p, c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("aecf_key_queue_push", c_int, [c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # supervised contrastive loss with a key queue: the calls above plus row_labels, col_labels and the ring of stored labels
+    # (int64, device) behind b_all; col_stats [3][cols]; the push that also writes the label ring (src_labels NULL: -1)
+    ("aecf_supcon_queue_workspace_bytes", c_size_t, [c_int64, c_int64, c_int64, c_int32]),
+    ("aecf_supcon_queue_pass1", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("aecf_supcon_queue_loss", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p,
+      c_void_p]),
+    ("aecf_supcon_queue_grads", c_int,
+     [c_int64, c_int64, c_int64, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("aecf_key_queue_push_labeled", c_int,
+     [c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # multi-view InfoNCE on the tile GEMMs: every pair of views of x [rows][views][d] in place, one all-reduce of [P][cols]
     ("aecf_nce_multi_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32]),
     ("aecf_nce_multi_pass1", c_int,

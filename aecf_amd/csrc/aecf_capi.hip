@@ -1137,6 +1137,73 @@ int aecf_key_queue_push(int64_t q_cap, int32_t d, int64_t n, const void* src_a, 
     return launch_status();
 }
 
+// ---- supervised contrastive loss with a key queue on the tile GEMMs (include/aecf_hip.h, "supervised contrastive loss with a key
+// queue, tile-GEMM form")
+
+size_t aecf_supcon_queue_workspace_bytes(int64_t rows, int64_t cols, int64_t q_cap, int32_t d) {
+    if (rows <= 0 || cols <= 0 || d <= 0 || rows > cols || cols > 0x7fffffff || q_cap <= 0 || q_cap > 0x7fffffff ||
+        !supcon_queue_gemm_supported(d, 0.025f, cols, q_cap))
+        return 0;
+    return supcon_queue_gemm_workspace_bytes(rows, cols, q_cap, d);
+}
+
+int aecf_supcon_queue_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                            const void* a_loc, const void* b_loc, const void* Qa, const void* Qb, int64_t q_cap, const int64_t* q_valid,
+                            const void* b_all, const int64_t* row_labels, const int64_t* col_labels, const int64_t* q_labels,
+                            void* workspace, size_t workspace_bytes, float* col_stats, void* stream) {
+    if (!nce_queue_dims_ok(rows, cols, row_offset, d, min_temperature, q_cap)) return AECF_ERR_BAD_DIMS;
+    if (!supcon_queue_gemm_supported(d, min_temperature, cols, q_cap)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_loc || !Qa || !Qb || !q_valid || !b_all || !row_labels || !col_labels || !q_labels || !workspace ||
+        !col_stats)
+        return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < supcon_queue_gemm_workspace_bytes(rows, cols, q_cap, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_supcon_queue_gemm_pass1(rows, cols, row_offset, d, dt, a_loc, b_loc, b_all, Qa, Qb, q_cap, q_valid, row_labels, col_labels,
+                                   q_labels, workspace, col_stats, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_supcon_queue_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                           const void* a_loc, const void* b_all, int64_t q_cap, const float* col_stats, void* workspace,
+                           size_t workspace_bytes, float* loss_rows, void* stream) {
+    if (!nce_queue_dims_ok(rows, cols, row_offset, d, min_temperature, q_cap)) return AECF_ERR_BAD_DIMS;
+    if (!supcon_queue_gemm_supported(d, min_temperature, cols, q_cap)) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_all || !col_stats || !workspace || !loss_rows) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < supcon_queue_gemm_workspace_bytes(rows, cols, q_cap, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, nullptr};
+    launch_supcon_queue_gemm_loss(rows, cols, row_offset, d, dt, a_loc, b_all, q_cap, col_stats, workspace, loss_rows,
+                                  (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_supcon_queue_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature, float min_temperature,
+                            float coef, const void* a_loc, const void* b_loc, const void* Qa, const void* Qb, int64_t q_cap,
+                            const int64_t* q_valid, const void* b_all, const int64_t* row_labels, const int64_t* col_labels,
+                            const int64_t* q_labels, void* workspace, size_t workspace_bytes, const float* upstream, int32_t grad_dtype,
+                            void* d_a_loc, void* d_b_loc, void* d_b_all, float* d_temperature, void* stream) {
+    if (!nce_queue_dims_ok(rows, cols, row_offset, d, min_temperature, q_cap)) return AECF_ERR_BAD_DIMS;
+    if (!supcon_queue_gemm_supported(d, min_temperature, cols, q_cap)) return AECF_ERR_UNSUPPORTED;
+    if (grad_dtype != AECF_BF16 && grad_dtype != AECF_F32) return AECF_ERR_UNSUPPORTED;
+    if (!temperature || !a_loc || !b_loc || !Qa || !Qb || !q_valid || !b_all || !row_labels || !col_labels || !q_labels || !workspace ||
+        !d_a_loc || !d_b_loc || !d_b_all)
+        return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < supcon_queue_gemm_workspace_bytes(rows, cols, q_cap, d)) return AECF_ERR_WORKSPACE;
+    const NceDevTemp dt = {temperature, min_temperature, d_temperature};
+    launch_supcon_queue_gemm_grads(rows, cols, row_offset, d, dt, coef, a_loc, b_loc, b_all, Qa, Qb, q_cap, q_valid, row_labels,
+                                   col_labels, q_labels, workspace, upstream, grad_dtype == AECF_BF16 ? 1 : 0, d_a_loc, d_b_loc,
+                                   d_b_all, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_key_queue_push_labeled(int64_t q_cap, int32_t d, int64_t n, const void* src_a, const void* src_b, const int64_t* src_labels,
+                                void* Qa, void* Qb, int64_t* Ql, int64_t* state, void* stream) {
+    if (q_cap <= 0 || q_cap > 0x7fffffff || d <= 0 || n < 0) return AECF_ERR_BAD_DIMS;
+    if (d % 8 != 0) return AECF_ERR_UNSUPPORTED;
+    if (!Qa || !Qb || !Ql || !state || (n > 0 && (!src_a || !src_b))) return AECF_ERR_NULL_POINTER;
+    launch_key_queue_push_labeled(q_cap, d, n, src_a, src_b, src_labels, Qa, Qb, Ql, state, (hipStream_t)stream);
+    return launch_status();
+}
+
 // ---- multi-view InfoNCE on the tile GEMMs (include/aecf_hip.h, "multi-view InfoNCE, tile-GEMM form")
 
 namespace {

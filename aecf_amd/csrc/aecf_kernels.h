@@ -390,6 +390,27 @@ void launch_nce_queue_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset,
 void launch_key_queue_push(int64_t q_cap, int d, int64_t n, const void* src_a, const void* src_b, void* qa, void* qb, int64_t* state,
                            hipStream_t s);
 
+// Supervised contrastive loss with a key queue on the tile GEMMs (aecf_nce_gemm.hip): the three blocks above with label positives.
+// X runs EPI_SUP; U and W run EPI_SUP_Q against the ring of stored labels q_labels [q_cap] (rows only; a slot at or above *q_valid
+// is no key and no positive, by index).  col_stats [3][cols] (X's column statistics, plus W's row statistics on this rank's own
+// range) is what ranks exchange.  launch_key_queue_push_labeled fills the label ring with the two key rings (src_labels NULL: -1).
+bool supcon_queue_gemm_supported(int d, float min_temperature, int64_t cols, int64_t q_cap);
+size_t supcon_queue_gemm_workspace_bytes(int64_t rows, int64_t cols, int64_t q_cap, int d);
+void launch_supcon_queue_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                    const void* b_loc, const void* b_all, const void* qa, const void* qb, int64_t q_cap,
+                                    const int64_t* q_valid, const int64_t* row_labels, const int64_t* col_labels,
+                                    const int64_t* q_labels, void* workspace, float* col_stats, hipStream_t s);
+void launch_supcon_queue_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                   const void* b_all, int64_t q_cap, const float* col_stats, void* workspace, float* loss_rows,
+                                   hipStream_t s);
+void launch_supcon_queue_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef,
+                                    const void* a_loc, const void* b_loc, const void* b_all, const void* qa, const void* qb,
+                                    int64_t q_cap, const int64_t* q_valid, const int64_t* row_labels, const int64_t* col_labels,
+                                    const int64_t* q_labels, void* workspace, const float* upstream, int out_bf16, void* d_a_loc,
+                                    void* d_b_loc, void* d_b_all, hipStream_t s);
+void launch_key_queue_push_labeled(int64_t q_cap, int d, int64_t n, const void* src_a, const void* src_b, const int64_t* src_labels,
+                                   void* qa, void* qb, int64_t* ql, int64_t* state, hipStream_t s);
+
 // Multi-view InfoNCE on the tile GEMMs (aecf_nce_gemm.hip): the symmetric InfoNCE of every pair of views (anchor < 0) or of every
 // pair with the anchor view, read in place from x_loc [rows][views][d] / x_all [cols][views][d]; one launch per stage for all
 // pairs, gradient products with K through every partner block of a view.  col_sums [P][cols] is what ranks exchange.

@@ -187,6 +187,17 @@
 // behind them, d b_loc = W_W Qa, d b_all = W_X^T a_loc.  The products run over all q_cap slots with an exact-zero weight above V
 // (the cost follows q_cap, not V; the slots must hold finite rows).  The ring buffer keeps (cursor, valid) on the device: a copy
 // kernel that reads the old cursor, a one-thread launch behind it that bumps both -- no host read, no atomics, capturable.
+//
+// The supervised contrastive loss with a key queue (aecf_supcon_queue_pass1 / _loss / _grads, aecf_key_queue_push_labeled) joins the
+// two: the three blocks above with the label statistics of the pooled supervised form.  X runs EPI_SUP unchanged; U and W run
+// EPI_SUP_Q -- EPI_EXP_Q's count, dead tile, unmasked tile and crossed tile, plus the ROW half of the label search against ONE ring
+// of stored labels Ql [q_cap] (slot s of Qa, Qb and Ql is the same past row).  A slot at or above V is no key and no positive by
+// its index: it gets the 32-bit key no row has, and its label is never read.  A stored key is nobody's partner and nobody's self.
+// sup_sums_kernel (row blocks alone), sup_pool_combine_kernel and sup_finalize_kernel serve unchanged on (Da, ka, sa) = X's + U's
+// and (Db, kb, sb) = the ranks' column statistics of X plus W's on the owner's range: one all-reduce of [3][cols].  W_X is
+// sup_weights_kernel<false>, W_U and W_W its QUEUE variant (m = [j < V] & label match, V from the device; v = rnc = 0; W with u, rn
+// gathered at off + i).  The four products, the slab sum and the dT reduction are those of the key-queue InfoNCE.  The label ring is
+// written by a copy kernel of its own between the key copy and the bump, from the cursor the push found.
 #include <math.h>
 #include <type_traits>
 
@@ -209,7 +220,8 @@ enum { OP_ROW = 0, OP_COL = 1, OP_COLB = 2 };      // OP_COLB: OP_COL from the t
 // sum of the raw accumulators of the elements that match by label (the partner and the padding excluded)
 enum { EPI_EXP = 0, EPI_OUT = 1, EPI_EXP_DT = 2, EPI_OUT_TD = 3, EPI_SIG = 4, EPI_OUT_S = 5, EPI_OUT_TD_S = 6, EPI_RANK = 7, EPI_TOPK = 8,
        EPI_SUP = 9, EPI_SETS_OV = 10, EPI_SETS_JAC = 11, EPI_EXP_SELF = 12, EPI_SUP_SELF = 13,
-       EPI_SETS_OV_SELF = 14, EPI_SETS_JAC_SELF = 15, EPI_EXP_MASK = 16, EPI_EXP_DTS = 17, EPI_EXP_MASK_S = 18, EPI_EXP_Q = 19 };
+       EPI_SETS_OV_SELF = 14, EPI_SETS_JAC_SELF = 15, EPI_EXP_MASK = 16, EPI_EXP_DTS = 17, EPI_EXP_MASK_S = 18, EPI_EXP_Q = 19,
+       EPI_SUP_Q = 20 };
 // EPI_SETS_OV / EPI_SETS_JAC (multi-label contrastive loss, logits pass): EPI_EXP_DT plus, per row and per column of the tile, the
 // float32 sums of w and of w * raw accumulator, w the overlap / Jaccard weight of the two class sets (partner and padding excluded)
 constexpr bool epi_is_sets(int epi) { return epi == EPI_SETS_OV || epi == EPI_SETS_JAC; }
@@ -237,9 +249,14 @@ constexpr bool epi_is_mask(int epi) { return epi == EPI_EXP_MASK || epi == EPI_E
 constexpr bool epi_has_ts(int epi) { return epi == EPI_EXP_DTS || epi == EPI_EXP_MASK_S; }
 // EPI_EXP_Q (InfoNCE with a key queue, the blocks of local rows against stored keys): EPI_EXP_SELF's E loop and row partials over
 // the n_valid slots of a ring buffer of which only columns 0 .. *q_valid - 1 hold keys (q_valid: a DEVICE int64, handed over in
-// lab_row and read once per block).  A column at or above it is E = 0 in the stored tile and in the row sum BY INDEX; a tile wholly
+// q_count and read once per block).  A column at or above it is E = 0 in the stored tile and in the row sum BY INDEX; a tile wholly
 // below it runs the unmasked loop, a tile wholly at or above it stores zeros without running its K loop, and only the tile the
 // count crosses pays for the per-column test.  No column sums or partials of any kind.
+// EPI_SUP_Q (supervised contrastive loss with a key queue, the same two blocks): EPI_EXP_Q's arrangement to the letter -- the count
+// in q_count, the dead tile, the unmasked tile, the crossed tile -- plus the ROW half of EPI_SUP's label search as EPI_SUP_SELF has
+// it, against the ring of stored labels in lab_col: rowcnt_part / rowsx_part get the count and the float32 raw-score sum of the
+// slots below the count whose label is the row's.  No partner and no self: a stored key is nobody's.
+constexpr bool epi_is_queue(int epi) { return epi == EPI_EXP_Q || epi == EPI_SUP_Q; }
 enum { MAP_2D = 0, MAP_UNITS = 1, MAP_SPLITX = 2 };
 
 constexpr int BT = 256;                 // block tile (m and n)
@@ -301,6 +318,8 @@ struct NceGemmArgs {
     const unsigned char* pres_row;      // [m_valid]  presence byte of output row i (bit v: view v present)
     const unsigned char* pres_col;      // [n_valid]  presence byte of output column j
     unsigned int pres_need;             // the bits a row and a column must both hold: the two views of the pair
+    // EPI_EXP_Q / EPI_SUP_Q (also read temp / min_temp; EPI_SUP_Q also lab_row / lab_col and writes rowcnt_part / rowsx_part)
+    const long long* q_count;           // DEVICE int64: columns 0 .. *q_count - 1 hold keys (read once per block)
 };
 
 // The match by label of the supervised contrastive loss: the same non-negative class, all 64 bits compared.  The ONE place that
@@ -1075,12 +1094,16 @@ __global__ __launch_bounds__(256) void sup_finalize_kernel(SupFinArgs p) {
 // SELF (blocks Y and Z of the pooled loss): the element at column row_offset + i is the anchor itself -- no positive, its weight
 // exactly ct * 0 (ediag is not read); the callers pass a vector of zeros for v and rnc, so that a chunk without a match has the
 // bits of nce_weights_dt_kernel at v = 0 and a match is E u_i - rn_i.
-template <bool SELF>
+// QUEUE (blocks U and W of the supervised loss with a key queue; cols = the capacity, lab_col = the ring of stored labels): NO
+// partner element and no self -- a stored key is nobody's -- and m = [j < *q_count] & the label match, the count read from the
+// device (clamped into 0 .. cols; the label of a slot at or above it may be anything).  v and rnc are the vector of zeros as for
+// SELF; ediag is not read.  A slot at or above the count holds E = 0 and m = 0: its weight is an exact zero.
+template <bool SELF, bool QUEUE = false>
 __global__ __launch_bounds__(256) void sup_weights_kernel(unsigned short* e, int64_t e_tiles, int64_t m_tiles, const float* u,
                                                           const float* v, const float* rn, const float* rnc, const float* ediag,
                                                           const long long* lab_row, const long long* lab_col, int64_t rows,
                                                           int64_t cols, int64_t row_offset, float coef, const float* upstream,
-                                                          const float* temp, float min_temp) {
+                                                          const float* temp, float min_temp, const long long* q_count) {
     float ct = coef * nce_dev_inv_temp(temp, min_temp);
     const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;         // 16-byte chunk: 2048 per tile, 8 per tile row
     if (id >= m_tiles * e_tiles * 2048) return;
@@ -1093,13 +1116,16 @@ __global__ __launch_bounds__(256) void sup_weights_kernel(unsigned short* e, int
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(v + j0), v1 = *reinterpret_cast<const f32x4*>(v + j0 + 4);
     const bool iok = i < rows;
     const long long lr = lab_row[iok ? i : rows - 1];
-    const int64_t jp = iok ? row_offset + i - j0 : -1;
+    const int64_t jp = (iok && !QUEUE) ? row_offset + i - j0 : -1;
+    int64_t qv = cols;
+    if (QUEUE) { const long long c = *q_count; qv = c < 0 ? 0 : (c > cols ? cols : c); }
     unsigned int mm = 0;                                        // bit k: element k is a positive (by label or the partner)
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const int64_t j = j0 + k;
         const long long lck = lab_col[j < cols ? j : cols - 1];
-        if (SELF) { if (iok && j < cols && sup_label_match(lr, lck) && jp != k) mm |= 1u << k; }
+        if (QUEUE) { if (iok && j < qv && sup_label_match(lr, lck)) mm |= 1u << k; }
+        else if (SELF) { if (iok && j < cols && sup_label_match(lr, lck) && jp != k) mm |= 1u << k; }
         else if (iok && j < cols && (sup_label_match(lr, lck) || jp == k)) mm |= 1u << k;
     }
     float x[8];
@@ -1916,7 +1942,7 @@ void launch_supcon_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, in
     const int64_t chunks = Rp * (Cp / 8);
     sup_weights_kernel<false><<<dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s>>>(
         w.e, Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, (const long long*)row_labels, (const long long*)col_labels, rows, cols,
-        row_offset, coef, upstream, dt.t, dt.min_t);
+        row_offset, coef, upstream, dt.t, dt.min_t, nullptr);
     // the tdot partials go into the first plane of the row partials (dead since the sums launch), as in launch_nce_gemm_grads
     launch_grad_products<EPI_OUT, EPI_OUT_TD>(rows, cols, d, NceGemmArgs{}, w.e, w.slabs, w.row_part, &dt, a, b, out_bf16, da, db, s);
 }
@@ -2232,7 +2258,7 @@ void launch_nce_queue_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset,
         g.e = w.e[k]; g.e_tiles = Qp / 64;
         g.rowsum_part = w.rowsum_part;
         g.temp = dt.t; g.min_temp = dt.min_t;
-        g.lab_row = reinterpret_cast<const long long*>(q_valid);            // EPI_EXP_Q: the device count of valid slots
+        g.q_count = reinterpret_cast<const long long*>(q_valid);            // EPI_EXP_Q: the device count of valid slots
         launch_gemm<OP_ROW, OP_ROW, EPI_EXP_Q, MAP_2D>(g, L.blocks, s);
         // the row blocks of the sums launch alone: this block leaves no column partials
         nce_sums_kernel<<<dim3((unsigned)(Rp / 64)), dim3(256), 0, s>>>(w.rowsum_part, nullptr, g.m_tiles, g.n_tiles, rows, q_cap,
@@ -2475,12 +2501,200 @@ void launch_supcon_pool_gemm_grads(int64_t rows, int64_t cols, int64_t row_offse
     const long long* lc = (const long long*)col_labels;
     sup_pool_prep_kernel<<<dim3((unsigned)(Cp / 256)), dim3(256), 0, s>>>(w.v, w.rnc, w.uz, w.rnz, w.zero, rows, row_offset, Rp, Cp);
     sup_weights_kernel<false><<<wgrid, dim3(256), 0, s>>>(w.e[0], Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, lr, lc, rows, cols,
-                                                          row_offset, coef, upstream, dt.t, dt.min_t);
+                                                          row_offset, coef, upstream, dt.t, dt.min_t, nullptr);
     sup_weights_kernel<true><<<wgrid, dim3(256), 0, s>>>(w.e[1], Cp / 64, Rp / BT, w.u, w.zero, w.rn, w.zero, nullptr, lr, lc, rows, cols,
-                                                         row_offset, coef, upstream, dt.t, dt.min_t);
+                                                         row_offset, coef, upstream, dt.t, dt.min_t, nullptr);
     sup_weights_kernel<true><<<wgrid, dim3(256), 0, s>>>(w.e[2], Cp / 64, Rp / BT, w.uz, w.zero, w.rnz, w.zero, nullptr, lr, lc, rows, cols,
-                                                         row_offset, coef, upstream, dt.t, dt.min_t);
+                                                         row_offset, coef, upstream, dt.t, dt.min_t, nullptr);
     sup_pool_products(w, rows, cols, d, dt, a_loc, b_loc, a_all, b_all, out_bf16, d_a_loc, d_b_loc, d_a_all, d_b_all, s);
+}
+
+// ---- supervised contrastive loss with a key queue: the key-queue InfoNCE's three blocks with the label statistics of the supervised
+// loss on each (include/aecf_hip.h) ---------------------------------------------------------------------------------------------------
+//   X = a_loc . b_all^T (EPI_SUP, the cross-view pass 1 to the bit: row statistics and this rank's column statistics)
+//   U = a_loc . Qb^T, W = b_loc . Qa^T (EPI_SUP_Q: the slots at or above *q_valid left out by index, of the sums and of the matches;
+//       the ring of stored labels Ql as column labels; row statistics alone)
+// Anchor a_i: (Da, ka, sa) = X's row statistics + U's; anchor b_g: (Db, kb, sb) = the ranks' column statistics of X plus W's row
+// statistics of the row's owner -- sup_pool_combine_kernel, before the ONE all-reduce of [3][cols].  sup_finalize_kernel serves
+// unchanged; W_X is sup_weights_kernel's, W_U and W_W its QUEUE variant (v = rnc = 0; W with u and rn gathered at off + i); the four
+// products are those of launch_nce_queue_gemm_grads.  The queues and their labels take no gradient.
+
+namespace {
+
+struct SupQueWs {
+    unsigned short* e[3];               // X [Rp][Cp] | U [Rp][Qp] | W [Rp][Qp] bf16, tiled as E
+    float* row_part;                    // [3][max(Cp, Qp) / 256][Rp]  sums of E | counts | matched sums, one block after the other
+    float* col_part;                    // [3][m_tiles][Cp]  block X
+    float* row_stats;                   // [3][Rp]  X's, then the combined Da | ka | sa
+    float* u_stats;                     // [3][Rp]
+    float* w_stats;                     // [3][Rp]
+    float* u;                           // [Rp]  1 / Da
+    float* rn;                          // [Rp]  1 / na
+    float* v;                           // [Cp]  1 / Db
+    float* rnc;                         // [Cp]  1 / nb
+    float* uz;                          // [Rp]  1 / Db_(off + i)
+    float* rnz;                         // [Rp]  1 / nb_(off + i)
+    float* ediag;                       // [Rp]
+    float* zero;                        // [max(Cp, Qp)]
+    float* tdot_part;                   // [3][splits <= 32][m_tiles][n_tiles_d <= 16]
+    float* slabs;                       // [splits X + splits Q][rows][d]: the slabs of W_X b_all, behind them those of W_U Qb
+    size_t bytes;
+};
+
+SupQueWs sup_que_carve(void* ws, int64_t rows, int64_t cols, int64_t q_cap, int d) {
+    const int64_t Rp = up256(rows), Cp = up256(cols), Qp = up256(q_cap), Zp = Cp > Qp ? Cp : Qp;
+    const int64_t mt = Rp / BT;
+    SupQueWs w;
+    char* p = (char*)ws;
+    size_t off = 0;
+    auto take = [&](size_t n) { char* r = p + off; off += al256(n); return r; };
+    w.e[0] = (unsigned short*)take((size_t)Rp * Cp * 2);
+    for (int k = 1; k < 3; ++k) w.e[k] = (unsigned short*)take((size_t)Rp * Qp * 2);
+    w.row_part = (float*)take((size_t)3 * (Zp / BT) * Rp * 4);
+    w.col_part = (float*)take((size_t)3 * mt * Cp * 4);
+    w.row_stats = (float*)take((size_t)3 * Rp * 4);
+    w.u_stats = (float*)take((size_t)3 * Rp * 4);
+    w.w_stats = (float*)take((size_t)3 * Rp * 4);
+    w.u = (float*)take((size_t)Rp * 4);
+    w.rn = (float*)take((size_t)Rp * 4);
+    w.v = (float*)take((size_t)Cp * 4);
+    w.rnc = (float*)take((size_t)Cp * 4);
+    w.uz = (float*)take((size_t)Rp * 4);
+    w.rnz = (float*)take((size_t)Rp * 4);
+    w.ediag = (float*)take((size_t)Rp * 4);
+    w.zero = (float*)take((size_t)Zp * 4);
+    w.tdot_part = (float*)take((size_t)3 * 32 * 16 * mt * 4);
+    w.slabs = (float*)take((size_t)(da_splits(Rp, Cp, d) + da_splits(Rp, Qp, d)) * rows * d * 4);
+    w.bytes = off;
+    return w;
+}
+
+// The ring of stored labels beside the two key rings: the label of row i of the m = min(n, q_cap) LAST source rows goes to the slot
+// key_queue_copy_kernel gives its keys, from the cursor the push found (the bump runs behind both copies).  src == NULL: -1, so
+// that no label of an overwritten key stays attached to a new one.
+__global__ __launch_bounds__(256) void key_queue_label_copy_kernel(int64_t q_cap, int64_t n, int64_t m, const long long* src,
+                                                                   long long* ql, const long long* state) {
+    const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (id >= m) return;
+    const int64_t i = n - m + id;
+    const long long cur = state[0];
+    const int64_t slot = (int64_t)(((cur < 0 ? 0 : cur) % q_cap + i % q_cap) % q_cap);
+    ql[slot] = src ? src[i] : -1ll;
+}
+
+}  // namespace
+
+// An anchor's count adds the matches of two blocks, at most cols - 1 of the batch (the partner excluded) and q_cap of the queue:
+// 1 + (cols - 1) + q_cap has to stay an exact float32 integer, so cols + q_cap <= 2^24.
+bool supcon_queue_gemm_supported(int d, float min_temperature, int64_t cols, int64_t q_cap) {
+    return nce_gemm_supported(0, d, min_temperature) && cols + q_cap <= ((int64_t)1 << 24);
+}
+
+size_t supcon_queue_gemm_workspace_bytes(int64_t rows, int64_t cols, int64_t q_cap, int d) {
+    return sup_que_carve(nullptr, rows, cols, q_cap, d).bytes + 256;
+}
+
+void launch_key_queue_push_labeled(int64_t q_cap, int d, int64_t n, const void* src_a, const void* src_b, const int64_t* src_labels,
+                                   void* qa, void* qb, int64_t* ql, int64_t* state, hipStream_t s) {
+    if (n <= 0) return;
+    const int64_t m = n < q_cap ? n : q_cap;
+    const int chunks = d / 8;
+    key_queue_copy_kernel<<<dim3((unsigned)((m * chunks + 255) / 256)), dim3(256), 0, s>>>(
+        q_cap, chunks, n, m, (const u32x4*)src_a, (const u32x4*)src_b, (u32x4*)qa, (u32x4*)qb, (const long long*)state);
+    key_queue_label_copy_kernel<<<dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s>>>(q_cap, n, m, (const long long*)src_labels,
+                                                                                       (long long*)ql, (const long long*)state);
+    key_queue_bump_kernel<<<dim3(1), dim3(64), 0, s>>>(q_cap, n, (long long*)state);
+}
+
+// pass 1: the three blocks, the combined row statistics (workspace) and col_stats [3][cols] = this rank's column statistics of X, plus
+// the row statistics of W on [row_offset, row_offset + rows)
+void launch_supcon_queue_gemm_pass1(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                    const void* b_loc, const void* b_all, const void* qa, const void* qb, int64_t q_cap,
+                                    const int64_t* q_valid, const int64_t* row_labels, const int64_t* col_labels,
+                                    const int64_t* q_labels, void* workspace, float* col_stats, hipStream_t s) {
+    const SupQueWs w = sup_que_carve(workspace, rows, cols, q_cap, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols), Qp = up256(q_cap);
+    {
+        LogitsLaunch L = logits_args(rows, cols, d, a_loc, b_all);
+        NceGemmArgs& g = L.g;
+        g.e = w.e[0]; g.e_tiles = Cp / 64;
+        g.temp = dt.t; g.min_temp = dt.min_t; g.row_offset = row_offset;
+        g.lab_row = (const long long*)row_labels; g.lab_col = (const long long*)col_labels;
+        const int64_t rplane = (int64_t)g.n_tiles * Rp, cplane = (int64_t)g.m_tiles * Cp;
+        g.rowsum_part = w.row_part; g.rowcnt_part = w.row_part + rplane; g.rowsx_part = w.row_part + 2 * rplane;
+        g.colsum_part = w.col_part; g.colcnt_part = w.col_part + cplane; g.colsx_part = w.col_part + 2 * cplane;
+        launch_gemm<OP_ROW, OP_ROW, EPI_SUP, MAP_2D>(g, L.blocks, s);
+        sup_sums_kernel<<<dim3((unsigned)((Rp + Cp) / 64), 3), dim3(256), 0, s>>>(w.row_part, w.col_part, g.m_tiles, g.n_tiles, rows, cols,
+                                                                                  w.row_stats, col_stats);
+    }
+    for (int k = 1; k < 3; ++k) {
+        LogitsLaunch L = logits_args(rows, q_cap, d, k == 1 ? a_loc : b_loc, k == 1 ? qb : qa);
+        NceGemmArgs& g = L.g;
+        g.e = w.e[k]; g.e_tiles = Qp / 64;
+        g.temp = dt.t; g.min_temp = dt.min_t;
+        g.lab_row = (const long long*)row_labels; g.lab_col = (const long long*)q_labels;
+        g.q_count = reinterpret_cast<const long long*>(q_valid);
+        const int64_t rplane = (int64_t)g.n_tiles * Rp;
+        g.rowsum_part = w.row_part; g.rowcnt_part = w.row_part + rplane; g.rowsx_part = w.row_part + 2 * rplane;
+        launch_gemm<OP_ROW, OP_ROW, EPI_SUP_Q, MAP_2D>(g, L.blocks, s);
+        // the row blocks of the sums launch alone: this block leaves no column partials
+        sup_sums_kernel<<<dim3((unsigned)(Rp / 64), 3), dim3(256), 0, s>>>(w.row_part, nullptr, g.m_tiles, g.n_tiles, rows, q_cap,
+                                                                           k == 1 ? w.u_stats : w.w_stats, nullptr);
+    }
+    sup_pool_combine_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s>>>(w.row_stats, w.u_stats, w.w_stats, col_stats, rows,
+                                                                                       cols, row_offset, Rp);
+}
+
+// normalisers + loss rows of this rank's pairs from the col_stats of all ranks: sup_finalize_kernel on the combined statistics
+void launch_supcon_queue_gemm_loss(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, const void* a_loc,
+                                   const void* b_all, int64_t q_cap, const float* col_stats, void* workspace, float* loss_rows,
+                                   hipStream_t s) {
+    const SupQueWs w = sup_que_carve(workspace, rows, cols, q_cap, d);
+    SupFinArgs f = {};
+    f.a = (const unsigned short*)a_loc; f.b = (const unsigned short*)b_all; f.row_stats = w.row_stats; f.col_stats = col_stats;
+    f.u = w.u; f.rn = w.rn; f.v = w.v; f.rnc = w.rnc; f.loss_rows = loss_rows; f.ediag = w.ediag;
+    f.rows = rows; f.cols = cols; f.row_offset = row_offset; f.Rp = up256(rows); f.Cp = up256(cols); f.d = d;
+    f.temp = dt.t; f.min_temp = dt.min_t;
+    sup_finalize_kernel<<<dim3((unsigned)((f.Rp + 3) / 4)), dim3(256), 0, s>>>(f);
+}
+
+// gradients: the three weights passes in place, then the four products of launch_nce_queue_gemm_grads
+//   d_a_loc = W_X b_all + W_U Qb (one slab sum over both products' slabs)      d_b_loc = W_W Qa      d_b_all = W_X^T a_loc
+// every output rounded once from its float32 sum; dt.d_t from the partials of the three da products, one fixed-order reduction.
+// Every slot of the key rings is read (the weight of a slot at or above *q_valid is an exact zero): they must hold finite rows.
+void launch_supcon_queue_gemm_grads(int64_t rows, int64_t cols, int64_t row_offset, int d, const NceDevTemp& dt, float coef,
+                                    const void* a_loc, const void* b_loc, const void* b_all, const void* qa, const void* qb,
+                                    int64_t q_cap, const int64_t* q_valid, const int64_t* row_labels, const int64_t* col_labels,
+                                    const int64_t* q_labels, void* workspace, const float* upstream, int out_bf16, void* d_a_loc,
+                                    void* d_b_loc, void* d_b_all, hipStream_t s) {
+    const SupQueWs w = sup_que_carve(workspace, rows, cols, q_cap, d);
+    const int64_t Rp = up256(rows), Cp = up256(cols), Qp = up256(q_cap), Zp = Cp > Qp ? Cp : Qp;
+    const dim3 xgrid((unsigned)((Rp * (Cp / 8) + 255) / 256)), qgrid((unsigned)((Rp * (Qp / 8) + 255) / 256));
+    const long long* lr = (const long long*)row_labels;
+    const long long* lc = (const long long*)col_labels;
+    const long long* lq = (const long long*)q_labels;
+    const long long* qv = (const long long*)q_valid;
+    sup_pool_prep_kernel<<<dim3((unsigned)(Zp / 256)), dim3(256), 0, s>>>(w.v, w.rnc, w.uz, w.rnz, w.zero, rows, row_offset, Rp, Zp);
+    sup_weights_kernel<false><<<xgrid, dim3(256), 0, s>>>(w.e[0], Cp / 64, Rp / BT, w.u, w.v, w.rn, w.rnc, w.ediag, lr, lc, rows, cols,
+                                                          row_offset, coef, upstream, dt.t, dt.min_t, nullptr);
+    sup_weights_kernel<false, true><<<qgrid, dim3(256), 0, s>>>(w.e[1], Qp / 64, Rp / BT, w.u, w.zero, w.rn, w.zero, nullptr, lr, lq, rows,
+                                                                q_cap, row_offset, coef, upstream, dt.t, dt.min_t, qv);
+    sup_weights_kernel<false, true><<<qgrid, dim3(256), 0, s>>>(w.e[2], Qp / 64, Rp / BT, w.uz, w.zero, w.rnz, w.zero, nullptr, lr, lq, rows,
+                                                                q_cap, row_offset, coef, upstream, dt.t, dt.min_t, qv);
+    const bool want_td = dt.d_t != nullptr;
+    const int64_t n_tdx = da_tdot_count(rows, cols, d), n_tdq = da_tdot_count(rows, q_cap, d), n_loc = rows * (int64_t)d;
+    const NceGemmArgs g0 = {};
+    // both products always leave float32 slabs, those of W_U Qb behind those of W_X b_all: one sum, one rounding
+    const int sx = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, cols, d, g0, w.e[0], w.slabs, w.tdot_part, want_td, a_loc, b_all, 0,
+                                                          nullptr, s);
+    const int su = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, q_cap, d, g0, w.e[1], w.slabs + sx * n_loc, w.tdot_part + n_tdx, want_td,
+                                                          a_loc, qb, 0, nullptr, s);
+    launch_slab_sum(w.slabs, sx + su, n_loc, d_a_loc, out_bf16, s);
+    const int sw = launch_da_product<EPI_OUT, EPI_OUT_TD>(rows, q_cap, d, g0, w.e[2], w.slabs, w.tdot_part + n_tdx + n_tdq, want_td, b_loc,
+                                                          qa, out_bf16, d_b_loc, s);
+    if (sw) launch_slab_sum(w.slabs, sw, n_loc, d_b_loc, out_bf16, s);
+    if (want_td) launch_nce_dtemp(w.tdot_part, n_tdx + 2 * n_tdq, 1, dt, s);
+    launch_db_product<EPI_OUT>(rows, cols, d, g0, w.e[0], a_loc, out_bf16, d_b_all, s);
 }
 
 // ---- pooled multi-label contrastive loss: the pooled form above with class sets and a weighting in place of the labels

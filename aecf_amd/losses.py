@@ -1404,9 +1404,11 @@ class KeyQueue:
     buffers ``keys_a``, ``keys_b`` [capacity, d] bfloat16 (zeros until written) and ``state``, a device int64 pair (cursor,
     valid).  The state is read and written by kernels alone (aecf_key_queue_push): a push captures into a graph and nothing of it
     is ever read on the host.  ``version`` counts the pushes on the host: the loss's backward reads the buffers again and
-    refuses to run across a push."""
+    refuses to run across a push.  ``labels=True`` adds ``self.labels``, ONE ring of int64 classes [capacity] beside the two key
+    rings (slot s of all three belongs to the same past row; -1 = unlabeled until written), which
+    ``queued_supervised_contrastive`` reads: a stored key of the anchor's class is a positive."""
 
-    def __init__(self, capacity: int, d: int, device):
+    def __init__(self, capacity: int, d: int, device, labels: bool = False):
         capacity, d = int(capacity), int(d)
         if not 1 <= capacity < 2 ** 31:
             raise ValueError(f"aecf_amd: a key queue holds 1 to 2^31 - 1 rows, got capacity = {capacity}")
@@ -1420,14 +1422,22 @@ class KeyQueue:
         self.keys_b = torch.zeros(capacity, d, dtype=torch.bfloat16, device=device)
         self.state = torch.zeros(2, dtype=torch.int64, device=device)
         self.valid = self.state[1:]         # what the loss reads as its count of valid slots
+        self.labels = torch.full((capacity,), -1, dtype=torch.int64, device=device) if labels else None
         self.version = 0
 
     @torch.no_grad()
-    def push(self, za: torch.Tensor, zb: torch.Tensor, group=None, normalize: bool = True) -> None:
+    def push(self, za: torch.Tensor, zb: torch.Tensor, group=None, normalize: bool = True,
+             labels: Optional[torch.Tensor] = None) -> None:
         """Append this step's rows of both views, the oldest slots overwritten first (more rows than the capacity: the last
         ``capacity`` of them stay).  ``za``, ``zb``: [b_local, d] bfloat16 on the queue's device; ``normalize`` runs
         ``l2_normalize`` on them first (pass False for rows that are unit-norm already).  No autograd.  Under data parallel the
-        rows of every rank of ``group`` go in, in all-gather order, so that every rank holds the same queue."""
+        rows of every rank of ``group`` go in, in all-gather order, so that every rank holds the same queue.  ``labels``: on a
+        queue made with ``labels=True``, the [b_local] int64 or int32 classes of the rows (gathered with them); None there writes
+        -1 into the slots the push fills, so that no label of an overwritten key stays attached to a new one.  A queue made
+        without a label ring takes no labels (ValueError)."""
+        if labels is not None and self.labels is None:
+            raise ValueError("aecf_amd: this key queue has no label ring (KeyQueue(..., labels=True) makes one); push takes no "
+                             "labels")
         _require_device(za, "za")
         _require_device(zb, "zb")
         _check_two_views("KeyQueue.push", za, zb)
@@ -1437,6 +1447,15 @@ class KeyQueue:
         na, nb = (l2_normalize(za.detach()), l2_normalize(zb.detach())) if normalize else (za.detach(), zb.detach())
         sizes, _, _ = _row_ranges(za.shape[0], za.device, group)
         na, nb = _all_rows(na, group, sizes).contiguous(), _all_rows(nb, group, sizes).contiguous()
+        if self.labels is not None:
+            lab = None
+            if labels is not None:
+                lab = _all_rows(_labels_arg(labels, za).detach().to(torch.int64), group, sizes).contiguous()
+            _lib.check(_lib.load().aecf_key_queue_push_labeled(self.capacity, self.d, na.shape[0], _ptr(na), _ptr(nb), _ptr(lab),
+                                                               _ptr(self.keys_a), _ptr(self.keys_b), _ptr(self.labels),
+                                                               _ptr(self.state), _stream()), "aecf_key_queue_push_labeled")
+            self.version += 1
+            return
         _lib.check(_lib.load().aecf_key_queue_push(self.capacity, self.d, na.shape[0], _ptr(na), _ptr(nb), _ptr(self.keys_a),
                                                    _ptr(self.keys_b), _ptr(self.state), _stream()), "aecf_key_queue_push")
         self.version += 1
@@ -1564,6 +1583,121 @@ def queued_info_nce(za: torch.Tensor, zb: torch.Tensor, queue: KeyQueue, tempera
     na, nb = l2_normalize(za), l2_normalize(zb)
     nb_all = _all_rows(nb, group, sizes)
     share = _QueuedNce.apply(na, nb, nb_all, queue, offset, t, 0.5 / float(b_all), group, float(min_temperature))
+    return _dp_value(share, group)
+
+
+class _QueuedSupCon(torch.autograd.Function):
+    """aecf_supcon_queue_pass1 / _loss / _grads: ``_QueuedNce`` with label positives -- the a_loc x b_all block with the label
+    statistics of ``_SupConSymmetric`` and the two blocks against the stored keys searched against the queue's label ring (a
+    slot at or above the device count left out by index, of the sums and of the matches).  The [3, cols] column statistics are the
+    one thing ranks exchange.  The queue takes no gradient, but the backward reads keys, labels and count again: it refuses to run
+    where the queue was pushed to since the forward."""
+
+    @staticmethod
+    def forward(ctx, a, b, b_all, lab, lab_all, queue, row_offset, temperature, coef, group, min_temperature):
+        lib = _lib.load()
+        rows, d = a.shape
+        cols = b_all.shape[0]
+        dev = a.device
+        operands = [x.detach().to(torch.bfloat16).contiguous() for x in (a, b, b_all)]
+        labels = [lab.contiguous(), lab_all.contiguous()]
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws_bytes = lib.aecf_supcon_queue_workspace_bytes(rows, cols, queue.capacity, d)
+        if ws_bytes == 0:
+            raise NotImplementedError("aecf_amd: the supervised contrastive loss with a key queue needs d % 64 == 0, 64 <= d <= 4096 "
+                                      f"and gathered rows + capacity <= 2^24; got d = {d}, {cols} rows, capacity {queue.capacity}")
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        col_stats = torch.empty(3, cols, **f32)
+        t = temperature.detach()
+        dims, t_min = (rows, cols, int(row_offset), d), float(min_temperature)
+        stored = (_ptr(queue.keys_a), _ptr(queue.keys_b), queue.capacity, _ptr(queue.valid))
+        riders = (_ptr(labels[0]), _ptr(labels[1]), _ptr(queue.labels))
+        _lib.check(lib.aecf_supcon_queue_pass1(*dims, _ptr(t), t_min, _ptr(operands[0]), _ptr(operands[1]), *stored, _ptr(operands[2]),
+                                               *riders, _ptr(ws), ws_bytes, _ptr(col_stats), _stream()), "aecf_supcon_queue_pass1")
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(col_stats, group=group)
+        loss_rows = torch.empty(rows, **f32)
+        _lib.check(lib.aecf_supcon_queue_loss(*dims, _ptr(t), t_min, _ptr(operands[0]), _ptr(operands[2]), queue.capacity,
+                                              _ptr(col_stats), _ptr(ws), ws_bytes, _ptr(loss_rows), _stream()),
+                   "aecf_supcon_queue_loss")
+        ctx.save_for_backward(t, ws, *operands, *labels)
+        ctx.queue, ctx.queue_version = queue, queue.version
+        ctx.meta = ([x.dtype for x in (a, b, b_all)], temperature.shape, dims, t_min, float(coef), ws_bytes)
+        return loss_rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        lib = _lib.load()
+        t, ws, *rest = ctx.saved_tensors
+        operands, labels = rest[:3], rest[3:]
+        dtypes, t_shape, dims, t_min, coef, ws_bytes = ctx.meta
+        queue = ctx.queue
+        if queue.version != ctx.queue_version:
+            raise RuntimeError("aecf_amd: the key queue was pushed to between the forward and the backward of "
+                               "queued_supervised_contrastive (the gradient products read the stored keys and labels again): the "
+                               "order is loss, backward, push")
+        _spend(ctx, "queued supervised contrastive")
+        gdt = torch.bfloat16 if dtypes.count(torch.bfloat16) == 3 else torch.float32
+        grads = [torch.empty_like(x, dtype=gdt) for x in operands]
+        up = d_loss.detach().to(torch.float32).reshape(1).contiguous()
+        d_t = torch.empty(1, dtype=torch.float32, device=ws.device) if ctx.needs_input_grad[7] else None
+        stored = (_ptr(queue.keys_a), _ptr(queue.keys_b), queue.capacity, _ptr(queue.valid))
+        riders = (_ptr(labels[0]), _ptr(labels[1]), _ptr(queue.labels))
+        _lib.check(lib.aecf_supcon_queue_grads(*dims, _ptr(t), t_min, coef, _ptr(operands[0]), _ptr(operands[1]), *stored,
+                                               _ptr(operands[2]), *riders, _ptr(ws), ws_bytes, _ptr(up), _DTYPES[gdt],
+                                               *map(_ptr, grads), _ptr(d_t), _stream()), "aecf_supcon_queue_grads")
+        g_t = d_t.reshape(t_shape) if d_t is not None else None
+        return (*[g.to(x) for g, x in zip(grads, dtypes)], None, None, None, None, g_t, None, None, None)
+
+
+def queued_supervised_contrastive(za: torch.Tensor, zb: torch.Tensor, labels: torch.Tensor, queue: KeyQueue,
+                                  temperature: Union[float, torch.Tensor] = 0.07, group=None,
+                                  min_temperature: float = MIN_TEMPERATURE) -> torch.Tensor:
+    """Symmetric supervised contrastive loss (L_out) between the local rows of two views with the stored keys of ``queue`` as
+    further keys AND, where their stored label is the anchor's, further positives (cross-batch memory with labels; MoCo-style
+    SupCon).  For an anchor of view a with label y >= 0 the positives are its partner (by index), the gathered rows of view b
+    with label y and the valid slots of ``queue.keys_b`` whose entry of ``queue.labels`` is y; an anchor of view b mirrors it on
+    view a and ``queue.keys_a``,
+
+        L = 0.5 / B_all * sum over both directions and rows i of [ log(sum_batch e^x + sum_queue e^x) - mean_{p in P(i)} x_ip ],
+        x = n . n_k / max(T, min_temperature)
+
+    Same-class keys stay in the denominator.  A negative label is unlabeled: its only positive is the partner, and a stored -1
+    matches nothing.  With an empty queue this is ``supervised_contrastive(..., low_memory=False)`` to the bit, with every label
+    negative ``queued_info_nce``.  ``queue`` must have been made with ``labels=True`` (ValueError otherwise) and be fed by
+    ``queue.push(za, zb, labels=labels)``.  ``labels``: [b_local] int64 or int32 on za's device, shared by the two views.
+
+    Shapes, temperature, ``torch.no_grad()`` and the order of a step (loss, backward, push: the backward reads keys, labels and
+    count again and raises RuntimeError across a push; it runs once per forward) are those of ``queued_info_nce``; on top of its
+    limits, gathered rows + capacity must not exceed 2^24 (an anchor's count of positives travels as an exact float32 integer).
+    Anything else raises NotImplementedError naming the limit.  There is one label per row and one temperature, the cost follows
+    the capacity, there is no streaming form, and the queue is replicated on every rank.  Under data parallel the ranks agree on
+    a refusal and all-reduce the [3, b_all] column statistics between the passes."""
+    _require_device(za, "za")
+    _require_device(zb, "zb")
+    _check_two_views("queued_supervised_contrastive", za, zb)
+    if not isinstance(queue, KeyQueue):
+        raise TypeError(f"aecf_amd: queue must be a KeyQueue, got {type(queue).__name__}")
+    if queue.labels is None:
+        raise ValueError("aecf_amd: queued_supervised_contrastive needs a key queue with a label ring: KeyQueue(..., labels=True)")
+    labels = _labels_arg(labels, za)
+    _check_min_temperature(min_temperature)
+    sizes, offset, b_all = _row_ranges(za.shape[0], za.device, group)
+    refusal = None
+    if b_all + queue.capacity > 2 ** 24:
+        refusal = (f"gathered rows + queue capacity <= 2^24 (got {b_all} + {queue.capacity}): an anchor's count of positives has to "
+                   "stay an exact float32 integer")
+    refusal = refusal or _queue_refusal(za, zb, b_all, queue, min_temperature)
+    # every rank must raise or run together (the ranks that run all-reduce between their passes)
+    refusal = _agreed_refusal(refusal, za.device, group)
+    if refusal is not None:
+        raise NotImplementedError("aecf_amd: the supervised contrastive loss with a key queue needs " + refusal)
+    t = _temperature_scalar(temperature, za, min_temperature)
+    lab = labels.detach().to(torch.int64)
+    na, nb = l2_normalize(za), l2_normalize(zb)
+    nb_all = _all_rows(nb, group, sizes)
+    lab_all = _all_rows(lab, group, sizes)
+    share = _QueuedSupCon.apply(na, nb, nb_all, lab, lab_all, queue, offset, t, 0.5 / float(b_all), group, float(min_temperature))
     return _dp_value(share, group)
 
 
@@ -2028,7 +2162,7 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
                      min_temperature: float = MIN_TEMPERATURE, contrastive: str = "info_nce",
                      bias: Union[None, float, torch.Tensor] = None, low_memory: Optional[bool] = None,
                      labels: Optional[torch.Tensor] = None, label_weighting: str = "overlap",
-                     intra_view: bool = False) -> torch.Tensor:
+                     intra_view: bool = False, queue: Optional["KeyQueue"] = None) -> torch.Tensor:
     """task + entropy_weight * entropy_loss(entropy) [ref README.md:205-208] + contrastive_weight * info_nce(za, zb)
     (``temperature`` / ``min_temperature``: as for ``info_nce``).  ``contrastive="sigmoid"`` takes ``sigmoid_contrastive(za, zb,
     temperature, bias)`` as the contrastive term instead (``bias``: None = its default of -10; ``low_memory``: its choice of
@@ -2046,16 +2180,27 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
     ``contrastive="multilabel_pool"`` takes ``pooled_multilabel_contrastive(za, zb, labels, label_weighting, temperature)``, the
     same pool with label sets: it takes ``labels`` (the sets) and ``label_weighting`` and ignores ``intra_view``; ``low_memory``
     None or False select its one implementation, the tile-GEMM form, and True raises NotImplementedError (there is no streaming
-    form)."""
-    with_labels = ("supervised", "multilabel", "supervised_pool", "multilabel_pool")
-    if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel", "nt_xent", "supervised_pool", "multilabel_pool"):
+    form).
+    ``contrastive="queued"`` takes ``queued_info_nce(za, zb, queue, temperature)`` and ``contrastive="supervised_queued"`` takes
+    ``queued_supervised_contrastive(za, zb, labels, queue, temperature)`` (it takes ``labels``; the queue must hold a label ring):
+    the two forms that take ``queue``, a ``KeyQueue`` the caller pushes to after the backward.  They have one implementation
+    (``low_memory`` is not read); ``queue`` given to any other form raises ValueError."""
+    with_labels = ("supervised", "multilabel", "supervised_pool", "multilabel_pool", "supervised_queued")
+    with_queue = ("queued", "supervised_queued")
+    if contrastive not in ("info_nce", "sigmoid", "supervised", "multilabel", "nt_xent", "supervised_pool", "multilabel_pool",
+                           "queued", "supervised_queued"):
         raise ValueError(f"aecf_amd: contrastive must be 'info_nce', 'sigmoid', 'supervised', 'multilabel', 'nt_xent', "
-                         f"'supervised_pool' or 'multilabel_pool', got {contrastive!r}")
+                         f"'supervised_pool', 'multilabel_pool', 'queued' or 'supervised_queued', got {contrastive!r}")
     if contrastive in with_labels and labels is None:
         raise ValueError(f"aecf_amd: contrastive={contrastive!r} needs labels")
     if contrastive not in with_labels and labels is not None:
-        raise ValueError(f"aecf_amd: labels are taken by contrastive='supervised', 'multilabel', 'supervised_pool' and "
-                         f"'multilabel_pool' only, got contrastive={contrastive!r}")
+        raise ValueError(f"aecf_amd: labels are taken by contrastive='supervised', 'multilabel', 'supervised_pool', "
+                         f"'multilabel_pool' and 'supervised_queued' only, got contrastive={contrastive!r}")
+    if contrastive in with_queue and queue is None:
+        raise ValueError(f"aecf_amd: contrastive={contrastive!r} needs queue, a KeyQueue")
+    if contrastive not in with_queue and queue is not None:
+        raise ValueError(f"aecf_amd: queue is taken by contrastive='queued' and 'supervised_queued' only, got "
+                         f"contrastive={contrastive!r}")
     if label_weighting not in SET_WEIGHTINGS:
         raise ValueError(f"aecf_amd: label_weighting must be 'overlap' or 'jaccard', got {label_weighting!r}")
     total = task_loss
@@ -2089,6 +2234,10 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
                 raise NotImplementedError("aecf_amd: contrastive='multilabel_pool' has no streaming form (low_memory=True); "
                                           "low_memory=None or False take its tile-GEMM form")
             term = pooled_multilabel_contrastive(za, zb, labels, label_weighting, temperature, group, min_temperature)
+        elif contrastive == "queued":
+            term = queued_info_nce(za, zb, queue, temperature, group, min_temperature)
+        elif contrastive == "supervised_queued":
+            term = queued_supervised_contrastive(za, zb, labels, queue, temperature, group, min_temperature)
         else:
             term = info_nce(za, zb, temperature, group, min_temperature)
         total = _plus(total, contrastive_weight * term)

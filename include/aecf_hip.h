@@ -876,6 +876,73 @@ int aecf_nce_queue_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t
 int aecf_key_queue_push(int64_t q_cap, int32_t d, int64_t n, const void* src_a, const void* src_b, void* Qa, void* Qb,
                         int64_t* state /* device (cursor, valid) */, void* stream);
 
+/* ---- supervised contrastive loss with a key queue, tile-GEMM form (build-defined; cross-batch memory with LABELLED past keys) ----
+ * aecf_supcon_sym_* with the stored keys of aecf_nce_queue_*: a stored key of the anchor's class is a POSITIVE, every stored key a
+ * term of the denominator.  A rank holds its local rows a_loc, b_loc [rows,d] with labels row_labels [rows] (shared by the two
+ * views), the gathered b_all [cols,d] with col_labels [cols], the two key rings Qa, Qb [q_cap,d] and ONE ring of stored labels
+ * q_labels [q_cap] (slot s of both key rings belongs to the same past row), int64 DEVICE labels, a negative label = unlabeled,
+ * never a match, all 64 bits compared; V = *q_valid as above.  For anchor a_i with partner p = row_offset + i:
+ *   P(i)   = {p, by INDEX} + {j != p: col_labels[j] == row_labels[i] >= 0} + {slots s < V of Qb: q_labels[s] == row_labels[i] >= 0}
+ *   Da_i   = sum_j E(a_i . b_j) + sum_{s<V} E(a_i . Qb_s)                                  same-class keys stay in the denominator
+ *   loss   = log Da_i + 1/Tc - (1/|P(i)|) sum_{k in P(i)} a_i . k / Tc
+ * Anchor b_g is the mirror image on the transpose of the same a x b block plus the slots of Qa; loss_rows[i] is the sum of both
+ * anchors of pair i, WITHOUT coef.  A slot at or above V is no key and no positive BY ITS INDEX, whatever row or label it holds; a
+ * stored key is nobody's partner: a bit-identical twin of the partner below V is a key like any other, a positive only by its label.
+ * Three logits blocks: X = a_loc . b_all^T runs aecf_supcon_sym_pass1's epilogue to the bit (row and column statistics: sum of E |
+ * count | float32 sum of the matched raw scores); U = a_loc . Qb^T and W = b_loc . Qa^T run ONE epilogue that joins the key-queue
+ * form's (the count read once per block; a tile at or above it stores zeros for E and all three row partials and skips its K loop;
+ * only the crossed tile selects per column in the E loop; the count enters the search through the column keys) with the row
+ * half of the label search (32-bit key vote, the 64-bit compare only in a
+ * row group with a hit, no column accumulators).
+ *   pass1: the three GEMMs; row statistics = X's + U's (workspace); col_stats [3][cols] float32 = this rank's column statistics of
+ *          X, plus W's row statistics on its own range [row_offset, row_offset + rows): one float32 addition each, no atomics.
+ *   caller: all-reduce (sum) of col_stats over the ranks (nothing to do on one rank).
+ *   loss:  loss_rows [rows] by aecf_supcon_sym_loss's kernel on the combined statistics (n = 1 + count); takes no labels.
+ *   grads: W_X = ct (E (1/Da_i + 1/Db_j) - m_ij (1/na_i + 1/nb_j)) as aecf_supcon_sym_grads; W_U = ct (E / Da_i - m_is / na_i) and
+ *          W_W = ct (E / Db_p - m_is / nb_p) with m_is = [s < V] [q_labels[s] == row_labels[i] >= 0], V read from the device; a slot
+ *          at or above V gets an exact zero.  Then the four products, the slab sum and the dT reduction of aecf_nce_queue_grads:
+ *          d_a_loc = W_X b_all + W_U Qb, d_b_loc = W_W Qa, d_b_all = W_X^T a_loc; float32 or bf16 (one rounding), times upstream[0];
+ *          d_temperature as there.  It consumes the stored blocks (once per pass1) and reads Qa, Qb, q_labels and *q_valid again:
+ *          none of them may change between pass1 and grads.  The key slots at or above V MUST HOLD FINITE ROWS (the products read
+ *          them with a zero weight); the label slots at or above V may hold anything.
+ * With an empty queue (V = 0) every output has the bits of aecf_supcon_sym_*; with every label negative, those of aecf_nce_queue_*.
+ * Served: bf16 unit rows, d % 64 == 0, 64 <= d <= 4096, min_temperature >= 0.025, rows <= cols, cols + q_cap <= 2^24: an anchor's
+ * count 1 + (cols - 1) + q_cap adds two blocks' counts and has to stay an exact float32 integer.  The query answers 0 elsewhere.
+ * Workspace, in order, each piece rounded up to 256 bytes, Rp / Cp / Qp rounded up to 256, Zp = max(Cp, Qp), + 256 bytes:
+ *   E_X [Rp][Cp] bf16 | E_U [Rp][Qp] bf16 | E_W [Rp][Qp] bf16 | row partials [3][Zp/256][Rp] | column partials [3][Rp/256][Cp] |
+ *   row statistics [3][Rp] | U's [3][Rp] | W's [3][Rp] | 1/Da [Rp] | 1/na [Rp] | 1/Db [Cp] | 1/nb [Cp] | 1/Db and 1/nb at the
+ *   partner [Rp] each | the partner's exponential [Rp] | zeros [Zp] | dT partials [3][32][16][Rp/256] |
+ *   da slabs [splits(Cp) + splits(Qp)][rows][d]      (float32 but E)
+ * Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host (capturable), nothing read
+ * from the workspace before it is written; no float atomics: the same inputs give the same bits.  Checks before any launch: the
+ * sizes of aecf_nce_queue_* (AECF_ERR_BAD_DIMS), then d, min_temperature < 0.025, cols + q_cap > 2^24 or a grad_dtype other than
+ * bf16 / float32 (AECF_ERR_UNSUPPORTED), then NULL pointers (AECF_ERR_NULL_POINTER; upstream and d_temperature may be NULL), then
+ * the workspace size (AECF_ERR_WORKSPACE).
+ *
+ * aecf_key_queue_push_labeled is aecf_key_queue_push with the label ring Ql [q_cap] int64: the label of source row i goes to the
+ * slot its keys go to, read from the cursor the push found (the label copy runs in front of the launch that bumps the state).
+ * src_labels == NULL writes -1 into the slots the push fills, so that no label of an overwritten key stays attached to a new one.
+ * Checks as aecf_key_queue_push, Ql among the pointers. */
+size_t aecf_supcon_queue_workspace_bytes(int64_t rows, int64_t cols, int64_t q_cap, int32_t d);      /* 0: not served */
+int aecf_supcon_queue_pass1(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                            float min_temperature, const void* a_loc, const void* b_loc, const void* Qa, const void* Qb,
+                            int64_t q_cap, const int64_t* q_valid, const void* b_all, const int64_t* row_labels,
+                            const int64_t* col_labels, const int64_t* q_labels, void* workspace, size_t workspace_bytes,
+                            float* col_stats /* [3][cols] */, void* stream);
+int aecf_supcon_queue_loss(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                           float min_temperature, const void* a_loc, const void* b_all, int64_t q_cap,
+                           const float* col_stats /* summed over ranks */, void* workspace, size_t workspace_bytes,
+                           float* loss_rows, void* stream);
+int aecf_supcon_queue_grads(int64_t rows, int64_t cols, int64_t row_offset, int32_t d, const float* temperature,
+                            float min_temperature, float coef, const void* a_loc, const void* b_loc, const void* Qa, const void* Qb,
+                            int64_t q_cap, const int64_t* q_valid, const void* b_all, const int64_t* row_labels,
+                            const int64_t* col_labels, const int64_t* q_labels, void* workspace, size_t workspace_bytes,
+                            const float* upstream, int32_t grad_dtype, void* d_a_loc, void* d_b_loc, void* d_b_all,
+                            float* d_temperature, void* stream);
+int aecf_key_queue_push_labeled(int64_t q_cap, int32_t d, int64_t n, const void* src_a, const void* src_b,
+                                const int64_t* src_labels, void* Qa, void* Qb, int64_t* Ql,
+                                int64_t* state /* device (cursor, valid) */, void* stream);
+
 /* ---- pooled supervised contrastive loss, tile-GEMM form (build-defined; aecf_supcon_pool_fwd_bwd's loss over both anchor halves) ----
  * The supervised contrastive loss of Khosla et al. over ONE pool of the 2 cols rows of both views: every row is an anchor, its
  * keys are the other 2 cols - 1 rows, its positives among them its partner in the other view (by INDEX) and every row of either
