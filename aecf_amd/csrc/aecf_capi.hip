@@ -1717,6 +1717,58 @@ int aecf_adamw_mp_step(int32_t n, void* const* param, const void* const* grad, v
     return launch_status();
 }
 
+int aecf_adamw_mp_ema_step(int32_t n, void* const* param, const void* const* grad, void* const* master, void* const* exp_avg,
+                           void* const* exp_avg_sq, void* const* step, const int64_t* numel, const int32_t* param_dtype,
+                           const int32_t* grad_dtype, void* ticket, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, const float* lr_dev, const float* grad_scale, const float* grad_coef,
+                           const float* found_inf, const float* found_inf2, void* const* ema, void* const* ema_out, float ema_decay,
+                           const float* ema_decay_dev, void* stream) {
+    if (n < 0) return AECF_ERR_BAD_DIMS;
+    if (n == 0) return AECF_OK;
+    if (!numel) return AECF_ERR_NULL_POINTER;
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (numel[i] < 0) return AECF_ERR_BAD_DIMS;
+        total += numel[i];
+    }
+    if (!param_dtype || !grad_dtype) return AECF_ERR_NULL_POINTER;
+    for (int i = 0; i < n; ++i)
+        if (!optim_dtype_ok(param_dtype[i]) || !optim_dtype_ok(grad_dtype[i])) return AECF_ERR_UNSUPPORTED;
+    if (total == 0) return AECF_OK;
+    // master and ema_out may be NULL; so may any entry of ema (that tensor has no average), but not the array
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !step || !ticket || !ema) return AECF_ERR_NULL_POINTER;
+    for (int i = 0; i < n; ++i)
+        if (numel[i] > 0 && (!param[i] || !grad[i] || !exp_avg[i] || !exp_avg_sq[i] || !step[i])) return AECF_ERR_NULL_POINTER;
+    launch_adamw_mp_ema(n, param, grad, (float* const*)master, (float* const*)exp_avg, (float* const*)exp_avg_sq,
+                        (float* const*)step, numel, param_dtype, grad_dtype, (unsigned int*)ticket, lr, beta1, beta2, eps,
+                        weight_decay, lr_dev, grad_scale, grad_coef, found_inf, found_inf2, (float* const*)ema, ema_out, ema_decay,
+                        ema_decay_dev, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_ema_update(int32_t n, const void* const* src, const int32_t* src_dtype, void* const* ema, void* const* ema_out,
+                    const int32_t* out_dtype, const int64_t* numel, float decay, const float* decay_dev, const float* found_inf,
+                    const float* found_inf2, void* stream) {
+    if (n < 0) return AECF_ERR_BAD_DIMS;
+    if (n == 0) return AECF_OK;
+    if (!numel) return AECF_ERR_NULL_POINTER;
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (numel[i] < 0) return AECF_ERR_BAD_DIMS;
+        total += numel[i];
+    }
+    if (!src_dtype || (ema_out && !out_dtype)) return AECF_ERR_NULL_POINTER;
+    for (int i = 0; i < n; ++i)
+        if (!optim_dtype_ok(src_dtype[i]) || (ema_out && !optim_dtype_ok(out_dtype[i]))) return AECF_ERR_UNSUPPORTED;
+    if (total == 0) return AECF_OK;
+    if (!src || !ema) return AECF_ERR_NULL_POINTER;                                    // ema_out, or any entry of it, may be NULL
+    for (int i = 0; i < n; ++i)
+        if (numel[i] > 0 && (!src[i] || !ema[i])) return AECF_ERR_NULL_POINTER;
+    launch_ema_update(n, src, src_dtype, (float* const*)ema, ema_out, out_dtype, numel, decay, decay_dev, found_inf, found_inf2,
+                      (hipStream_t)stream);
+    return launch_status();
+}
+
 size_t aecf_grad_norm_workspace_bytes(int32_t n, const int64_t* numel) {
     if (n <= 0 || !numel) return 0;
     for (int i = 0; i < n; ++i)

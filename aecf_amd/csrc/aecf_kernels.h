@@ -531,6 +531,15 @@ int launch_adamw_mp(int n, void* const* p, const void* const* g, float* const* m
                     float* const* step, const int64_t* numel, const int32_t* pdt, const int32_t* gdt, unsigned int* ticket, float lr,
                     float beta1, float beta2, float eps, float weight_decay, const float* lr_dev, const float* grad_scale,
                     const float* grad_coef, const float* found_inf, const float* found_inf2, hipStream_t s);
+// the same step with the averages' tables (ema[i] NULL: no average; ema_out, or an entry, NULL: none), and the EMA alone
+int launch_adamw_mp_ema(int n, void* const* p, const void* const* g, float* const* master, float* const* m, float* const* v,
+                        float* const* step, const int64_t* numel, const int32_t* pdt, const int32_t* gdt, unsigned int* ticket,
+                        float lr, float beta1, float beta2, float eps, float weight_decay, const float* lr_dev,
+                        const float* grad_scale, const float* grad_coef, const float* found_inf, const float* found_inf2,
+                        float* const* ema, void* const* ema_out, float ema_decay, const float* ema_decay_dev, hipStream_t s);
+int launch_ema_update(int n, const void* const* src, const int32_t* sdt, float* const* ema, void* const* ema_out, const int32_t* odt,
+                      const int64_t* numel, float decay, const float* decay_dev, const float* found_inf, const float* found_inf2,
+                      hipStream_t s);
 int64_t grad_norm_blocks(int n, const int64_t* numel);
 void launch_grad_norm(int n, const void* const* g, const int32_t* gdt, const int64_t* numel, float max_norm, const float* grad_scale,
                       float* partial, float* out, hipStream_t s);

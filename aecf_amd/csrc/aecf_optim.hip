@@ -199,8 +199,18 @@ template <typename T> constexpr bool opt_is_f32 = std::is_same<T, F32>::value;
 template <typename PT, typename GT> constexpr int opt_lane_elems = (opt_is_f32<PT> && opt_is_f32<GT>) ? 4 : 8;
 static int opt_block_elems(int pdt, int gdt) { return (pdt == AECF_F32 && gdt == AECF_F32) ? OPT_BLOCK_ELEMS : 2 * OPT_BLOCK_ELEMS; }
 
-template <typename PT, typename GT>
-__device__ __forceinline__ void adamw_mp_body(const AdamMpArgs& a, int t, float lr, float gmul) {
+// the weight as STORED, in float32: the new master / float32 parameter itself, or the rounded 16-bit parameter widened again
+template <typename PT> __device__ __forceinline__ float opt_stored(float f, bool has_master) {
+    if constexpr (opt_is_f32<PT>) return f;
+    else return has_master ? f : Tr<PT>::to_f32(Tr<PT>::from_f32(f));
+}
+// e' = e + om (w' - e), one rounding of the difference and one of the fused sum (the form tests/ema_cases.py tells from the others)
+__device__ __forceinline__ float ema_next(float om, float w, float e) { return __fmaf_rn(om, __fsub_rn(w, e), e); }
+
+// EMA (compile-time): after the update also e <- ema_next(om, w', e) on the float32 average `e` (NULL: this tensor has none)
+// and, for a 16-bit parameter, eo <- round(e') (NULL: none).  EMA = false is adamw_mp_kernel's body, unchanged.
+template <typename PT, typename GT, bool EMA>
+__device__ __forceinline__ void adamw_mp_body(const AdamMpArgs& a, int t, float lr, float gmul, float* e, void* eo, float om) {
     constexpr int L = opt_lane_elems<PT, GT>;
     // (the expressions of adamw_multi_kernel, in its order)
     const float step = a.step[t][0] + 1.0f;
@@ -221,8 +231,11 @@ __device__ __forceinline__ void adamw_mp_body(const AdamMpArgs& a, int t, float 
         const float denom = sqrtf(vv) / bc2_sqrt + a.eps;
         pp -= step_size * (mm / denom);
     };
-    const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                       reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(w)) & 15) == 0;
+    if constexpr (opt_is_f32<PT>) eo = nullptr;                   // (the caller lets `ema` BE the output tensor)
+    uintptr_t bits = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                     reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(w);
+    if constexpr (EMA) bits |= reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(eo);
+    const bool vec = (bits & 15) == 0;
     if (vec && base + L <= n) {
         float pa[L], ga[L], ma[L], va[L];
         if (w) opt_loadv<F32, L>(w, base, pa);
@@ -236,6 +249,18 @@ __device__ __forceinline__ void adamw_mp_body(const AdamMpArgs& a, int t, float 
         opt_storev<PT, L>(p, base, pa);
         opt_storev<F32, L>(m, base, ma);
         opt_storev<F32, L>(v, base, va);
+        if constexpr (EMA) {
+            if (e) {
+                float ea[L];
+                opt_loadv<F32, L>(e, base, ea);
+#pragma unroll
+                for (int i = 0; i < L; ++i) ea[i] = ema_next(om, opt_stored<PT>(pa[i], w != nullptr), ea[i]);
+                opt_storev<F32, L>(e, base, ea);
+                if constexpr (!opt_is_f32<PT>) {
+                    if (eo) opt_storev<PT, L>(eo, base, ea);
+                }
+            }
+        }
     } else {
         for (int64_t i = base; i < base + L && i < n; ++i) {
             float pp = w ? w[i] : opt_load1<PT>(p, i), mm = m[i], vv = v[i];
@@ -244,8 +269,41 @@ __device__ __forceinline__ void adamw_mp_body(const AdamMpArgs& a, int t, float 
             opt_store1<PT>(p, i, pp);
             m[i] = mm;
             v[i] = vv;
+            if constexpr (EMA) {
+                if (e) {
+                    const float en = ema_next(om, opt_stored<PT>(pp, w != nullptr), e[i]);
+                    e[i] = en;
+                    if constexpr (!opt_is_f32<PT>) {
+                        if (eo) opt_store1<PT>(eo, i, en);
+                    }
+                }
+            }
         }
     }
+}
+
+// the averages' part of a launch (adamw_mp_ema_kernel only): tables beside AdamMpArgs, one decay for the launch
+struct EmaTail {
+    float* ema[OPT_MAX_TENSORS];                      // float32 [numel]; NULL: the tensor has no average
+    void* ema_out[OPT_MAX_TENSORS];                   // the parameter's dtype; NULL: none (ignored beside a float32 parameter)
+    const float* decay_dev;                           // replaces `decay` when set, read at replay time
+    float decay;
+};
+// AdamMpArgs is 1576 bytes of kernel arguments (7 x 192 of tables, 100 + 48 of first_block / dtypes, 4 of padding, 6 x 8 of
+// pointers, 32 of scalars); EmaTail adds 2 x 192 + 8 + 4 (+ 4 of padding) = 400: 1976 of the 4096 a launch may carry
+struct AdamMpEmaArgs {
+    AdamMpArgs a;
+    EmaTail x;
+};
+static_assert(sizeof(AdamMpArgs) == 1576 && sizeof(AdamMpEmaArgs) == 1976, "the byte counts of the comment above");
+
+// 1 - beta of an EMA launch, block-uniform: beta clamped to [0, 1] by selects (a NaN passes both and comes out NaN: the
+// caller then skips the averages, and only them)
+__device__ __forceinline__ float ema_one_minus(const float* decay_dev, float decay) {
+    float b = decay_dev ? decay_dev[0] : decay;
+    b = b < 0.0f ? 0.0f : b;
+    b = b > 1.0f ? 1.0f : b;
+    return __fsub_rn(1.0f, b);
 }
 
 __global__ __launch_bounds__(256) void adamw_mp_kernel(AdamMpArgs a) {
@@ -257,15 +315,15 @@ __global__ __launch_bounds__(256) void adamw_mp_kernel(AdamMpArgs a) {
     float gmul = a.grad_scale ? __fdiv_rn(1.0f, a.grad_scale[0]) : 1.0f;
     if (a.grad_coef) gmul *= a.grad_coef[0];
     switch (a.pdt[t] * 3 + a.gdt[t]) {                // aecf_dtype: AECF_BF16 = 0, AECF_F32 = 1, AECF_F16 = 2
-        case 0: adamw_mp_body<BF16, BF16>(a, t, lr, gmul); break;
-        case 1: adamw_mp_body<BF16, F32>(a, t, lr, gmul); break;
-        case 2: adamw_mp_body<BF16, F16>(a, t, lr, gmul); break;
-        case 3: adamw_mp_body<F32, BF16>(a, t, lr, gmul); break;
-        case 4: adamw_mp_body<F32, F32>(a, t, lr, gmul); break;
-        case 5: adamw_mp_body<F32, F16>(a, t, lr, gmul); break;
-        case 6: adamw_mp_body<F16, BF16>(a, t, lr, gmul); break;
-        case 7: adamw_mp_body<F16, F32>(a, t, lr, gmul); break;
-        default: adamw_mp_body<F16, F16>(a, t, lr, gmul); break;
+        case 0: adamw_mp_body<BF16, BF16, false>(a, t, lr, gmul, nullptr, nullptr, 0.0f); break;
+        case 1: adamw_mp_body<BF16, F32, false>(a, t, lr, gmul, nullptr, nullptr, 0.0f); break;
+        case 2: adamw_mp_body<BF16, F16, false>(a, t, lr, gmul, nullptr, nullptr, 0.0f); break;
+        case 3: adamw_mp_body<F32, BF16, false>(a, t, lr, gmul, nullptr, nullptr, 0.0f); break;
+        case 4: adamw_mp_body<F32, F32, false>(a, t, lr, gmul, nullptr, nullptr, 0.0f); break;
+        case 5: adamw_mp_body<F32, F16, false>(a, t, lr, gmul, nullptr, nullptr, 0.0f); break;
+        case 6: adamw_mp_body<F16, BF16, false>(a, t, lr, gmul, nullptr, nullptr, 0.0f); break;
+        case 7: adamw_mp_body<F16, F32, false>(a, t, lr, gmul, nullptr, nullptr, 0.0f); break;
+        default: adamw_mp_body<F16, F16, false>(a, t, lr, gmul, nullptr, nullptr, 0.0f); break;
     }
     // the two-level ticket of adamw_multi_kernel, and no fence for the reason given there
     __shared__ int is_last;
@@ -286,6 +344,122 @@ __global__ __launch_bounds__(256) void adamw_mp_kernel(AdamMpArgs a) {
     }
     __syncthreads();
     if (is_last && (int)threadIdx.x < a.n) a.step[threadIdx.x][0] += 1.0f;
+}
+
+// ---- AdamW + exponential moving average of the weights in the same pass (aecf_adamw_mp_ema_step) ----
+// adamw_mp_kernel with its body's EMA flag set: the lane that holds the new float32 weight also reads and writes its average,
+// two more 16-byte accesses per float32 vector (one more store for a 16-bit ema_out).  A set found_inf / found_inf2 returns
+// before anything is written, the averages included.
+__global__ __launch_bounds__(256) void adamw_mp_ema_kernel(AdamMpEmaArgs k) {
+    const AdamMpArgs& a = k.a;
+    // block-uniform, read by every block and written by none of this launch
+    if ((a.found_inf && a.found_inf[0] != 0.0f) || (a.found_inf2 && a.found_inf2[0] != 0.0f)) return;
+    int t = 0;
+    while (t + 1 < a.n && blockIdx.x >= a.first_block[t + 1]) ++t;
+    const float lr = a.lr_dev ? a.lr_dev[0] : a.lr;
+    float gmul = a.grad_scale ? __fdiv_rn(1.0f, a.grad_scale[0]) : 1.0f;
+    if (a.grad_coef) gmul *= a.grad_coef[0];
+    float* e = nullptr;
+    void* eo = nullptr;
+    const float om = ema_one_minus(k.x.decay_dev, k.x.decay);
+    if (om == om) {
+        e = k.x.ema[t];
+        eo = k.x.ema_out[t];
+    }
+    switch (a.pdt[t] * 3 + a.gdt[t]) {                // aecf_dtype: AECF_BF16 = 0, AECF_F32 = 1, AECF_F16 = 2
+        case 0: adamw_mp_body<BF16, BF16, true>(a, t, lr, gmul, e, eo, om); break;
+        case 1: adamw_mp_body<BF16, F32, true>(a, t, lr, gmul, e, eo, om); break;
+        case 2: adamw_mp_body<BF16, F16, true>(a, t, lr, gmul, e, eo, om); break;
+        case 3: adamw_mp_body<F32, BF16, true>(a, t, lr, gmul, e, eo, om); break;
+        case 4: adamw_mp_body<F32, F32, true>(a, t, lr, gmul, e, eo, om); break;
+        case 5: adamw_mp_body<F32, F16, true>(a, t, lr, gmul, e, eo, om); break;
+        case 6: adamw_mp_body<F16, BF16, true>(a, t, lr, gmul, e, eo, om); break;
+        case 7: adamw_mp_body<F16, F32, true>(a, t, lr, gmul, e, eo, om); break;
+        default: adamw_mp_body<F16, F16, true>(a, t, lr, gmul, e, eo, om); break;
+    }
+    // (the ticket of adamw_mp_kernel)
+    __shared__ int is_last;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int last = 0;
+        const unsigned int sub = blockIdx.x % OPT_SUBTICKETS;
+        const unsigned int expect = (gridDim.x - sub + OPT_SUBTICKETS - 1) / OPT_SUBTICKETS;
+        if (atomicAdd(a.ticket + 1 + sub, 1u) == expect - 1) {
+            a.ticket[1 + sub] = 0u;
+            const unsigned int nsub = gridDim.x < OPT_SUBTICKETS ? gridDim.x : OPT_SUBTICKETS;
+            if (atomicAdd(a.ticket, 1u) == nsub - 1) {
+                a.ticket[0] = 0u;
+                last = 1;
+            }
+        }
+        is_last = last;
+    }
+    __syncthreads();
+    if (is_last && (int)threadIdx.x < a.n) a.step[threadIdx.x][0] += 1.0f;
+}
+
+// ---- the same EMA without an optimiser step (aecf_ema_update): tensors that had no gradient, callers on another optimiser ----
+// w' = float32(src); a lane takes 4 elements where source and output are float32 and 8 where either is 16-bit.  No tickets:
+// nothing is counted.
+struct EmaArgs {
+    const void* src[OPT_MAX_TENSORS];
+    float* ema[OPT_MAX_TENSORS];
+    void* ema_out[OPT_MAX_TENSORS];                   // NULL: none
+    int64_t numel[OPT_MAX_TENSORS];
+    unsigned int first_block[OPT_MAX_TENSORS + 1];
+    unsigned char sdt[OPT_MAX_TENSORS], odt[OPT_MAX_TENSORS];          // aecf_dtype; odt is AECF_F32 where there is no ema_out
+    const float *decay_dev, *found_inf, *found_inf2;
+    int n;
+    float decay;
+};
+
+template <typename ST, typename OT>
+__device__ __forceinline__ void ema_body(const EmaArgs& a, int t, float om) {
+    constexpr int L = opt_lane_elems<ST, OT>;
+    const int64_t base = ((int64_t)(blockIdx.x - a.first_block[t]) * 256 + threadIdx.x) * L;
+    const int64_t n = a.numel[t];
+    const void* src = a.src[t];
+    float* e = a.ema[t];
+    void* eo = opt_is_f32<OT> ? nullptr : a.ema_out[t];
+    const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(eo)) & 15) == 0;
+    if (vec && base + L <= n) {
+        float wa[L], ea[L];
+        opt_loadv<ST, L>(src, base, wa);
+        opt_loadv<F32, L>(e, base, ea);
+#pragma unroll
+        for (int i = 0; i < L; ++i) ea[i] = ema_next(om, wa[i], ea[i]);
+        opt_storev<F32, L>(e, base, ea);
+        if constexpr (!opt_is_f32<OT>) {
+            if (eo) opt_storev<OT, L>(eo, base, ea);
+        }
+    } else {
+        for (int64_t i = base; i < base + L && i < n; ++i) {
+            const float en = ema_next(om, opt_load1<ST>(src, i), e[i]);
+            e[i] = en;
+            if constexpr (!opt_is_f32<OT>) {
+                if (eo) opt_store1<OT>(eo, i, en);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ema_update_kernel(EmaArgs a) {
+    if ((a.found_inf && a.found_inf[0] != 0.0f) || (a.found_inf2 && a.found_inf2[0] != 0.0f)) return;
+    const float om = ema_one_minus(a.decay_dev, a.decay);
+    if (!(om == om)) return;
+    int t = 0;
+    while (t + 1 < a.n && blockIdx.x >= a.first_block[t + 1]) ++t;
+    switch (a.sdt[t] * 3 + a.odt[t]) {
+        case 0: ema_body<BF16, BF16>(a, t, om); break;
+        case 1: ema_body<BF16, F32>(a, t, om); break;
+        case 2: ema_body<BF16, F16>(a, t, om); break;
+        case 3: ema_body<F32, BF16>(a, t, om); break;
+        case 4: ema_body<F32, F32>(a, t, om); break;
+        case 5: ema_body<F32, F16>(a, t, om); break;
+        case 6: ema_body<F16, BF16>(a, t, om); break;
+        case 7: ema_body<F16, F32>(a, t, om); break;
+        default: ema_body<F16, F16>(a, t, om); break;
+    }
 }
 
 // ---- global L2 norm of gradients of mixed dtype (torch.nn.utils.clip_grad_norm_'s norm; torch.amp.GradScaler's inf check) ----
@@ -364,13 +538,17 @@ __global__ __launch_bounds__(256) void grad_sumsq_finalize_kernel(const float* _
 
 }  // namespace
 
-// tensors with numel > 0 in groups of OPT_MAX_TENSORS; ticket as for launch_adamw_multi.  Returns the number of launches
-int launch_adamw_mp(int n, void* const* p, const void* const* g, float* const* master, float* const* m, float* const* v,
-                    float* const* step, const int64_t* numel, const int32_t* pdt, const int32_t* gdt, unsigned int* ticket, float lr,
-                    float beta1, float beta2, float eps, float weight_decay, const float* lr_dev, const float* grad_scale,
-                    const float* grad_coef, const float* found_inf, const float* found_inf2, hipStream_t s) {
+// tensors with numel > 0 in groups of OPT_MAX_TENSORS; ticket as for launch_adamw_multi.  Returns the number of launches.
+// with_ema: adamw_mp_ema_kernel with the averages' tables beside the same arguments (ema required then, ema_out may be NULL)
+static int launch_adamw_mp_any(bool with_ema, int n, void* const* p, const void* const* g, float* const* master, float* const* m,
+                               float* const* v, float* const* step, const int64_t* numel, const int32_t* pdt, const int32_t* gdt,
+                               unsigned int* ticket, float lr, float beta1, float beta2, float eps, float weight_decay,
+                               const float* lr_dev, const float* grad_scale, const float* grad_coef, const float* found_inf,
+                               const float* found_inf2, float* const* ema, void* const* ema_out, float ema_decay,
+                               const float* ema_decay_dev, hipStream_t s) {
     int launches = 0;
-    AdamMpArgs a;
+    AdamMpEmaArgs k;
+    AdamMpArgs& a = k.a;
     a.n = 0;
     unsigned int blocks = 0;
     auto flush = [&]() {
@@ -381,19 +559,79 @@ int launch_adamw_mp(int n, void* const* p, const void* const* g, float* const* m
         a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
         a.log_beta1 = (float)log((double)beta1);
         a.log_beta2 = (float)log((double)beta2);
-        adamw_mp_kernel<<<dim3(blocks), dim3(256), 0, s>>>(a);
+        if (with_ema) {
+            k.x.decay = ema_decay; k.x.decay_dev = ema_decay_dev;
+            adamw_mp_ema_kernel<<<dim3(blocks), dim3(256), 0, s>>>(k);
+        } else {
+            adamw_mp_kernel<<<dim3(blocks), dim3(256), 0, s>>>(a);
+        }
         ++launches;
         a.n = 0;
         blocks = 0;
     };
     for (int i = 0; i < n; ++i) {
         if (numel[i] == 0) continue;
-        const int k = a.n++;
-        a.p[k] = p[i]; a.g[k] = g[i]; a.master[k] = master ? master[i] : nullptr; a.m[k] = m[i]; a.v[k] = v[i]; a.step[k] = step[i];
-        a.numel[k] = numel[i];
-        a.pdt[k] = (unsigned char)pdt[i]; a.gdt[k] = (unsigned char)gdt[i];
-        a.first_block[k] = blocks;
+        const int j = a.n++;
+        a.p[j] = p[i]; a.g[j] = g[i]; a.master[j] = master ? master[i] : nullptr; a.m[j] = m[i]; a.v[j] = v[i]; a.step[j] = step[i];
+        a.numel[j] = numel[i];
+        a.pdt[j] = (unsigned char)pdt[i]; a.gdt[j] = (unsigned char)gdt[i];
+        a.first_block[j] = blocks;
+        if (with_ema) {
+            k.x.ema[j] = ema[i];
+            k.x.ema_out[j] = ema_out ? ema_out[i] : nullptr;
+        }
         const int be = opt_block_elems(pdt[i], gdt[i]);
+        blocks += (unsigned int)((numel[i] + be - 1) / be);
+        if (a.n == OPT_MAX_TENSORS) flush();
+    }
+    flush();
+    return launches;
+}
+
+int launch_adamw_mp(int n, void* const* p, const void* const* g, float* const* master, float* const* m, float* const* v,
+                    float* const* step, const int64_t* numel, const int32_t* pdt, const int32_t* gdt, unsigned int* ticket, float lr,
+                    float beta1, float beta2, float eps, float weight_decay, const float* lr_dev, const float* grad_scale,
+                    const float* grad_coef, const float* found_inf, const float* found_inf2, hipStream_t s) {
+    return launch_adamw_mp_any(false, n, p, g, master, m, v, step, numel, pdt, gdt, ticket, lr, beta1, beta2, eps, weight_decay,
+                               lr_dev, grad_scale, grad_coef, found_inf, found_inf2, nullptr, nullptr, 0.0f, nullptr, s);
+}
+
+int launch_adamw_mp_ema(int n, void* const* p, const void* const* g, float* const* master, float* const* m, float* const* v,
+                        float* const* step, const int64_t* numel, const int32_t* pdt, const int32_t* gdt, unsigned int* ticket,
+                        float lr, float beta1, float beta2, float eps, float weight_decay, const float* lr_dev,
+                        const float* grad_scale, const float* grad_coef, const float* found_inf, const float* found_inf2,
+                        float* const* ema, void* const* ema_out, float ema_decay, const float* ema_decay_dev, hipStream_t s) {
+    return launch_adamw_mp_any(true, n, p, g, master, m, v, step, numel, pdt, gdt, ticket, lr, beta1, beta2, eps, weight_decay,
+                               lr_dev, grad_scale, grad_coef, found_inf, found_inf2, ema, ema_out, ema_decay, ema_decay_dev, s);
+}
+
+// tensors with numel > 0 in groups of OPT_MAX_TENSORS, one launch each.  Returns the number of launches
+int launch_ema_update(int n, const void* const* src, const int32_t* sdt, float* const* ema, void* const* ema_out, const int32_t* odt,
+                      const int64_t* numel, float decay, const float* decay_dev, const float* found_inf, const float* found_inf2,
+                      hipStream_t s) {
+    int launches = 0;
+    EmaArgs a;
+    a.n = 0;
+    unsigned int blocks = 0;
+    auto flush = [&]() {
+        if (a.n == 0) return;
+        a.first_block[a.n] = blocks;
+        a.decay = decay; a.decay_dev = decay_dev; a.found_inf = found_inf; a.found_inf2 = found_inf2;
+        ema_update_kernel<<<dim3(blocks), dim3(256), 0, s>>>(a);
+        ++launches;
+        a.n = 0;
+        blocks = 0;
+    };
+    for (int i = 0; i < n; ++i) {
+        if (numel[i] == 0) continue;
+        const int j = a.n++;
+        void* out = ema_out ? ema_out[i] : nullptr;
+        const int od = (out && odt) ? odt[i] : AECF_F32;
+        a.src[j] = src[i]; a.ema[j] = ema[i]; a.ema_out[j] = od == AECF_F32 ? nullptr : out;
+        a.numel[j] = numel[i];
+        a.sdt[j] = (unsigned char)sdt[i]; a.odt[j] = (unsigned char)od;
+        a.first_block[j] = blocks;
+        const int be = opt_block_elems(sdt[i], od);
         blocks += (unsigned int)((numel[i] + be - 1) / be);
         if (a.n == OPT_MAX_TENSORS) flush();
     }

@@ -15,9 +15,16 @@ Under capture the Python-number hyper-parameters are kernel ARGUMENTS: a capture
 with.  A learning-rate schedule therefore passes ``lr`` as a one-element float32 tensor on the parameters' device (as torch's
 fused AdamW allows): the kernel reads it at replay time, so ``lr.fill_(...)`` between replays is followed.  A replay moves no
 version counter: ``xray.GraphedTrainStep`` tells the pools of its model after each one; after replays of a graph of your own,
-call ``invalidate_cast_cache()`` on the pools before inference."""
+call ``invalidate_cast_cache()`` on the pools before inference.
+
+``FusedAdamW(ema_decay=...)`` keeps an exponential moving average of the weights, ``e <- e + (1 - decay) (w - e)``, in the
+step's own launch (``aecf_adamw_mp_ema_step``; ``aecf_ema_update`` for the parameters that had no gradient): the momentum key
+encoder of MoCo beside ``losses.KeyQueue``, and the averaged weights people evaluate and ship.  ``EmaModel`` is a copy of the
+model whose parameters ARE those averages; ``FusedAdamW.ema_weights()`` puts them into the live model for a ``with`` block."""
 from __future__ import annotations
 
+import contextlib
+import copy
 import ctypes
 from itertools import chain
 from typing import Iterable
@@ -28,7 +35,7 @@ from . import _lib
 from .layer import _stream
 
 _DTYPES = {torch.bfloat16: _lib.AECF_BF16, torch.float32: _lib.AECF_F32, torch.float16: _lib.AECF_F16}
-_F32_STATE = ("master", "exp_avg", "exp_avg_sq")
+_F32_STATE = ("master", "exp_avg", "exp_avg_sq", "ema")
 
 
 def _ptr_array(tensors):
@@ -89,12 +96,18 @@ class FusedAdamW(torch.optim.Optimizer):
     ``skipped_steps`` (None until the first clipped step) goes up by one.
     ``torch.amp.GradScaler``: ``scaler.step(opt)`` hands over its scale and its found-inf flag as device tensors; the kernel
     unscales and skips by them, with no ``.item()``.  With clipping on, the scaler's flag and the norm's are two pointer
-    arguments of the same launch (OR-ed by the kernel)."""
+    arguments of the same launch (OR-ed by the kernel).
+    ``ema_decay``: None (no average: the calls and bits of an optimiser without the argument), a number in [0, 1], or a
+    one-element float32 tensor on the parameters' device that the kernel reads at replay time (a schedule -- a warm-up, say --
+    is written into that tensor; there is no built-in rule).  ``state[p]["ema"]`` is a float32 average of the weight as STORED
+    (the master where there is one), created from it at the parameter's first step and moved by every step that is not
+    skipped on the device -- for the parameters without a gradient in that step too -- and by none that is.  One decay for
+    the whole optimiser; under data parallel every rank keeps the same averages (replicated, not sharded)."""
 
     _step_supports_amp_scaling = True
 
     def __init__(self, params: Iterable, lr=1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, *,
-                 master_weights: bool = False, max_grad_norm=None):
+                 master_weights: bool = False, max_grad_norm=None, ema_decay=None):
         if torch.is_tensor(lr):
             if lr.numel() != 1 or lr.dtype != torch.float32:
                 raise ValueError("FusedAdamW: a tensor lr is ONE float32 element (on the parameters' device)")
@@ -104,7 +117,18 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError("FusedAdamW: invalid hyper-parameter")
         if max_grad_norm is not None and not float(max_grad_norm) > 0:
             raise ValueError("FusedAdamW: max_grad_norm must be positive (None: no clipping)")
+        if torch.is_tensor(ema_decay):
+            if ema_decay.numel() != 1 or ema_decay.dtype != torch.float32:
+                raise ValueError("FusedAdamW: a tensor ema_decay is ONE float32 element (on the parameters' device)")
+        elif ema_decay is not None:
+            if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= float(ema_decay) <= 1.0:
+                raise ValueError("FusedAdamW: ema_decay is None, a number in [0, 1] or a one-element float32 tensor")
+            ema_decay = float(ema_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.ema_decay = ema_decay
+        self._ema_out = {}                # 16-bit parameter -> the tensor of its dtype an EmaModel reads (ema.to(dtype))
+        self._ema_held = {}               # parameter -> the float32 average an EmaModel is bound to: never replaced, only written
+        self._ema_models = []
         self.master_weights = bool(master_weights)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.last_grad_norm = self.last_clip_coef = None
@@ -145,6 +169,63 @@ class FusedAdamW(torch.optim.Optimizer):
         _launch_grad_norm(grads, self.max_grad_norm, grad_scale, workspace, self._norm_out)
         self.skipped_steps.add_(self._norm_out[2])                 # (bookkeeping on the device; the skip itself is the kernel's)
 
+    def _ema_state(self, p, st):
+        """``st["ema"]`` of parameter ``p``, created from the stored weight (the master, or the widened parameter) if missing."""
+        ema = st.get("ema")
+        held = self._ema_held.get(p)
+        if ema is None:
+            src = st.get("master") if p.dtype != torch.float32 else None
+            src = p.detach() if src is None else src
+            if held is None:
+                ema = src.to(torch.float32, memory_format=torch.contiguous_format, copy=True)
+            else:
+                ema = held.copy_(src)
+            st["ema"] = ema
+            if p in self._ema_out:
+                self._ema_out[p].copy_(ema)
+        elif ema.device != p.device or ema.dtype != torch.float32 or not ema.is_contiguous():
+            ema = st["ema"] = ema.to(device=p.device, dtype=torch.float32).contiguous()
+        return ema
+
+    def _bind_ema(self, p, q):
+        """``q`` -- the parameter of an EmaModel's copy that pairs with ``p`` -- becomes the average's output: a float32 ``q``
+        IS ``state[p]["ema"]`` from here on (same storage, same version counter), a 16-bit one is written beside it."""
+        if p in self._ema_held:
+            raise RuntimeError("FusedAdamW: one EmaModel per optimiser")
+        if not q.is_contiguous() or q.shape != p.shape or q.dtype != p.dtype or q.device != p.device:
+            raise RuntimeError("EmaModel: a copy's parameter must match its original (contiguous, same shape, dtype and device)")
+        st = self.state[p]
+        with torch.no_grad():
+            ema = self._ema_state(p, st)
+            q.copy_(ema)
+            if p.dtype == torch.float32:
+                ema = st["ema"] = q.detach()
+            else:
+                self._ema_out[p] = q
+            self._ema_held[p] = ema
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate the SAME module on the averaged weights: every parameter that has an average is overwritten from it (cast to
+        the parameter's dtype) on entry and restored bit for bit on exit, both by ``copy_`` (version counters move, so the pools'
+        inference caches follow).  Masters are not touched.  Not for use under capture."""
+        if self.ema_decay is None:
+            raise RuntimeError("FusedAdamW.ema_weights: the optimiser was built without ema_decay")
+        saved = []
+        with torch.no_grad():
+            for group in self.param_groups:
+                for p in group["params"]:
+                    ema = self.state.get(p, {}).get("ema")
+                    if ema is not None:
+                        saved.append((p, p.detach().clone()))
+                        p.copy_(ema)
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                for p, keep in saved:
+                    p.copy_(keep)
+
     def load_state_dict(self, state_dict):
         """``Optimizer.load_state_dict`` casts floating-point state to the parameter's dtype, which would round the float32
         masters and moments of a bf16 / f16 parameter: the float32 tensors of the incoming state are put back afterwards, on
@@ -161,6 +242,17 @@ class FusedAdamW(torch.optim.Optimizer):
                 value = src.get(key)
                 if torch.is_tensor(value) and value.dtype == torch.float32:
                     self.state[p][key] = value.detach().to(device=p.device, copy=True)
+        # an average an EmaModel is bound to keeps its tensor: the loaded values are written INTO it (a loaded state without
+        # "ema" gets one from the weights at the next step, in the same tensor)
+        for p, held in self._ema_held.items():
+            st = self.state[p]
+            value = st.get("ema")
+            if torch.is_tensor(value) and value is not held:
+                with torch.no_grad():
+                    held.copy_(value)
+                    if p in self._ema_out:
+                        self._ema_out[p].copy_(held)
+                st["ema"] = held
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -194,7 +286,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 if not p.is_contiguous():
                     raise RuntimeError("FusedAdamW: parameters must be contiguous")
                 st = self.state[p]
-                if len(st) == 0:
+                if "step" not in st and "exp_avg" not in st:             # (an average alone may be there already)
                     st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
                     st["exp_avg"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
@@ -214,13 +306,22 @@ class FusedAdamW(torch.optim.Optimizer):
                             st["master"] = p.detach().to(torch.float32, memory_format=torch.contiguous_format)
                     elif master.device != p.device or master.dtype != torch.float32 or not master.is_contiguous():
                         st["master"] = master.to(device=p.device, dtype=torch.float32).contiguous()
+                if self.ema_decay is not None:
+                    self._ema_state(p, st)
             grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
             work.append((gi, group, ps, grads))
         if not work:
+            if self.ema_decay is not None:
+                self._ema_rest(lib, found_inf, None)
             return loss
         clip = self.max_grad_norm is not None
         if clip:
             self._clip([g for _, _, _, grads in work for g in grads], grad_scale)
+        ema_dev = None
+        if torch.is_tensor(self.ema_decay):
+            ema_dev = self.ema_decay
+            if ema_dev.numel() != 1 or ema_dev.dtype != torch.float32 or ema_dev.device != work[0][2][0].device:
+                raise RuntimeError("FusedAdamW: a tensor ema_decay is ONE float32 element on the parameters' device")
         for gi, group, ps, grads in work:
             dev = ps[0].device
             lr = group["lr"]
@@ -230,7 +331,7 @@ class FusedAdamW(torch.optim.Optimizer):
             ticket = self._ticket(dev, gi, len(ps)).data_ptr()
             plain = (not clip and grad_scale is None and found_inf is None and not torch.is_tensor(lr)
                      and all(p.dtype == torch.float32 and g.dtype == torch.float32 for p, g in zip(ps, grads)))
-            if plain:
+            if plain and self.ema_decay is None:
                 _lib.check(lib.aecf_adamw_step(
                     len(ps), _ptr_array(ps), _ptr_array(grads), _ptr_array([st["exp_avg"] for st in states]),
                     _ptr_array([st["exp_avg_sq"] for st in states]), _ptr_array([st["step"] for st in states]),
@@ -246,7 +347,14 @@ class FusedAdamW(torch.optim.Optimizer):
                     if t is not None and t.device != dev:
                         raise RuntimeError("FusedAdamW: the GradScaler's tensors and the parameters must share a device")
                 i32 = ctypes.c_int32 * len(ps)
-                _lib.check(lib.aecf_adamw_mp_step(
+                if ema_dev is not None and ema_dev.device != dev:
+                    raise RuntimeError("FusedAdamW: a tensor ema_decay is ONE float32 element on the parameters' device")
+                tail, entry, name = (), lib.aecf_adamw_mp_step, "aecf_adamw_mp_step"
+                if self.ema_decay is not None:
+                    tail = (_ptr_array([st["ema"] for st in states]), _ptr_array([self._ema_out.get(p) for p in ps]),
+                            0.0 if ema_dev is not None else self.ema_decay, None if ema_dev is None else ema_dev.data_ptr())
+                    entry, name = lib.aecf_adamw_mp_ema_step, "aecf_adamw_mp_ema_step"
+                _lib.check(entry(
                     len(ps), _ptr_array(ps), _ptr_array(grads), _ptr_array([st.get("master") for st in states]),
                     _ptr_array([st["exp_avg"] for st in states]), _ptr_array([st["exp_avg_sq"] for st in states]),
                     _ptr_array([st["step"] for st in states]), numel, i32(*[_DTYPES[p.dtype] for p in ps]),
@@ -255,8 +363,93 @@ class FusedAdamW(torch.optim.Optimizer):
                     None if grad_scale is None else grad_scale.data_ptr(),
                     self._norm_out[1:].data_ptr() if clip else None,
                     None if found_inf is None else found_inf.data_ptr(),
-                    self._norm_out[2:].data_ptr() if clip else None, _stream()), "aecf_adamw_mp_step")
+                    self._norm_out[2:].data_ptr() if clip else None, *tail, _stream()), name)
             # the launch wrote the parameters through raw pointers: move their version counters the way an in-place torch op
             # would, so that whatever keys on them (the pool's inference caches, autograd's saved-tensor checks) sees the update
             torch.autograd.graph.increment_version(ps)
+            if self.ema_decay is not None:
+                self._ema_written(ps)
+        if self.ema_decay is not None:
+            self._ema_rest(lib, found_inf, self._norm_out[2:] if clip else None)
         return loss
+
+    def _ema_written(self, ps):
+        """Version counters of the output tensors an EmaModel reads, as for the parameters."""
+        outs = [self._ema_out[p] if p in self._ema_out else self._ema_held[p] for p in ps if p in self._ema_held]
+        if outs:
+            torch.autograd.graph.increment_version(outs)
+
+    def _ema_rest(self, lib, found_inf, found_inf2):
+        """The averages of the parameters WITHOUT a gradient in this step: one ``aecf_ema_update`` (per device) under the same
+        skip flags, so that every average moves on every step that is not skipped, and on none that is."""
+        rest = {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None and p.numel() > 0 and p.device.type == "cuda" and p.dtype in _DTYPES and p.is_contiguous():
+                    rest.setdefault(p.device, []).append(p)
+        for dev, ps in rest.items():
+            ema_dev = self.ema_decay if torch.is_tensor(self.ema_decay) else None
+            for t in (ema_dev, found_inf, found_inf2):
+                if t is not None and t.device != dev:
+                    raise RuntimeError("FusedAdamW: ema_decay and the skip flags must live on the parameters' device")
+            emas = [self._ema_state(p, self.state[p]) for p in ps]
+            # the weight as stored: the float32 master of a 16-bit parameter where there is one
+            srcs = [self.state[p].get("master") if p.dtype != torch.float32 else None for p in ps]
+            srcs = [p if s is None else s for p, s in zip(ps, srcs)]
+            i32 = ctypes.c_int32 * len(ps)
+            with torch.cuda.device(dev):
+                _lib.check(lib.aecf_ema_update(
+                    len(ps), _ptr_array(srcs), i32(*[_DTYPES[s.dtype] for s in srcs]), _ptr_array(emas),
+                    _ptr_array([self._ema_out.get(p) for p in ps]), i32(*[_DTYPES[p.dtype] for p in ps]),
+                    (ctypes.c_int64 * len(ps))(*[p.numel() for p in ps]), 0.0 if ema_dev is not None else self.ema_decay,
+                    None if ema_dev is None else ema_dev.data_ptr(), None if found_inf is None else found_inf.data_ptr(),
+                    None if found_inf2 is None else found_inf2.data_ptr(), _stream()), "aecf_ema_update")
+            self._ema_written(ps)
+
+
+class EmaModel:
+    """A copy of ``model`` whose parameters are the moving averages ``optimizer`` (a ``FusedAdamW(ema_decay=...)``) keeps: the
+    momentum key encoder of MoCo (``k = ema.module(x)`` under ``no_grad``), the model to validate and ship.
+
+    ``module``: ``copy.deepcopy(model)`` with ``requires_grad_(False)``.  Parameters pair by name.  A float32 parameter of the
+    copy IS that parameter's ``state["ema"]`` (no second buffer); a 16-bit one is written by the step as ``ema.to(dtype)``
+    beside the float32 ``state["ema"]``.  Parameters the optimiser does not hold, and all buffers, are copied from the model
+    by ``sync()`` (buffers are copied, not averaged).  Build it once the model is on its device and BEFORE a step is captured
+    (the graph holds the addresses); after replays of a graph of your own call ``after_replay()``, as ``invalidate_cast_cache()``
+    is called on the model's pools (``xray.GraphedTrainStep`` does both)."""
+
+    def __init__(self, model: torch.nn.Module, optimizer: FusedAdamW):
+        if getattr(optimizer, "ema_decay", None) is None:
+            raise ValueError("EmaModel: the optimiser keeps no average (FusedAdamW(..., ema_decay=...))")
+        params = dict(model.named_parameters())
+        if len({p.device for p in params.values()}) > 1:
+            raise ValueError("EmaModel: the parameters of the model live on several devices")
+        self.model, self.optimizer = model, optimizer
+        self.module = copy.deepcopy(model).requires_grad_(False)
+        held = {id(p) for group in optimizer.param_groups for p in group["params"]}
+        copies = dict(self.module.named_parameters())
+        self._unheld = []
+        for name, p in params.items():
+            if id(p) in held and p.numel() > 0 and p.dtype in _DTYPES:
+                optimizer._bind_ema(p, copies[name])
+            else:
+                self._unheld.append((p, copies[name]))
+        self._pools = tuple(m for m in self.module.modules() if hasattr(m, "invalidate_cast_cache"))
+        optimizer._ema_models.append(self)
+        self.sync()
+
+    @torch.no_grad()
+    def sync(self):
+        """Copy what the optimiser does not average: the parameters it does not hold, and all buffers."""
+        for p, q in self._unheld:
+            q.copy_(p)
+        for src, dst in zip(self.model.buffers(), self.module.buffers()):
+            dst.copy_(src)
+
+    def after_replay(self):
+        """A graph replay moves no version counter: the copy's pools forget what inference derived from the old averages."""
+        for pool in self._pools:
+            pool.invalidate_cast_cache()
+
+    def __call__(self, *args, **kwargs):
+        return self.module(*args, **kwargs)

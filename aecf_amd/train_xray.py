@@ -6,6 +6,7 @@ of ``train_both_models`` / ``main`` in ``xrays/train_xrays_example.py:312-427, 7
     python -m aecf_amd.train_xray --epochs 60 --switch-epoch 40                     # one GPU
     python -m torch.distributed.run --nproc-per-node 4 --master-addr 127.0.0.1 -m aecf_amd.train_xray   # DP x 4
     python -m aecf_amd.train_xray --param-dtype bfloat16 --max-grad-norm 1.0        # bf16 model, float32 masters, clipping
+    python -m aecf_amd.train_xray --ema-decay 0.999                                 # + validation of the averaged weights
 
 The reference trains on precomputed CLIP features of a chest X-ray set that is not part of its repository
 (``.MISSING_LARGE_BLOBS``); ``--data train.pt,val.pt`` loads such files (dicts with image / text / labels), otherwise a
@@ -24,7 +25,7 @@ import torch
 import torch.distributed as dist
 
 from . import dp
-from .optim import FusedAdamW
+from .optim import EmaModel, FusedAdamW
 from .xray import AECFModel
 
 
@@ -86,6 +87,8 @@ def main(argv=None):
     ap.add_argument("--param-dtype", choices=("float32", "bfloat16"), default="float32",
                     help="bfloat16: the model and its inputs in bf16, FusedAdamW keeps float32 master weights and moments")
     ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm inside the optimiser step")
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="keep an exponential moving average of the weights inside the optimiser step and validate it too")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -121,7 +124,8 @@ def main(argv=None):
     dp.broadcast_parameters(params + list(model.buffers()))
     bucket = dp.FlatGradBucket(params) if world > 1 else None
     opt = FusedAdamW(params, lr=args.lr, weight_decay=0.01,                 # ref :322-323 (torch.optim.AdamW's update, one launch)
-                     master_weights=low, max_grad_norm=args.max_grad_norm)
+                     master_weights=low, max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay)
+    ema = EmaModel(model, opt) if args.ema_decay is not None else None      # (every rank keeps the same averages)
     crit = torch.nn.BCEWithLogitsLoss()
     n = image.shape[0]
     steps = (n + args.batch - 1) // args.batch                              # the short last batch is kept (DataLoader default)
@@ -174,6 +178,11 @@ def main(argv=None):
             row.update(val_map=evaluate(model, v_image, v_text, v_labels, "none"),
                        val_map_no_images=evaluate(model, v_image, v_text, v_labels, "images"),
                        val_map_no_texts=evaluate(model, v_image, v_text, v_labels, "texts"))
+            if ema is not None:
+                ema.sync()
+                row.update(ema_val_map=evaluate(ema.module, v_image, v_text, v_labels, "none"),
+                           ema_val_map_no_images=evaluate(ema.module, v_image, v_text, v_labels, "images"),
+                           ema_val_map_no_texts=evaluate(ema.module, v_image, v_text, v_labels, "texts"))
             print(json.dumps(row), flush=True)
         history.append(row)
         if world > 1:

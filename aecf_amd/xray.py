@@ -15,6 +15,7 @@ from __future__ import annotations
 import copy
 import ctypes
 import os
+from itertools import chain
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
@@ -443,6 +444,20 @@ class GraphedTrainStep:
                     for val in st.values():
                         if torch.is_tensor(val):
                             val.zero_()
+            if getattr(optimizer, "ema_decay", None) is not None:
+                # a moving average (and a master beside it) that the capture steps created comes back as the restored WEIGHTS
+                # -- zeros are no average --; one the caller handed over has been restored above.  Then the tensors an
+                # attached EmaModel reads
+                saved = opt_state["state"] if had_state else {}
+                index = {id(p): i for i, p in enumerate(chain.from_iterable(g["params"] for g in optimizer.param_groups))}
+                for p, st in optimizer.state.items():
+                    had = saved.get(index[id(p)], {})
+                    if torch.is_tensor(st.get("master")) and "master" not in had:
+                        st["master"].copy_(p)
+                    if torch.is_tensor(st.get("ema")) and "ema" not in had:
+                        st["ema"].copy_(p if st.get("master") is None else st["master"])
+                for p, out in optimizer._ema_out.items():
+                    out.copy_(optimizer.state[p]["ema"])
 
     def _step(self):
         self.optimizer.zero_grad(set_to_none=True)
@@ -459,6 +474,8 @@ class GraphedTrainStep:
         self.graph.replay()
         for pool in self._pools:
             pool.invalidate_cast_cache()
+        for ema in getattr(self.optimizer, "_ema_models", ()):
+            ema.after_replay()
         return self.loss
 
 

@@ -444,6 +444,38 @@ int aecf_adamw_mp_step(int32_t n, void* const* param, const void* const* grad, v
                        const int32_t* grad_dtype, void* ticket, float lr, float beta1, float beta2, float eps,
                        float weight_decay, const float* lr_dev, const float* grad_scale, const float* grad_coef,
                        const float* found_inf, const float* found_inf2, void* stream);
+/* aecf_adamw_mp_ema_step: aecf_adamw_mp_step (its arguments, update, ticket contract, launch grouping and checks; the moments and
+ * weights it writes are bit-equal) that also keeps an exponential moving average of the weights in the SAME launch -- the
+ * momentum key encoder of MoCo, the averaged weights people evaluate and ship (NOT in the reference, whose trainer has no
+ * averaged model; it replaces a torch._foreach_lerp_ over every parameter plus a cast pass after the step).  New entry points
+ * under ABI v10, no bump.
+ *   ema            array of n device pointers, required; ema[i]: float32 [numel[i]], or NULL: tensor i has no average;
+ *   ema_out        the array or any entry may be NULL; ema_out[i]: [numel[i]] of param_dtype[i], written as the
+ *                  round-to-nearest-even of the new average by the conversions of aecf_cast_f32_to_bf16 / _f16
+ *                  (ema_out == ema.to(dtype) bit for bit).  Beside a float32 parameter it is ignored: let `ema` BE the output;
+ *   ema_decay      beta; ema_decay_dev (may be NULL): ONE device float that replaces it, read at replay time as lr_dev is.
+ * After the update of an element, with w' the weight as STORED (the new float32 master, the float32 parameter itself, or --
+ * 16-bit parameter without a master -- the float32 value of the rounded parameter) and om = fl(1 - beta):
+ *   e' = fma(om, fl(w' - e), e)           (one rounding of the difference, one of the fused sum)
+ * beta is clamped to [0, 1] on the device; a NaN beta leaves every average and ema_out as it was and the step itself goes on.
+ * A non-zero found_inf / found_inf2 writes nothing, the averages included. */
+int aecf_adamw_mp_ema_step(int32_t n, void* const* param, const void* const* grad, void* const* master, void* const* exp_avg,
+                           void* const* exp_avg_sq, void* const* step, const int64_t* numel, const int32_t* param_dtype,
+                           const int32_t* grad_dtype, void* ticket, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, const float* lr_dev, const float* grad_scale, const float* grad_coef,
+                           const float* found_inf, const float* found_inf2, void* const* ema, void* const* ema_out,
+                           float ema_decay, const float* ema_decay_dev, void* stream);
+/* aecf_ema_update: the same average without an optimiser step, for tensors that had no gradient in a step and for callers on
+ * another optimiser: one launch per 24 tensors, no tickets.  w' = float32(src[i]) (src_dtype[i]), the arithmetic above, so the
+ * result is bit-equal to the fused step's on the same stored weights.  ema[i]: float32 [numel[i]], required; ema_out (the array
+ * or any entry may be NULL): [numel[i]] of out_dtype[i] (read only where ema_out is given; an AECF_F32 output is ignored, as
+ * above).  decay / decay_dev / found_inf / found_inf2 as above.  Tensors with numel[i] == 0 are skipped.
+ * Checks, before anything touches the device: n < 0 or a negative numel -> AECF_ERR_BAD_DIMS; a dtype outside the three ->
+ * AECF_ERR_UNSUPPORTED; n == 0 or every tensor empty -> AECF_OK without a launch; a required pointer NULL ->
+ * AECF_ERR_NULL_POINTER. */
+int aecf_ema_update(int32_t n, const void* const* src, const int32_t* src_dtype, void* const* ema, void* const* ema_out,
+                    const int32_t* out_dtype, const int64_t* numel, float decay, const float* decay_dev,
+                    const float* found_inf, const float* found_inf2, void* stream);
 /* Global L2 norm of n gradients of mixed dtype (replaces the norm of torch.nn.utils.clip_grad_norm_ and the inf check of
  * torch.amp.GradScaler) in two launches, fixed summation order, no float atomics: blocks store partial sums of squares into
  * `workspace` (aecf_grad_norm_workspace_bytes(n, numel); 0 for n <= 0, NULL or a negative numel), one block adds them in index
