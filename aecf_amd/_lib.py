@@ -339,6 +339,12 @@ _SYMBOLS = [
     ("aecf_retrieval_topk_workspace_bytes", c_size_t, [c_int64, c_int64, c_int32, c_int32]),
     ("aecf_retrieval_topk", c_int,
      [c_int64, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # multi-label evaluation: class-major keys + compacted positives, the four compare-and-count integers, float64 shares [5][C]
+    ("aecf_mlmetrics_workspace_bytes", c_size_t, [c_int64, c_int32]),
+    ("aecf_mlmetrics_prepare", c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("aecf_mlmetrics_counts", c_int, [c_int64, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("aecf_mlmetrics_finalize", c_int,
+     [c_int64, c_int32, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 

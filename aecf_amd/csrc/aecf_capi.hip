@@ -1621,6 +1621,49 @@ int aecf_retrieval_topk(int64_t rows, int64_t cols, int64_t row_offset, int32_t 
     return launch_status();
 }
 
+// ---- multi-label evaluation (include/aecf_hip.h, "multi-label evaluation")
+
+size_t aecf_mlmetrics_workspace_bytes(int64_t n_all, int32_t classes) {
+    if (n_all <= 0 || classes <= 0 || !mlmetrics_supported(n_all, classes)) return 0;
+    return mlmetrics_workspace_bytes(n_all, classes);
+}
+
+int aecf_mlmetrics_prepare(int64_t n_all, int32_t classes, int32_t dtype, const void* logits, const uint8_t* labels,
+                           int32_t* class_counts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_all <= 0 || classes <= 0) return AECF_ERR_BAD_DIMS;
+    if (!mlmetrics_supported(n_all, classes)) return AECF_ERR_UNSUPPORTED;
+    if (dtype != AECF_BF16 && dtype != AECF_F32 && dtype != AECF_F16) return AECF_ERR_UNSUPPORTED;
+    if (!logits || !labels || !class_counts || !workspace) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < mlmetrics_workspace_bytes(n_all, classes)) return AECF_ERR_WORKSPACE;
+    launch_mlmetrics_prepare(n_all, classes, dtype, logits, labels, class_counts, workspace, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_mlmetrics_counts(int64_t n_all, int32_t classes, int64_t row_offset, int64_t rows, const int32_t* class_counts,
+                          int32_t* counts, const void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_all <= 0 || classes <= 0 || rows < 0) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset > n_all || rows > n_all - row_offset) return AECF_ERR_BAD_DIMS;
+    if (!mlmetrics_supported(n_all, classes)) return AECF_ERR_UNSUPPORTED;
+    if (!class_counts || !workspace || (rows > 0 && !counts)) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < mlmetrics_workspace_bytes(n_all, classes)) return AECF_ERR_WORKSPACE;
+    if (rows == 0) return AECF_OK;
+    launch_mlmetrics_counts(n_all, classes, row_offset, rows, class_counts, counts, workspace, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_mlmetrics_finalize(int64_t n_all, int32_t classes, int64_t row_offset, int64_t rows, float logit_threshold,
+                            const int32_t* class_counts, const int32_t* counts, double* shares, const void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    if (n_all <= 0 || classes <= 0 || rows < 0 || logit_threshold != logit_threshold) return AECF_ERR_BAD_DIMS;
+    if (row_offset < 0 || row_offset > n_all || rows > n_all - row_offset) return AECF_ERR_BAD_DIMS;
+    if (!mlmetrics_supported(n_all, classes)) return AECF_ERR_UNSUPPORTED;
+    if (!class_counts || !shares || !workspace || (rows > 0 && !counts)) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < mlmetrics_workspace_bytes(n_all, classes)) return AECF_ERR_WORKSPACE;
+    launch_mlmetrics_finalize(n_all, classes, row_offset, rows, logit_threshold, class_counts, counts, shares, workspace,
+                              (hipStream_t)stream);
+    return launch_status();
+}
+
 int aecf_route_build(int64_t rows, const uint8_t* present_a, const uint8_t* present_b, int32_t* route, int32_t* slot,
                      int32_t* index, int32_t* counts, void* stream) {
     if (rows <= 0 || rows > 0x7fffffff) return AECF_ERR_BAD_DIMS;

@@ -518,6 +518,17 @@ void launch_retrieval_topk(int64_t rows, int64_t cols, int64_t row_offset, int d
 void launch_topk_gemm(int64_t rows, int64_t cols, int64_t row_offset, int d, int k, int kp, int exclude_partner, const void* a,
                       const void* b, unsigned long long* part, hipStream_t s);
 
+// Multi-label evaluation counts (aecf_metrics.hip): class-major keys and the compacted valid positives of every class (prepare),
+// the four compare-and-count integers of this rank's valid positives (counts), this rank's float64 shares [5][C] (finalize).
+bool mlmetrics_supported(int64_t n_all, int classes);
+size_t mlmetrics_workspace_bytes(int64_t n_all, int classes);
+void launch_mlmetrics_prepare(int64_t n_all, int classes, int dtype, const void* logits, const uint8_t* labels, int32_t* class_counts,
+                              void* workspace, hipStream_t s);
+void launch_mlmetrics_counts(int64_t n_all, int classes, int64_t row_offset, int64_t rows, const int32_t* class_counts, int32_t* counts,
+                             const void* workspace, hipStream_t s);
+void launch_mlmetrics_finalize(int64_t n_all, int classes, int64_t row_offset, int64_t rows, float threshold, const int32_t* class_counts,
+                               const int32_t* counts, double* shares, const void* workspace, hipStream_t s);
+
 // ---------------- presence routing (aecf_route.hip) ----------------
 void launch_route_build(int64_t rows, const uint8_t* pa, const uint8_t* pb, int32_t* route, int32_t* slot, int32_t* index,
                         int32_t* counts, hipStream_t s);

@@ -7,12 +7,14 @@ of ``train_both_models`` / ``main`` in ``xrays/train_xrays_example.py:312-427, 7
     python -m torch.distributed.run --nproc-per-node 4 --master-addr 127.0.0.1 -m aecf_amd.train_xray   # DP x 4
     python -m aecf_amd.train_xray --param-dtype bfloat16 --max-grad-norm 1.0        # bf16 model, float32 masters, clipping
     python -m aecf_amd.train_xray --ema-decay 0.999                                 # + validation of the averaged weights
+    python -m aecf_amd.train_xray --full-metrics                                    # + tie-exact mAP, AUROC, macro F1, all ranks
 
 The reference trains on precomputed CLIP features of a chest X-ray set that is not part of its repository
 (``.MISSING_LARGE_BLOBS``); ``--data train.pt,val.pt`` loads such files (dicts with image / text / labels), otherwise a
 synthetic set of the same shape is generated (CLIP-like 512-d features whose label signal is split between the
-modalities, so that the fusion has something to learn).  Plots, sklearn metrics and the baseline model of the reference
-script are reporting code outside the path and are not rebuilt.
+modalities, so that the fusion has something to learn).  Plots and the baseline model of the reference script are
+reporting code outside the path and are not rebuilt; its sklearn metrics (``calculate_metrics``, ref :260-295) are served by
+``--full-metrics`` through ``aecf_amd.metrics.multilabel_metrics``, every rank evaluating its shard of the validation set.
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ import torch
 import torch.distributed as dist
 
 from . import dp
+from .metrics import multilabel_metrics
 from .optim import EmaModel, FusedAdamW
 from .xray import AECFModel
 
@@ -71,6 +74,34 @@ def evaluate(model: AECFModel, image, text, labels, drop: str, batch: int = 4096
     return mean_average_precision(torch.cat(outs), labels)
 
 
+@torch.no_grad()
+def evaluate_full(model: AECFModel, image, text, labels, drop: str, rank: int, world: int, batch: int = 4096) -> dict:
+    """Tie-exact mAP, macro AUROC and macro F1 of the whole validation set (aecf_amd.metrics.multilabel_metrics): this rank
+    runs the model on its ``dp.shard_bounds`` rows and the ranks join their logits inside the call, so every rank must make
+    it.  The logits are scored in the model's dtype, as they are."""
+    model.eval()
+    lo, hi = dp.shard_bounds(image.shape[0], rank, world)
+    outs = []
+    for i in range(lo, hi, batch):
+        im, tx = image[i:min(i + batch, hi)], text[i:min(i + batch, hi)]
+        if drop == "images":
+            im = torch.zeros_like(im)
+        elif drop == "texts":
+            tx = torch.zeros_like(tx)
+        outs.append(model(im, tx))
+    logits = torch.cat(outs) if outs else torch.empty(0, labels.shape[1], dtype=next(model.parameters()).dtype, device=image.device)
+    m = multilabel_metrics(logits, labels[lo:hi], group=dist.group.WORLD if world > 1 else None)
+    return dict(val_map_exact=m["map"], val_auroc=m["macro_auroc"], val_macro_f1=m["macro_f1"])
+
+
+def _full_metric_rows(prefix: str, model: AECFModel, image, text, labels, rank: int, world: int) -> dict:
+    row = {}
+    for drop, suffix in (("none", ""), ("images", "_no_images"), ("texts", "_no_texts")):
+        for name, value in evaluate_full(model, image, text, labels, drop, rank, world).items():
+            row[prefix + name + suffix] = float(value) if rank == 0 else None
+    return row
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=60)
@@ -89,6 +120,9 @@ def main(argv=None):
     ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm inside the optimiser step")
     ap.add_argument("--ema-decay", type=float, default=None,
                     help="keep an exponential moving average of the weights inside the optimiser step and validate it too")
+    ap.add_argument("--full-metrics", action="store_true",
+                    help="also report tie-exact mAP, macro AUROC and macro F1 (val_map_exact, val_auroc, val_macro_f1 and their "
+                         "_no_images / _no_texts / ema_ forms), evaluated by every rank on its shard of the validation set")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -183,6 +217,14 @@ def main(argv=None):
                 row.update(ema_val_map=evaluate(ema.module, v_image, v_text, v_labels, "none"),
                            ema_val_map_no_images=evaluate(ema.module, v_image, v_text, v_labels, "images"),
                            ema_val_map_no_texts=evaluate(ema.module, v_image, v_text, v_labels, "texts"))
+        if args.full_metrics:                                               # a collective evaluation: every rank takes part
+            full = _full_metric_rows("", model, v_image, v_text, v_labels, rank, world)
+            if ema is not None:
+                ema.sync()
+                full.update(_full_metric_rows("ema_", ema.module, v_image, v_text, v_labels, rank, world))
+            if rank == 0:
+                row.update(full)
+        if rank == 0:
             print(json.dumps(row), flush=True)
         history.append(row)
         if world > 1:

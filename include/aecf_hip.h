@@ -1393,6 +1393,50 @@ int aecf_retrieval_topk(int64_t rows, int64_t cols, int64_t row_offset, int32_t 
                         const void* a, const void* b, float* values, int32_t* indices, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---- multi-label evaluation: tie-exact average precision, AUROC and F1 counts (what the reference's example computes on the
+ * host with sklearn, xrays/train_xrays_example.py:260-295 calculate_metrics, plus AUROC; the compare-and-count form is
+ * build-defined) ----
+ * logits [n_all,classes] row-major, AECF_F32 / AECF_BF16 / AECF_F16; labels [n_all,classes] uint8, positive iff non-zero.  For a
+ * class c the VALID entries are the non-NaN logits.  For every valid positive i, over the valid entries j of its class:
+ *   ge_all_i = #{ s_j >= s_i }   gt_all_i = #{ s_j > s_i }   ge_pos_i, gt_pos_i: the same over the valid positives only
+ * from which, with npos / nneg / nvalid the class's numbers of valid positives, valid negatives and valid entries,
+ *   AP_c    = (1 / npos) sum_i ge_pos_i / ge_all_i            (every sample at one score shares that threshold's precision)
+ *   AUROC_c = sum_i (lt_neg_i + eq_neg_i / 2) / (npos nneg),  lt_neg_i = (nvalid - ge_all_i) - (npos - ge_pos_i),
+ *                                                             eq_neg_i = (ge_all_i - gt_all_i) - (ge_pos_i - gt_pos_i)
+ * Nothing is sorted; the counts are integers, the same for any tile, block or rank arrangement.
+ *   prepare:   reads all n_all rows; fills the workspace and class_counts int32 [3][classes] = npos | nvalid | ninvalid.
+ *              Every rank runs it on the gathered rows.
+ *   counts:    for this rank's rows row_offset .. row_offset + rows, counts int32 [4][classes][rows] =
+ *              ge_all | gt_all | ge_pos | gt_pos at (class, row - row_offset); 0 where the entry is not a valid positive.
+ *              WRITTEN, not accumulated.  rows == 0 is valid and launches nothing (counts may then be NULL).
+ *   finalize:  shares float64 [5][classes] over this rank's rows = sum ge_pos / ge_all | sum (lt_neg + eq_neg / 2) | TP | FP | FN,
+ *              the last three with "predicted positive" = logit > logit_threshold among the valid entries.  Quotients and
+ *              sums in float64 in a fixed order (lane t of 256 takes rows t, t + 256, ..; then a fixed tree); the second and
+ *              the last three are sums of integers and half-integers, exact.  The caller adds the ranks' shares and divides.
+ * NaN rule: a NaN logit is an invalid entry of its class: never a key, never an anchor, in none of npos, nneg, TP, FP, FN, and
+ * counted in ninvalid.  It is excluded by selects (a NaN's order image lies below -inf's; a non-positive's divisor is 1), never
+ * by a division by zero.  +-inf, +-0 and denormals are ordinary values and -0 ties +0: values are compared through an integer
+ * image of their order, which does not depend on the float mode.
+ * Workspace, in this order, every part rounded up to 256 bytes, with Np = n_all rounded up to 64 and nch = Np / 64:
+ *   keys float32 [classes][Np] (class-major, an exact conversion) | positive keys float32 [classes][Np] and their rows int32
+ *   [classes][Np] (the valid positives of a class in row order, npos of them) | uint64 [classes][nch] ballots of the valid
+ *   positives | int32 [classes][nch] list offsets of the chunks | int32 [classes][nch] valid entries of the chunks
+ * i.e. 3 * 4 classes Np + 16 classes nch bytes before the rounding.  counts and finalize read the workspace prepare filled.
+ * Served: 1 <= classes <= 4096, 1 <= n_all <= 2^24, n_all * classes <= 2^28; outside them aecf_mlmetrics_workspace_bytes
+ * answers 0 and the calls AECF_ERR_UNSUPPORTED.  Cost: npos (n_all + npos) compare-and-count pairs per class, a few vector
+ * operations each.  Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host, no
+ * atomics.  Checks before any launch: sizes -- n_all, classes <= 0, rows < 0, row_offset < 0, row_offset + rows > n_all, a NaN
+ * threshold -- (AECF_ERR_BAD_DIMS), then the limits and the dtype (AECF_ERR_UNSUPPORTED), then NULL pointers
+ * (AECF_ERR_NULL_POINTER), then the workspace size (AECF_ERR_WORKSPACE). */
+size_t aecf_mlmetrics_workspace_bytes(int64_t n_all, int32_t classes);      /* 0: shape not served */
+int aecf_mlmetrics_prepare(int64_t n_all, int32_t classes, int32_t dtype, const void* logits, const uint8_t* labels,
+                           int32_t* class_counts, void* workspace, size_t workspace_bytes, void* stream);
+int aecf_mlmetrics_counts(int64_t n_all, int32_t classes, int64_t row_offset, int64_t rows, const int32_t* class_counts,
+                          int32_t* counts, const void* workspace, size_t workspace_bytes, void* stream);
+int aecf_mlmetrics_finalize(int64_t n_all, int32_t classes, int64_t row_offset, int64_t rows, float logit_threshold,
+                            const int32_t* class_counts, const int32_t* counts, double* shares, const void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
