@@ -18,6 +18,10 @@ AECF_BF16 = 0
 AECF_F32 = 1
 AECF_F16 = 2
 AECF_SETS_U8 = 3            # aecf_label_sets_pack: one byte per class (torch bool / uint8)
+AECF_MLLOSS_U8 = 3          # aecf_mlloss_*: label codes beside the aecf_dtype values (bool / uint8, int8 with negative = unknown)
+AECF_MLLOSS_I8 = 4
+AECF_MLLOSS_MEAN = 0        # aecf_mlloss_*: reduction
+AECF_MLLOSS_SUM = 1
 AECF_SETS_OVERLAP = 0
 AECF_SETS_JACCARD = 1
 AECF_PRECISE = 1
@@ -345,6 +349,14 @@ _SYMBOLS = [
     ("aecf_mlmetrics_counts", c_int, [c_int64, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     ("aecf_mlmetrics_finalize", c_int,
      [c_int64, c_int32, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # multi-label classification loss (BCE / focal / asymmetric): per-class stats + totals, then the gradient in one pass
+    ("aecf_mlloss_workspace_bytes", c_size_t, [c_int64, c_int32]),
+    ("aecf_mlloss_forward", c_int,
+     [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int32,
+      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("aecf_mlloss_backward", c_int,
+     [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int32,
+      c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 

@@ -1664,6 +1664,58 @@ int aecf_mlmetrics_finalize(int64_t n_all, int32_t classes, int64_t row_offset, 
     return launch_status();
 }
 
+// ---- multi-label classification loss (include/aecf_hip.h, "multi-label classification loss")
+
+namespace {
+
+// sizes and options first (BAD_DIMS), then the limits and the dtype codes (UNSUPPORTED)
+int mlloss_check(int64_t n, int32_t classes, int32_t dtype, int32_t label_dtype, float gamma_pos, float gamma_neg, float margin,
+                 float label_smoothing, int32_t reduction, float factor) {
+    if (n <= 0 || classes <= 0) return AECF_ERR_BAD_DIMS;
+    if (!(gamma_pos >= 0.0f) || !(gamma_neg >= 0.0f) || !__builtin_isfinite(gamma_pos) || !__builtin_isfinite(gamma_neg))
+        return AECF_ERR_BAD_DIMS;
+    if (!__builtin_isfinite(factor)) return AECF_ERR_BAD_DIMS;
+    if (!(margin >= 0.0f && margin < 1.0f) || !(label_smoothing >= 0.0f && label_smoothing < 1.0f)) return AECF_ERR_BAD_DIMS;
+    if (reduction != AECF_MLLOSS_MEAN && reduction != AECF_MLLOSS_SUM) return AECF_ERR_BAD_DIMS;
+    if (!mlloss_supported(n, classes)) return AECF_ERR_UNSUPPORTED;
+    if (dtype != AECF_BF16 && dtype != AECF_F32 && dtype != AECF_F16) return AECF_ERR_UNSUPPORTED;
+    if (label_dtype < AECF_BF16 || label_dtype > AECF_MLLOSS_I8) return AECF_ERR_UNSUPPORTED;
+    return AECF_OK;
+}
+
+}  // namespace
+
+size_t aecf_mlloss_workspace_bytes(int64_t n, int32_t classes) {
+    if (n <= 0 || classes <= 0 || !mlloss_supported(n, classes)) return 0;
+    return mlloss_workspace_bytes(n, classes);
+}
+
+int aecf_mlloss_forward(int64_t n, int32_t classes, int32_t dtype, int32_t label_dtype, const void* logits, const void* labels,
+                        const float* pos_scale, const float* neg_scale, float gamma_pos, float gamma_neg, float margin,
+                        float label_smoothing, int32_t reduction, double* stats, double* totals, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    const int st = mlloss_check(n, classes, dtype, label_dtype, gamma_pos, gamma_neg, margin, label_smoothing, reduction, 1.0f);
+    if (st != AECF_OK) return st;
+    if (!logits || !labels || !stats || !totals || !workspace) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < mlloss_workspace_bytes(n, classes)) return AECF_ERR_WORKSPACE;
+    launch_mlloss_forward(n, classes, dtype, label_dtype, logits, labels, pos_scale, neg_scale, gamma_pos, gamma_neg, margin,
+                          label_smoothing, reduction == AECF_MLLOSS_MEAN ? 1 : 0, stats, totals, workspace, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_mlloss_backward(int64_t n, int32_t classes, int32_t dtype, int32_t label_dtype, const void* logits, const void* labels,
+                         const float* pos_scale, const float* neg_scale, float gamma_pos, float gamma_neg, float margin,
+                         float label_smoothing, int32_t reduction, const double* totals, const float* grad_out, float factor,
+                         void* dlogits, void* stream) {
+    const int st = mlloss_check(n, classes, dtype, label_dtype, gamma_pos, gamma_neg, margin, label_smoothing, reduction, factor);
+    if (st != AECF_OK) return st;
+    if (!logits || !labels || !totals || !dlogits) return AECF_ERR_NULL_POINTER;
+    launch_mlloss_backward(n, classes, dtype, label_dtype, logits, labels, pos_scale, neg_scale, gamma_pos, gamma_neg, margin,
+                           label_smoothing, reduction == AECF_MLLOSS_MEAN ? 1 : 0, totals, grad_out, factor, dlogits,
+                           (hipStream_t)stream);
+    return launch_status();
+}
+
 int aecf_route_build(int64_t rows, const uint8_t* present_a, const uint8_t* present_b, int32_t* route, int32_t* slot,
                      int32_t* index, int32_t* counts, void* stream) {
     if (rows <= 0 || rows > 0x7fffffff) return AECF_ERR_BAD_DIMS;

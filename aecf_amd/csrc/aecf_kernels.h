@@ -529,6 +529,19 @@ void launch_mlmetrics_counts(int64_t n_all, int classes, int64_t row_offset, int
 void launch_mlmetrics_finalize(int64_t n_all, int classes, int64_t row_offset, int64_t rows, float threshold, const int32_t* class_counts,
                                const int32_t* counts, double* shares, const void* workspace, hipStream_t s);
 
+// Multi-label classification loss (aecf_mlloss.hip): BCE / focal / asymmetric loss of logits [n, C] as one elementwise formula.
+// forward: one pass (per-row-block float64 loss sums and int32 valid counts per class) and a fixed-order finalize (stats [2][C],
+// totals); backward: one pass that recomputes the element and scales it by upstream * factor / N read from totals.
+// dtype: aecf_dtype of the logits; label_dtype: aecf_dtype, AECF_MLLOSS_U8 or AECF_MLLOSS_I8.
+bool mlloss_supported(int64_t n, int classes);
+size_t mlloss_workspace_bytes(int64_t n, int classes);
+void launch_mlloss_forward(int64_t n, int classes, int dtype, int label_dtype, const void* logits, const void* labels,
+                           const float* pos_scale, const float* neg_scale, float gamma_pos, float gamma_neg, float margin, float eps,
+                           int mean, double* stats, double* totals, void* workspace, hipStream_t s);
+void launch_mlloss_backward(int64_t n, int classes, int dtype, int label_dtype, const void* logits, const void* labels,
+                            const float* pos_scale, const float* neg_scale, float gamma_pos, float gamma_neg, float margin, float eps,
+                            int mean, const double* totals, const float* grad_out, float factor, void* dlogits, hipStream_t s);
+
 // ---------------- presence routing (aecf_route.hip) ----------------
 void launch_route_build(int64_t rows, const uint8_t* pa, const uint8_t* pb, int32_t* route, int32_t* slot, int32_t* index,
                         int32_t* counts, hipStream_t s);

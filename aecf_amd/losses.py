@@ -2242,3 +2242,289 @@ def fusion_objective(task_loss: torch.Tensor, masking: Optional[CurriculumMaskin
             term = info_nce(za, zb, temperature, group, min_temperature)
         total = _plus(total, contrastive_weight * term)
     return total
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Multi-label classification loss: binary cross-entropy, focal and asymmetric loss as one elementwise formula
+# (aecf_mlloss_forward / _backward, include/aecf_hip.h "multi-label classification loss"); replaces the torch criterion of the
+# reference's example, nn.BCEWithLogitsLoss (ref xrays/train_xrays_example.py:327, 366, 374).
+# ---------------------------------------------------------------------------------------------------------------------------
+
+_MLLOSS_LABEL_KINDS = {torch.float32: _lib.AECF_F32, torch.bfloat16: _lib.AECF_BF16, torch.float16: _lib.AECF_F16,
+                       torch.bool: _lib.AECF_MLLOSS_U8, torch.uint8: _lib.AECF_MLLOSS_U8, torch.int8: _lib.AECF_MLLOSS_I8}
+_MLLOSS_LOGIT_KINDS = {torch.float32: _lib.AECF_F32, torch.bfloat16: _lib.AECF_BF16, torch.float16: _lib.AECF_F16}
+_MLLOSS_REDUCTIONS = {"mean": _lib.AECF_MLLOSS_MEAN, "sum": _lib.AECF_MLLOSS_SUM}
+MLLOSS_MAX_CLASSES = 4096
+MLLOSS_MAX_ELEMENTS = 1 << 30
+
+
+class _MultilabelLoss(torch.autograd.Function):
+    """aecf_mlloss_forward (two launches: the pass over (logits, targets) and the fixed-order finalize) and aecf_mlloss_backward
+    (one launch that recomputes the element and reads its scale, upstream * factor / N, on the device).  Returns the reduced
+    loss (0-dim float32) and the float64 [2, C] stats (loss sums | valid counts per class), global over ``group`` after ONE
+    all-reduce of the stats.  Nothing of size n x C is kept between the passes; nothing is read on the host."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, pos_scale, neg_scale, gamma_pos, gamma_neg, margin, eps, reduction, group):
+        lib = _lib.load()
+        rows, C = logits.shape
+        dev = logits.device
+        x, y = logits.detach(), targets.detach()         # (the steps of a host-bound call are counted: no op that does nothing)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        if not y.is_contiguous():
+            y = y.contiguous()
+        if y.dtype == torch.bool:
+            y = y.view(torch.uint8)
+        kinds = (_MLLOSS_LOGIT_KINDS[x.dtype], _MLLOSS_LABEL_KINDS[targets.dtype])
+        opts = (float(gamma_pos), float(gamma_neg), float(margin), float(eps), _MLLOSS_REDUCTIONS[reduction])
+        world = dp.world_info(group)[1]
+        stats = torch.empty(2, C, dtype=torch.float64, device=dev)
+        totals = torch.empty(6, dtype=torch.float32, device=dev)     # the 24-byte record: float64 sum, float64 N, float32 loss, 0
+        if rows == 0:                       # an empty shard: nothing to launch, its stats are zeros
+            stats.zero_()
+            totals.zero_()
+        else:
+            ws_bytes = lib.aecf_mlloss_workspace_bytes(rows, C)
+            if ws_bytes == 0:
+                raise NotImplementedError(f"aecf_amd: multilabel_loss serves C <= {MLLOSS_MAX_CLASSES} and n * C <= 2**30 per rank, "
+                                          f"got {rows} x {C}")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.aecf_mlloss_forward(rows, C, *kinds, _ptr(x), _ptr(y), _ptr(pos_scale), _ptr(neg_scale), *opts,
+                                               _ptr(stats), _ptr(totals), _ptr(ws), ws_bytes, _stream()), "aecf_mlloss_forward")
+        if world > 1:
+            torch.distributed.all_reduce(stats, group=group)
+            total, count = stats[0].sum(), stats[1].sum()
+            if reduction == "mean":
+                value = torch.where(count > 0, total / torch.where(count > 0, count, torch.ones_like(count)), torch.zeros_like(total))
+            else:
+                value = total
+            totals = torch.stack((total, count, torch.zeros_like(total)))
+            loss = value.to(torch.float32)
+        else:
+            loss = totals[4]
+        ctx.save_for_backward(x, y, pos_scale, neg_scale, totals)
+        ctx.meta = (rows, C, kinds, opts, float(world))
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_loss, _d_stats):
+        lib = _lib.load()
+        x, y, pos_scale, neg_scale, totals = ctx.saved_tensors
+        rows, C, kinds, opts, factor = ctx.meta
+        dx = torch.empty_like(x)
+        if rows > 0:
+            up = d_loss if d_loss.dtype == torch.float32 else d_loss.to(torch.float32)       # one element, read on the device
+            _lib.check(lib.aecf_mlloss_backward(rows, C, *kinds, _ptr(x), _ptr(y), _ptr(pos_scale), _ptr(neg_scale), *opts,
+                                                _ptr(totals), _ptr(up), factor, _ptr(dx), _stream()), "aecf_mlloss_backward")
+        return dx, None, None, None, None, None, None, None, None, None
+
+
+def _class_vector(value, name: str, C: int, device) -> Optional[torch.Tensor]:
+    """``pos_weight`` / ``class_weight`` as a float32 [C] tensor on the device.  A sequence is checked on the host (finite, not
+    negative); a tensor is taken as it is -- checking it would be a host read."""
+    if value is None:
+        return None
+    if isinstance(value, torch.Tensor):
+        if value.dim() != 1 or value.shape[0] != C:
+            raise ValueError(f"aecf_amd: {name} must hold one value per class, [{C}], got shape {tuple(value.shape)}")
+        if not value.dtype.is_floating_point:
+            raise TypeError(f"aecf_amd: a tensor {name} must be floating point, got {value.dtype}")
+        return value.detach().to(device=device, dtype=torch.float32)
+    if isinstance(value, (str, bytes)) or not hasattr(value, "__len__"):
+        raise TypeError(f"aecf_amd: {name} must be a [C] tensor or a sequence of numbers, got {type(value).__name__}")
+    vals = [float(v) for v in value]
+    if len(vals) != C:
+        raise ValueError(f"aecf_amd: {name} must hold one value per class, {C}, got {len(vals)}")
+    if any(not (v >= 0.0 and v != float("inf")) for v in vals):
+        raise ValueError(f"aecf_amd: {name} must be finite and not negative")
+    return torch.tensor(vals, dtype=torch.float32, device=device)
+
+
+def _compute_scales(pos_weight, class_weight, alpha, C: int, device):
+    """a = w p (alpha or 1), b = w ((1 - alpha) or 1) as float32 [C] device tensors, None where the vector is all ones"""
+    p = _class_vector(pos_weight, "pos_weight", C, device)
+    w = _class_vector(class_weight, "class_weight", C, device)
+    a, b = w, w
+    if p is not None:
+        a = p if a is None else a * p
+    if alpha is not None:
+        a = torch.full((C,), alpha, dtype=torch.float32, device=device) if a is None else a * alpha
+        b = torch.full((C,), 1.0 - alpha, dtype=torch.float32, device=device) if b is None else b * (1.0 - alpha)
+    return (None if a is None else a.contiguous()), (None if b is None else b.contiguous())
+
+
+def _weight_key(value):
+    """what names a weight argument in a fold's key: a tensor by identity and version, a sequence by its values"""
+    if value is None or isinstance(value, torch.Tensor):
+        return (id(value), getattr(value, "_version", None))
+    try:
+        return tuple(float(v) for v in value)
+    except TypeError:
+        return (id(value), None)
+
+
+_mlloss_scales: list = []           # the functional form's last fold: (key, the objects the key names, pos_scale, neg_scale)
+
+
+def _fold_scales(pos_weight, class_weight, alpha, C: int, device):
+    """The scale vectors of the FUNCTIONAL form.  The last fold is kept and reused while the same weights come again (tensors by
+    identity and version, sequences by value); another call's weights replace it.  A captured graph holds the vectors' addresses,
+    not the vectors: a caller that captures the functional form with ``alpha`` or with both weights keeps the fold alive by not
+    calling it with other weights -- or uses ``MultilabelLoss``, which owns its vectors."""
+    if pos_weight is None and class_weight is None and alpha is None:
+        return None, None
+    key = (_weight_key(pos_weight), _weight_key(class_weight), alpha, C, str(device))
+    if _mlloss_scales and _mlloss_scales[0][0] == key:
+        return _mlloss_scales[0][2], _mlloss_scales[0][3]
+    a, b = _compute_scales(pos_weight, class_weight, alpha, C, device)
+    _mlloss_scales[:] = [(key, (pos_weight, class_weight), a, b)]
+    return a, b
+
+
+def _unit_interval(value, name: str, closed_top: bool = False) -> float:
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise TypeError(f"aecf_amd: {name} must be a Python number, got {type(value).__name__}")
+    v = float(value)
+    if not (0.0 <= v <= 1.0 if closed_top else 0.0 <= v < 1.0):
+        raise ValueError(f"aecf_amd: {name} must lie in [0, 1{']' if closed_top else ')'}, got {value!r}")
+    return v
+
+
+def _gamma(value, name: str) -> float:
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise TypeError(f"aecf_amd: {name} must be a Python number, got {type(value).__name__}")
+    v = float(value)
+    if not (0.0 <= v < float("inf")):
+        raise ValueError(f"aecf_amd: {name} must be finite and >= 0, got {value!r}")
+    return v
+
+
+def multilabel_loss(logits: torch.Tensor, targets: torch.Tensor, *, pos_weight=None, class_weight=None, alpha: Optional[float] = None,
+                    gamma_pos: float = 0.0, gamma_neg: float = 0.0, margin: float = 0.0, label_smoothing: float = 0.0,
+                    reduction: str = "mean", group=None, return_per_class: bool = False, _fold=_fold_scales):
+    """The multi-label classification loss of ``logits`` [n, C] (float32, bfloat16 or float16 on a ROCm device, read as stored)
+    against ``targets`` [n, C], in float32 on the library's kernels.  With s = sigmoid(x), t' = t (1 - label_smoothing) +
+    label_smoothing / 2, q = max(s - margin, 0), a = class_weight * pos_weight * (alpha or 1) and b = class_weight * ((1 - alpha)
+    or 1) per class:
+
+        l = - a t' (1 - s)^gamma_pos log s  -  b (1 - t') q^gamma_neg log(1 - q)            (p^0 = 1 for every p)
+
+    ``gamma_pos = gamma_neg = margin = 0`` is ``F.binary_cross_entropy_with_logits(x, t, weight=class_weight,
+    pos_weight=pos_weight)`` (soft targets included); ``gamma_pos = gamma_neg = gamma`` with ``alpha`` is the focal loss (Lin et
+    al. 2017); hard targets with ``(gamma_pos, gamma_neg, margin) = (0, 4, 0.05)`` are the asymmetric loss (Ridnik et al. 2021)
+    without its 1e-8 clamps.  Where s - margin <= 0 in float32 the second term and its gradient are exact zeros.
+
+    UNKNOWN targets are left out of the loss and of its normalisation: a floating-point target that is NaN or < 0, a negative
+    int8 target (bool and uint8 have no unknown value; an integer target that is not zero counts as 1).  Their gradient is an
+    exact zero and their logit reaches no output.  ``reduction="mean"`` divides by the number N of valid elements over all
+    ranks (N = 0: loss 0, zero gradients); ``"sum"`` does not divide; there is no ``"none"``.
+
+    Returns a 0-dim float32 device tensor; with ``return_per_class`` also a detached float32 [C]: the mean loss over the valid
+    elements of each class, 0 where a class has none.  Once differentiable.  Data parallel (``group``): ONE all-reduce of the
+    float64 [2, C] stats; the value is the global loss on every rank and the gradient carries ``world / N`` for the averaging
+    collectives of ``dp`` (the convention of the contrastive drivers).  Shards may be uneven or empty.  ``pos_weight`` /
+    ``class_weight``: [C] tensors or sequences, folded into the two scale vectors with torch ops on [C] tensors (the last fold
+    is reused while the same weights come again; ``MultilabelLoss`` owns its folds, which is what a captured step needs).  There is no torch fallback: unserved shapes raise NotImplementedError."""
+    _require_device(logits, "logits")
+    _require_device(targets, "targets")
+    if logits.dim() != 2 or targets.shape != logits.shape:
+        raise ValueError(f"multilabel_loss expects logits and targets of one shape [n, C], got {tuple(logits.shape)} and "
+                         f"{tuple(targets.shape)}")
+    if logits.dtype not in _MLLOSS_LOGIT_KINDS:
+        raise TypeError(f"aecf_amd: multilabel_loss takes float32, bfloat16 or float16 logits, got {logits.dtype}")
+    if targets.dtype not in _MLLOSS_LABEL_KINDS:
+        raise TypeError(f"aecf_amd: multilabel_loss takes float32, bfloat16, float16, bool, uint8 or int8 targets, got {targets.dtype}")
+    if targets.device != logits.device:
+        raise ValueError(f"aecf_amd: the targets live on {targets.device}, the logits on {logits.device}")
+    if reduction not in _MLLOSS_REDUCTIONS:
+        raise ValueError(f"aecf_amd: multilabel_loss reduces by 'mean' or 'sum' (there is no 'none'), got {reduction!r}")
+    gamma_pos, gamma_neg = _gamma(gamma_pos, "gamma_pos"), _gamma(gamma_neg, "gamma_neg")
+    margin = _unit_interval(margin, "margin")
+    eps = _unit_interval(label_smoothing, "label_smoothing")
+    if alpha is not None:
+        alpha = _unit_interval(alpha, "alpha", closed_top=True)
+    rows, C = logits.shape
+    if C < 1:
+        raise ValueError("aecf_amd: multilabel_loss needs at least one class")
+    if C > MLLOSS_MAX_CLASSES or rows * C > MLLOSS_MAX_ELEMENTS:
+        raise NotImplementedError(f"aecf_amd: multilabel_loss serves C <= {MLLOSS_MAX_CLASSES} and n * C <= 2**30 per rank, got "
+                                  f"{rows} x {C}")
+    a, b = _fold(pos_weight, class_weight, alpha, C, logits.device)
+    loss, stats = _MultilabelLoss.apply(logits, targets, a, b, gamma_pos, gamma_neg, margin, eps, reduction, group)
+    if not return_per_class:
+        return loss
+    count = stats[1]
+    per_class = torch.where(count > 0, stats[0] / torch.where(count > 0, count, torch.ones_like(count)), torch.zeros_like(count))
+    return loss, per_class.to(torch.float32)
+
+
+class MultilabelLoss(torch.nn.Module):
+    """``multilabel_loss`` with its options fixed, called as ``criterion(logits, labels)``: a drop-in for the criterion of
+    ``xray.train_step`` and ``xray.GraphedTrainStep``.  ``pos_weight`` / ``class_weight`` are kept as float32 buffers (they move
+    with the module).  The module OWNS its folded scale vectors: one fold per device and state of the buffers (identity and
+    version), kept for the module's life, so the addresses a captured graph holds stay valid whatever other losses are called
+    in between.  (A graph captured before the buffers were edited or moved keeps reading the fold of its capture.)"""
+
+    def __init__(self, pos_weight=None, class_weight=None, alpha: Optional[float] = None, gamma_pos: float = 0.0,
+                 gamma_neg: float = 0.0, margin: float = 0.0, label_smoothing: float = 0.0, reduction: str = "mean", group=None):
+        super().__init__()
+        if reduction not in _MLLOSS_REDUCTIONS:
+            raise ValueError(f"aecf_amd: multilabel_loss reduces by 'mean' or 'sum' (there is no 'none'), got {reduction!r}")
+        self.gamma_pos, self.gamma_neg = _gamma(gamma_pos, "gamma_pos"), _gamma(gamma_neg, "gamma_neg")
+        self.margin = _unit_interval(margin, "margin")
+        self.label_smoothing = _unit_interval(label_smoothing, "label_smoothing")
+        self.alpha = None if alpha is None else _unit_interval(alpha, "alpha", closed_top=True)
+        self.reduction, self.group = reduction, group
+        for name, value in (("pos_weight", pos_weight), ("class_weight", class_weight)):
+            if value is not None and not isinstance(value, torch.Tensor):
+                value = _class_vector(value, name, len(value), "cpu")
+            self.register_buffer(name, None if value is None else value.detach().to(torch.float32).clone())
+        self._folds = {}                    # (buffers' identity and version, C, device) -> (pos_scale, neg_scale), never dropped
+
+    def _fold(self, pos_weight, class_weight, alpha, C: int, device):
+        if pos_weight is None and class_weight is None and alpha is None:
+            return None, None
+        key = (_weight_key(pos_weight), _weight_key(class_weight), alpha, C, str(device))
+        if key not in self._folds:
+            # (the entry holds the tensors its key names by id(): an id is not reused while its object lives)
+            self._folds[key] = _compute_scales(pos_weight, class_weight, alpha, C, device) + (pos_weight, class_weight)
+        return self._folds[key][:2]
+
+    def forward(self, logits: torch.Tensor, targets: torch.Tensor, return_per_class: bool = False):
+        return multilabel_loss(logits, targets, pos_weight=self.pos_weight, class_weight=self.class_weight, alpha=self.alpha,
+                               gamma_pos=self.gamma_pos, gamma_neg=self.gamma_neg, margin=self.margin,
+                               label_smoothing=self.label_smoothing, reduction=self.reduction, group=self.group,
+                               return_per_class=return_per_class, _fold=self._fold)
+
+    def extra_repr(self) -> str:
+        return (f"gamma_pos={self.gamma_pos}, gamma_neg={self.gamma_neg}, margin={self.margin}, alpha={self.alpha}, "
+                f"label_smoothing={self.label_smoothing}, reduction={self.reduction!r}")
+
+
+def class_balance_weights(labels: torch.Tensor, group=None, max_weight: Optional[float] = None) -> torch.Tensor:
+    """``pos_weight[c] = n_neg[c] / n_pos[c]`` over the valid labels [n, C] of every rank of ``group`` (``multilabel_loss``'s
+    rule for unknown targets; a valid target counts as positive iff it is not zero), 1 where a class has no positive, clamped to
+    ``max_weight`` if given.  A float32 [C] device tensor; torch reductions over the label matrix, run once before training --
+    nothing is read on the host on one rank, the ranks join their float64 [2, C] counts in one all-reduce."""
+    _require_device(labels, "labels")
+    if labels.dim() != 2:
+        raise ValueError(f"class_balance_weights expects labels [n, C], got {tuple(labels.shape)}")
+    if labels.dtype not in _MLLOSS_LABEL_KINDS:
+        raise TypeError(f"aecf_amd: class_balance_weights takes float32, bfloat16, float16, bool, uint8 or int8 labels, got {labels.dtype}")
+    if max_weight is not None and not (isinstance(max_weight, (int, float)) and not isinstance(max_weight, bool) and max_weight > 0):
+        raise ValueError(f"aecf_amd: max_weight must be a positive number, got {max_weight!r}")
+    with torch.no_grad():
+        y = labels.detach()
+        valid = torch.ones_like(y, dtype=torch.bool) if y.dtype in (torch.bool, torch.uint8) else y >= 0
+        pos = valid & (y != 0)
+        counts = torch.stack((pos.sum(0), valid.sum(0))).to(torch.float64)
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(counts, group=group)
+        n_pos, n_neg = counts[0], counts[1] - counts[0]
+        w = torch.where(n_pos > 0, n_neg / torch.where(n_pos > 0, n_pos, torch.ones_like(n_pos)), torch.ones_like(n_pos))
+        if max_weight is not None:
+            w = w.clamp(max=float(max_weight))
+        return w.to(torch.float32)

@@ -8,6 +8,7 @@ of ``train_both_models`` / ``main`` in ``xrays/train_xrays_example.py:312-427, 7
     python -m aecf_amd.train_xray --param-dtype bfloat16 --max-grad-norm 1.0        # bf16 model, float32 masters, clipping
     python -m aecf_amd.train_xray --ema-decay 0.999                                 # + validation of the averaged weights
     python -m aecf_amd.train_xray --full-metrics                                    # + tie-exact mAP, AUROC, macro F1, all ranks
+    python -m aecf_amd.train_xray --loss asymmetric --pos-weight auto               # the library's multi-label loss, class balance
 
 The reference trains on precomputed CLIP features of a chest X-ray set that is not part of its repository
 (``.MISSING_LARGE_BLOBS``); ``--data train.pt,val.pt`` loads such files (dicts with image / text / labels), otherwise a
@@ -15,6 +16,8 @@ synthetic set of the same shape is generated (CLIP-like 512-d features whose lab
 modalities, so that the fusion has something to learn).  Plots and the baseline model of the reference script are
 reporting code outside the path and are not rebuilt; its sklearn metrics (``calculate_metrics``, ref :260-295) are served by
 ``--full-metrics`` through ``aecf_amd.metrics.multilabel_metrics``, every rank evaluating its shard of the validation set.
+``--loss`` / ``--pos-weight auto`` replace the torch criterion (ref :327, 366, 374) by ``aecf_amd.losses.MultilabelLoss`` on the
+logits as the model leaves them; with neither flag the torch ``BCEWithLogitsLoss`` line runs as before.
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ import torch
 import torch.distributed as dist
 
 from . import dp
+from .losses import MultilabelLoss, class_balance_weights
 from .metrics import multilabel_metrics
 from .optim import EmaModel, FusedAdamW
 from .xray import AECFModel
@@ -102,6 +106,9 @@ def _full_metric_rows(prefix: str, model: AECFModel, image, text, labels, rank: 
     return row
 
 
+LOSS_FORMS = {"bce": (0.0, 0.0, 0.0), "focal": (2.0, 2.0, 0.0), "asymmetric": (0.0, 4.0, 0.05)}     # gamma+, gamma-, margin
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=60)
@@ -123,6 +130,11 @@ def main(argv=None):
     ap.add_argument("--full-metrics", action="store_true",
                     help="also report tie-exact mAP, macro AUROC and macro F1 (val_map_exact, val_auroc, val_macro_f1 and their "
                          "_no_images / _no_texts / ema_ forms), evaluated by every rank on its shard of the validation set")
+    ap.add_argument("--loss", choices=tuple(LOSS_FORMS), default=None,
+                    help="the library's multi-label loss on the logits as they are: bce, focal (gamma 2) or asymmetric "
+                         "(gamma- 4, margin 0.05); unknown labels (NaN or < 0) are left out.  Default: torch's BCEWithLogitsLoss")
+    ap.add_argument("--pos-weight", choices=("auto",), default=None,
+                    help="auto: per-class n_neg / n_pos of the training labels as pos_weight (implies --loss bce if none is given)")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -160,7 +172,14 @@ def main(argv=None):
     opt = FusedAdamW(params, lr=args.lr, weight_decay=0.01,                 # ref :322-323 (torch.optim.AdamW's update, one launch)
                      master_weights=low, max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay)
     ema = EmaModel(model, opt) if args.ema_decay is not None else None      # (every rank keeps the same averages)
-    crit = torch.nn.BCEWithLogitsLoss()
+    fused_loss = args.loss is not None or args.pos_weight is not None
+    if fused_loss:
+        gamma_pos, gamma_neg, margin = LOSS_FORMS[args.loss or "bce"]
+        crit = MultilabelLoss(pos_weight=class_balance_weights(labels) if args.pos_weight == "auto" else None,
+                              gamma_pos=gamma_pos, gamma_neg=gamma_neg, margin=margin,
+                              group=dist.group.WORLD if world > 1 else None)     # the global mean over the valid labels of all ranks
+    else:
+        crit = torch.nn.BCEWithLogitsLoss()
     n = image.shape[0]
     steps = (n + args.batch - 1) // args.batch                              # the short last batch is kept (DataLoader default)
     perm_gen = torch.Generator(device=device).manual_seed(args.seed + 3)    # same permutation on every rank
@@ -187,17 +206,22 @@ def main(argv=None):
                 da, db = model.draw_missing(b, device, generator=miss_gen)  # the GLOBAL batch's draws; this rank's rows
                 missing = (da[lo:hi], db[lo:hi])
             if hi <= lo:                                # fewer rows than ranks: this rank only joins the collective
+                if fused_loss:                          # (the loss's all-reduce first, as on the ranks that hold rows)
+                    loss_sum += crit(torch.empty(0, args.classes, dtype=params[0].dtype, device=device), labels[sel])
                 bucket.zero()
                 bucket.all_reduce(average=True)
                 opt.step()
                 continue
             logits, info = model(image[sel], text[sel], return_info=True, mask_uniforms=u, missing=missing)
-            loss = crit(logits.float(), labels[sel])
+            loss = crit(logits, labels[sel]) if fused_loss else crit(logits.float(), labels[sel])
             if bucket is None:
                 opt.zero_grad(set_to_none=True)
             else:
                 bucket.zero()
-            (loss * dp.shard_loss_scale(hi - lo, b, world)).backward()
+            if fused_loss and world > 1:                # already the global loss, its gradient scaled for the averaging bucket
+                loss.backward()
+            else:
+                (loss * dp.shard_loss_scale(hi - lo, b, world)).backward()
             if bucket is not None:
                 bucket.all_reduce(average=True)
             opt.step()

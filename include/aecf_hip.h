@@ -1437,6 +1437,53 @@ int aecf_mlmetrics_finalize(int64_t n_all, int32_t classes, int64_t row_offset, 
                             const int32_t* class_counts, const int32_t* counts, double* shares, const void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---- multi-label classification loss: binary cross-entropy, focal and asymmetric loss as one elementwise formula (replaces the
+ * reference example's torch criterion, xrays/train_xrays_example.py:327 nn.BCEWithLogitsLoss(), applied at :366 and :374; the
+ * weights, the focusing exponents, the margin, the smoothing and the unknown labels are build-defined) ----
+ * logits [n,classes] row-major, AECF_F32 / AECF_BF16 / AECF_F16, read as stored; labels [n,classes] of label_dtype: an aecf_dtype
+ * value, AECF_MLLOSS_U8 (torch bool / uint8) or AECF_MLLOSS_I8.  With s = sigmoid(x), t' = t (1 - eps) + eps / 2,
+ * q = max(s - margin, 0), a = pos_scale[c] and b = neg_scale[c] (float32 [classes], NULL: 1):
+ *   l     = - a t' (1 - s)^gamma_pos log s  -  b (1 - t') q^gamma_neg log(1 - q)
+ *   dl/dx = - a t' (1 - s)^gamma_pos [ (1 - s) - gamma_pos s log s ]
+ *           - b (1 - t') s (1 - s) [ gamma_neg q^(gamma_neg - 1) log(1 - q) - q^gamma_neg / (1 - q) ]
+ * with p^0 = 1 for every p.  Where s - margin <= 0 in float32 the second term and its gradient are exact zeros.  Float32
+ * arithmetic: e = exp(-|x|), l1p = log1p(e), r = 1 / (1 + e); s and 1 - s are r and e r (by the sign of x), -log s and
+ * -log(1 - s) are max(-+x, 0) + l1p, powers are exp(gamma log(.)) with the exponent-0 case exactly 1, and with a margin 1 - q is
+ * (1 - s) + margin.  A term whose coefficient a t' or b (1 - t') is 0 is an exact 0 whatever the logit holds.
+ * UNKNOWN targets: floating point: NaN or < 0; AECF_MLLOSS_I8: < 0 (other non-zero -> 1); AECF_MLLOSS_U8: none (non-zero -> 1).
+ * An unknown element adds nothing, is not counted, and its gradient is an exact zero by select: its logit reaches no output.
+ * On a valid element a +-inf logit gives the limit of the formula, a NaN logit a NaN loss and a NaN gradient there only.
+ *   forward:  two launches.  stats float64 [2][classes] = loss sums | valid counts per class; totals, 24 bytes: float64 sum of
+ *             the loss, float64 N (valid elements), float32 reduced loss (AECF_MLLOSS_MEAN: sum / N, 0 where N == 0;
+ *             AECF_MLLOSS_SUM: sum), one zero float32.  Per-thread float32 sums over the rows a thread owns, float64 above them in
+ *             a fixed order, no atomics: the same bits on every run.
+ *   backward: one launch, recomputes the element from (logits, labels) and stores dlogits [n,classes] of dtype =
+ *             dl/dx * scale, rounded once; scale = grad_out[0] (float32 on the device, NULL: 1) * factor, divided by totals' N for
+ *             AECF_MLLOSS_MEAN (0 where N == 0).  Reads only N of totals, so a caller that sums stats over ranks hands over the
+ *             global N.
+ * Workspace (forward), with nrb0 = min(max(ceil(n classes / 16384), 1), min(1024, max(1, 2^20 / classes))),
+ * rows_pb = ceil(n / nrb0) and nrb = ceil(n / rows_pb): float64 [nrb][classes] | int32 [nrb][classes], each rounded up to 256
+ * bytes.  16-byte loads and stores where classes is a multiple of the 16-byte vector of the logits and the pointers are 16-byte
+ * aligned, else element accesses.  Served: 1 <= classes <= 4096, n classes <= 2^30; outside them aecf_mlloss_workspace_bytes
+ * answers 0 and the calls AECF_ERR_UNSUPPORTED.  Caller-owned buffers, a stream argument, no allocation, no synchronisation,
+ * nothing read on the host.  Checks before any pointer is read: n, classes <= 0, a gamma that is negative or not finite, margin or
+ * label_smoothing outside [0, 1), a reduction outside the two, a factor that is not finite (AECF_ERR_BAD_DIMS), then the limits
+ * and the two dtype codes (AECF_ERR_UNSUPPORTED), then NULL pointers (AECF_ERR_NULL_POINTER), then the workspace size
+ * (AECF_ERR_WORKSPACE). */
+#define AECF_MLLOSS_U8 3
+#define AECF_MLLOSS_I8 4
+#define AECF_MLLOSS_MEAN 0
+#define AECF_MLLOSS_SUM 1
+size_t aecf_mlloss_workspace_bytes(int64_t n, int32_t classes);             /* 0: shape not served */
+int aecf_mlloss_forward(int64_t n, int32_t classes, int32_t dtype, int32_t label_dtype, const void* logits, const void* labels,
+                        const float* pos_scale, const float* neg_scale, float gamma_pos, float gamma_neg, float margin,
+                        float label_smoothing, int32_t reduction, double* stats, double* totals, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int aecf_mlloss_backward(int64_t n, int32_t classes, int32_t dtype, int32_t label_dtype, const void* logits, const void* labels,
+                         const float* pos_scale, const float* neg_scale, float gamma_pos, float gamma_neg, float margin,
+                         float label_smoothing, int32_t reduction, const double* totals, const float* grad_out, float factor,
+                         void* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
