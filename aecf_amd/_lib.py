@@ -22,6 +22,10 @@ AECF_MLLOSS_U8 = 3          # aecf_mlloss_*: label codes beside the aecf_dtype v
 AECF_MLLOSS_I8 = 4
 AECF_MLLOSS_MEAN = 0        # aecf_mlloss_*: reduction
 AECF_MLLOSS_SUM = 1
+AECF_MLCAL_MAX_BINS = 32    # aecf_mlcal_*: bins at most, and the fit's modes
+AECF_MLCAL_TEMPERATURE = 0
+AECF_MLCAL_CLASS_TEMPERATURE = 1
+AECF_MLCAL_PLATT = 2
 AECF_SETS_OVERLAP = 0
 AECF_SETS_JACCARD = 1
 AECF_PRECISE = 1
@@ -357,6 +361,14 @@ _SYMBOLS = [
     ("aecf_mlloss_backward", c_int,
      [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int32,
       c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    # multi-label calibration: reliability bins + Brier + NLL per class, the Newton sums of a scaling fit and its damped step
+    ("aecf_mlcal_workspace_bytes", c_size_t, [c_int64, c_int32, c_int32]),
+    ("aecf_mlcal_stats", c_int,
+     [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t,
+      c_void_p]),
+    ("aecf_mlcal_fit_sums", c_int,
+     [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("aecf_mlcal_fit_update", c_int, [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 ]
 SYMBOL_NAMES = [s[0] for s in _SYMBOLS]
 

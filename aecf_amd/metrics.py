@@ -22,6 +22,7 @@ iff non-zero); a NaN logit is an invalid entry of its class -- in no count, repo
 from __future__ import annotations
 
 import math
+from typing import Optional
 
 import torch
 
@@ -29,7 +30,8 @@ from . import _lib, dp
 from .layer import _POOL_DTYPES, _ptr, _require_device, _stream
 from .losses import _all_rows, _row_ranges
 
-__all__ = ["multilabel_metrics"]
+__all__ = ["multilabel_metrics"]         # (pinned by tests/test_metrics_cpu.py; multilabel_calibration and fit_calibration, below,
+#                                          are public all the same)
 
 
 def _labels_u8(labels: torch.Tensor) -> torch.Tensor:
@@ -126,3 +128,205 @@ def _close(shares: torch.Tensor, class_counts: torch.Tensor) -> dict:
     return dict(ap=ap, auroc=auroc, f1=f1, n_pos=n_pos, n_invalid=n_invalid,
                 map=mean_over(ap, has_pos, 0.0), macro_auroc=mean_over(auroc, both, float("nan")),
                 macro_f1=mean_over(f1, f1 > 0, 0.0))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Calibration: reliability bins (ECE / MCE), Brier score and NLL under a per-class scale and bias, and the fit of that scaling
+# (aecf_mlcal_stats / _fit_sums / _fit_update, include/aecf_hip.h "multi-label calibration").  The reference names calibration
+# as the property its fusion layer keeps when modalities are missing; this is what measures it.
+# ---------------------------------------------------------------------------------------------------------------------------
+
+_CAL_MODES = {"temperature": _lib.AECF_MLCAL_TEMPERATURE, "class_temperature": _lib.AECF_MLCAL_CLASS_TEMPERATURE,
+              "platt": _lib.AECF_MLCAL_PLATT}
+_CAL_FIT_ROWS = 9           # L | g1 | g0 | h11 | h01 | h00 | n_used | used positives | n_skipped
+_CAL_STATE_ROWS = 12        # accepted scale | bias | L | lambda | g1 | g0 | h11 | h01 | h00 | phase | first L | accepted steps
+
+
+def calibration_edges(n_bins: int):
+    """The ``n_bins - 1`` inner edges of equal-width probability bins in logit space, ``float32(log(j / (n_bins - j)))`` with
+    the logarithm in float64, as the ctypes array the library takes (None for one bin)."""
+    import ctypes
+    if n_bins == 1:
+        return None
+    return (ctypes.c_float * (n_bins - 1))(*[math.log(j / (n_bins - j)) for j in range(1, n_bins)])
+
+
+def _check_pair(logits: torch.Tensor, labels: torch.Tensor, what: str) -> None:
+    from .losses import _MLLOSS_LABEL_KINDS
+    _require_device(logits, "logits")
+    _require_device(labels, "labels")
+    if logits.dim() != 2 or labels.shape != logits.shape:
+        raise ValueError(f"{what} expects logits and labels of one shape [n, C], got {tuple(logits.shape)} and "
+                         f"{tuple(labels.shape)}")
+    if logits.dtype not in _POOL_DTYPES:
+        raise TypeError(f"aecf_amd: {what} takes float32, bfloat16 or float16 logits (nothing is rounded on the way in), got "
+                        f"{logits.dtype}")
+    if labels.dtype not in _MLLOSS_LABEL_KINDS:
+        raise TypeError(f"aecf_amd: {what} takes float32, bfloat16, float16, bool, uint8 or int8 labels, got {labels.dtype}")
+    if labels.device != logits.device:
+        raise ValueError(f"aecf_amd: the labels live on {labels.device}, the logits on {logits.device}")
+    if logits.shape[1] < 1:
+        raise ValueError(f"aecf_amd: {what} needs at least one class")
+
+
+def _cal_inputs(logits: torch.Tensor, labels: torch.Tensor):
+    from .losses import _MLLOSS_LABEL_KINDS
+    x, y = logits.detach(), labels.detach()
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if not y.is_contiguous():
+        y = y.contiguous()
+    kinds = (_POOL_DTYPES[x.dtype], _MLLOSS_LABEL_KINDS[labels.dtype])
+    if y.dtype == torch.bool:
+        y = y.view(torch.uint8)
+    return x, y, kinds
+
+
+def _class_param(value, name: str, C: int, device) -> Optional[torch.Tensor]:
+    """``scale`` / ``bias`` as a float32 [C] device tensor: None stays None, a number fills, a tensor is taken as it is"""
+    if value is None:
+        return None
+    if isinstance(value, torch.Tensor):
+        if value.dim() != 1 or value.shape[0] != C:
+            raise ValueError(f"aecf_amd: {name} must hold one value per class, [{C}], got shape {tuple(value.shape)}")
+        if not value.dtype.is_floating_point:
+            raise TypeError(f"aecf_amd: a tensor {name} must be floating point, got {value.dtype}")
+        return value.detach().to(device=device, dtype=torch.float32).contiguous()
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise TypeError(f"aecf_amd: {name} must be None, a Python number or a [C] tensor, got {type(value).__name__}")
+    return torch.full((C,), float(value), dtype=torch.float32, device=device)
+
+
+def multilabel_calibration(logits: torch.Tensor, labels: torch.Tensor, n_bins: int = 15, scale=None, bias=None, group=None) -> dict:
+    """Calibration of ``sigmoid(logits * scale + bias)`` [n, C] (float32, bfloat16 or float16 logits on a ROCm device, read as
+    stored) against ``labels`` [n, C] (``multilabel_loss``'s kinds and rule for unknown targets: a floating-point NaN or value
+    < 0, a negative int8), global over the rows of every rank of ``group``.  ``scale`` / ``bias``: None, a number, or a float32
+    [C] device tensor (what ``fit_calibration`` returns).  The bins are ``n_bins`` (1 .. 32) equal-width probability bins, taken
+    in logit space: an element falls into bin ``#{j : z > float32(log(j / (n_bins - j)))}``, an element on an edge into the lower
+    bin -- sklearn's ``calibration_curve(strategy="uniform")`` without the rounding of a float32 sigmoid.  A NaN logit on a known
+    target is an invalid entry: counted in ``n_invalid``, in nothing else.
+
+    Returns a dict of device tensors, the same on every rank:
+
+    ``ece``, ``mce``, ``brier``, ``nll``            0-dim float64, POOLED: every valid (row, class) element as one binary problem;
+                                                    ece = sum_k |conf_k - pos_k| / N, mce = max over the non-empty bins of
+                                                    |conf_k - pos_k| / count_k.  NaN without a valid element.
+    ``ece_per_class`` .. ``nll_per_class``          float64 [C], the same per class; NaN for a class without a valid entry.
+    ``macro_ece``, ``macro_brier``, ``macro_nll``   means over the classes with a valid entry (NaN if there is none).
+    ``bin_count``, ``bin_pos``, ``bin_conf``        [C, n_bins]: the reliability diagram (int64, int64, float64 sums of p).
+    ``n_valid``, ``n_pos``, ``n_invalid``           int64 [C].
+
+    One pass of the library over this rank's OWN rows (nothing is gathered), ONE all-reduce of the float64 [3 n_bins + 5, C]
+    block, float64 torch to close.  Shards may be uneven, empty or fully unknown.  One rank reads nothing on the host: the call
+    captures into a graph.  Unserved shapes raise NotImplementedError."""
+    _check_pair(logits, labels, "multilabel_calibration")
+    if isinstance(n_bins, bool) or not isinstance(n_bins, int) or not 1 <= n_bins <= _lib.AECF_MLCAL_MAX_BINS:
+        raise ValueError(f"aecf_amd: multilabel_calibration needs n_bins in 1 .. {_lib.AECF_MLCAL_MAX_BINS}, got {n_bins!r}")
+    rows, C = logits.shape
+    dev = logits.device
+    lib = _lib.load()
+    with torch.no_grad():
+        sc, bi = _class_param(scale, "scale", C, dev), _class_param(bias, "bias", C, dev)
+        x, y, kinds = _cal_inputs(logits, labels)
+        stats = torch.empty(3 * n_bins + 5, C, dtype=torch.float64, device=dev)
+        if rows == 0:                       # an empty shard: nothing to launch, its block is zeros
+            stats.zero_()
+        else:
+            ws_bytes = lib.aecf_mlcal_workspace_bytes(rows, C, n_bins)
+            if ws_bytes == 0:
+                raise NotImplementedError(f"aecf_amd: multilabel_calibration serves C <= 4096 and n * C <= 2**30 per rank, got "
+                                          f"{rows} x {C}")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.aecf_mlcal_stats(rows, C, *kinds, _ptr(x), _ptr(y), _ptr(sc), _ptr(bi), n_bins, calibration_edges(n_bins),
+                                            _ptr(stats), _ptr(ws), ws_bytes, _stream()), "aecf_mlcal_stats")
+        if dp.world_info(group)[1] > 1:
+            torch.distributed.all_reduce(stats, group=group)
+        return _close_calibration(stats, n_bins)
+
+
+def _close_calibration(stats: torch.Tensor, B: int) -> dict:
+    """The closing values from the summed block [3 B + 5, C]: float64, selects in place of divisions by zero, no host read"""
+    f64 = torch.float64
+    dev = stats.device
+    cnt, pos, conf = stats[0:B], stats[B:2 * B], stats[2 * B:3 * B]
+    brier, nll, n_invalid, n_valid, n_pos = (stats[3 * B + k] for k in range(5))
+    zero, one = torch.zeros((), dtype=f64, device=dev), torch.ones((), dtype=f64, device=dev)
+    nan = torch.full((), float("nan"), dtype=f64, device=dev)
+
+    def close(cnt, pos, conf, brier, nll, n):
+        has = n > 0
+        n1 = torch.where(has, n, one)
+        gap = (conf - pos).abs()
+        filled = cnt > 0
+        worst = torch.where(filled, gap / torch.where(filled, cnt, one), zero).max(0).values
+        return (torch.where(has, gap.sum(0) / n1, nan), torch.where(has, worst, nan), torch.where(has, brier / n1, nan),
+                torch.where(has, nll / n1, nan))
+
+    ece_c, mce_c, brier_c, nll_c = close(cnt, pos, conf, brier, nll, n_valid)
+    ece, mce, brier_p, nll_p = close(cnt.sum(1), pos.sum(1), conf.sum(1), brier.sum(), nll.sum(), n_valid.sum())
+    has = n_valid > 0
+    k = has.sum()
+
+    def macro(values):
+        m = torch.where(has, values, zero).sum() / torch.where(k > 0, k, torch.ones_like(k)).to(f64)
+        return torch.where(k > 0, m, nan)
+
+    i64 = torch.int64
+    return dict(ece=ece, mce=mce, brier=brier_p, nll=nll_p, ece_per_class=ece_c, mce_per_class=mce_c, brier_per_class=brier_c,
+                nll_per_class=nll_c, macro_ece=macro(ece_c), macro_brier=macro(brier_c), macro_nll=macro(nll_c),
+                bin_count=cnt.t().to(i64), bin_pos=pos.t().to(i64), bin_conf=conf.t().contiguous(),
+                n_valid=n_valid.to(i64), n_pos=n_pos.to(i64), n_invalid=n_invalid.to(i64))
+
+
+def fit_calibration(logits: torch.Tensor, labels: torch.Tensor, mode: str = "temperature", max_iter: int = 32, group=None) -> dict:
+    """Fit the scaling ``z = x * scale + bias`` that minimises the NLL of ``sigmoid(z)`` against ``labels`` over the rows of
+    every rank of ``group`` (temperature scaling, Guo et al. 2017).  ``mode``: ``"temperature"`` -- ONE scale for all classes
+    (T = 1 / scale); ``"class_temperature"`` -- a scale per class; ``"platt"`` -- a scale and a bias per class.  The fit uses
+    the valid elements with a finite logit.  It is a damped Newton iteration on the device (include/aecf_hip.h, "optimiser
+    rule"): exactly ``max_iter`` rounds of (sums pass, all-reduce of the float64 [9, C] sums when there is a group, one update
+    launch), no host read and no data-dependent stop, so the loop captures on one rank and every rank holds the same bits.
+
+    Returns device tensors: ``scale``, ``bias`` float32 [C] -- the last ACCEPTED parameters, what ``multilabel_calibration``
+    takes; ``temperature`` float64 [C] = 1 / scale; per problem ([1] for ``"temperature"``, else [C]) ``fitted`` (False: no used
+    element, no positive or no negative -- scale 1, bias 0), ``converged`` (an accepted step at most 2**-20 max(1, |theta|)),
+    ``nll_before`` and ``nll_after`` (float64 SUMS over the used elements: at scale 1, bias 0, and the smallest of the accepted
+    trials -- a trial is accepted while its sum is not above that by more than 2**-14 of it, the float32 noise of two sums, so
+    the returned parameters' own sum may exceed ``nll_after`` by that much); ``n_used`` and ``n_skipped`` int64 [C]
+    (``n_skipped``: +-inf logits on known targets)."""
+    _check_pair(logits, labels, "fit_calibration")
+    if mode not in _CAL_MODES:
+        raise ValueError(f"aecf_amd: fit_calibration fits 'temperature', 'class_temperature' or 'platt', got {mode!r}")
+    if isinstance(max_iter, bool) or not isinstance(max_iter, int) or max_iter < 1:
+        raise ValueError(f"aecf_amd: fit_calibration needs max_iter >= 1, got {max_iter!r}")
+    rows, C = logits.shape
+    dev = logits.device
+    lib = _lib.load()
+    with torch.no_grad():
+        x, y, kinds = _cal_inputs(logits, labels)
+        ws_bytes = 0
+        if rows > 0:
+            ws_bytes = lib.aecf_mlcal_workspace_bytes(rows, C, 1)
+            if ws_bytes == 0:
+                raise NotImplementedError(f"aecf_amd: fit_calibration serves C <= 4096 and n * C <= 2**30 per rank, got {rows} x {C}")
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        sums = torch.zeros(_CAL_FIT_ROWS, C, dtype=torch.float64, device=dev)
+        state = torch.zeros(_CAL_STATE_ROWS, C, dtype=torch.float64, device=dev)
+        scale_eval, scale = (torch.ones(C, dtype=torch.float32, device=dev) for _ in range(2))
+        bias_eval, bias = (torch.zeros(C, dtype=torch.float32, device=dev) for _ in range(2))
+        world = dp.world_info(group)[1]
+        st = _stream()
+        for _ in range(max_iter):
+            if rows > 0:
+                _lib.check(lib.aecf_mlcal_fit_sums(rows, C, *kinds, _ptr(x), _ptr(y), _ptr(scale_eval), _ptr(bias_eval), _ptr(sums),
+                                                   _ptr(ws), ws_bytes, st), "aecf_mlcal_fit_sums")
+            if world > 1:
+                if rows == 0:
+                    sums.zero_()
+                torch.distributed.all_reduce(sums, group=group)
+            _lib.check(lib.aecf_mlcal_fit_update(C, _CAL_MODES[mode], _ptr(sums), _ptr(state), _ptr(scale_eval), _ptr(bias_eval),
+                                                 _ptr(scale), _ptr(bias), st), "aecf_mlcal_fit_update")
+        P = 1 if mode == "temperature" else C
+        phase = state[9, :P]
+        return dict(scale=scale, bias=bias, temperature=1.0 / scale.to(torch.float64), fitted=phase != 3.0, converged=phase == 2.0,
+                    nll_before=state[10, :P].clone(), nll_after=state[2, :P].clone(), n_used=sums[6].to(torch.int64),
+                    n_skipped=sums[8].to(torch.int64))

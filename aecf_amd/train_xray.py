@@ -9,6 +9,7 @@ of ``train_both_models`` / ``main`` in ``xrays/train_xrays_example.py:312-427, 7
     python -m aecf_amd.train_xray --ema-decay 0.999                                 # + validation of the averaged weights
     python -m aecf_amd.train_xray --full-metrics                                    # + tie-exact mAP, AUROC, macro F1, all ranks
     python -m aecf_amd.train_xray --loss asymmetric --pos-weight auto               # the library's multi-label loss, class balance
+    python -m aecf_amd.train_xray --calibration --calibrate temperature             # + ECE, Brier, NLL; a temperature fit at the end
 
 The reference trains on precomputed CLIP features of a chest X-ray set that is not part of its repository
 (``.MISSING_LARGE_BLOBS``); ``--data train.pt,val.pt`` loads such files (dicts with image / text / labels), otherwise a
@@ -17,7 +18,10 @@ modalities, so that the fusion has something to learn).  Plots and the baseline 
 reporting code outside the path and are not rebuilt; its sklearn metrics (``calculate_metrics``, ref :260-295) are served by
 ``--full-metrics`` through ``aecf_amd.metrics.multilabel_metrics``, every rank evaluating its shard of the validation set.
 ``--loss`` / ``--pos-weight auto`` replace the torch criterion (ref :327, 366, 374) by ``aecf_amd.losses.MultilabelLoss`` on the
-logits as the model leaves them; with neither flag the torch ``BCEWithLogitsLoss`` line runs as before.
+logits as the model leaves them; with neither flag the torch ``BCEWithLogitsLoss`` line runs as before.  ``--calibration``
+adds the pooled ECE, Brier score and NLL of the three modality plans to every epoch's row (``aecf_amd.metrics.
+multilabel_calibration``, every rank on its shard); ``--calibrate MODE`` fits a scaling on the validation logits with all
+modalities present after the last epoch (``fit_calibration``) and reports the three plans' ECE and NLL before and after it.
 """
 from __future__ import annotations
 
@@ -31,7 +35,7 @@ import torch.distributed as dist
 
 from . import dp
 from .losses import MultilabelLoss, class_balance_weights
-from .metrics import multilabel_metrics
+from .metrics import fit_calibration, multilabel_calibration, multilabel_metrics
 from .optim import EmaModel, FusedAdamW
 from .xray import AECFModel
 
@@ -106,6 +110,39 @@ def _full_metric_rows(prefix: str, model: AECFModel, image, text, labels, rank: 
     return row
 
 
+PLANS = (("none", ""), ("images", "_no_images"), ("texts", "_no_texts"))
+
+
+@torch.no_grad()
+def shard_logits(model: AECFModel, image, text, labels, drop: str, rank: int, world: int, batch: int = 4096):
+    """this rank's ``dp.shard_bounds`` rows of the validation set through the model: (logits in the model's dtype, labels)"""
+    model.eval()
+    lo, hi = dp.shard_bounds(image.shape[0], rank, world)
+    outs = []
+    for i in range(lo, hi, batch):
+        im, tx = image[i:min(i + batch, hi)], text[i:min(i + batch, hi)]
+        if drop == "images":
+            im = torch.zeros_like(im)
+        elif drop == "texts":
+            tx = torch.zeros_like(tx)
+        outs.append(model(im, tx))
+    logits = torch.cat(outs) if outs else torch.empty(0, labels.shape[1], dtype=next(model.parameters()).dtype, device=image.device)
+    return logits, labels[lo:hi]
+
+
+def _calibration_rows(prefix: str, model: AECFModel, image, text, labels, rank: int, world: int, scale=None, bias=None,
+                      names=("ece", "brier", "nll"), tag: str = "") -> dict:
+    """pooled calibration values of the three modality plans, a collective: every rank scores its shard"""
+    row = {}
+    group = dist.group.WORLD if world > 1 else None
+    for drop, suffix in PLANS:
+        logits, y = shard_logits(model, image, text, labels, drop, rank, world)
+        m = multilabel_calibration(logits, y, scale=scale, bias=bias, group=group)
+        for name in names:
+            row[f"{prefix}val_{name}{tag}{suffix}"] = float(m[name]) if rank == 0 else None
+    return row
+
+
 LOSS_FORMS = {"bce": (0.0, 0.0, 0.0), "focal": (2.0, 2.0, 0.0), "asymmetric": (0.0, 4.0, 0.05)}     # gamma+, gamma-, margin
 
 
@@ -135,6 +172,12 @@ def main(argv=None):
                          "(gamma- 4, margin 0.05); unknown labels (NaN or < 0) are left out.  Default: torch's BCEWithLogitsLoss")
     ap.add_argument("--pos-weight", choices=("auto",), default=None,
                     help="auto: per-class n_neg / n_pos of the training labels as pos_weight (implies --loss bce if none is given)")
+    ap.add_argument("--calibration", action="store_true",
+                    help="also report the pooled ECE (15 bins), Brier score and NLL of the validation logits (val_ece, val_brier, "
+                         "val_nll and their _no_images / _no_texts forms), evaluated by every rank on its shard")
+    ap.add_argument("--calibrate", choices=("temperature", "class_temperature", "platt"), default=None,
+                    help="after the last epoch fit this scaling on the validation logits with all modalities present and report "
+                         "the three plans' ECE and NLL before and after it, and the fitted temperature")
     args = ap.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -248,11 +291,29 @@ def main(argv=None):
                 full.update(_full_metric_rows("ema_", ema.module, v_image, v_text, v_labels, rank, world))
             if rank == 0:
                 row.update(full)
+        if args.calibration:                                                # collective as well
+            cal = _calibration_rows("", model, v_image, v_text, v_labels, rank, world)
+            if rank == 0:
+                row.update(cal)
         if rank == 0:
             print(json.dumps(row), flush=True)
         history.append(row)
         if world > 1:
             dist.barrier()
+    if args.calibrate:                                                      # post-hoc calibration: fit once, score the three plans
+        logits, y = shard_logits(model, v_image, v_text, v_labels, "none", rank, world)
+        fit = fit_calibration(logits, y, mode=args.calibrate, group=dist.group.WORLD if world > 1 else None)
+        row = dict(calibrate=args.calibrate)
+        row.update(_calibration_rows("", model, v_image, v_text, v_labels, rank, world, names=("ece", "nll")))
+        row.update(_calibration_rows("", model, v_image, v_text, v_labels, rank, world, scale=fit["scale"], bias=fit["bias"],
+                                     names=("ece", "nll"), tag="_calibrated"))
+        if rank == 0:
+            row.update(temperature=[float(v) for v in fit["temperature"]], bias=[float(v) for v in fit["bias"]],
+                       fitted=[bool(v) for v in fit["fitted"]], converged=[bool(v) for v in fit["converged"]])
+            print(json.dumps(row), flush=True)
+            if args.calibrate == "temperature":
+                print(f"fitted temperature T = {row['temperature'][0]:.6f}", flush=True)
+        history.append(row)
     if rank == 0 and args.save:
         torch.save({"aecf_state_dict": model.state_dict(), "history": history}, args.save)
     if world > 1:

@@ -1484,6 +1484,77 @@ int aecf_mlloss_backward(int64_t n, int32_t classes, int32_t dtype, int32_t labe
                          float label_smoothing, int32_t reduction, const double* totals, const float* grad_out, float factor,
                          void* dlogits, void* stream);
 
+/* ---- multi-label calibration: reliability bins (ECE / MCE), Brier score and NLL of logits [n,classes] under a per-class scale
+ * and bias, and the fit of that scaling by minimising the NLL (temperature scaling after Guo et al. 2017; Platt scaling per
+ * class).  The reference names calibration as the property its fusion layer keeps and measures none of it; the statistics, the
+ * bins in logit space and the optimiser are build-defined ----
+ * logits [n,classes] row-major, AECF_F32 / AECF_BF16 / AECF_F16, read as stored; labels [n,classes] of label_dtype with the label
+ * kinds and the UNKNOWN rule of aecf_mlloss_* (floating point: NaN or < 0; AECF_MLLOSS_I8: < 0; AECF_MLLOSS_U8: none).  A known
+ * target is positive iff non-zero.  An element is VALID iff its target is known and its logit is not NaN.  A NaN logit on a known
+ * target is counted in n_invalid[c] and reaches nothing else; an unknown target's logit reaches no output.  Exclusions are
+ * selects, never products with 0.
+ * Calibrated logit: z = x scale[c] + bias[c] in float32 (float32 [classes] on the device, either may be NULL: scale 1, bias 0),
+ * the product and the sum rounded one after the other, never an fma; with both NULL z = x and nothing is multiplied.  +-inf
+ * gives the limits (p = 1 / 0, NLL 0 or inf).  (A z that is NaN though x is not -- inf 0, inf - inf -- makes its class's sums NaN.)
+ * Bin: edges is a HOST array of bins - 1 ascending float32 values e_1 .. e_{bins-1} (1 <= bins <= AECF_MLCAL_MAX_BINS; it is
+ * copied into the launch arguments and may be NULL for bins == 1); the bin of an element is #{ j : z > e_j }, so an element on
+ * an edge belongs to the lower bin.  Equal-width probability bins are e_j = float32(log(j / (bins - j))).
+ * Per element, float32, aecf_mlloss's forms: e = exp(-|z|), l1p = log1p(e), r = 1 / (1 + e); p = sigmoid(z) and 1 - p are r and
+ * e r by the sign of z, -log p and -log(1 - p) are max(-+z, 0) + l1p.  Brier term: (1 - p)^2 for a positive, p^2 for a negative;
+ * NLL term: -log p or -log(1 - p).
+ *   stats:    two launches.  stats float64 [3 bins + 5][classes], rows in this order: bin_count [bins] | bin_pos [bins] | bin_conf
+ *             [bins] (the sum of p over a bin's elements) | brier_sum | nll_sum | n_invalid | n_valid | n_pos.  Counts are exact
+ *             float64 integers, so one all-reduce of the block joins the ranks.
+ *   fit_sums: two launches.  Over the valid elements with a FINITE logit (a +-inf logit stays +-inf under every positive scale
+ *             and is left out), with s = sigmoid(z), y the target, w = s (1 - s) and x the stored logit as float32, sums float64
+ *             [9][classes] = L = sum nll | g1 = sum (s - y) x | g0 = sum (s - y) | h11 = sum w x^2 | h01 = sum w x | h00 = sum w |
+ *             n_used | n_used positives | n_skipped (the +-inf logits on known targets).  s - y is -(1 - p) or p, no subtraction.
+ *   Sums: per-thread float32 over the rows a thread owns, float64 above that in a fixed order (the threads of a class in row
+ *   order, the row blocks in order), no atomics: the same bits on every run; the integer rows are the same for any block, tile
+ *   or rank arrangement.
+ *   fit_update: one launch holding the optimiser, one lane per independent problem.  mode AECF_MLCAL_TEMPERATURE: ONE problem,
+ *             the classes' sums added in class order in float64, one scale written to all classes, bias 0 (T = 1 / scale);
+ *             AECF_MLCAL_CLASS_TEMPERATURE: a scale per class, bias 0; AECF_MLCAL_PLATT: a scale and a bias per class.
+ *             sums are those of the parameters in scale_eval / bias_eval (float32 [classes], what fit_sums was given); the call
+ *             overwrites them with the parameters to evaluate next and writes the last ACCEPTED parameters to scale_out /
+ *             bias_out.  state is float64 [12][classes], ZEROED by the caller before the first call (the shared temperature
+ *             uses column 0), rows: accepted scale | accepted bias | accepted L | lambda | accepted g1 | g0 | h11 | h01 | h00 |
+ *             phase (0 fresh, 1 running, 2 converged, 3 not fitted) | the first L | accepted steps.
+ * Optimiser rule: a Newton step damped in Levenberg-Marquardt fashion on the convex NLL.  First call: the evaluated parameters
+ * (the caller hands over scale 1, bias 0) are accepted; a problem without a used element, without a positive or without a
+ * negative among them is not fitted (phase 3: scale 1, bias 0 for good).  Later calls: a trial whose L does not exceed the
+ * accepted L by more than 2^-14 of it -- two L of float32 elements cannot be told apart more finely, and without the slack the
+ * last Newton steps, which lower L by less than that, would be refused -- is accepted and lambda divided by 10 (floor 1e-9);
+ * the accepted L kept in the state is the smallest L of an accepted trial.  If the step was at most 2^-20 max(1, |theta|) in
+ * every parameter the problem is converged and stops moving.  Any other trial (a NaN L too) is rejected: the accepted
+ * parameters and their sums stay, lambda is multiplied by 10 (at most 1e12).  The next trial is accepted - (H + lambda diag H)^-1 g, lambda starting at 1e-3, with H =
+ * [h11 h01; h01 h00] and g = (g1, g0) for AECF_MLCAL_PLATT and H = h11, g = g1 for the temperatures (no step where the damped
+ * matrix is not positive), clamped to scale in [1/64, 64] and bias in [-16, 16] and ROUNDED to float32: the fit evaluates z with
+ * the float32 values aecf_mlcal_stats later applies, and an unevaluated trial is never an output.
+ * Workspace (stats and fit_sums), with nrb0 = min(max(ceil(n classes / 16384), 1), min(1024, max(1, 2^19 / classes))),
+ * rows_pb = ceil(n / nrb0), nrb = ceil(n / rows_pb): float64 [nrb][max(3 bins + 5, 9)][classes], rounded up to 256 bytes; a
+ * workspace sized for bins serves fit_sums too.  16-byte loads where classes is a multiple of the logits' 16-byte vector and the
+ * pointers are 16-byte aligned (stats: 8-byte loads of 16-bit logits where bins > 8, element accesses where bins > 16 -- the
+ * bins of a thread's classes live in LDS), else element accesses.  Served: 1 <= classes <=
+ * 4096, n classes <= 2^30; outside them aecf_mlcal_workspace_bytes answers 0 and the calls AECF_ERR_UNSUPPORTED.  Caller-owned
+ * buffers, a stream argument, no allocation, no synchronisation, nothing read from the device on the host.  Checks before any
+ * launch: n, classes <= 0, bins outside 1 .. 32, a mode outside the three (AECF_ERR_BAD_DIMS), then the limits and the two dtype
+ * codes (AECF_ERR_UNSUPPORTED), then NULL pointers (AECF_ERR_NULL_POINTER; the edges are then read: a NaN or a descent among
+ * them is AECF_ERR_BAD_DIMS), then the workspace size (AECF_ERR_WORKSPACE). */
+#define AECF_MLCAL_MAX_BINS 32
+#define AECF_MLCAL_TEMPERATURE 0
+#define AECF_MLCAL_CLASS_TEMPERATURE 1
+#define AECF_MLCAL_PLATT 2
+size_t aecf_mlcal_workspace_bytes(int64_t n, int32_t classes, int32_t bins);            /* 0: shape or bins not served */
+int aecf_mlcal_stats(int64_t n, int32_t classes, int32_t dtype, int32_t label_dtype, const void* logits, const void* labels,
+                     const float* scale, const float* bias, int32_t bins, const float* edges, double* stats, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int aecf_mlcal_fit_sums(int64_t n, int32_t classes, int32_t dtype, int32_t label_dtype, const void* logits, const void* labels,
+                        const float* scale, const float* bias, double* sums, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int aecf_mlcal_fit_update(int32_t classes, int32_t mode, const double* sums, double* state, float* scale_eval, float* bias_eval,
+                          float* scale_out, float* bias_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
