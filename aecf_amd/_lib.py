@@ -361,6 +361,15 @@ _SYMBOLS = [
     ("aecf_mlloss_backward", c_int,
      [c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int32,
       c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    # fused classifier head: that loss of h W^T + bias and dh / dW / dbias on the streaming loop, nothing of size n x classes
+    ("aecf_mlhead_workspace_bytes", c_size_t, [c_int64, c_int32, c_int32]),
+    ("aecf_mlhead_forward", c_int,
+     [c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+      c_float, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("aecf_mlhead_backward", c_int,
+     [c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+      c_float, c_float, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+      c_size_t, c_void_p]),
     # multi-label calibration: reliability bins + Brier + NLL per class, the Newton sums of a scaling fit and its damped step
     ("aecf_mlcal_workspace_bytes", c_size_t, [c_int64, c_int32, c_int32]),
     ("aecf_mlcal_stats", c_int,

@@ -1716,6 +1716,68 @@ int aecf_mlloss_backward(int64_t n, int32_t classes, int32_t dtype, int32_t labe
     return launch_status();
 }
 
+// ---- fused classifier head (include/aecf_hip.h, "fused classifier head")
+
+namespace {
+
+// mlloss_check's order with the head's sizes and limits
+int mlhead_check(int64_t n, int32_t classes, int32_t k, int32_t dtype, int32_t label_dtype, float gamma_pos, float gamma_neg,
+                 float margin, float label_smoothing, int32_t reduction, float factor, int32_t flag, int32_t out_dtype) {
+    if (n <= 0 || classes <= 0 || k <= 0 || (flag != 0 && flag != 1)) return AECF_ERR_BAD_DIMS;
+    if (!(gamma_pos >= 0.0f) || !(gamma_neg >= 0.0f) || !__builtin_isfinite(gamma_pos) || !__builtin_isfinite(gamma_neg))
+        return AECF_ERR_BAD_DIMS;
+    if (!__builtin_isfinite(factor)) return AECF_ERR_BAD_DIMS;
+    if (!(margin >= 0.0f && margin < 1.0f) || !(label_smoothing >= 0.0f && label_smoothing < 1.0f)) return AECF_ERR_BAD_DIMS;
+    if (reduction != AECF_MLLOSS_MEAN && reduction != AECF_MLLOSS_SUM) return AECF_ERR_BAD_DIMS;
+    if (!mlhead_supported(n, classes, k)) return AECF_ERR_UNSUPPORTED;
+    if (dtype != AECF_BF16 || (out_dtype != AECF_BF16 && out_dtype != AECF_F32)) return AECF_ERR_UNSUPPORTED;
+    if (label_dtype < AECF_BF16 || label_dtype > AECF_MLLOSS_I8) return AECF_ERR_UNSUPPORTED;
+    return AECF_OK;
+}
+
+}  // namespace
+
+size_t aecf_mlhead_workspace_bytes(int64_t n, int32_t classes, int32_t k) {
+    if (n <= 0 || classes <= 0 || k <= 0 || !mlhead_supported(n, classes, k)) return 0;
+    return mlhead_workspace_bytes(n, classes, k);
+}
+
+int aecf_mlhead_forward(int64_t n, int32_t classes, int32_t k, int32_t dtype, int32_t label_dtype, const void* h, const void* w,
+                        const float* bias, const void* labels, const float* pos_scale, const float* neg_scale, float gamma_pos,
+                        float gamma_neg, float margin, float label_smoothing, int32_t reduction, int32_t want_grads, double* stats,
+                        double* totals, float* dw_unscaled, float* db_unscaled, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    const int st = mlhead_check(n, classes, k, dtype, label_dtype, gamma_pos, gamma_neg, margin, label_smoothing, reduction, 1.0f,
+                                want_grads, AECF_BF16);
+    if (st != AECF_OK) return st;
+    if (!h || !w || !labels || !stats || !totals || !workspace) return AECF_ERR_NULL_POINTER;
+    if (want_grads && (!dw_unscaled || !db_unscaled)) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < mlhead_workspace_bytes(n, classes, k)) return AECF_ERR_WORKSPACE;
+    launch_mlhead_forward(n, classes, k, label_dtype, h, w, bias, labels, pos_scale, neg_scale, gamma_pos, gamma_neg, margin,
+                          label_smoothing, reduction == AECF_MLLOSS_MEAN ? 1 : 0, want_grads, stats, totals, dw_unscaled,
+                          db_unscaled, workspace, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_mlhead_backward(int64_t n, int32_t classes, int32_t k, int32_t dtype, int32_t label_dtype, const void* h, const void* w,
+                         const float* bias, const void* labels, const float* pos_scale, const float* neg_scale, float gamma_pos,
+                         float gamma_neg, float margin, float label_smoothing, int32_t reduction, const double* totals,
+                         const float* grad_out, float factor, const float* dw_unscaled, const float* db_unscaled, int32_t dh_dtype,
+                         void* dh, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream) {
+    const int st = mlhead_check(n, classes, k, dtype, label_dtype, gamma_pos, gamma_neg, margin, label_smoothing, reduction, factor,
+                                0, dh_dtype);
+    if (st != AECF_OK) return st;
+    if (!totals) return AECF_ERR_NULL_POINTER;
+    if (dh && (!h || !w || !labels || !workspace)) return AECF_ERR_NULL_POINTER;
+    if ((dw && !dw_unscaled) || (db && !db_unscaled)) return AECF_ERR_NULL_POINTER;
+    if (dh && workspace_bytes < mlhead_workspace_bytes(n, classes, k)) return AECF_ERR_WORKSPACE;
+    if (!dh && !dw && !db) return AECF_OK;                          // nothing wanted: nothing launched
+    launch_mlhead_backward(n, classes, k, label_dtype, h, w, bias, labels, pos_scale, neg_scale, gamma_pos, gamma_neg, margin,
+                           label_smoothing, reduction == AECF_MLLOSS_MEAN ? 1 : 0, totals, grad_out, factor, dw_unscaled,
+                           db_unscaled, dh_dtype == AECF_F32 ? 1 : 0, dh, dw, db, workspace, (hipStream_t)stream);
+    return launch_status();
+}
+
 int aecf_route_build(int64_t rows, const uint8_t* present_a, const uint8_t* present_b, int32_t* route, int32_t* slot,
                      int32_t* index, int32_t* counts, void* stream) {
     if (rows <= 0 || rows > 0x7fffffff) return AECF_ERR_BAD_DIMS;

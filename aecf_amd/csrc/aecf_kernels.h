@@ -542,6 +542,22 @@ void launch_mlloss_backward(int64_t n, int classes, int dtype, int label_dtype, 
                             const float* pos_scale, const float* neg_scale, float gamma_pos, float gamma_neg, float margin, float eps,
                             int mean, const double* totals, const float* grad_out, float factor, void* dlogits, hipStream_t s);
 
+// Fused classifier head (aecf_mlhead_flash.hip): that loss of logits = h W^T + bias, and dh, dW, dbias, on the streaming loop of
+// aecf_flash_stream.h -- nothing of size n x classes exists.  forward: the CLS role (stationary classes, rows split), a combine
+// of the splits (stats, and with want_grads the unscaled float32 dW / dbias) and the totals; backward: the ROW role (stationary
+// rows, classes split) for dh where it is wanted, and the scaling of dW / dbias.  bf16 h [n, k] and w [classes, k].
+bool mlhead_supported(int64_t n, int classes, int k);
+size_t mlhead_workspace_bytes(int64_t n, int classes, int k);
+void launch_mlhead_forward(int64_t n, int classes, int k, int label_dtype, const void* h, const void* w, const float* bias,
+                           const void* labels, const float* pos_scale, const float* neg_scale, float gamma_pos, float gamma_neg,
+                           float margin, float eps, int mean, int want_grads, double* stats, double* totals, float* dw_unscaled,
+                           float* db_unscaled, void* workspace, hipStream_t s);
+void launch_mlhead_backward(int64_t n, int classes, int k, int label_dtype, const void* h, const void* w, const float* bias,
+                            const void* labels, const float* pos_scale, const float* neg_scale, float gamma_pos, float gamma_neg,
+                            float margin, float eps, int mean, const double* totals, const float* grad_out, float factor,
+                            const float* dw_unscaled, const float* db_unscaled, int dh_f32, void* dh, float* dw, float* db,
+                            void* workspace, hipStream_t s);
+
 // ---------------- presence routing (aecf_route.hip) ----------------
 void launch_route_build(int64_t rows, const uint8_t* pa, const uint8_t* pb, int32_t* route, int32_t* slot, int32_t* index,
                         int32_t* counts, hipStream_t s);

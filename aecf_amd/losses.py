@@ -2528,3 +2528,234 @@ def class_balance_weights(labels: torch.Tensor, group=None, max_weight: Optional
         if max_weight is not None:
             w = w.clamp(max=float(max_weight))
         return w.to(torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Fused classifier head: that loss of hidden @ W.T + b and all three gradients without the [n, C] logits
+# (aecf_mlhead_forward / _backward, include/aecf_hip.h "fused classifier head"); replaces classifier[3] of the reference
+# example's model together with its criterion.
+# ---------------------------------------------------------------------------------------------------------------------------
+
+MLHEAD_WIDTHS = (128, 256, 384, 512, 768, 1024)
+MLHEAD_MAX_CLASSES = 65536
+_MLHEAD_ALTERNATIVE = "use F.linear(hidden, weight, bias) with multilabel_loss"
+
+
+class _LinearMultilabelLoss(torch.autograd.Function):
+    """aecf_mlhead_forward (the CLS role over the rows, the combine of its splits, the totals) and aecf_mlhead_backward (the ROW
+    role for d hidden where it is wanted, the scaling of dW / dbias).  ``want_params``: the forward also forms the unscaled
+    float32 dW and dbias, which are all it saves beside the inputs and the 24-byte totals; the split slabs are transient.
+    Returns the reduced loss and the float64 [2, C] stats, global over ``group`` after ONE all-reduce of the stats."""
+
+    @staticmethod
+    def forward(ctx, hidden, weight, bias, targets, pos_scale, neg_scale, gamma_pos, gamma_neg, margin, eps, reduction, group,
+                want_params):
+        lib = _lib.load()
+        rows, K = hidden.shape
+        C = weight.shape[0]
+        dev = hidden.device
+        h, w, y = hidden.detach(), weight.detach(), targets.detach()
+        if not h.is_contiguous():
+            h = h.contiguous()
+        if not w.is_contiguous():
+            w = w.contiguous()
+        if not y.is_contiguous():
+            y = y.contiguous()
+        if y.dtype == torch.bool:
+            y = y.view(torch.uint8)
+        b = None
+        if bias is not None:
+            b = bias.detach()
+            if b.dtype != torch.float32:
+                b = b.to(torch.float32)                 # [C]: the kernels add the bias in float32
+            if not b.is_contiguous():
+                b = b.contiguous()
+        kinds = (_lib.AECF_BF16, _MLLOSS_LABEL_KINDS[targets.dtype])
+        opts = (float(gamma_pos), float(gamma_neg), float(margin), float(eps), _MLLOSS_REDUCTIONS[reduction])
+        world = dp.world_info(group)[1]
+        stats = torch.empty(2, C, dtype=torch.float64, device=dev)
+        totals = torch.empty(6, dtype=torch.float32, device=dev)     # the 24-byte record: float64 sum, float64 N, float32 loss, 0
+        dw_u = torch.empty(C, K, dtype=torch.float32, device=dev) if want_params else None
+        db_u = torch.empty(C, dtype=torch.float32, device=dev) if want_params else None
+        if rows == 0:                       # an empty shard: nothing to launch, its stats and gradient sums are zeros
+            stats.zero_()
+            totals.zero_()
+            if want_params:
+                dw_u.zero_()
+                db_u.zero_()
+        else:
+            ws_bytes = lib.aecf_mlhead_workspace_bytes(rows, C, K)
+            if ws_bytes == 0:
+                raise NotImplementedError(f"aecf_amd: linear_multilabel_loss does not serve {rows} x {C} x {K}; {_MLHEAD_ALTERNATIVE}")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.aecf_mlhead_forward(rows, C, K, *kinds, _ptr(h), _ptr(w), _ptr(b), _ptr(y), _ptr(pos_scale),
+                                               _ptr(neg_scale), *opts, 1 if want_params else 0, _ptr(stats), _ptr(totals),
+                                               _ptr(dw_u), _ptr(db_u), _ptr(ws), ws_bytes, _stream()), "aecf_mlhead_forward")
+        if world > 1:
+            torch.distributed.all_reduce(stats, group=group)
+            total, count = stats[0].sum(), stats[1].sum()
+            if reduction == "mean":
+                value = torch.where(count > 0, total / torch.where(count > 0, count, torch.ones_like(count)), torch.zeros_like(total))
+            else:
+                value = total
+            totals = torch.stack((total, count, torch.zeros_like(total)))
+            loss = value.to(torch.float32)
+        else:
+            loss = totals[4]
+        ctx.save_for_backward(h, w, b, y, pos_scale, neg_scale, totals, dw_u, db_u)
+        ctx.meta = (rows, C, K, kinds, opts, float(world), weight.dtype, None if bias is None else bias.dtype)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_loss, _d_stats):
+        lib = _lib.load()
+        h, w, b, y, pos_scale, neg_scale, totals, dw_u, db_u = ctx.saved_tensors
+        rows, C, K, kinds, opts, factor, w_dtype, b_dtype = ctx.meta
+        want_h, want_w, want_b = ctx.needs_input_grad[:3]
+        if (want_w or want_b) and dw_u is None:
+            raise RuntimeError("aecf_amd: linear_multilabel_loss was run without the parameter gradients (grad mode was off)")
+        dev = h.device
+        dh = torch.empty_like(h) if want_h else None
+        dw = torch.empty(C, K, dtype=torch.float32, device=dev) if want_w else None
+        db = torch.empty(C, dtype=torch.float32, device=dev) if want_b else None
+        if rows > 0 or want_w or want_b:
+            up = d_loss if d_loss.dtype == torch.float32 else d_loss.to(torch.float32)       # one element, read on the device
+            run_h = want_h and rows > 0
+            ws, ws_bytes = None, 0
+            if run_h:
+                ws_bytes = lib.aecf_mlhead_workspace_bytes(rows, C, K)
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.aecf_mlhead_backward(max(rows, 1), C, K, *kinds, _ptr(h), _ptr(w), _ptr(b), _ptr(y), _ptr(pos_scale),
+                                                _ptr(neg_scale), *opts, _ptr(totals), _ptr(up), factor, _ptr(dw_u), _ptr(db_u),
+                                                _lib.AECF_BF16, _ptr(dh) if run_h else None, _ptr(dw), _ptr(db), _ptr(ws),
+                                                ws_bytes, _stream()), "aecf_mlhead_backward")
+        if dw is not None and dw.dtype != w_dtype:
+            dw = dw.to(w_dtype)
+        if db is not None and db.dtype != b_dtype:
+            db = db.to(b_dtype)
+        return dh, dw, db, None, None, None, None, None, None, None, None, None, None
+
+
+def linear_multilabel_loss(hidden: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], targets: torch.Tensor, *,
+                           pos_weight=None, class_weight=None, alpha: Optional[float] = None, gamma_pos: float = 0.0,
+                           gamma_neg: float = 0.0, margin: float = 0.0, label_smoothing: float = 0.0, reduction: str = "mean",
+                           group=None, return_per_class: bool = False, _fold=_fold_scales):
+    """``multilabel_loss(F.linear(hidden, weight, bias), targets, ...)`` and its gradients with respect to ``hidden`` [n, K],
+    ``weight`` [C, K] (``nn.Linear``'s layout) and ``bias`` [C] or None, with nothing of size n x C ever allocated: the logits
+    z = hidden @ weight.T + bias live in registers, one streaming pass over the rows in the forward (which also forms dW and
+    dbias when grad mode is on and ``weight`` or ``bias`` requires grad) and one over the classes in the backward (only when
+    ``hidden`` requires grad -- a linear probe on frozen features is ONE pass per step).
+
+    Options, the folding of the weights, the rule for UNKNOWN targets, the reductions and the return values are those of
+    ``multilabel_loss``.  Arithmetic: z is the float32 accumulation of the bf16 products plus the bias in one float32 add, never
+    rounded to bfloat16 (``F.linear`` in bfloat16 would round it); the element is ``multilabel_loss``'s; dl/dz enters the two
+    gradient products rounded once to bfloat16, dbias sums it unrounded; ``weight.grad`` and ``bias.grad`` are float32 sums cast
+    once to the parameter's dtype.  No atomics: the same bits on every run.  Nothing is read on the host on one rank, so forward
+    + backward capture into a graph.  Data parallel (``group``): ``multilabel_loss``'s contract -- ONE all-reduce of the float64
+    [2, C] stats, the value is the global loss on every rank, all three gradients carry ``world / N`` for the averaging
+    collectives of ``dp``; shards may be uneven, empty or fully unknown.
+
+    Non-finite features are the caller's problem, as in any GEMM: a NaN row of ``hidden`` reaches ``weight.grad`` even when all
+    its targets are unknown, because the product forms 0 x NaN.
+
+    Served: bfloat16 ``hidden`` and ``weight`` on a ROCm device, K in {128, 256, 384, 512, 768, 1024}, C <= 65536, n < 2**31;
+    everything else raises NotImplementedError naming the limit -- there ``F.linear`` + ``multilabel_loss`` is the way."""
+    _require_device(hidden, "hidden")
+    _require_device(weight, "weight")
+    _require_device(targets, "targets")
+    if hidden.dim() != 2 or weight.dim() != 2 or hidden.shape[1] != weight.shape[1]:
+        raise ValueError(f"linear_multilabel_loss expects hidden [n, K] and weight [C, K], got {tuple(hidden.shape)} and "
+                         f"{tuple(weight.shape)}")
+    rows, K = hidden.shape
+    C = weight.shape[0]
+    if targets.dim() != 2 or tuple(targets.shape) != (rows, C):
+        raise ValueError(f"linear_multilabel_loss expects targets [n, C] = [{rows}, {C}], got {tuple(targets.shape)}")
+    if bias is not None:
+        _require_device(bias, "bias")
+        if bias.dim() != 1 or bias.shape[0] != C or not bias.dtype.is_floating_point:
+            raise ValueError(f"linear_multilabel_loss expects a floating-point bias [C] = [{C}], got {tuple(bias.shape)} {bias.dtype}")
+    for name, t in (("weight", weight), ("targets", targets), ("bias", bias)):
+        if t is not None and t.device != hidden.device:
+            raise ValueError(f"aecf_amd: the {name} lives on {t.device}, the hidden features on {hidden.device}")
+    if hidden.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16:
+        raise NotImplementedError(f"aecf_amd: linear_multilabel_loss serves bfloat16 hidden and weight only, got {hidden.dtype} and "
+                                  f"{weight.dtype}; {_MLHEAD_ALTERNATIVE}")
+    if targets.dtype not in _MLLOSS_LABEL_KINDS:
+        raise TypeError(f"aecf_amd: linear_multilabel_loss takes float32, bfloat16, float16, bool, uint8 or int8 targets, got {targets.dtype}")
+    if reduction not in _MLLOSS_REDUCTIONS:
+        raise ValueError(f"aecf_amd: linear_multilabel_loss reduces by 'mean' or 'sum' (there is no 'none'), got {reduction!r}")
+    gamma_pos, gamma_neg = _gamma(gamma_pos, "gamma_pos"), _gamma(gamma_neg, "gamma_neg")
+    margin = _unit_interval(margin, "margin")
+    eps = _unit_interval(label_smoothing, "label_smoothing")
+    if alpha is not None:
+        alpha = _unit_interval(alpha, "alpha", closed_top=True)
+    if C < 1:
+        raise ValueError("aecf_amd: linear_multilabel_loss needs at least one class")
+    if K not in MLHEAD_WIDTHS:
+        raise NotImplementedError(f"aecf_amd: linear_multilabel_loss serves K in {MLHEAD_WIDTHS}, got K = {K}; {_MLHEAD_ALTERNATIVE}")
+    if C > MLHEAD_MAX_CLASSES or rows >= 1 << 31:
+        raise NotImplementedError(f"aecf_amd: linear_multilabel_loss serves C <= {MLHEAD_MAX_CLASSES} and n < 2**31, got {rows} x {C}; "
+                                  f"{_MLHEAD_ALTERNATIVE}")
+    a, b = _fold(pos_weight, class_weight, alpha, C, hidden.device)
+    want_params = torch.is_grad_enabled() and (weight.requires_grad or (bias is not None and bias.requires_grad))
+    loss, stats = _LinearMultilabelLoss.apply(hidden, weight, bias, targets, a, b, gamma_pos, gamma_neg, margin, eps, reduction, group,
+                                              want_params)
+    if not return_per_class:
+        return loss
+    count = stats[1]
+    per_class = torch.where(count > 0, stats[0] / torch.where(count > 0, count, torch.ones_like(count)), torch.zeros_like(count))
+    return loss, per_class.to(torch.float32)
+
+
+class MultilabelHead(torch.nn.Module):
+    """A linear classifier head with its multi-label loss fused in: ``weight`` [num_classes, in_features] and ``bias`` are
+    initialised as ``nn.Linear`` initialises them and carry its state_dict keys, so the head and an ``nn.Linear`` load each
+    other's state.  ``forward(hidden)`` returns the logits (``F.linear``, for evaluation); ``loss(hidden, targets)`` is
+    ``linear_multilabel_loss`` with the options given here -- no logits exist.  ``from_linear(linear, **options)`` SHARES the
+    layer's parameter objects.  ``pos_weight`` / ``class_weight`` are float32 buffers outside the state_dict, and the module
+    owns its folded scale vectors as ``MultilabelLoss`` does, so the addresses a captured graph holds stay valid."""
+
+    def __init__(self, in_features: int, num_classes: int, bias: bool = True, *, pos_weight=None, class_weight=None,
+                 alpha: Optional[float] = None, gamma_pos: float = 0.0, gamma_neg: float = 0.0, margin: float = 0.0,
+                 label_smoothing: float = 0.0, reduction: str = "mean", group=None, device=None, dtype=None, _linear=None):
+        super().__init__()
+        if reduction not in _MLLOSS_REDUCTIONS:
+            raise ValueError(f"aecf_amd: linear_multilabel_loss reduces by 'mean' or 'sum' (there is no 'none'), got {reduction!r}")
+        self.gamma_pos, self.gamma_neg = _gamma(gamma_pos, "gamma_pos"), _gamma(gamma_neg, "gamma_neg")
+        self.margin = _unit_interval(margin, "margin")
+        self.label_smoothing = _unit_interval(label_smoothing, "label_smoothing")
+        self.alpha = None if alpha is None else _unit_interval(alpha, "alpha", closed_top=True)
+        self.reduction, self.group = reduction, group
+        linear = _linear if _linear is not None else torch.nn.Linear(in_features, num_classes, bias=bias, device=device, dtype=dtype)
+        self.in_features, self.num_classes = linear.in_features, linear.out_features
+        self.weight = linear.weight
+        self.bias = linear.bias
+        for name, value in (("pos_weight", pos_weight), ("class_weight", class_weight)):
+            if value is not None and not isinstance(value, torch.Tensor):
+                value = _class_vector(value, name, len(value), "cpu")
+            self.register_buffer(name, None if value is None else value.detach().to(torch.float32).clone(), persistent=False)
+        self._folds = {}                    # (buffers' identity and version, C, device) -> (pos_scale, neg_scale), never dropped
+
+    _fold = MultilabelLoss._fold
+
+    @classmethod
+    def from_linear(cls, linear: torch.nn.Linear, **options) -> "MultilabelHead":
+        if not isinstance(linear, torch.nn.Linear):
+            raise TypeError(f"aecf_amd: MultilabelHead.from_linear takes an nn.Linear, got {type(linear).__name__}")
+        return cls(linear.in_features, linear.out_features, linear.bias is not None, _linear=linear, **options)
+
+    def forward(self, hidden: torch.Tensor) -> torch.Tensor:
+        return torch.nn.functional.linear(hidden, self.weight, self.bias)
+
+    def loss(self, hidden: torch.Tensor, targets: torch.Tensor, return_per_class: bool = False):
+        return linear_multilabel_loss(hidden, self.weight, self.bias, targets, pos_weight=self.pos_weight,
+                                      class_weight=self.class_weight, alpha=self.alpha, gamma_pos=self.gamma_pos,
+                                      gamma_neg=self.gamma_neg, margin=self.margin, label_smoothing=self.label_smoothing,
+                                      reduction=self.reduction, group=self.group, return_per_class=return_per_class, _fold=self._fold)
+
+    def extra_repr(self) -> str:
+        return (f"in_features={self.in_features}, num_classes={self.num_classes}, bias={self.bias is not None}, "
+                f"gamma_pos={self.gamma_pos}, gamma_neg={self.gamma_neg}, margin={self.margin}, alpha={self.alpha}, "
+                f"label_smoothing={self.label_smoothing}, reduction={self.reduction!r}")

@@ -10,6 +10,7 @@ of ``train_both_models`` / ``main`` in ``xrays/train_xrays_example.py:312-427, 7
     python -m aecf_amd.train_xray --full-metrics                                    # + tie-exact mAP, AUROC, macro F1, all ranks
     python -m aecf_amd.train_xray --loss asymmetric --pos-weight auto               # the library's multi-label loss, class balance
     python -m aecf_amd.train_xray --calibration --calibrate temperature             # + ECE, Brier, NLL; a temperature fit at the end
+    python -m aecf_amd.train_xray --param-dtype bfloat16 --fused-head               # classifier[3] + loss in one call, no logits
 
 The reference trains on precomputed CLIP features of a chest X-ray set that is not part of its repository
 (``.MISSING_LARGE_BLOBS``); ``--data train.pt,val.pt`` loads such files (dicts with image / text / labels), otherwise a
@@ -18,7 +19,10 @@ modalities, so that the fusion has something to learn).  Plots and the baseline 
 reporting code outside the path and are not rebuilt; its sklearn metrics (``calculate_metrics``, ref :260-295) are served by
 ``--full-metrics`` through ``aecf_amd.metrics.multilabel_metrics``, every rank evaluating its shard of the validation set.
 ``--loss`` / ``--pos-weight auto`` replace the torch criterion (ref :327, 366, 374) by ``aecf_amd.losses.MultilabelLoss`` on the
-logits as the model leaves them; with neither flag the torch ``BCEWithLogitsLoss`` line runs as before.  ``--calibration``
+logits as the model leaves them; with neither flag the torch ``BCEWithLogitsLoss`` line runs as before.  ``--fused-head`` (needs
+``--param-dtype bfloat16``, implies ``--loss bce`` if none is given) trains through ``aecf_amd.losses.MultilabelHead`` sharing
+``classifier[3]``'s parameters: the model hands over that layer's input and no training logits exist; validation keeps using the
+logits.  ``--calibration``
 adds the pooled ECE, Brier score and NLL of the three modality plans to every epoch's row (``aecf_amd.metrics.
 multilabel_calibration``, every rank on its shard); ``--calibrate MODE`` fits a scaling on the validation logits with all
 modalities present after the last epoch (``fit_calibration``) and reports the three plans' ECE and NLL before and after it.
@@ -34,7 +38,7 @@ import torch
 import torch.distributed as dist
 
 from . import dp
-from .losses import MultilabelLoss, class_balance_weights
+from .losses import MLHEAD_WIDTHS, MultilabelHead, MultilabelLoss, class_balance_weights
 from .metrics import fit_calibration, multilabel_calibration, multilabel_metrics
 from .optim import EmaModel, FusedAdamW
 from .xray import AECFModel
@@ -172,6 +176,9 @@ def main(argv=None):
                          "(gamma- 4, margin 0.05); unknown labels (NaN or < 0) are left out.  Default: torch's BCEWithLogitsLoss")
     ap.add_argument("--pos-weight", choices=("auto",), default=None,
                     help="auto: per-class n_neg / n_pos of the training labels as pos_weight (implies --loss bce if none is given)")
+    ap.add_argument("--fused-head", action="store_true",
+                    help="train classifier[3] and the loss as one fused call on the layer's input (losses.MultilabelHead): no "
+                         "training logits exist.  Needs --param-dtype bfloat16; implies --loss bce if none is given")
     ap.add_argument("--calibration", action="store_true",
                     help="also report the pooled ECE (15 bins), Brier score and NLL of the validation logits (val_ece, val_brier, "
                          "val_nll and their _no_images / _no_texts forms), evaluated by every rank on its shard")
@@ -179,6 +186,12 @@ def main(argv=None):
                     help="after the last epoch fit this scaling on the validation logits with all modalities present and report "
                          "the three plans' ECE and NLL before and after it, and the fitted temperature")
     args = ap.parse_args(argv)
+    if args.fused_head:
+        if args.param_dtype != "bfloat16":
+            ap.error("--fused-head needs --param-dtype bfloat16 (the fused head serves bfloat16 features and weights)")
+        if args.hidden not in MLHEAD_WIDTHS:
+            ap.error(f"--fused-head needs --hidden in {MLHEAD_WIDTHS}")
+        args.loss = args.loss or "bce"
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -221,8 +234,12 @@ def main(argv=None):
         crit = MultilabelLoss(pos_weight=class_balance_weights(labels) if args.pos_weight == "auto" else None,
                               gamma_pos=gamma_pos, gamma_neg=gamma_neg, margin=margin,
                               group=dist.group.WORLD if world > 1 else None)     # the global mean over the valid labels of all ranks
+        head = None
+        if args.fused_head:                 # the same options on the layer's own parameter objects
+            head = MultilabelHead.from_linear(model.classifier[3], pos_weight=crit.pos_weight, gamma_pos=gamma_pos,
+                                              gamma_neg=gamma_neg, margin=margin, group=crit.group)
     else:
-        crit = torch.nn.BCEWithLogitsLoss()
+        crit, head = torch.nn.BCEWithLogitsLoss(), None
     n = image.shape[0]
     steps = (n + args.batch - 1) // args.batch                              # the short last batch is kept (DataLoader default)
     perm_gen = torch.Generator(device=device).manual_seed(args.seed + 3)    # same permutation on every rank
@@ -249,14 +266,20 @@ def main(argv=None):
                 da, db = model.draw_missing(b, device, generator=miss_gen)  # the GLOBAL batch's draws; this rank's rows
                 missing = (da[lo:hi], db[lo:hi])
             if hi <= lo:                                # fewer rows than ranks: this rank only joins the collective
-                if fused_loss:                          # (the loss's all-reduce first, as on the ranks that hold rows)
+                if head is not None:
+                    loss_sum += head.loss(torch.empty(0, args.hidden, dtype=params[0].dtype, device=device), labels[sel]).detach()
+                elif fused_loss:                        # (the loss's all-reduce first, as on the ranks that hold rows)
                     loss_sum += crit(torch.empty(0, args.classes, dtype=params[0].dtype, device=device), labels[sel])
                 bucket.zero()
                 bucket.all_reduce(average=True)
                 opt.step()
                 continue
-            logits, info = model(image[sel], text[sel], return_info=True, mask_uniforms=u, missing=missing)
-            loss = crit(logits, labels[sel]) if fused_loss else crit(logits.float(), labels[sel])
+            if head is not None:
+                hidden, info = model(image[sel], text[sel], return_info=True, mask_uniforms=u, missing=missing, return_hidden=True)
+                loss = head.loss(hidden, labels[sel])
+            else:
+                logits, info = model(image[sel], text[sel], return_info=True, mask_uniforms=u, missing=missing)
+                loss = crit(logits, labels[sel]) if fused_loss else crit(logits.float(), labels[sel])
             if bucket is None:
                 opt.zero_grad(set_to_none=True)
             else:

@@ -288,8 +288,9 @@ class AECFModel(nn.Module):
 
     def forward(self, image_features: torch.Tensor, text_features: torch.Tensor, return_info: bool = False, *,
                 mask_uniforms: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None,
-                missing: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
-        """``mask_uniforms`` / ``generator`` are handed to the pool's curriculum masking (``[n_both, 1, 2]``).  ``missing`` =
+                missing: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, return_hidden: bool = False):
+        """``return_hidden``: the input of ``classifier[3]`` (the features a fused head, ``losses.MultilabelHead``, takes) in
+        place of the logits, on both routings.  ``mask_uniforms`` / ``generator`` are handed to the pool's curriculum masking (``[n_both, 1, 2]``).  ``missing`` =
         (drop_a, drop_b) for this call's rows, drawn by the caller: a data-parallel trainer draws them for the GLOBAL batch from
         a shared-seed generator (``draw_missing``) and hands every rank its rows, so that which rows lose a modality does not
         depend on the number of ranks (as for the mask uniforms); without it they are drawn here."""
@@ -302,7 +303,7 @@ class AECFModel(nn.Module):
             if simulate and missing is None:
                 u = torch.rand(3, image_features.size(0), device=image_features.device, generator=generator)
             xa, xb, _, _, cls = front_pair(image_features, text_features, u, 0.3, missing if simulate else None)
-            return self._forward_static(xa, xb, cls, return_info, mask_uniforms, generator)
+            return self._forward_static(xa, xb, cls, return_info, mask_uniforms, generator, return_hidden)
         if simulate:
             if missing is not None:
                 drop_a, drop_b = missing
@@ -336,11 +337,18 @@ class AECFModel(nn.Module):
         from_a = self.image_proj(_ClassGather.apply(enc_a, route, ONLY_A)) if route.counts[ONLY_A] else enc_a.new_zeros(0, width)
         from_b = self.text_proj(_ClassGather.apply(enc_b, route, ONLY_B)) if route.counts[ONLY_B] else enc_a.new_zeros(0, width)
         fused = _BranchSelect.apply(from_both, from_a, from_b, route, width)
-        logits = self.classifier(fused)
+        logits = self._classify(fused, return_hidden)
         return (logits, info) if return_info else logits
 
+    def _classify(self, fused: torch.Tensor, return_hidden: bool) -> torch.Tensor:
+        if not return_hidden:
+            return self.classifier(fused)
+        for layer in list(self.classifier)[:3]:
+            fused = layer(fused)
+        return fused
 
-def _forward_static(self, image_features, text_features, cls, return_info, mask_uniforms, generator):
+
+def _forward_static(self, image_features, text_features, cls, return_info, mask_uniforms, generator, return_hidden=False):
     """Every row runs every branch; ``image_features`` / ``text_features`` come from ``front_pair``: an ABSENT modality's rows
     are zeros there, so its features never reach a weight (compact routing never touches them; presence = norm > 1e-6, ref
     :202-203, is False for NaN / Inf rows, and 0 * NaN = NaN would poison the batch sums of every parameter gradient)."""
@@ -351,7 +359,7 @@ def _forward_static(self, image_features, text_features, cls, return_info, mask_
     pooled, pool_info = self.attention_pool(self.fusion_query.expand(rows, -1, -1), pairs, pairs, return_info=True,
                                             uniforms=mask_uniforms, generator=generator)
     fused = _StaticSelect.apply(self.fusion_proj(pooled.squeeze(1)), self.image_proj(enc_a), self.text_proj(enc_b), cls)
-    logits = self.classifier(fused)
+    logits = self._classify(fused, return_hidden)
     if not return_info:
         return logits
     info = dict(pool_info)
@@ -481,17 +489,23 @@ class GraphedTrainStep:
 
 def train_step(model: AECFModel, optimizer: torch.optim.Optimizer, criterion: nn.Module, images: torch.Tensor,
                texts: torch.Tensor, labels: torch.Tensor, bucket: Optional[dp.FlatGradBucket] = None,
-               loss_scale: float = 1.0) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+               loss_scale: float = 1.0, head=None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """One optimisation step (ref :360-377: zero_grad, forward with info, BCE, backward, step).  Data parallel: pass the
     model's FlatGradBucket -- all gradients of all ranks are then averaged by one all-reduce before the optimizer step;
     ``loss_scale`` = ``world * b_local / B_global`` makes that average the gradient of the global-batch mean loss when
-    the shards are uneven (1.0 for even shards)."""
+    the shards are uneven (1.0 for even shards).  ``head``: a ``losses.MultilabelHead`` made by
+    ``from_linear(model.classifier[3], ...)``; the step is then hidden -> ``head.loss(hidden, labels)`` without the logits, and
+    ``criterion`` is not called."""
     if bucket is None:
         optimizer.zero_grad(set_to_none=True)
     else:
         bucket.zero()
-    logits, info = model(images, texts, return_info=True)
-    loss = criterion(logits, labels)
+    if head is not None:
+        hidden, info = model(images, texts, return_info=True, return_hidden=True)
+        loss = head.loss(hidden, labels)
+    else:
+        logits, info = model(images, texts, return_info=True)
+        loss = criterion(logits, labels)
     (loss * loss_scale if loss_scale != 1.0 else loss).backward()
     if bucket is not None:
         bucket.all_reduce(average=True)

@@ -1484,6 +1484,61 @@ int aecf_mlloss_backward(int64_t n, int32_t classes, int32_t dtype, int32_t labe
                          float label_smoothing, int32_t reduction, const double* totals, const float* grad_out, float factor,
                          void* dlogits, void* stream);
 
+/* ---- fused classifier head: the multi-label classification loss above of logits = h W^T + bias and its three gradients,
+ * without the logits (replaces classifier[3] of the reference example's model, xrays/train_xrays_example.py nn.Linear, together
+ * with the criterion; the streaming form is build-defined) ----
+ * h [n,k] and w [classes,k] (nn.Linear's layout) row-major AECF_BF16; bias float32 [classes] or NULL; labels [n,classes] of
+ * label_dtype with the label kinds and the UNKNOWN rule of aecf_mlloss_*; pos_scale / neg_scale float32 [classes] or NULL; the
+ * form parameters of aecf_mlloss_forward.  With z_ic = h_i . w_c + bias_c, l and g = dl/dz the element of aecf_mlloss_* at z:
+ *   loss = sum_ic l_ic (/ N)      dh_i = scale sum_c g_ic w_c      dW_c = scale sum_i g_ic h_i      dbias_c = scale sum_i g_ic
+ * Nothing of size n x classes is allocated, written or read besides the labels.  Both passes are one streaming loop: 64
+ * stationary rows per block in registers, the other matrix through LDS in tiles of 32 rows, S = streamed . stationary on bf16
+ * MFMAs with float32 accumulation, the element, then Out^T += streamed^T g on MFMAs again.
+ * Rounding points: z = S + bias_c is ONE rounded float32 add after the MFMA chain (bias NULL: no add) and is never rounded to
+ * bf16; the element is aecf_mlloss's float32 arithmetic; g enters both gradient products rounded ONCE to bf16 (unscaled), the
+ * products accumulate in float32; dbias sums the UNROUNDED float32 g; the scale meets the float32 sums and each output is
+ * rounded once.  An unknown target, whatever its logit, adds nothing, is not counted and has g = 0 by select.  Non-finite
+ * features are the caller's problem as in any GEMM: a NaN row of h reaches dW even when all its targets are unknown, because
+ * the product forms 0 x NaN.
+ *   forward:  the CLS role (stationary = 64 classes, streamed = rows of h, the rows split over
+ *             KSc = splits(classes, n) blocks per class block), a combine of the splits in split order and a one-block sum
+ *             over the classes.  stats float64 [2][classes] = loss sums | valid counts and totals (24 bytes) as
+ *             aecf_mlloss_forward leaves them.  A lane adds the losses of the rows it meets in float32; the four lanes of a
+ *             class, the splits and the classes are added in float64 in a fixed order; no atomics: the same bits on every
+ *             run.  want_grads = 1: also dw_unscaled float32 [classes][k] = sum_i g_ic h_i and db_unscaled float32 [classes] =
+ *             sum_i g_ic (before any scale).  want_grads = 0: the loss-only pass, without the second product: the same float
+ *             operations in the same order for the loss; dw_unscaled / db_unscaled are not touched and may be NULL.
+ *   backward: scale = grad_out[0] (float32 on the device, NULL: 1) * factor, divided by totals' N for AECF_MLLOSS_MEAN (0 where
+ *             N == 0); reads only N of totals, so a caller that sums stats over ranks hands over the global N.  dh [n][k] of
+ *             dh_dtype (AECF_BF16 or AECF_F32) by the ROW role (stationary = 64 rows of h, streamed = rows of w, the classes
+ *             split over KSr = splits(n, classes) blocks per row block; one split stores from its epilogue, more are combined
+ *             in split order); dw float32 [classes][k] = scale dw_unscaled and db float32 [classes] = scale db_unscaled by one
+ *             small launch.  Any of dh, dw, db may be NULL; with dh NULL no ROW launch happens and h, w, labels and the
+ *             workspace are not read.
+ * splits(s, m): ks = min(ceil(256 / ceil(s / 64)), ceil(m / 512), 64), at least 1; per = ceil(m / ks) rounded up to 32; the
+ * count is ceil(m / per).  Widths 768 and 1024 take their output columns from two launches per role (the scores recomputed).
+ * Workspace, every part rounded up to 256 bytes: float32 [max(KSc classes, KSr n where KSr > 1)][k] partial rows | float64
+ * [KSc][classes] loss sums | int32 [KSc][classes] valid counts | float32 [KSc][classes] g sums.  One size serves both calls; the
+ * forward's contents are not needed by the backward.
+ * Served: AECF_BF16 h and w, k in {128, 256, 384, 512, 768, 1024}, 1 <= classes <= 65536, 1 <= n < 2^31; every index into the
+ * label matrix is formed in 64-bit arithmetic.  Outside them aecf_mlhead_workspace_bytes answers 0 and the calls
+ * AECF_ERR_UNSUPPORTED.  Caller-owned buffers, a stream argument, no allocation, no synchronisation, nothing read on the host.
+ * Checks before any pointer is read: n, classes, k <= 0, want_grads outside {0, 1}, a gamma that is negative or not finite,
+ * margin or label_smoothing outside [0, 1), a reduction outside the two, a factor that is not finite (AECF_ERR_BAD_DIMS), then
+ * the limits and the dtype codes (AECF_ERR_UNSUPPORTED), then NULL pointers (AECF_ERR_NULL_POINTER), then the workspace size
+ * (AECF_ERR_WORKSPACE; the backward needs it only with dh). */
+size_t aecf_mlhead_workspace_bytes(int64_t n, int32_t classes, int32_t k);  /* 0: shape not served */
+int aecf_mlhead_forward(int64_t n, int32_t classes, int32_t k, int32_t dtype, int32_t label_dtype, const void* h, const void* w,
+                        const float* bias, const void* labels, const float* pos_scale, const float* neg_scale, float gamma_pos,
+                        float gamma_neg, float margin, float label_smoothing, int32_t reduction, int32_t want_grads, double* stats,
+                        double* totals, float* dw_unscaled, float* db_unscaled, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int aecf_mlhead_backward(int64_t n, int32_t classes, int32_t k, int32_t dtype, int32_t label_dtype, const void* h, const void* w,
+                         const float* bias, const void* labels, const float* pos_scale, const float* neg_scale, float gamma_pos,
+                         float gamma_neg, float margin, float label_smoothing, int32_t reduction, const double* totals,
+                         const float* grad_out, float factor, const float* dw_unscaled, const float* db_unscaled, int32_t dh_dtype,
+                         void* dh, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- multi-label calibration: reliability bins (ECE / MCE), Brier score and NLL of logits [n,classes] under a per-class scale
  * and bias, and the fit of that scaling by minimising the NLL (temperature scaling after Guo et al. 2017; Platt scaling per
  * class).  The reference names calibration as the property its fusion layer keeps and measures none of it; the statistics, the
