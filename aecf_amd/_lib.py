@@ -353,6 +353,14 @@ _SYMBOLS = [
     ("aecf_mlmetrics_counts", c_int, [c_int64, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     ("aecf_mlmetrics_finalize", c_int,
      [c_int64, c_int32, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # multi-label bootstrap: the stable descending order by counting, the multiplicities uint8 [n_all][Rp], the walk with one lane
+    # per replicate -> int64 [replicates][7][C]
+    ("aecf_mlboot_workspace_bytes", c_size_t, [c_int64, c_int32]),
+    ("aecf_mlboot_draw_workspace_bytes", c_size_t, [c_int64, c_int32]),
+    ("aecf_mlboot_order", c_int,
+     [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("aecf_mlboot_draw", c_int, [c_int64, c_int32, c_int64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("aecf_mlboot_walk", c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # multi-label classification loss (BCE / focal / asymmetric): per-class stats + totals, then the gradient in one pass
     ("aecf_mlloss_workspace_bytes", c_size_t, [c_int64, c_int32]),
     ("aecf_mlloss_forward", c_int,

@@ -1664,6 +1664,46 @@ int aecf_mlmetrics_finalize(int64_t n_all, int32_t classes, int64_t row_offset, 
     return launch_status();
 }
 
+// ---- multi-label bootstrap (include/aecf_hip.h, "multi-label bootstrap")
+
+size_t aecf_mlboot_workspace_bytes(int64_t n_all, int32_t classes) { return aecf_mlmetrics_workspace_bytes(n_all, classes); }
+
+size_t aecf_mlboot_draw_workspace_bytes(int64_t n_all, int32_t replicates) {
+    if (n_all <= 0 || n_all > (1ll << 24) || replicates <= 0 || replicates > MLBOOT_MAX_REPLICATES) return 0;
+    return mlboot_draw_workspace_bytes(n_all, replicates);
+}
+
+int aecf_mlboot_order(int64_t n_all, int32_t classes, int32_t dtype, const void* logits, const uint8_t* labels, const float* thresholds,
+                      int32_t* class_counts, int32_t* order, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_all <= 0 || classes <= 0) return AECF_ERR_BAD_DIMS;
+    if (!mlmetrics_supported(n_all, classes)) return AECF_ERR_UNSUPPORTED;
+    if (dtype != AECF_BF16 && dtype != AECF_F32 && dtype != AECF_F16) return AECF_ERR_UNSUPPORTED;
+    if (!logits || !labels || !thresholds || !class_counts || !order || !workspace) return AECF_ERR_NULL_POINTER;
+    if (workspace_bytes < mlmetrics_workspace_bytes(n_all, classes)) return AECF_ERR_WORKSPACE;
+    launch_mlmetrics_prepare(n_all, classes, dtype, logits, labels, class_counts, workspace, (hipStream_t)stream);
+    launch_mlboot_order(n_all, classes, thresholds, order, workspace, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_mlboot_draw(int64_t n_all, int32_t replicates, int64_t replicate0, uint64_t seed, const int32_t* counts, uint8_t* weights,
+                     int32_t* n_saturated, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_all <= 0 || replicates <= 0 || replicate0 < 0 || replicate0 > (1ll << 31) - replicates) return AECF_ERR_BAD_DIMS;
+    if (n_all > (1ll << 24) || replicates > MLBOOT_MAX_REPLICATES) return AECF_ERR_UNSUPPORTED;
+    if (!weights || !n_saturated || (!counts && !workspace)) return AECF_ERR_NULL_POINTER;
+    if (!counts && workspace_bytes < mlboot_draw_workspace_bytes(n_all, replicates)) return AECF_ERR_WORKSPACE;
+    launch_mlboot_draw(n_all, replicates, replicate0, seed, counts, weights, n_saturated, workspace, (hipStream_t)stream);
+    return launch_status();
+}
+
+int aecf_mlboot_walk(int64_t n_all, int32_t classes, int32_t replicates, const int32_t* class_counts, const int32_t* order,
+                     const uint8_t* weights, int64_t* stats, void* stream) {
+    if (n_all <= 0 || classes <= 0 || replicates <= 0) return AECF_ERR_BAD_DIMS;
+    if (!mlmetrics_supported(n_all, classes) || replicates > MLBOOT_MAX_REPLICATES) return AECF_ERR_UNSUPPORTED;
+    if (!class_counts || !order || !weights || !stats) return AECF_ERR_NULL_POINTER;
+    launch_mlboot_walk(n_all, classes, replicates, class_counts, order, weights, stats, (hipStream_t)stream);
+    return launch_status();
+}
+
 // ---- multi-label classification loss (include/aecf_hip.h, "multi-label classification loss")
 
 namespace {

@@ -528,6 +528,25 @@ void launch_mlmetrics_counts(int64_t n_all, int classes, int64_t row_offset, int
                              const void* workspace, hipStream_t s);
 void launch_mlmetrics_finalize(int64_t n_all, int classes, int64_t row_offset, int64_t rows, float threshold, const int32_t* class_counts,
                                const int32_t* counts, double* shares, const void* workspace, hipStream_t s);
+// what prepare left in the workspace, for another reader of the class-major keys (aecf_mlboot.hip)
+struct MlmPrepared {
+    const float* keys;                      // [C][Np], rows past n_all are NaN
+    const unsigned long long* posmask;      // [C][nch] ballots of the valid positives
+    int64_t Np, nch;
+};
+MlmPrepared mlmetrics_prepared(const void* workspace, int64_t n_all, int classes);
+
+// Multi-label bootstrap (aecf_mlboot.hip): the stable descending order of every class by counting (after the evaluation's prepare,
+// whose workspace it reads), the multiplicities W [n_all][Rp] uint8 of the replicates (Rp: replicates rounded up to 64) -- drawn,
+// or packed from the caller's counts -- and the walk of the order with one lane per replicate: stats int64 [replicates][7][C] =
+// Wpos | Wvalid | U2 | TP | FP | FN | the bits of the float64 S.
+constexpr int MLBOOT_MAX_REPLICATES = 4096;
+size_t mlboot_draw_workspace_bytes(int64_t n_all, int replicates);
+void launch_mlboot_order(int64_t n_all, int classes, const float* thr, int32_t* order, const void* workspace, hipStream_t s);
+void launch_mlboot_draw(int64_t n_all, int replicates, int64_t replicate0, uint64_t seed, const int32_t* counts, uint8_t* w,
+                        int32_t* n_saturated, void* workspace, hipStream_t s);
+void launch_mlboot_walk(int64_t n_all, int classes, int replicates, const int32_t* class_counts, const int32_t* order, const uint8_t* w,
+                        int64_t* stats, hipStream_t s);
 
 // Multi-label classification loss (aecf_mlloss.hip): BCE / focal / asymmetric loss of logits [n, C] as one elementwise formula.
 // forward: one pass (per-row-block float64 loss sums and int32 valid counts per class) and a fixed-order finalize (stats [2][C],

@@ -287,6 +287,11 @@ bool mlmetrics_supported(int64_t n_all, int classes) {
 
 size_t mlmetrics_workspace_bytes(int64_t n_all, int classes) { return mlm_carve(nullptr, n_all, classes).bytes; }
 
+MlmPrepared mlmetrics_prepared(const void* workspace, int64_t n_all, int classes) {
+    const MlmWs w = mlm_carve(workspace, n_all, classes);
+    return MlmPrepared{w.keys, w.posmask, w.Np, w.nch};
+}
+
 void launch_mlmetrics_prepare(int64_t n_all, int classes, int dtype, const void* logits, const uint8_t* labels, int32_t* class_counts,
                               void* workspace, hipStream_t s) {
     const MlmWs w = mlm_carve(workspace, n_all, classes);

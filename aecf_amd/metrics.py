@@ -330,3 +330,250 @@ def fit_calibration(logits: torch.Tensor, labels: torch.Tensor, mode: str = "tem
         return dict(scale=scale, bias=bias, temperature=1.0 / scale.to(torch.float64), fitted=phase != 3.0, converged=phase == 2.0,
                     nll_before=state[10, :P].clone(), nll_after=state[2, :P].clone(), n_used=sums[6].to(torch.int64),
                     n_skipped=sums[8].to(torch.int64))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Bootstrap confidence intervals of AP, AUROC and F1 (aecf_mlboot_order / _draw / _walk, include/aecf_hip.h "multi-label
+# bootstrap").  The reference's experiment is a comparison -- baseline against AECF, full against a missing modality -- on a
+# validation set where several classes hold a handful of positives; this is what says whether a difference means anything.
+# ---------------------------------------------------------------------------------------------------------------------------
+
+_BOOT_SCORES = ("ap", "auroc", "f1", "map", "macro_auroc", "macro_f1")
+_BOOT_CALL_REPLICATES = 4096        # aecf_mlboot_*: replicates of one call at most
+_BOOT_CHUNK_ELEMS = 1 << 26         # rows x replicates of one draw + walk: 256 MiB of int32 scratch, 64 MiB of weights
+
+
+def _boot_chunk(n_all: int) -> int:
+    """replicates of one draw + walk: a multiple of 64, at least 64, at most one call's, about _BOOT_CHUNK_ELEMS / n_all"""
+    return max(64, min(_BOOT_CALL_REPLICATES, _BOOT_CHUNK_ELEMS // n_all // 64 * 64))
+
+
+def _boot_thresholds(threshold, C: int, device) -> torch.Tensor:
+    """``threshold`` as float32 [C] logit thresholds: a probability inside (0, 1) for all classes, or a [C] tensor of logit
+    thresholds taken as it is"""
+    if isinstance(threshold, torch.Tensor):
+        if threshold.dim() != 1 or threshold.shape[0] != C or not threshold.dtype.is_floating_point:
+            raise ValueError(f"aecf_amd: a tensor threshold holds one floating-point logit threshold per class, [{C}], got "
+                             f"{threshold.dtype} {tuple(threshold.shape)}")
+        return threshold.detach().to(device=device, dtype=torch.float32).contiguous()
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0.0 < threshold < 1.0:
+        raise ValueError(f"aecf_amd: bootstrap_metrics needs a threshold inside (0, 1) or a [C] tensor of logit thresholds, got "
+                         f"{threshold!r}")
+    return torch.full((C,), math.log(threshold / (1.0 - threshold)), dtype=torch.float32, device=device)
+
+
+def _boot_stats(logits, labels, n_boot, threshold, seed, weights, group, want_weights):
+    """The checks, the gather and the three library passes: (stats int64 [R, 7, C] of the R = n_boot + 1 replicates, replicate 0
+    all ones; n_saturated int32 [1]; the uint8 weights [R, n_all] or None).  Each rank walks a contiguous slice of the
+    replicates and ONE all-reduce of the zero-filled int64 block joins the slices: an integer sum with zeros moves no bit."""
+    _require_device(logits, "logits")
+    _require_device(labels, "labels")
+    if logits.dim() != 2 or labels.shape != logits.shape:
+        raise ValueError(f"bootstrap_metrics expects logits and labels of one shape [n, C], got {tuple(logits.shape)} and "
+                         f"{tuple(labels.shape)}")
+    if logits.dtype not in _POOL_DTYPES:
+        raise TypeError(f"aecf_amd: bootstrap_metrics takes float32, bfloat16 or float16 logits (nothing is rounded on the way in), "
+                        f"got {logits.dtype}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"aecf_amd: bootstrap_metrics needs a seed in [0, 2**64), got {seed!r}")
+    rows, C = logits.shape
+    if C < 1:
+        raise ValueError("aecf_amd: bootstrap_metrics needs at least one class")
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] < 1:
+            raise ValueError("aecf_amd: weights are a [R, n] tensor of row multiplicities over the rows of every rank")
+        if weights.dtype not in (torch.uint8, torch.int16, torch.int32, torch.int64):
+            raise TypeError(f"aecf_amd: weights are uint8 (or int16 / int32 / int64, clipped to 0 .. 255 and counted in n_saturated), "
+                            f"got {weights.dtype}")
+        _require_device(weights, "weights")
+        n_boot = weights.shape[0]
+    if isinstance(n_boot, bool) or not isinstance(n_boot, int) or not 1 <= n_boot < (1 << 31) - 1:
+        raise ValueError(f"aecf_amd: bootstrap_metrics needs n_boot >= 1, got {n_boot!r}")
+    lib = _lib.load()
+    dev = logits.device
+    y = _labels_u8(labels.detach())
+    x = logits.detach().contiguous()
+    thr = _boot_thresholds(threshold, C, dev)
+    sizes, _, n_all = _row_ranges(rows, dev, group)
+    if n_all < 1:
+        raise ValueError("aecf_amd: bootstrap_metrics needs at least one row")
+    if weights is not None and weights.shape[1] != n_all:
+        raise ValueError(f"aecf_amd: weights hold one multiplicity per row of every rank, [R, {n_all}], got {tuple(weights.shape)}")
+    ws_bytes = lib.aecf_mlboot_workspace_bytes(n_all, C)
+    if ws_bytes == 0:
+        raise NotImplementedError(f"aecf_amd: bootstrap_metrics serves C <= 4096, n <= 2**24 and n * C <= 2**28 over all ranks, got "
+                                  f"{n_all} x {C}")
+    x_all = _all_rows(x, group, sizes).contiguous()
+    y_all = _all_rows(y, group, sizes).contiguous()
+    R = n_boot + 1
+    rank, world = dp.world_info(group)
+    lo, hi = dp.shard_bounds(R, rank, world)
+    Np = (n_all + 63) // 64 * 64
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    class_counts = torch.empty(3, C, dtype=torch.int32, device=dev)
+    order = torch.empty(C, Np, dtype=torch.int32, device=dev)
+    n_sat = torch.zeros(1, dtype=torch.int32, device=dev)
+    stats = torch.zeros(R, 7, C, dtype=torch.int64, device=dev) if world > 1 else torch.empty(R, 7, C, dtype=torch.int64, device=dev)
+    kept = torch.empty(R, n_all, dtype=torch.uint8, device=dev) if want_weights else None
+    st = _stream()
+    _lib.check(lib.aecf_mlboot_order(n_all, C, _POOL_DTYPES[x_all.dtype], _ptr(x_all), _ptr(y_all), _ptr(thr), _ptr(class_counts),
+                                     _ptr(order), _ptr(ws), ws_bytes, st), "aecf_mlboot_order")
+    chunk = _boot_chunk(n_all)
+    for r0 in range(lo, hi, chunk):
+        reps = min(chunk, hi - r0)
+        Rp = (reps + 63) // 64 * 64
+        w = torch.empty(n_all, Rp, dtype=torch.uint8, device=dev)
+        if weights is None:
+            dws_bytes = lib.aecf_mlboot_draw_workspace_bytes(n_all, reps)
+            dws = torch.empty(dws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.aecf_mlboot_draw(n_all, reps, r0, seed, None, _ptr(w), _ptr(n_sat), _ptr(dws), dws_bytes, st),
+                       "aecf_mlboot_draw")
+        else:                                   # replicate 0 stays the point estimate: ones, then the caller's rows
+            counts = torch.zeros(n_all, Rp, dtype=torch.int32, device=dev)
+            a = max(r0, 1)
+            if r0 == 0:
+                counts[:, 0] = 1
+            counts[:, a - r0:reps] = weights[a - 1:r0 + reps - 1].t()
+            _lib.check(lib.aecf_mlboot_draw(n_all, reps, r0, seed, _ptr(counts), _ptr(w), _ptr(n_sat), None, 0, st),
+                       "aecf_mlboot_draw")
+        _lib.check(lib.aecf_mlboot_walk(n_all, C, reps, _ptr(class_counts), _ptr(order), _ptr(w), _ptr(stats[r0:r0 + reps]), st),
+                   "aecf_mlboot_walk")
+        if kept is not None:
+            kept[r0:r0 + reps] = w[:, :reps].t()
+    if world > 1:
+        torch.distributed.all_reduce(stats, group=group)
+        torch.distributed.all_reduce(n_sat, group=group)
+        if kept is not None:
+            kept[:lo].zero_()
+            kept[hi:].zero_()
+            torch.distributed.all_reduce(kept, group=group)
+    return stats, n_sat, kept
+
+
+def _close_replicates(stats: torch.Tensor) -> dict:
+    """``_close``'s rules for every replicate at once, from stats int64 [R, 7, C] = Wpos | Wvalid | U2 | TP | FP | FN | S bits:
+    ap / auroc / f1 float64 [R, C] and map / macro_auroc / macro_f1 [R].  AP 0 without positive weight; AUROC NaN without positive
+    or without negative weight; F1 0 without a true positive; mAP over the classes with positive weight IN THAT REPLICATE;
+    macro AUROC over the defined ones; macro F1 over F1 > 0.  float64, selects in place of divisions by zero, no host read.
+    (The integers convert exactly below 2**53: U2 and 2 Wpos Wneg pass it only beyond about 6e7 weighted pairs.)"""
+    f64 = torch.float64
+    dev = stats.device
+    wpos, wvalid, u2, tp, fp, fn = (stats[:, k].to(f64) for k in range(6))
+    s = stats[:, 6].contiguous().view(f64)
+    wneg = wvalid - wpos
+    zero, one = torch.zeros((), dtype=f64, device=dev), torch.ones((), dtype=f64, device=dev)
+    nan = torch.full((), float("nan"), dtype=f64, device=dev)
+    has_pos = wpos > 0
+    both = has_pos & (wneg > 0)
+    ap = torch.where(has_pos, s / torch.where(has_pos, wpos, one), zero)
+    auroc = torch.where(both, u2 / torch.where(both, 2.0 * wpos * wneg, one), nan)
+    scored = has_pos & (tp > 0)
+    f1 = torch.where(scored, 2.0 * tp / torch.where(scored, 2.0 * tp + fp + fn, one), zero)
+
+    def mean_over(values, keep, empty):
+        k = keep.sum(1)
+        m = torch.where(keep, values, zero).sum(1) / torch.where(k > 0, k, torch.ones_like(k)).to(f64)
+        return torch.where(k > 0, m, torch.full((), empty, dtype=f64, device=dev))
+
+    return dict(ap=ap, auroc=auroc, f1=f1, map=mean_over(ap, has_pos, 0.0), macro_auroc=mean_over(auroc, both, float("nan")),
+                macro_f1=mean_over(f1, f1 > 0, 0.0))
+
+
+def _boot_summary(values: torch.Tensor, confidence: float) -> dict:
+    """point | ci | se | n_defined of replicate values [R, ...] (replicate 0: the point estimate).  Percentile interval over the
+    replicates 1 .. R - 1 that are not NaN, ``torch.nanquantile(..., interpolation="linear")`` in float64; the standard error is
+    their standard deviation (n - 1 in the divisor; NaN below two defined replicates)."""
+    reps = values[1:]
+    alpha = (1.0 - confidence) / 2.0
+    ci = torch.stack([torch.nanquantile(reps, q, dim=0, interpolation="linear") for q in (alpha, 1.0 - alpha)])
+    defined = ~torch.isnan(reps)
+    n = defined.sum(0)
+    nf = n.to(torch.float64)
+    filled = torch.where(defined, reps, torch.zeros((), dtype=reps.dtype, device=reps.device))
+    mean = filled.sum(0) / torch.clamp(nf, min=1.0)
+    dev2 = torch.where(defined, (reps - mean) ** 2, torch.zeros((), dtype=reps.dtype, device=reps.device)).sum(0)
+    se = torch.where(n > 1, (dev2 / torch.clamp(nf - 1.0, min=1.0)).sqrt(), torch.full((), float("nan"), dtype=reps.dtype, device=reps.device))
+    return dict(point=values[0], ci=ci, se=se, n_defined=n)
+
+
+def _check_confidence(confidence) -> None:
+    if isinstance(confidence, bool) or not isinstance(confidence, (int, float)) or not 0.0 < confidence < 1.0:
+        raise ValueError(f"aecf_amd: a confidence level lies inside (0, 1), got {confidence!r}")
+
+
+def bootstrap_metrics(logits: torch.Tensor, labels: torch.Tensor, n_boot: int = 1000, confidence: float = 0.95, threshold=0.5,
+                      seed: int = 0, weights: Optional[torch.Tensor] = None, group=None, return_replicates: bool = False,
+                      return_weights: bool = False) -> dict:
+    """``multilabel_metrics`` with percentile-bootstrap confidence intervals: ``n_boot`` resamples of the ROWS (a row carries all
+    its classes, so the macro scores see the joint resample) of ``logits`` / ``labels`` [n, C] (``multilabel_metrics``' dtypes
+    and label kinds), global over the rows of every rank of ``group``.  ``threshold``: a probability inside (0, 1), or a float
+    [C] tensor of LOGIT thresholds, one per class.  Replicate r >= 1 is the classical multinomial bootstrap -- n draws with
+    replacement, from Philox keyed by ``seed`` -- and depends on (seed, r, n) only; ``weights``, uint8 [R, n] row multiplicities
+    (or a wider integer type, clipped to 0 .. 255 and counted in ``n_saturated``), replace the draw, and ``n_boot`` is then R.
+
+    The classes are ranked once, by counting, and that one order is walked once for all replicates with one lane per replicate
+    (include/aecf_hip.h, "multi-label bootstrap").  Up to the final quotients the arithmetic is integer: a replicate's scores are
+    those of ``multilabel_metrics`` on the rows physically repeated by their multiplicities (AP to the rounding of its float64
+    sum), whatever the tiles, blocks or ranks.
+
+    Returns a dict of device tensors, the same on every rank.  For each of ``ap``, ``auroc``, ``f1`` (float64 [C]) and ``map``,
+    ``macro_auroc``, ``macro_f1`` (0-dim): the point value under its name (replicate 0, all weights one: ``multilabel_metrics``'
+    value), ``<name>_ci`` [2, ...] the lower and upper percentile limits at ``confidence`` over the replicates that are not NaN,
+    ``<name>_se`` their standard deviation; ``n_defined``: a dict name -> int64 count of those replicates (an AUROC is NaN in a
+    replicate that drew no positive or no negative of the class; per replicate mAP runs over the classes with a drawn
+    positive, macro F1 over F1 > 0, ``_close``'s rules); ``n_saturated`` int64 0-dim.  ``return_replicates``: ``replicates``, a
+    dict name -> float64 [n_boot + 1, C] / [n_boot + 1] with replicate 0 first; ``return_weights``: ``weights`` uint8
+    [n_boot + 1, n], row 0 all ones.
+
+    One rank reads nothing on the host: the call captures into a graph and a replay follows logits and labels changed in place.
+    Data parallel: the rows are gathered as ``multilabel_metrics`` gathers them, every rank walks a contiguous slice of the
+    replicates, and one all-reduce joins the int64 [n_boot + 1, 7, C] block -- the bits of the one-rank call.  More than about
+    2**26 / n replicates are processed in chunks inside the call."""
+    _check_confidence(confidence)
+    with torch.no_grad():
+        stats, n_sat, kept = _boot_stats(logits, labels, n_boot, threshold, seed, weights, group, return_weights)
+        reps = _close_replicates(stats)
+        out = dict(n_defined={}, n_saturated=n_sat[0].to(torch.int64))
+        for name in _BOOT_SCORES:
+            s = _boot_summary(reps[name], confidence)
+            out[name], out[name + "_ci"], out[name + "_se"] = s["point"], s["ci"], s["se"]
+            out["n_defined"][name] = s["n_defined"]
+        if return_replicates:
+            out["replicates"] = reps
+        if return_weights:
+            out["weights"] = kept
+        return out
+
+
+def bootstrap_compare(logits_a: torch.Tensor, logits_b: torch.Tensor, labels: torch.Tensor, n_boot: int = 1000,
+                      confidence: float = 0.95, threshold=0.5, seed: int = 0, weights: Optional[torch.Tensor] = None, group=None,
+                      return_replicates: bool = False) -> dict:
+    """The PAIRED bootstrap of two models on the same rows: both are walked under the SAME resamples (the same ``seed``, or the
+    same ``weights``), and every score's difference a - b is formed per replicate -- the reference's baseline-against-AECF and
+    full-against-missing-modality question.  For each of ``ap``, ``auroc``, ``f1``, ``map``, ``macro_auroc``, ``macro_f1``:
+    ``<name>`` the point difference, ``<name>_ci`` [2, ...] its percentile interval, ``<name>_se``, and ``<name>_p_le0`` /
+    ``<name>_p_ge0``: the fractions of the defined replicates (neither side NaN) with a difference <= 0 and >= 0 (NaN without a
+    defined replicate); ``n_defined`` as in ``bootstrap_metrics``; ``a`` and ``b``: the two ``bootstrap_metrics`` results."""
+    _check_confidence(confidence)
+    with torch.no_grad():
+        kw = dict(n_boot=n_boot, confidence=confidence, threshold=threshold, seed=seed, weights=weights, group=group,
+                  return_replicates=True)
+        a = bootstrap_metrics(logits_a, labels, **kw)
+        b = bootstrap_metrics(logits_b, labels, **kw)
+        out = dict(n_defined={}, a=a, b=b)
+        diffs = {}
+        for name in _BOOT_SCORES:
+            d = a["replicates"][name] - b["replicates"][name]            # NaN where either side is
+            diffs[name] = d
+            s = _boot_summary(d, confidence)
+            out[name], out[name + "_ci"], out[name + "_se"] = s["point"], s["ci"], s["se"]
+            out["n_defined"][name] = s["n_defined"]
+            n = s["n_defined"].to(torch.float64)
+            nan = torch.full((), float("nan"), dtype=torch.float64, device=d.device)
+            for key, hit in (("_p_le0", d[1:] <= 0), ("_p_ge0", d[1:] >= 0)):
+                out[name + key] = torch.where(n > 0, hit.sum(0).to(torch.float64) / torch.clamp(n, min=1.0), nan)
+        if return_replicates:
+            out["replicates"] = diffs
+        else:
+            del a["replicates"], b["replicates"]
+        return out

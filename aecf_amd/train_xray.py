@@ -11,6 +11,7 @@ of ``train_both_models`` / ``main`` in ``xrays/train_xrays_example.py:312-427, 7
     python -m aecf_amd.train_xray --loss asymmetric --pos-weight auto               # the library's multi-label loss, class balance
     python -m aecf_amd.train_xray --calibration --calibrate temperature             # + ECE, Brier, NLL; a temperature fit at the end
     python -m aecf_amd.train_xray --param-dtype bfloat16 --fused-head               # classifier[3] + loss in one call, no logits
+    python -m aecf_amd.train_xray --bootstrap 1000                                  # + 95 % intervals and paired differences at the end
 
 The reference trains on precomputed CLIP features of a chest X-ray set that is not part of its repository
 (``.MISSING_LARGE_BLOBS``); ``--data train.pt,val.pt`` loads such files (dicts with image / text / labels), otherwise a
@@ -39,7 +40,7 @@ import torch.distributed as dist
 
 from . import dp
 from .losses import MLHEAD_WIDTHS, MultilabelHead, MultilabelLoss, class_balance_weights
-from .metrics import fit_calibration, multilabel_calibration, multilabel_metrics
+from .metrics import bootstrap_compare, fit_calibration, multilabel_calibration, multilabel_metrics
 from .optim import EmaModel, FusedAdamW
 from .xray import AECFModel
 
@@ -147,6 +148,32 @@ def _calibration_rows(prefix: str, model: AECFModel, image, text, labels, rank: 
     return row
 
 
+BOOT_SCORES = (("map", "map"), ("macro_auroc", "auroc"), ("macro_f1", "macro_f1"))      # bootstrap_metrics' name, the row's
+
+
+def _bootstrap_row(model: AECFModel, image, text, labels, rank: int, world: int, n_boot: int, seed: int) -> dict:
+    """Point value and 95 % interval of mAP, macro AUROC and macro F1 for the three modality plans, and the PAIRED differences
+    full - no_images and full - no_texts (aecf_amd.metrics.bootstrap_compare: the same resampled rows on both sides) with
+    the share of resamples at or below zero.  A collective: every rank scores its shard."""
+    group = dist.group.WORLD if world > 1 else None
+    logits = {}
+    for drop, _ in PLANS:
+        logits[drop], y = shard_logits(model, image, text, labels, drop, rank, world)
+    row = dict(bootstrap=n_boot, bootstrap_seed=seed)
+    val = lambda t: float(t) if rank == 0 else None
+    for drop, suffix in PLANS[1:]:
+        cmp = bootstrap_compare(logits["none"], logits[drop], y, n_boot=n_boot, seed=seed, group=group)
+        for (name, short), (side, sfx) in ((s, p) for s in BOOT_SCORES for p in (("a", ""), ("b", suffix))):
+            m = cmp[side]
+            row[f"val_{short}{sfx}"] = val(m[name])
+            row[f"val_{short}{sfx}_ci"] = [val(m[name + "_ci"][0]), val(m[name + "_ci"][1])]
+        for name, short in BOOT_SCORES:
+            row[f"val_{short}_minus{suffix}"] = val(cmp[name])
+            row[f"val_{short}_minus{suffix}_ci"] = [val(cmp[name + "_ci"][0]), val(cmp[name + "_ci"][1])]
+            row[f"val_{short}_minus{suffix}_p_le0"] = val(cmp[name + "_p_le0"])
+    return row
+
+
 LOSS_FORMS = {"bce": (0.0, 0.0, 0.0), "focal": (2.0, 2.0, 0.0), "asymmetric": (0.0, 4.0, 0.05)}     # gamma+, gamma-, margin
 
 
@@ -185,7 +212,14 @@ def main(argv=None):
     ap.add_argument("--calibrate", choices=("temperature", "class_temperature", "platt"), default=None,
                     help="after the last epoch fit this scaling on the validation logits with all modalities present and report "
                          "the three plans' ECE and NLL before and after it, and the fitted temperature")
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="R",
+                    help="after the last epoch report 95 %% percentile-bootstrap intervals (R resamples of the validation rows) of "
+                         "mAP, macro AUROC and macro F1 for the three modality plans, and the paired differences full - no_images "
+                         "and full - no_texts with their intervals; evaluated by every rank on its shard")
+    ap.add_argument("--bootstrap-seed", type=int, default=0, help="seed of the resamples (the same rows for every plan)")
     args = ap.parse_args(argv)
+    if args.bootstrap < 0:
+        ap.error("--bootstrap takes a number of resamples >= 1 (0: off)")
     if args.fused_head:
         if args.param_dtype != "bfloat16":
             ap.error("--fused-head needs --param-dtype bfloat16 (the fused head serves bfloat16 features and weights)")
@@ -336,6 +370,11 @@ def main(argv=None):
             print(json.dumps(row), flush=True)
             if args.calibrate == "temperature":
                 print(f"fitted temperature T = {row['temperature'][0]:.6f}", flush=True)
+        history.append(row)
+    if args.bootstrap:                                                      # collective: every rank scores its shard
+        row = _bootstrap_row(model, v_image, v_text, v_labels, rank, world, args.bootstrap, args.bootstrap_seed)
+        if rank == 0:
+            print(json.dumps(row), flush=True)
         history.append(row)
     if rank == 0 and args.save:
         torch.save({"aecf_state_dict": model.state_dict(), "history": history}, args.save)

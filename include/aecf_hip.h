@@ -1437,6 +1437,58 @@ int aecf_mlmetrics_finalize(int64_t n_all, int32_t classes, int64_t row_offset, 
                             const int32_t* class_counts, const int32_t* counts, double* shares, const void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---- multi-label bootstrap: R resamples of the ROWS walked along one order per class, for confidence intervals of average
+ * precision, AUROC and F1 (the reference's example compares point estimates only, xrays/train_xrays_example.py:260-295; the
+ * resampling, the order by counting and the walk are build-defined) ----
+ * A resample of rows is a vector of integer multiplicities w_j (a row carries all its classes, so macro scores see the joint
+ * resample).  The descending order of a class's scores does not depend on it, and weighted AP, AUROC and the confusion counts
+ * are running sums along that order.  Inputs as "multi-label evaluation": logits [n_all,classes], labels uint8, a NaN logit is
+ * an invalid entry of its class and gets no slot.
+ *   order:  runs the evaluation's prepare (workspace and class_counts int32 [3][classes] = npos | nvalid | ninvalid as there), then
+ *           writes order int32 [classes][Np] (Np: n_all rounded up to 64): for a valid row r of class c, with img the integer
+ *           order image of the evaluation, slot = #{k : img_k > img_r} + #{k < r : img_k == img_r} -- the STABLE DESCENDING
+ *           order, a bijection of the valid rows onto [0, nvalid) -- and order[c][slot] = r | head << 31 | pos << 30 | pred << 29:
+ *           head = no equal key before r (the first of its tie group), pos = the label, pred = logit > thresholds[c]
+ *           (thresholds: float32 [classes] on the device, logit thresholds; a NaN threshold predicts every valid entry
+ *           positive).  Slots nvalid .. Np - 1 are not written.  Every slot is written exactly once; no atomics.
+ *   draw:   weights uint8 [n_all][Rp] (Rp: replicates rounded up to 64; row-major by data row, replicates contiguous) for the
+ *           replicates replicate0 .. replicate0 + replicates - 1; columns past `replicates` are 0.  counts == NULL: global
+ *           replicate 0 is all ones (the point estimate); replicate r >= 1 is the multinomial bootstrap, n_all draws: draw t
+ *           takes philox4x32_10 (Salmon et al. 2011; 10 rounds, multipliers 0xD2511F53 / 0xCD9E8D57, key increments
+ *           0x9E3779B9 / 0xBB67AE85) with key (seed lo, seed hi) and counter (t >> 1 lo, t >> 1 hi, r, 0x626f6f74); its 64-bit
+ *           value is c[2 (t & 1) + 1] << 32 | c[2 (t & 1)], its row the high 64 bits of value * n_all; weights[j][r - replicate0]
+ *           is the number of draws that hit j.  A replicate depends on (seed, r, n_all) only.  The hits are counted with int32
+ *           integer atomics in the workspace (zeroed by the call); integer adds commute, so the bits are the same on every run.
+ *           counts != NULL: int32 [n_all][Rp] multiplicities of the caller (nothing is drawn, no replicate is forced to ones, the
+ *           workspace is not used and may be NULL).  Either way a count outside 0 .. 255 is clipped to that range and the number
+ *           of clipped entries is ADDED to *n_saturated (int32 on the device; the caller zeroes it).
+ *   walk:   stats int64 [replicates][7][classes] = Wpos | Wvalid | U2 | TP | FP | FN | S, the last as the bits of a float64.
+ *           Along the order of class c, with w the replicate's weights, per tie group g (gall = sum w, gpos = sum w pos over
+ *           the group; cum_pos, cum_all: the same sums over the groups before it):
+ *             S  += gpos > 0 ? (double)gpos * ((double)(cum_pos + gpos) / (double)(cum_all + gall)) : 0     in slot order
+ *             U2 += (gall - gpos) * (2 cum_pos + gpos)                                          (uint64, <= 2 Wpos Wneg <= 2^63)
+ *           and TP / FP / FN the weighted counts of pos and pred.  From them AP = S / Wpos (sklearn's step-wise average
+ *           precision with sample_weight), AUROC = U2 / (2 Wpos (Wvalid - Wpos)) (half credit for ties), F1 = 2 TP / (2 TP + FP
+ *           + FN).  Everything but S is an integer; S is one float64 quotient, product and sum per group that holds a positive
+ *           weight, in slot order, by one lane: the statistics of a replicate depend on nothing but the inputs and its weights.
+ *           One wave per (64 replicates, class); the wave takes n_all steps.
+ * Workspace: order's is the evaluation's (aecf_mlboot_workspace_bytes = aecf_mlmetrics_workspace_bytes); draw's is int32
+ * [n_all][Rp], rounded up to 256 bytes (aecf_mlboot_draw_workspace_bytes).  Served: the evaluation's limits, 1 <= replicates <=
+ * 4096 per call, replicate0 + replicates <= 2^31; outside them the size queries answer 0 and the calls AECF_ERR_UNSUPPORTED.
+ * Buffers are 16-byte aligned, caller-owned; a stream argument, no allocation, no synchronisation, nothing read on the host.
+ * Checks before any launch and before any pointer is read: sizes -- n_all, classes, replicates <= 0, replicate0 < 0 or beyond
+ * 2^31 - replicates -- (AECF_ERR_BAD_DIMS), then the limits and the dtype (AECF_ERR_UNSUPPORTED), then NULL pointers
+ * (AECF_ERR_NULL_POINTER), then the workspace size (AECF_ERR_WORKSPACE). */
+size_t aecf_mlboot_workspace_bytes(int64_t n_all, int32_t classes);                 /* 0: shape not served */
+size_t aecf_mlboot_draw_workspace_bytes(int64_t n_all, int32_t replicates);         /* 0: not served */
+int aecf_mlboot_order(int64_t n_all, int32_t classes, int32_t dtype, const void* logits, const uint8_t* labels,
+                      const float* thresholds, int32_t* class_counts, int32_t* order, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int aecf_mlboot_draw(int64_t n_all, int32_t replicates, int64_t replicate0, uint64_t seed, const int32_t* counts, uint8_t* weights,
+                     int32_t* n_saturated, void* workspace, size_t workspace_bytes, void* stream);
+int aecf_mlboot_walk(int64_t n_all, int32_t classes, int32_t replicates, const int32_t* class_counts, const int32_t* order,
+                     const uint8_t* weights, int64_t* stats, void* stream);
+
 /* ---- multi-label classification loss: binary cross-entropy, focal and asymmetric loss as one elementwise formula (replaces the
  * reference example's torch criterion, xrays/train_xrays_example.py:327 nn.BCEWithLogitsLoss(), applied at :366 and :374; the
  * weights, the focusing exponents, the margin, the smoothing and the unknown labels are build-defined) ----
